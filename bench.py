@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the `--com disco` hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One STEP = one pass of the hot path over one batch of synthetic scenes already
@@ -15,15 +15,24 @@ collective on the data path -> "scaling": "weak".
 
 Steps are replayed from one captured hipGraph on ONE stream, strictly one at a
 time (--in-flight 1, the default; DESIGN.md 3.6 explains why nothing runs side
-by side).  The run checks that a graph replay equals the eager step bit for bit
-(`graph_equals_eager`).  --task seg measures BASELINE configs[3], --mode agent
-configs[4].
+by side).  With --full the run checks that a graph replay equals the eager
+step bit for bit (`graph_equals_eager`).  --task seg measures BASELINE
+configs[3], --mode agent configs[4].
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-`roofline` (dominant kernel = the split-f16 MFMA implicit-GEMM conv on
-split-planar activations, HIP-event timed per launch on the launch stream, and
-the committed rocprofv3 figure beside it) and `cpu_baseline` (the CPU oracle,
-i.e. a port: the reference itself is not in the mount; batch 1 and batch 4).
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run
+does only what the headline needs: set up, warm up, time the K steps, print the
+line.  --full adds every other measurement and check: `repeat`, `roofline`
+(dominant kernel = the split-f16 MFMA implicit-GEMM conv on split-planar
+activations, HIP-event timed per launch on the launch stream, and the committed
+rocprofv3 figure beside it), `graph_equals_eager`, `alt_math`,
+`agent_sharded*`, `voxelize`, `cpu_baseline` (the CPU oracle, a port of the
+upstream model; batch 1 and batch 4) and `train_step`.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy
+(float32, float64 where the output is; an output of more than DUMP_MAX_ELEMS
+values as a fixed, seeded sample of them).  Inputs and weights are seeded: the
+same arguments give the same inputs on every run, so two builds of the project
+can be compared output for output.
 """
 import argparse
 import json
@@ -58,12 +67,46 @@ def _sp_bevs(ops, indices, offsets, n_img, dims):
     return ops.scatter_dense_bits(indices, offsets, n_img, dims)
 
 
+DUMP_MAX_ELEMS = 1 << 22        # 16 MiB of float32 per output; no path returns more than three -> under 64 MB in all
+
+
+def dump_sample_index(numel):
+    """The flat indices --dump-outputs keeps of an output of `numel` values (None: all of them)."""
+    if numel <= DUMP_MAX_ELEMS:
+        return None
+    g = torch.Generator().manual_seed(0)
+    return torch.randint(0, numel, (DUMP_MAX_ELEMS,), generator=g).unique()
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float64 if the tensor is, else float32.  An output of more
+    than DUMP_MAX_ELEMS values is written as its values at a fixed set of flat indices (DUMP_MAX_ELEMS draws from a
+    generator seeded with 0, deduplicated, ascending): the same indices for the same shape on every run.  Called after
+    the timed region."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        t = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        idx = dump_sample_index(t.numel())
+        arr = (t.cpu() if idx is None else t.reshape(-1)[idx.to(t.device)].cpu()).numpy()
+        total += arr.nbytes
+        assert total <= 64 * 2 ** 20, "--dump-outputs: more than 64 MiB"
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements and checks (repeat, roofline, graph_equals_eager, alt_math, "
+                         "agent_sharded, voxelize, cpu_baseline, train_step); the --no-* options below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most %d values each: "
+                         "a fixed, seeded sample of a larger output)" % DUMP_MAX_ELEMS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pre-roll", type=int, default=60,
                     help="untimed replays after the W warm-up steps and before the timed region (clock settling)")
@@ -222,7 +265,7 @@ def cpu_baseline_bounded(state_dict, threads, timeout_s):
                 "sample": "1 scene (5 agents, 256x256x13)", "error": type(e).__name__}, None
 
 
-def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0):
+def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0, dump_dir=None):
     """BASELINE configs[4] (the north star's multi-GPU split): 8-agent scenes, the agents sharded across the
     ranks, ONE RCCL all-gather of the layer-3 maps per step as the V2X exchange, everything else rank-local.
     Fixed work (--agent-batch, default 4, 8-agent scenes) for every N -> strong scaling.  One step = dense rebuild of this
@@ -234,6 +277,7 @@ def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0):
     T(share): an upper bound for the W-GPU curve (no link latency, no rank skew).
     check_steps: replay that many steps and compare a checksum of every step's outputs with the first one's
     (the collective's kernel runs between our two graphs; outputs must stay bit-identical).
+    dump_dir: rank 0 writes the last timed step's cls, loc and fused map there (dump_outputs).  phases_us: --full only.
     Returns the result dict on rank 0, None elsewhere.  Needs an initialised process group unless emulating."""
     from disconet_amd import Config, DiscoNet, ops, sharded
     from disconet_amd.synthetic import make_sparse_scene_batch, make_trans_matrices, randomize_bn_stats
@@ -275,13 +319,15 @@ def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0):
             dist.barrier()
             torch.cuda.synchronize()
 
+    last = {}
+
     def time_steps(stepper, steps, warmup):
         for _ in range(warmup):
             stepper()
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
-            stepper()
+            last["out"] = stepper()
         fence()
         dt = time.perf_counter() - t0
         if dist.is_initialized():
@@ -305,9 +351,15 @@ def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0):
     first, count = sharded.agent_range(agents, world, rank)
     stepper = sharded.GraphedAgentStep(engine, rank_inputs(first, count), trans, na, batch, first, count, range_guard=False)
     elapsed = time_steps(stepper, args.steps, args.warmup)
+    if dump_dir and rank == 0:
+        res_last, fused_last = last["out"]
+        dump_outputs({"cls": res_last["cls"], "loc": res_last["loc"],
+                      "fused": fused_last.nhwc() if isinstance(fused_last, ops.SpTensor) else fused_last}, dump_dir)
     # per-phase times on EVERY rank (the exchange is a collective: all ranks must call it the same number of times)
-    phases = {"graph_a_encode": phase_us(stepper.graph_a), "allgather": phase_us(stepper.exchange),
-              "graph_b_fuse_decode_heads": phase_us(stepper.graph_b)}
+    phases = None
+    if args.full:
+        phases = {"graph_a_encode": phase_us(stepper.graph_a), "allgather": phase_us(stepper.exchange),
+                  "graph_b_fuse_decode_heads": phase_us(stepper.graph_b)}
     fence()
     res = None
     if rank == 0:
@@ -323,7 +375,7 @@ def agent_sharded_leg(args, world, rank, dist, emulate_world=0, check_steps=0):
                        "agents": agents, "batch": batch, "conv_math": args.math,
                        "launch": "hipGraph A (rebuild + encoder) -> all-gather -> hipGraph B (fusion + decoder + heads)",
                        "parallelism": "agent-parallel x%d" % world},
-            "phases_us": phases,
+            **({"phases_us": phases} if phases is not None else {}),
             "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 0,
             "collective_backend": str(dist.get_backend()) if dist.is_initialized() else "none",
             "exchanged_bytes_per_rank_per_step": int(stepper.feat_all.numel() * stepper.feat_all.element_size()
@@ -420,7 +472,8 @@ def agent_sharded_bench(args, world, rank, dist):
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29517", rank=0, world_size=1,
                                 device_id=torch.device("cuda", torch.cuda.current_device()),
                                 timeout=datetime.timedelta(seconds=120))
-    res = agent_sharded_leg(args, world, rank, dist, emulate_world=args.emulate_world, check_steps=args.agent_check)
+    res = agent_sharded_leg(args, world, rank, dist, emulate_world=args.emulate_world, check_steps=args.agent_check,
+                            dump_dir=args.dump_outputs)
     if rank == 0:
         emit(res)
     if dist.is_initialized():
@@ -507,6 +560,8 @@ def seg_bench(args, world, rank, dist, use_pg):
         elapsed = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs({"loss": loss, "logits": logits}, args.dump_outputs)
     result = {
         "metric": "scenes/sec (5-agent 256x256 BEV, seg)", "value": round(world * BATCH * args.steps / elapsed, 3),
         "unit": "scenes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -522,7 +577,7 @@ def seg_bench(args, world, rank, dist, use_pg):
                    "launch": "hipGraph replay" if graphed is not None else "eager",
                    "parallelism": "scene-parallel x%d (no data-path collective)" % world},
         "loss": round(float(loss), 6)}
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         timer = KernelTimer()
         torch.cuda.synchronize()
         with timing(timer):
@@ -553,7 +608,7 @@ def seg_bench(args, world, rank, dist, use_pg):
                 print("[seg] %-12s %8.4f ms/step %9.2f TFLOP/s" % (
                     k, v["ms_total"] / args.steps, v["flops"] / (v["ms_total"] * 1e-3) / 1e12 if v["ms_total"] else 0),
                     file=sys.stderr)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU oracle of the same model on ONE scene (bounded sample), all usable cores
         from oracle.seg_ref import SegDiscoNetRef, seg_loss
         from disconet_amd.synthetic import make_scene_batch
@@ -576,7 +631,7 @@ def seg_bench(args, world, rank, dist, use_pg):
             "sample": "1 scene (5 agents, 256x256x13), eval fwd, fp32, best of 2 after 1 warm-up; torch-CPU "
                       "oracle (reference source not in the mount)",
             "parity_max_abs_err": float((got.cpu() - want).abs().max())}
-    if world == 1 and args.train_steps > 0:
+    if args.full and world == 1 and args.train_steps > 0:
         # SegModule.step on the same batch (train() mode: batch statistics, cross entropy, explicit HIP reverse
         # pass through the UNet and the fusion, Adam) -- reported beside the headline value, never in it
         try:
@@ -758,7 +813,7 @@ def main(argv=None):
     intra_overlap = os.environ.get("DISCONET_OVERLAP", "0") == "1" and os.environ.get("DISCONET_UNSAFE_OVERLAP", "0") == "1"
     model.overlap_streams = args.in_flight > 1 or intra_overlap        # concurrency features together, guarded below
     model.eval().cuda()
-    state_dict_cpu = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    state_dict_cpu = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.full else None
 
     # synthetic scenes, resident in HBM before the timed region
     indices, offsets, _ = make_sparse_scene_batch(BATCH, AGENTS, MAP_HW)
@@ -821,6 +876,7 @@ def main(argv=None):
         return out["cls"].view(torch.int64).sum() + 3 * out["loc"].view(torch.int64).sum()
 
     checks = None
+    last = {}
 
     def timed(events, depth=None):
         nonlocal checks
@@ -839,7 +895,7 @@ def main(argv=None):
                     step()
         else:
             for i in range(args.steps):
-                run_step(i, depth)
+                last["out"] = run_step(i, depth)
         fence() if not events else torch.cuda.synchronize()
         return time.perf_counter() - t0, timer
 
@@ -929,9 +985,11 @@ def main(argv=None):
         run_step(i)
     elapsed, _ = timed(False)                      # timed region #1 -> value
     replay_checks = checks
+    if args.dump_outputs and rank == 0:
+        dump_outputs({k: last["out"][k] for k in ("cls", "loc")}, args.dump_outputs)
     # lease noise made visible inside one line: the same K steps, five more times (never part of `value`)
     repeats = None
-    if args.in_flight == 1 and args.steps > 0:
+    if args.full and args.in_flight == 1 and args.steps > 0:
         reps = sorted(timed(False)[0] for _ in range(5))
         per = [round(BATCH * world * args.steps / r, 1) for r in reps[::-1]]       # scenes/s, ascending
         repeats = {"runs": 5, "steps_each": args.steps, "scenes_per_s": {"min": per[0], "median": per[2], "max": per[4]},
@@ -941,7 +999,7 @@ def main(argv=None):
                            "box-to-box spread is larger (profiles/)"}
     elapsed_serial = timed(False, depth=1)[0] if (args.in_flight > 1 and not args.no_graph) else None
     timer, elapsed_events = None, 0.0
-    if rank == 0 and not args.no_kernel_events:
+    if args.full and rank == 0 and not args.no_kernel_events:
         elapsed_events, timer = timed(True)        # timed region #2 -> roofline
     # every rank checks that EVERY replay it had in flight wrote the same bits as the serial replay
     outputs_same, replays_differing = None, None
@@ -953,7 +1011,7 @@ def main(argv=None):
         outputs_same = replays_differing == 0
     # the captured graph must reproduce the eager step bit for bit (profiles/r02_hazard_repro.txt part A)
     graph_ok = None
-    if graphed.get(model.conv_math):
+    if args.full and graphed.get(model.conv_math):
         eager = step()
         eager = {k: eager[k].clone() for k in ("cls", "loc")}
         replay = graphed[model.conv_math][0][0]()
@@ -975,7 +1033,7 @@ def main(argv=None):
     # the north star's multi-GPU split rides in the same line: BASELINE configs[4], agents sharded across the ranks,
     # one RCCL all-gather per step (every rank runs it; at N = 1 with rank 0's share of an 8-rank run emulated)
     agent_res = agent_res16 = None
-    if not args.no_agent_leg and args.math == "sp" and 8 % world == 0 and args.in_flight == 1:
+    if args.full and not args.no_agent_leg and args.math == "sp" and 8 % world == 0 and args.in_flight == 1:
         try:
             agent_res = agent_sharded_leg(args, world, rank, dist, emulate_world=8 if world == 1 else 0)
         except Exception as e:      # never lose the headline line to the extra leg
@@ -1061,7 +1119,7 @@ def main(argv=None):
                 result["agent_sharded_batch16"] = agent_res16
         if timer is not None:
             result["roofline"] = roofline_of(timer, elapsed_events, args.math)
-        if world == 1 and not args.no_alt_math:
+        if args.full and world == 1 and not args.no_alt_math:
             # the other conv arithmetic on the same workload, K steps each way
             alt = "f32" if args.math != "f32" else "sp"
             model.conv_math = alt
@@ -1076,7 +1134,7 @@ def main(argv=None):
                 alt_res["roofline"] = roofline_of(alt_timer, alt_ev, alt)
             result["alt_math"] = alt_res
             model.conv_math = args.math
-        if world == 1 and not args.no_voxelize:
+        if args.full and world == 1 and not args.no_voxelize:
             # K1 from raw points (not part of the step: the reference voxelizes offline and
             # ships sparse lists): one 60k-point cloud -> dense grid -> sorted index list
             try:
@@ -1097,7 +1155,7 @@ def main(argv=None):
                                       "note": "dn_voxelize_occupy (memset + scatter), HIP events, not in `value`"}
             except Exception as e:
                 result["voxelize"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = usable_cores()
             base, ref_out = cpu_baseline_bounded(state_dict_cpu, threads, args.cpu_baseline_timeout)
             if ref_out is not None:
@@ -1157,7 +1215,7 @@ def main(argv=None):
                 except Exception as e:   # never lose the bench line to the accuracy add-on
                     base["map_vs_oracle_detections"] = {"error": repr(e)}
             result["cpu_baseline"] = base
-        if world == 1 and args.train_steps > 0:
+        if args.full and world == 1 and args.train_steps > 0:
             # CoDetModule.step on the same batch (train() mode, batch statistics)
             try:
                 from disconet_amd import CoDetModule

@@ -49,7 +49,7 @@ def test_bench_through_its_own_launcher_on_one_gpu():
     agent-sharded leg with the real collective (rccl_ranks = 1) and the launcher relays rank 0's ONE JSON line and rc 0."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--via-launcher", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--via-launcher", "--full", "--steps", "3", "--warmup", "1",
                         "--pre-roll", "2", "--no-cpu-baseline", "--no-alt-math", "--no-voxelize", "--train-steps", "0"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -72,7 +72,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DN_BENCH_SHARE_DEVICE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pre-roll", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--pre-roll", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -86,3 +86,51 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
         assert a["n_gpus"] == 2 and a["rccl_ranks"] == 2 and a["collective_backend"] == "gloo", a
         assert a["exchanged_bytes_per_rank_per_step"] > 0 and a["value"] > 0 and a["scaling"] == "strong"
     assert "cpu_baseline" not in d and "alt_math" not in d          # N = 1 extras stay out of the N > 1 line
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract fields for exactly K timed steps and none of the
+    extras.  --dump-outputs writes the last timed step's cls / loc (a seeded sample of each); they equal an eager forward of
+    the same seeded model on the same seeded batch, and a second run writes the same values."""
+    import json
+    import numpy as np
+    import bench
+    from disconet_amd import Config, DiscoNet, ops
+    from disconet_amd.synthetic import make_sparse_scene_batch, make_trans_matrices, randomize_bn_stats
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["unit"] == "scenes/s" and d["higher_is_better"] is True and d["dtype"]
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for extra in ("repeat", "roofline", "graph_equals_eager", "alt_math", "agent_sharded", "voxelize", "cpu_baseline",
+                  "train_step"):
+        assert extra not in d, extra
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("cls", "loc")}
+    assert sum(v.nbytes for v in got.values()) <= 64 * 2 ** 20
+    for k, v in got.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all()
+        np.testing.assert_array_equal(v, np.load(str(tmp_path / "b" / (k + ".npy"))))
+    # the same step, eager, in this process: bench.py's seeds, batch and input form
+    torch.manual_seed(0)
+    model = DiscoNet(Config(map_hw=bench.MAP_HW), kd_flag=0, num_agent=bench.AGENTS)
+    randomize_bn_stats(model)
+    model.conv_math = "sp"
+    model.eval().cuda()
+    indices, offsets, _ = make_sparse_scene_batch(bench.BATCH, bench.AGENTS, bench.MAP_HW)
+    trans = make_trans_matrices(bench.BATCH, bench.AGENTS, jitter_seed=0).cuda()
+    na = torch.full((bench.BATCH,), bench.AGENTS, dtype=torch.int32).cuda()
+    bevs = ops.scatter_dense_bits(indices.cuda(), offsets.cuda(), bench.AGENTS * bench.BATCH, (bench.MAP_HW, bench.MAP_HW, 13))
+    with torch.no_grad():
+        want = model(bevs, trans, na, bench.BATCH)
+    torch.cuda.synchronize()
+    for k, v in got.items():
+        w = want[k].reshape(-1)
+        idx = bench.dump_sample_index(w.numel())
+        w = (w if idx is None else w[idx.cuda()]).cpu().numpy()
+        np.testing.assert_allclose(v, w, rtol=1e-5, atol=1e-6 * float(np.abs(w).max()))

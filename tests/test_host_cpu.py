@@ -283,3 +283,25 @@ def test_bench_summary_is_short_and_last():
     assert len(json.dumps(s)) < 1900
     assert s["alt_math"]["roofline"]["frac"] == 0.73 and s["train_step"]["all_gradients_f32"]["losses"] == losses
     assert s["agent_sharded"]["emulated_share"]["projected_speedup"] == 4.33
+
+
+def test_bench_extras_are_opt_in_and_dumps_are_bounded(tmp_path):
+    """A plain bench run carries no extras (`--full` is off by default); --dump-outputs writes float32 / float64 .npy files,
+    an output above DUMP_MAX_ELEMS as the same seeded sample of flat indices every time, under 64 MB in all."""
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"]).full is False
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    n = bench.DUMP_MAX_ELEMS
+    big = torch.arange(3 * n, dtype=torch.float32).view(3, n)
+    outs = {"big": big, "small": torch.ones(2, 3, dtype=torch.float16), "loss": torch.tensor([1.5], dtype=torch.float64)}
+    bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in outs}
+    assert got["small"].dtype == np.float32 and got["small"].shape == (2, 3)
+    assert got["loss"].dtype == np.float64 and got["loss"][0] == 1.5
+    idx = bench.dump_sample_index(3 * n)
+    assert bench.dump_sample_index(n) is None and 0.7 * n < idx.numel() <= n
+    assert np.array_equal(got["big"], big.reshape(-1)[idx].numpy())          # the values at the sampled flat indices
+    assert np.array_equal(got["big"], np.load(str(tmp_path / "b" / "big.npy")))
+    assert sum(v.nbytes for v in got.values()) <= 64 * 2 ** 20

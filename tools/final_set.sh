@@ -18,12 +18,12 @@ cp $P/rocprof_conv_sp.json profiles/${RD}_rocprof_conv_sp.json
 cp $P/pmc_traffic_sp.json profiles/${RD}_pmc_traffic_sp.json
 [ -s $P/pmc_traffic_seg.json ] && cp $P/pmc_traffic_seg.json profiles/${RD}_pmc_traffic_seg.json
 cd $R
-timeout 600 python bench.py 2> $O/bench_default.err | tail -1 > $O/bench_default.json
-timeout 400 python bench.py --mode agent --no-pg --emulate-world 8 --agent-check 1000 2> $O/agent_share.err | tail -1 > $O/agent_share.json
+timeout 600 python bench.py --full 2> $O/bench_default.err | tail -1 > $O/bench_default.json
+timeout 400 python bench.py --full --mode agent --no-pg --emulate-world 8 --agent-check 1000 2> $O/agent_share.err | tail -1 > $O/agent_share.json
 for b in 8 16 32; do
-  timeout 300 python bench.py --mode agent --no-pg --emulate-world 8 --agent-batch $b --steps 10 --warmup 2 2> $O/agent_share_b$b.err | tail -1 > $O/agent_share_b$b.json
+  timeout 300 python bench.py --full --mode agent --no-pg --emulate-world 8 --agent-batch $b --steps 10 --warmup 2 2> $O/agent_share_b$b.err | tail -1 > $O/agent_share_b$b.json
 done
-timeout 500 python bench.py --task seg --train-steps 4 2> $O/bench_seg.err | tail -1 > $O/bench_seg.json
+timeout 500 python bench.py --full --task seg --train-steps 4 2> $O/bench_seg.err | tail -1 > $O/bench_seg.json
 python3 - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))
