@@ -54,7 +54,6 @@
 // Replaces the conv2d/conv3d(1x1x1)+batch_norm+relu(+interpolate+cat) chains of
 // upstream:coperception/models/det/backbone/Backbone.py.
 #include "dn_internal.h"
-#include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -665,14 +664,6 @@ conv_mfma_kernel(const ConvArgs a) {
   }
 }
 
-// Persistent-workgroup policy: 0 = never, 1 = only the 256-pixel / fused tiles with 2-4 chunks,
-// 2 = always (default).  History on MI355X, batch 4: with one step at a time and the first
-// (channel-block-major) work-item order, policy 1 measured best (persistence +4-13 % on the short
-// 32- and 64-channel full/half-resolution layers, -2-20 % on stride-2 and long-K launches).  With
-// the XCD-aware order, interleaved A/B runs put "always" 1.5-2 % ahead of policy 1 (split-f16)
-// and 3.4 % (exact fp32); "never" lands within 0.5 % of "always".
-int g_persist = 2;
-
 // ---------------------------------------------------------------------------
 // tile menu and per-launch selection
 // ---------------------------------------------------------------------------
@@ -903,26 +894,16 @@ int launch(ConvArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   const long total = (long)a.n_images * a.tiles_y * a.tiles_x * ((d.c_out + BN - 1) / BN);
   DN_REQUIRE(total < (1L << 31), "conv: too many tiles (%ld)", total);
   a.total_items = (int)total;
-  // DN_CONV_XCD=0 restores channel-block-major order, 1 interleaves pixel tiles over the
-  // XCDs.  Measured (batch 4): conv FETCH per step 3.54 GB (0) -> 2.79 GB (1) -> 2.49 GB (2);
+  // order 2: each XCD walks its own contiguous run of pixel tiles.  Measured (batch 4): conv FETCH per step
+  // 3.54 GB (channel-block-major order, 0) -> 2.79 GB (pixel tiles interleaved over the XCDs, 1) -> 2.49 GB (2);
   // step time within 1 % of each other -- the re-reads came out of the 256 MB MALL.
-  static const int xcd_env = [] {
-    const char* e = getenv("DN_CONV_XCD");
-    return e ? atoi(e) : 2;
-  }();
-  a.xcd_order = xcd_env;
+  a.xcd_order = 2;
   // persistent grid: as many workgroups as are resident (no inter-workgroup sync
-  // depends on the count; an over-estimate only queues the surplus)
+  // depends on the count; an over-estimate only queues the surplus).  History on MI355X, batch 4: with
+  // the XCD-aware order, interleaved A/B runs put "always persistent" 1.5-2 % ahead of persisting only the
+  // 256-pixel / fused tiles with 2-4 chunks (split-f16) and 3.4 % (exact fp32); "never" lands within 0.5 %.
   const long resident = (long)occupancy * kNumCUs;
-  static const int persist_env = [] {   // experiments: DN_CONV_PERSIST=0|1|2 overrides the policy
-    const char* e = getenv("DN_CONV_PERSIST");
-    return e ? atoi(e) : -1;
-  }();
-  const int pmode = persist_env >= 0 ? persist_env : g_persist;
-  // fused-1x1 launches: short tiles with a long epilogue and per-workgroup weight registers
-  const bool persist = pmode == 2 || (pmode == 1 && (POST != 0 || T::BM >= 256) && a.nchunks >= 2 &&
-                                      a.nchunks <= 4);
-  dim3 grid((unsigned)((persist && total > resident) ? resident : total));
+  dim3 grid((unsigned)(total > resident ? resident : total));
   hipLaunchKernelGGL(kern, grid, dim3(T::NT), T::LDS_BYTES, stream, a);
   return dn::check_launch("conv_mfma_kernel");
 }
@@ -1057,13 +1038,8 @@ extern "C" int dn_conv2d_post1x1(const dn_conv_desc* d, const dn_post1x1_desc* p
   a.w2 = packed2; a.scale2 = scale2; a.shift2 = shift2; a.out_b = out_b;
   a.c_out2 = p->c_out2; a.relu2 = p->relu2; a.split2 = p->split; a.ldo_b = p->ldo_b;
   // 8x32-pixel workgroups (4 MFMA tiles per wave): +2.9 % per step over 8x16 (weights staged and
-  // barriers paid half as often per pixel); DN_POST_TILE=128 selects the smaller tile
-  static const int tile_env = [] {
-    const char* e = getenv("DN_POST_TILE");
-    return e ? atoi(e) : 256;
-  }();
-  if (tile_env == 256) return launch<3, 1, 8, 32, 64, 16, 2, 2, 4, 1, 0, 1, 1>(a, *d, (hipStream_t)stream);
-  return launch<3, 1, 8, 16, 64, 16, 2, 2, 2, 1, 0, 1, 1>(a, *d, (hipStream_t)stream);
+  // barriers paid half as often per pixel)
+  return launch<3, 1, 8, 32, 64, 16, 2, 2, 4, 1, 0, 1, 1>(a, *d, (hipStream_t)stream);
 }
 
 namespace {

@@ -22,10 +22,6 @@
 // LDS: patch 2 x 39168 + conv_pre_2 weights 36864 + conv_pre_1 weights 18432 + occupancy words 2880 + affines 512 + the
 // byte -> fragment table 4096 = 141120 B.
 
-#ifndef DN_PRE_LUT
-#define DN_PRE_LUT 1     // tools/ab: 0 = the occupancy bytes expanded with VALU instructions instead of a table in LDS
-#endif
-
 namespace {
 
 namespace pp {
@@ -89,9 +85,7 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
     aff[96 + tid] = tid < a.c_out ? a.t2[tid] : 0.f;
   }
 
-#if DN_PRE_LUT
   if (tid < 256) *reinterpret_cast<half8*>(smem + OFF_LUT + tid * 16) = expand_octet((unsigned)tid);
-#endif
 #if DN_PHASE_TIMING
   unsigned long long ph[7] = {0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_prev = __builtin_readcyclecounter();
@@ -190,12 +184,8 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
 #pragma unroll
       for (int u = 0; u < 9; ++u) {
         const unsigned word = *reinterpret_cast<const unsigned*>(wp + ((u / 3) * BW + u % 3) * 4);
-#if DN_PRE_LUT
         // (a table read instead of 17 VALU instructions; at LiDAR occupancies most lanes read entry 0: one broadcast)
         const half8 x = *reinterpret_cast<const half8*>(smem + OFF_LUT + ((word >> (8 * lh)) & 0xffu) * 16);
-#else
-        const half8 x = expand_octet((word >> (8 * lh)) & 0xffu);
-#endif
         const half8 bh = *reinterpret_cast<const half8*>(w1p + u * 2048);
         const half8 bl = *reinterpret_cast<const half8*>(w1p + u * 2048 + 1024);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, x, acc, 0, 0, 0);

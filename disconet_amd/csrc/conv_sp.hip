@@ -24,30 +24,15 @@
 // Replaces the conv2d + batch_norm + relu (+ interpolate x2 + cat) chains of
 // upstream:coperception/models/det/backbone/Backbone.py :: encode / decode and the heads of
 // upstream:coperception/models/det/base/* (SURVEY.md §8 a3, a8, a9).
-#ifndef DN_EPI_SOFF
-#define DN_EPI_SOFF 0
-#endif
-#ifndef DN_MFMA_PRIO
-#define DN_MFMA_PRIO 0
-#endif
-#ifndef DN_MMA_GRAY
-#define DN_MMA_GRAY 1      // Gray order of the accumulator tiles inside a product group (compute :: mma; 0 = rounds 2-5's row-major order: same bits, conv launches +0.3 %, profiles/r06_mma_gray_ab.txt)
-#endif
 // tools/ab: 1 = the weight-stationary kernels time their phases with s_memtime (wave 0 of every workgroup, summed into
 // g_phase_cycles: [0] wait for the patch + barrier, [1] issue of the next patch, [2] MFMA loop, [3] epilogue, [4] tile decode + rest,
 // [5] tiles, [6] total) -- read with dn_sp_phase_cycles().  Never in the shipped build.
 #ifndef DN_PHASE_TIMING
 #define DN_PHASE_TIMING 0
 #endif
-#ifndef DN_S2_ABL
-#define DN_S2_ABL 0      // tools/ab: 1 = instantiate the timing-only ablations of the stride-2 8 x 8 tile (dn_spconv_force_config(400..407))
-#endif
-#ifndef DN_UNIFORM_TILE
-#define DN_UNIFORM_TILE 0   // tools/ab: 1 = every kernel's tile coordinates through v_readfirstlane (scalar registers)
-#endif
-#ifndef DN_HEADS_W2_REGS
-#define DN_HEADS_W2_REGS 1   // 1: the heads' 1x1 weight fragments held in registers across tiles (shipped); 0: read per tile -- 54 VGPRs fewer, measured 0.5 % slower (round 4, same lease)
-#endif
+#ifndef DN_SP_ABL
+#define DN_SP_ABL 0      // 1 = instantiate the timing-only ablation kernels that dn_spconv_force_config(101..105, 201..207, 400..407)
+#endif                   // selects (tools/sp_conv_check.cpp).  Never in the shipped build.
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
@@ -241,7 +226,7 @@ conv_sp_kernel(const SpArgs a) {
     tc.img = fdivmod(spi, a.tiles_y, a.rcp_ty, ty);
     tc.ox0 = tx * TW;
     tc.oy0 = ty * TH;
-    if constexpr (AHI == 2 || DN_UNIFORM_TILE) {   // plain buffer loads in the K loop: without this the compiler treats the tile as divergent
+    if constexpr (AHI == 2) {   // plain buffer loads in the K loop: without this the compiler treats the tile as divergent
       tc.n0 = __builtin_amdgcn_readfirstlane(tc.n0);      // and wraps every buffer store of the epilogue in a waterfall loop
       tc.img = __builtin_amdgcn_readfirstlane(tc.img);
       tc.ox0 = __builtin_amdgcn_readfirstlane(tc.ox0);
@@ -462,17 +447,14 @@ conv_sp_kernel(const SpArgs a) {
     };
     auto mma = [&](auto u_c) {
       constexpr int s = decltype(u_c)::value & 1;
-#if DN_MFMA_PRIO
-      __builtin_amdgcn_s_setprio(DN_MFMA_PRIO);     // tools/ab: the wave that has its fragments issues MFMAs ahead of a neighbour's epilogue VALU
-#endif
       // D[i = channel][j = pixel]; small terms first; independent accumulators interleaved
-      // DN_MMA_GRAY (tools/ab): walk the accumulator tiles of a product group in Gray order -- consecutive MFMAs then differ in ONE
-      // operand register set, not two (every accumulator still receives its three products in the same order: same bits)
+      // The accumulator tiles of a product group are walked in Gray order -- consecutive MFMAs then differ in ONE operand
+      // register set, not two (every accumulator still receives its three products in the same order: same bits)
 #pragma unroll
       for (int wm = 0; wm < WTM; ++wm)
 #pragma unroll
         for (int k = 0; k < WTN; ++k) {
-          const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+          const int wn = (wm & 1) ? WTN - 1 - k : k;
           acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s][wn], ah[s][wm], acc[wm][wn], 0, 0, 0);
         }
       if constexpr (AHI == 0) {
@@ -480,7 +462,7 @@ conv_sp_kernel(const SpArgs a) {
       for (int wm = 0; wm < WTM; ++wm)
 #pragma unroll
         for (int k = 0; k < WTN; ++k) {
-          const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+          const int wn = (wm & 1) ? WTN - 1 - k : k;
           acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][wn], al[s][wm], acc[wm][wn], 0, 0, 0);
         }
       }
@@ -488,12 +470,9 @@ conv_sp_kernel(const SpArgs a) {
       for (int wm = 0; wm < WTM; ++wm)
 #pragma unroll
         for (int k = 0; k < WTN; ++k) {
-          const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+          const int wn = (wm & 1) ? WTN - 1 - k : k;
           acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][wn], ah[s][wm], acc[wm][wn], 0, 0, 0);
         }
-#if DN_MFMA_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
     };
     load(std::integral_constant<int, 0>{});
     auto body = [&](auto u_c) {
@@ -526,12 +505,10 @@ conv_sp_kernel(const SpArgs a) {
   constexpr bool kRegAffine = POST == 0;
   f32x4 sc_r[kRegAffine ? WTN : 1][4], sh_r[kRegAffine ? WTN : 1][4];
   int aff_n0 = -1;
-#if DN_HEADS_W2_REGS
   half8 w2h[POST == 2 ? WTN : 1][2][2], w2l[POST == 2 ? WTN : 1][2][2];   // POST 2: the heads' 1x1 weights
   int w2_cb[POST == 2 ? WTN : 1];
 #pragma unroll
   for (int wn = 0; wn < (POST == 2 ? WTN : 1); ++wn) w2_cb[wn] = -1;
-#endif
   auto load_affine = [&](int n0) {
     if (!kRegAffine || n0 == aff_n0) return;
     aff_n0 = n0;
@@ -550,9 +527,7 @@ conv_sp_kernel(const SpArgs a) {
     // first use -- the epilogue, inside the persistent loop -- gets an s_waitcnt vmcnt(0), which in steady state (no loads
     // pending, the registers long valid) waits for the NEXT tile's patch DMA instead: every epilogue started only after
     // the prefetch it was meant to hide had landed (round 4, phase timing: tools/phase_probe.py).
-#if DN_EPI_NO_DMA_WAIT
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
-#endif
   };
   // One 32-pixel x 32-channel accumulator tile -> SP pieces.  Stores are buffer stores against a descriptor of the
   // output IMAGE (32-bit lane offset computed once per tile + the quarter-plane offset; a lane outside the map
@@ -574,7 +549,6 @@ conv_sp_kernel(const SpArgs a) {
       const float fl = relu_here ? floor_v : -__builtin_inff();
       if (wn_r >= 0) {            // register-resident affine (channels past c_out: scale = shift = 0 -> 0)
         v = affine4(quad_of(c, g), sc_r[kRegAffine ? wn_r : 0][g], sh_r[kRegAffine ? wn_r : 0][g]);
-        note_nan4_tile(nan_seen, v, g);
         if (relu_here) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], fl);
@@ -583,7 +557,6 @@ conv_sp_kernel(const SpArgs a) {
         const f32x4 sc = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[POST == 1 ? 2 : 0][co & 63]), smem);
         const f32x4 sh = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[POST == 1 ? 3 : 0][co & 63]), smem);
         v = affine4(quad_of(c, g), sc, sh);
-        note_nan4_tile(nan_seen, v, g);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (relu_here) v[e] = fmaxf(v[e], fl);
@@ -596,7 +569,6 @@ conv_sp_kernel(const SpArgs a) {
           const int ci = min(co + e, c_lim - 1);
           v[e] = c[4 * g + e] * scale[ci] + shift[ci];
         }
-        note_nan4_tile(nan_seen, v, g);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (relu_here) v[e] = fmaxf(v[e], fl);
@@ -645,28 +617,8 @@ conv_sp_kernel(const SpArgs a) {
         // operand hipcc leaves out the wait states between a dwordx4 store and a VALU write of its data registers
         // (its hazard recognizer exempts SGPR offsets; gfx950 needs them): the round-3 form wrote ~1e-4 of the lo
         // pieces wrong, lanes 12-15 / 28-31 of both halves.  DESIGN.md 3.6 (C); tools/soff; tests/test_isa_hazard_cpu.py.
-#if DN_EPI_SOFF == 4   // both scalar offsets formed BEFORE the pair: no SALU write of a store's soffset register behind it
-        int so_h = __builtin_amdgcn_readfirstlane(cg * 4 * plane), so_l = __builtin_amdgcn_readfirstlane((cg * 4 + 2) * plane);
-        asm volatile("" : "+s"(so_h), "+s"(so_l));
-        __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff, so_h, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff, so_l, 0);
-#elif DN_EPI_SOFF >= 1   // tools/soff: the round-3 form with the plane offset in the SCALAR operand (1), + wait states behind each store (2, 3)
-        __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff, cg * 4 * plane, 0);
-#if DN_EPI_SOFF == 2
-        asm volatile("s_nop 1" ::: "memory");
-#elif DN_EPI_SOFF == 3
-        asm volatile("s_nop 7" ::: "memory");
-#endif
-        __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff, (cg * 4 + 2) * plane, 0);
-#if DN_EPI_SOFF == 2
-        asm volatile("s_nop 1" ::: "memory");
-#elif DN_EPI_SOFF == 3
-        asm volatile("s_nop 7" ::: "memory");
-#endif
-#else
         __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff + cg * 4 * plane, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff + (cg * 4 + 2) * plane, 0, 0);
-#endif
       }
     }
   };
@@ -684,10 +636,9 @@ conv_sp_kernel(const SpArgs a) {
       float* obase = cb ? a.out_b : reinterpret_cast<float*>(a.out);
       const int ldo = cb ? a.ldo_b : a.ldo_a;
       // stage-2 weight fragments of this head (W2 image: [cb][nt][ks][part][h][32] x 16 B, 4 KB per head, L2-resident):
-      // held in registers across tiles (245 VGPRs, no spills, two workgroups per CU either way).  The per-tile read
-      // (DN_HEADS_W2_REGS=0: 191 VGPRs) measured 10 us slower per launch in the same lease -- the L2 round trip sits in
-      // front of every tile's second stage.
-#if DN_HEADS_W2_REGS
+      // held in registers across tiles (245 VGPRs, no spills, two workgroups per CU either way).  A per-tile read
+      // (191 VGPRs) measured 10 us slower per launch in the same lease -- the L2 round trip sits in front of every
+      // tile's second stage.
       if (cb != w2_cb[wn]) {
         w2_cb[wn] = cb;
 #pragma unroll
@@ -698,27 +649,8 @@ conv_sp_kernel(const SpArgs a) {
             w2h[wn][nt][ks] = *reinterpret_cast<const half8*>(wp);
             w2l[wn][nt][ks] = *reinterpret_cast<const half8*>(wp + 2 * 32 * 16);
           }
-#if DN_EPI_NO_DMA_WAIT
         __builtin_amdgcn_s_waitcnt(0x0F70);   // as in load_affine: no vmcnt(0) at the fragments' first use in later tiles
-#endif
       }
-      auto w2_hi = [&](int nt, int ks) { return w2h[wn][nt][ks]; };
-      auto w2_lo = [&](int nt, int ks) { return w2l[wn][nt][ks]; };
-#else
-      half8 w2h_t[2][2], w2l_t[2][2];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        if (nt * 32 >= c2) break;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const unsigned char* wp = a.w2 + (size_t)((((((cb * 2 + nt) * 2 + ks) * 2 + 0) * 2 + lh) * 32 + li)) * 16;
-          w2h_t[nt][ks] = *reinterpret_cast<const half8*>(wp);
-          w2l_t[nt][ks] = *reinterpret_cast<const half8*>(wp + 2 * 32 * 16);
-        }
-      }
-      auto w2_hi = [&](int nt, int ks) { return w2h_t[nt][ks]; };
-      auto w2_lo = [&](int nt, int ks) { return w2l_t[nt][ks]; };
-#endif
 #pragma unroll
       for (int wm = 0; wm < WTM; ++wm) {
         u32x2 hi[4], lo[4];
@@ -750,7 +682,7 @@ conv_sp_kernel(const SpArgs a) {
           for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
-            const half8 wh = w2_hi(nt, ks), wl = w2_lo(nt, ks);
+            const half8 wh = w2h[wn][nt][ks], wl = w2l[wn][nt][ks];
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[ks], acc2, 0, 0, 0);
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[ks], acc2, 0, 0, 0);
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[ks], acc2, 0, 0, 0);
@@ -802,7 +734,6 @@ conv_sp_kernel(const SpArgs a) {
             const f32x4 sc = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[0][POST == 1 ? co : 0]), smem);
             const f32x4 sh = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[POST == 1 ? 1 : 0][POST == 1 ? co : 0]), smem);
             v = affine4(quad_of(acc[wm][wn], g), sc, sh);
-            note_nan4_tile(nan_seen, v, g);
             split4(v, hi[g], lo[g], amax, a.relu ? 0.f : -65504.f);   // the ReLU rides in the split's clamp
           }
 #pragma unroll
@@ -1438,13 +1369,12 @@ inline int cout_pad_of(int c_out) { return (c_out + 63) / 64 * 64; }
 inline int chunks_of(int c) { return (c + 15) / 16; }
 // weights are padded to whole groups of 4 chunks so that a 1x1 A group never runs past them
 // Row-merged form of a 3x3 conv whose first source is nearest-upsampled (SpTile UPM): decided by the layer
-// alone, so that pack time and run time agree (DN_SP_UPMERGE=0 switches it off for the process).
+// alone, so that pack time and run time agree.
 // -> 0: plain taps; 1: row-merged (UPM, this file); 2: row- and column-merged per parity class (conv_spq.hip, the
-// default).  DN_SP_UPMERGE=0|1|2 / dn_spconv_set_upmode() choose for the process: set before the first pack.
+// default).  dn_spconv_set_upmode() chooses for the process (-1: the default): set before the first pack.
 int g_sp_upmode = -1;
 inline int up_mode(const dn_conv_desc& d) {
-  static const int env = [] { const char* e = getenv("DN_SP_UPMERGE"); return e ? atoi(e) : 2; }();
-  const int mode = g_sp_upmode >= 0 ? g_sp_upmode : env;
+  const int mode = g_sp_upmode >= 0 ? g_sp_upmode : 2;
   const bool ok = d.up0 == 1 && d.ksize == 3 && d.stride == 1 && d.c0 > 0 && d.c0 % 16 == 0 && d.h_in % 2 == 0 &&
                   d.w_in % 2 == 0;
   return ok ? (mode < 0 ? 0 : mode > 2 ? 2 : mode) : 0;
@@ -1551,8 +1481,7 @@ SpCfg select_cfg(const dn_conv_desc& d, int kslices = 1, bool can_split = false)
     const double cost = rounds * c.th * c.tw * c.bn * g_sp_bias[c.id];
     if (cost < best_cost * 0.999) { best_cost = cost; best = c; best_blocks = blocks; }
   }
-  static const int deep_env = [] { const char* e = getenv("DN_SP_DEEP"); return e ? atoi(e) : 1; }();
-  if (deep_env && g_sp_force < 0 && !upm && best_blocks * (ksl && can_split ? kslices : 1) <= kCUs) best = kSpCfgs[deep_variant(best.id)];
+  if (g_sp_force < 0 && !upm && best_blocks * (ksl && can_split ? kslices : 1) <= kCUs) best = kSpCfgs[deep_variant(best.id)];
   return best;
 }
 
@@ -1878,7 +1807,7 @@ extern "C" int dn_spconv2d_nhwc(const dn_conv_desc* d, const void* src0, const v
 inline bool ks_layer(const dn_conv_desc& d) { return d.ksize == 3 && d.math != 3 && d.math != 4 && up_mode(d) != 1; }
 
 // Can the layer run with `kslices` canonical K slices?  A property of the layer and of the process's up-conv form
-// (DN_SP_UPMERGE / dn_spconv_set_upmode), never of the batch: callers that take the count from a table fall back to 1
+// (dn_spconv_set_upmode), never of the batch: callers that take the count from a table fall back to 1
 // where this says no, instead of meeting DN_ERR_ARG in dn_spconv2d_ks.
 extern "C" int dn_spconv_ks_supported(const dn_conv_desc* d, int kslices) {
   if (validate(d) != DN_OK) return 0;
@@ -1967,7 +1896,22 @@ int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, con
       default: return dn::fail(DN_ERR_UNSUPPORTED, "spconv: tile configuration %d has no row-merged form", (int)c.id);
     }
   }
-  if (g_sp_force >= 100 && d->ksize == 3 && d->stride == 1) {   // tools: timing-only ablations
+  // tools: timing-only ablations (results wrong by construction; tools/sp_conv_check.cpp).  Those of the deep-regime tile are
+  // in every build: without them hipcc schedules the shipped 8 x 8 and 8 x 16 tiles' prologues differently (same registers,
+  // a few instructions moved), and the shipped kernels are to stay as measured.  The others only with DN_SP_ABL; without
+  // it a forced id 101.. falls through like any other.
+  if (g_sp_force >= 300 && d->ksize == 3 && d->stride == 1) {
+    switch (g_sp_force) {
+      case 301: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 1>(a, *d, s);   // the deep-regime tile
+      case 302: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 2>(a, *d, s);
+      case 303: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 3>(a, *d, s);
+      case 304: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 4>(a, *d, s);
+      case 305: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 5>(a, *d, s);
+      default: break;
+    }
+  }
+#if DN_SP_ABL
+  if (g_sp_force >= 100 && d->ksize == 3 && d->stride == 1) {
     switch (g_sp_force) {
       case 101: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 1>(a, *d, s);
       case 102: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 2>(a, *d, s);
@@ -1981,15 +1925,9 @@ int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, con
       case 205: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 5>(a, *d, s);
       case 206: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 6>(a, *d, s);
       case 207: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 7>(a, *d, s);
-      case 301: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 1>(a, *d, s);   // the deep-regime tile
-      case 302: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 2>(a, *d, s);
-      case 303: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 3>(a, *d, s);
-      case 304: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 4>(a, *d, s);
-      case 305: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 5>(a, *d, s);
       default: break;
     }
   }
-#if DN_S2_ABL   // tools/ab build only (AB_FILES=conv_sp tools/ab/build.sh DN_S2_ABL 1): timing-only ablations of the stride-2 8 x 8 tile
   if (g_sp_force >= 400 && d->ksize == 3 && d->stride == 2) {
     switch (g_sp_force) {
       case 400: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0>(a, *d, s);   // as shipped in round 4 (two weight stages)
@@ -2004,13 +1942,11 @@ int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, con
   }
 #endif
   // weight-stationary forms (short-K full-resolution layers): two workgroups per CU
-  // DN_SP_STATIONARY=0: weights streamed per step everywhere (A/B runs)
-  static const int stat_env = [] { const char* e = getenv("DN_SP_STATIONARY"); return e ? atoi(e) : 1; }();
   // (a 16x32-pixel stationary tile -- four MFMA tiles per wave, ONE workgroup per CU -- measured
   // 14 % slower on conv8_2 and 33 % slower on the heads than 8x32 with two workgroups per CU, and
   // weights held in registers instead of LDS spilled at the 256-VGPR budget of two workgroups: what
   // these short-K layers need is a second workgroup to run under the first one's waits)
-  if (stat_env && g_sp_force < 0 && c.id == S3_256x32) {
+  if (g_sp_force < 0 && c.id == S3_256x32) {
     using T32 = SpTile<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 1>;
     if (fits_stationary(*d, 32, T32::A_STAGE, 0, 2))
       return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 1>(a, *d, s);
@@ -2079,30 +2015,13 @@ extern "C" int dn_spconv2d_post1x1(const dn_conv_desc* d, const dn_post1x1_desc*
     DN_REQUIRE(out_f32 && p->split < p->c_out2 && p->split <= 64 &&
                    p->c_out2 - p->split <= 64,
                "spconv+1x1: the block-diagonal form needs two fp32 outputs of <= 64 columns each");
-    using TS = SpTile<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 1>;
-    static const int stat_env = [] { const char* e = getenv("DN_SP_STATIONARY"); return e ? atoi(e) : 1; }();
-    // both heads in one workgroup (the input patch is staged once; -4 % on the heads launch): 1 = streaming
-    // weights (default), 2 = LDS-resident weights, 0 = one head per workgroup
-    static const int heads64 = [] { const char* e = getenv("DN_SP_HEADS64"); return e ? atoi(e) : 1; }();
-    using TS64 = SpTile<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 2, 1>;
-    if (heads64 == 2 && fits_stationary(*d, 64, TS64::A_STAGE, 1024, 1, true))
-      return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 2, 0, 1>(a, *d, (hipStream_t)stream);
-    if (heads64 >= 1) return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 2, 0, 0>(a, *d, (hipStream_t)stream);
-    // ablations of the heads launch (measurement only): 3 = no operand DMA, 4 = no stores, 5 = no LDS reads
-    static const int heads_abl = [] { const char* e = getenv("DN_SP_HEADS_ABL"); return e ? atoi(e) : 0; }();
-    if (heads_abl == 3) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 3, 0>(a, *d, (hipStream_t)stream);
-    if (heads_abl == 4) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 4, 0>(a, *d, (hipStream_t)stream);
-    if (heads_abl == 5) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 5, 0>(a, *d, (hipStream_t)stream);
-    if (heads_abl == 9) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 0, 0>(a, *d, (hipStream_t)stream);
-    if (stat_env && fits_stationary(*d, 32, TS::A_STAGE, 1024, 2, true))
-      return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 0, 1>(a, *d, (hipStream_t)stream);
-    return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 2, 0, 0>(a, *d, (hipStream_t)stream);
+    // both heads in one workgroup, weights streamed: the input patch is staged once (-4 % on the heads launch)
+    return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 2>(a, *d, (hipStream_t)stream);
   }
   {
     using TP = SpTile<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1, 1>;
-    static const int stat_env = [] { const char* e = getenv("DN_SP_STATIONARY"); return e ? atoi(e) : 1; }();
     const int extra = TP::W2_BYTES + (out_f32 ? TP::NW * 32 * (p->c_out2 + 4) * 4 : 0) + 1024;   // + the static affine block
-    if (stat_env && g_sp_force != 0 && fits_stationary(*d, 64, TP::A_STAGE, extra, 1))
+    if (g_sp_force != 0 && fits_stationary(*d, 64, TP::A_STAGE, extra, 1))
       return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1, 0, 1>(a, *d, (hipStream_t)stream);
   }
   return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1>(a, *d, (hipStream_t)stream);

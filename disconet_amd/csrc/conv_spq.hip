@@ -24,16 +24,12 @@
 // Pipeline (double-buffered patch per chunk, double-buffered weights per step, raw s_barrier + counted
 // vmcnt waits, next tile's first operands under the current tile's last step), persistent workgroups, XCD-aware
 // item order and the register epilogue are those of conv_sp_kernel.
-#ifndef DN_MFMA_PRIO
-#define DN_MFMA_PRIO 0
-#endif
-#ifndef DN_MMA_GRAY
-#define DN_MMA_GRAY 1      // see conv_sp.hip
+#ifndef DN_SP_ABL
+#define DN_SP_ABL 0      // 1 = the timing-only ablations of the BN = 32 form (bn 101..103; see conv_sp.hip)
 #endif
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -284,35 +280,29 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
     half8 ah[2], al[2], bh[WTN], bl[WTN];
   };
   auto mma = [&](const Frags& f) {
-#if DN_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(DN_MFMA_PRIO);
-#endif
     // (Gray order of the accumulator tiles inside a product group, as conv_sp_kernel's mma: consecutive MFMAs differ in one
     // operand register set; every accumulator receives its three products in the same order -- same bits)
 #pragma unroll
     for (int wm = 0; wm < 2; ++wm)
 #pragma unroll
       for (int k = 0; k < WTN; ++k) {
-        const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+        const int wn = (wm & 1) ? WTN - 1 - k : k;
         acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bl[wn], f.ah[wm], acc[wm][wn], 0, 0, 0);
       }
 #pragma unroll
     for (int wm = 0; wm < 2; ++wm)
 #pragma unroll
       for (int k = 0; k < WTN; ++k) {
-        const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+        const int wn = (wm & 1) ? WTN - 1 - k : k;
         acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bh[wn], f.al[wm], acc[wm][wn], 0, 0, 0);
       }
 #pragma unroll
     for (int wm = 0; wm < 2; ++wm)
 #pragma unroll
       for (int k = 0; k < WTN; ++k) {
-        const int wn = (DN_MMA_GRAY && (wm & 1)) ? WTN - 1 - k : k;
+        const int wn = (wm & 1) ? WTN - 1 - k : k;
         acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bh[wn], f.ah[wm], acc[wm][wn], 0, 0, 0);
       }
-#if DN_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
   };
   // step ST of a source-1 chunk: taps (dy = ST, dx = 0..2), weights shared by the four waves
   auto compute1 = [&](auto st_c, const unsigned char* As, const unsigned char* Bs) {
@@ -451,7 +441,6 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
           const f32x4 sc = *reinterpret_cast<const f32x4*>(aff_s + wn * 32 + 8 * g + 4 * lh);
           const f32x4 sh = *reinterpret_cast<const f32x4*>(aff_s + 64 + wn * 32 + 8 * g + 4 * lh);
           const f32x4 v = affine4(quad_of(acc[wm][wn], g), sc, sh);
-          note_nan4_tile(nan_seen, v, g);
           split4(v, hi[g], lo[g], amax, lo_clamp);      // the ReLU rides in the split's clamp (sp_device.h)
         }
 #pragma unroll
@@ -801,8 +790,7 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
     // K-sliced layer: the 32-channel tile whatever the launch size (the result must not depend on it); the
     // one-step-per-chunk form when even the slices leave CUs without a workgroup
     const long tiles = (long)d->n_images * ((d->h_in + QTH - 1) / QTH) * ((d->w_in + QTW - 1) / QTW);
-    static const int deep_env = [] { const char* e = getenv("DN_SP_DEEP"); return e ? atoi(e) : 1; }();
-    const bool deep = deep_env && tiles * ((d->c_out + 31) / 32) * kslices <= (long)kCUs;
+    const bool deep = tiles * ((d->c_out + 31) / 32) * kslices <= (long)kCUs;
     if (bn == 33 || (bn == 0 && deep)) return launch_spq<32, 1, 0, 1>(a, stream, workspace_bytes);
     return launch_spq<32, 0, 0, 1>(a, stream, workspace_bytes);
   }
@@ -812,14 +800,15 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
     // 1280 items: 129 vs 153 us; conv6_1 640 items: 146 vs 142 us; conv5_1 320 items: 174 vs 171 us)
     bn = (d->c_out > 32 && tiles * ((d->c_out + 63) / 64) >= 4L * kCUs) ? 64 : 32;
     // fewer items than CUs: latency regime (SpqTile DEEP)
-    static const int deep_env = [] { const char* e = getenv("DN_SP_DEEP"); return e ? atoi(e) : 1; }();
-    if (deep_env && bn == 32 && tiles * ((d->c_out + 31) / 32) <= (long)kCUs) bn = 33;
+    if (bn == 32 && tiles * ((d->c_out + 31) / 32) <= (long)kCUs) bn = 33;
   }
   if (bn == 64) return launch_spq<64>(a, stream);
   if (bn == 33) return launch_spq<32, 1>(a, stream);
+#if DN_SP_ABL
   if (bn == 101) return launch_spq<32, 0, 1>(a, stream);   // timing-only ablations of the BN = 32 form
   if (bn == 102) return launch_spq<32, 0, 2>(a, stream);
   if (bn == 103) return launch_spq<32, 0, 3>(a, stream);
+#endif
   return launch_spq<32>(a, stream);
 }
 

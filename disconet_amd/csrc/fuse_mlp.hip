@@ -25,7 +25,6 @@
 // upstream:coperception/models/det/DiscoNet.py :: DiscoNet.forward (Appx A.5).
 #include "dn_internal.h"
 #include "sp_device.h"
-#include <cstdlib>
 #include <type_traits>
 
 // tools/ab (DN_FUSE_PHASES 1): every active wave of the weight-in-LDS form adds its cycles per phase into g_fuse_phase --
@@ -49,13 +48,9 @@ namespace {
 constexpr int MAX_AGENTS = 8;
 constexpr size_t kW2Bytes = 8 * 2 * 2 * 32 * 16, kW3Bytes = 2 * 2 * 2 * 32 * 16;
 constexpr int FUSE_G = 3;   // list slots per layer-1 pass: 3 accumulator sets (192 AGPRs) is what hipcc allocates without spilling
-#ifndef DN_FUSE_RING
-#define DN_FUSE_RING 4   // row ring of the weight-in-LDS form's layer-1 loop (k-steps); 8 measured the same (67.5 vs 67.9 us standalone): the loop does not wait for its rows
-#endif
-#ifndef DN_FUSE_GL
-#define DN_FUSE_GL 2      // 3 spills 16 registers there (tools/kernel_resources.py fuse_mlp); the grouping does not change a bit of any slot's chain
-#endif
-constexpr int FUSE_GL = DN_FUSE_GL;   // the same for the weight-in-LDS form (the ego term holds 64 more registers there)
+// the same for the weight-in-LDS form, whose ego term holds 64 more registers: 3 spills 16 of them (tools/kernel_resources.py
+// fuse_mlp); the grouping does not change a bit of any slot's chain
+constexpr int FUSE_GL = 2;
 
 struct FuseMlpArgs {
   const float* feat;
@@ -72,21 +67,10 @@ struct FuseMlpArgs {
   int total_tiles;   // batch * ego_count * tiles (the weight-in-LDS form has workgroups of several tiles)
   int warped_fm;   // `warped` is fragment-major (dn_warp_neighbors_fm): a k-step of a tile is two contiguous 1 KB runs
 };
-// Timing-only ablations (results are garbage), COMPILE-time so that the shipped kernel carries none of it: build a variant
-// with tools/ab/build.sh DN_FUSE_ABL <mask>: 1 = pass 2 reads no rows, 2 = layer 1 reads each row's first k-step only,
-// 4 = no layers 2-4, 8 = layer 1 splits no operands.  (As a run-time argument the four tests cost 4 us of the launch.)
-#ifndef DN_FUSE_ABL
-#define DN_FUSE_ABL 0
-#endif
-constexpr int kAbl = DN_FUSE_ABL;
-// layer-1 weight fragments (L2): how many k-steps ahead of their MFMAs they are requested (1: two register sets, shipped).  2 and 3
+// layer-1 weight fragments (L2): requested one k-step ahead of their MFMAs, two register sets.  Two and three steps ahead
 // (ring of four sets, no spills, counted vmcnt waits in the ISA) measured 83.7 us against 84.5 in the same lease: the launch is not
 // waiting on the L2 latency of these loads.
-#ifndef DN_FUSE_WAHEAD
-#define DN_FUSE_WAHEAD 1
-#endif
-constexpr int kWAhead = DN_FUSE_WAHEAD, kWRing = kWAhead == 1 ? 2 : 4;
-static_assert(kWAhead >= 1 && kWAhead <= 3, "weight prefetch distance");
+constexpr int kWAhead = 1, kWRing = 2;
 
 __device__ inline half8 frag_of(const unsigned char* base, int idx) {
   return *reinterpret_cast<const half8*>(base + (size_t)idx * 16);
@@ -256,8 +240,9 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
     const unsigned char* wbase = a.w1 + (size_t)mat * 4 * KS * 2 * 2 * 32 * 16 + (size_t)(lh * 32 + li) * 16;
     // fragment (nt, ks, part) at wbase + (((nt * KS + ks) * 2 + part) * 64) * 16
     half8 wh[kWRing][4], wl[kWRing][4];   // weight fragments: ring of kWRing k-steps, loaded kWAhead k-steps before their MFMAs
-    // row pieces: ring of RING k-steps (the maps come from HBM / the far L2); DN_FUSE_RING deepens it for the weight-in-LDS form (A/B)
-    constexpr int RING = (kWL && KS % DN_FUSE_RING == 0) ? DN_FUSE_RING : 4;
+    // row pieces: ring of RING k-steps (the maps come from HBM / the far L2).  Eight for the weight-in-LDS form measured
+    // the same (67.5 vs 67.9 us standalone): the loop does not wait for its rows
+    constexpr int RING = 4;
     f32x4 r0[RING][NG], r1[RING][NG];
     auto wload = [&](int ks, int s) {
 #pragma unroll
@@ -275,9 +260,8 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
 #pragma unroll
       for (int g = 0; g < NG; ++g)
         if (g < cnt) {
-          const int kk = (kAbl & 2) ? 0 : ks;
-          r0[s][g] = *reinterpret_cast<const f32x4*>(rows[g].p + kk * rows[g].kss);
-          r1[s][g] = *reinterpret_cast<const f32x4*>(rows[g].p + kk * rows[g].kss + rows[g].r1);
+          r0[s][g] = *reinterpret_cast<const f32x4*>(rows[g].p + ks * rows[g].kss);
+          r1[s][g] = *reinterpret_cast<const f32x4*>(rows[g].p + ks * rows[g].kss + rows[g].r1);
         }
     };
     auto mma = [&](int sw, int sr) {
@@ -285,12 +269,7 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
       for (int g = 0; g < NG; ++g)
         if (g < cnt) {
           half8 fh, fl;
-          if constexpr ((kAbl & 8) != 0) {
-            fh = __builtin_bit_cast(half8, r0[sr][g]);
-            fl = __builtin_bit_cast(half8, r1[sr][g]);
-          } else {
-            frag_from(r0[sr][g], r1[sr][g], fh, fl);
-          }
+          frag_from(r0[sr][g], r1[sr][g], fh, fl);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[g][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[sw][nt], fh, acc[g][nt], 0, 0, 0);
 #pragma unroll
@@ -320,7 +299,6 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
 
   // ---- layers 2-4 on acc (= E + F_k) -> exp(s)
   auto tail = [&](f32x16 (&acc)[4]) -> float {
-    if constexpr ((kAbl & 4) != 0) return acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3];
     f32x16 acc2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
@@ -515,11 +493,6 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
   f32x4 f0[KSW], f1[KSW], y0[2][KSW], y1[2][KSW];
   auto yload = [&](int k, int s) {
     const Row row = row_of(k);
-    if constexpr ((kAbl & 1) != 0) {
-#pragma unroll
-      for (int ks = 0; ks < KSW; ++ks) y0[s][ks] = y1[s][ks] = f32x4{1.f, 2.f, 3.f, (float)k};
-      return;
-    }
 #pragma unroll
     for (int ks = 0; ks < KSW; ++ks) {
       y0[s][ks] = *reinterpret_cast<const f32x4*>(row.p + (ks_first + ks) * row.kss);
@@ -585,7 +558,7 @@ inline size_t w1_bytes(int c) { return (size_t)2 * 4 * (c / 16) * 2 * 2 * 32 * 1
 
 namespace dn { void range_collect_fuse_mlp(unsigned* dst, bool reset, hipStream_t s) { sp_range_collect_here(dst, reset, s); } }
 
-int g_fuse_waves = 0;   // 0 = DN_FUSE_MLP_WAVES, else chosen per launch
+int g_fuse_waves = 0;   // 0 = chosen per launch
 
 // tools / tests: the launch form -- 1 or 4 waves per 32-pixel tile, 2 = the weight-in-LDS form (0 = default)
 extern "C" int dn_fuse_mlp_set_waves(int waves) {
@@ -696,11 +669,9 @@ int fuse_mlp_impl(const float* feat, const float* warped, int warped_fm, const i
   //        share of the agent-sharded step, 87 -> 45 us);
   //   2 -- layer-1 weights staged in LDS once per workgroup of WL tiles (round 5), from 2 tiles per CU up (the BASELINE
   //        size: 640 tiles -> 214 workgroups of three one-wave chains);
-  //   1 -- one wave per tile streaming its weight fragments from L2 (rounds 2-4's form at the BASELINE size; kept for A/B).
-  // DN_FUSE_MLP_WAVES / dn_fuse_mlp_set_waves force a form (tools, tests).
-  static const int waves_env = [] { const char* e = getenv("DN_FUSE_MLP_WAVES"); return e ? atoi(e) : 0; }();
-  const int forced = g_fuse_waves > 0 ? g_fuse_waves : waves_env;
-  const int waves = forced > 0 ? forced : (grid.x < 2u * 256u ? 4 : 2);
+  //   1 -- one wave per tile streaming its weight fragments from L2 (rounds 2-4's form at the BASELINE size).
+  // dn_fuse_mlp_set_waves forces a form (tools, tests).
+  const int waves = g_fuse_waves > 0 ? g_fuse_waves : (grid.x < 2u * 256u ? 4 : 2);
   if (waves == 2) {
     // workgroups of WL tiles so that the launch is one resident generation (one workgroup per CU: 128 KB of LDS at C = 256)
     const int wl = a.total_tiles <= 2 * 256 ? 2 : a.total_tiles <= 3 * 256 ? 3 : 4;

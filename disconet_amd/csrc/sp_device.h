@@ -57,21 +57,14 @@ __device__ inline void note_range(float amax, bool nan_seen = false) {
 }
 // NaN test of four values BEFORE a max / clamp can hide them: two unordered compares (true when either operand is a
 // NaN), the lane masks OR-ed on the scalar unit -- half a VALU instruction per value.
-#ifndef DN_NANCHECK
-#define DN_NANCHECK 0      // conv epilogues: 0 = no test (shipped), 1 = every register quad, 2 = quad 0 of every accumulator tile
-#endif
 __device__ inline void note_nan4(bool& seen, const f32x4 t) {
   seen |= __builtin_isunordered(t[0], t[1]) | __builtin_isunordered(t[2], t[3]);
 }
-// NaN test of a conv epilogue's pre-activation values.  Measured in one lease (profiles/r04_nancheck_ab.txt): every quad
-// costs 1.3 % of the step (3-8 us on each short-K layer), quad 0 of every tile 0.5-1 % -- so the shipped conv epilogues
-// carry NONE.  A NaN cannot appear inside the conv stack out of finite operands (overflow is clamped and flagged):
-// its sources are the parameters (refused when the plan is packed, model.py :: _check_finite_parameters), the inputs
-// (dn_sp_from_nhwc flags them; an occupancy grid cannot hold one) and inf / inf in the attention softmax, which
-// dn_disco_fuse_mlp's output test reports (bit 2).
-__device__ inline void note_nan4_tile(bool& seen, const f32x4 t, int g) {
-  if (DN_NANCHECK == 1 || (DN_NANCHECK == 2 && g == 0)) note_nan4(seen, t);
-}
+// The conv epilogues carry no NaN test of their pre-activation values.  Measured in one lease (profiles/r04_nancheck_ab.txt):
+// testing every quad costs 1.3 % of the step (3-8 us on each short-K layer), quad 0 of every tile 0.5-1 %.  A NaN cannot
+// appear inside the conv stack out of finite operands (overflow is clamped and flagged): its sources are the parameters
+// (refused when the plan is packed, model.py :: _check_finite_parameters), the inputs (dn_sp_from_nhwc flags them; an
+// occupancy grid cannot hold one) and inf / inf in the attention softmax, which dn_disco_fuse_mlp's output test reports (bit 2).
 
 // Stream-ordered readers (no null-stream copy: a hipMemcpyFromSymbol would neither wait for kernels on non-blocking
 // streams nor be legal inside a capture).  One thread ORs this translation unit's word into *dst.
@@ -96,30 +89,17 @@ __device__ __attribute__((always_inline)) inline f32x4 lds_table4(const f32x4* _
   (void)not_p;
   return *p;
 }
-#ifndef DN_EPI_NO_DMA_WAIT
-#define DN_EPI_NO_DMA_WAIT 1   // tools/ab: 0 = round 3's epilogues (their first affine use waits for the next tile's patch DMA)
-#endif
-#if !DN_EPI_NO_DMA_WAIT
-#define lds_table4(p, q) (*(p))
-#endif
 
 // x -> (hi, lo) halves, 4 values -> two dword pairs.  amax: running max |x| of what this lane has split
 // (note_range() reports it once per epilogue).
 // Vector form on purpose: gfx950 has v_cvt_pk_f16_f32 (two fp32 -> packed halves, round to nearest even, the scalar
 // conversion's result) and v_med3_f32 / v_max3_f32 -- 18 VALU instructions per 4 values against ~30 for the
 // element-wise form; every epilogue of the short-K layers runs this for each of its outputs.
-#ifndef DN_RANGECHECK
-#define DN_RANGECHECK 1     // tools/ab: 0 = the splits track no magnitudes (what the range guard costs)
-#endif
 // lo_clamp: the lower clamp bound -- -65504 (a plain split) or 0 (the ReLU of an epilogue rides in the clamp: max(v, 0) then
 // clamp to +-65504 is med3(v, 0, 65504)).  amax is taken from the CLAMPED values: a clamped value is exactly +-65504, which is
 // what note_range() reports as "clamped", and anything a ReLU zeroes must not count.
 // The lo half: v - float(hi) is exact in fp32; v_fma_mix_f32 reads the f16 half of the packed hi pair directly
 // (fma(float(hi), -1, v): the same exact difference) -- one instruction instead of v_cvt_f32_f16 + v_sub_f32.
-// DN_SPLIT_V2 = 0 builds round 3's instruction sequence (tools/ab); the values are identical.
-#ifndef DN_SPLIT_V2
-#define DN_SPLIT_V2 1
-#endif
 template <int HIGH>
 __device__ inline float lo_of_pair(unsigned hpair, float x) {
   float r;
@@ -131,18 +111,12 @@ __device__ inline void split4(const f32x4 v, u32x2& hi, u32x2& lo, float& amax, 
   f32x4 x;
 #pragma unroll
   for (int e = 0; e < 4; ++e) x[e] = __builtin_amdgcn_fmed3f(v[e], lo_clamp, 65504.f);
-#if DN_RANGECHECK
   amax = fmaxf(fmaxf(amax, fabsf(x[0])), fabsf(x[1]));
   amax = fmaxf(fmaxf(amax, fabsf(x[2])), fabsf(x[3]));
-#endif
   const half4 h = __builtin_convertvector(x, half4);
   hi = __builtin_bit_cast(u32x2, h);
-#if DN_SPLIT_V2
   const f32x4 d = {lo_of_pair<0>(hi[0], x[0]), lo_of_pair<1>(hi[0], x[1]), lo_of_pair<0>(hi[1], x[2]), lo_of_pair<1>(hi[1], x[3])};
   const half4 l = __builtin_convertvector(d, half4);
-#else
-  const half4 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), half4);
-#endif
   lo = __builtin_bit_cast(u32x2, l);
 }
 __device__ inline void split4(const f32x4 v, u32x2& hi, u32x2& lo) {
@@ -152,16 +126,9 @@ __device__ inline void split4(const f32x4 v, u32x2& hi, u32x2& lo) {
 // c * scale + shift of four values as two packed fp32 FMAs (v_pk_fma_f32: the IEEE fma of v_fma_f32, two per instruction)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ inline f32x4 affine4(const f32x4 c, const f32x4 sc, const f32x4 sh) {
-#if DN_SPLIT_V2
   const f32x2 a = __builtin_elementwise_fma(f32x2{c[0], c[1]}, f32x2{sc[0], sc[1]}, f32x2{sh[0], sh[1]});
   const f32x2 b = __builtin_elementwise_fma(f32x2{c[2], c[3]}, f32x2{sc[2], sc[3]}, f32x2{sh[2], sh[3]});
   return f32x4{a[0], a[1], b[0], b[1]};
-#else
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = c[e] * sc[e] + sh[e];
-  return v;
-#endif
 }
 __device__ inline f32x4 quad_of(const f32x16& c, int g) { return f32x4{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]}; }
 

@@ -10,9 +10,6 @@
 // (nn.BatchNorm2d / BatchNorm3d in train(), F.relu, torch.exp / div / mul of the fusion
 // loop in upstream:.../det/DiscoNet.py :: forward, loss.py's focal / smooth-L1 losses,
 // torch.optim.Adam).
-#ifndef DN_REDUCE_REVERSE
-#define DN_REDUCE_REVERSE 0      // tools/ab: 1 = the per-channel reductions walk the map from its end (profiles/r06_reduce_reverse_ab.txt)
-#endif
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -88,13 +85,7 @@ __device__ inline void group_channel_sums_v4(int c, long rows_per_group, double*
   const int tx_n = lanes_for(c4n), ty_n = blockDim.x / tx_n;
   const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
   const long chunk = (rows_per_group + gridDim.x - 1) / gridDim.x;
-#if DN_REDUCE_REVERSE
-  // tools/ab: the workgroups take their row chunks from the END of the map first (what the producer wrote last), same partial slots
-  const unsigned lb = gridDim.x - 1 - blockIdx.x;
-#else
-  const unsigned lb = blockIdx.x;
-#endif
-  const long r0 = lb * chunk;
+  const long r0 = blockIdx.x * chunk;
   const long r1 = r0 + chunk < rows_per_group ? r0 + chunk : rows_per_group;
   for (int c4 = tx; c4 < c4n; c4 += tx_n) {
     double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
@@ -132,7 +123,7 @@ __device__ inline void group_channel_sums_v4(int c, long rows_per_group, double*
     }
   }
   __syncthreads();
-  double* out = part_g + (size_t)lb * NQ * c;
+  double* out = part_g + (size_t)blockIdx.x * NQ * c;
   for (int i = threadIdx.x; i < NQ * c; i += blockDim.x) {
     const int q = i / c, cc = i % c;
     double t = 0.0;
@@ -327,22 +318,18 @@ __global__ void bn_update_running_kernel(const float* __restrict__ mean, const f
 // (lane l adds blocks l, l + 64, ...; xor butterfly): the same sums bit for bit, then the finish arithmetic of the kernel it
 // replaces -- bn_stats_finalize_kernel (+ optionally bn_update_running_kernel: one group), bn_param_grad_kernel (one group),
 // channel_sum_finalize_kernel.
-// DN_FOLD_BATCH: partials a lane fetches before it adds them (in the same order: the same bits).  With one load per iteration a
+// FOLD_BATCH: partials a lane fetches before it adds them (in the same order: the same bits).  With one load per iteration a
 // lane's up to 16 partials were 16 L2 round trips in a row: 7-11 us per launch, 72 launches per step (profiles/r06_fold_batch_ab.txt).
-#ifndef DN_FOLD_BATCH
-#define DN_FOLD_BATCH 8
-#endif
+constexpr int FOLD_BATCH = 8;
 __device__ inline double fold_one(const double* __restrict__ p, int n_blocks, size_t stride, int lane) {
   double t = 0.0;
   int b = lane;
-  if constexpr (DN_FOLD_BATCH > 1) {
-    for (; b + 64 * (DN_FOLD_BATCH - 1) < n_blocks; b += 64 * DN_FOLD_BATCH) {
-      double v[DN_FOLD_BATCH];
+  for (; b + 64 * (FOLD_BATCH - 1) < n_blocks; b += 64 * FOLD_BATCH) {
+    double v[FOLD_BATCH];
 #pragma unroll
-      for (int u = 0; u < DN_FOLD_BATCH; ++u) v[u] = p[(size_t)(b + 64 * u) * stride];
+    for (int u = 0; u < FOLD_BATCH; ++u) v[u] = p[(size_t)(b + 64 * u) * stride];
 #pragma unroll
-      for (int u = 0; u < DN_FOLD_BATCH; ++u) t += v[u];
-    }
+    for (int u = 0; u < FOLD_BATCH; ++u) t += v[u];
   }
   for (; b < n_blocks; b += 64) t += p[(size_t)b * stride];
 #pragma unroll
@@ -354,19 +341,17 @@ __device__ inline void fold_two(const double* __restrict__ p0, const double* __r
                                 double& t0, double& t1) {
   double a = 0.0, c = 0.0;
   int b = lane;
-  if constexpr (DN_FOLD_BATCH > 1) {
-    for (; b + 64 * (DN_FOLD_BATCH - 1) < n_blocks; b += 64 * DN_FOLD_BATCH) {
-      double v[DN_FOLD_BATCH], w[DN_FOLD_BATCH];
+  for (; b + 64 * (FOLD_BATCH - 1) < n_blocks; b += 64 * FOLD_BATCH) {
+    double v[FOLD_BATCH], w[FOLD_BATCH];
 #pragma unroll
-      for (int u = 0; u < DN_FOLD_BATCH; ++u) {
-        v[u] = p0[(size_t)(b + 64 * u) * stride];
-        w[u] = p1[(size_t)(b + 64 * u) * stride];
-      }
+    for (int u = 0; u < FOLD_BATCH; ++u) {
+      v[u] = p0[(size_t)(b + 64 * u) * stride];
+      w[u] = p1[(size_t)(b + 64 * u) * stride];
+    }
 #pragma unroll
-      for (int u = 0; u < DN_FOLD_BATCH; ++u) {
-        a += v[u];
-        c += w[u];
-      }
+    for (int u = 0; u < FOLD_BATCH; ++u) {
+      a += v[u];
+      c += w[u];
     }
   }
   for (; b < n_blocks; b += 64) {
@@ -1124,20 +1109,12 @@ bool vec4_ok(int c, std::initializer_list<int> lds, std::initializer_list<const 
 }
 
 // Workgroups of a per-channel reduction over all groups.  1024 since round 5 (2048 before): measured in one lease
-// (tools/r05_reduce_blocks.sh, profiles/r05_reduce_blocks.txt) the folds of a training step cost 0.69 / 0.48 / 0.36 ms at 2048 / 1024 /
-// 512 and the reductions themselves 2.13 / 2.02 / 2.64 ms -- four workgroups per CU still saturate the HBM, two do not.
-// DN_REDUCE_BLOCKS overrides (tools).
-int reduce_blocks_total() {
-  static const int n = [] {
-    const char* e = getenv("DN_REDUCE_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return v >= 64 && v <= 8192 ? v : 1024;
-  }();
-  return n;
-}
+// (profiles/r05_reduce_blocks.txt) the folds of a training step cost 0.69 / 0.48 / 0.36 ms at 2048 / 1024 / 512 and the
+// reductions themselves 2.13 / 2.02 / 2.64 ms -- four workgroups per CU still saturate the HBM, two do not.
+constexpr int kReduceBlocks = 1024;
 int blocks_per_group(long rows_per_group, int n_groups) {
   // ~1024 workgroups over all groups, at least 64 rows each
-  long b = reduce_blocks_total() / n_groups;
+  long b = kReduceBlocks / n_groups;
   if (b > rows_per_group / 64) b = rows_per_group / 64;
   return (int)(b < 1 ? 1 : b);
 }
@@ -1153,14 +1130,11 @@ extern "C" size_t dn_reduce_workspace_bytes(int n_groups, long rows_per_group, i
 // workspace of the fused bias gradient of dn_bn_train_backward_finish_bias: [c] folded sums + one double per (workgroup of
 // the apply launch, channel)
 // workgroups of the apply launch when it also leaves the bias partials: every workgroup is one row of partials for the fold
-// (one wavefront per channel walks them), so fewer than the plain launch's 8192 (DN_BN_BIAS_BLOCKS: tools)
-static int bias_blocks_cap() {
-  static const int cap = [] { const char* e = getenv("DN_BN_BIAS_BLOCKS"); const int v = e ? atoi(e) : 1024; return v < 64 ? 64 : (v > 8192 ? 8192 : v); }();
-  return cap;
-}
+// (one wavefront per channel walks them), so fewer than the plain launch's 8192
+constexpr int kBiasBlocks = 1024;
 extern "C" size_t dn_bn_bias_workspace_bytes(long rows, int c) {
   if (rows <= 0 || c <= 0) return 0;
-  return sizeof(double) * (size_t)c * (size_t)(1 + grid_for(rows * (long)c / 4, bias_blocks_cap()));
+  return sizeof(double) * (size_t)c * (size_t)(1 + grid_for(rows * (long)c / 4, kBiasBlocks));
 }
 
 // Two-phase forms (round 5: agent-parallel training, sharded.py).  A rank that holds only SOME images of a BatchNorm batch
@@ -1368,7 +1342,7 @@ int bn_backward_finish_impl(const float* dy_a, int ld_a, int up_a, const float* 
   // the fused bias gradient (round 6): the apply launch leaves one double per (workgroup, channel), folded in a fixed order
   auto bias_launch = [&](auto sp_c, void* sp_ptr, float lift, unsigned* fl, int fsh) -> int {
     constexpr bool SPF = decltype(sp_c)::value;
-    const int blocks = grid_for(total / 4, bias_blocks_cap());
+    const int blocks = grid_for(total / 4, kBiasBlocks);
     DN_REQUIRE(bias_ws && bias_ws_bytes >= dn_bn_bias_workspace_bytes(rows_per_group, c),
                "bn backward: bias workspace of %zu bytes, dn_bn_bias_workspace_bytes() asks for %zu", bias_ws_bytes,
                dn_bn_bias_workspace_bytes(rows_per_group, c));
@@ -1607,8 +1581,7 @@ extern "C" int dn_det_loss(const float* cls, const float* labels, const float* l
   if (dn::zero_fill(losses, 2 * sizeof(double), s) != hipSuccess)
     return dn::fail(DN_ERR_LAUNCH, "det loss: memset failed");
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  static const bool legacy = [] { const char* e = getenv("DN_DET_LOSS_LEGACY"); return e && e[0] == '1'; }();
-  if (!legacy && n % 2 == 0 && (n * code) % 4 == 0 && al16(cls) && al16(labels) && al16(loc) && al16(targets) && al16(dcls) && al16(dloc))
+  if (n % 2 == 0 && (n * code) % 4 == 0 && al16(cls) && al16(labels) && al16(loc) && al16(targets) && al16(dcls) && al16(dloc))
     hipLaunchKernelGGL(det_loss_v4_kernel, dim3(grid_for(n * code / 4, 4096)), dim3(256), 0, s, cls, labels, loc, targets,
                        mask, n, code, alpha, gamma, sigma, 1.f / norm, losses, dcls, dloc);
   else

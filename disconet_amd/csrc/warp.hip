@@ -286,10 +286,7 @@ warp_gather1_kernel(const float* __restrict__ d_out1, const float* __restrict__ 
 // pass2_taps of the same integers), a ballot gives the hits, and the hits are added in ascending candidate order -- the order of the
 // loops above -- four rows in flight at a time.  Deterministic like them; against them the sums agree to a few ulp, not bit for bit
 // (the compiler contracts the tap arithmetic per kernel: weights differ in their last bit).  PIXW: output pixels per wave.
-#ifndef DN_GATHER_PIXW
-#define DN_GATHER_PIXW 1
-#endif
-constexpr int GATHER_PIXW = DN_GATHER_PIXW;
+constexpr int GATHER_PIXW = 1;
 struct GatherHits {
   unsigned long long mask;
   float wt;
@@ -423,9 +420,6 @@ warp_gather1_lanes_kernel(const float* __restrict__ d_out1, const float* __restr
 constexpr int WT = 8, WQ = WT + 2, WCS = 64;
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 typedef int i32x4w __attribute__((ext_vector_type(4)));
-#ifndef DN_WARP_SHARED_TAPS
-#define DN_WARP_SHARED_TAPS 1   // 0: round 3's form (every lane derives its pixel's tap sets), for A/B builds
-#endif
 
 __global__ void __launch_bounds__(256)
 warp_neighbors_tiled_kernel(const float* __restrict__ feat, const float* __restrict__ trans,
@@ -465,7 +459,6 @@ warp_neighbors_tiled_kernel(const float* __restrict__ feat, const float* __restr
   const float r00 = m[0], r01 = m[1], r10 = m[4], r11 = m[5];
   const float x_trans = (4.f * m[3]) / 128.f;
   const float y_trans = -(4.f * m[7]) / 128.f;
-#if DN_WARP_SHARED_TAPS
   // The tap sets depend on the pixel only, and sixteen lanes share a pixel: computed ONCE per pixel into LDS (clamped byte
   // offsets / LDS rows and validity-masked weights, the expressions of sample_src and of the blend below), then every lane
   // does loads and FMAs only.  Round 3's form re-derived them in every lane: 1290 VALU instructions per wave, half of the
@@ -550,45 +543,6 @@ warp_neighbors_tiled_kernel(const float* __restrict__ feat, const float* __restr
     for (int k = 0; k < 4; ++k) acc += rot[row[k]][l] * wt[k];
     *reinterpret_cast<f32x4*>(out_of(py * w + px)) = acc;
   }
-#else
-  // north-west q of the tile: the smallest x0(p) - (p - tile origin) over the tile's columns / rows
-  int qx_base = 1 << 30, qy_base = 1 << 30;
-#pragma unroll
-  for (int k = 0; k < WT; ++k) {
-    const Bilinear t = bilinear_taps((2.f * (tile_x0 + k) + 1.f) / w - 1.f + x_trans,
-                                     (2.f * (tile_y0 + k) + 1.f) / h - 1.f + y_trans, w, h);
-    qx_base = min(qx_base, t.x0 - k);
-    qy_base = min(qy_base, t.y0 - k);
-  }
-  // pass 1 (rotation) of the tile's q block
-  for (int idx = tid; idx < WQ * WQ * 16; idx += 256) {
-    const int q = idx >> 4;
-    const int qx = qx_base + q % WQ, qy = qy_base + q / WQ;
-    const float qbx = (2.f * qx + 1.f) / w - 1.f;
-    const float qby = (2.f * qy + 1.f) / h - 1.f;
-    const Bilinear t1 = bilinear_taps(r00 * qbx + r01 * qby, r10 * qbx + r11 * qby, w, h);
-    rot[q][l] = sample_src(src, t1, w, h, c, slice * (WCS / 4) + l);
-  }
-  __syncthreads();
-  // pass 2 (translation): blend the four q of every output pixel
-  for (int pl = tid >> 4; pl < WT * WT; pl += 16) {
-    const int px = tile_x0 + pl % WT, py = tile_y0 + pl / WT;
-    if (px >= w || py >= h) continue;
-    const float bx = (2.f * px + 1.f) / w - 1.f;
-    const float by = (2.f * py + 1.f) / h - 1.f;
-    const Bilinear t2 = bilinear_taps(bx + x_trans, by + y_trans, w, h);
-    const float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
-      const bool qok = qx >= 0 && qx < w && qy >= 0 && qy < h;
-      const int lx = min(max(qx - qx_base, 0), WQ - 1), ly = min(max(qy - qy_base, 0), WQ - 1);
-      acc += rot[ly * WQ + lx][l] * (qok ? qw[k] : 0.f);
-    }
-    *reinterpret_cast<f32x4*>(out_of(py * w + px)) = acc;
-  }
-#endif
 }
 
 }  // namespace
@@ -666,8 +620,7 @@ int warp_neighbors_impl(const float* feat, const float* trans, const int32_t* nu
              "warp: ego range [%d, %d) outside 0..%d", ego_first, ego_first + ego_count, agents);
   if (agents < 2) return DN_OK;   // no neighbours to warp
   const int hw = h * w;
-  static const int tiled_env = [] { const char* e = getenv("DN_WARP_TILED"); return e ? atoi(e) : 1; }();
-  if ((tiled_env || fm) && c % WCS == 0) {
+  if (c % WCS == 0) {
     const int tiles_x = (w + WT - 1) / WT, tiles_y = (h + WT - 1) / WT;
     dim3 tgrid(tiles_x * tiles_y * (c / WCS), agents - 1, batch * ego_count);
     hipLaunchKernelGGL(warp_neighbors_tiled_kernel, tgrid, dim3(256), 0, (hipStream_t)stream, feat, trans,

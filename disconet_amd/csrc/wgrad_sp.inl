@@ -304,15 +304,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradSpArgs
 // j = 0..16: tap columns 0 and 2) and E (columns 2 (ox0 + j), j = 0..15: tap column 1), 9 + 8 pixel pairs per row.  Tap column 0
 // reads O pairs 4 kb .. 4 kb + 3, tap column 1 the same E pairs, tap column 2 is O one entry on: v_alignbit of neighbouring dwords,
 // as tap column 1 of the stride-1 kernel.  Output row r sees patch rows 2 r + ty.  The patch of a tile is ~4 x the stride-1 kernel's
-// per output pixel, so the tiles are short: CB = 64: DN_WSP_S2_TH64 x 16 outputs (3 patch rows at 1), the four waves = the four quadrants;
+// per output pixel, so the tiles are short: CB = 64: 1 x 16 outputs (3 patch rows), the four waves = the four quadrants;
 // CB = 32: 4 x 16 outputs (9 patch rows), one output row per wave, fixed-order LDS sum at the end.  No upsample / concat (the
 // stride-2 layers have one source).
-#ifndef DN_WSP_S2_TH64
-#define DN_WSP_S2_TH64 1          // output rows per tile of the CB = 64 stride-2 kernel; 2 (58 KB of LDS, 255 VGPRs) measured equal: profiles/r06_wgrad_s2_tile.txt
-#endif
 template <int CB>
 struct WspShape2 {
-  static constexpr int TH = CB == 64 ? DN_WSP_S2_TH64 : 4, TW = 16, PH = 2 * TH + 1;
+  // output rows per tile: at CB = 64, 2 (58 KB of LDS, 255 VGPRs) measured equal to 1 (profiles/r06_wgrad_s2_tile.txt)
+  static constexpr int TH = CB == 64 ? 1 : 4, TW = 16, PH = 2 * TH + 1;
   static constexpr int ROWS = CB == 64 ? TH : 1;                    // output rows each wave walks (CB = 32: one row per wave)
   static constexpr int QN = CB / 4;
   static constexpr int RP = 17;                                     // pixel pairs per patch row: 9 of plane O, 8 of plane E

@@ -124,14 +124,9 @@ _DUPLICATE_BACKBONE_KEY = re.compile(
     r"|com_compresser|bn_compress|com_decompresser|bn_decompress)\." + _TENSORS + r")$")
 
 
-# K-sliced layers of the detector (SURVEY.md 8 a3 / a8 names).  DN_SP_KSLICES=all slices every deep layer (A/B runs);
-# the default is the one layer where it pays in both regimes: conv5_1, 48 chunks of K on 640 tiles
-_KSLICES_ALL = {"conv3_2": 4, "conv4_1": 4, "conv4_2": 4, "conv5_1": 4, "conv5_2": 4, "conv6_1": 4}
+# K-sliced layers of the detector (SURVEY.md 8 a3 / a8 names): the one layer where it pays in both regimes
+# (DESIGN.md 3.1d): conv5_1, 48 chunks of K on 640 tiles
 _KSLICES = {"conv5_1": 4}
-
-
-def _ks_enabled():
-    return os.environ.get("DN_SP_KSLICES", "1") != "0"
 
 
 class _ConvLayer:
@@ -149,8 +144,7 @@ class _ConvLayer:
         # K slices of the layer (SP engine; include/disconet_hip.h :: dn_spconv2d_ks): a property of the LAYER, never of
         # the batch -- the deep layers, whose launches are a round and a quarter on the chip at the BASELINE batch and
         # fewer tiles than CUs on an agent-sharded rank
-        table = _KSLICES_ALL if os.environ.get("DN_SP_KSLICES", "1") == "all" else _KSLICES
-        self.kslices = table.get(name, 1) if (math == 2 and _ks_enabled()) else 1
+        self.kslices = _KSLICES.get(name, 1) if math == 2 else 1
         c_out = weight.shape[0]
         c_in = weight.shape[1]
         if up_split is not None and math == 2:
@@ -204,7 +198,7 @@ class _ConvLayer:
             src0, src1 = ops.as_sp(src0), (ops.as_sp(src1) if src1 is not None else None)
             # executed MFMA work: 3 products per MAC (hi*hi, hi*lo, lo*hi); the tap-merged kernel (conv_spq.hip: 3x3 over a
             # nearest-upsampled first source) runs 4 merged taps instead of 9 on that source's chunks
-            taps0 = {2: 4, 1: 6}.get(ops.sp_upmode(), 9) if (up0 and self.ksize == 3 and self.stride == 1) else self.ksize ** 2
+            taps0 = 4 if (up0 and self.ksize == 3 and self.stride == 1) else self.ksize ** 2
             xflops = 3.0 * 2.0 * n * ho * wo * self.c_out * (taps0 * c0 + self.ksize ** 2 * c1)
             with region(self.name, "conv_sp_kernel", flops, nbytes, exec_flops=xflops):
                 dual = nhwc_copy and not up0 and self.c_out % 4 == 0
@@ -585,7 +579,7 @@ class DiscoNet(nn.Module):
                              device=feat.device)
         # the one-launch attention kernel takes the warped maps in its own (fragment-major) read order when the shape
         # allows: an opaque intermediate between the two launches (include/disconet_hip.h :: dn_warp_neighbors_fm)
-        fm = ("_fuse_mlp" in P and os.environ.get("DN_FUSE_FM", "1") != "0" and A > 1 and ops.warp_fm_supported(h, w, c))
+        fm = ("_fuse_mlp" in P and A > 1 and ops.warp_fm_supported(h, w, c))
         with region("warp", "warp_neighbors_kernel", 0.0, map_bytes * (n + pairs)):
             ops.warp_neighbors(feat, trans_matrices, num_agent, B, A, self.only_v2i,
                                ego_first, E, out=warped, fm=fm)

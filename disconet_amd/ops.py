@@ -385,18 +385,6 @@ def drain_sp_range():
     _range_guard.drain()
 
 
-def sp_upmode():
-    """The process's up-conv form as the library reads it (csrc/conv_sp.hip :: sp_upmode): DN_SP_UPMERGE, default 2 = the
-    row- and column-merged kernel (4 of 9 taps on the upsampled source), 1 = row-merged (6 of 9), 0 = plain taps.
-    (dn_spconv_set_upmode() overrides are a tools / test matter and not mirrored here: this only feeds the executed-work
-    figure of the profiling regions.)"""
-    import os
-    try:
-        return int(os.environ.get("DN_SP_UPMERGE", "2"))
-    except ValueError:
-        return 2
-
-
 def as_sp(x):
     return x if isinstance(x, SpTensor) else SpTensor.from_nhwc(x)
 
@@ -519,11 +507,9 @@ def sp_conv2d(d, src0, packed, scale, shift, src1=None, out=None, nhwc_copy=Fals
     flat = torch.empty((d.n_images, ho, wo, d.c_out), dtype=torch.float32, device=src0.device) if nhwc_copy else None
     p1 = _ptr(src1.data) if src1 is not None else None
     if kslices > 1 and not lib.dn_spconv_ks_supported(ctypes.byref(d), kslices):
-        kslices = 1      # the process's up-conv form (DN_SP_UPMERGE=1) or a short layer has no K-sliced form: run whole
+        kslices = 1      # the process's up-conv form (dn_spconv_set_upmode(1)) or a short layer has no K-sliced form: run whole
     if kslices > 1:
         nbytes = min(int(lib.dn_spconv_workspace_bytes(ctypes.byref(d), kslices)), _KS_WORKSPACE_CAP)
-        if os.environ.get("DN_SP_KS_NOSPLIT", "0") == "1":      # A/B runs: every tile whole (the slices folded in registers)
-            nbytes = 0
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=src0.device)
         check(lib.dn_spconv2d_ks(ctypes.byref(d), kslices, _ptr(src0.data), p1, _ptr(packed), _ptr(scale), _ptr(shift),
                                  _ptr(out.data), _ptr(flat), d.c_out if nhwc_copy else 0, _ptr(ws) if nbytes else None, nbytes,

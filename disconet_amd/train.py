@@ -410,8 +410,7 @@ class TrainEngine:
         z, d = self._conv(w, b, src0, src1, up0, lay.stride, lay.ksize)
         # one process, one group, the layer's own BatchNorm: the running-statistics update rides in the statistics' finish launch
         # (the momentum updates of different BatchNorms touch different buffers: their order is free)
-        fused_running = (lay.bn is not None and groups == 1 and (self.shard is None or self.shard.world == 1)
-                         and os.environ.get("DN_BN_FUSED_RUNNING", "1") != "0")
+        fused_running = lay.bn is not None and groups == 1 and (self.shard is None or self.shard.world == 1)
         mean, var = T.bn_stats(z, groups, running=(lay.bn.running_mean, lay.bn.running_var, _MOMENTUM) if fused_running else None,
                                **self._bn_sync(z, groups))
         gamma = lay.bn.weight if gamma is None else gamma
@@ -497,8 +496,7 @@ class TrainEngine:
         if (self.dgrad_math != "sp" or not need_dx or d.ksize != 3 or c["groups"] != 1
                 or d.c_out % 16 != 0 or (d.c0 + d.c1) % 4 != 0):
             return None, None
-        if d.stride != 1 and not (s2d_ok and d.stride == 2 and d.c1 == 0 and not d.up0 and d.h_in % 2 == 0 and d.w_in % 2 == 0
-                                  and os.environ.get("DN_DGRAD_S2D", "1") != "0"):
+        if d.stride != 1 and not (s2d_ok and d.stride == 2 and d.c1 == 0 and not d.up0 and d.h_in % 2 == 0 and d.w_in % 2 == 0):
             return None, None       # (a stride-2 layer: only as the one-launch space-to-depth form, where the caller can take it)
         ent = self._dz_lift.get(lay.name)
         if ent is None:
@@ -578,8 +576,7 @@ class TrainEngine:
             ops.sp_conv2d_nhwc(dd, dz_sp, packed, self._const(dev, n_in, 1.0 / (dz_lift * wmul)), self._const(dev, n_in, 0.0),
                                dx_out)
             return dx_out
-        if (d.stride == 2 and d.ksize == 3 and d.h_in % 2 == 0 and d.w_in % 2 == 0
-                and os.environ.get("DN_DGRAD_PARITY", "1") != "0"):
+        if d.stride == 2 and d.ksize == 3 and d.h_in % 2 == 0 and d.w_in % 2 == 0:
             # parity-phase form: four stride-1 convs over dz of 1 / 2 / 2 / 4 taps, each writing one parity class of dx
             # (include/disconet_train.h :: dn_conv_dgrad_class_weights) -- a quarter of the zero-stuffed form's MFMAs
             n_in = (w4.shape[1] - ci_first) if c_in is None else c_in

@@ -190,8 +190,7 @@ def bn_backward_bias_supported(z, n_groups=1):
     """can bn_backward(..., dbias=...) fuse the conv bias gradient (sum of dz per channel) into its apply launch?"""
     c = z.shape[-1]
     return (z.dim() == 4 and n_groups == 1 and c % 4 == 0 and ((c // 4) & (c // 4 - 1)) == 0 and c <= 1024
-            and z.numel() // 4 < (1 << 31) and os.environ.get("DN_BN_LEGACY", "0") != "1"
-            and os.environ.get("DN_BN_FUSED_BIAS", "1") != "0")
+            and z.numel() // 4 < (1 << 31) and os.environ.get("DN_BN_LEGACY", "0") != "1")
 
 
 def bn_backward(dy_a, y, z, mean, var, gamma, eps, dgamma, dbeta, relu=True, dy_b=None, up_a=False,

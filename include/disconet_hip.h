@@ -28,8 +28,9 @@
  *   - return 0 on success, negative on error; dn_last_error() returns a
  *     thread-local message for the last failing call on this thread;
  *   - re-entrant.  Process-wide state is limited to launch-time caches filled on first use
- *     (kernel attributes / occupancy per instantiation) and the tools-only knobs
- *     dn_spconv_force_config() and the DN_* environment variables read once.
+ *     (kernel attributes / occupancy per instantiation), the tools-only hooks dn_spconv_force_config(),
+ *     dn_spconv_set_upmode() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
+ *     DN_WARP_GATHER_LEGACY (environment, read once: the other side of a bitwise / agreement test).
  */
 #ifndef DISCONET_HIP_H
 #define DISCONET_HIP_H
@@ -288,7 +289,7 @@ int dn_spconv2d(const dn_conv_desc* d, const void* src0_sp, const void* src1_sp,
  * (dn_spconv_set_upmode(1)), layers with fewer chunks than slices. */
 size_t dn_spconv_workspace_bytes(const dn_conv_desc* d, int kslices);
 /* 1 if the layer can run with `kslices` canonical K slices (1, 2 or 4) in this process -- 3x3, no hi-only / bit-grid
- * source, not the row-merged up-conv image (DN_SP_UPMERGE=1), at least `kslices` 16-channel chunks -- else 0.  Depends on
+ * source, not the row-merged up-conv image (dn_spconv_set_upmode(1)), at least `kslices` 16-channel chunks -- else 0.  Depends on
  * the layer and the process-wide up-conv form only, never on the batch. */
 int dn_spconv_ks_supported(const dn_conv_desc* d, int kslices);
 int dn_spconv2d_ks(const dn_conv_desc* d, int kslices, const void* src0, const void* src1, const void* packed,
@@ -338,8 +339,7 @@ int dn_spconv2d_post1x1(const dn_conv_desc* d, const dn_post1x1_desc* p, const v
  * applies to the layer, -1 = automatic selection.  Process-wide, not thread-safe. */
 int dn_spconv_force_config(int cfg);
 /* tools only: form of the packed image / kernel of layers whose first source is upsampled: 0 = plain taps,
- * 1 = row-merged, 2 = row- and column-merged per parity class (default), -1 = the DN_SP_UPMERGE
- * environment value.  Process-wide; weights packed under one mode must run under the same mode. */
+ * 1 = row-merged, 2 = row- and column-merged per parity class, -1 = the default (2).  Process-wide; weights packed under one mode must run under the same mode. */
 int dn_spconv_set_upmode(int mode);
 
 /* ------------------------------------------------------------------------
@@ -421,8 +421,8 @@ int dn_fuse_mlp_supported(int c);
 /* tools / tests only: the launch form of dn_disco_fuse_mlp -- 4 (the ego term, the list slots and the channels of the
  * weighted sum of a 32-pixel tile split over four waves: launches of fewer than 512 tiles), 2 (round 5: one wave per
  * tile, workgroups of 2-4 tiles that stage the layer-1 weights in LDS once: 512 tiles and more) or 1 (one wave per
- * tile streaming its weight fragments from L2: rounds 2-4's form for large launches, kept for A/B);
- * 0 = chosen per launch unless DN_FUSE_MLP_WAVES is set.  All forms give bit-identical results.
+ * tile streaming its weight fragments from L2: rounds 2-4's form for large launches);
+ * 0 = chosen per launch (the default).  All forms give bit-identical results.
  * Process-wide, not thread-safe. */
 int dn_fuse_mlp_set_waves(int waves);
 size_t dn_fuse_mlp_packed_bytes(int c);

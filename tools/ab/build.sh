@@ -5,7 +5,7 @@
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd); C=$R/disconet_amd/csrc
 # tools/ab/build.sh FLAGS name "<extra hipcc flags>"  builds tools/ab/FLAGS_name with those flags instead of a macro
-FILES=${AB_FILES:-"conv_sp conv_spq fuse_mlp"}     # AB_FILES="warp" tools/ab/build.sh DN_WARP_SHARED_TAPS 0 1
+FILES=${AB_FILES:-"conv_sp conv_spq fuse_mlp"}     # AB_FILES="conv_sp conv_spq" tools/ab/build.sh DN_SP_ABL 1
 M=$1; shift
 if [ "$M" = FLAGS ]; then set -- "$1:$2"; fi
 for v in "$@"; do

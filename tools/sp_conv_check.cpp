@@ -206,16 +206,19 @@ static void run_layer(const char* name, int n, int h, int w, int c0, int c1, int
   HCK(hipMalloc(&pk, dn_spconv_packed_weight_bytes(&d)));
   CK(dn_spconv_pack_weights(&d, wt, wmul, pk, 0));
   std::vector<int> cfgs = {-1};
+  // SPCHECK_ABL=1 with a -DDN_SP_ABL=1 library: the timing-only ablations outside the shipped build (tiles 23-25, 101-207, 400-407)
+  const bool abl = g_mode == 2 && getenv("SPCHECK_ABL") && atoi(getenv("SPCHECK_ABL"));
   if (up0 && upmode == 2) {
     printf(" [quad]");
     cfgs.insert(cfgs.end(), {20, 21, 22});
-    if (g_mode == 2) cfgs.insert(cfgs.end(), {23, 24, 25});   // timing only: no weight DMA / no patch DMA / neither
+    if (abl) cfgs.insert(cfgs.end(), {23, 24, 25});   // timing only: no weight DMA / no patch DMA / neither
   } else if (!quick) {
     if (ks == 1) cfgs.insert(cfgs.end(), {6, 7});
     else if (stride == 2) cfgs.insert(cfgs.end(), {4, 5, 15, 16});
     else cfgs.insert(cfgs.end(), {0, 1, 2, 3, 8, 9, 10, 12, 13, 14});
-    if (g_mode == 2 && ks == 3 && stride == 2 && getenv("SPCHECK_S2_ABL")) cfgs.insert(cfgs.end(), {400, 401, 402, 403, 404, 405, 407});   // a -DDN_S2_ABL=1 library
-    if (g_mode == 2 && ks == 3 && stride == 1) cfgs.insert(cfgs.end(), {101, 102, 103, 104, 105, 201, 202, 203, 204, 205, 206, 207, 301, 302, 303, 304, 305});
+    if (abl && ks == 3 && stride == 2) cfgs.insert(cfgs.end(), {400, 401, 402, 403, 404, 405, 407});
+    if (abl && ks == 3 && stride == 1) cfgs.insert(cfgs.end(), {101, 102, 103, 104, 105, 201, 202, 203, 204, 205, 206, 207});
+    if (g_mode == 2 && ks == 3 && stride == 1) cfgs.insert(cfgs.end(), {301, 302, 303, 304, 305});
   }
   if (!g_only_cfgs.empty()) {
     std::vector<int> keep;
