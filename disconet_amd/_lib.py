@@ -186,6 +186,7 @@ SIGNATURES = {
                                                           c_void_p]),
     "dn_channel_sum_partial": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, POINTER(c_int), c_void_p]),
     "dn_channel_sum_fold_multi": (c_int, [POINTER(FoldJob), c_int, c_void_p]),
+    "dn_bn_train_form_supported": (c_int, [c_int, c_int, c_long, c_int]),
     "dn_bn_train_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                   c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
     "dn_bn_train_apply_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_long, c_int, c_int,

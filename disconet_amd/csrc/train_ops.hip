@@ -1080,20 +1080,6 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
-// DN_BN_LEGACY=1: the general apply kernels and one row per iteration in the reductions (tests: the bitwise A/B; tools)
-bool bn_legacy() {
-  static const bool legacy = [] { const char* e = getenv("DN_BN_LEGACY"); return e && e[0] == '1'; }();
-  return legacy;
-}
-// the one-group fast kernels (bn_apply_v4_fast_kernel, bn_bwd_apply_v4_fast_kernel): log2(c / 4) when they apply, else -1
-int bn_fast_shift(int n_groups, int c, long total) {
-  const int c4n = c >> 2;
-  if (bn_legacy() || n_groups != 1 || c % 4 != 0 || c > kMaxC || c4n <= 0 || (c4n & (c4n - 1)) != 0 || total / 4 >= (1L << 31)) return -1;
-  int sh = 0;
-  while ((1 << sh) < c4n) ++sh;
-  return sh;
-}
-
 int grid_for(long total, int cap = 4096) {
   const long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -1108,6 +1094,34 @@ bool vec4_ok(int c, std::initializer_list<int> lds, std::initializer_list<const 
   return true;
 }
 
+// DN_BN_LEGACY=1: the general apply kernels and one row per iteration in the reductions (tests: the bitwise A/B; tools)
+bool bn_legacy() {
+  static const bool legacy = [] { const char* e = getenv("DN_BN_LEGACY"); return e && e[0] == '1'; }();
+  return legacy;
+}
+
+// the one-group fast kernels (bn_apply_v4_fast_kernel, bn_bwd_apply_v4_fast_kernel): log2(c / 4) where they take the shape,
+// else -1.  DN_BN_LEGACY=1 gives their shapes to the general kernels -- not the SP apply's (honour_legacy false): no general twin
+int bn_fast_shift(int n_groups, long rows_per_group, int c, bool honour_legacy = true) {
+  const int c4n = c >> 2;
+  if ((honour_legacy && bn_legacy()) || n_groups != 1 || rows_per_group <= 0 || c % 4 != 0 || c > kMaxC || c4n <= 0 ||
+      (c4n & (c4n - 1)) != 0 || rows_per_group * c / 4 >= (1L << 31))
+    return -1;
+  int sh = 0;
+  while ((1 << sh) < c4n) ++sh;
+  return sh;
+}
+
+// The kernels a BatchNorm pass runs: the general ones (any c, stride, alignment), the float4 ones (c % 4 == 0, 16-byte aligned
+// strides and tensors) or, of those, the one-group fast ones (`shift`: bn_fast_shift).  A reduction runs float4 unless general.
+enum class BnKernels { general, vec4, fast };
+struct BnForm { BnKernels k; int shift; };
+BnForm bn_form(int n_groups, long rows_per_group, int c, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
+  if (!vec4_ok(c, lds, ptrs)) return {BnKernels::general, -1};
+  const int sh = bn_fast_shift(n_groups, rows_per_group, c);
+  return {sh >= 0 ? BnKernels::fast : BnKernels::vec4, sh};
+}
+
 // Workgroups of a per-channel reduction over all groups.  1024 since round 5 (2048 before): measured in one lease
 // (profiles/r05_reduce_blocks.txt) the folds of a training step cost 0.69 / 0.48 / 0.36 ms at 2048 / 1024 / 512 and the
 // reductions themselves 2.13 / 2.02 / 2.64 ms -- four workgroups per CU still saturate the HBM, two do not.
@@ -1117,6 +1131,71 @@ int blocks_per_group(long rows_per_group, int n_groups) {
   long b = kReduceBlocks / n_groups;
   if (b > rows_per_group / 64) b = rows_per_group / 64;
   return (int)(b < 1 ? 1 : b);
+}
+
+// phase 1 of the statistics: every workgroup's partial sums, [n_groups][*nblk][2 c] doubles behind the [n_groups][2 c] folded
+// sums at the start of `sums`
+int bn_stats_reduce(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
+                    int* nblk, hipStream_t s) {
+  DN_REQUIRE(z && sums, "bn stats: null pointer");
+  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && c <= kMaxC && ldz >= c,
+             "bn stats: bad shape (groups %d rows %ld c %d ld %d)", n_groups, rows_per_group, c, ldz);
+  DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(n_groups, rows_per_group, c),
+             "bn stats: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
+             dn_reduce_workspace_bytes(n_groups, rows_per_group, c));
+  *nblk = blocks_per_group(rows_per_group, n_groups);
+  double* part = sums + (size_t)2 * c * n_groups;
+  if (bn_form(n_groups, rows_per_group, c, {ldz}, {z}).k != BnKernels::general)
+    hipLaunchKernelGGL(bn_legacy() ? bn_stats_v4_kernel<1> : bn_stats_v4_kernel<4>, dim3(*nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
+  else
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(*nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
+  return 0;
+}
+
+int bn_stats_one_call(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
+                      float* mean, float* var, float* rmean, float* rvar, float momentum, long unbias_rows, void* stream) {
+  DN_REQUIRE(mean && var, "bn stats: null pointer");
+  DN_REQUIRE(!rmean || (rvar && n_groups == 1), "bn stats: the fused running-statistics update takes one group");
+  hipStream_t s = (hipStream_t)stream;
+  int nblk;
+  if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
+  // fold + finish (+ the running statistics) in one launch: the sums and statistics of the two-launch path, bit for bit
+  hipLaunchKernelGGL(fold_stats_finish_kernel, dim3((n_groups * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups, nblk, c,
+                     n_groups, rows_per_group, sums, mean, var, rmean, rvar, momentum, unbias_rows);
+  return dn::check_launch("bn_stats_kernel");
+}
+
+// dn_bn_train_apply; relu_mask: dn_bn_train_apply_mask (relu on, the float4 kernels only)
+int bn_apply_impl(const float* z, const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                  int n_groups, long rows_per_group, int c, int ldz, float* y, unsigned char* relu_mask, void* stream) {
+  DN_REQUIRE(z && mean && var && gamma && beta && y, "bn apply: null pointer");
+  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && ldz >= c, "bn apply: bad shape");
+  const BnForm f = bn_form(n_groups, rows_per_group, c, {ldz}, {z, y, mean, var, gamma, beta});
+  DN_REQUIRE(!relu_mask || f.k != BnKernels::general, "bn apply (mask): needs c %% 4 == 0 and 16-byte aligned tensors");
+  const long total = (long)n_groups * rows_per_group * c;
+  if (f.k == BnKernels::fast)
+    hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
+                       gamma, beta, eps, relu, c, f.shift, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)nullptr, 1u,
+                       (unsigned*)nullptr);
+  else if (f.k == BnKernels::vec4)
+    hipLaunchKernelGGL(bn_apply_v4_kernel, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
+                       gamma, beta, eps, relu, rows_per_group, c, ldz, total / 4, y, relu_mask);
+  else
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, z,
+                       mean, var, gamma, beta, eps, relu, rows_per_group, c, ldz, total, y);
+  return dn::check_launch("bn_apply_kernel");
+}
+
+// the arguments both phases of the backward take
+int bn_backward_args(int ld_a, int up_a, const float* dy_b, int ld_b, const float* y, int relu, int n_groups, int h, int w,
+                     int images_per_group, int c) {
+  DN_REQUIRE(!relu || y, "bn backward: relu needs y");
+  DN_REQUIRE(relu >= 0 && relu <= 2 && (relu != 2 || c % 4 == 0), "bn backward: relu = 2 (y is the byte mask) needs c %% 4 == 0");
+  DN_REQUIRE(up_a >= 0 && up_a <= 2 && (up_a != 2 || (h % 2 == 0 && w % 2 == 0 && ld_a >= 4 * c)),
+             "bn backward: up_a = 2 (dy_a is the space-to-depth image [h / 2][w / 2][4 c]) needs even h, w and ld_a >= 4 c");
+  DN_REQUIRE(n_groups > 0 && h > 0 && w > 0 && images_per_group > 0 && c > 0 && c <= kMaxC && ld_a >= c && (!dy_b || ld_b >= c),
+             "bn backward: bad shape");
+  return 0;
 }
 
 }  // namespace
@@ -1137,28 +1216,27 @@ extern "C" size_t dn_bn_bias_workspace_bytes(long rows, int c) {
   return sizeof(double) * (size_t)c * (size_t)(1 + grid_for(rows * (long)c / 4, kBiasBlocks));
 }
 
+// The one rule of the fused forms: each entry point's DN_REQUIRE asks this, Python asks it through the C ABI.
+extern "C" int dn_bn_train_form_supported(int form, int n_groups, long rows_per_group, int c) {
+  switch (form) {
+    case DN_BN_FORM_SP_APPLY: return c % 16 == 0 && bn_fast_shift(n_groups, rows_per_group, c, false) >= 0;
+    case DN_BN_FORM_BIAS: return bn_fast_shift(n_groups, rows_per_group, c) >= 0;
+    case DN_BN_FORM_DZ_NULL: return c % 16 == 0 && bn_fast_shift(n_groups, rows_per_group, c) >= 0;
+  }
+  return 0;
+}
+
 // Two-phase forms (round 5: agent-parallel training, sharded.py).  A rank that holds only SOME images of a BatchNorm batch
 // reduces its own rows (`_partial`: the folded sums [n_groups][2 c] doubles land at the start of `sums`), the caller
 // all-reduces those doubles over the ranks, and `_finish` normalises by the GLOBAL row count.  The one-call forms below are
 // the two phases back to back with norm_rows = rows_per_group.
 extern "C" int dn_bn_train_stats_partial(const float* z, int n_groups, long rows_per_group, int c, int ldz,
                                          double* sums, size_t sums_bytes, void* stream) {
-  DN_REQUIRE(z && sums, "bn stats: null pointer");
-  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && c <= kMaxC && ldz >= c,
-             "bn stats: bad shape (groups %d rows %ld c %d ld %d)", n_groups, rows_per_group, c, ldz);
-  DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(n_groups, rows_per_group, c),
-             "bn stats: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
-             dn_reduce_workspace_bytes(n_groups, rows_per_group, c));
   hipStream_t s = (hipStream_t)stream;
-  // workspace: [n_groups][2 c] folded sums, then the workgroups' partials [n_groups][blocks][2 c]
-  const int nblk = blocks_per_group(rows_per_group, n_groups);
-  double* part = sums + (size_t)2 * c * n_groups;
-  if (vec4_ok(c, {ldz}, {z}))
-    hipLaunchKernelGGL(bn_legacy() ? bn_stats_v4_kernel<1> : bn_stats_v4_kernel<4>, dim3(nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
-  hipLaunchKernelGGL(fold_partials_kernel, dim3((n_groups * 2 * c + 3) / 4), dim3(256), 0, s, part, nblk, 2 * c,
-                     n_groups, sums);
+  int nblk;
+  if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
+  hipLaunchKernelGGL(fold_partials_kernel, dim3((n_groups * 2 * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups,
+                     nblk, 2 * c, n_groups, sums);
   return dn::check_launch("bn_stats_kernel");
 }
 
@@ -1171,29 +1249,6 @@ extern "C" int dn_bn_train_stats_finish(const double* sums, int n_groups, long n
                      norm_rows, mean, var);
   return dn::check_launch("bn_stats_finalize_kernel");
 }
-
-namespace {
-int bn_stats_one_call(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
-                      float* mean, float* var, float* rmean, float* rvar, float momentum, long unbias_rows, void* stream) {
-  DN_REQUIRE(z && sums && mean && var, "bn stats: null pointer");
-  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && c <= kMaxC && ldz >= c, "bn stats: bad shape");
-  DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(n_groups, rows_per_group, c),
-             "bn stats: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
-             dn_reduce_workspace_bytes(n_groups, rows_per_group, c));
-  DN_REQUIRE(!rmean || (rvar && n_groups == 1), "bn stats: the fused running-statistics update takes one group");
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = blocks_per_group(rows_per_group, n_groups);
-  double* part = sums + (size_t)2 * c * n_groups;      // workspace layout: see dn_bn_train_stats_partial
-  if (vec4_ok(c, {ldz}, {z}))
-    hipLaunchKernelGGL(bn_legacy() ? bn_stats_v4_kernel<1> : bn_stats_v4_kernel<4>, dim3(nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
-  // fold + finish (+ the running statistics) in one launch: the sums and statistics of the two-launch path, bit for bit
-  hipLaunchKernelGGL(fold_stats_finish_kernel, dim3((n_groups * c + 3) / 4), dim3(256), 0, s, part, nblk, c, n_groups, rows_per_group, sums,
-                     mean, var, rmean, rvar, momentum, unbias_rows);
-  return dn::check_launch("bn_stats_kernel");
-}
-}  // namespace
 
 extern "C" int dn_bn_train_stats(const float* z, int n_groups, long rows_per_group, int c, int ldz,
                                  double* sums, size_t sums_bytes, float* mean, float* var, void* stream) {
@@ -1210,57 +1265,29 @@ extern "C" int dn_bn_train_apply(const float* z, const float* mean, const float*
                                  const float* gamma, const float* beta, float eps, int relu,
                                  int n_groups, long rows_per_group, int c, int ldz, float* y,
                                  void* stream) {
-  DN_REQUIRE(z && mean && var && gamma && beta && y, "bn apply: null pointer");
-  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && ldz >= c, "bn apply: bad shape");
-  const long total = (long)n_groups * rows_per_group * c;
-  const int fsh = bn_fast_shift(n_groups, c, total);
-  if (vec4_ok(c, {ldz}, {z, y, mean, var, gamma, beta}) && fsh >= 0)
-    hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
-                       gamma, beta, eps, relu, c, fsh, ldz, (unsigned)(total / 4), y, (unsigned char*)nullptr,
-                       (unsigned char*)nullptr, 1u, (unsigned*)nullptr);
-  else if (vec4_ok(c, {ldz}, {z, y, mean, var, gamma, beta}))
-    hipLaunchKernelGGL(bn_apply_v4_kernel, dim3(grid_for(total / 4, 8192)), dim3(256), 0,
-                       (hipStream_t)stream, z, mean, var, gamma, beta, eps, relu, rows_per_group, c, ldz,
-                       total / 4, y, (unsigned char*)nullptr);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, z,
-                       mean, var, gamma, beta, eps, relu, rows_per_group, c, ldz, total, y);
-  return dn::check_launch("bn_apply_kernel");
+  return bn_apply_impl(z, mean, var, gamma, beta, eps, relu, n_groups, rows_per_group, c, ldz, y, nullptr, stream);
 }
 
 extern "C" int dn_bn_train_apply_mask(const float* z, const float* mean, const float* var, const float* gamma,
                                       const float* beta, float eps, int n_groups, long rows_per_group, int c, int ldz,
                                       float* y, unsigned char* relu_mask, void* stream) {
-  DN_REQUIRE(z && mean && var && gamma && beta && y && relu_mask, "bn apply (mask): null pointer");
-  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && ldz >= c, "bn apply (mask): bad shape");
-  DN_REQUIRE(vec4_ok(c, {ldz}, {z, y, mean, var, gamma, beta}), "bn apply (mask): needs c %% 4 == 0 and 16-byte aligned tensors");
-  const long total = (long)n_groups * rows_per_group * c;
-  const int fsh = bn_fast_shift(n_groups, c, total);
-  if (fsh >= 0)
-    hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
-                       gamma, beta, eps, 1, c, fsh, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)nullptr, 1u,
-                       (unsigned*)nullptr);
-  else
-    hipLaunchKernelGGL(bn_apply_v4_kernel, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
-                       gamma, beta, eps, 1, rows_per_group, c, ldz, total / 4, y, relu_mask);
-  return dn::check_launch("bn_apply_kernel (mask)");
+  DN_REQUIRE(relu_mask, "bn apply (mask): null pointer");
+  return bn_apply_impl(z, mean, var, gamma, beta, eps, 1, n_groups, rows_per_group, c, ldz, y, relu_mask, stream);
 }
 
 extern "C" int dn_bn_train_apply_mask_sp(const float* z, const float* mean, const float* var, const float* gamma,
                                          const float* beta, float eps, long rows, int hw, int c, int ldz, float* y,
                                          unsigned char* relu_mask, void* y_sp, void* stream) {
   DN_REQUIRE(z && mean && var && gamma && beta && y && relu_mask && y_sp, "bn apply (mask + SP): null pointer");
-  DN_REQUIRE(rows > 0 && hw > 0 && rows % hw == 0 && c > 0 && c % 16 == 0 && ldz >= c, "bn apply (mask + SP): bad shape");
+  DN_REQUIRE(rows > 0 && hw > 0 && rows % hw == 0 && c > 0 && ldz >= c, "bn apply (mask + SP): bad shape");
+  DN_REQUIRE(dn_bn_train_form_supported(DN_BN_FORM_SP_APPLY, 1, rows, c),
+             "bn apply (mask + SP): needs c %% 16 == 0, c / 4 a power of two, c <= %d and the map below 2^31 float4s (c = %d)", kMaxC, c);
   DN_REQUIRE(vec4_ok(c, {ldz}, {z, y, mean, var, gamma, beta}) && (reinterpret_cast<uintptr_t>(y_sp) & 15) == 0,
              "bn apply (mask + SP): needs 16-byte aligned tensors");
   const long total = rows * c;
-  const int c4n = c >> 2;      // (its own test: the SP form has no general-kernel twin for DN_BN_LEGACY to select)
-  DN_REQUIRE(c <= kMaxC && (c4n & (c4n - 1)) == 0 && total / 4 < (1L << 31),
-             "bn apply (mask + SP): c / 4 must be a power of two and the map below 2^31 float4s (c = %d)", c);
-  int fsh = 0;
-  while ((1 << fsh) < c4n) ++fsh;
   unsigned* flags = dn::sp_range_word();
   DN_REQUIRE(flags, "bn apply (mask + SP): the range word of the split-f16 engine is not addressable");
+  const int fsh = bn_fast_shift(1, rows, c, false);      // (the SP form has no general-kernel twin for DN_BN_LEGACY to select)
   hipLaunchKernelGGL(bn_apply_v4_fast_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
                      gamma, beta, eps, 1, c, fsh, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)y_sp, (unsigned)hw, flags);
   return dn::check_launch("bn_apply_kernel (mask + SP)");
@@ -1283,13 +1310,7 @@ extern "C" int dn_bn_train_backward_partial(const float* dy_a, int ld_a, int up_
                                             int relu, int n_groups, int h, int w, int images_per_group, int c, double* sums,
                                             size_t sums_bytes, float* dgamma, float* dbeta, int accumulate, void* stream) {
   DN_REQUIRE(dy_a && z && mean && var && sums && dgamma && dbeta, "bn backward: null pointer");
-  DN_REQUIRE(!relu || y, "bn backward: relu needs y");
-  DN_REQUIRE(relu >= 0 && relu <= 2 && (relu != 2 || c % 4 == 0), "bn backward: relu = 2 (y is the byte mask) needs c %% 4 == 0");
-  DN_REQUIRE(up_a >= 0 && up_a <= 2 && (up_a != 2 || (h % 2 == 0 && w % 2 == 0 && ld_a >= 4 * c)),
-             "bn backward: up_a = 2 (dy_a is the space-to-depth image [h / 2][w / 2][4 c]) needs even h, w and ld_a >= 4 c");
-  DN_REQUIRE(n_groups > 0 && h > 0 && w > 0 && images_per_group > 0 && c > 0 && c <= kMaxC &&
-                 ld_a >= c && (!dy_b || ld_b >= c),
-             "bn backward: bad shape");
+  if (int rc = bn_backward_args(ld_a, up_a, dy_b, ld_b, y, relu, n_groups, h, w, images_per_group, c)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const long rows_per_group = (long)images_per_group * h * w;
   DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(n_groups, rows_per_group, c),
@@ -1298,7 +1319,7 @@ extern "C" int dn_bn_train_backward_partial(const float* dy_a, int ld_a, int up_
   GradSrc src{dy_a, dy_b, y, ld_a, up_a, ld_b, relu, h, w, c};
   const int nblk = blocks_per_group(rows_per_group, n_groups);
   double* part = sums + (size_t)2 * c * n_groups;      // workspace layout: see dn_bn_train_stats_partial
-  if (vec4_ok(c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var}))
+  if (bn_form(n_groups, rows_per_group, c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var}).k != BnKernels::general)
     hipLaunchKernelGGL(bn_legacy() ? bn_bwd_reduce_v4_kernel<1> : bn_bwd_reduce_v4_kernel<2>, dim3(nblk, n_groups), dim3(256), 0, s, src, z, mean, var, eps,
                        rows_per_group, part);
   else
@@ -1324,68 +1345,53 @@ int bn_backward_finish_impl(const float* dy_a, int ld_a, int up_a, const float* 
                             void* dz_sp, float sp_lift, void* stream, float* dbias = nullptr, double* bias_ws = nullptr,
                             size_t bias_ws_bytes = 0, int* defer_blocks = nullptr) {
   DN_REQUIRE(dy_a && z && mean && var && gamma && sums && (dz || dz_sp), "bn backward finish: null pointer");
-  DN_REQUIRE(!relu || y, "bn backward: relu needs y");
-  // dz NULL (round 6): only the SP copy is written -- for a layer whose weight gradient (dn_conv_wgrad_sp_z), data gradient and
-  // bias gradient all read dz through this launch's other outputs; the one-group fast kernels only
-  DN_REQUIRE(dz || (n_groups == 1 && bn_fast_shift(n_groups, c, (long)images_per_group * h * w * c) >= 0),
-             "bn backward: dz may be NULL only where the one-group fast form runs (one group, c / 4 a power of two; DN_BN_LEGACY unset)");
-  DN_REQUIRE(relu >= 0 && relu <= 2 && (relu != 2 || c % 4 == 0), "bn backward: relu = 2 (y is the byte mask) needs c %% 4 == 0");
-  DN_REQUIRE(up_a >= 0 && up_a <= 2 && (up_a != 2 || (h % 2 == 0 && w % 2 == 0 && ld_a >= 4 * c)),
-             "bn backward: up_a = 2 (dy_a is the space-to-depth image [h / 2][w / 2][4 c]) needs even h, w and ld_a >= 4 c");
-  DN_REQUIRE(n_groups > 0 && h > 0 && w > 0 && images_per_group > 0 && c > 0 && c <= kMaxC && norm_rows > 0 &&
-                 ld_a >= c && (!dy_b || ld_b >= c),
-             "bn backward finish: bad shape");
+  if (int rc = bn_backward_args(ld_a, up_a, dy_b, ld_b, y, relu, n_groups, h, w, images_per_group, c)) return rc;
+  DN_REQUIRE(norm_rows > 0, "bn backward finish: bad shape");
   hipStream_t s = (hipStream_t)stream;
   const long rows_per_group = (long)images_per_group * h * w;
+  // dz NULL (round 6): only the SP copy is written -- for a layer whose weight gradient (dn_conv_wgrad_sp_z), data gradient and
+  // bias gradient all read dz through this launch's other outputs; the one-group fast kernels only
+  DN_REQUIRE(dz || dn_bn_train_form_supported(DN_BN_FORM_DZ_NULL, n_groups, rows_per_group, c),
+             "bn backward: dz may be NULL only where the one-group fast form runs (one group, c %% 16 == 0, c / 4 a power of two; DN_BN_LEGACY unset)");
+  const BnForm f = bn_form(n_groups, rows_per_group, c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz});
+  const bool bias = dbias || defer_blocks;
+  DN_REQUIRE(!bias || (dn_bn_train_form_supported(DN_BN_FORM_BIAS, n_groups, rows_per_group, c) && f.k != BnKernels::general),
+             "bn backward: the fused bias gradient needs the one-group fast form (c / 4 a power of two, aligned tensors; DN_BN_LEGACY unset)");
+  unsigned* flags = nullptr;
+  if (dz_sp) {
+    DN_REQUIRE(n_groups == 1 && c % 16 == 0 && f.k != BnKernels::general && (reinterpret_cast<uintptr_t>(dz_sp) & 15) == 0 &&
+                   rows_per_group < (1L << 31),
+               "bn backward: the SP copy of dz needs one group, c %% 16 == 0, 16-byte aligned tensors (c = %d, groups = %d)", c, n_groups);
+    DN_REQUIRE(sp_lift > 0.f && std::isfinite(sp_lift), "bn backward: sp_lift must be a positive finite power of two");
+    flags = dn::sp_range_word();
+    DN_REQUIRE(flags, "bn backward: the range word of the split-f16 engine is not addressable");
+  }
   GradSrc src{dy_a, dy_b, y, ld_a, up_a, ld_b, relu, h, w, c};
   const long total = (long)n_groups * rows_per_group * c;
-  // the fused bias gradient (round 6): the apply launch leaves one double per (workgroup, channel), folded in a fixed order
-  auto bias_launch = [&](auto sp_c, void* sp_ptr, float lift, unsigned* fl, int fsh) -> int {
-    constexpr bool SPF = decltype(sp_c)::value;
+  unsigned char* sp = (unsigned char*)dz_sp;
+  const float lift = dz_sp ? sp_lift : 1.f;
+  if (bias) {
+    // the fused bias gradient (round 6): the apply launch leaves one double per (workgroup, channel), folded in a fixed order
     const int blocks = grid_for(total / 4, kBiasBlocks);
     DN_REQUIRE(bias_ws && bias_ws_bytes >= dn_bn_bias_workspace_bytes(rows_per_group, c),
                "bn backward: bias workspace of %zu bytes, dn_bn_bias_workspace_bytes() asks for %zu", bias_ws_bytes,
                dn_bn_bias_workspace_bytes(rows_per_group, c));
     double* part = bias_ws + c;      // [c] folded sums, then [blocks][c] partials
-    hipLaunchKernelGGL((bn_bwd_apply_v4_fast_kernel<SPF, true>), dim3(blocks), dim3(256), 0, s, src, z, mean, var, gamma, eps,
-                       norm_rows, sums, fsh, (unsigned)(total / 4), dz, (unsigned char*)sp_ptr, lift, (unsigned)(h * w), fl, part);
+    hipLaunchKernelGGL((dz_sp ? bn_bwd_apply_v4_fast_kernel<true, true> : bn_bwd_apply_v4_fast_kernel<false, true>), dim3(blocks), dim3(256), 0,
+                       s, src, z, mean, var, gamma, eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, (unsigned)(h * w), flags, part);
     if (defer_blocks)      // the fold is the caller's (dn_channel_sum_fold_multi): the partials stay in bias_ws
       *defer_blocks = blocks;
     else
       hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, blocks, c, bias_ws, dbias, 0);
     return dn::check_launch("bn backward apply kernel (+ bias gradient)");
-  };
-  if (dz_sp) {
-    DN_REQUIRE(n_groups == 1 && c % 16 == 0 && vec4_ok(c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz}) &&
-                   (reinterpret_cast<uintptr_t>(dz_sp) & 15) == 0 && rows_per_group < (1L << 31),
-               "bn backward: the SP copy of dz needs one group, c %% 16 == 0, 16-byte aligned tensors (c = %d, groups = %d)", c, n_groups);
-    DN_REQUIRE(sp_lift > 0.f && std::isfinite(sp_lift), "bn backward: sp_lift must be a positive finite power of two");
-    unsigned* flags = dn::sp_range_word();
-    DN_REQUIRE(flags, "bn backward: the range word of the split-f16 engine is not addressable");
-    const int fsh = bn_fast_shift(n_groups, c, total);
-    if (fsh >= 0 && (dbias || defer_blocks))
-      return bias_launch(std::true_type{}, dz_sp, sp_lift, flags, fsh);
-    DN_REQUIRE(!dbias && !defer_blocks, "bn backward: the fused bias gradient needs the one-group fast form (c / 4 a power of two; DN_BN_LEGACY unset)");
-    if (fsh >= 0)
-      hipLaunchKernelGGL(bn_bwd_apply_v4_fast_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, src, z, mean, var, gamma,
-                         eps, norm_rows, sums, fsh, (unsigned)(total / 4), dz, (unsigned char*)dz_sp, sp_lift, (unsigned)(h * w), flags);
-    else
-      hipLaunchKernelGGL(bn_bwd_apply_v4_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, src, z, mean, var, gamma,
-                         eps, rows_per_group, norm_rows, sums, total / 4, dz, (unsigned char*)dz_sp, sp_lift, (unsigned)(h * w), flags);
-    return dn::check_launch("bn backward apply kernel (SP copy)");
   }
-  const int fsh = bn_fast_shift(n_groups, c, total);
-  if (dbias || defer_blocks) {
-    DN_REQUIRE(vec4_ok(c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz}) && fsh >= 0,
-               "bn backward: the fused bias gradient needs the one-group fast form (c / 4 a power of two, aligned tensors; DN_BN_LEGACY unset)");
-    return bias_launch(std::false_type{}, nullptr, 1.f, nullptr, fsh);
-  }
-  if (vec4_ok(c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz}) && fsh >= 0)
-    hipLaunchKernelGGL(bn_bwd_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, src, z, mean, var, gamma,
-                       eps, norm_rows, sums, fsh, (unsigned)(total / 4), dz, nullptr, 1.f, 1u, nullptr);
-  else if (vec4_ok(c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz}))
-    hipLaunchKernelGGL(bn_bwd_apply_v4_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, src, z,
-                       mean, var, gamma, eps, rows_per_group, norm_rows, sums, total / 4, dz, nullptr, 1.f, 1u, nullptr);
+  const unsigned hw = dz_sp ? (unsigned)(h * w) : 1u;
+  if (f.k == BnKernels::fast)
+    hipLaunchKernelGGL(dz_sp ? bn_bwd_apply_v4_fast_kernel<true> : bn_bwd_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256),
+                       0, s, src, z, mean, var, gamma, eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, hw, flags, (double*)nullptr);
+  else if (f.k == BnKernels::vec4)
+    hipLaunchKernelGGL(dz_sp ? bn_bwd_apply_v4_kernel<true> : bn_bwd_apply_v4_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s,
+                       src, z, mean, var, gamma, eps, rows_per_group, norm_rows, sums, total / 4, dz, sp, lift, hw, flags);
   else
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, src, z, mean,
                        var, gamma, eps, rows_per_group, norm_rows, sums, total, dz);
@@ -1467,27 +1473,9 @@ extern "C" int dn_bn_train_backward(const float* dy_a, int ld_a, int up_a, const
                                      images_per_group, c, sums, (long)images_per_group * h * w, dz, stream);
 }
 
-extern "C" int dn_channel_sum(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, float* out,
-                              int accumulate, void* stream) {
-  DN_REQUIRE(x && sums && out, "channel sum: null pointer");
-  DN_REQUIRE(rows > 0 && c > 0 && c <= kMaxC && ld >= c, "channel sum: bad shape");
-  DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(1, rows, c),
-             "channel sum: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
-             dn_reduce_workspace_bytes(1, rows, c));
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = blocks_per_group(rows, 1);
-  double* part = sums + c;                              // [c] folded sums, then the workgroups' partials [blocks][c]
-  if (vec4_ok(c, {ld}, {x}))
-    hipLaunchKernelGGL(bn_legacy() ? channel_sum_v4_kernel<1> : channel_sum_v4_kernel<4>, dim3(nblk), dim3(256), 0, s, x, rows, c, ld, part);
-  else
-    hipLaunchKernelGGL(channel_sum_kernel, dim3(nblk), dim3(256), 0, s, x, rows, c, ld, part);
-  hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, nblk, c, sums, out, accumulate);
-  return dn::check_launch("channel_sum_kernel");
-}
-
 extern "C" int dn_channel_sum_partial(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, int* n_blocks,
                                       void* stream) {
-  DN_REQUIRE(x && sums && n_blocks, "channel sum (partial): null pointer");
+  DN_REQUIRE(x && sums && n_blocks, "channel sum: null pointer");
   DN_REQUIRE(rows > 0 && c > 0 && c <= kMaxC && ld >= c, "channel sum: bad shape");
   DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(1, rows, c),
              "channel sum: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
@@ -1501,6 +1489,16 @@ extern "C" int dn_channel_sum_partial(const float* x, long rows, int c, int ld, 
     hipLaunchKernelGGL(channel_sum_kernel, dim3(nblk), dim3(256), 0, s, x, rows, c, ld, part);
   *n_blocks = nblk;
   return dn::check_launch("channel_sum_kernel");
+}
+
+extern "C" int dn_channel_sum(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, float* out,
+                              int accumulate, void* stream) {
+  DN_REQUIRE(out, "channel sum: null pointer");
+  int nblk;
+  if (int rc = dn_channel_sum_partial(x, rows, c, ld, sums, sums_bytes, &nblk, stream)) return rc;
+  hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, (hipStream_t)stream, sums + c, nblk, c, sums, out,
+                     accumulate);
+  return dn::check_launch("fold_channel_sum_kernel");
 }
 
 extern "C" int dn_add_rows(float* a, int ld_a, const float* b, int ld_b, long rows, int c,

@@ -469,7 +469,7 @@ class TrainEngine:
         # copy (dn_conv_wgrad_sp_z), the bias gradient out of the same launch and no re-measurement of the lift due this step,
         # nothing does -- a quarter of the launch's bytes (DN_TRAIN_DZ_SP_ONLY=0: always written)
         sp_only = (sp is not None and fused_bias and wsp and ent is not None and abs(self.step_count - ent[1]) < 64
-                   and os.environ.get("DN_TRAIN_DZ_SP_ONLY", "1") != "0")
+                   and os.environ.get("DN_TRAIN_DZ_SP_ONLY", "1") != "0" and T.bn_form_supported(T.BN_FORM_DZ_NULL, c["z"], c["groups"]))
         dz = T.bn_backward(dy_a, c["y"], c["z"], c["mean"], c["var"], c["gamma"], _EPS, ggamma, gbeta,
                            relu=True, dy_b=dy_b, up_a=up_a, sp_out=sp, sp_lift=lift, relu_mask=c.get("mask"),
                            dbias=gb if fused_bias else None, folds=self.__dict__.get("_folds_active") if fused_bias else None,

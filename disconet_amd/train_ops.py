@@ -5,7 +5,6 @@ Maps are NHWC; a tensor argument that is a channel slice of a wider map is passe
 as (tensor_view, ld) with the view's data_ptr at the first channel.
 """
 import ctypes
-import os
 
 import torch
 
@@ -109,37 +108,47 @@ def bn_stats(z, n_groups=1, sync=None, norm_rows=None, running=None):
     running = (running_mean, running_var, momentum): one group, no sync -- the momentum update of the running statistics leaves
     the launch that finishes the statistics (dn_bn_train_stats_running), bit for bit bn_update_running's."""
     _need_gpu(z)
+    if running is not None and (sync is not None or n_groups != 1):
+        raise _lib.DnError("bn_stats: the fused running-statistics update takes one group and no sync")
     c = z.shape[-1]
     rows = z.numel() // c
     assert rows % n_groups == 0
+    rpg = rows // n_groups
     mean = torch.empty((n_groups, c), dtype=torch.float32, device=z.device)
     var = torch.empty_like(mean)
     lib = _lib.load()
-    sums = _ws(z.device, lib.dn_reduce_workspace_bytes(n_groups, rows // n_groups, c))
-    if running is not None:
-        if sync is not None or n_groups != 1:
-            raise _lib.DnError("bn_stats: the fused running-statistics update takes one group and no sync")
+    sums = _ws(z.device, lib.dn_reduce_workspace_bytes(n_groups, rpg, c))
+    if sync is not None:
+        check(lib.dn_bn_train_stats_partial(_ptr(z), n_groups, rpg, c, c, _ptr(sums), sums.numel(), _stream()),
+              "dn_bn_train_stats_partial")
+        sync(_folded(sums, n_groups, c))
+        check(lib.dn_bn_train_stats_finish(_ptr(sums), n_groups, int(norm_rows if norm_rows is not None else rpg), c,
+                                           _ptr(mean), _ptr(var), _stream()), "dn_bn_train_stats_finish")
+    elif running is not None:
         rm, rv, momentum = running
         _need_gpu(rm, rv)
         check(lib.dn_bn_train_stats_running(_ptr(z), rows, c, c, _ptr(sums), sums.numel(), _ptr(mean), _ptr(var), _ptr(rm), _ptr(rv),
                                             float(momentum), _stream()), "dn_bn_train_stats_running")
-        return mean, var
-    if sync is None:
-        check(lib.dn_bn_train_stats(_ptr(z), n_groups, rows // n_groups, c, c, _ptr(sums), sums.numel(),
-                                    _ptr(mean), _ptr(var), _stream()), "dn_bn_train_stats")
-        return mean, var
-    check(lib.dn_bn_train_stats_partial(_ptr(z), n_groups, rows // n_groups, c, c, _ptr(sums), sums.numel(), _stream()),
-          "dn_bn_train_stats_partial")
-    sync(_folded(sums, n_groups, c))
-    check(lib.dn_bn_train_stats_finish(_ptr(sums), n_groups, int(norm_rows if norm_rows is not None else rows // n_groups), c,
-                                       _ptr(mean), _ptr(var), _stream()), "dn_bn_train_stats_finish")
+    else:
+        check(lib.dn_bn_train_stats(_ptr(z), n_groups, rpg, c, c, _ptr(sums), sums.numel(), _ptr(mean), _ptr(var), _stream()),
+              "dn_bn_train_stats")
     return mean, var
 
 
-def bn_apply_sp_supported(z, n_groups=1):
-    """can bn_apply(..., sp_out=...) also write y as an SP tensor?  (one group, [n, h, w, c] with c % 16 == 0, c / 4 a power of two)"""
+# the fused BatchNorm forms of include/disconet_train.h (dn_bn_train_form_supported)
+BN_FORM_SP_APPLY, BN_FORM_BIAS, BN_FORM_DZ_NULL = 0, 1, 2
+
+
+def bn_form_supported(form, z, n_groups=1):
+    """does the library run the fused BatchNorm form `form` on z [n, h, w, c] in n_groups groups?  The shape rule of the
+    matching C entry point, asked of the library (the tensors' alignment is still checked by the call)"""
     c = z.shape[-1]
-    return z.dim() == 4 and n_groups == 1 and c % 16 == 0 and ((c // 4) & (c // 4 - 1)) == 0 and c <= 1024
+    return z.dim() == 4 and bool(_lib.load().dn_bn_train_form_supported(form, n_groups, z.numel() // c // n_groups, c))
+
+
+def bn_apply_sp_supported(z, n_groups=1):
+    """can bn_apply(..., sp_out=...) also write y as an SP tensor?"""
+    return bn_form_supported(BN_FORM_SP_APPLY, z, n_groups)
 
 
 def bn_apply(z, mean, var, gamma, beta, eps, relu=True, out=None, relu_mask=None, sp_out=None):
@@ -151,26 +160,25 @@ def bn_apply(z, mean, var, gamma, beta, eps, relu=True, out=None, relu_mask=None
     c = z.shape[-1]
     n_groups = mean.shape[0]
     rows = z.numel() // c
+    if sp_out is not None and (relu_mask is None or not bn_apply_sp_supported(z, n_groups) or tuple(sp_out.shape) != tuple(z.shape)
+                               or sp_out.hi_only or sp_out.bits):
+        raise _lib.DnError("bn_apply: sp_out needs relu + relu_mask, one group, c % 16 == 0 with c / 4 a power of two, and a "
+                           "full SP tensor of z's shape")
+    if relu_mask is not None and (not relu or relu_mask.dtype != torch.uint8 or relu_mask.numel() * 4 != z.numel()
+                                  or not relu_mask.is_contiguous()):
+        raise _lib.DnError("bn_apply: relu_mask must be a contiguous uint8 tensor of z.numel() / 4 bytes, with relu on")
     y = torch.empty_like(z) if out is None else out
+    lib = _lib.load()
     if sp_out is not None:
-        if relu_mask is None or not relu or not bn_apply_sp_supported(z, n_groups) or tuple(sp_out.shape) != tuple(z.shape) \
-                or sp_out.hi_only or sp_out.bits or relu_mask.dtype != torch.uint8 or relu_mask.numel() * 4 != z.numel():
-            raise _lib.DnError("bn_apply: sp_out needs relu + relu_mask, one group, c % 16 == 0 with c / 4 a power of two, and a "
-                               "full SP tensor of z's shape")
-        check(_lib.load().dn_bn_train_apply_mask_sp(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), rows,
-                                                    z.shape[1] * z.shape[2], c, c, _ptr(y), _ptr(relu_mask), _ptr(sp_out.data),
-                                                    _stream()), "dn_bn_train_apply_mask_sp")
-        return y
-    if relu_mask is not None:
-        if not relu or relu_mask.dtype != torch.uint8 or relu_mask.numel() * 4 != z.numel() or not relu_mask.is_contiguous():
-            raise _lib.DnError("bn_apply: relu_mask must be a contiguous uint8 tensor of z.numel() / 4 bytes, with relu on")
-        check(_lib.load().dn_bn_train_apply_mask(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), n_groups,
-                                                 rows // n_groups, c, c, _ptr(y), _ptr(relu_mask), _stream()),
-              "dn_bn_train_apply_mask")
-        return y
-    check(_lib.load().dn_bn_train_apply(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta),
-                                        float(eps), int(relu), n_groups, rows // n_groups, c, c,
-                                        _ptr(y), _stream()), "dn_bn_train_apply")
+        check(lib.dn_bn_train_apply_mask_sp(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), rows,
+                                            z.shape[1] * z.shape[2], c, c, _ptr(y), _ptr(relu_mask), _ptr(sp_out.data), _stream()),
+              "dn_bn_train_apply_mask_sp")
+    elif relu_mask is not None:
+        check(lib.dn_bn_train_apply_mask(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), n_groups,
+                                         rows // n_groups, c, c, _ptr(y), _ptr(relu_mask), _stream()), "dn_bn_train_apply_mask")
+    else:
+        check(lib.dn_bn_train_apply(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), int(relu), n_groups,
+                                    rows // n_groups, c, c, _ptr(y), _stream()), "dn_bn_train_apply")
     return y
 
 
@@ -188,9 +196,7 @@ _BIAS_WS = {}      # the fused bias gradient's partials: never the buffer the re
 
 def bn_backward_bias_supported(z, n_groups=1):
     """can bn_backward(..., dbias=...) fuse the conv bias gradient (sum of dz per channel) into its apply launch?"""
-    c = z.shape[-1]
-    return (z.dim() == 4 and n_groups == 1 and c % 4 == 0 and ((c // 4) & (c // 4 - 1)) == 0 and c <= 1024
-            and z.numel() // 4 < (1 << 31) and os.environ.get("DN_BN_LEGACY", "0") != "1")
+    return bn_form_supported(BN_FORM_BIAS, z, n_groups)
 
 
 def bn_backward(dy_a, y, z, mean, var, gamma, eps, dgamma, dbeta, relu=True, dy_b=None, up_a=False,
@@ -218,69 +224,48 @@ def bn_backward(dy_a, y, z, mean, var, gamma, eps, dgamma, dbeta, relu=True, dy_
     assert n % n_groups == 0
     if not want_dz and (sp_out is None or dbias is None or out is not None):
         raise _lib.DnError("bn_backward: want_dz = False needs sp_out and dbias (the fused forms) and no out")
+    if dbias is not None and (not bn_backward_bias_supported(z, n_groups) or dbias.numel() != c or not dbias.is_contiguous()):
+        raise _lib.DnError("bn_backward: dbias needs one group, c / 4 a power of two and a contiguous [c] tensor")
+    if sp_out is not None and (tuple(sp_out.shape) != (n, h, w, c) or sp_out.hi_only or sp_out.bits):
+        raise _lib.DnError("bn_backward: sp_out must be a full SP tensor of z's shape")
     dz = (torch.empty_like(z) if out is None else out) if want_dz else None
+    ipg = n // n_groups
     lib = _lib.load()
-    sums = _ws(z.device, lib.dn_reduce_workspace_bytes(n_groups, (n // n_groups) * h * w, c))
-    if dbias is not None:
-        if not bn_backward_bias_supported(z, n_groups) or dbias.numel() != c or not dbias.is_contiguous():
-            raise _lib.DnError("bn_backward: dbias needs one group, c / 4 a power of two and a contiguous [c] tensor")
-        if sp_out is not None and (tuple(sp_out.shape) != (n, h, w, c) or sp_out.hi_only or sp_out.bits):
-            raise _lib.DnError("bn_backward: sp_out must be a full SP tensor of z's shape")
-        src = (_ptr(dy_a), _ld(dy_a), int(up_a), _ptr(dy_b), _ld(dy_b) if dy_b is not None else 0, _ptr(y), _ptr(z),
-               _ptr(mean), _ptr(var))
-        check(lib.dn_bn_train_backward_partial(*src, float(eps), int(relu), n_groups, h, w, n, c, _ptr(sums),
-                                               sums.numel(), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()),
-              "dn_bn_train_backward_partial")
-        if sync is not None:
-            sync(_folded(sums, n_groups, c))
-        rows = int(norm_rows if norm_rows is not None else n * h * w)
-        nb = int(lib.dn_bn_bias_workspace_bytes(n * h * w, c))
-        if folds is not None:
-            bws = folds.workspace(dbias, nb)
-            blocks = ctypes.c_int(0)
-            check(lib.dn_bn_train_backward_finish_bias_deferred(
-                *src, _ptr(gamma), float(eps), int(relu), h, w, n, c, _ptr(sums), rows, _ptr(dz),
-                _ptr(sp_out.data) if sp_out is not None else None, float(sp_lift) if sp_out is not None else 1.0,
-                _ptr(bws), bws.numel(), ctypes.byref(blocks), _stream()), "dn_bn_train_backward_finish_bias_deferred")
-            folds.add(bws, blocks.value, c, dbias, False)
-            return dz
-        bws = _ws(z.device, nb, _BIAS_WS)
-        check(lib.dn_bn_train_backward_finish_bias(*src, _ptr(gamma), float(eps), int(relu), h, w, n, c, _ptr(sums), rows, _ptr(dz),
-                                                   _ptr(sp_out.data) if sp_out is not None else None,
-                                                   float(sp_lift) if sp_out is not None else 1.0, _ptr(dbias),
-                                                   _ptr(bws), bws.numel(), _stream()), "dn_bn_train_backward_finish_bias")
-        return dz
-    if sp_out is not None:
-        if tuple(sp_out.shape) != (n, h, w, c) or sp_out.hi_only or sp_out.bits:
-            raise _lib.DnError("bn_backward: sp_out must be a full SP tensor of z's shape")
-        src = (_ptr(dy_a), _ld(dy_a), int(up_a), _ptr(dy_b), _ld(dy_b) if dy_b is not None else 0, _ptr(y), _ptr(z),
-               _ptr(mean), _ptr(var))
-        check(lib.dn_bn_train_backward_partial(*src, float(eps), int(relu), n_groups, h, w, n // n_groups, c, _ptr(sums),
-                                               sums.numel(), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()),
-              "dn_bn_train_backward_partial")
-        if sync is not None:
-            sync(_folded(sums, n_groups, c))
-        rows = int(norm_rows if norm_rows is not None else (n // n_groups) * h * w)
-        check(lib.dn_bn_train_backward_finish_sp(*src, _ptr(gamma), float(eps), int(relu), n_groups, h, w, n // n_groups, c,
-                                                 _ptr(sums), rows, _ptr(dz), _ptr(sp_out.data), float(sp_lift), _stream()),
-              "dn_bn_train_backward_finish_sp")
-        return dz
-    if sync is None:
-        check(lib.dn_bn_train_backward(
-            _ptr(dy_a), _ld(dy_a), int(up_a), _ptr(dy_b), _ld(dy_b) if dy_b is not None else 0,
-            _ptr(y), _ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), float(eps), int(relu), n_groups, h, w,
-            n // n_groups, c, _ptr(sums), sums.numel(), _ptr(dz), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)),
-            _stream()), "dn_bn_train_backward")
-        return dz
+    sums = _ws(z.device, lib.dn_reduce_workspace_bytes(n_groups, ipg * h * w, c))
     src = (_ptr(dy_a), _ld(dy_a), int(up_a), _ptr(dy_b), _ld(dy_b) if dy_b is not None else 0, _ptr(y), _ptr(z),
            _ptr(mean), _ptr(var))
-    check(lib.dn_bn_train_backward_partial(*src, float(eps), int(relu), n_groups, h, w, n // n_groups, c, _ptr(sums),
-                                           sums.numel(), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()),
+    # phase 1: the sums of g and g * zhat, dgamma, dbeta -- with phase 2's plain form in the same library call where nothing is
+    # asked for in between or of phase 2
+    if sync is None and sp_out is None and dbias is None:
+        check(lib.dn_bn_train_backward(*src, _ptr(gamma), float(eps), int(relu), n_groups, h, w, ipg, c, _ptr(sums), sums.numel(),
+                                       _ptr(dz), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()), "dn_bn_train_backward")
+        return dz
+    check(lib.dn_bn_train_backward_partial(*src, float(eps), int(relu), n_groups, h, w, ipg, c, _ptr(sums), sums.numel(),
+                                           _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()),
           "dn_bn_train_backward_partial")
-    sync(_folded(sums, n_groups, c))
-    rows = int(norm_rows if norm_rows is not None else (n // n_groups) * h * w)
-    check(lib.dn_bn_train_backward_finish(*src, _ptr(gamma), float(eps), int(relu), n_groups, h, w, n // n_groups, c,
-                                          _ptr(sums), rows, _ptr(dz), _stream()), "dn_bn_train_backward_finish")
+    if sync is not None:
+        sync(_folded(sums, n_groups, c))
+    # phase 2: dz (+ its SP copy, + the bias gradient)
+    fin = src + (_ptr(gamma), float(eps), int(relu))
+    rows = int(norm_rows if norm_rows is not None else ipg * h * w)
+    sp = (_ptr(sp_out.data), float(sp_lift)) if sp_out is not None else (None, 1.0)
+    if dbias is None and sp_out is None:
+        check(lib.dn_bn_train_backward_finish(*fin, n_groups, h, w, ipg, c, _ptr(sums), rows, _ptr(dz), _stream()),
+              "dn_bn_train_backward_finish")
+    elif dbias is None:
+        check(lib.dn_bn_train_backward_finish_sp(*fin, n_groups, h, w, ipg, c, _ptr(sums), rows, _ptr(dz), *sp, _stream()),
+              "dn_bn_train_backward_finish_sp")
+    elif folds is None:
+        bws = _ws(z.device, lib.dn_bn_bias_workspace_bytes(n * h * w, c), _BIAS_WS)
+        check(lib.dn_bn_train_backward_finish_bias(*fin, h, w, n, c, _ptr(sums), rows, _ptr(dz), *sp, _ptr(dbias), _ptr(bws),
+                                                   bws.numel(), _stream()), "dn_bn_train_backward_finish_bias")
+    else:
+        bws = folds.workspace(dbias, lib.dn_bn_bias_workspace_bytes(n * h * w, c))
+        blocks = ctypes.c_int(0)
+        check(lib.dn_bn_train_backward_finish_bias_deferred(*fin, h, w, n, c, _ptr(sums), rows, _ptr(dz), *sp, _ptr(bws), bws.numel(),
+                                                            ctypes.byref(blocks), _stream()),
+              "dn_bn_train_backward_finish_bias_deferred")
+        folds.add(bws, blocks.value, c, dbias, False)
     return dz
 
 
@@ -320,17 +305,18 @@ def channel_sum(x, out, accumulate=False, folds=None):
     _need_gpu(x, out)
     c = x.shape[-1]
     rows = x.numel() // c
-    if folds is not None:
-        lib = _lib.load()
-        ws = folds.workspace(out, lib.dn_reduce_workspace_bytes(1, rows, c))
+    lib = _lib.load()
+    nbytes = lib.dn_reduce_workspace_bytes(1, rows, c)
+    if folds is None:
+        sums = _ws(x.device, nbytes)
+        check(lib.dn_channel_sum(_ptr(x), rows, c, _ld(x), _ptr(sums), sums.numel(), _ptr(out), int(bool(accumulate)), _stream()),
+              "dn_channel_sum")
+    else:
+        ws = folds.workspace(out, nbytes)
         blocks = ctypes.c_int(0)
         check(lib.dn_channel_sum_partial(_ptr(x), rows, c, _ld(x), _ptr(ws), ws.numel(), ctypes.byref(blocks), _stream()),
               "dn_channel_sum_partial")
         folds.add(ws, blocks.value, c, out, accumulate)
-        return out
-    sums = _ws(x.device, _lib.load().dn_reduce_workspace_bytes(1, rows, c))
-    check(_lib.load().dn_channel_sum(_ptr(x), rows, c, _ld(x), _ptr(sums), sums.numel(), _ptr(out),
-                                     int(bool(accumulate)), _stream()), "dn_channel_sum")
     return out
 
 

@@ -221,6 +221,19 @@ int dn_bn_train_backward_finish_bias_deferred(const float* dy_a, int ld_a, int u
 int dn_channel_sum_partial(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, int* n_blocks, void* stream);
 int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, void* stream);
 
+/* Does the fused BatchNorm form `form` take this shape?  1 or 0: exactly the shape condition its entry points enforce (they ask
+ * this function), so a caller can pick the plain entry points instead of meeting an error.  The tensors' alignment (16 bytes,
+ * row strides % 4) is not part of it: the call still checks that.
+ *   DN_BN_FORM_SP_APPLY  dn_bn_train_apply_mask_sp (n_groups = 1): c % 16 == 0, c / 4 a power of two, c <= 512,
+ *                        rows_per_group * c / 4 < 2^31.  DN_BN_LEGACY=1 does not change it (the SP apply has no general twin).
+ *   DN_BN_FORM_BIAS      dn_bn_train_backward_finish_bias(_deferred): one group, c % 4 == 0, c / 4 a power of two, c <= 512,
+ *                        rows_per_group * c / 4 < 2^31, DN_BN_LEGACY unset (the one-group fast kernels).
+ *   DN_BN_FORM_DZ_NULL   dz = NULL in _finish_sp / _finish_bias(_deferred) (only the SP copy of dz written): DN_BN_FORM_BIAS
+ *                        and c % 16 == 0.
+ * Any other n_groups, a non-positive size or an unknown form: 0. */
+enum { DN_BN_FORM_SP_APPLY = 0, DN_BN_FORM_BIAS = 1, DN_BN_FORM_DZ_NULL = 2 };
+int dn_bn_train_form_supported(int form, int n_groups, long rows_per_group, int c);
+
 /* Backward of the decoder's nearest x2 upsample as a pass of its own (only needed where no
  * BatchNorm backward follows directly: the fusion on layer 4): out [n, h, w, c] dense = 2 x 2
  * block sums of g [n, 2h, 2w, c'] read with row stride ld. */

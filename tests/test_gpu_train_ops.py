@@ -464,6 +464,9 @@ for shape, up_a, sp, two in (((20, 64, 64, 128), 0, True, True), ((3, 16, 32, 64
     bias = train_ops.channel_sum(dz, torch.empty(c, device=dev))
     out += [t.cpu() for t in (mean, var, y, y2, mask, dz, dz2, dg, db, bias)] + ([spt.data.view(torch.int16).cpu()] if sp else [])
 torch.save(out, sys.argv[1])
+from disconet_amd import _lib
+print(*(_lib.load().dn_bn_train_form_supported(f, 1, 4096, 64) for f in (train_ops.BN_FORM_SP_APPLY, train_ops.BN_FORM_BIAS,
+                                                                          train_ops.BN_FORM_DZ_NULL)))
 """
 
 
@@ -477,12 +480,15 @@ def test_bn_fast_kernels_equal_the_general_kernels_bit_for_bit(tmp_path):
     import subprocess
     import sys
     from tests.conftest import ROOT
-    files = []
+    files, forms = [], []
     for legacy in ("0", "1"):
         f = str(tmp_path / ("bn_%s.pt" % legacy))
         env = dict(os.environ, DN_BN_LEGACY=legacy)
-        subprocess.run([sys.executable, "-c", _BN_AB_SCRIPT % ROOT, f], check=True, env=env, timeout=600)
+        r = subprocess.run([sys.executable, "-c", _BN_AB_SCRIPT % ROOT, f], check=True, env=env, timeout=600, stdout=subprocess.PIPE, text=True)
         files.append(torch.load(f))
+        forms.append(r.stdout.split()[-3:])
+    # the query agrees with the entry points: DN_BN_LEGACY=1 takes the fused bias gradient and dz = NULL, not the SP apply
+    assert forms == [["1", "1", "1"], ["1", "0", "0"]], forms
     assert len(files[0]) == len(files[1]) > 60
     for a, b in zip(*files):
         assert a.dtype == b.dtype and a.shape == b.shape
@@ -928,3 +934,42 @@ def test_bn_backward_fuses_the_conv_bias_gradient(shape, up_a, sp):
     assert float((runs[1][4].double().cpu() - want).abs().max()) <= 2e-6 * scale
     assert float((runs[0][4].double().cpu() - want).abs().max()) <= 2e-6 * scale
     assert not train_ops.bn_backward_bias_supported(torch.empty(1, 4, 4, 24))    # c / 4 = 6: the general kernels, channel_sum stays
+
+
+@pytest.mark.parametrize("c", [16, 24, 48, 64, 96, 512, 1024])
+@pytest.mark.parametrize("groups", [1, 2])
+def test_bn_fused_forms_run_exactly_where_the_library_says(c, groups, monkeypatch):
+    """dn_bn_train_form_supported against the entry points of each fused form -- bn_apply(sp_out=), bn_backward(dbias=),
+    bn_backward(want_dz=False): where the query says yes they run, where it says no they raise DnError.  For one group the
+    refusal is checked once more with the Python predicates bypassed: then it is the C entry point's own."""
+    from disconet_amd import _lib, ops, train_ops
+    n, h, w = 2, 4, 6
+    g = torch.Generator().manual_seed(c + groups)
+    z = (torch.randn(n, h, w, c, generator=g) + 0.2).to(_dev())
+    mean, var = z.view(groups, -1, c).mean(1), z.view(groups, -1, c).var(1, unbiased=False)     # (dn_bn_train_stats: c <= 512)
+    gm, bt = torch.ones(c, device=_dev()), torch.zeros(c, device=_dev())
+    mask = torch.empty(z.numel() // 4, dtype=torch.uint8, device=_dev())
+    y = train_ops.bn_apply(z, mean, var, gm, bt, 1e-5, relu_mask=mask)
+    dy = torch.randn(n, h, w, c, generator=g).to(_dev())
+    dg, db, dbias = (torch.empty(c, device=_dev()) for _ in range(3))
+    sp = lambda: ops.SpTensor(n, h, w, c, device=_dev())
+    calls = {
+        train_ops.BN_FORM_SP_APPLY: lambda: train_ops.bn_apply(z, mean, var, gm, bt, 1e-5, relu_mask=mask, sp_out=sp()),
+        train_ops.BN_FORM_BIAS: lambda: train_ops.bn_backward(dy, y, z, mean, var, gm, 1e-5, dg, db, relu_mask=mask, dbias=dbias),
+        train_ops.BN_FORM_DZ_NULL: lambda: train_ops.bn_backward(dy, y, z, mean, var, gm, 1e-5, dg, db, relu_mask=mask, dbias=dbias,
+                                                                 sp_out=sp(), sp_lift=2.0, want_dz=False),
+    }
+    lib = _lib.load()
+    for form, call in calls.items():
+        if lib.dn_bn_train_form_supported(form, groups, n * h * w // groups, c):
+            out = call()
+            assert (out is None) == (form == train_ops.BN_FORM_DZ_NULL)
+            continue
+        with pytest.raises(_lib.DnError):
+            call()
+        if groups == 1:
+            with monkeypatch.context() as m:
+                m.setattr(train_ops, "bn_form_supported", lambda *a, **k: True)
+                with pytest.raises(_lib.DnError):
+                    call()
+    torch.cuda.synchronize()

@@ -105,6 +105,30 @@ def test_argument_errors_are_reported_not_thrown():
     assert b"dims" in lib.dn_last_error()
 
 
+def test_bn_fused_form_query_follows_the_documented_rule():
+    """dn_bn_train_form_supported (include/disconet_train.h) over channel counts, group counts and row counts at the
+    2^31-float4 limit of the fast kernels: the rule the header documents, never true past kMaxC = 512 or for two groups."""
+    from disconet_amd import _lib
+    lib = _lib.load()
+    legacy = os.environ.get("DN_BN_LEGACY", "")[:1] == "1"
+    seen = set()
+    for c in (16, 24, 48, 64, 96, 512, 1024):
+        at_limit = -(-2 ** 33 // c)                       # the first row count with rows * c / 4 >= 2^31
+        for groups in (1, 2):
+            for rows in (1, 4096, at_limit - 1, at_limit):
+                fast = groups == 1 and c % 4 == 0 and (c // 4) & (c // 4 - 1) == 0 and c <= 512 and rows * c // 4 < 2 ** 31
+                want = {0: fast and c % 16 == 0, 1: fast and not legacy, 2: fast and c % 16 == 0 and not legacy}
+                for form, w in want.items():
+                    got = lib.dn_bn_train_form_supported(form, groups, rows, c)
+                    assert got == int(w), (form, groups, rows, c, got)
+                    seen.add((form, got))
+                    if c == 1024 or groups > 1:
+                        assert got == 0
+    assert (0, 1) in seen and (0, 0) in seen and (2, 0) in seen
+    assert lib.dn_bn_train_form_supported(3, 1, 4096, 64) == 0              # no such form
+    assert lib.dn_bn_train_form_supported(0, 1, 0, 64) == 0                 # no rows
+
+
 def test_packed_weight_image_sizes():
     """size queries are host arithmetic (no GPU): 9 tap blocks per 16-channel chunk, chunks padded to a
     multiple of 4; a 3x3 stride-1 layer over a nearest-upsampled first source packs that source's chunks
