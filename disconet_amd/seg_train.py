@@ -20,7 +20,7 @@ gradients enter the BatchNorm backward of the layer that produced it (its `dy_b`
 import torch
 
 from . import ops, train_ops as T
-from .train import TrainEngine, _Layer, _EPS, _MOMENTUM
+from .train import TrainEngine, _Layer, _fusion_mlp_layers
 
 _DOUBLES = ("inc", "down1", "down2", "down3", "down4", "up1", "up2", "up3", "up4")
 
@@ -50,10 +50,7 @@ class SegTrainEngine(TrainEngine):
         for k in (1, 2, 3, 4):
             double("down%d" % k, getattr(m, "down%d" % k).maxpool_conv[1])
             double("up%d" % k, getattr(m, "up%d" % k).conv)
-        f = m.pixel_weighted_fusion
-        for i, (cname, bname) in enumerate((("conv1_2", "bn1_2"), ("conv1_3", "bn1_3")), 2):
-            conv = getattr(f, cname)
-            L["mlp%d" % i] = _Layer("mlp%d" % i, conv.weight, conv.bias, getattr(f, bname), 1)
+        L.update(_fusion_mlp_layers(m.pixel_weighted_fusion))
         self.L = L
 
     # ------------------------------------------------------------------
@@ -99,15 +96,7 @@ class SegTrainEngine(TrainEngine):
         logits, d_out = self._conv(m.outc.conv.weight, m.outc.conv.bias, x9, ksize=1)
         self.sctx = dict(x1=x1, x2=x2, x3=x3, fused=fused, x9=x9, d_out=d_out)
 
-        self._tracked = []
-        for lay in L.values():          # running statistics, the reference's momentum update (inside the statistics' launch where
-            if lay.name.startswith("mlp"):      # _layer_fwd could fuse it: `running_done`)
-                continue
-            c = lay.ctx
-            self._update_running(lay.bn, c["mean"], c["var"], c["z"].numel() // c["z"].shape[-1], done=c.get("running_done", False))
-        if self._tracked:
-            torch._foreach_add_(self._tracked, 1)
-        self._tracked = []
+        self._update_running_stats()
         self.outs = dict(x9=x9, x8=x8, x7=x7, x6=x6, x5=x5, fused=fused)
         self.last_logits = logits
         return logits

@@ -39,13 +39,21 @@ _MOMENTUM = 0.1
 
 
 class _Layer:
-    """conv (+ BatchNorm in training mode + ReLU) of the graph and what its backward needs"""
+    """conv (+ BatchNorm in training mode + ReLU) of the graph and what its backward needs.  per_call: the BatchNorm's
+    statistics are one group per call of the attention MLP, and its running statistics are updated once per CALL
+    (TrainEngine._update_running_stats); every other layer's BatchNorm is updated once per forward"""
 
-    def __init__(self, name, conv_w, conv_b, bn, ksize, stride=1):
+    def __init__(self, name, conv_w, conv_b, bn, ksize, stride=1, per_call=False):
         self.name, self.w, self.b, self.bn = name, conv_w, conv_b, bn
-        self.ksize, self.stride = ksize, stride
+        self.ksize, self.stride, self.per_call = ksize, stride, per_call
         self.c_out, self.c_in = conv_w.shape[0], conv_w.shape[1]
         self.ctx = None
+
+
+def _fusion_mlp_layers(f):
+    """the attention MLP's two hidden 1x1 layers (pixel_weighted_fusion conv1_2 / bn1_2, conv1_3 / bn1_3): per-call statistics"""
+    return {"mlp%d" % i: _Layer("mlp%d" % i, getattr(f, "conv1_%d" % i).weight, getattr(f, "conv1_%d" % i).bias,
+                                getattr(f, "bn1_%d" % i), 1, per_call=True) for i in (2, 3)}
 
 
 def _desc_key(d):
@@ -303,10 +311,7 @@ class TrainEngine:
                                    enc.bn_compress, 1)
             L["decompress"] = _Layer("decompress", enc.com_decompresser.weight, enc.com_decompresser.bias,
                                      enc.bn_decompress, 1)
-        f = m.pixel_weighted_fusion
-        for i, (cname, bname) in enumerate((("conv1_2", "bn1_2"), ("conv1_3", "bn1_3")), 2):
-            conv = getattr(f, cname)
-            L["mlp%d" % i] = _Layer("mlp%d" % i, conv.weight, conv.bias, getattr(f, bname), 1)
+        L.update(_fusion_mlp_layers(m.pixel_weighted_fusion))
         self.L = L
 
     # ------------------------------------------------------------------
@@ -408,11 +413,8 @@ class TrainEngine:
         w = lay.w if w is None else w
         b = lay.b if b is None else b
         z, d = self._conv(w, b, src0, src1, up0, lay.stride, lay.ksize)
-        # one process, one group, the layer's own BatchNorm: the running-statistics update rides in the statistics' finish launch
-        # (the momentum updates of different BatchNorms touch different buffers: their order is free)
-        fused_running = lay.bn is not None and groups == 1 and (self.shard is None or self.shard.world == 1)
-        mean, var = T.bn_stats(z, groups, running=(lay.bn.running_mean, lay.bn.running_var, _MOMENTUM) if fused_running else None,
-                               **self._bn_sync(z, groups))
+        running = (lay.bn.running_mean, lay.bn.running_var, _MOMENTUM) if self._fused_running(lay) else None
+        mean, var = T.bn_stats(z, groups, running=running, **self._bn_sync(z, groups))
         gamma = lay.bn.weight if gamma is None else gamma
         beta = lay.bn.bias if beta is None else beta
         # the backward's ReLU gate as one byte per four channels: its two passes then do not read y (1/16 of the bytes)
@@ -424,7 +426,7 @@ class TrainEngine:
         if y_sp is not None:
             y._dn_sp = y_sp
         lay.ctx = dict(src0=src0, src1=src1, up0=up0, z=z, y=y, mean=mean, var=var, desc=d,
-                       groups=groups, w=w, gamma=gamma, mask=mask, running_done=fused_running)
+                       groups=groups, w=w, gamma=gamma, mask=mask)
         return y
 
     def _bn_sync(self, z, groups):
@@ -435,16 +437,43 @@ class TrainEngine:
             return {}
         return {"sync": self.shard.sum_, "norm_rows": (z.numel() // z.shape[-1]) * self.shard.world}
 
-    def _update_running(self, bn, mean, var, rows, order=None, calls=1, done=False):
-        """done: the momentum update already ran inside the statistics' finish launch (_layer_fwd); only the call counter is left"""
-        if not done:
-            if self.shard is not None and order is None:
-                rows = rows * self.shard.world            # the unbiased variance's n / (n - 1) is the global batch's
-            T.bn_update_running(mean, var, rows, bn.running_mean, bn.running_var, _MOMENTUM, order)
-        if calls == 1 and getattr(self, "_tracked", None) is not None:
-            self._tracked.append(bn.num_batches_tracked)      # forward() adds 1 to all of them in one launch
-        else:
-            bn.num_batches_tracked.add_(calls)
+    def _fused_running(self, lay):
+        """does the momentum update of the layer's running statistics ride in its statistics' finish launch?  Only where this
+        forward updates that BatchNorm exactly once, from that launch's statistics: the layer's own BatchNorm, not per_call, no
+        cross-rank sync.  _update_running_stats does every other update."""
+        return lay.bn is not None and not lay.per_call and (self.shard is None or self.shard.world == 1)
+
+    def _update_running_stats(self, heads=()):
+        """The running-statistics updates that _layer_fwd did not fuse, and every call counter, once at the end of a forward
+        (the momentum updates of different BatchNorms touch different buffers: their order is free).
+        heads: (BatchNorm, mean, var, z) of BatchNorms outside the layer table, updated once per forward."""
+        m, F, fc = self.model, self.F, self.fctx
+        world = self.shard.world if self.shard is not None else 1
+        once = [lay for lay in self.L.values() if not lay.per_call]
+        unfused = [(lay.bn, lay.ctx["mean"], lay.ctx["var"], lay.ctx["z"]) for lay in once if not self._fused_running(lay)]
+        for bn, mean, var, z in unfused + list(heads):
+            # (an agent shard: the statistics span every rank's images -- the unbiased variance's n / (n - 1) is the global batch's)
+            T.bn_update_running(mean, var, z.numel() // z.shape[-1] * world, bn.running_mean, bn.running_var, _MOMENTUM)
+        # the attention MLP's BatchNorms: the reference updates them once per CALL, in its loop order (scene, then ego)
+        f = m.pixel_weighted_fusion
+        per_call = [(f.bn1_1, fc["mean1"], fc["var1"])] + [(lay.bn, lay.ctx["mean"], lay.ctx["var"]) for lay in self.L.values()
+                                                            if lay.per_call]
+        n_calls, order, rows = F["n_calls"], F["order"], lambda t: t
+        if world > 1:
+            # every rank owns some egos' calls: the per-call statistics travel (all-gather) and every rank replays all of them
+            calls = self.shard.calls_in_reference_order(
+                fusion_call_counts(m.agent_num, m.only_v2i, self._num_agent_cpu, self._batch), F["n_calls"])
+            local = F["order"].long()
+            n_calls, order = calls["total"], calls["index"]
+            rows = lambda t: self.shard.gather_padded(t[local], calls["max_per_rank"]).reshape(-1, t.shape[1])
+        if n_calls:
+            order, hw = order.to(fc["z1"].device), fc["z1"].shape[1] * fc["z1"].shape[2]
+            for bn, mean, var in per_call:
+                T.bn_update_running(rows(mean), rows(var), hw, bn.running_mean, bn.running_var, _MOMENTUM, order)
+        # every call counter in one launch
+        counters = [lay.bn.num_batches_tracked for lay in once] + [h[0].num_batches_tracked for h in heads]
+        torch._foreach_add_(counters + [bn.num_batches_tracked for bn, _, _ in per_call],
+                            [1] * len(counters) + [n_calls] * len(per_call))
 
     def _layer_bwd(self, lay, dy_a, G, dy_b=None, up_a=False, need_dx=True, gw=None, gb=None,
                    ggamma=None, gbeta=None, s2d_ok=False):
@@ -780,22 +809,9 @@ class TrainEngine:
         loc_out, dr = self._conv(reg[3].weight, reg[3].bias, h1[..., 32:], ksize=1)
         self.head_ctx = dict(h1=h1, dc=dc, dr=dr)
 
-        # running statistics (momentum updates in the reference's call order)
-        self._tracked = []
-        for lay in L.values():
-            if lay.name.startswith("mlp"):
-                continue
-            c = lay.ctx
-            self._update_running(lay.bn, c["mean"], c["var"], c["z"].numel() // c["z"].shape[-1], done=c.get("running_done", False))
         hc = self.head1.ctx
-        rows = (hc["z"].numel() // 64) * (sh.world if sh is not None else 1)
-        T.bn_update_running(hc["mean"][:, :32], hc["var"][:, :32], rows, cls.bn1.running_mean,
-                            cls.bn1.running_var, _MOMENTUM)
-        T.bn_update_running(hc["mean"][:, 32:], hc["var"][:, 32:], rows, reg[1].running_mean,
-                            reg[1].running_var, _MOMENTUM)
-        self._tracked += [cls.bn1.num_batches_tracked, reg[1].num_batches_tracked]
-        torch._foreach_add_(self._tracked, 1)      # every layer's call counter in one launch (25 one-element adds before)
-        self._tracked = []
+        self._update_running_stats(heads=((cls.bn1, hc["mean"][:, :32], hc["var"][:, :32], hc["z"]),
+                                          (reg[1], hc["mean"][:, 32:], hc["var"][:, 32:], hc["z"])))
 
         nI, h, w = cls_out.shape[0], cls_out.shape[1], cls_out.shape[2]
         self.outs = dict(x5=x5, x6=x6, x7=x7, x8=x8, fused=x3f)
@@ -808,7 +824,6 @@ class TrainEngine:
         f = m.pixel_weighted_fusion
         C = maps.shape[-1]
         P = NI + NW
-        hw = maps.shape[1] * maps.shape[2]
         if NW:
             T.warp_list(maps, F["poses"], F["src_image"], out=maps[NI:])
         # W1 = [W_ego | W_nbr]: two 1x1 convs over column cuts of one weight
@@ -825,26 +840,6 @@ class TrainEngine:
         weights = T.fuse_combine(z4, maps, F["first"], F["pair_index"], F["map_image"], F["ego_out"], fused)
         self.fctx = dict(maps=maps, NI=NI, NW=NW, z1=z1, mean1=mean1, var1=var1, h1=h1, d_e=d_e, d_f=d_f,
                          h3=h3, z4=z4, d4=d4, weights=weights)
-        stats = ((f.bn1_1, mean1, var1), (f.bn1_2, L["mlp2"].ctx["mean"], L["mlp2"].ctx["var"]),
-                 (f.bn1_3, L["mlp3"].ctx["mean"], L["mlp3"].ctx["var"]))
-        if self.shard is not None and self.shard.world > 1:
-            # the reference updates the MLP's running statistics once per CALL, in its loop order (scene, then ego): every
-            # rank owns some egos' calls, so the per-call statistics travel (all-gather) and every rank replays all of them
-            calls = self.shard.calls_in_reference_order(
-                fusion_call_counts(m.agent_num, m.only_v2i, self._num_agent_cpu, self._batch), F["n_calls"])
-            if calls["total"]:
-                local = F["order"][:F["n_calls"]].long()
-                for bn, mean, var in stats:
-                    allm = self.shard.gather_padded(mean[local], calls["max_per_rank"])
-                    allv = self.shard.gather_padded(var[local], calls["max_per_rank"])
-                    T.bn_update_running(allm.reshape(-1, mean.shape[1]), allv.reshape(-1, var.shape[1]), hw, bn.running_mean,
-                                        bn.running_var, _MOMENTUM, calls["index"].to(mean.device))
-                    bn.num_batches_tracked += calls["total"]
-        elif F["n_calls"]:
-            for bn, mean, var in stats:
-                T.bn_update_running(mean, var, hw, bn.running_mean, bn.running_var, _MOMENTUM,
-                                    F["order"][:F["n_calls"]].contiguous())
-                bn.num_batches_tracked += F["n_calls"]
         return fused
 
     # ------------------------------------------------------------------

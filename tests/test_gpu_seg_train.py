@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import cases
-from tests.test_gpu_train_step import _assert_grads
+from tests.test_gpu_train_step import _assert_fusion_bns_then_sync, _assert_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -126,6 +126,28 @@ def test_seg_train_step_matches_oracle(case, monkeypatch):
         want = ref_eval(x, trans, na, c["batch"])
         got = model(x.cuda(), trans.cuda(), na.cuda(), c["batch"])
     assert float((got.cpu() - want).abs().max()) < 1e-4 * max(1.0, float(want.abs().max()) / 5.0)
+
+
+def test_seg_single_agent_step_updates_the_mlp_bns_per_call():
+    """the detector's single-agent check (test_gpu_train_step.py) on the segmentation engine: one agent, batch 1, P = 1 pair"""
+    from disconet_amd import SegDiscoNet, SegModule
+    from disconet_amd.synthetic import make_scene_batch
+    from oracle.seg_train_ref import seg_train_step
+    ref = cases.seg_ref_model(1)
+    model = SegDiscoNet(num_agent=1)
+    model.load_state_dict(ref.state_dict())
+    model = model.cuda()
+    bevs, trans, na = make_scene_batch(1, 1, 128)
+    x = bevs[:, 0].permute(0, 3, 1, 2).contiguous()
+    labels = torch.randint(0, 8, (1, 128, 128), generator=torch.Generator().manual_seed(31))
+    opt = torch.optim.Adam(ref.parameters(), lr=1e-3)
+    mod = SegModule(model, lr=1e-3)
+    data = {"bev_seq": x.cuda(), "trans_matrices": trans.cuda(), "num_agent": na.cuda(), "labels": labels.cuda()}
+    for step in (1, 2):
+        seg_train_step(ref, opt, x, trans, na, 1, labels)
+        mod.step(data, 1)
+        assert mod._trainer.engine.F["n_calls"] == 1
+        _assert_fusion_bns_then_sync(model, ref, step)
 
 
 def test_seg_train_step_at_baseline_size_properties():

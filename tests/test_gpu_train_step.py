@@ -22,12 +22,14 @@ from tests import cases
 pytestmark = pytest.mark.gpu
 
 STEP_CASES = cases.TRAIN_CASES
+# one agent, batch 1: the attention MLP sees P = 1 pair (no golden entry: test_single_agent_step_updates_the_mlp_bns_per_call)
+SOLO_CASE = dict(map_hw=128, agents=1, batch=1, live=None, jitter=None)
 
 
 def _setup(case, math, only_v2i=False, compress_level=0, layer=3):
     from disconet_amd import Config, DiscoNet
     from disconet_amd.synthetic import make_scene_batch, make_train_targets
-    c = STEP_CASES[case]
+    c = case if isinstance(case, dict) else STEP_CASES[case]
     ref = cases.ref_model(c["map_hw"], c["agents"], kd_flag=0, only_v2i=only_v2i,
                           compress_level=compress_level, layer=layer)
     cfg = Config(map_hw=c["map_hw"])
@@ -475,6 +477,42 @@ def test_train_step_scene_with_a_single_live_agent(monkeypatch):
     for name, b in model.named_buffers():          # MLP BNs saw 5 calls, in the reference's order
         if "pixel_weighted_fusion" in name and name.endswith("num_batches_tracked"):
             assert int(b) == int(ref_buf[name]) == 5, name
+
+
+def _assert_fusion_bns_then_sync(model, ref, calls):
+    """every pixel_weighted_fusion.bn1_* buffer against the oracle's (the bound of test_train_step_matches_oracle's buffer
+    check), then the oracle takes the HIP model's parameters for the next step: Adam's first move of a conv bias in front of a
+    BatchNorm follows the sign of a rounding-noise gradient, differently in each implementation, and shifts the next batch mean"""
+    ref_buf = dict(ref.named_buffers())
+    bufs = {n: b for n, b in model.named_buffers() if n.startswith("pixel_weighted_fusion.bn1_")}
+    assert len(bufs) == 9, sorted(bufs)
+    for name, b in bufs.items():
+        r = ref_buf[name]
+        if name.endswith("num_batches_tracked"):
+            assert int(b) == int(r) == calls, name
+        else:
+            assert float((b.cpu() - r).abs().max()) < 1e-4 * max(float(r.abs().max()), 1.0), name
+    ref_named = dict(ref.named_parameters())
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            ref_named[name].copy_(p.cpu())
+
+
+def test_single_agent_step_updates_the_mlp_bns_per_call():
+    """one agent, batch 1: the attention MLP's statistics are one group (P = 1 pair), yet its BatchNorms take the per-call
+    update only -- not also the fused update of a one-group statistics launch.  Checked after each of two steps."""
+    from disconet_amd import CoDetModule
+    from oracle.train_ref import train_step
+    c, ref, model, (bevs, trans, na), (labels, targets, mask) = _setup(SOLO_CASE, "f16x3")
+    opt = torch.optim.Adam(ref.parameters(), lr=1e-3)
+    mod = CoDetModule(model, lr=1e-3)
+    data = {"bev_seq": bevs.cuda(), "trans_matrices": trans.cuda(), "num_agent": na.cuda(),
+            "labels": labels.cuda(), "reg_targets": targets.cuda(), "reg_loss_mask": mask.cuda()}
+    for step in (1, 2):
+        train_step(ref, opt, bevs, trans, na, c["batch"], labels, targets, mask)
+        mod.step(data, c["batch"])
+        assert mod.engine.F["n_calls"] == 1 and mod.engine.F["n_warps"] == 0
+        _assert_fusion_bns_then_sync(model, ref, step)
 
 
 def test_backward_after_a_second_forward_fails_loudly():
