@@ -20,6 +20,7 @@ forward path packs them once into the kernels' tile-major layouts and runs
 NHWC (channels-last) end to end.  There is no torch/CPU fallback: tensors must
 be on the GPU and the shared object must be built.
 """
+import collections
 import os
 import re
 
@@ -44,10 +45,43 @@ _DEC_CONVS = [  # name, c_in, c_out
     ("conv7_1", 128 + 64, 64), ("conv7_2", 64, 64),
     ("conv8_1", 64 + 32, 32), ("conv8_2", 32, 32),
 ]
+# the encoder's pyramid levels: the last layer of group k yields e[k]
+_ENC_GROUPS = (("conv_pre_1", "conv_pre_2"), ("conv1_1", "conv1_2", "conv3d_1"),
+               ("conv2_1", "conv2_2", "conv3d_2"), ("conv3_1", "conv3_2"), ("conv4_1", "conv4_2"))
 
 
 def _bn_name(conv_name):
     return "bn" + conv_name[len("conv"):]
+
+
+# one conv of a network's layer table.  up_split = (c0, c1): the layer reads cat([up2(src0), src1]) with these channel
+# counts (the decoder's *_1 convs); bn None: a linear output conv
+ConvRow = collections.namedtuple("ConvRow", "name weight bias bn ksize stride up_split")
+
+
+def backbone_layers(enc, dec):
+    """the detector backbone's convs in plan order: the encoder (with the 1x1x1 Conv3Ds and, when built, the compress
+    pair) from `enc`, the decoder from `dec` -- the same module for the teacher's STPN"""
+    for name, _, _, stride in _ENC_CONVS:
+        conv = getattr(enc, name)
+        yield ConvRow(name, conv.weight, conv.bias, getattr(enc, _bn_name(name)), 3, stride, None)
+    for name in ("conv3d_1", "conv3d_2"):
+        m = getattr(enc, name)
+        yield ConvRow(name, m.conv3d.weight, m.conv3d.bias, m.bn3d, 1, 1, None)
+    if enc.compress_level > 0:       # 1x1 compress / decompress of the exchanged map
+        yield ConvRow("compress", enc.com_compresser.weight, enc.com_compresser.bias, enc.bn_compress, 1, 1, None)
+        yield ConvRow("decompress", enc.com_decompresser.weight, enc.com_decompresser.bias, enc.bn_decompress, 1, 1, None)
+    for name, cin, cout in _DEC_CONVS:
+        conv = getattr(dec, name)
+        # conv5_1..conv8_1 read cat([up2(deeper level), skip]): the deeper level has 2 * cout channels
+        split = (2 * cout, cin - 2 * cout) if name.endswith("_1") else None
+        yield ConvRow(name, conv.weight, conv.bias, getattr(dec, _bn_name(name)), 3, 1, split)
+
+
+def _pack_layers(rows, math):
+    """the plan's packed convs, one per row of a layer table"""
+    return {r.name: _ConvLayer(r.name, r.weight, r.bias, r.bn, r.ksize, r.stride, relu=r.bn is not None, math=math,
+                               up_split=r.up_split) for r in rows}
 
 
 class _Conv3DParams(nn.Module):
@@ -272,210 +306,95 @@ class _ConvPostLayer:
         return out_a, out_b
 
 
-class DiscoNet(nn.Module):
-    def __init__(self, config, layer=3, in_channels=13, kd_flag=True, num_agent=5,
-                 compress_level=0, only_v2i=False):
-        super().__init__()
-        self.kd_flag = kd_flag
-        self.layer = layer
-        self.agent_num = num_agent
-        self.only_v2i = only_v2i
-        self.in_channels = in_channels
-        self.category_num = config.category_num
-        self.anchor_num_per_loc = len(config.anchor_size)
-        self.box_code_size = config.box_code_size
-        self.out_seq_len = 1 if config.only_det else config.pred_len
-
-        self.u_encoder = _EncoderParams(in_channels, compress_level)
-        self.decoder = _DecoderParams()
-        self.classification = _ClsHeadParams(config)
-        self.regression = _RegHeadParams(config, self.out_seq_len)
-        self.pixel_weighted_fusion = _FusionParams(LAYER_CHANNEL[layer])
-
-        self._plan = None
-        self._plan_sig = None
-        # conv arithmetic: "f16x3" (default) = split-f16: every fp32 operand as hi + lo halves,
-        # three f16 MFMAs per product, fp32 accumulate -- max abs deviation from the fp32 oracle
-        # ~1e-5 over the whole network (the 1e-4 parity bar; same size as the exact mode's own
-        # summation-order noise); needs |activations|, |weights| < 65504.  "f32" = exact-fp32
-        # MFMA at half the throughput.  Not a constructor argument so the reference's signature
-        # is untouched: set model.conv_math or DISCONET_CONV_MATH before the first forward.
-        # "sp" (the default) = the same split-f16 arithmetic with the activations kept pre-split in HBM
-        # (ops.SpTensor, csrc/conv_sp.hip): no conversion work in the conv loop.
-        self.conv_math = os.environ.get("DISCONET_CONV_MATH", "sp")
-        # fold the 1x1 layers that follow a 64-channel 3x3 conv into that conv's launch
-        self.fuse_1x1 = os.environ.get("DISCONET_FUSE_1X1", "1") != "0"
-        # one-launch attention MLP + softmax + weighted sum (csrc/fuse_mlp.hip) instead of
-        # two 1x1 conv launches + the tail kernel (split-f16 engines, C in {64, 128, 256})
-        self.fuse_mlp = os.environ.get("DISCONET_FUSE_MLP", "1") != "0"
-        # run the encoder levels above the exchanged one beside the fusion block on a second HIP stream:
-        # REFUSED unless DISCONET_UNSAFE_OVERLAP=1 (the property below).  A kernel that shares a SIMD with
-        # the split-f16 conv kernels has been observed to compute with corrupted VGPR lanes (DESIGN.md
-        # 3.6 (B), profiles/r02_hazard_repro.txt), so the library runs strictly in stream order;
-        # bench.py --in-flight N > 1 sets the override and checksums every replay.
-        self._overlap_streams = False
-        self.overlap_streams = os.environ.get("DISCONET_OVERLAP", "0") == "1"
-        self._side = {}
-
-    @property
-    def overlap_streams(self):
-        return self._overlap_streams
-
-    @overlap_streams.setter
-    def overlap_streams(self, value):
-        self._overlap_streams = ops.check_overlap_request(value, "DiscoNet.overlap_streams")
-
-    # ------------------------------------------------------------------
-    # checkpoint compatibility
-    # ------------------------------------------------------------------
-    def _replicate_for_data_parallel(self):
-        # nn.DataParallel over ONE device never replicates (it calls self.module directly): the reference tools'
-        # wrapper works unchanged there.  Over several devices it would clone this module per call and per thread --
-        # replicas sharing one packed-weight plan and one stream: refused instead of undefined behaviour.
-        raise RuntimeError(
-            "disconet_amd: nn.DataParallel over more than one device is not supported (its per-call replicas would "
-            "share one packed-weight plan and one HIP stream).  Keep nn.DataParallel(model, device_ids=[k]) for one "
-            "device, or launch one process per GPU: python -m torch.distributed.run --nproc-per-node N ... "
-            "(bench.py --gpus N, disconet_amd.sharded)")
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        """Accepts a reference model_state_dict: strips the DataParallel
-        `module.` prefix and ignores the duplicate, unused parameters the
-        reference keeps because its encoder and decoder both instantiate the
-        whole Backbone (SURVEY.md Appx A.3)."""
-        own = set(super().state_dict().keys())
-        cleaned, dropped, unknown = {}, [], []
-        for k, v in state_dict.items():
-            k = k[len("module."):] if k.startswith("module.") else k
-            if k not in own and _DUPLICATE_BACKBONE_KEY.match(k):
-                dropped.append(k)      # the half of the shared Backbone definition this side never runs
-            elif k not in own and (k.startswith("u_encoder.") or k.startswith("decoder.")):
-                # The duplicate-key list above is written from recollection (the reference source is not in
-                # the mount).  A Backbone key it does not know is dropped WITH a warning rather than failing
-                # the load of a real checkpoint: every parameter this model runs is in `own`, and a missing
-                # one still fails torch's strict check below.
-                unknown.append(k)
-            else:
-                cleaned[k] = v         # anything else: torch reports it when it is unexpected (strict)
-        if unknown:
-            import warnings
-            warnings.warn("DiscoNet.load_state_dict: dropped %d Backbone keys this model does not run and the "
-                          "duplicate-Backbone list does not name: %s" % (len(unknown), ", ".join(sorted(unknown)[:8])))
-        self._plan = None
-        return super().load_state_dict(cleaned, strict=strict, **kw)
-
-    def _side_stream(self, device):
-        key = str(device)
-        if key not in self._side:
-            self._side[key] = torch.cuda.Stream(device=device)
-        return self._side[key]
-
-    def train(self, mode=True):
-        """train(): forward() runs the training-mode graph of disconet_amd/train.py (batch
-        statistics, explicit HIP backward); eval(): the fused inference plan."""
-        self._plan = None
-        return super().train(mode)
-
-    # ------------------------------------------------------------------
-    # plan: packed weights + folded BN, rebuilt when any parameter changes
-    # ------------------------------------------------------------------
-    def _signature(self):
-        if self.conv_math not in ops.MATH_MODES:
-            raise ValueError("conv_math must be one of %s" % sorted(ops.MATH_MODES))
-        return (self.conv_math, self.fuse_1x1, self.fuse_mlp) + tuple((t.data_ptr(), t._version) for t in
-                                         list(self.parameters()) + list(self.buffers()))
-
-    def _build_plan(self):
-        enc, dec = self.u_encoder, self.decoder
-        P = {}
-        math = ops.MATH_MODES[self.conv_math]
-
-        def _Layer(*args, **kw):          # every conv of the plan uses the model's math mode
-            return _ConvLayer(*args, math=math, **kw)
-
-        for name, _, _, stride in _ENC_CONVS:
-            conv = getattr(enc, name)
-            P[name] = _Layer(name, conv.weight, conv.bias, getattr(enc, _bn_name(name)), 3, stride)
-        for name in ("conv3d_1", "conv3d_2"):
-            m = getattr(enc, name)
-            P[name] = _Layer(name, m.conv3d.weight, m.conv3d.bias, m.bn3d, 1)
-        if enc.compress_level > 0:
-            P["compress"] = _Layer("compress", enc.com_compresser.weight, enc.com_compresser.bias,
-                                   enc.bn_compress, 1)
-            P["decompress"] = _Layer("decompress", enc.com_decompresser.weight, enc.com_decompresser.bias,
-                                     enc.bn_decompress, 1)
-        for name, cin, cout in _DEC_CONVS:
-            conv = getattr(dec, name)
-            # conv5_1..conv8_1 read cat([up2(deeper level), skip]): the deeper level has 2 * cout channels
-            split = (2 * cout, cin - 2 * cout) if name.endswith("_1") else None
-            P[name] = _Layer(name, conv.weight, conv.bias, getattr(dec, _bn_name(name)), 3, up_split=split)
-        cls, reg = self.classification, self.regression.box_prediction
-        P["cls1"] = _Layer("cls1", cls.conv1.weight, cls.conv1.bias, cls.bn1, 3)
-        P["cls2"] = _Layer("cls2", cls.conv2.weight, cls.conv2.bias, None, 1, relu=False)
-        P["reg1"] = _Layer("reg1", reg[0].weight, reg[0].bias, reg[1], 3)
-        P["reg2"] = _Layer("reg2", reg[3].weight, reg[3].bias, None, 1, relu=False)
-
-        if math in (1, 2) and self.fuse_1x1:
-            # split-f16 only: 1x1 layers ride in the epilogue of the 3x3 conv before them
-            dev = cls.conv1.weight.device
-            n_cls, n_reg = cls.conv2.weight.shape[0], reg[3].weight.shape[0]
-            if n_cls % 4 == 0 and n_reg % 4 == 0 and n_cls + n_reg <= 64:
-                w1 = torch.cat([cls.conv1.weight, reg[0].weight], 0).detach()
-                w2 = torch.zeros(n_cls + n_reg, 64, device=dev)
-                w2[:n_cls, :32] = cls.conv2.weight.detach().reshape(n_cls, 32)
-                w2[n_cls:, 32:] = reg[3].weight.detach().reshape(n_reg, 32)
-                P["heads_fused"] = _ConvPostLayer(
-                    "heads", w1, torch.cat([P["cls1"].affine[0], P["reg1"].affine[0]]),
-                    torch.cat([P["cls1"].affine[1], P["reg1"].affine[1]]), w2,
-                    torch.ones(n_cls + n_reg, device=dev),
-                    torch.cat([cls.conv2.bias, reg[3].bias]).detach().float(), n_cls, False, math=math,
-                    block_diag=True)
-            c3 = enc.conv3d_1
-            s3, t3 = ops.fold_bn(c3.conv3d.bias, c3.bn3d, 64)
-            P["conv1_2_3d"] = _ConvPostLayer(
-                "conv1_2+3d", enc.conv1_2.weight.detach(), P["conv1_2"].affine[0], P["conv1_2"].affine[1],
-                c3.conv3d.weight.detach().reshape(64, 64), s3, t3, 64, True, math=math)
-
-        # attention MLP: layer 1 split W1 = [W1_ego | W1_nbr] (see fuse_tail.hip)
-        f = self.pixel_weighted_fusion
-        C = LAYER_CHANNEL[self.layer]
-        w1 = f.conv1_1.weight.detach().reshape(128, 2 * C)
-        dev = w1.device
-        w_cat = torch.cat([w1[:, :C], w1[:, C:]], 0).contiguous()          # [256, C]
-        ones256 = torch.ones(256, device=dev)
-        shift_g = torch.cat([f.conv1_1.bias.detach().float(), torch.zeros(128, device=dev)])
-        # the fusion block's kernels read fp32 NHWC maps: its two 1x1 launches stay on the NHWC engine
-        nmath = ops.nhwc_math(math)
-        P["mlp_g"] = _ConvLayer("mlp_g", w_cat.reshape(256, C, 1, 1), None, None, 1, relu=False,
-                                scale_shift=(ones256, shift_g.contiguous()), math=nmath)
-        P["mlp_f"] = _ConvLayer("mlp_f", w1[:, C:].contiguous().reshape(128, C, 1, 1), None, None, 1,
-                                relu=False, scale_shift=(torch.ones(128, device=dev),
-                                                         torch.zeros(128, device=dev)), math=nmath)
-        bn1_scale, bn1_shift = ops.fold_bn(None, f.bn1_1, 128)
-        s2, t2 = ops.fold_bn(f.conv1_2.bias, f.bn1_2, 32)
-        s3, t3 = ops.fold_bn(f.conv1_3.bias, f.bn1_3, 8)
-        tail = {
-            "bn1_scale": bn1_scale, "bn1_shift": bn1_shift,
-            "w2": f.conv1_2.weight.detach().reshape(32, 128).float().contiguous(),
-            "s2": s2, "t2": t2,
-            "w3": f.conv1_3.weight.detach().reshape(8, 32).float().contiguous(),
-            "s3": s3, "t3": t3,
+def attention_mlp_plan(f, C, math, fuse_mlp):
+    """the plan entries of the attention MLP (_FusionParams `f` over C-channel maps) for the model's math mode: its two
+    1x1 launches on the NHWC engine (layer 1 split W1 = [W1_ego | W1_nbr], see fuse_tail.hip) + the tail kernel's
+    parameters, and the one-launch form (_fuse_mlp) where the split-f16 engines, `fuse_mlp` and the channel count allow"""
+    w1 = f.conv1_1.weight.detach().reshape(128, 2 * C)
+    dev = w1.device
+    w_cat = torch.cat([w1[:, :C], w1[:, C:]], 0).contiguous()          # [256, C]
+    ones256 = torch.ones(256, device=dev)
+    shift_g = torch.cat([f.conv1_1.bias.detach().float(), torch.zeros(128, device=dev)])
+    # the fusion block's kernels read fp32 NHWC maps: its two 1x1 launches stay on the NHWC engine
+    nmath = ops.nhwc_math(math)
+    P = {}
+    P["mlp_g"] = _ConvLayer("mlp_g", w_cat.reshape(256, C, 1, 1), None, None, 1, relu=False,
+                            scale_shift=(ones256, shift_g.contiguous()), math=nmath)
+    P["mlp_f"] = _ConvLayer("mlp_f", w1[:, C:].contiguous().reshape(128, C, 1, 1), None, None, 1,
+                            relu=False, scale_shift=(torch.ones(128, device=dev),
+                                                     torch.zeros(128, device=dev)), math=nmath)
+    bn1_scale, bn1_shift = ops.fold_bn(None, f.bn1_1, 128)
+    s2, t2 = ops.fold_bn(f.conv1_2.bias, f.bn1_2, 32)
+    s3, t3 = ops.fold_bn(f.conv1_3.bias, f.bn1_3, 8)
+    tail = {"bn1_scale": bn1_scale, "bn1_shift": bn1_shift,
+            "w2": f.conv1_2.weight.detach().reshape(32, 128).float().contiguous(), "s2": s2, "t2": t2,
+            "w3": f.conv1_3.weight.detach().reshape(8, 32).float().contiguous(), "s3": s3, "t3": t3,
             "w4": f.conv1_4.weight.detach().reshape(8).float().contiguous(),
-            "b4": f.conv1_4.bias.detach().float().contiguous(),
-        }
-        P["_tail_tensors"] = tail                 # keep the storage alive
-        P["_tail"] = ops.make_tail_params(tail)
-        if math != 0 and self.fuse_mlp and ops.fuse_mlp_supported(C):
-            # split-f16 engines: the whole attention MLP + agent softmax + weighted sum in one launch
-            P["_fuse_mlp"], P["_fuse_mlp_tensors"] = ops.make_fuse_mlp_params(
-                w1, f.conv1_1.bias, (bn1_scale, bn1_shift),
-                f.conv1_2.weight.reshape(32, 128), f.conv1_2.bias, ops.fold_bn(None, f.bn1_2, 32),
-                f.conv1_3.weight.reshape(8, 32), f.conv1_3.bias, ops.fold_bn(None, f.bn1_3, 8),
-                f.conv1_4.weight, f.conv1_4.bias, C)
-        return P
+            "b4": f.conv1_4.bias.detach().float().contiguous()}
+    P["_tail_tensors"] = tail                 # keep the storage alive
+    P["_tail"] = ops.make_tail_params(tail)
+    if math != 0 and fuse_mlp and ops.fuse_mlp_supported(C):
+        # split-f16 engines: the whole attention MLP + agent softmax + weighted sum in one launch
+        P["_fuse_mlp"], P["_fuse_mlp_tensors"] = ops.make_fuse_mlp_params(
+            w1, f.conv1_1.bias, (bn1_scale, bn1_shift),
+            f.conv1_2.weight.reshape(32, 128), f.conv1_2.bias, ops.fold_bn(None, f.bn1_2, 32),
+            f.conv1_3.weight.reshape(8, 32), f.conv1_3.bias, ops.fold_bn(None, f.bn1_3, 8),
+            f.conv1_4.weight, f.conv1_4.bias, C)
+    return P
+
+
+def disco_fuse(feat, trans_matrices, num_agent, batch_size, P, agents, only_v2i, want_weights=False,
+               ego_first=0, ego_count=None, sp_out=False):
+    """DiscoGraph fusion of one pyramid level.  `feat` holds the maps of ALL agents (agent-major NHWC); the result
+    covers the egos [ego_first, ego_first + ego_count) -- every agent on one GPU, this rank's agents when a scene is
+    sharded one agent per GPU (sharded.py)."""
+    A = agents
+    E = A if ego_count is None else ego_count
+    feat = ops.as_nhwc(feat)
+    n, h, w, c = feat.shape
+    B = batch_size
+    map_bytes = 4.0 * h * w * c
+    pairs = B * E * (A - 1)
+    warped = torch.empty((B, E, max(A - 1, 0), h, w, c), dtype=torch.float32, device=feat.device)
+    # the one-launch attention kernel takes the warped maps in its own (fragment-major) read order when the shape
+    # allows: an opaque intermediate between the two launches (include/disconet_hip.h :: dn_warp_neighbors_fm)
+    fm = ("_fuse_mlp" in P and A > 1 and ops.warp_fm_supported(h, w, c))
+    with region("warp", "warp_neighbors_kernel", 0.0, map_bytes * (n + pairs)):
+        ops.warp_neighbors(feat, trans_matrices, num_agent, B, A, only_v2i, ego_first, E, out=warped, fm=fm)
+    if "_fuse_mlp" in P:
+        flops = 2.0 * B * E * h * w * (128.0 * c * (2 + (A - 1)) + A * (128 * 32 + 32 * 8 + 8))
+        with region("fuse_mlp", "disco_fuse_mlp_kernel", flops, map_bytes * (3 * E * B + 2 * pairs)):
+            return ops.disco_fuse_mlp(feat, warped, num_agent, P["_fuse_mlp"], B, A, only_v2i,
+                                      want_weights, ego_first, E, sp_out=sp_out, fm=fm)
+    g = P["mlp_g"].run(feat[ego_first * B:(ego_first + E) * B])
+    fw = P["mlp_f"].run(warped.view(pairs, h, w, c)) if A > 1 else None
+    fused = torch.empty((E * B, h, w, c), dtype=torch.float32, device=feat.device)
+    with region("fuse_tail", "disco_fuse_tail_kernel", 0.0, map_bytes * (2 * E * B + pairs)):
+        return ops.disco_fuse_tail(feat, warped, g, fw, num_agent, P["_tail"], B, A,
+                                   only_v2i, want_weights, ego_first, E, out=fused)
+
+
+def _conv_math(mode):
+    """the ops.MATH_MODES value of a model's conv_math"""
+    if mode not in ops.MATH_MODES:
+        raise ValueError("conv_math must be one of %s" % sorted(ops.MATH_MODES))
+    return ops.MATH_MODES[mode]
+
+
+class _PlanModule(nn.Module):
+    """What DiscoNet, TeacherNet and SegDiscoNet share: the packed-weight plan (_build_plan), rebuilt when a parameter, a
+    buffer or the class's _plan_key() changes and dropped by train() and load_state_dict(), and the module plumbing of the
+    reference's tools (nn.DataParallel, `module.`-prefixed checkpoints)."""
+
+    _plan, _plan_sig = None, None
+
+    def _plan_key(self):
+        """what the plan depends on besides the parameters and buffers"""
+        return ()
 
     def _get_plan(self):
-        sig = self._signature()
+        sig = self._plan_key() + tuple((t.data_ptr(), t._version) for t in
+                                       list(self.parameters()) + list(self.buffers()))
         if self._plan is None or sig != self._plan_sig:
             self._check_finite_parameters()
             self._plan = self._build_plan()
@@ -491,12 +410,39 @@ class DiscoNet(nn.Module):
         bad = [n for n, t in list(self.named_parameters()) + list(self.named_buffers())
                if t.is_floating_point() and t.numel() and not bool(torch.isfinite(t).all())]
         if bad:
-            raise ops._lib.DnError("DiscoNet: non-finite values in %s%s: refusing to pack a plan whose outputs would hold "
-                                   "plausible garbage" % (", ".join(bad[:4]), " ..." if len(bad) > 4 else ""))
+            raise ops._lib.DnError("%s: non-finite values in %s%s: refusing to pack a plan whose outputs would hold "
+                                   "plausible garbage" % (type(self).__name__, ", ".join(bad[:4]),
+                                                          " ..." if len(bad) > 4 else ""))
 
-    # ------------------------------------------------------------------
-    # forward
-    # ------------------------------------------------------------------
+    def train(self, mode=True):
+        self._plan = None
+        return super().train(mode)
+
+    def _own_keys(self, state_dict):
+        """a checkpoint's entries under this module's names: the DataParallel `module.` prefix stripped"""
+        return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        self._plan = None
+        return super().load_state_dict(self._own_keys(state_dict), strict=strict, **kw)
+
+    def _replicate_for_data_parallel(self):
+        # nn.DataParallel over ONE device never replicates (it calls self.module directly): the reference tools'
+        # wrapper works unchanged there.  Over several devices it would clone this module per call and per thread --
+        # replicas sharing one packed-weight plan and one stream: refused instead of undefined behaviour.
+        raise RuntimeError(
+            "disconet_amd: nn.DataParallel over more than one device is not supported (its per-call replicas would "
+            "share one packed-weight plan and one HIP stream).  Keep nn.DataParallel(model, device_ids=[k]) for one "
+            "device, or launch one process per GPU: python -m torch.distributed.run --nproc-per-node N ... "
+            "(bench.py --gpus N, disconet_amd.sharded)")
+
+
+class _BackboneNet(_PlanModule):
+    """The detector backbone's inference walk, shared by DiscoNet and the distillation teacher.  `layer`: the exchanged
+    pyramid level, which leaves the conv engine as fp32 NHWC (None: every level stays in the engine's layout)."""
+
+    layer = None
+
     def _enc_input(self, bevs):
         if isinstance(bevs, ops.SpTensor):      # ops.scatter_dense_sp: already in the engine's layout
             return bevs
@@ -533,19 +479,17 @@ class DiscoNet(nn.Module):
         layer also writes the level as fp32 NHWC from its epilogue (the exchanged level: no dn_sp_to_nhwc pass);
         returns (level, nhwc copy or None)."""
         dual = nhwc_copy and self.conv_math == "sp"
-        unpack = lambda r: r if isinstance(r, tuple) else (r, None)
-        if k == 0:
-            pair = self._stem_pair(x, P) if not dual else None
+        if k == 0 and not dual:
+            pair = self._stem_pair(x, P)
             if pair is not None:
                 return pair, None
-            return unpack(P["conv_pre_2"].run(P["conv_pre_1"].run(x), nhwc_copy=dual))
-        if k == 1:
-            if "conv1_2_3d" in P:
-                return P["conv1_2_3d"].run(P["conv1_1"].run(x))[0], None
-            return unpack(P["conv3d_1"].run(P["conv1_2"].run(P["conv1_1"].run(x)), nhwc_copy=dual))
-        if k == 2:
-            return unpack(P["conv3d_2"].run(P["conv2_2"].run(P["conv2_1"].run(x)), nhwc_copy=dual))
-        return unpack(P["conv%d_2" % k].run(P["conv%d_1" % k].run(x), nhwc_copy=dual))
+        if k == 1 and "conv1_2_3d" in P:
+            return P["conv1_2_3d"].run(P["conv1_1"].run(x))[0], None
+        *first, last = _ENC_GROUPS[k]
+        for name in first:
+            x = P[name].run(x)
+        r = P[last].run(x, nhwc_copy=dual)
+        return r if isinstance(r, tuple) else (r, None)
 
     def encode(self, bevs, P):
         x = self._enc_input(bevs)
@@ -559,43 +503,9 @@ class DiscoNet(nn.Module):
             enc[3] = P["decompress"].run(P["compress"].run(enc[3]))
         # the exchanged level leaves the conv engine (fusion kernels, the agent all-gather): fp32 NHWC, written by the
         # producing conv's own epilogue where that form exists, else converted
-        enc[self.layer] = flat if flat is not None else ops.as_nhwc(enc[self.layer])
+        if self.layer is not None:
+            enc[self.layer] = flat if flat is not None else ops.as_nhwc(enc[self.layer])
         return enc
-
-    def fuse(self, feat, trans_matrices, num_agent, batch_size, P, want_weights=False,
-             ego_first=0, ego_count=None, sp_out=False):
-        """DiscoGraph fusion of the layer-`layer` maps.  `feat` holds the maps of
-        ALL agents (agent-major NHWC); the result covers the egos
-        [ego_first, ego_first + ego_count) -- every agent on one GPU, this rank's
-        agents when a scene is sharded one agent per GPU (sharded.py)."""
-        A = self.agent_num
-        E = A if ego_count is None else ego_count
-        feat = ops.as_nhwc(feat)
-        n, h, w, c = feat.shape
-        B = batch_size
-        map_bytes = 4.0 * h * w * c
-        pairs = B * E * (A - 1)
-        warped = torch.empty((B, E, max(A - 1, 0), h, w, c), dtype=torch.float32,
-                             device=feat.device)
-        # the one-launch attention kernel takes the warped maps in its own (fragment-major) read order when the shape
-        # allows: an opaque intermediate between the two launches (include/disconet_hip.h :: dn_warp_neighbors_fm)
-        fm = ("_fuse_mlp" in P and A > 1 and ops.warp_fm_supported(h, w, c))
-        with region("warp", "warp_neighbors_kernel", 0.0, map_bytes * (n + pairs)):
-            ops.warp_neighbors(feat, trans_matrices, num_agent, B, A, self.only_v2i,
-                               ego_first, E, out=warped, fm=fm)
-        if "_fuse_mlp" in P:
-            flops = 2.0 * B * E * h * w * (128.0 * c * (2 + (A - 1)) + A * (128 * 32 + 32 * 8 + 8))
-            with region("fuse_mlp", "disco_fuse_mlp_kernel", flops, map_bytes * (3 * E * B + 2 * pairs)):
-                return ops.disco_fuse_mlp(feat, warped, num_agent, P["_fuse_mlp"], B, A, self.only_v2i,
-                                          want_weights, ego_first, E, sp_out=sp_out, fm=fm)
-        g = P["mlp_g"].run(feat[ego_first * B:(ego_first + E) * B])
-        fw = None
-        if A > 1:
-            fw = P["mlp_f"].run(warped.view(pairs, h, w, c))
-        fused = torch.empty((E * B, h, w, c), dtype=torch.float32, device=feat.device)
-        with region("fuse_tail", "disco_fuse_tail_kernel", 0.0, map_bytes * (2 * E * B + pairs)):
-            return ops.disco_fuse_tail(feat, warped, g, fw, num_agent, P["_tail"], B, A,
-                                       self.only_v2i, want_weights, ego_first, E, out=fused)
 
     def decode(self, enc, P):
         x0, x1, x2, x3, x4 = enc
@@ -604,6 +514,136 @@ class DiscoNet(nn.Module):
         x7 = P["conv7_2"].run(P["conv7_1"].run(x6, x1, up0=True))
         x8 = P["conv8_2"].run(P["conv8_1"].run(x7, x0, up0=True))
         return x8, x7, x6, x5
+
+
+class DiscoNet(_BackboneNet):
+    def __init__(self, config, layer=3, in_channels=13, kd_flag=True, num_agent=5,
+                 compress_level=0, only_v2i=False):
+        super().__init__()
+        self.kd_flag = kd_flag
+        self.layer = layer
+        self.agent_num = num_agent
+        self.only_v2i = only_v2i
+        self.in_channels = in_channels
+        self.category_num = config.category_num
+        self.anchor_num_per_loc = len(config.anchor_size)
+        self.box_code_size = config.box_code_size
+        self.out_seq_len = 1 if config.only_det else config.pred_len
+
+        self.u_encoder = _EncoderParams(in_channels, compress_level)
+        self.decoder = _DecoderParams()
+        self.classification = _ClsHeadParams(config)
+        self.regression = _RegHeadParams(config, self.out_seq_len)
+        self.pixel_weighted_fusion = _FusionParams(LAYER_CHANNEL[layer])
+
+        # conv arithmetic: "f16x3" (default) = split-f16: every fp32 operand as hi + lo halves,
+        # three f16 MFMAs per product, fp32 accumulate -- max abs deviation from the fp32 oracle
+        # ~1e-5 over the whole network (the 1e-4 parity bar; same size as the exact mode's own
+        # summation-order noise); needs |activations|, |weights| < 65504.  "f32" = exact-fp32
+        # MFMA at half the throughput.  Not a constructor argument so the reference's signature
+        # is untouched: set model.conv_math or DISCONET_CONV_MATH before the first forward.
+        # "sp" (the default) = the same split-f16 arithmetic with the activations kept pre-split in HBM
+        # (ops.SpTensor, csrc/conv_sp.hip): no conversion work in the conv loop.
+        self.conv_math = os.environ.get("DISCONET_CONV_MATH", "sp")
+        # fold the 1x1 layers that follow a 64-channel 3x3 conv into that conv's launch
+        self.fuse_1x1 = os.environ.get("DISCONET_FUSE_1X1", "1") != "0"
+        # one-launch attention MLP + softmax + weighted sum (csrc/fuse_mlp.hip) instead of
+        # two 1x1 conv launches + the tail kernel (split-f16 engines, C in {64, 128, 256})
+        self.fuse_mlp = os.environ.get("DISCONET_FUSE_MLP", "1") != "0"
+        # run the encoder levels above the exchanged one beside the fusion block on a second HIP stream:
+        # REFUSED unless DISCONET_UNSAFE_OVERLAP=1 (the property below).  A kernel that shares a SIMD with
+        # the split-f16 conv kernels has been observed to compute with corrupted VGPR lanes (DESIGN.md
+        # 3.6 (B), profiles/r02_hazard_repro.txt), so the library runs strictly in stream order;
+        # bench.py --in-flight N > 1 sets the override and checksums every replay.
+        self._overlap_streams = False
+        self.overlap_streams = os.environ.get("DISCONET_OVERLAP", "0") == "1"
+        self._side = {}
+
+    @property
+    def overlap_streams(self):
+        return self._overlap_streams
+
+    @overlap_streams.setter
+    def overlap_streams(self, value):
+        self._overlap_streams = ops.check_overlap_request(value, "DiscoNet.overlap_streams")
+
+    def _own_keys(self, state_dict):
+        """Accepts a reference model_state_dict: strips the DataParallel
+        `module.` prefix and ignores the duplicate, unused parameters the
+        reference keeps because its encoder and decoder both instantiate the
+        whole Backbone (SURVEY.md Appx A.3)."""
+        own = set(self.state_dict().keys())
+        cleaned, dropped, unknown = {}, [], []
+        for k, v in super()._own_keys(state_dict).items():
+            if k not in own and _DUPLICATE_BACKBONE_KEY.match(k):
+                dropped.append(k)      # the half of the shared Backbone definition this side never runs
+            elif k not in own and (k.startswith("u_encoder.") or k.startswith("decoder.")):
+                # The duplicate-key list above is written from recollection (the reference source is not in
+                # the mount).  A Backbone key it does not know is dropped WITH a warning rather than failing
+                # the load of a real checkpoint: every parameter this model runs is in `own`, and a missing
+                # one still fails torch's strict check below.
+                unknown.append(k)
+            else:
+                cleaned[k] = v         # anything else: torch reports it when it is unexpected (strict)
+        if unknown:
+            import warnings
+            warnings.warn("DiscoNet.load_state_dict: dropped %d Backbone keys this model does not run and the "
+                          "duplicate-Backbone list does not name: %s" % (len(unknown), ", ".join(sorted(unknown)[:8])))
+        return cleaned
+
+    def _side_stream(self, device):
+        key = str(device)
+        if key not in self._side:
+            self._side[key] = torch.cuda.Stream(device=device)
+        return self._side[key]
+
+    # ------------------------------------------------------------------
+    # plan: packed weights + folded BN, rebuilt when any parameter changes
+    # ------------------------------------------------------------------
+    def _plan_key(self):
+        return (_conv_math(self.conv_math), self.fuse_1x1, self.fuse_mlp)
+
+    def _build_plan(self):
+        enc = self.u_encoder
+        math = ops.MATH_MODES[self.conv_math]
+        P = _pack_layers(backbone_layers(enc, self.decoder), math)
+        cls, reg = self.classification, self.regression.box_prediction
+        P["cls1"] = _ConvLayer("cls1", cls.conv1.weight, cls.conv1.bias, cls.bn1, 3, math=math)
+        P["cls2"] = _ConvLayer("cls2", cls.conv2.weight, cls.conv2.bias, None, 1, relu=False, math=math)
+        P["reg1"] = _ConvLayer("reg1", reg[0].weight, reg[0].bias, reg[1], 3, math=math)
+        P["reg2"] = _ConvLayer("reg2", reg[3].weight, reg[3].bias, None, 1, relu=False, math=math)
+
+        if math in (1, 2) and self.fuse_1x1:
+            # split-f16 only: 1x1 layers ride in the epilogue of the 3x3 conv before them
+            dev = cls.conv1.weight.device
+            n_cls, n_reg = cls.conv2.weight.shape[0], reg[3].weight.shape[0]
+            if n_cls % 4 == 0 and n_reg % 4 == 0 and n_cls + n_reg <= 64:
+                w1 = torch.cat([cls.conv1.weight, reg[0].weight], 0).detach()
+                w2 = torch.zeros(n_cls + n_reg, 64, device=dev)
+                w2[:n_cls, :32] = cls.conv2.weight.detach().reshape(n_cls, 32)
+                w2[n_cls:, 32:] = reg[3].weight.detach().reshape(n_reg, 32)
+                P["heads_fused"] = _ConvPostLayer(
+                    "heads", w1, torch.cat([P["cls1"].affine[0], P["reg1"].affine[0]]),
+                    torch.cat([P["cls1"].affine[1], P["reg1"].affine[1]]), w2,
+                    torch.ones(n_cls + n_reg, device=dev),
+                    torch.cat([cls.conv2.bias, reg[3].bias]).detach().float(), n_cls, False, math=math,
+                    block_diag=True)
+            c3 = enc.conv3d_1
+            s3, t3 = ops.fold_bn(c3.conv3d.bias, c3.bn3d, 64)
+            P["conv1_2_3d"] = _ConvPostLayer(
+                "conv1_2+3d", enc.conv1_2.weight.detach(), P["conv1_2"].affine[0], P["conv1_2"].affine[1],
+                c3.conv3d.weight.detach().reshape(64, 64), s3, t3, 64, True, math=math)
+        P.update(attention_mlp_plan(self.pixel_weighted_fusion, LAYER_CHANNEL[self.layer], math, self.fuse_mlp))
+        return P
+
+    # ------------------------------------------------------------------
+    # forward
+    # ------------------------------------------------------------------
+    def fuse(self, feat, trans_matrices, num_agent, batch_size, P, want_weights=False,
+             ego_first=0, ego_count=None, sp_out=False):
+        """DiscoGraph fusion of the layer-`layer` maps (disco_fuse)"""
+        return disco_fuse(feat, trans_matrices, num_agent, batch_size, P, self.agent_num, self.only_v2i,
+                          want_weights, ego_first, ego_count, sp_out)
 
     def heads(self, x8, P):
         if "heads_fused" in P:                          # conv1 of both heads + both conv2, one launch

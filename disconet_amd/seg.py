@@ -28,8 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .model import _ConvLayer, _FusionParams
-from .profiling import region
+from .model import ConvRow, _FusionParams, _pack_layers, _PlanModule, attention_mlp_plan, disco_fuse
 
 
 class _DoubleConv(nn.Module):
@@ -59,7 +58,19 @@ class _OutConv(nn.Module):
         self.conv = nn.Conv2d(cin, cout, 1)
 
 
-class SegDiscoNet(nn.Module):
+def unet_layers(m):
+    """the UNet's convs in plan order: the two 3x3 convs of each DoubleConv (<block>a, <block>b), then the 1x1 outc"""
+    blocks = [("inc", m.inc)]
+    for k in (1, 2, 3, 4):
+        blocks += [("down%d" % k, getattr(m, "down%d" % k).maxpool_conv[1]), ("up%d" % k, getattr(m, "up%d" % k).conv)]
+    for name, dc in blocks:
+        seq = dc.double_conv
+        yield ConvRow(name + "a", seq[0].weight, seq[0].bias, seq[1], 3, 1, None)
+        yield ConvRow(name + "b", seq[3].weight, seq[3].bias, seq[4], 3, 1, None)
+    yield ConvRow("outc", m.outc.conv.weight, m.outc.conv.bias, None, 1, 1, None)
+
+
+class SegDiscoNet(_PlanModule):
     FUSE_CHANNELS = 512
 
     def __init__(self, n_channels=13, n_classes=8, num_agent=5, kd_flag=False, compress_level=0,
@@ -74,85 +85,20 @@ class SegDiscoNet(nn.Module):
         self.up1, self.up2, self.up3, self.up4 = _Up(1024, 256), _Up(512, 128), _Up(256, 64), _Up(128, 64)
         self.outc = _OutConv(64, n_classes)
         self.pixel_weighted_fusion = _FusionParams(self.FUSE_CHANNELS)
-        self._plan, self._plan_sig = None, None
 
-    def _replicate_for_data_parallel(self):
-        # nn.DataParallel over ONE device never replicates (it calls self.module directly): the reference tools'
-        # wrapper works unchanged there.  Over several devices it would clone this module per call and per thread --
-        # replicas sharing one packed-weight plan and one stream: refused instead of undefined behaviour.
-        raise RuntimeError(
-            "disconet_amd: nn.DataParallel over more than one device is not supported (its per-call replicas would "
-            "share one packed-weight plan and one HIP stream).  Keep nn.DataParallel(model, device_ids=[k]) for one "
-            "device, or launch one process per GPU: python -m torch.distributed.run --nproc-per-node N ... "
-            "(bench.py --gpus N, disconet_amd.sharded)")
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        cleaned = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
-        self._plan = None
-        return super().load_state_dict(cleaned, strict=strict, **kw)
-
-    def train(self, mode=True):
-        """train(): SegModule.step / SegTrainStep run the explicit HIP training graph (seg_train.py); the module's
-        own forward() stays the eval plan -- a train()-mode forward() through autograd is not provided."""
-        self._plan = None
-        return super().train(mode)
+    # train(): SegModule.step / SegTrainStep run the explicit HIP training graph (seg_train.py); the module's own forward()
+    # stays the eval plan -- a train()-mode forward() through autograd is not provided.
 
     # ------------------------------------------------------------------
-    def _get_plan(self):
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
-        if self._plan is not None and sig == self._plan_sig:
-            return self._plan
-        P = {}
-
-        def double(name, dc):
-            seq = dc.double_conv
-            P[name + "a"] = _ConvLayer(name + "a", seq[0].weight, seq[0].bias, seq[1], 3, math=2)
-            P[name + "b"] = _ConvLayer(name + "b", seq[3].weight, seq[3].bias, seq[4], 3, math=2)
-
-        double("inc", self.inc)
-        for k in (1, 2, 3, 4):
-            double("down%d" % k, getattr(self, "down%d" % k).maxpool_conv[1])
-            double("up%d" % k, getattr(self, "up%d" % k).conv)
-        P["outc"] = _ConvLayer("outc", self.outc.conv.weight, self.outc.conv.bias, None, 1, relu=False, math=2)
-        # attention MLP at C = 512: layer 1 split W1 = [W_ego | W_nbr] on the NHWC engine + the tail kernel
-        f, C = self.pixel_weighted_fusion, self.FUSE_CHANNELS
-        w1 = f.conv1_1.weight.detach().reshape(128, 2 * C)
-        dev = w1.device
-        P["mlp_g"] = _ConvLayer("mlp_g", torch.cat([w1[:, :C], w1[:, C:]], 0).contiguous().reshape(256, C, 1, 1),
-                                None, None, 1, relu=False, math=1,
-                                scale_shift=(torch.ones(256, device=dev),
-                                             torch.cat([f.conv1_1.bias.detach().float(),
-                                                        torch.zeros(128, device=dev)]).contiguous()))
-        P["mlp_f"] = _ConvLayer("mlp_f", w1[:, C:].contiguous().reshape(128, C, 1, 1), None, None, 1, relu=False,
-                                math=1, scale_shift=(torch.ones(128, device=dev), torch.zeros(128, device=dev)))
-        bn1_scale, bn1_shift = ops.fold_bn(None, f.bn1_1, 128)
-        s2, t2 = ops.fold_bn(f.conv1_2.bias, f.bn1_2, 32)
-        s3, t3 = ops.fold_bn(f.conv1_3.bias, f.bn1_3, 8)
-        tail = {"bn1_scale": bn1_scale, "bn1_shift": bn1_shift,
-                "w2": f.conv1_2.weight.detach().reshape(32, 128).float().contiguous(), "s2": s2, "t2": t2,
-                "w3": f.conv1_3.weight.detach().reshape(8, 32).float().contiguous(), "s3": s3, "t3": t3,
-                "w4": f.conv1_4.weight.detach().reshape(8).float().contiguous(),
-                "b4": f.conv1_4.bias.detach().float().contiguous()}
-        P["_tail_tensors"], P["_tail"] = tail, ops.make_tail_params(tail)
-        self._plan, self._plan_sig = P, sig
+    def _build_plan(self):
+        # every conv on the SP engine; the attention MLP at C = 512 as two 1x1 launches on the NHWC engine + the tail kernel
+        P = _pack_layers(unet_layers(self), 2)
+        P.update(attention_mlp_plan(self.pixel_weighted_fusion, self.FUSE_CHANNELS, 2, fuse_mlp=False))
         return P
 
     def fuse(self, x4, trans, num_agent, batch_size, P):
         """DiscoGraph fusion of the bottleneck maps: x4 SpTensor / NHWC [A*B, h, w, 512] -> NHWC"""
-        A, B = self.agent_num, batch_size
-        feat = ops.as_nhwc(x4)
-        n, h, w, c = feat.shape
-        pairs = B * A * (A - 1)
-        map_bytes = 4.0 * h * w * c
-        warped = torch.empty((B, A, max(A - 1, 0), h, w, c), dtype=torch.float32, device=feat.device)
-        with region("warp", "warp_neighbors_kernel", 0.0, map_bytes * (n + pairs)):
-            ops.warp_neighbors(feat, trans, num_agent, B, A, self.only_v2i, 0, A, out=warped)
-        g = P["mlp_g"].run(feat)
-        fw = P["mlp_f"].run(warped.view(pairs, h, w, c)) if A > 1 else None
-        fused = torch.empty((A * B, h, w, c), dtype=torch.float32, device=feat.device)
-        with region("fuse_tail", "disco_fuse_tail_kernel", 0.0, map_bytes * (2 * A * B + pairs)):
-            return ops.disco_fuse_tail(feat, warped, g, fw, num_agent, P["_tail"], B, A, self.only_v2i,
-                                       False, 0, A, out=fused)
+        return disco_fuse(x4, trans, num_agent, batch_size, P, self.agent_num, self.only_v2i)
 
     def forward(self, bevs, trans_matrices, num_agent_tensor, batch_size=None):
         if self.training:

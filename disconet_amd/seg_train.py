@@ -20,9 +20,8 @@ gradients enter the BatchNorm backward of the layer that produced it (its `dy_b`
 import torch
 
 from . import ops, train_ops as T
-from .train import TrainEngine, _Layer, _fusion_mlp_layers
-
-_DOUBLES = ("inc", "down1", "down2", "down3", "down4", "up1", "up2", "up3", "up4")
+from .seg import unet_layers
+from .train import TrainEngine
 
 
 class SegTrainEngine(TrainEngine):
@@ -37,21 +36,8 @@ class SegTrainEngine(TrainEngine):
         # exact-fp32 MFMA, set model.train_math); data and weight gradients are always exact fp32 (train.py)
         return ops.nhwc_math(getattr(self.model, "train_math", "f16x3"))
 
-    def _graph(self):
-        m = self.model
-        L = {}
-
-        def double(name, dc):
-            seq = dc.double_conv
-            L[name + "a"] = _Layer(name + "a", seq[0].weight, seq[0].bias, seq[1], 3)
-            L[name + "b"] = _Layer(name + "b", seq[3].weight, seq[3].bias, seq[4], 3)
-
-        double("inc", m.inc)
-        for k in (1, 2, 3, 4):
-            double("down%d" % k, getattr(m, "down%d" % k).maxpool_conv[1])
-            double("up%d" % k, getattr(m, "up%d" % k).conv)
-        L.update(_fusion_mlp_layers(m.pixel_weighted_fusion))
-        self.L = L
+    def _layers(self):
+        return unet_layers(self.model)
 
     # ------------------------------------------------------------------
     def forward(self, x, trans_matrices, num_agent_tensor, batch_size):

@@ -16,60 +16,39 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .model import _DEC_CONVS, _ENC_CONVS, _ClsHeadParams, _Conv3DParams, _ConvLayer, _RegHeadParams, _bn_name
+from .model import (_DEC_CONVS, _BackboneNet, _ClsHeadParams, _EncoderParams, _RegHeadParams, _bn_name, _conv_math,
+                    _pack_layers, backbone_layers)
 
 
-class _BackboneParams(nn.Module):
+class _BackboneParams(_EncoderParams):
     """upstream Backbone.py :: STPN_KD parameter names (one module holds encoder and decoder)"""
 
     def __init__(self, in_channels):
-        super().__init__()
-        for name, cin, cout, stride in _ENC_CONVS:
-            setattr(self, name, nn.Conv2d(cin or in_channels, cout, 3, stride, 1))
-            setattr(self, _bn_name(name), nn.BatchNorm2d(cout))
-        self.conv3d_1 = _Conv3DParams(64)
-        self.conv3d_2 = _Conv3DParams(128)
+        super().__init__(in_channels, 0)
         for name, cin, cout in _DEC_CONVS:
             setattr(self, name, nn.Conv2d(cin, cout, 3, 1, 1))
             setattr(self, _bn_name(name), nn.BatchNorm2d(cout))
 
 
-class TeacherNet(nn.Module):
+class TeacherNet(_BackboneNet):
     def __init__(self, config, in_channels=13):
         super().__init__()
         self.stpn = _BackboneParams(in_channels)
         self.classification = _ClsHeadParams(config)
         self.regression = _RegHeadParams(config, 1 if config.only_det else config.pred_len)
         self.conv_math = os.environ.get("DISCONET_CONV_MATH", "sp")
-        self._plan, self._plan_sig = None, None
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        cleaned = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
-        self._plan = None
-        return super().load_state_dict(cleaned, strict=strict, **kw)
 
     def train(self, mode=True):
         if mode:
             raise NotImplementedError("TeacherNet is the frozen distillation teacher: eval() only")
         return super().train(mode)
 
-    def _get_plan(self):
-        sig = (self.conv_math,) + tuple((t.data_ptr(), t._version) for t in
-                                        list(self.parameters()) + list(self.buffers()))
-        if self._plan is None or sig != self._plan_sig:
-            math = ops.MATH_MODES[self.conv_math]
-            s, P = self.stpn, {}
-            for name, _, _, stride in _ENC_CONVS:
-                conv = getattr(s, name)
-                P[name] = _ConvLayer(name, conv.weight, conv.bias, getattr(s, _bn_name(name)), 3, stride, math=math)
-            for name in ("conv3d_1", "conv3d_2"):
-                m = getattr(s, name)
-                P[name] = _ConvLayer(name, m.conv3d.weight, m.conv3d.bias, m.bn3d, 1, math=math)
-            for name, _, _ in _DEC_CONVS:
-                conv = getattr(s, name)
-                P[name] = _ConvLayer(name, conv.weight, conv.bias, getattr(s, _bn_name(name)), 3, math=math)
-            self._plan, self._plan_sig = P, sig
-        return self._plan
+    def _plan_key(self):
+        return (_conv_math(self.conv_math),)
+
+    def _build_plan(self):
+        # the backbone's convs only: dense float voxels in (no stem pair), no fused 1x1 layers, no heads
+        return _pack_layers(backbone_layers(self.stpn, self.stpn), ops.MATH_MODES[self.conv_math])
 
     def forward_nhwc(self, bevs):
         """-> (x8, x7, x6, x5, x3, x2) as dense NHWC tensors (what the KD kernel reads)"""
@@ -78,20 +57,8 @@ class TeacherNet(nn.Module):
         if not bevs.is_cuda:
             raise ops._lib.DnError("TeacherNet.forward needs GPU tensors; there is no CPU path")
         P = self._get_plan()
-        n = bevs.shape[0] * bevs.shape[1]
-        x = bevs.reshape(n, bevs.shape[2], bevs.shape[3], bevs.shape[4])
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        x0 = P["conv_pre_2"].run(P["conv_pre_1"].run(x))
-        x1 = P["conv3d_1"].run(P["conv1_2"].run(P["conv1_1"].run(x0)))
-        x2 = P["conv3d_2"].run(P["conv2_2"].run(P["conv2_1"].run(x1)))
-        x3 = P["conv3_2"].run(P["conv3_1"].run(x2))
-        x4 = P["conv4_2"].run(P["conv4_1"].run(x3))
-        x5 = P["conv5_2"].run(P["conv5_1"].run(x4, x3, up0=True))
-        x6 = P["conv6_2"].run(P["conv6_1"].run(x5, x2, up0=True))
-        x7 = P["conv7_2"].run(P["conv7_1"].run(x6, x1, up0=True))
-        x8 = P["conv8_2"].run(P["conv8_1"].run(x7, x0, up0=True))
-        return tuple(ops.as_nhwc(t) for t in (x8, x7, x6, x5, x3, x2))
+        enc = self.encode(bevs, P)
+        return tuple(ops.as_nhwc(t) for t in self.decode(enc, P) + (enc[3], enc[2]))
 
     def forward(self, bevs):
         with torch.no_grad():

@@ -26,10 +26,8 @@ import os
 import torch
 
 from . import ops, train_ops as T
-from .model import LAYER_CHANNEL, _bn_name
+from .model import _ENC_GROUPS, LAYER_CHANNEL, backbone_layers
 
-_ENC_GROUPS = (("conv_pre_1", "conv_pre_2"), ("conv1_1", "conv1_2", "conv3d_1"),
-               ("conv2_1", "conv2_2", "conv3d_2"), ("conv3_1", "conv3_2"), ("conv4_1", "conv4_2"))
 _EPS = 1e-5          # nn.BatchNorm default
 _DGRAD_MATH_DEFAULT = "sp"        # measured (round 5): per-tensor gradient error vs the float64 oracle equal to the fp32 form's to 3 digits
 _WGRAD_MATH_DEFAULT = "sp"        # the weight gradients of the layers dn_conv_wgrad_sp takes on the f16 MFMA with split operands
@@ -292,27 +290,14 @@ class TrainEngine:
         off, n, shape = self.grad_of[id(p)]
         return (self.flat_g if flat is None else flat)[off:off + n].view(shape)
 
+    def _layers(self):      # the network's layer table (model.backbone_layers; the segmentation variant: seg.unet_layers)
+        return backbone_layers(self.model.u_encoder, self.model.decoder)
+
     def _graph(self):
-        m = self.model
-        enc, dec = m.u_encoder, m.decoder
-        L = {}
-        for name in ("conv_pre_1", "conv_pre_2", "conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1",
-                     "conv3_2", "conv4_1", "conv4_2"):
-            conv = getattr(enc, name)
-            L[name] = _Layer(name, conv.weight, conv.bias, getattr(enc, _bn_name(name)), 3, conv.stride[0])
-        for name in ("conv3d_1", "conv3d_2"):
-            mod = getattr(enc, name)
-            L[name] = _Layer(name, mod.conv3d.weight, mod.conv3d.bias, mod.bn3d, 1)
-        for name in ("conv5_1", "conv5_2", "conv6_1", "conv6_2", "conv7_1", "conv7_2", "conv8_1", "conv8_2"):
-            conv = getattr(dec, name)
-            L[name] = _Layer(name, conv.weight, conv.bias, getattr(dec, _bn_name(name)), 3)
-        if enc.compress_level > 0:       # 1x1 compress / decompress of the exchanged map
-            L["compress"] = _Layer("compress", enc.com_compresser.weight, enc.com_compresser.bias,
-                                   enc.bn_compress, 1)
-            L["decompress"] = _Layer("decompress", enc.com_decompresser.weight, enc.com_decompresser.bias,
-                                     enc.bn_decompress, 1)
-        L.update(_fusion_mlp_layers(m.pixel_weighted_fusion))
-        self.L = L
+        # (a conv without BatchNorm -- the UNet's outc -- is no layer of the graph: it runs through _conv)
+        self.L = {r.name: _Layer(r.name, r.weight, r.bias, r.bn, r.ksize, r.stride) for r in self._layers()
+                  if r.bn is not None}
+        self.L.update(_fusion_mlp_layers(self.model.pixel_weighted_fusion))
 
     # ------------------------------------------------------------------
     # one conv + BN(train) + ReLU

@@ -337,6 +337,18 @@ def test_non_finite_parameters_and_inputs_are_refused():
     m = _product(ref, c["map_hw"], c["agents"], math="sp")
     with pytest.raises(DnError, match="non-finite values in u_encoder.conv1_1.bias"):
         _gpu_outputs(m, bevs, trans, na, c["batch"])
+    # the distillation teacher and the segmentation model pack their plans through the same check
+    from disconet_amd import Config, SegDiscoNet, TeacherNet
+    teacher = TeacherNet(Config(map_hw=c["map_hw"])).eval().cuda()
+    with torch.no_grad():
+        teacher.stpn.conv5_1.weight[0, 0, 1, 1] = float("inf")
+    with pytest.raises(DnError, match="TeacherNet: non-finite values in stpn.conv5_1.weight"):
+        teacher.forward_nhwc(bevs.cuda())
+    seg = SegDiscoNet(num_agent=2).eval().cuda()
+    with torch.no_grad():
+        seg.up2.conv.double_conv[4].running_var[7] = float("nan")
+    with pytest.raises(DnError, match="SegDiscoNet: non-finite values in up2.conv.double_conv.4.running_var"):
+        seg(torch.zeros(2, 13, 32, 32).cuda(), torch.eye(4).expand(1, 2, 2, 4, 4).cuda(), torch.full((1, 2), 2).cuda())
     ops.sp_range_flags(reset=True)
     x = torch.rand(2, 8, 8, 16)
     x[1, 3, 4, 5] = float("nan")
