@@ -117,6 +117,9 @@ SIGNATURES = {
     "dn_spconv_set_upmode": (c_int, [c_int]),
     "dn_decode_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p,
                                 c_void_p]),
+    "dn_detect_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "dn_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_double, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -4,9 +4,10 @@
 //
 // Replaces the dense part of upstream:coperception/utils/postprocess.py
 // (softmax + box decode vs anchors) that CoDetModule.predict_all runs on the CPU
-// after the forward; NMS and mAP stay CPU-side as in the
-// reference.
+// after the forward.  The per-anchor expression lives in decode_device.h: detect.hip
+// (top-k + rotated NMS on the GPU) decodes its selected anchors with the same function.
 #include "dn_internal.h"
+#include "decode_device.h"
 
 namespace {
 
@@ -15,20 +16,10 @@ __global__ void decode_kernel(const float* __restrict__ cls, const float* __rest
                               float* __restrict__ scores, float* __restrict__ boxes) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
-    const float c0 = cls[2 * i], c1 = cls[2 * i + 1];
-    // softmax over {background, foreground}, max-shifted like F.softmax
-    const float m = fmaxf(c0, c1);
-    const float e0 = expf(c0 - m), e1 = expf(c1 - m);
-    scores[i] = e1 / (e0 + e1);
-    const float* a = anchors + 6 * (i % per_image);
-    const float* t = loc + 6 * i;
+    float b[6];
+    scores[i] = dn::decode_anchor(cls, loc, anchors, i, per_image, b);
     float* o = boxes + 6 * i;
-    o[0] = a[0] + t[0] * a[2];
-    o[1] = a[1] + t[1] * a[3];
-    o[2] = a[2] * expf(t[2]);
-    o[3] = a[3] * expf(t[3]);
-    o[4] = a[4] * t[5] + a[5] * t[4];
-    o[5] = a[5] * t[5] - a[4] * t[4];
+    for (int q = 0; q < 6; ++q) o[q] = b[q];
   }
 }
 

@@ -2,7 +2,9 @@
 (upstream:coperception/utils/CoDetModule.py, postprocess.py; SURVEY.md §8(f)
 next #3): softmax + box decode for every anchor (one HIP kernel), candidate
 selection, then rotated NMS on the host -- the reference runs NMS on the CPU too,
-so this is its placement, not a fallback.
+so this is its placement, not a fallback (predict_all / host_detections).
+detect() runs the same tail on the GPU (dn_detect: top-k, rotated NMS, padded rows)
+for graph-captured inference; host_detections is the reference it is tested against.
 """
 import ctypes
 import math
@@ -110,13 +112,9 @@ def nms_rotated(boxes, scores, iou_thr=0.01):
     return np.asarray(keep, dtype=np.int64)
 
 
-def predict_all(model, anchors, bevs, trans_matrices, num_agent_tensor, batch_size=1,
-                pre_nms_top_k=300, iou_thr=0.01, score_thr=None):
-    """Per-image detections [(boxes [K, 6], scores [K])] for the agent-major batch: forward
-    (HIP), decode (HIP), top-k by score (torch on the GPU), rotated NMS (host)."""
-    with torch.no_grad():
-        out = model(bevs, trans_matrices, num_agent_tensor, batch_size)
-    result = out[0] if isinstance(out, tuple) else out
+def host_detections(result, anchors, pre_nms_top_k=300, iou_thr=0.01, score_thr=None):
+    """Per-image detections [(boxes [K, 6], scores [K])] of the heads' outputs (`result` = {"cls", "loc"}, agent-major
+    images): decode (HIP), top-k by score (torch on the GPU), rotated NMS (host).  The host reference of detect()."""
     scores, boxes = decode(result, anchors)
     dets = []
     for i in range(scores.shape[0]):
@@ -132,3 +130,62 @@ def predict_all(model, anchors, bevs, trans_matrices, num_agent_tensor, batch_si
         keep = nms_rotated(bb, sb, iou_thr)
         dets.append((bb[keep], sb[keep]))
     return dets
+
+
+def predict_all(model, anchors, bevs, trans_matrices, num_agent_tensor, batch_size=1,
+                pre_nms_top_k=300, iou_thr=0.01, score_thr=None):
+    """Per-image detections [(boxes [K, 6], scores [K])] for the agent-major batch: forward
+    (HIP), decode (HIP), top-k by score (torch on the GPU), rotated NMS (host)."""
+    with torch.no_grad():
+        out = model(bevs, trans_matrices, num_agent_tensor, batch_size)
+    result = out[0] if isinstance(out, tuple) else out
+    return host_detections(result, anchors, pre_nms_top_k, iou_thr, score_thr)
+
+
+# ---------------------------------------------------------------------------
+# the same tail on the GPU: one batched call, no host synchronisation (dn_detect)
+# ---------------------------------------------------------------------------
+MAX_TOP_K = 1024
+
+
+def detect(result, anchors, pre_nms_top_k=300, iou_thr=0.01, score_thr=None):
+    """host_detections' tail on the GPU for every image at once: top-k by score (descending, lower anchor index first),
+    rotated greedy NMS, padded rows.  `result` = {"cls": [N, A, 2], "loc": [N, ..., 6]} (N agent-major images; with
+    kd_flag pass the dict of the forward's tuple).  Returns device tensors {"boxes" [N, K, 6], "scores" [N, K],
+    "index" [N, K] (anchor index within the image, -1 past count), "count" [N]}; rows >= count are zero.  Runs on torch's
+    current stream, allocates through torch's caching allocator and never waits for the device, so it can be captured
+    into a graph behind the forward (graph.GraphedStep).  One difference from host_detections: a NaN score is never a
+    candidate (the host lets it take a top-k slot, then drops it)."""
+    k = int(pre_nms_top_k)
+    if not 1 <= k <= MAX_TOP_K:
+        raise ValueError("pre_nms_top_k = %d: detect() supports 1..%d" % (k, MAX_TOP_K))
+    cls, loc = result["cls"], result["loc"]
+    _need_gpu(cls, loc, anchors)
+    n, apl = cls.shape[0], cls.shape[1]
+    cls = cls.contiguous()
+    loc = loc.reshape(n, apl, 6).contiguous()
+    anchors = anchors.reshape(apl, 6).contiguous()
+    lib = _lib.load()
+    dev = cls.device
+    nbytes = int(lib.dn_detect_workspace_bytes(n, apl, k))
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    out = {"boxes": torch.empty((n, k, 6), dtype=torch.float32, device=dev),
+           "scores": torch.empty((n, k), dtype=torch.float32, device=dev),
+           "index": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "count": torch.empty((n,), dtype=torch.int32, device=dev)}
+    use_thr = score_thr is not None
+    _lib.check(lib.dn_detect(_ptr(cls), _ptr(loc), _ptr(anchors), n, apl, k, int(use_thr),
+                             float(score_thr) if use_thr else 0.0, float(iou_thr), _ptr(out["boxes"]),
+                             _ptr(out["scores"]), _ptr(out["index"]), _ptr(out["count"]), _ptr(ws), nbytes, _stream()),
+               "dn_detect")
+    return out
+
+
+def detections_to_host(det):
+    """detect()'s device tensors -> host_detections' form [(boxes [c, 6], scores [c])] with one device-to-host copy."""
+    n, k = det["scores"].shape
+    packed = torch.cat([det["boxes"].reshape(n, 6 * k), det["scores"], det["count"].view(torch.float32)[:, None]],
+                       dim=1).cpu().numpy()
+    counts = packed[:, 7 * k].view(np.int32)
+    return [(packed[i, :6 * k].reshape(k, 6)[:counts[i]].copy(), packed[i, 6 * k:7 * k][:counts[i]].copy())
+            for i in range(n)]

@@ -455,12 +455,32 @@ int dn_disco_fuse_mlp_fm(const float* feat, const float* warped_fm, const int32_
  * Replaces the dense part of upstream:coperception/utils/postprocess.py that
  * CoDetModule.predict_all runs on the CPU: foreground probability = softmax of
  * the 2 class logits, box = anchor-relative decode of the 6-value code
- * (x, y, w, h, sin, cos).  NMS / mAP stay on the CPU as in the reference.
+ * (x, y, w, h, sin, cos).  dn_detect below runs top-k + NMS on the GPU; mAP stays on the CPU.
  *   cls [n_images][anchors_per_image][2], loc [n_images][anchors_per_image][6],
  *   anchors [anchors_per_image][6] -> scores [n][apl], boxes [n][apl][6]
  * ------------------------------------------------------------------------ */
 int dn_decode_boxes(const float* cls, const float* loc, const float* anchors, int n_images,
                     long anchors_per_image, float* scores, float* boxes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Detection tail (disconet_amd/csrc/detect.hip): per image, the tail of
+ * postprocess.host_detections -- top-k anchors by foreground score, rotated greedy NMS -- batched, graph-capturable,
+ * with no host synchronisation; the launch sequence depends on the shapes only.
+ *   cls, loc, anchors as dn_decode_boxes.  Per image:
+ *   - candidates: every anchor (use_score_thr = 0) or those with score > score_thr; a NaN score never is one;
+ *   - order: score descending, anchor index ascending (torch.sort(stable=True)); the first min(top_k, #candidates);
+ *   - greedy NMS in that order: j is suppressed by an earlier kept i when union > 0 and inter / union > iou_thr
+ *     (union = w_i h_i + w_j h_j - inter; fp64 geometry, operation for operation postprocess._intersection_area);
+ *   - out: count[n] kept rows; rows < count of boxes [n][top_k][6], scores [n][top_k], index [n][top_k] (anchor
+ *     index within the image) in keep order, bit for bit what dn_decode_boxes writes for those anchors; rows >= count
+ *     are 0 with index -1, on every call.
+ *   1 <= top_k <= 1024, iou_thr finite and >= 0; workspace: dn_detect_workspace_bytes(n, apl, top_k) bytes
+ *   (0 for arguments dn_detect refuses); the results are the same bits on every run.
+ * ------------------------------------------------------------------------ */
+size_t dn_detect_workspace_bytes(int n_images, long anchors_per_image, int top_k);
+int dn_detect(const float* cls, const float* loc, const float* anchors, int n_images, long anchors_per_image,
+              int top_k, int use_score_thr, float score_thr, double iou_thr, float* boxes, float* scores,
+              int32_t* index, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
