@@ -585,17 +585,7 @@ def _poses(n, seed=4):
     return torch.from_numpy(out)
 
 
-def _warp_ref(nb, pose):
-    """the two-pass warp of the oracle (upstream feature_transformation), differentiable"""
-    theta_rot = torch.tensor([[pose[0, 0], pose[0, 1], 0.0], [pose[1, 0], pose[1, 1], 0.0]],
-                             dtype=nb.dtype).unsqueeze(0)
-    theta_trans = torch.tensor([[1.0, 0.0, 4 * pose[0, 3] / 128], [0.0, 1.0, -4 * pose[1, 3] / 128]],
-                               dtype=nb.dtype).unsqueeze(0)
-    size = (1,) + tuple(nb.shape)
-    r = F.grid_sample(nb.unsqueeze(0), F.affine_grid(theta_rot, size, align_corners=False),
-                      align_corners=False)
-    return F.grid_sample(r, F.affine_grid(theta_trans, size, align_corners=False),
-                         align_corners=False)[0]
+from tests.fusion_fp64 import warp64 as _warp_ref      # the two-pass warp of the oracle in float64, differentiable
 
 
 @pytest.mark.parametrize("rigid,c", [(False, 64), (True, 64), (True, 512)])
