@@ -6,7 +6,7 @@ module raises.  The library is built in-tree by disconet_amd/csrc/build.py
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_size_t,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_longlong, c_size_t,
                     c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,6 +120,11 @@ SIGNATURES = {
     "dn_detect_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "dn_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_double, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dn_ap_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_ap_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int,
+                            c_int, c_void_p]),
+    "dn_ap_reset": (c_int, [c_void_p, c_int, c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -21,6 +21,7 @@
 
 #include "dn_internal.h"
 #include "decode_device.h"
+#include "rot_iou_device.h"   // Box64, box64, intersection_area: rotated IoU in fp64 (shared with ap_match.hip)
 
 namespace {
 
@@ -29,7 +30,10 @@ constexpr int kItems = 16;
 constexpr long kChunk = (long)kThreads * kItems;   // anchors per workgroup of the select passes
 constexpr int kBins = 1024;                         // 10-bit digits
 constexpr int kMaxK = 1024;
-constexpr int kClipCap = 12;   // vertices of a clipped polygon kept per lane (a convex quad clipped 4 times has <= 8)
+using dn::Box64;
+using dn::box64;
+using dn::intersection_area;
+using dn::kClipCap;
 
 struct Layout {
   size_t keys, hist, gcount, state, ties, cand, sbox, sscore, sidx, nvalid, mask, total;
@@ -265,78 +269,6 @@ __global__ void __launch_bounds__(kSortThreads) detect_sort_kernel(const float* 
   }
   __syncthreads();
   if (threadIdx.x == 0) nvalid[img] = nv;
-}
-
-// ---- rotated IoU in fp64, operation for operation postprocess._corners / _intersection_area ----
-struct Box64 {
-  double x[4], y[4];
-  double cx, cy, radius, area;
-};
-
-__device__ void box64(const float* __restrict__ b, Box64& o) {
-#pragma clang fp contract(off)
-  const double bx = b[0], by = b[1], w = b[2], h = b[3], sn = b[4], cs = b[5];
-  const double n = fmax(hypot(sn, cs), 1e-12);
-  const double s = sn / n, c = cs / n;
-  const double dx = w / 2.0, dy = h / 2.0;
-  const double lx[4] = {-dx, dx, dx, -dx}, ly[4] = {-dy, -dy, dy, dy};
-  for (int k = 0; k < 4; ++k) {
-    o.x[k] = lx[k] * c - ly[k] * s + bx;
-    o.y[k] = lx[k] * s + ly[k] * c + by;
-  }
-  o.cx = bx;
-  o.cy = by;
-  o.radius = 0.5 * hypot(w, h);
-  o.area = w * h;
-}
-
-// Area of (quad a) clipped by the four edges of quad b (Sutherland-Hodgman).  The polygons live in LDS, one column per
-// lane: px/py/qx/qy point at vertex 0 of this lane's column, vertex v is at [64 * v].
-__device__ double intersection_area(const double* ax, const double* ay, const double* bx, const double* by,
-                                    double* px, double* py, double* qx, double* qy) {
-#pragma clang fp contract(off)
-  int n = 4;
-  for (int k = 0; k < 4; ++k) {
-    px[64 * k] = ax[k];
-    py[64 * k] = ay[k];
-  }
-  for (int e = 0; e < 4; ++e) {
-    const double a0 = bx[e], a1 = by[e], b0 = bx[(e + 1) & 3], b1 = by[(e + 1) & 3];
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-      const int k1 = k + 1 == n ? 0 : k + 1;
-      const double p0 = px[64 * k], p1 = py[64 * k], q0 = px[64 * k1], q1 = py[64 * k1];
-      const double sp = (b0 - a0) * (p1 - a1) - (b1 - a1) * (p0 - a0);
-      const double sq = (b0 - a0) * (q1 - a1) - (b1 - a1) * (q0 - a0);
-      if (sp >= 0) {
-        if (m < kClipCap) {
-          qx[64 * m] = p0;
-          qy[64 * m] = p1;
-        }
-        ++m;
-      }
-      if (sp * sq < 0) {
-        const double t = sp / (sp - sq);
-        if (m < kClipCap) {
-          qx[64 * m] = p0 + t * (q0 - p0);
-          qy[64 * m] = p1 + t * (q1 - p1);
-        }
-        ++m;
-      }
-    }
-    n = m < kClipCap ? m : kClipCap;
-    double* t;
-    t = px; px = qx; qx = t;
-    t = py; py = qy; qy = t;
-    if (n < 3) return 0.0;
-  }
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < n; ++k) {
-    const int k1 = k + 1 == n ? 0 : k + 1;
-    s1 = s1 + px[64 * k] * py[64 * k1];
-    s2 = s2 + py[64 * k] * px[64 * k1];
-  }
-  return 0.5 * fabs(s1 - s2);
 }
 
 // Tile (row block, 16-column piece) of one image: lane t is row i = 64 * rb + t; bit jj of its 16-bit piece q of mask

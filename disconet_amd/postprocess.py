@@ -189,3 +189,257 @@ def detections_to_host(det):
     counts = packed[:, 7 * k].view(np.int32)
     return [(packed[i, :6 * k].reshape(k, 6)[:counts[i]].copy(), packed[i, 6 * k:7 * k][:counts[i]].copy())
             for i in range(n)]
+
+
+# ---------------------------------------------------------------------------
+# mAP at IoU 0.5 / 0.7: ground-truth matching per frame (dn_ap_match on the GPU, numpy reference below) and the
+# precision / recall curve on the host from one copy of the records
+# ---------------------------------------------------------------------------
+MAX_GT = 1024            # ground-truth rows per image
+MAX_IOU_THRS = 8         # one bit per threshold in a record
+MAX_AGENTS = 64          # per-agent ground-truth counters a MeanAP owns
+
+
+def pad_boxes(rows, width=None):
+    """list of [n_i, 6] box arrays -> (padded [N, width, 6] float32, counts [N] int32); width >= 1."""
+    rows = [np.asarray(r, dtype=np.float32).reshape(-1, 6) for r in rows]
+    width = max([1] + [len(r) for r in rows]) if width is None else int(width)
+    out = np.zeros((len(rows), width, 6), dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out, np.asarray([len(r) for r in rows], dtype=np.int32)
+
+
+def pad_detections(boxes, scores, width=None):
+    """per-image lists (boxes [n_i, 6], scores [n_i]) -> {"boxes" [N, K, 6], "scores" [N, K], "count" [N]} (numpy): the
+    form detect() returns, for detections that come from elsewhere."""
+    b, count = pad_boxes(boxes, width)
+    s = np.zeros(b.shape[:2], dtype=np.float32)
+    for i, r in enumerate(scores):
+        s[i, :len(r)] = np.asarray(r, dtype=np.float32)
+    return {"boxes": b, "scores": s, "count": count}
+
+
+def _check_thrs(iou_thrs):
+    thrs = [float(t) for t in iou_thrs]
+    if not 1 <= len(thrs) <= MAX_IOU_THRS:
+        raise ValueError("%d IoU thresholds: 1..%d are supported" % (len(thrs), MAX_IOU_THRS))
+    if not all(0.0 < t <= 1.0 for t in thrs):
+        raise ValueError("IoU thresholds %s: each must be in (0, 1]" % (thrs,))
+    return thrs
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def host_match_ground_truth(det, gt_boxes, gt_count, iou_thrs=(0.5, 0.7)):
+    """numpy / float64 reference of match_ground_truth (the steps dn_ap_match runs, on _corners / _intersection_area).
+    `det` = {"boxes" [N, K, 6], "scores" [N, K], "count" [N]}, gt_boxes [N, G, 6], gt_count [N] (numpy or tensors) ->
+    {"best_iou" [N, K] float64, "best_gt" [N, K] int32, "rank" [N, K] int32, "tp" [T, N, K] uint8} (numpy).
+    A row is valid when it is below its image's count and its score is finite; the other rows get rank -1, best_gt -1,
+    best_iou 0 and tp 0.  rank = position in the stable descending score order; best_gt = the lowest ground-truth index
+    with the largest IoU among those that pass the strict circumscribed-circle test (an IoU of 0 never matches); a row is
+    a true positive at t when best_iou >= t and no row of lower rank with the same best_gt has best_iou >= t."""
+    thrs = _check_thrs(iou_thrs)
+    boxes, scores, count = _host(det["boxes"]), _host(det["scores"]), _host(det["count"])
+    gt_boxes, gt_count = _host(gt_boxes), _host(gt_count)
+    n, k = scores.shape
+    g = gt_boxes.shape[1]
+    best_iou = np.zeros((n, k), dtype=np.float64)
+    best_gt = np.full((n, k), -1, dtype=np.int32)
+    rank = np.full((n, k), -1, dtype=np.int32)
+    tp = np.zeros((len(thrs), n, k), dtype=np.uint8)
+    for img in range(n):
+        c, gc = min(max(int(count[img]), 0), k), min(max(int(gt_count[img]), 0), g)
+        valid = np.nonzero(np.isfinite(scores[img, :c]))[0]
+        order = valid[np.argsort(-scores[img, valid], kind="stable")]
+        rank[img, order] = np.arange(len(order), dtype=np.int32)
+        if gc == 0 or len(order) == 0:
+            continue
+        d = np.asarray(boxes[img, :c], dtype=np.float64)
+        t = np.asarray(gt_boxes[img, :gc], dtype=np.float64)
+        dc, tc = _corners(d), _corners(t)
+        d_rad, t_rad = 0.5 * np.hypot(d[:, 2], d[:, 3]), 0.5 * np.hypot(t[:, 2], t[:, 3])
+        d_area, t_area = d[:, 2] * d[:, 3], t[:, 2] * t[:, 3]
+        for i in order:
+            near = np.nonzero(np.hypot(t[:, 0] - d[i, 0], t[:, 1] - d[i, 1]) < t_rad + d_rad[i])[0]
+            best, best_j = 0.0, -1
+            for j in near:
+                inter = _intersection_area(dc[i], tc[j])
+                union = d_area[i] + t_area[j] - inter
+                iou = inter / union if union > 0 else 0.0
+                if iou > best:
+                    best, best_j = iou, j
+            best_iou[img, i], best_gt[img, i] = best, best_j
+        for ti, thr in enumerate(thrs):
+            taken = np.zeros(gc, dtype=bool)
+            for i in order:
+                if best_gt[img, i] >= 0 and best_iou[img, i] >= thr and not taken[best_gt[img, i]]:
+                    taken[best_gt[img, i]] = True
+                    tp[ti, img, i] = 1
+    return {"best_iou": best_iou, "best_gt": best_gt, "rank": rank, "tp": tp}
+
+
+def records_from_match(det, match):
+    """The records one call contributes, in accumulation order (image, then rank): (scores [R] float32, tp [T, R] uint8,
+    image [R] int32)."""
+    scores, rank, tp = _host(det["scores"]), _host(match["rank"]), _host(match["tp"])
+    s, f, im = [], [], []
+    for img in range(scores.shape[0]):
+        rows = np.nonzero(rank[img] >= 0)[0]
+        rows = rows[np.argsort(rank[img, rows], kind="stable")]
+        s.append(scores[img, rows])
+        f.append(tp[:, img, rows])
+        im.append(np.full(len(rows), img, dtype=np.int32))
+    return (np.concatenate(s).astype(np.float32), np.concatenate(f, axis=1).astype(np.uint8), np.concatenate(im))
+
+
+def average_precision_from_records(scores, tp, n_gt):
+    """Area under the interpolated precision / recall curve (mmdetection's "area" mode) of the records (scores [R], tp [R]
+    0 / 1) in float64: records by descending score, equal scores in the order given (the accumulation order); n_gt == 0
+    -> 0.0."""
+    if int(n_gt) == 0:
+        return 0.0
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    hit = np.asarray(tp).reshape(-1).astype(bool)[np.argsort(-scores, kind="stable")]
+    tps = np.cumsum(hit.astype(np.int64))
+    fps = np.cumsum((~hit).astype(np.int64))
+    recall = tps / int(n_gt)
+    precision = tps / np.maximum(tps + fps, 1)
+    mrec = np.concatenate([[0.0], recall, [1.0]])
+    mpre = np.concatenate([[0.0], precision, [0.0]])
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    idx = np.nonzero(mrec[1:] != mrec[:-1])[0]
+    return float(np.sum((mrec[idx + 1] - mrec[idx]) * mpre[idx + 1]))
+
+
+def _ap_inputs(det, gt_boxes, gt_count):
+    boxes, scores, count = det["boxes"], det["scores"], det["count"]
+    for t in (boxes, scores, count, gt_boxes, gt_count):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.DnError("match_ground_truth / MeanAP.update need device tensors (got %s); "
+                               "host_match_ground_truth is the numpy reference" % type(t).__name__)
+    _need_gpu(boxes, scores, count, gt_boxes, gt_count)
+    n, k = scores.shape
+    g = gt_boxes.shape[1]
+    if not 1 <= k <= MAX_TOP_K or not 1 <= g <= MAX_GT:
+        raise ValueError("K = %d detection rows, G = %d ground-truth rows: 1..%d and 1..%d are supported"
+                         % (k, g, MAX_TOP_K, MAX_GT))
+    if tuple(boxes.shape) != (n, k, 6) or tuple(gt_boxes.shape) != (n, g, 6) or count.numel() != n or gt_count.numel() != n:
+        raise ValueError("shapes: boxes %s scores %s count %s gt_boxes %s gt_count %s" % (
+            tuple(boxes.shape), tuple(scores.shape), tuple(count.shape), tuple(gt_boxes.shape), tuple(gt_count.shape)))
+    return (boxes.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous(),
+            count.to(torch.int32).contiguous(), gt_boxes.to(torch.float32).contiguous(),
+            gt_count.to(torch.int32).contiguous(), n, k, g)
+
+
+def _ap_match(det, gt_boxes, gt_count, thrs, accum=None):
+    boxes, scores, count, gt_boxes, gt_count, n, k, g = _ap_inputs(det, gt_boxes, gt_count)
+    lib = _lib.load()
+    dev = scores.device
+    nt = len(thrs)
+    nbytes = int(lib.dn_ap_match_workspace_bytes(n, k, g, nt))
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    out = {"best_iou": torch.empty((n, k), dtype=torch.float64, device=dev),
+           "best_gt": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "rank": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "tp": torch.empty((nt, n, k), dtype=torch.uint8, device=dev)}
+    records, capacity, state, n_agents, batch = accum if accum is not None else (None, 0, None, 0, 1)
+    _lib.check(lib.dn_ap_match(_ptr(boxes), _ptr(scores), _ptr(count), _ptr(gt_boxes), _ptr(gt_count), n, k, g,
+                               (ctypes.c_double * nt)(*thrs), nt, _ptr(out["best_iou"]), _ptr(out["best_gt"]),
+                               _ptr(out["rank"]), _ptr(out["tp"]), _ptr(ws), nbytes, _ptr(records), capacity,
+                               _ptr(state), n_agents, batch, _stream()), "dn_ap_match")
+    return out
+
+
+def match_ground_truth(det, gt_boxes, gt_count, iou_thrs=(0.5, 0.7)):
+    """Per-image ground-truth matching on the GPU (dn_ap_match; host_match_ground_truth is its reference).  `det` is
+    detect()'s dict or any dict of device tensors "boxes" [N, K, 6], "scores" [N, K], "count" [N] (the rows need not be
+    sorted); gt_boxes [N, G, 6], gt_count [N]; K, G <= 1024, up to 8 thresholds in (0, 1].  Returns device tensors
+    {"best_iou" [N, K] float64, "best_gt" [N, K] int32, "rank" [N, K] int32, "tp" [T, N, K] uint8}.  Runs on torch's
+    current stream and never waits for the device."""
+    return _ap_match(det, gt_boxes, gt_count, _check_thrs(iou_thrs))
+
+
+class MeanAP:
+    """mAP over an evaluation run: update() after every frame's detect() (enqueues dn_ap_match on the current stream:
+    matching on the GPU, records appended to device arrays at a device-resident cursor, no host synchronisation), compute()
+    once at the end (one copy of the state words and one of the filled part of the records, then the precision / recall
+    curve on the host in float64).
+
+    Images are agent-major, `batch_size` per agent: image i belongs to agent i // batch_size (up to 64 agents).
+    `capacity` = records (detections) the run may accumulate; compute() raises DnError when more arrived, or when a row
+    below its count carried a non-finite score -- never a silently truncated metric.
+
+    update() is usable inside graph.GraphedStep (forward + detect() + update() in one captured graph; every replay
+    appends that frame's records).  GraphedStep runs its step three times to warm up before it captures and those runs
+    append records too: call reset() after constructing the GraphedStep, before the first replay that counts."""
+
+    def __init__(self, batch_size, iou_thrs=(0.5, 0.7), capacity=1 << 20):
+        self.batch_size = int(batch_size)
+        self.iou_thrs = _check_thrs(iou_thrs)
+        self.capacity = int(capacity)
+        if self.batch_size < 1 or self.capacity < 1:
+            raise ValueError("MeanAP: batch_size = %d, capacity = %d, both must be positive" % (self.batch_size, self.capacity))
+        self.n_agents = 0            # agents seen by update() (host-side: from the shapes only)
+        self.records = None          # [capacity, 2] int32 on the device: {score bits, agent << 8 | tp bits}
+        self.state = None            # [2 + MAX_AGENTS] int64 on the device: cursor, status, ground truth per agent
+
+    def _allocate(self, device):
+        self.records = torch.empty((self.capacity, 2), dtype=torch.int32, device=device)
+        self.state = torch.empty((2 + MAX_AGENTS,), dtype=torch.int64, device=device)
+        self.reset()
+
+    def reset(self):
+        """Forget every record and counter (a one-thread kernel on the current stream)."""
+        if self.state is not None:
+            _lib.check(_lib.load().dn_ap_reset(_ptr(self.state), MAX_AGENTS, _stream()), "dn_ap_reset")
+
+    def update(self, det, gt_boxes, gt_count):
+        """Match one call's detections (detect()'s dict) against its ground truth and append the records.  Enqueues only.
+        Returns match_ground_truth's tensors for that call."""
+        _ap_inputs(det, gt_boxes, gt_count)
+        n = det["scores"].shape[0]
+        agents = -(-n // self.batch_size)
+        if agents > MAX_AGENTS:
+            raise ValueError("MeanAP: %d images at batch %d are %d agents, at most %d" % (n, self.batch_size, agents, MAX_AGENTS))
+        if self.state is None:
+            self._allocate(det["scores"].device)
+        self.n_agents = max(self.n_agents, agents)
+        return _ap_match(det, gt_boxes, gt_count, self.iou_thrs,
+                         (self.records, self.capacity, self.state, MAX_AGENTS, self.batch_size))
+
+    def host_records(self):
+        """(scores [R] float32, tp [T, R] uint8, agent [R] int32, gt per agent [n_agents] int64, status) -- waits for the
+        device; R = records kept (at most capacity)."""
+        if self.state is None:
+            return (np.zeros(0, np.float32), np.zeros((len(self.iou_thrs), 0), np.uint8), np.zeros(0, np.int32),
+                    np.zeros(0, np.int64), 0)
+        state = self.state.cpu().numpy()
+        filled = int(min(state[0], self.capacity))
+        rec = self.records[:filled].cpu().numpy()
+        flags = rec[:, 1].view(np.uint32)
+        tp = np.stack([((flags >> t) & 1).astype(np.uint8) for t in range(len(self.iou_thrs))])
+        return (rec[:, 0].copy().view(np.float32), tp, (flags >> 8).astype(np.int32),
+                state[2:2 + self.n_agents].copy(), int(state[1]))
+
+    def compute(self):
+        """{"mAP@<t>": AP over every record, ..., "per_agent": [{"mAP@<t>": ..., "n_det", "n_gt", "n_tp"}, ...], "n_det",
+        "n_gt", "n_tp"}; n_tp = true positives per threshold."""
+        scores, tp, agent, gt, status = self.host_records()
+        if status & 1:
+            raise _lib.DnError("MeanAP: more detections arrived than the capacity of %d records; the metric would be "
+                               "truncated (raise `capacity`)" % self.capacity)
+        if status & 2:
+            raise _lib.DnError("MeanAP: a detection with a non-finite score was passed to update()")
+        names = ["mAP@%g" % t for t in self.iou_thrs]
+        out = {name: average_precision_from_records(scores, tp[t], gt.sum()) for t, name in enumerate(names)}
+        out["per_agent"] = []
+        for a in range(self.n_agents):
+            m = agent == a
+            row = {name: average_precision_from_records(scores[m], tp[t][m], gt[a]) for t, name in enumerate(names)}
+            row.update(n_det=int(m.sum()), n_gt=int(gt[a]), n_tp=[int(tp[t][m].sum()) for t in range(len(names))])
+            out["per_agent"].append(row)
+        out.update(n_det=int(len(scores)), n_gt=int(gt.sum()), n_tp=[int(tp[t].sum()) for t in range(len(names))])
+        return out

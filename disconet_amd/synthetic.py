@@ -144,3 +144,22 @@ def make_train_targets(n_images, map_hw=256, anchors=6, code=6, seed=17, p_fg=0.
     return (labels.view(n_images, -1, 2),
             reg_targets.view(n_images, map_hw, map_hw, anchors, 1, code),
             fg.view(n_images, map_hw, map_hw, anchors, 1))
+
+
+def make_gt_boxes(n_images, seed=0, max_boxes=64, extent=32.0, min_boxes=None):
+    """Seeded ground-truth boxes to score detections against: (gt_boxes [N, max_boxes, 6] float32 = (x, y, w, h, sin,
+    cos), gt_count [N] int32), rows >= gt_count zero.  Per image min_boxes (default max_boxes // 2) .. max_boxes
+    car-sized boxes, centres ~ U(-extent, extent)^2, yaw ~ U(-pi, pi).  They have nothing to do with the synthetic
+    occupancy: an mAP against them checks the plumbing, not the detector."""
+    rng = np.random.RandomState(seed)
+    lo = max_boxes // 2 if min_boxes is None else int(min_boxes)
+    boxes = np.zeros((n_images, max_boxes, 6), dtype=np.float32)
+    count = rng.randint(lo, max_boxes + 1, size=n_images).astype(np.int32)
+    for i in range(n_images):
+        c = int(count[i])
+        yaw = rng.uniform(-math.pi, math.pi, c)
+        boxes[i, :c, 0:2] = rng.uniform(-extent, extent, (c, 2))
+        boxes[i, :c, 2] = rng.uniform(1.6, 2.4, c)
+        boxes[i, :c, 3] = rng.uniform(3.5, 5.5, c)
+        boxes[i, :c, 4], boxes[i, :c, 5] = np.sin(yaw), np.cos(yaw)
+    return torch.from_numpy(boxes), torch.from_numpy(count)

@@ -455,7 +455,8 @@ int dn_disco_fuse_mlp_fm(const float* feat, const float* warped_fm, const int32_
  * Replaces the dense part of upstream:coperception/utils/postprocess.py that
  * CoDetModule.predict_all runs on the CPU: foreground probability = softmax of
  * the 2 class logits, box = anchor-relative decode of the 6-value code
- * (x, y, w, h, sin, cos).  dn_detect below runs top-k + NMS on the GPU; mAP stays on the CPU.
+ * (x, y, w, h, sin, cos).  dn_detect below runs top-k + NMS on the GPU and dn_ap_match the per-frame part
+ * of mAP; the final precision / recall curve is computed on the host from one copy of the records.
  *   cls [n_images][anchors_per_image][2], loc [n_images][anchors_per_image][6],
  *   anchors [anchors_per_image][6] -> scores [n][apl], boxes [n][apl][6]
  * ------------------------------------------------------------------------ */
@@ -481,6 +482,41 @@ size_t dn_detect_workspace_bytes(int n_images, long anchors_per_image, int top_k
 int dn_detect(const float* cls, const float* loc, const float* anchors, int n_images, long anchors_per_image,
               int top_k, int use_score_thr, float score_thr, double iou_thr, float* boxes, float* scores,
               int32_t* index, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Detection mAP, per-frame part (disconet_amd/csrc/ap_match.hip): ground-truth matching and true / false positives
+ * at up to 8 IoU thresholds for every image of a call, and the append of one record per detection to caller-owned
+ * arrays.  Graph-capturable behind dn_detect: kernel launches only, no host synchronisation, no allocation; the launch
+ * sequence depends on the shapes only.  Host reference: postprocess.host_match_ground_truth.
+ *   boxes [n][k][6], scores [n][k], count [n]: dn_detect's outputs or any rows (they need not be sorted);
+ *   gt_boxes [n][g][6], gt_count [n]: padded ground truth.  1 <= k <= 1024, 1 <= g <= 1024, 1 <= n_thr <= 8,
+ *   every iou_thrs[t] (a HOST array, read before the launch) in (0, 1].  Counts are clamped to [0, k] / [0, g].
+ *   Per image, a row i is valid when i < count and its score is finite:
+ *   - rank [n][k]: position in the stable descending score order among the valid rows
+ *     (#{q : s_q > s_i or (s_q == s_i and q < i)}); -1 for the other rows;
+ *   - best_iou [n][k] (fp64), best_gt [n][k]: the largest IoU over the ground truth that passes the strict
+ *     circumscribed-circle test and the lowest column that attains it (IoU as dn_detect's NMS: inter / union, 0 when
+ *     union <= 0, fp64 geometry); 0 and -1 when no IoU is above 0 and for rows that are not valid;
+ *   - tp [n_thr][n][k] (bytes): 1 when best_iou >= iou_thrs[t] and no row of the image with the same best_gt,
+ *     best_iou >= iou_thrs[t] and a lower rank exists; 0 otherwise and for rows that are not valid.
+ *   workspace: dn_ap_match_workspace_bytes(n, k, g, n_thr) bytes (0 for arguments dn_ap_match refuses).
+ *   Accumulation (records != NULL; NULL skips it and ignores capacity / state / n_agents / batch):
+ *   - state: 2 + n_agents 64-bit integers on the device -- [0] cursor = records appended so far (those dropped
+ *     included), [1] status: bit 0 = records were dropped because the cursor passed `capacity` (sticky), bit 1 = a row
+ *     below count had a non-finite score (sticky; such a row produces no record), [2 + a] ground-truth boxes of agent a
+ *     (image / batch: images are agent-major); dn_ap_reset zeroes all of it with one thread;
+ *   - records [capacity][2] 32-bit words: {score bits, agent << 8 | tp bit t at bit t}, written at
+ *     cursor + (valid rows of the images before this one) + rank: image-major, rank order within an image;
+ *   - (n + batch - 1) / batch <= n_agents <= 65536, capacity > 0.
+ *   Only integer atomics: two runs write the same bytes.
+ * ------------------------------------------------------------------------ */
+size_t dn_ap_match_workspace_bytes(int n_images, int k, int g, int n_thr);
+int dn_ap_match(const float* boxes, const float* scores, const int32_t* count, const float* gt_boxes,
+                const int32_t* gt_count, int n_images, int k, int g, const double* iou_thrs, int n_thr,
+                double* best_iou, int32_t* best_gt, int32_t* rank, uint8_t* tp, void* workspace,
+                size_t workspace_bytes, void* records, long long capacity, long long* state, int n_agents, int batch,
+                void* stream);
+int dn_ap_reset(long long* state, int n_agents, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,83 @@
+#!/usr/bin/env python
+"""test_codet.py's evaluation run with the metric: the same flags, model and synthetic scenes; per frame the forward, the
+detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothing read back -- and after the last frame
+mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
+
+    python tools/det/eval_codet.py --com disco [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
+        [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self]
+
+--gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
+    have nothing to do with the synthetic occupancy (there is no V2X-Sim data here): the figure checks the plumbing, not
+    the detector.
+--gt self: every frame's detections are their own ground truth.  At the default --iou_thr 0.01 every kept box has IoU 1
+    with itself and at most 0.01 with every other, so both figures are 1.0000: a smoke check that needs no labels.
+"""
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, HERE)
+
+from disconet_amd import Config, DiscoNet, postprocess  # noqa: E402
+from disconet_amd.synthetic import make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
+from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
+
+GT_MAX_BOXES = 64
+
+
+def main(argv=None):
+    ap = build_parser()
+    ap.add_argument("--pre_nms_top_k", type=int, default=300)
+    ap.add_argument("--iou_thr", type=float, default=0.01)
+    ap.add_argument("--score_thr", type=float, default=None)
+    ap.add_argument("--gt", choices=("synthetic", "self"), default="synthetic")
+    args = ap.parse_args(argv)
+    if args.tracking or args.visualization:
+        print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
+    if args.com != "disco":
+        raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
+    num_agent = args.num_agent + (1 if args.rsu else 0)
+
+    config = Config("test", binary=True, only_det=True)
+    torch.manual_seed(0)              # without --resume the weights are random: seeded, so that a run can be reproduced
+    model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
+                     compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
+    if args.resume:
+        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
+        model.load_state_dict(checkpoint["model_state_dict"])
+        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
+    else:
+        randomize_bn_stats(model)
+    model.eval().cuda()
+    anchors = postprocess.make_anchors(config)
+    n_images = num_agent * args.batch
+    metric = postprocess.MeanAP(args.batch, capacity=max(1, args.frames * n_images * args.pre_nms_top_k))
+
+    for frame in range(args.frames):
+        bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
+        with torch.no_grad():
+            out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
+        det = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors, pre_nms_top_k=args.pre_nms_top_k,
+                                 iou_thr=args.iou_thr, score_thr=args.score_thr)
+        if args.gt == "self":
+            gt_boxes, gt_count = det["boxes"], det["count"]
+        else:
+            gt_boxes, gt_count = (t.cuda() for t in make_gt_boxes(n_images, seed=frame, max_boxes=GT_MAX_BOXES))
+        metric.update(det, gt_boxes, gt_count)
+
+    res = metric.compute()
+    what = ("ground truth = the detections themselves" if args.gt == "self" else
+            "synthetic ground truth%s: plumbing, not accuracy" % ("" if args.resume else " and random weights"))
+    print("%d frames x %d images (%s)" % (args.frames, n_images, what))
+    for a, row in enumerate(res["per_agent"]):
+        print("agent %d: mAP@0.5 %.4f  mAP@0.7 %.4f  (%d detections, %d ground-truth boxes, true positives %d / %d)" % (
+            a, row["mAP@0.5"], row["mAP@0.7"], row["n_det"], row["n_gt"], row["n_tp"][0], row["n_tp"][1]))
+    print("overall: mAP@0.5 %.4f  mAP@0.7 %.4f  (%d detections, %d ground-truth boxes, true positives %d / %d)" % (
+        res["mAP@0.5"], res["mAP@0.7"], res["n_det"], res["n_gt"], res["n_tp"][0], res["n_tp"][1]))
+
+
+if __name__ == "__main__":
+    main()
