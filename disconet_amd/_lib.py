@@ -7,7 +7,7 @@ module raises.  The library is built in-tree by disconet_amd/csrc/build.py
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_longlong, c_size_t,
-                    c_void_p)
+                    c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DISCONET_HIP_LIB: load another build of the same library (A/B runs of a kernel variant)
@@ -35,6 +35,19 @@ class FoldJob(Structure):
     """struct dn_fold_job"""
     _fields_ = [("partials", c_void_p), ("sums", c_void_p), ("out", c_void_p), ("n_blocks", c_int32), ("c", c_int32),
                 ("accumulate", c_int32), ("reserved", c_int32)]
+
+
+class BnBwdDesc(Structure):
+    """struct dn_bn_bwd_desc"""
+    _fields_ = ([(n, c_void_p) for n in ("dy_a", "dy_b", "y", "z", "mean", "var", "gamma")] +
+                [(n, c_int32) for n in ("ld_a", "up_a", "ld_b", "relu", "n_groups", "h", "w", "images_per_group", "c")] +
+                [("eps", c_float)])
+
+
+class BnBwdOut(Structure):
+    """struct dn_bn_bwd_out"""
+    _fields_ = [("dz", c_void_p), ("dz_sp", c_void_p), ("dbias", c_void_p), ("bias_ws", c_void_p), ("n_blocks", c_void_p),
+                ("bias_ws_bytes", c_uint64), ("sp_lift", c_float), ("reserved", c_int32)]
 
 
 class Post1x1Desc(Structure):
@@ -169,44 +182,22 @@ SIGNATURES = {
                                       c_void_p]),
     "dn_conv_dgrad_class_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                             POINTER(c_int), c_void_p]),
-    "dn_bn_train_stats": (c_int, [c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p,
-                                  c_void_p, c_void_p]),
+    "dn_bn_train_stats": (c_int, [c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_float, c_void_p]),
     "dn_bn_train_stats_partial": (c_int, [c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "dn_bn_train_stats_finish": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p]),
-    "dn_bn_train_backward_partial": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
-                                             c_void_p, c_int, c_void_p]),
-    "dn_bn_train_backward_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long,
-                                            c_void_p, c_void_p]),
-    "dn_bn_train_backward_finish_sp": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long,
-                                               c_void_p, c_void_p, c_float, c_void_p]),
-    "dn_bn_train_stats_running": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_float, c_void_p]),
-    "dn_bn_bias_workspace_bytes": (c_size_t, [c_long, c_int]),
-    "dn_bn_train_backward_finish_bias": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                 c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long,
-                                                 c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "dn_bn_train_backward_finish_bias_deferred": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                                          c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                                          c_long, c_void_p, c_void_p, c_float, c_void_p, c_size_t, POINTER(c_int),
-                                                          c_void_p]),
-    "dn_channel_sum_partial": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, POINTER(c_int), c_void_p]),
-    "dn_channel_sum_fold_multi": (c_int, [POINTER(FoldJob), c_int, c_void_p]),
-    "dn_bn_train_form_supported": (c_int, [c_int, c_int, c_long, c_int]),
-    "dn_bn_train_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
-                                  c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
-    "dn_bn_train_apply_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_long, c_int, c_int,
-                                       c_void_p, c_void_p, c_void_p]),
-    "dn_bn_train_apply_mask_sp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_long, c_int, c_int, c_int,
-                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dn_bn_train_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_long, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dn_bn_update_running": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p]),
-    "dn_bn_train_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
-                                     c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                                     c_int, c_void_p]),
+    "dn_bn_bias_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "dn_bn_train_form_supported": (c_int, [c_int, c_int, c_long, c_int]),
+    "dn_bn_train_backward_partial": (c_int, [POINTER(BnBwdDesc), c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "dn_bn_train_backward_finish": (c_int, [POINTER(BnBwdDesc), c_void_p, c_long, POINTER(BnBwdOut), c_void_p]),
+    "dn_bn_train_backward": (c_int, [POINTER(BnBwdDesc), c_void_p, c_size_t, POINTER(BnBwdOut), c_void_p, c_void_p, c_int,
+                                     c_void_p]),
+    "dn_channel_sum_partial": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, POINTER(c_int), c_void_p]),
+    "dn_channel_sum_fold_multi": (c_int, [POINTER(FoldJob), c_int, c_void_p]),
     "dn_channel_sum": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "dn_upsample2_sum": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_add_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_void_p]),

@@ -423,7 +423,7 @@ fold_channel_sum_kernel(const double* __restrict__ part, int n_blocks, int c, do
 
 // ---- the channel-sum folds of a whole backward pass in ONE launch (dn_channel_sum_fold_multi).  The sums they finish -- bias
 // gradients: leaves of the backward -- are not read before the optimizer step, so the launches that leave the partials
-// (dn_bn_train_backward_finish_bias_deferred, dn_channel_sum_partial) need not be followed by a fold each (26 launches of
+// (dn_bn_bwd_out.n_blocks, dn_channel_sum_partial) need not be followed by a fold each (26 launches of
 // 5 us per step).  Jobs ride in the kernel arguments; one wavefront per (job, channel) runs fold_channel_sum_kernel's body.
 constexpr int kFoldJobs = 32;
 struct FoldJobs {
@@ -474,7 +474,7 @@ struct GradSrc {
       g = dy_a[row * ld_a + cc];
     }
     if (dy_b) g += dy_b[row * ld_b + cc];
-    if (relu == 2) {          // y is the byte mask of dn_bn_train_apply_mask (c % 4 == 0)
+    if (relu == 2) {          // y is the byte mask of dn_bn_train_apply (c % 4 == 0)
       if (!((reinterpret_cast<const unsigned char*>(y)[(row * c + cc) >> 2] >> (cc & 3)) & 1)) g = 0.f;
     } else if (relu && !(y[row * c + cc] > 0.f)) g = 0.f;
     return g;
@@ -1152,50 +1152,23 @@ int bn_stats_reduce(const float* z, int n_groups, long rows_per_group, int c, in
   return 0;
 }
 
-int bn_stats_one_call(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
-                      float* mean, float* var, float* rmean, float* rvar, float momentum, long unbias_rows, void* stream) {
-  DN_REQUIRE(mean && var, "bn stats: null pointer");
-  DN_REQUIRE(!rmean || (rvar && n_groups == 1), "bn stats: the fused running-statistics update takes one group");
-  hipStream_t s = (hipStream_t)stream;
-  int nblk;
-  if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
-  // fold + finish (+ the running statistics) in one launch: the sums and statistics of the two-launch path, bit for bit
-  hipLaunchKernelGGL(fold_stats_finish_kernel, dim3((n_groups * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups, nblk, c,
-                     n_groups, rows_per_group, sums, mean, var, rmean, rvar, momentum, unbias_rows);
-  return dn::check_launch("bn_stats_kernel");
-}
-
-// dn_bn_train_apply; relu_mask: dn_bn_train_apply_mask (relu on, the float4 kernels only)
-int bn_apply_impl(const float* z, const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
-                  int n_groups, long rows_per_group, int c, int ldz, float* y, unsigned char* relu_mask, void* stream) {
-  DN_REQUIRE(z && mean && var && gamma && beta && y, "bn apply: null pointer");
-  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && ldz >= c, "bn apply: bad shape");
-  const BnForm f = bn_form(n_groups, rows_per_group, c, {ldz}, {z, y, mean, var, gamma, beta});
-  DN_REQUIRE(!relu_mask || f.k != BnKernels::general, "bn apply (mask): needs c %% 4 == 0 and 16-byte aligned tensors");
-  const long total = (long)n_groups * rows_per_group * c;
-  if (f.k == BnKernels::fast)
-    hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
-                       gamma, beta, eps, relu, c, f.shift, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)nullptr, 1u,
-                       (unsigned*)nullptr);
-  else if (f.k == BnKernels::vec4)
-    hipLaunchKernelGGL(bn_apply_v4_kernel, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
-                       gamma, beta, eps, relu, rows_per_group, c, ldz, total / 4, y, relu_mask);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, z,
-                       mean, var, gamma, beta, eps, relu, rows_per_group, c, ldz, total, y);
-  return dn::check_launch("bn_apply_kernel");
-}
-
-// the arguments both phases of the backward take
-int bn_backward_args(int ld_a, int up_a, const float* dy_b, int ld_b, const float* y, int relu, int n_groups, int h, int w,
-                     int images_per_group, int c) {
-  DN_REQUIRE(!relu || y, "bn backward: relu needs y");
+// the description both phases of the backward take
+int bn_backward_args(const dn_bn_bwd_desc* d) {
+  DN_REQUIRE(d && d->dy_a && d->z && d->mean && d->var, "bn backward: null pointer");
+  const int ld_a = d->ld_a, up_a = d->up_a, ld_b = d->ld_b, relu = d->relu, n_groups = d->n_groups, h = d->h, w = d->w,
+            images_per_group = d->images_per_group, c = d->c;
+  const float* dy_b = d->dy_b;
+  DN_REQUIRE(!relu || d->y, "bn backward: relu needs y");
   DN_REQUIRE(relu >= 0 && relu <= 2 && (relu != 2 || c % 4 == 0), "bn backward: relu = 2 (y is the byte mask) needs c %% 4 == 0");
   DN_REQUIRE(up_a >= 0 && up_a <= 2 && (up_a != 2 || (h % 2 == 0 && w % 2 == 0 && ld_a >= 4 * c)),
              "bn backward: up_a = 2 (dy_a is the space-to-depth image [h / 2][w / 2][4 c]) needs even h, w and ld_a >= 4 c");
   DN_REQUIRE(n_groups > 0 && h > 0 && w > 0 && images_per_group > 0 && c > 0 && c <= kMaxC && ld_a >= c && (!dy_b || ld_b >= c),
              "bn backward: bad shape");
   return 0;
+}
+
+GradSrc bn_grad_src(const dn_bn_bwd_desc* d) {
+  return GradSrc{d->dy_a, d->dy_b, (const float*)d->y, d->ld_a, d->up_a, d->ld_b, d->relu, d->h, d->w, d->c};
 }
 
 }  // namespace
@@ -1206,7 +1179,7 @@ extern "C" size_t dn_reduce_workspace_bytes(int n_groups, long rows_per_group, i
   return sizeof(double) * 2 * c * n_groups * (size_t)(1 + blocks_per_group(rows_per_group, n_groups));
 }
 
-// workspace of the fused bias gradient of dn_bn_train_backward_finish_bias: [c] folded sums + one double per (workgroup of
+// workspace of the fused bias gradient (dn_bn_bwd_out.dbias): [c] folded sums + one double per (workgroup of
 // the apply launch, channel)
 // workgroups of the apply launch when it also leaves the bias partials: every workgroup is one row of partials for the fold
 // (one wavefront per channel walks them), so fewer than the plain launch's 8192
@@ -1250,45 +1223,56 @@ extern "C" int dn_bn_train_stats_finish(const double* sums, int n_groups, long n
   return dn::check_launch("bn_stats_finalize_kernel");
 }
 
-extern "C" int dn_bn_train_stats(const float* z, int n_groups, long rows_per_group, int c, int ldz,
-                                 double* sums, size_t sums_bytes, float* mean, float* var, void* stream) {
-  return bn_stats_one_call(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, mean, var, nullptr, nullptr, 0.f, 0, stream);
+extern "C" int dn_bn_train_stats(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
+                                 float* mean, float* var, float* running_mean, float* running_var, float momentum, void* stream) {
+  DN_REQUIRE(mean && var, "bn stats: null pointer");
+  DN_REQUIRE(!running_mean == !running_var, "bn stats (+ running): running_mean and running_var go together: null pointer");
+  DN_REQUIRE(!running_mean || n_groups == 1, "bn stats: the fused running-statistics update takes one group");
+  hipStream_t s = (hipStream_t)stream;
+  int nblk;
+  if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
+  // fold + finish (+ the running statistics) in one launch: the sums and statistics of the two-launch path, bit for bit
+  hipLaunchKernelGGL(fold_stats_finish_kernel, dim3((n_groups * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups, nblk, c,
+                     n_groups, rows_per_group, sums, mean, var, running_mean, running_var, running_mean ? momentum : 0.f,
+                     running_mean ? rows_per_group : 0L);
+  return dn::check_launch("bn_stats_kernel");
 }
 
-extern "C" int dn_bn_train_stats_running(const float* z, long rows, int c, int ldz, double* sums, size_t sums_bytes, float* mean,
-                                         float* var, float* running_mean, float* running_var, float momentum, void* stream) {
-  DN_REQUIRE(running_mean && running_var, "bn stats (+ running): null pointer");
-  return bn_stats_one_call(z, 1, rows, c, ldz, sums, sums_bytes, mean, var, running_mean, running_var, momentum, rows, stream);
-}
-
-extern "C" int dn_bn_train_apply(const float* z, const float* mean, const float* var,
-                                 const float* gamma, const float* beta, float eps, int relu,
-                                 int n_groups, long rows_per_group, int c, int ldz, float* y,
-                                 void* stream) {
-  return bn_apply_impl(z, mean, var, gamma, beta, eps, relu, n_groups, rows_per_group, c, ldz, y, nullptr, stream);
-}
-
-extern "C" int dn_bn_train_apply_mask(const float* z, const float* mean, const float* var, const float* gamma,
-                                      const float* beta, float eps, int n_groups, long rows_per_group, int c, int ldz,
-                                      float* y, unsigned char* relu_mask, void* stream) {
-  DN_REQUIRE(relu_mask, "bn apply (mask): null pointer");
-  return bn_apply_impl(z, mean, var, gamma, beta, eps, 1, n_groups, rows_per_group, c, ldz, y, relu_mask, stream);
-}
-
-extern "C" int dn_bn_train_apply_mask_sp(const float* z, const float* mean, const float* var, const float* gamma,
-                                         const float* beta, float eps, long rows, int hw, int c, int ldz, float* y,
-                                         unsigned char* relu_mask, void* y_sp, void* stream) {
-  DN_REQUIRE(z && mean && var && gamma && beta && y && relu_mask && y_sp, "bn apply (mask + SP): null pointer");
-  DN_REQUIRE(rows > 0 && hw > 0 && rows % hw == 0 && c > 0 && ldz >= c, "bn apply (mask + SP): bad shape");
-  DN_REQUIRE(dn_bn_train_form_supported(DN_BN_FORM_SP_APPLY, 1, rows, c),
-             "bn apply (mask + SP): needs c %% 16 == 0, c / 4 a power of two, c <= %d and the map below 2^31 float4s (c = %d)", kMaxC, c);
+extern "C" int dn_bn_train_apply(const float* z, const float* mean, const float* var, const float* gamma, const float* beta,
+                                 float eps, int relu, int n_groups, long rows_per_group, int c, int ldz, float* y,
+                                 unsigned char* relu_mask, void* y_sp, int hw, void* stream) {
+  DN_REQUIRE(z && mean && var && gamma && beta && y, "bn apply: null pointer");
+  DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0 && ldz >= c, "bn apply: bad shape");
+  DN_REQUIRE(!relu_mask || relu == 1, "bn apply (mask): the relu mask is written with relu = 1 only");
+  const long total = (long)n_groups * rows_per_group * c;
+  hipStream_t s = (hipStream_t)stream;
+  if (!y_sp) {
+    const BnForm f = bn_form(n_groups, rows_per_group, c, {ldz}, {z, y, mean, var, gamma, beta});
+    DN_REQUIRE(!relu_mask || f.k != BnKernels::general, "bn apply (mask): needs c %% 4 == 0 and 16-byte aligned tensors");
+    if (f.k == BnKernels::fast)
+      hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, z, mean, var,
+                         gamma, beta, eps, relu, c, f.shift, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)nullptr, 1u,
+                         (unsigned*)nullptr);
+    else if (f.k == BnKernels::vec4)
+      hipLaunchKernelGGL(bn_apply_v4_kernel, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, z, mean, var,
+                         gamma, beta, eps, relu, rows_per_group, c, ldz, total / 4, y, relu_mask);
+    else
+      hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, z,
+                         mean, var, gamma, beta, eps, relu, rows_per_group, c, ldz, total, y);
+    return dn::check_launch("bn_apply_kernel");
+  }
+  // y_sp: the one-group fast kernel that also writes the SP copy
+  DN_REQUIRE(relu_mask, "bn apply (mask + SP): y_sp needs relu_mask: null pointer");
+  DN_REQUIRE(hw > 0 && rows_per_group % hw == 0, "bn apply (mask + SP): bad shape");
+  DN_REQUIRE(dn_bn_train_form_supported(DN_BN_FORM_SP_APPLY, n_groups, rows_per_group, c),
+             "bn apply (mask + SP): needs one group, c %% 16 == 0, c / 4 a power of two, c <= %d and the map below 2^31 float4s (c = %d, groups = %d)",
+             kMaxC, c, n_groups);
   DN_REQUIRE(vec4_ok(c, {ldz}, {z, y, mean, var, gamma, beta}) && (reinterpret_cast<uintptr_t>(y_sp) & 15) == 0,
              "bn apply (mask + SP): needs 16-byte aligned tensors");
-  const long total = rows * c;
   unsigned* flags = dn::sp_range_word();
   DN_REQUIRE(flags, "bn apply (mask + SP): the range word of the split-f16 engine is not addressable");
-  const int fsh = bn_fast_shift(1, rows, c, false);      // (the SP form has no general-kernel twin for DN_BN_LEGACY to select)
-  hipLaunchKernelGGL(bn_apply_v4_fast_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, (hipStream_t)stream, z, mean, var,
+  const int fsh = bn_fast_shift(1, rows_per_group, c, false);      // (the SP form has no general-kernel twin for DN_BN_LEGACY to select)
+  hipLaunchKernelGGL(bn_apply_v4_fast_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, z, mean, var,
                      gamma, beta, eps, 1, c, fsh, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)y_sp, (unsigned)hw, flags);
   return dn::check_launch("bn_apply_kernel (mask + SP)");
 }
@@ -1303,27 +1287,29 @@ extern "C" int dn_bn_update_running(const float* mean, const float* var, int n_g
   return dn::check_launch("bn_update_running_kernel");
 }
 
+static_assert(sizeof(dn_bn_bwd_desc) == 7 * sizeof(void*) + 10 * 4 && sizeof(dn_bn_bwd_out) == 5 * sizeof(void*) + 16,
+              "dn_bn_bwd_desc / dn_bn_bwd_out: the layout include/disconet_train.h documents (and _lib.py restates)");
+
 // phase 1 of the backward: this rank's sums of g and g * zhat (folded, at the start of `sums`) and the parameter gradients
 // out of THESE rows (dgamma / dbeta are sums over rows: ranks add theirs with the gradient all-reduce)
-extern "C" int dn_bn_train_backward_partial(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                            const float* y, const float* z, const float* mean, const float* var, float eps,
-                                            int relu, int n_groups, int h, int w, int images_per_group, int c, double* sums,
-                                            size_t sums_bytes, float* dgamma, float* dbeta, int accumulate, void* stream) {
-  DN_REQUIRE(dy_a && z && mean && var && sums && dgamma && dbeta, "bn backward: null pointer");
-  if (int rc = bn_backward_args(ld_a, up_a, dy_b, ld_b, y, relu, n_groups, h, w, images_per_group, c)) return rc;
+extern "C" int dn_bn_train_backward_partial(const dn_bn_bwd_desc* d, double* sums, size_t sums_bytes, float* dgamma, float* dbeta,
+                                            int accumulate, void* stream) {
+  if (int rc = bn_backward_args(d)) return rc;
+  DN_REQUIRE(sums && dgamma && dbeta, "bn backward: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const long rows_per_group = (long)images_per_group * h * w;
+  const int n_groups = d->n_groups, c = d->c;
+  const long rows_per_group = (long)d->images_per_group * d->h * d->w;
   DN_REQUIRE(sums_bytes >= dn_reduce_workspace_bytes(n_groups, rows_per_group, c),
              "bn backward: workspace of %zu bytes, dn_reduce_workspace_bytes() asks for %zu", sums_bytes,
              dn_reduce_workspace_bytes(n_groups, rows_per_group, c));
-  GradSrc src{dy_a, dy_b, y, ld_a, up_a, ld_b, relu, h, w, c};
+  const GradSrc src = bn_grad_src(d);
   const int nblk = blocks_per_group(rows_per_group, n_groups);
   double* part = sums + (size_t)2 * c * n_groups;      // workspace layout: see dn_bn_train_stats_partial
-  if (bn_form(n_groups, rows_per_group, c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var}).k != BnKernels::general)
-    hipLaunchKernelGGL(bn_legacy() ? bn_bwd_reduce_v4_kernel<1> : bn_bwd_reduce_v4_kernel<2>, dim3(nblk, n_groups), dim3(256), 0, s, src, z, mean, var, eps,
+  if (bn_form(n_groups, rows_per_group, c, {d->ld_a, d->dy_b ? d->ld_b : 0}, {d->dy_a, d->dy_b, d->y, d->z, d->mean, d->var}).k != BnKernels::general)
+    hipLaunchKernelGGL(bn_legacy() ? bn_bwd_reduce_v4_kernel<1> : bn_bwd_reduce_v4_kernel<2>, dim3(nblk, n_groups), dim3(256), 0, s, src, d->z, d->mean, d->var, d->eps,
                        rows_per_group, part);
   else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk, n_groups), dim3(256), 0, s, src, z, mean, var, eps,
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk, n_groups), dim3(256), 0, s, src, d->z, d->mean, d->var, d->eps,
                        rows_per_group, part);
   if (n_groups == 1 && !bn_legacy()) {      // fold + parameter gradients in one launch (same sums, same bits)
     hipLaunchKernelGGL(fold_param_grad_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, nblk, c, sums, dgamma, dbeta, accumulate);
@@ -1336,87 +1322,71 @@ extern "C" int dn_bn_train_backward_partial(const float* dy_a, int ld_a, int up_
   return dn::check_launch("bn_backward reduce kernels");
 }
 
-// phase 2: dz of this rank's rows from the (all-reduced) sums, means taken over norm_rows rows per group
-namespace {
-int bn_backward_finish_impl(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                            const float* y, const float* z, const float* mean, const float* var,
-                            const float* gamma, float eps, int relu, int n_groups, int h, int w,
-                            int images_per_group, int c, const double* sums, long norm_rows, float* dz,
-                            void* dz_sp, float sp_lift, void* stream, float* dbias = nullptr, double* bias_ws = nullptr,
-                            size_t bias_ws_bytes = 0, int* defer_blocks = nullptr) {
-  DN_REQUIRE(dy_a && z && mean && var && gamma && sums && (dz || dz_sp), "bn backward finish: null pointer");
-  if (int rc = bn_backward_args(ld_a, up_a, dy_b, ld_b, y, relu, n_groups, h, w, images_per_group, c)) return rc;
+// phase 2: what `out` asks for of this rank's rows from the (all-reduced) sums, means taken over norm_rows rows per group
+extern "C" int dn_bn_train_backward_finish(const dn_bn_bwd_desc* d, const double* sums, long norm_rows, const dn_bn_bwd_out* out,
+                                           void* stream) {
+  if (int rc = bn_backward_args(d)) return rc;
+  DN_REQUIRE(d->gamma && sums && out && (out->dz || out->dz_sp), "bn backward finish: null pointer");
   DN_REQUIRE(norm_rows > 0, "bn backward finish: bad shape");
   hipStream_t s = (hipStream_t)stream;
-  const long rows_per_group = (long)images_per_group * h * w;
-  // dz NULL (round 6): only the SP copy is written -- for a layer whose weight gradient (dn_conv_wgrad_sp_z), data gradient and
-  // bias gradient all read dz through this launch's other outputs; the one-group fast kernels only
+  const int n_groups = d->n_groups, c = d->c, h = d->h, w = d->w;
+  const long rows_per_group = (long)d->images_per_group * h * w;
+  float* dz = out->dz;
+  // dz NULL (round 6): only the SP copy is written; the one-group fast kernels only
   DN_REQUIRE(dz || dn_bn_train_form_supported(DN_BN_FORM_DZ_NULL, n_groups, rows_per_group, c),
              "bn backward: dz may be NULL only where the one-group fast form runs (one group, c %% 16 == 0, c / 4 a power of two; DN_BN_LEGACY unset)");
-  const BnForm f = bn_form(n_groups, rows_per_group, c, {ld_a, dy_b ? ld_b : 0}, {dy_a, dy_b, y, z, mean, var, gamma, dz});
-  const bool bias = dbias || defer_blocks;
+  const BnForm f = bn_form(n_groups, rows_per_group, c, {d->ld_a, d->dy_b ? d->ld_b : 0},
+                           {d->dy_a, d->dy_b, d->y, d->z, d->mean, d->var, d->gamma, dz});
+  const bool bias = out->dbias || out->n_blocks;
+  DN_REQUIRE(!(out->dbias && out->n_blocks), "bn backward: dbias is either folded here (dbias) or deferred (n_blocks), not both");
   DN_REQUIRE(!bias || (dn_bn_train_form_supported(DN_BN_FORM_BIAS, n_groups, rows_per_group, c) && f.k != BnKernels::general),
-             "bn backward: the fused bias gradient needs the one-group fast form (c / 4 a power of two, aligned tensors; DN_BN_LEGACY unset)");
+             "bn backward: the fused bias gradient needs the one-group fast form (one group, c / 4 a power of two, aligned tensors; DN_BN_LEGACY unset)");
   unsigned* flags = nullptr;
-  if (dz_sp) {
-    DN_REQUIRE(n_groups == 1 && c % 16 == 0 && f.k != BnKernels::general && (reinterpret_cast<uintptr_t>(dz_sp) & 15) == 0 &&
+  if (out->dz_sp) {
+    DN_REQUIRE(n_groups == 1 && c % 16 == 0 && f.k != BnKernels::general && (reinterpret_cast<uintptr_t>(out->dz_sp) & 15) == 0 &&
                    rows_per_group < (1L << 31),
                "bn backward: the SP copy of dz needs one group, c %% 16 == 0, 16-byte aligned tensors (c = %d, groups = %d)", c, n_groups);
-    DN_REQUIRE(sp_lift > 0.f && std::isfinite(sp_lift), "bn backward: sp_lift must be a positive finite power of two");
+    DN_REQUIRE(out->sp_lift > 0.f && std::isfinite(out->sp_lift), "bn backward: sp_lift must be a positive finite power of two");
     flags = dn::sp_range_word();
     DN_REQUIRE(flags, "bn backward: the range word of the split-f16 engine is not addressable");
   }
-  GradSrc src{dy_a, dy_b, y, ld_a, up_a, ld_b, relu, h, w, c};
+  const GradSrc src = bn_grad_src(d);
   const long total = (long)n_groups * rows_per_group * c;
-  unsigned char* sp = (unsigned char*)dz_sp;
-  const float lift = dz_sp ? sp_lift : 1.f;
+  unsigned char* sp = (unsigned char*)out->dz_sp;
+  const float lift = sp ? out->sp_lift : 1.f;
   if (bias) {
     // the fused bias gradient (round 6): the apply launch leaves one double per (workgroup, channel), folded in a fixed order
     const int blocks = grid_for(total / 4, kBiasBlocks);
-    DN_REQUIRE(bias_ws && bias_ws_bytes >= dn_bn_bias_workspace_bytes(rows_per_group, c),
-               "bn backward: bias workspace of %zu bytes, dn_bn_bias_workspace_bytes() asks for %zu", bias_ws_bytes,
+    DN_REQUIRE(out->bias_ws && out->bias_ws_bytes >= dn_bn_bias_workspace_bytes(rows_per_group, c),
+               "bn backward: bias workspace of %zu bytes, dn_bn_bias_workspace_bytes() asks for %zu", (size_t)out->bias_ws_bytes,
                dn_bn_bias_workspace_bytes(rows_per_group, c));
-    double* part = bias_ws + c;      // [c] folded sums, then [blocks][c] partials
-    hipLaunchKernelGGL((dz_sp ? bn_bwd_apply_v4_fast_kernel<true, true> : bn_bwd_apply_v4_fast_kernel<false, true>), dim3(blocks), dim3(256), 0,
-                       s, src, z, mean, var, gamma, eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, (unsigned)(h * w), flags, part);
-    if (defer_blocks)      // the fold is the caller's (dn_channel_sum_fold_multi): the partials stay in bias_ws
-      *defer_blocks = blocks;
+    double* part = out->bias_ws + c;      // [c] folded sums, then [blocks][c] partials
+    hipLaunchKernelGGL((sp ? bn_bwd_apply_v4_fast_kernel<true, true> : bn_bwd_apply_v4_fast_kernel<false, true>), dim3(blocks), dim3(256), 0,
+                       s, src, d->z, d->mean, d->var, d->gamma, d->eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, (unsigned)(h * w), flags, part);
+    if (out->n_blocks)      // the fold is the caller's (dn_channel_sum_fold_multi): the partials stay in bias_ws
+      *out->n_blocks = blocks;
     else
-      hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, blocks, c, bias_ws, dbias, 0);
+      hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, blocks, c, out->bias_ws, out->dbias, 0);
     return dn::check_launch("bn backward apply kernel (+ bias gradient)");
   }
-  const unsigned hw = dz_sp ? (unsigned)(h * w) : 1u;
+  const unsigned hw = sp ? (unsigned)(h * w) : 1u;
   if (f.k == BnKernels::fast)
-    hipLaunchKernelGGL(dz_sp ? bn_bwd_apply_v4_fast_kernel<true> : bn_bwd_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256),
-                       0, s, src, z, mean, var, gamma, eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, hw, flags, (double*)nullptr);
+    hipLaunchKernelGGL(sp ? bn_bwd_apply_v4_fast_kernel<true> : bn_bwd_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256),
+                       0, s, src, d->z, d->mean, d->var, d->gamma, d->eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, hw, flags, (double*)nullptr);
   else if (f.k == BnKernels::vec4)
-    hipLaunchKernelGGL(dz_sp ? bn_bwd_apply_v4_kernel<true> : bn_bwd_apply_v4_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s,
-                       src, z, mean, var, gamma, eps, rows_per_group, norm_rows, sums, total / 4, dz, sp, lift, hw, flags);
+    hipLaunchKernelGGL(sp ? bn_bwd_apply_v4_kernel<true> : bn_bwd_apply_v4_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s,
+                       src, d->z, d->mean, d->var, d->gamma, d->eps, rows_per_group, norm_rows, sums, total / 4, dz, sp, lift, hw, flags);
   else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, src, z, mean,
-                       var, gamma, eps, rows_per_group, norm_rows, sums, total, dz);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, src, d->z, d->mean,
+                       d->var, d->gamma, d->eps, rows_per_group, norm_rows, sums, total, dz);
   return dn::check_launch("bn_backward apply kernels");
 }
-}  // namespace
 
-extern "C" int dn_bn_train_backward_finish_bias(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                                const float* y, const float* z, const float* mean, const float* var,
-                                                const float* gamma, float eps, int relu, int h, int w, int images, int c,
-                                                const double* sums, long norm_rows, float* dz, void* dz_sp, float sp_lift,
-                                                float* dbias, double* bias_ws, size_t bias_ws_bytes, void* stream) {
-  DN_REQUIRE(dbias && bias_ws, "bn backward finish (+ bias gradient): null pointer");
-  return bn_backward_finish_impl(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, gamma, eps, relu, 1, h, w, images, c, sums,
-                                 norm_rows, dz, dz_sp, sp_lift, stream, dbias, bias_ws, bias_ws_bytes);
-}
-
-extern "C" int dn_bn_train_backward_finish_bias_deferred(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                                         const float* y, const float* z, const float* mean, const float* var,
-                                                         const float* gamma, float eps, int relu, int h, int w, int images, int c,
-                                                         const double* sums, long norm_rows, float* dz, void* dz_sp, float sp_lift,
-                                                         double* bias_ws, size_t bias_ws_bytes, int* n_blocks, void* stream) {
-  DN_REQUIRE(bias_ws && n_blocks, "bn backward finish (bias gradient deferred): null pointer");
-  return bn_backward_finish_impl(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, gamma, eps, relu, 1, h, w, images, c, sums,
-                                 norm_rows, dz, dz_sp, sp_lift, stream, nullptr, bias_ws, bias_ws_bytes, n_blocks);
+extern "C" int dn_bn_train_backward(const dn_bn_bwd_desc* d, double* sums, size_t sums_bytes, const dn_bn_bwd_out* out,
+                                    float* dgamma, float* dbeta, int accumulate, void* stream) {
+  DN_REQUIRE(d && d->gamma && out && (out->dz || out->dz_sp), "bn backward: null pointer");
+  if (int rc = dn_bn_train_backward_partial(d, sums, sums_bytes, dgamma, dbeta, accumulate, stream)) return rc;
+  return dn_bn_train_backward_finish(d, sums, (long)d->images_per_group * d->h * d->w, out, stream);
 }
 
 extern "C" int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, void* stream) {
@@ -1438,39 +1408,6 @@ extern "C" int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, vo
     hipLaunchKernelGGL(fold_channel_sum_multi_kernel, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, J, n);
   }
   return dn::check_launch("fold_channel_sum_multi_kernel");
-}
-
-extern "C" int dn_bn_train_backward_finish(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                           const float* y, const float* z, const float* mean, const float* var,
-                                           const float* gamma, float eps, int relu, int n_groups, int h, int w,
-                                           int images_per_group, int c, const double* sums, long norm_rows, float* dz,
-                                           void* stream) {
-  return bn_backward_finish_impl(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, gamma, eps, relu, n_groups, h, w,
-                                 images_per_group, c, sums, norm_rows, dz, nullptr, 1.f, stream);
-}
-
-extern "C" int dn_bn_train_backward_finish_sp(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                              const float* y, const float* z, const float* mean, const float* var,
-                                              const float* gamma, float eps, int relu, int n_groups, int h, int w,
-                                              int images_per_group, int c, const double* sums, long norm_rows, float* dz,
-                                              void* dz_sp, float sp_lift, void* stream) {
-  DN_REQUIRE(dz_sp, "bn backward finish (SP copy): null pointer");
-  return bn_backward_finish_impl(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, gamma, eps, relu, n_groups, h, w,
-                                 images_per_group, c, sums, norm_rows, dz, dz_sp, sp_lift, stream);
-}
-
-extern "C" int dn_bn_train_backward(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                                    const float* y, const float* z, const float* mean,
-                                    const float* var, const float* gamma, float eps, int relu,
-                                    int n_groups, int h, int w, int images_per_group, int c,
-                                    double* sums, size_t sums_bytes, float* dz, float* dgamma, float* dbeta,
-                                    int accumulate, void* stream) {
-  DN_REQUIRE(gamma && dz, "bn backward: null pointer");
-  if (int rc = dn_bn_train_backward_partial(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, eps, relu, n_groups, h, w,
-                                            images_per_group, c, sums, sums_bytes, dgamma, dbeta, accumulate, stream))
-    return rc;
-  return dn_bn_train_backward_finish(dy_a, ld_a, up_a, dy_b, ld_b, y, z, mean, var, gamma, eps, relu, n_groups, h, w,
-                                     images_per_group, c, sums, (long)images_per_group * h * w, dz, stream);
 }
 
 extern "C" int dn_channel_sum_partial(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, int* n_blocks,

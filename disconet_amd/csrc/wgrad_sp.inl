@@ -28,7 +28,7 @@ struct WgradSpArgs {
   const unsigned char* dz_sp;      // ZSP kernels: dz * dz_lift as the SP tensor the BatchNorm backward wrote (include/disconet_hip.h "SP tensor")
 };
 
-// ZSP (round 6): dz comes PRE-SPLIT -- the SP copy of dz * lift that dn_bn_train_backward_finish_sp / _bias write for the data
+// ZSP (round 6): dz comes PRE-SPLIT -- the SP copy of dz * lift that the BatchNorm backward (dn_bn_bwd_out.dz_sp) writes for the data
 // gradient, the same hi / lo halves this kernel's staging pass derives from the fp32 rows (same lift, same split: the results are
 // the same bits) -- so the fp32 copy of dz need not be written at all, and the tile's staging is 16 byte permutes per 16 values
 // instead of a multiply, two conversions and a subtraction per value.  A thread takes the hi and lo pieces (8 channels each) of

@@ -503,7 +503,7 @@ class TrainEngine:
         (None, None) / (None, 1.0) while the lift is still unknown.  The engine's operands are f16 hi + lo pairs: 2^-22 relative
         only while 2^-3 <= |x| <= 65504, and a gradient's magnitude is anything -- so dz is LIFTED by a power of two that puts its
         largest element near 2^8 (19 binades of full precision below it, 256 x of head room above; include/disconet_train.h ::
-        dn_bn_train_backward_finish_sp).  The lift of a layer is measured (max |dz|, a host read) on the first step, which runs
+        dn_bn_bwd_out.sp_lift).  The lift of a layer is measured (max |dz|, a host read) on the first step, which runs
         that layer's data gradient in fp32, and again every 64 steps; a dz that outgrows it is clamped AND flagged (the range
         guard polled at the end of the pass: backward() then drops the lifts and repeats the pass on the fp32 kernels)."""
         d = c["desc"]

@@ -106,7 +106,7 @@ def bn_stats(z, n_groups=1, sync=None, norm_rows=None, running=None):
     sync (agent-parallel training): callable that all-reduces a float64 tensor in place -- this rank's sums are reduced,
     `sync` adds the other ranks', and the statistics are normalised by `norm_rows` rows per group (the global count).
     running = (running_mean, running_var, momentum): one group, no sync -- the momentum update of the running statistics leaves
-    the launch that finishes the statistics (dn_bn_train_stats_running), bit for bit bn_update_running's."""
+    the launch that finishes the statistics (dn_bn_train_stats' running_mean / running_var), bit for bit bn_update_running's."""
     _need_gpu(z)
     if running is not None and (sync is not None or n_groups != 1):
         raise _lib.DnError("bn_stats: the fused running-statistics update takes one group and no sync")
@@ -124,14 +124,11 @@ def bn_stats(z, n_groups=1, sync=None, norm_rows=None, running=None):
         sync(_folded(sums, n_groups, c))
         check(lib.dn_bn_train_stats_finish(_ptr(sums), n_groups, int(norm_rows if norm_rows is not None else rpg), c,
                                            _ptr(mean), _ptr(var), _stream()), "dn_bn_train_stats_finish")
-    elif running is not None:
-        rm, rv, momentum = running
-        _need_gpu(rm, rv)
-        check(lib.dn_bn_train_stats_running(_ptr(z), rows, c, c, _ptr(sums), sums.numel(), _ptr(mean), _ptr(var), _ptr(rm), _ptr(rv),
-                                            float(momentum), _stream()), "dn_bn_train_stats_running")
     else:
-        check(lib.dn_bn_train_stats(_ptr(z), n_groups, rpg, c, c, _ptr(sums), sums.numel(), _ptr(mean), _ptr(var), _stream()),
-              "dn_bn_train_stats")
+        rm, rv, momentum = running if running is not None else (None, None, 0.0)
+        _need_gpu(rm, rv)
+        check(lib.dn_bn_train_stats(_ptr(z), n_groups, rpg, c, c, _ptr(sums), sums.numel(), _ptr(mean), _ptr(var), _ptr(rm), _ptr(rv),
+                                    float(momentum), _stream()), "dn_bn_train_stats")
     return mean, var
 
 
@@ -153,8 +150,8 @@ def bn_apply_sp_supported(z, n_groups=1):
 
 def bn_apply(z, mean, var, gamma, beta, eps, relu=True, out=None, relu_mask=None, sp_out=None):
     """relu_mask: a uint8 tensor of z.numel() / 4 bytes that receives the backward's ReLU gate, one byte per four channels
-    (dn_bn_train_apply_mask; relu must be on, c % 4 == 0) -- bn_backward(relu_mask=...) reads it instead of y.
-    sp_out: an ops.SpTensor of z's shape that ALSO receives y as f16 hi / lo planes (dn_bn_train_apply_mask_sp: the operand of
+    (dn_bn_train_apply's relu_mask; relu must be on, c % 4 == 0) -- bn_backward(relu_mask=...) reads it instead of y.
+    sp_out: an ops.SpTensor of z's shape that ALSO receives y as f16 hi / lo planes (dn_bn_train_apply's y_sp: the operand of
     the next layer's forward conv on the split-f16 engine; needs relu_mask, bn_apply_sp_supported)."""
     _need_gpu(z, mean, var, gamma, beta, relu_mask)
     c = z.shape[-1]
@@ -168,17 +165,9 @@ def bn_apply(z, mean, var, gamma, beta, eps, relu=True, out=None, relu_mask=None
                                   or not relu_mask.is_contiguous()):
         raise _lib.DnError("bn_apply: relu_mask must be a contiguous uint8 tensor of z.numel() / 4 bytes, with relu on")
     y = torch.empty_like(z) if out is None else out
-    lib = _lib.load()
-    if sp_out is not None:
-        check(lib.dn_bn_train_apply_mask_sp(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), rows,
-                                            z.shape[1] * z.shape[2], c, c, _ptr(y), _ptr(relu_mask), _ptr(sp_out.data), _stream()),
-              "dn_bn_train_apply_mask_sp")
-    elif relu_mask is not None:
-        check(lib.dn_bn_train_apply_mask(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), n_groups,
-                                         rows // n_groups, c, c, _ptr(y), _ptr(relu_mask), _stream()), "dn_bn_train_apply_mask")
-    else:
-        check(lib.dn_bn_train_apply(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), int(relu), n_groups,
-                                    rows // n_groups, c, c, _ptr(y), _stream()), "dn_bn_train_apply")
+    check(_lib.load().dn_bn_train_apply(_ptr(z), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), float(eps), int(relu), n_groups,
+                                        rows // n_groups, c, c, _ptr(y), _ptr(relu_mask), _ptr(sp_out.data) if sp_out is not None else None,
+                                        z.shape[1] * z.shape[2] if sp_out is not None else 0, _stream()), "dn_bn_train_apply")
     return y
 
 
@@ -207,10 +196,10 @@ def bn_backward(dy_a, y, z, mean, var, gamma, eps, dgamma, dbeta, relu=True, dy_
     optional second gradient (same resolution as y).  Returns dz; fills dgamma / dbeta.
     sync / norm_rows (agent-parallel training, see bn_stats): dgamma / dbeta are then THIS rank's share (sums over its rows).
     sp_out / sp_lift: an ops.SpTensor [n, h, w, c] that also receives dz * sp_lift as f16 hi / lo planes
-    (dn_bn_train_backward_finish_sp: the operand of the split-f16 data gradient; one group, c % 16 == 0).
+    (dn_bn_bwd_out.dz_sp: the operand of the split-f16 data gradient; one group, c % 16 == 0).
     relu_mask: bn_apply's byte mask of (y > 0) -- read in place of y by both passes (relu = 2 of the C entry points).
     dbias [c]: also receives sum over this call's rows of dz -- the gradient of the conv bias in front of this BatchNorm --
-    from the launch that writes dz (dn_bn_train_backward_finish_bias; bn_backward_bias_supported), instead of a channel_sum
+    from the launch that writes dz (dn_bn_bwd_out.dbias; bn_backward_bias_supported), instead of a channel_sum
     pass over dz.  folds (a DeferredFolds): dbias' fold joins it instead of being launched here -- dbias is valid after
     folds.run().  want_dz = False (with sp_out and dbias): the fp32 dz is not written, None is returned -- for a layer whose
     weight gradient reads the SP copy (conv_wgrad(..., dz_sp=))."""
@@ -232,39 +221,41 @@ def bn_backward(dy_a, y, z, mean, var, gamma, eps, dgamma, dbeta, relu=True, dy_
     ipg = n // n_groups
     lib = _lib.load()
     sums = _ws(z.device, lib.dn_reduce_workspace_bytes(n_groups, ipg * h * w, c))
-    src = (_ptr(dy_a), _ld(dy_a), int(up_a), _ptr(dy_b), _ld(dy_b) if dy_b is not None else 0, _ptr(y), _ptr(z),
-           _ptr(mean), _ptr(var))
-    # phase 1: the sums of g and g * zhat, dgamma, dbeta -- with phase 2's plain form in the same library call where nothing is
-    # asked for in between or of phase 2
-    if sync is None and sp_out is None and dbias is None:
-        check(lib.dn_bn_train_backward(*src, _ptr(gamma), float(eps), int(relu), n_groups, h, w, ipg, c, _ptr(sums), sums.numel(),
-                                       _ptr(dz), _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()), "dn_bn_train_backward")
-        return dz
-    check(lib.dn_bn_train_backward_partial(*src, float(eps), int(relu), n_groups, h, w, ipg, c, _ptr(sums), sums.numel(),
-                                           _ptr(dgamma), _ptr(dbeta), int(bool(accumulate)), _stream()),
-          "dn_bn_train_backward_partial")
-    if sync is not None:
+    d = _lib.BnBwdDesc()
+    d.dy_a, d.ld_a, d.up_a = dy_a.data_ptr(), _ld(dy_a), int(up_a)
+    if dy_b is not None:
+        d.dy_b, d.ld_b = dy_b.data_ptr(), _ld(dy_b)
+    if y is not None:
+        d.y = y.data_ptr()
+    d.z, d.mean, d.var, d.gamma = z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr()
+    d.relu, d.n_groups, d.h, d.w, d.images_per_group, d.c, d.eps = int(relu), n_groups, h, w, ipg, c, float(eps)
+    # what phase 2 writes: dz (+ its SP copy, + the bias gradient, folded here or left to `folds`)
+    wr = _lib.BnBwdOut()
+    if dz is not None:
+        wr.dz = dz.data_ptr()
+    if sp_out is not None:
+        wr.dz_sp, wr.sp_lift = sp_out.data.data_ptr(), float(sp_lift)
+    blocks = None
+    if dbias is not None:
+        nbytes = lib.dn_bn_bias_workspace_bytes(n * h * w, c)
+        bws = _ws(z.device, nbytes, _BIAS_WS) if folds is None else folds.workspace(dbias, nbytes)
+        wr.bias_ws, wr.bias_ws_bytes = bws.data_ptr(), bws.numel()
+        if folds is None:
+            wr.dbias = dbias.data_ptr()
+        else:
+            blocks = ctypes.c_int(0)
+            wr.n_blocks = ctypes.addressof(blocks)
+    acc, stream = int(bool(accumulate)), _stream()
+    if sync is None:     # both phases in one library call: nothing is asked for in between
+        check(lib.dn_bn_train_backward(d, _ptr(sums), sums.numel(), wr, _ptr(dgamma), _ptr(dbeta), acc, stream),
+              "dn_bn_train_backward")
+    else:                # phase 1: the sums of g and g * zhat, dgamma, dbeta; the ranks add theirs; phase 2
+        check(lib.dn_bn_train_backward_partial(d, _ptr(sums), sums.numel(), _ptr(dgamma), _ptr(dbeta), acc, stream),
+              "dn_bn_train_backward_partial")
         sync(_folded(sums, n_groups, c))
-    # phase 2: dz (+ its SP copy, + the bias gradient)
-    fin = src + (_ptr(gamma), float(eps), int(relu))
-    rows = int(norm_rows if norm_rows is not None else ipg * h * w)
-    sp = (_ptr(sp_out.data), float(sp_lift)) if sp_out is not None else (None, 1.0)
-    if dbias is None and sp_out is None:
-        check(lib.dn_bn_train_backward_finish(*fin, n_groups, h, w, ipg, c, _ptr(sums), rows, _ptr(dz), _stream()),
+        check(lib.dn_bn_train_backward_finish(d, _ptr(sums), int(norm_rows if norm_rows is not None else ipg * h * w), wr, stream),
               "dn_bn_train_backward_finish")
-    elif dbias is None:
-        check(lib.dn_bn_train_backward_finish_sp(*fin, n_groups, h, w, ipg, c, _ptr(sums), rows, _ptr(dz), *sp, _stream()),
-              "dn_bn_train_backward_finish_sp")
-    elif folds is None:
-        bws = _ws(z.device, lib.dn_bn_bias_workspace_bytes(n * h * w, c), _BIAS_WS)
-        check(lib.dn_bn_train_backward_finish_bias(*fin, h, w, n, c, _ptr(sums), rows, _ptr(dz), *sp, _ptr(dbias), _ptr(bws),
-                                                   bws.numel(), _stream()), "dn_bn_train_backward_finish_bias")
-    else:
-        bws = folds.workspace(dbias, lib.dn_bn_bias_workspace_bytes(n * h * w, c))
-        blocks = ctypes.c_int(0)
-        check(lib.dn_bn_train_backward_finish_bias_deferred(*fin, h, w, n, c, _ptr(sums), rows, _ptr(dz), *sp, _ptr(bws), bws.numel(),
-                                                            ctypes.byref(blocks), _stream()),
-              "dn_bn_train_backward_finish_bias_deferred")
+    if blocks is not None:
         folds.add(bws, blocks.value, c, dbias, False)
     return dz
 

@@ -315,9 +315,9 @@ int dn_spconv2d_dual(const dn_conv_desc* d, const void* src0_sp, const void* src
                      const float* scale, const float* shift, void* out_sp, float* out_nhwc, int ld_nhwc,
                      void* stream);
 /* dn_spconv2d whose ONLY output is the float32 NHWC copy (no SP tensor is written, nothing is split, no magnitude is
- * tracked): the training step's split-f16 data gradient -- src0 = dz as an SP tensor (dn_bn_train_backward_finish_sp),
+ * tracked): the training step's split-f16 data gradient -- src0 = dz as an SP tensor (dn_bn_bwd_out.dz_sp, disconet_train.h),
  * packed = the flipped / transposed weights, scale = 1 / (sp_lift * wmul), shift = 0, relu = 0 -- and (round 6) the training
- * step's FORWARD convs: src = the previous layer's y as the SP tensor dn_bn_train_apply_mask_sp writes, scale = 1 / wmul,
+ * step's FORWARD convs: src = the previous layer's y as the SP tensor dn_bn_train_apply's y_sp receives, scale = 1 / wmul,
  * shift = bias, out = z (what the BatchNorm statistics read).  Same restrictions as dn_spconv2d_dual. */
 int dn_spconv2d_nhwc(const dn_conv_desc* d, const void* src0_sp, const void* src1_sp, const void* packed,
                      const float* scale, const float* shift, float* out_nhwc, int ld_nhwc, void* stream);

@@ -46,7 +46,7 @@ int dn_conv_wgrad(const dn_conv_desc* d, const float* src0, const float* src1, c
  * fp32 accumulation -- 5.3 x the fp32 MFMA's rate per product.  The maps stay what dn_conv_wgrad takes (float32 NHWC, same
  * descriptor, same gather: x2 upsample of source 0, concat); the kernel multiplies by the lifts, splits and transposes while
  * it stages (K = pixels: a lane's fragment is 8 consecutive pixels of one channel).
- *   dz_lift, x_lift: powers of two.  dz_lift brings max |dz| * dz_lift to ~2^8 (the lift of dn_bn_train_backward_finish_sp);
+ *   dz_lift, x_lift: powers of two.  dz_lift brings max |dz| * dz_lift to ~2^8 (the lift of dn_bn_bwd_out.sp_lift);
  *   x_lift (activations: 16) keeps the lo halves of small activations out of the f16 subnormal range.  A lifted value beyond
  *   +-65504 is clamped and sets bit 0 of dn_sp_range_flags: that step's gradients are invalid.  1 / (dz_lift * x_lift) is
  *   applied by the fixed-order slice sum (exact).
@@ -62,10 +62,10 @@ size_t dn_conv_wgrad_sp_workspace(const dn_conv_desc* d);
 int dn_conv_wgrad_sp(const dn_conv_desc* d, const float* src0, const float* src1, const float* dz, void* workspace, float* dw,
                      int dw_cin_total, int accumulate, float dz_lift, float x_lift, void* stream);
 /* dn_conv_wgrad_sp with dz taken from its SP copy (round 6): dz_sp = dz * dz_lift as the SP tensor [n][c_out / 16][4][h_out][w_out]
- * that dn_bn_train_backward_finish_sp / _finish_bias(_deferred) write for the data gradient (c_out % 16 == 0) -- the same hi / lo
+ * that the BatchNorm backward writes for the data gradient (dn_bn_bwd_out.dz_sp; c_out % 16 == 0) -- the same hi / lo
  * halves the fp32 form derives while it stages dz, so dw is the same bits; the staging of the dz tile becomes byte permutes, and
- * a layer whose data gradient and bias gradient do not read the fp32 dz either can pass dz = NULL to those BatchNorm entry
- * points and save the fp32 copy's write (a quarter of that launch's bytes). */
+ * a layer whose data gradient and bias gradient do not read the fp32 dz either can leave dn_bn_bwd_out.dz NULL and save the
+ * fp32 copy's write (a quarter of that launch's bytes). */
 int dn_conv_wgrad_sp_z(const dn_conv_desc* d, const float* src0, const float* src1, const void* dz_sp, void* workspace, float* dw,
                        int dw_cin_total, int accumulate, float dz_lift, float x_lift, void* stream);
 
@@ -92,9 +92,12 @@ int dn_conv_dgrad_class_weights(const float* w_oihw, int c_out, int cin_total, i
  * layers, which see one (ego, neighbour) pair of 1 x C x 32 x 32 per call).
  * sums: workspace of dn_reduce_workspace_bytes(n_groups, rows_per_group, c) bytes (the folded sums and every
  * workgroup's partial: the per-channel sums are DETERMINISTIC -- fixed thread, workgroup and fold order, no
- * atomics).  var is the biased variance. */
-int dn_bn_train_stats(const float* z, int n_groups, long rows_per_group, int c, int ldz,
-                      double* sums, size_t sums_bytes, float* mean, float* var, void* stream);
+ * atomics).  var is the biased variance.
+ *   running_mean, running_var (both or neither; NULL = none; ONE group): the launch that finishes the statistics also applies
+ *   the running-statistics update of dn_bn_update_running (momentum, unbiased variance with rows / (rows - 1)) -- one launch
+ *   instead of three behind the reduction (round 6), bit for bit the separate calls.  momentum is read only then. */
+int dn_bn_train_stats(const float* z, int n_groups, long rows_per_group, int c, int ldz, double* sums, size_t sums_bytes,
+                      float* mean, float* var, float* running_mean, float* running_var, float momentum, void* stream);
 
 /* Two-phase form for a BatchNorm batch that is spread over several ranks (agent-parallel training, disconet_amd/sharded.py):
  *   dn_bn_train_stats_partial   this rank's rows -> the folded sums [n_groups][2 c] doubles (sum z, sum z^2) at the START of `sums`
@@ -105,35 +108,21 @@ int dn_bn_train_stats_partial(const float* z, int n_groups, long rows_per_group,
                               double* sums, size_t sums_bytes, void* stream);
 int dn_bn_train_stats_finish(const double* sums, int n_groups, long norm_rows, int c, float* mean, float* var, void* stream);
 
-/* dn_bn_train_stats for ONE group that also applies the running-statistics update of dn_bn_update_running (momentum, unbiased
- * variance with rows / (rows - 1)) from the launch that finishes the statistics (round 6: one launch instead of three behind the
- * reduction).  Bit for bit the separate calls. */
-int dn_bn_train_stats_running(const float* z, long rows, int c, int ldz, double* sums, size_t sums_bytes, float* mean, float* var,
-                              float* running_mean, float* running_var, float momentum, void* stream);
-
-/* y = act((z - mean) * rsqrt(var + eps) * gamma + beta), act = ReLU if relu */
-int dn_bn_train_apply(const float* z, const float* mean, const float* var, const float* gamma,
-                      const float* beta, float eps, int relu, int n_groups, long rows_per_group,
-                      int c, int ldz, float* y, void* stream);
-
-/* dn_bn_train_apply with ReLU that also writes the ReLU gate of the backward as ONE BYTE PER FOUR CHANNELS:
- * relu_mask[(row * c + ch) / 4] bit (ch % 4) = (y[row][ch] > 0) -- rows * c / 4 bytes, 1/16 of y.  The backward entry points
- * below take it in place of y with relu = 2: their two passes then read 1/4 byte per element where y costs 4 (same gate, same
- * results bit for bit).  c % 4 == 0, 16-byte aligned tensors. */
-int dn_bn_train_apply_mask(const float* z, const float* mean, const float* var, const float* gamma, const float* beta,
-                           float eps, int n_groups, long rows_per_group, int c, int ldz, float* y,
-                           unsigned char* relu_mask, void* stream);
-
-/* dn_bn_train_apply_mask (one group) that ALSO writes y as an SP tensor (include/disconet_hip.h "SP tensor":
- * [image][c / 16][4 quarters][hw][8 halves]; y_sp of dn_sp_tensor_bytes(rows / hw, ., ., c) bytes) -- the operand of the NEXT
- * layer's forward conv on the split-f16 LDS-DMA engine (dn_spconv2d_nhwc), so that the training forward runs the inference
- * engine's kernels instead of splitting fp32 rows on the VALU while staging them (round 6).  The split is dn_sp_from_nhwc's
- * (clamp to +-65504, hi = half(y), lo = half(y - hi)); a clamped value sets the engine's sticky range flag.  y (fp32) is
- * still written: the weight gradient of the next layer and the skip consumers read it.  rows % hw == 0, c % 16 == 0, c / 4 a
- * power of two, 16-byte aligned tensors. */
-int dn_bn_train_apply_mask_sp(const float* z, const float* mean, const float* var, const float* gamma, const float* beta,
-                              float eps, long rows, int hw, int c, int ldz, float* y, unsigned char* relu_mask, void* y_sp,
-                              void* stream);
+/* y = act((z - mean) * rsqrt(var + eps) * gamma + beta), act = ReLU if relu.  Two optional outputs of the same launch:
+ *   relu_mask (NULL = none; relu == 1, c % 4 == 0, 16-byte aligned tensors): the ReLU gate of the backward as ONE BYTE PER FOUR
+ *     CHANNELS, relu_mask[(row * c + ch) / 4] bit (ch % 4) = (y[row][ch] > 0) -- rows * c / 4 bytes, 1/16 of y.  The backward
+ *     takes it in place of y with dn_bn_bwd_desc.relu = 2: its two passes then read 1/4 byte per element where y costs 4 (same
+ *     gate, same results bit for bit).
+ *   y_sp (NULL = none; needs relu_mask, ONE group and DN_BN_FORM_SP_APPLY below; rows_per_group % hw == 0, hw = pixels per
+ *     image; 16-byte aligned tensors): y ALSO as an SP tensor (include/disconet_hip.h "SP tensor": [image][c / 16][4 quarters]
+ *     [hw][8 halves]; dn_sp_tensor_bytes(rows / hw, ., ., c) bytes) -- the operand of the NEXT layer's forward conv on the
+ *     split-f16 LDS-DMA engine (dn_spconv2d_nhwc), so that the training forward runs the inference engine's kernels instead of
+ *     splitting fp32 rows on the VALU while staging them (round 6).  The split is dn_sp_from_nhwc's (clamp to +-65504,
+ *     hi = half(y), lo = half(y - hi)); a clamped value sets the engine's sticky range flag.  y (fp32) is still written: the
+ *     weight gradient of the next layer and the skip consumers read it.  hw is read only with y_sp. */
+int dn_bn_train_apply(const float* z, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                      int relu, int n_groups, long rows_per_group, int c, int ldz, float* y, unsigned char* relu_mask,
+                      void* y_sp, int hw, void* stream);
 
 /* running = (1 - momentum) * running + momentum * batch stat, group after group in the order
  * `order` lists them (null = 0..n_groups-1); running_var takes the unbiased variance. */
@@ -141,60 +130,68 @@ int dn_bn_update_running(const float* mean, const float* var, int n_groups, long
                          int c, const int* order, float momentum, float* running_mean,
                          float* running_var, void* stream);
 
-/* Backward of y = act(bn(z)).  The incoming gradient is dy_a (+ dy_b if not null); each has
- * its own row stride, and dy_a may live at twice the resolution (up_a = 1: the 2 x 2 block
- * sum, i.e. the backward of the decoder's nearest upsample; h, w are then y's dims).
- *   up_a = 2: dy_a is the SPACE-TO-DEPTH image of the gradient, [img][h / 2][w / 2][4 c] with pixel (y, x), channel ch at
- *   (y / 2, x / 2), channel ((y & 1) * 2 + (x & 1)) * c + ch -- what one split-f16 launch over the four parity classes of a
- *   stride-2 layer's data gradient writes (round 5; even h, w; ld_a >= 4 c).
- *   g = (dy_a + dy_b) * (y > 0)      dbeta = sum g      dgamma = sum g * zhat
- *   (relu = 2: `y` is not the map but dn_bn_train_apply_mask's byte mask of (y > 0), cast to const float*)
- *   dz = gamma * rstd * (g - mean(g) - zhat * mean(g * zhat))       (means per group)
- * dgamma / dbeta are summed over groups and ADDED when accumulate != 0.
- * sums: workspace of dn_reduce_workspace_bytes(n_groups, images_per_group * h * w, c) bytes. */
-int dn_bn_train_backward(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b,
-                         const float* y, const float* z, const float* mean, const float* var,
-                         const float* gamma, float eps, int relu, int n_groups, int h, int w,
-                         int images_per_group, int c, double* sums, size_t sums_bytes, float* dz,
-                         float* dgamma, float* dbeta, int accumulate, void* stream);
+/* Backward of y = act(bn(z)), in two phases over the same description of the pass:
+ *   g = (dy_a + dy_b) * (y > 0)      dbeta = sum g      dgamma = sum g * zhat                          (phase 1)
+ *   dz = gamma * rstd * (g - mean(g) - zhat * mean(g * zhat))       (means per group)                  (phase 2)
+ * Pointers first, then 32-bit fields: 96 bytes, no padding on any ABI with 8-byte pointers. */
+typedef struct dn_bn_bwd_desc {
+  const float* dy_a;   /* the incoming gradient, row stride ld_a; its resolution and layout: up_a */
+  const float* dy_b;   /* NULL, or a second gradient at y's resolution (row stride ld_b) that is added to dy_a */
+  const void* y;       /* relu = 1: the fp32 map y; relu = 2: dn_bn_train_apply's byte mask of (y > 0) instead (c % 4 == 0);
+                        * relu = 0: not read */
+  const float *z, *mean, *var;
+  const float* gamma;  /* read by phase 2 only */
+  int32_t ld_a;
+  int32_t up_a;        /* 0: dy_a is [img][h][w][.].  1: dy_a lives at twice the resolution and its 2 x 2 block sum is taken (the
+                        * backward of the decoder's nearest upsample).  2: dy_a is the SPACE-TO-DEPTH image of the gradient,
+                        * [img][h / 2][w / 2][4 c] with pixel (y, x), channel ch at (y / 2, x / 2), channel
+                        * ((y & 1) * 2 + (x & 1)) * c + ch -- what one split-f16 launch over the four parity classes of a
+                        * stride-2 layer's data gradient writes (round 5; even h, w; ld_a >= 4 c). */
+  int32_t ld_b, relu;
+  int32_t n_groups, h, w, images_per_group, c;      /* h, w: y's dims; rows per group = images_per_group * h * w */
+  float eps;
+} dn_bn_bwd_desc;
 
-/* Two-phase form of the backward (see dn_bn_train_stats_partial): `_partial` leaves this rank's folded sums of g and
- * g * zhat at the start of `sums` and writes dgamma / dbeta out of THESE rows (they are plain sums over rows: the ranks'
- * shares meet in the gradient all-reduce); the caller all-reduces the n_groups * 2 * c doubles; `_finish` writes dz of this
- * rank's rows with the means taken over `norm_rows` rows per group. */
-int dn_bn_train_backward_partial(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b, const float* y,
-                                 const float* z, const float* mean, const float* var, float eps, int relu, int n_groups,
-                                 int h, int w, int images_per_group, int c, double* sums, size_t sums_bytes, float* dgamma,
-                                 float* dbeta, int accumulate, void* stream);
-int dn_bn_train_backward_finish(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b, const float* y,
-                                const float* z, const float* mean, const float* var, const float* gamma, float eps, int relu,
-                                int n_groups, int h, int w, int images_per_group, int c, const double* sums, long norm_rows,
-                                float* dz, void* stream);
-
-/* dn_bn_train_backward_finish that ALSO writes dz * sp_lift as the SP tensor [n][c / 16][4][h][w] x 16 bytes of the inference conv
- * engine (disconet_hip.h "SP tensor") -- the pre-split operand of the split-f16 data gradient (dn_spconv2d_nhwc): the split is
- * paid once, by the kernel that produces dz, not by the conv's staging.  One group, c % 16 == 0, 16-byte aligned tensors.
- * sp_lift: a power of two that brings max |dz| * sp_lift to ~2^8 -- a value is stored as half(x) + half(x - half(x)): 2^-22
- * relative while 2^-3 <= |x| <= 65504, so the top 19 binades of the tensor keep full precision, smaller elements an absolute floor
- * of 2^-25 / sp_lift, and 256 x of head room remains before the clamp (which sets bit 0 of dn_sp_range_flags: the gradients of
- * that step are invalid).  The caller folds 1 / sp_lift into the data gradient's scale vector (exact). */
-int dn_bn_train_backward_finish_sp(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b, const float* y,
-                                   const float* z, const float* mean, const float* var, const float* gamma, float eps, int relu,
-                                   int n_groups, int h, int w, int images_per_group, int c, const double* sums, long norm_rows,
-                                   float* dz, void* dz_sp, float sp_lift, void* stream);
-
-/* dn_bn_train_backward_finish (dz_sp NULL) / _finish_sp with the BIAS GRADIENT of the conv in front of this BatchNorm fused in
- * (round 6): dbias[ch] = sum over this call's rows of dz[.][ch], written by the same launch that writes dz (a thread adds its
- * own values in fp32, a workgroup its threads in double, fold in a fixed order: deterministic) -- in place of a
- * dn_channel_sum pass that reads dz again.  One group; c / 4 a power of two; bias_ws of dn_bn_bias_workspace_bytes(rows, c).
- * dz may be NULL when dz_sp is given (and in dn_bn_train_backward_finish_sp where the one-group fast form runs): only the SP
- * copy is written (dn_conv_wgrad_sp_z reads that). */
+/* What phase 2 writes.  Every member is optional (0 / NULL = not asked for); at least one of dz, dz_sp is given.  56 bytes. */
+typedef struct dn_bn_bwd_out {
+  float* dz;           /* the fp32 dz.  NULL (needs dz_sp and DN_BN_FORM_DZ_NULL below): only the SP copy is written -- for a layer
+                        * whose weight gradient (dn_conv_wgrad_sp_z), data gradient and bias gradient all read dz through this
+                        * launch's other outputs; saves a quarter of the launch's bytes */
+  void* dz_sp;         /* dz * sp_lift ALSO as the SP tensor [n][c / 16][4][h][w] x 16 bytes of the inference conv engine
+                        * (disconet_hip.h "SP tensor") -- the pre-split operand of the split-f16 data gradient (dn_spconv2d_nhwc)
+                        * and of dn_conv_wgrad_sp_z: the split is paid once, by the kernel that produces dz, not by the convs'
+                        * staging.  One group, c % 16 == 0, 16-byte aligned tensors. */
+  float* dbias;        /* the BIAS GRADIENT of the conv in front of this BatchNorm (round 6): dbias[ch] = sum over this call's
+                        * rows of dz[.][ch], written by the same launch that writes dz (a thread adds its own values in fp32, a
+                        * workgroup its threads in double, fold in a fixed order: deterministic) -- in place of a dn_channel_sum
+                        * pass that reads dz again.  Needs DN_BN_FORM_BIAS below, aligned tensors and bias_ws. */
+  double* bias_ws;     /* workspace of the bias gradient, dn_bn_bias_workspace_bytes(rows, c) bytes: [c] doubles for the folded
+                        * sums, then [blocks][c] partials.  Never the reduction's `sums` (the same launch reads those). */
+  int* n_blocks;       /* non-NULL (dbias must then be NULL): the bias gradient with its FOLD DEFERRED -- the partials stay in
+                        * bias_ws, *n_blocks receives their count, and a dn_fold_job of dn_channel_sum_fold_multi folds them
+                        * later (see there); the same bits as dbias */
+  uint64_t bias_ws_bytes;
+  float sp_lift;       /* with dz_sp: a power of two that brings max |dz| * sp_lift to ~2^8 -- a value is stored as
+                        * half(x) + half(x - half(x)): 2^-22 relative while 2^-3 <= |x| <= 65504, so the top 19 binades of the
+                        * tensor keep full precision, smaller elements an absolute floor of 2^-25 / sp_lift, and 256 x of head
+                        * room remains before the clamp (which sets bit 0 of dn_sp_range_flags: the gradients of that step are
+                        * invalid).  The caller folds 1 / sp_lift into the data gradient's scale vector (exact). */
+  int32_t reserved;
+} dn_bn_bwd_out;
 size_t dn_bn_bias_workspace_bytes(long rows, int c);
-int dn_bn_train_backward_finish_bias(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b, const float* y,
-                                     const float* z, const float* mean, const float* var, const float* gamma, float eps,
-                                     int relu, int h, int w, int images, int c, const double* sums, long norm_rows, float* dz,
-                                     void* dz_sp /* may be NULL */, float sp_lift, float* dbias, double* bias_ws,
-                                     size_t bias_ws_bytes, void* stream);
+
+/* The two phases, for a BatchNorm batch that is spread over several ranks (see dn_bn_train_stats_partial): `_partial` leaves this
+ * rank's folded sums of g and g * zhat at the start of `sums` (workspace of dn_reduce_workspace_bytes(n_groups,
+ * images_per_group * h * w, c) bytes) and writes dgamma / dbeta out of THESE rows (plain sums over rows and groups, ADDED when
+ * accumulate != 0: the ranks' shares meet in the gradient all-reduce); the caller all-reduces the n_groups * 2 * c doubles;
+ * `_finish` writes `out` for this rank's rows with the means taken over `norm_rows` rows per group.
+ * dn_bn_train_backward is the two phases back to back with norm_rows = images_per_group * h * w, for every form of `out`. */
+int dn_bn_train_backward_partial(const dn_bn_bwd_desc* d, double* sums, size_t sums_bytes, float* dgamma, float* dbeta,
+                                 int accumulate, void* stream);
+int dn_bn_train_backward_finish(const dn_bn_bwd_desc* d, const double* sums, long norm_rows, const dn_bn_bwd_out* out,
+                                void* stream);
+int dn_bn_train_backward(const dn_bn_bwd_desc* d, double* sums, size_t sums_bytes, const dn_bn_bwd_out* out, float* dgamma,
+                         float* dbeta, int accumulate, void* stream);
 
 /* out[c] (+)= sum over rows of x[row][c] (bias gradients); sums: dn_reduce_workspace_bytes(1, rows, c) bytes */
 int dn_channel_sum(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, float* out,
@@ -202,8 +199,8 @@ int dn_channel_sum(const float* x, long rows, int c, int ld, double* sums, size_
 
 /* The same sums with their FOLDS DEFERRED (round 6).  A bias gradient is a leaf of the backward: nothing reads it before the
  * optimizer step, so the launch that leaves the per-workgroup partials need not be followed by a fold of its own (26 launches of
- * ~5 us per training step on a stream with nothing to run beside them).  dn_bn_train_backward_finish_bias_deferred /
- * dn_channel_sum_partial are dn_bn_train_backward_finish_bias / dn_channel_sum without the fold: the partials stay in the
+ * ~5 us per training step on a stream with nothing to run beside them).  dn_bn_bwd_out.n_blocks / dn_channel_sum_partial are
+ * dn_bn_bwd_out.dbias / dn_channel_sum without the fold: the partials stay in the
  * workspace ([c] doubles for the folded sums, then [*n_blocks][c] partials), which must stay untouched until
  * dn_channel_sum_fold_multi has folded it: one launch for every job (32 per launch), each in dn_channel_sum's fixed order --
  * out[ch] = (accumulate ? out[ch] : 0) + (float) sum, the same bits as the undeferred calls. */
@@ -213,23 +210,17 @@ typedef struct dn_fold_job {
   float* out;
   int32_t n_blocks, c, accumulate, reserved;
 } dn_fold_job;
-int dn_bn_train_backward_finish_bias_deferred(const float* dy_a, int ld_a, int up_a, const float* dy_b, int ld_b, const float* y,
-                                              const float* z, const float* mean, const float* var, const float* gamma, float eps,
-                                              int relu, int h, int w, int images, int c, const double* sums, long norm_rows,
-                                              float* dz, void* dz_sp /* may be NULL */, float sp_lift, double* bias_ws,
-                                              size_t bias_ws_bytes, int* n_blocks, void* stream);
 int dn_channel_sum_partial(const float* x, long rows, int c, int ld, double* sums, size_t sums_bytes, int* n_blocks, void* stream);
 int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, void* stream);
 
-/* Does the fused BatchNorm form `form` take this shape?  1 or 0: exactly the shape condition its entry points enforce (they ask
- * this function), so a caller can pick the plain entry points instead of meeting an error.  The tensors' alignment (16 bytes,
- * row strides % 4) is not part of it: the call still checks that.
- *   DN_BN_FORM_SP_APPLY  dn_bn_train_apply_mask_sp (n_groups = 1): c % 16 == 0, c / 4 a power of two, c <= 512,
+/* Does the fused BatchNorm form `form` take this shape?  1 or 0: exactly the shape condition the entry points enforce on the
+ * member that selects the form (they ask this function), so a caller can leave that member NULL instead of meeting an error.
+ * The tensors' alignment (16 bytes, row strides % 4) is not part of it: the call still checks that.
+ *   DN_BN_FORM_SP_APPLY  dn_bn_train_apply's y_sp: one group, c % 16 == 0, c / 4 a power of two, c <= 512,
  *                        rows_per_group * c / 4 < 2^31.  DN_BN_LEGACY=1 does not change it (the SP apply has no general twin).
- *   DN_BN_FORM_BIAS      dn_bn_train_backward_finish_bias(_deferred): one group, c % 4 == 0, c / 4 a power of two, c <= 512,
+ *   DN_BN_FORM_BIAS      dn_bn_bwd_out's dbias / n_blocks: one group, c % 4 == 0, c / 4 a power of two, c <= 512,
  *                        rows_per_group * c / 4 < 2^31, DN_BN_LEGACY unset (the one-group fast kernels).
- *   DN_BN_FORM_DZ_NULL   dz = NULL in _finish_sp / _finish_bias(_deferred) (only the SP copy of dz written): DN_BN_FORM_BIAS
- *                        and c % 16 == 0.
+ *   DN_BN_FORM_DZ_NULL   dn_bn_bwd_out's dz = NULL (only the SP copy of dz written): DN_BN_FORM_BIAS and c % 16 == 0.
  * Any other n_groups, a non-positive size or an unknown form: 0. */
 enum { DN_BN_FORM_SP_APPLY = 0, DN_BN_FORM_BIAS = 1, DN_BN_FORM_DZ_NULL = 2 };
 int dn_bn_train_form_supported(int form, int n_groups, long rows_per_group, int c);

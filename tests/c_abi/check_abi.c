@@ -22,7 +22,7 @@
 static float frand(unsigned* s) { *s = *s * 1664525u + 1013904223u; return ((*s >> 8) / 8388608.0f) - 1.0f; }
 
 static int errors_only(void) {
-  CHECK(dn_version() >= 130, "version");
+  CHECK(dn_version() >= 137, "version");
   CHECK(dn_build_id() != NULL && strlen(dn_build_id()) == 16, "build id: %s", dn_build_id() ? dn_build_id() : "(null)");
   dn_conv_desc d;
   memset(&d, 0, sizeof d);
@@ -51,24 +51,48 @@ static int errors_only(void) {
   d.stride = 1; d.c0 = 32; d.ld0 = 32;
   CHECK(dn_adam_step(NULL, NULL, NULL, NULL, 10, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1, NULL) == DN_ERR_ARG,
         "adam null");
-  CHECK(dn_bn_train_stats(NULL, 1, 10, 600, 600, NULL, 0, NULL, NULL, NULL) == DN_ERR_ARG, "bn null");
+  CHECK(dn_bn_train_stats(NULL, 1, 10, 600, 600, NULL, 0, NULL, NULL, NULL, NULL, 0.f, NULL) == DN_ERR_ARG, "bn null");
   /* round 5: two-phase BatchNorm reductions (agent-parallel training) and the K-slice query */
   CHECK(dn_bn_train_stats_partial(NULL, 1, 10, 8, 8, NULL, 0, NULL) == DN_ERR_ARG, "bn stats partial null");
   CHECK(dn_bn_train_stats_finish(NULL, 1, 10, 8, NULL, NULL, NULL) == DN_ERR_ARG, "bn stats finish null");
-  CHECK(dn_bn_train_stats_running(NULL, 16, 16, 16, NULL, 0, NULL, NULL, NULL, NULL, 0.1f, NULL) == DN_ERR_ARG, "bn stats (+ running) null");
-  CHECK(dn_bn_bias_workspace_bytes(0, 32) == 0 && dn_bn_bias_workspace_bytes(1024, 32) == 8u * 32u * (1 + 32), "bn bias workspace");
-  CHECK(dn_bn_train_backward_finish_bias(NULL, 8, 0, NULL, 0, NULL, NULL, NULL, NULL, NULL, 1e-5f, 0, 4, 4, 1, 16, NULL, 16, NULL, NULL,
-                                         1.f, NULL, NULL, 0, NULL) == DN_ERR_ARG, "bn backward finish (+ bias) null");
-  CHECK(dn_bn_train_apply_mask_sp(NULL, NULL, NULL, NULL, NULL, 1e-5f, 16, 16, 16, 16, NULL, NULL, NULL, NULL) == DN_ERR_ARG,
-        "bn apply (mask + SP) null");
-  CHECK(dn_bn_train_apply_mask_sp((const float*)16, (const float*)16, (const float*)16, (const float*)16, (const float*)16, 1e-5f,
-                                  16, 16, 24, 24, (float*)16, (unsigned char*)16, (void*)16, NULL) == DN_ERR_ARG,
-        "bn apply (mask + SP): c %% 16");
-  CHECK(dn_bn_train_stats_finish((const double*)16, 1, 0, 8, (float*)16, (float*)16, NULL) == DN_ERR_ARG, "bn stats finish: zero rows");
-  CHECK(dn_bn_train_backward_partial(NULL, 8, 0, NULL, 0, NULL, NULL, NULL, NULL, 1e-5f, 0, 1, 4, 4, 1, 8, NULL, 0, NULL, NULL, 0,
-                                     NULL) == DN_ERR_ARG, "bn bwd partial null");
-  CHECK(dn_bn_train_backward_finish(NULL, 8, 0, NULL, 0, NULL, NULL, NULL, NULL, NULL, 1e-5f, 0, 1, 4, 4, 1, 8, NULL, 16, NULL,
-                                    NULL) == DN_ERR_ARG, "bn bwd finish null");
+  {
+    /* the optional outputs of the BatchNorm passes: each condition sits on the pointer that selects the form */
+    float* const p = (float*)16;      /* never dereferenced: every call below is refused on the host */
+    CHECK(dn_bn_train_stats(NULL, 1, 16, 16, 16, NULL, 0, NULL, NULL, NULL, NULL, 0.1f, NULL) == DN_ERR_ARG, "bn stats (+ running) null");
+    CHECK(dn_bn_train_stats(p, 1, 16, 16, 16, (double*)p, 1 << 20, p, p, p, NULL, 0.1f, NULL) == DN_ERR_ARG && strstr(dn_last_error(), "running"),
+          "bn stats: running_mean without running_var: %s", dn_last_error());
+    CHECK(dn_bn_bias_workspace_bytes(0, 32) == 0 && dn_bn_bias_workspace_bytes(1024, 32) == 8u * 32u * (1 + 32), "bn bias workspace");
+    CHECK(dn_bn_train_apply(NULL, NULL, NULL, NULL, NULL, 1e-5f, 1, 1, 16, 16, 16, NULL, NULL, NULL, 16, NULL) == DN_ERR_ARG,
+          "bn apply (mask + SP) null");
+    CHECK(dn_bn_train_apply(p, p, p, p, p, 1e-5f, 1, 1, 16, 24, 24, p, (unsigned char*)p, p, 16, NULL) == DN_ERR_ARG &&
+              strstr(dn_last_error(), "c % 16"), "bn apply (mask + SP): c %% 16: %s", dn_last_error());
+    CHECK(dn_bn_train_apply(p, p, p, p, p, 1e-5f, 1, 1, 16, 16, 16, p, NULL, p, 16, NULL) == DN_ERR_ARG, "bn apply: y_sp without relu_mask");
+    CHECK(dn_bn_train_stats_finish((const double*)16, 1, 0, 8, (float*)16, (float*)16, NULL) == DN_ERR_ARG, "bn stats finish: zero rows");
+    dn_bn_bwd_desc b;
+    dn_bn_bwd_out o;
+    memset(&b, 0, sizeof b);
+    memset(&o, 0, sizeof o);
+    b.ld_a = 8; b.n_groups = 1; b.h = 4; b.w = 4; b.images_per_group = 1; b.c = 8; b.eps = 1e-5f;
+    CHECK(dn_bn_train_backward_partial(NULL, NULL, 0, NULL, NULL, 0, NULL) == DN_ERR_ARG, "bn bwd partial: no descriptor");
+    CHECK(dn_bn_train_backward_partial(&b, NULL, 0, NULL, NULL, 0, NULL) == DN_ERR_ARG, "bn bwd partial null");
+    CHECK(dn_bn_train_backward_finish(&b, NULL, 16, &o, NULL) == DN_ERR_ARG, "bn bwd finish null");
+    CHECK(dn_bn_train_backward(&b, NULL, 0, &o, NULL, NULL, 0, NULL) == DN_ERR_ARG, "bn bwd null");
+    b.dy_a = b.z = b.mean = b.var = b.gamma = p;
+    CHECK(dn_bn_train_backward_finish(&b, (const double*)p, 16, NULL, NULL) == DN_ERR_ARG, "bn bwd finish: no outputs");
+    CHECK(dn_bn_train_backward_finish(&b, (const double*)p, 16, &o, NULL) == DN_ERR_ARG, "bn bwd finish: neither dz nor dz_sp");
+    b.ld_a = 16; b.c = 16;
+    o.dz = p; o.dbias = p;      /* the fused bias gradient without its workspace */
+    CHECK(dn_bn_train_backward_finish(&b, (const double*)p, 16, &o, NULL) == DN_ERR_ARG && strstr(dn_last_error(), "bias workspace"),
+          "bn backward finish (+ bias) null: %s", dn_last_error());
+    int blocks = 0;
+    o.bias_ws = (double*)p; o.bias_ws_bytes = 1 << 20; o.n_blocks = &blocks;
+    CHECK(dn_bn_train_backward_finish(&b, (const double*)p, 16, &o, NULL) == DN_ERR_ARG && strstr(dn_last_error(), "not both"),
+          "bn backward finish: dbias and n_blocks: %s", dn_last_error());
+    o.n_blocks = NULL;
+    b.n_groups = 2;             /* the bias gradient is a one-group form: the removed entry points could not even say this */
+    CHECK(dn_bn_train_backward_finish(&b, (const double*)p, 16, &o, NULL) == DN_ERR_ARG && strstr(dn_last_error(), "one group"),
+          "bn backward finish (+ bias), two groups: %s", dn_last_error());
+  }
   memset(&d, 0, sizeof d);
   d.n_images = 4; d.h_in = 32; d.w_in = 32; d.c0 = 256; d.c_out = 256; d.ksize = 3; d.stride = 1; d.math = 2;
   CHECK(dn_spconv_ks_supported(&d, 1) == 1 && dn_spconv_ks_supported(&d, 4) == 1 && dn_spconv_ks_supported(&d, 3) == 0, "ks supported");

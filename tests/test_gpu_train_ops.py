@@ -355,7 +355,7 @@ def test_bn_backward_of_upsampled_gradient_and_running_stats():
 @pytest.mark.parametrize("shape,up_a,lift", [((3, 16, 32, 64), False, 2.0 ** 9), ((2, 8, 8, 512), False, 2.0 ** 12),
                                              ((2, 32, 32, 32), True, 2.0 ** 14)])
 def test_bn_backward_sp_copy_is_the_split_of_the_lifted_dz(shape, up_a, lift):
-    """dn_bn_train_backward_finish_sp: dz itself is bit for bit the plain call's, and the SP copy holds exactly the f16 hi / lo
+    """dn_bn_bwd_out.dz_sp: dz itself is bit for bit the plain call's, and the SP copy holds exactly the f16 hi / lo
     split of dz * lift (what dn_sp_from_nhwc makes of it) -- pieces of two threads' values, ragged wavefronts, the x2 gradient."""
     from disconet_amd import ops, train_ops
     n, h, w, c = shape
@@ -380,7 +380,7 @@ def test_bn_backward_sp_copy_is_the_split_of_the_lifted_dz(shape, up_a, lift):
 
 @pytest.mark.parametrize("shape,up_a,sp", [((3, 16, 32, 64), False, False), ((2, 9, 7, 36), False, False), ((2, 32, 32, 32), True, True)])
 def test_bn_relu_byte_mask_replaces_y_in_the_backward_bit_for_bit(shape, up_a, sp):
-    """dn_bn_train_apply_mask: y is the plain call's, the mask is (y > 0) packed four channels to a byte; the backward reading
+    """dn_bn_train_apply with relu_mask: y is the plain call's, the mask is (y > 0) packed four channels to a byte; the backward reading
     the mask (relu = 2) equals the backward reading y bit for bit -- dz, the SP copy, dgamma, dbeta; ragged sizes included."""
     from disconet_amd import ops, train_ops
     n, h, w, c = shape
@@ -837,7 +837,7 @@ def test_adam_matches_torch_optim():
 
 @pytest.mark.parametrize("shape", [(3, 16, 24, 64), (2, 32, 32, 256), (1, 64, 64, 32), (2, 8, 8, 512)])
 def test_bn_apply_writes_y_a_second_time_as_an_sp_tensor(shape):
-    """Round 6 (the training forward on the inference engine): dn_bn_train_apply_mask_sp = dn_bn_train_apply_mask bit for bit
+    """Round 6 (the training forward on the inference engine): dn_bn_train_apply with y_sp = the call with relu_mask alone bit for bit
     (y, the byte mask) + y as the split-planar f16 hi / lo tensor -- the bits dn_sp_from_nhwc makes of that y."""
     from disconet_amd import ops, train_ops
     g = torch.Generator().manual_seed(17)

@@ -81,6 +81,9 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.MlpTailParams) == 10 * ctypes.sizeof(ctypes.c_void_p)
     assert ctypes.sizeof(_lib.Post1x1Desc) == 6 * 4
     assert ctypes.sizeof(_lib.FuseMlpParams) == 9 * ctypes.sizeof(ctypes.c_void_p)
+    assert ctypes.sizeof(_lib.BnBwdDesc) == 7 * ctypes.sizeof(ctypes.c_void_p) + 10 * 4      # the library static_asserts the same
+    assert ctypes.sizeof(_lib.BnBwdOut) == 5 * ctypes.sizeof(ctypes.c_void_p) + 8 + 4 + 4
+    assert _lib.BnBwdDesc.eps.offset == 7 * ctypes.sizeof(ctypes.c_void_p) + 9 * 4 and _lib.BnBwdOut.sp_lift.offset == 48
 
 
 def test_argument_errors_are_reported_not_thrown():

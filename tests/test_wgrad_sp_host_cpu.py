@@ -61,7 +61,10 @@ def test_bn_backward_refuses_bad_gate_and_gradient_modes():
     p = ctypes.c_void_p(16)
 
     def partial(relu, up_a, h, w, c, ld_a):
-        return lib.dn_bn_train_backward_partial(p, ld_a, up_a, None, 0, p, p, p, p, 1e-5, relu, 1, h, w, 2, c, p, 1 << 30, p, p, 0, None)
+        d = _lib.BnBwdDesc()
+        d.dy_a = d.y = d.z = d.mean = d.var = 16
+        d.ld_a, d.up_a, d.relu, d.n_groups, d.h, d.w, d.images_per_group, d.c, d.eps = ld_a, up_a, relu, 1, h, w, 2, c, 1e-5
+        return lib.dn_bn_train_backward_partial(d, p, 1 << 30, p, p, 0, None)
     assert partial(3, 0, 8, 8, 32, 32) != 0 and b"relu" in lib.dn_last_error()
     assert partial(2, 0, 8, 8, 6, 6) != 0 and b"c % 4" in lib.dn_last_error()
     assert partial(1, 3, 8, 8, 32, 32) != 0 and b"up_a" in lib.dn_last_error()
