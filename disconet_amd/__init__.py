@@ -6,8 +6,11 @@ include/disconet_hip.h).  See DESIGN.md.
 """
 from .config import Config
 from .model import DiscoNet
+from . import targets
 from .seg import SegDiscoNet, SegModule
 from .teacher import TeacherNet
+from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
-__all__ = ["Config", "DiscoNet", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule"]
+__all__ = ["Config", "DiscoNet", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "targets",
+           "assign_targets"]

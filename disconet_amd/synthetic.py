@@ -163,3 +163,118 @@ def make_gt_boxes(n_images, seed=0, max_boxes=64, extent=32.0, min_boxes=None):
         boxes[i, :c, 3] = rng.uniform(3.5, 5.5, c)
         boxes[i, :c, 4], boxes[i, :c, 5] = np.sin(yaw), np.cos(yaw)
     return torch.from_numpy(boxes), torch.from_numpy(count)
+
+
+# ---------------------------------------------------------------------------
+# scenes whose boxes and occupancy agree: world boxes -> per-agent ground truth and point clouds -> occupancy
+# ---------------------------------------------------------------------------
+BOX_SCENE_PITCH = 8.0            # grid pitch of the world boxes (m); centres are jittered by at most +-1 m
+BOX_Z = (-2.0, -0.5)             # floor and roof of every box (m), inside the extents' (-3, 2)
+
+
+def _box_points(box, step=0.1):
+    """Points on the four sides (four heights) and on the roof of one world box (x, y, w, h, sin, cos): [P, 3] float64.
+    The first point is the roof's centre."""
+    x, y, w, h, s, c = (float(v) for v in box)
+    us = np.arange(-w / 2.0, w / 2.0 + 1e-9, step)
+    vs = np.arange(-h / 2.0, h / 2.0 + 1e-9, step)
+    zs = np.linspace(BOX_Z[0] + 0.1, BOX_Z[1] - 0.1, 4)
+    side = np.concatenate([np.stack([us, np.full_like(us, -h / 2.0)], 1), np.stack([us, np.full_like(us, h / 2.0)], 1),
+                           np.stack([np.full_like(vs, -w / 2.0), vs], 1), np.stack([np.full_like(vs, w / 2.0), vs], 1)], 0)
+    side = np.concatenate([np.concatenate([side, np.full((len(side), 1), z)], 1) for z in zs], 0)
+    ru, rv = np.meshgrid(us[1:-1:2], vs[1:-1:2], indexing="ij")
+    roof = np.stack([ru.ravel(), rv.ravel(), np.full(ru.size, BOX_Z[1])], 1)
+    loc = np.concatenate([[[0.0, 0.0, BOX_Z[1]]], roof, side], 0)
+    out = loc.copy()
+    out[:, 0] = loc[:, 0] * c - loc[:, 1] * s + x
+    out[:, 1] = loc[:, 0] * s + loc[:, 1] * c + y
+    return out
+
+
+def boxes_in_agent_frame(world_boxes, agent):
+    """World boxes [K, 6] float64 under agent_pose(agent)^-1: centre and heading in that agent's frame."""
+    T = np.linalg.inv(agent_pose(agent))
+    b = np.asarray(world_boxes, dtype=np.float64).reshape(-1, 6)
+    out = b.copy()
+    out[:, 0] = T[0, 0] * b[:, 0] + T[0, 1] * b[:, 1] + T[0, 3]
+    out[:, 1] = T[1, 0] * b[:, 0] + T[1, 1] * b[:, 1] + T[1, 3]
+    out[:, 4] = T[1, 0] * b[:, 5] + T[1, 1] * b[:, 4]          # the heading vector (cos, sin) turned by -yaw_agent
+    out[:, 5] = T[0, 0] * b[:, 5] + T[0, 1] * b[:, 4]
+    return out
+
+
+def host_occupancy(pts, voxel_size, extents, dims):
+    """numpy form of the voxelizer (ops.voxelize_occupy; upstream voxelize_occupy): strict extent filter on the float32
+    coordinates, floor(pts / voxel) in float64, shifted by floor(extent_lo / voxel) -> dense [X, Y, Z] float32."""
+    pts = np.asarray(pts, dtype=np.float32)
+    ext = np.asarray(extents, dtype=np.float64)
+    vs = np.asarray(voxel_size, dtype=np.float64)
+    keep = np.ones(len(pts), dtype=bool)
+    for d in range(3):
+        keep &= (ext[d, 0] < pts[:, d]) & (pts[:, d] < ext[d, 1])
+    idx = (np.floor(pts[keep, :3] / vs) - np.floor(ext[:, 0] / vs)).astype(np.int64)
+    dense = np.zeros(tuple(int(v) for v in dims), dtype=np.float32)
+    dense[idx[:, 0], idx[:, 1], idx[:, 2]] = 1.0
+    return dense
+
+
+def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_per_scene=24, clutter=200, device=None):
+    """Seeded scenes in which the ground truth and the occupancy describe the same boxes.  Per scene up to
+    `boxes_per_scene` car-sized world boxes (w ~ U(1.6, 2.4), l ~ U(3.5, 5.5), any yaw) sit on a grid of pitch 8 m over
+    agent 0's extents, centres jittered by at most 1 m: two centres are at least 6 m apart, the boxes' circumscribed
+    circles (radius <= 3 m) never meet.  Agent i sits at agent_pose(i); its ground truth is the world boxes in its frame
+    whose centre is strictly inside the extents, its cloud the points on the boxes' sides and roofs plus `clutter` seeded
+    points, both in its frame; the cloud goes through the voxelizer (ops.voxelize_occupy on `device`; device = None: the
+    numpy form host_occupancy, tensors stay on the host).  Images are agent-major (image = agent * B + b).  Returns
+    {"bev_seq" [A*B, 1, H, W, Z], "trans_matrices", "num_agent" (as make_scene_batch), "gt_boxes" [A*B, boxes_per_scene, 6]
+    float32, "gt_count" [A*B] int32 (rows >= count zero), "points": per image [P, 4] float32, "world_boxes": per scene
+    [K, 6] float64}."""
+    from .config import Config
+    cfg = Config(map_hw=map_hw)
+    ext, vs, dims = cfg.area_extents, cfg.voxel_size, cfg.map_dims
+    half = float(ext[0][1])
+    cells = max(1, int(round(2 * half / BOX_SCENE_PITCH)))
+    g = int(boxes_per_scene)
+    n_img = num_agent * batch_size
+    gt_boxes = np.zeros((n_img, g, 6), dtype=np.float32)
+    gt_count = np.zeros(n_img, dtype=np.int32)
+    points, world = [None] * n_img, []
+    for b in range(batch_size):
+        rng = np.random.RandomState((int(seed) * 9973 + b) % (2 ** 31))
+        k = min(g, cells * cells)
+        cell = rng.permutation(cells * cells)[:k]
+        wb = np.zeros((k, 6), dtype=np.float64)
+        wb[:, 0] = -half + (cell // cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+        wb[:, 1] = -half + (cell % cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+        wb[:, 2] = rng.uniform(1.6, 2.4, k)
+        wb[:, 3] = rng.uniform(3.5, 5.5, k)
+        yaw = rng.uniform(-math.pi, math.pi, k)
+        wb[:, 4], wb[:, 5] = np.sin(yaw), np.cos(yaw)
+        world.append(wb)
+        cloud = np.concatenate([_box_points(row) for row in wb], 0) if k else np.zeros((0, 3))
+        for a in range(num_agent):
+            img = a * batch_size + b
+            mine = boxes_in_agent_frame(wb, a)
+            kept = mine[(np.abs(mine[:, 0]) < half) & (np.abs(mine[:, 1]) < half)]
+            gt_boxes[img, :len(kept)] = kept.astype(np.float32)
+            gt_count[img] = len(kept)
+            T = np.linalg.inv(agent_pose(a))
+            pts = cloud.copy()
+            pts[:, 0] = T[0, 0] * cloud[:, 0] + T[0, 1] * cloud[:, 1] + T[0, 3]
+            pts[:, 1] = T[1, 0] * cloud[:, 0] + T[1, 1] * cloud[:, 1] + T[1, 3]
+            noise = rng.uniform([-half, -half, ext[2][0]], [half, half, ext[2][1]], size=(int(clutter), 3))
+            pts = np.concatenate([pts, noise], 0)
+            points[img] = np.concatenate([pts, rng.uniform(0, 1, (len(pts), 1))], 1).astype(np.float32)
+    if device is None:
+        bevs = torch.from_numpy(np.stack([host_occupancy(p, vs, ext, dims) for p in points], 0))[:, None]
+    else:
+        from . import ops
+        bevs = torch.stack([ops.voxelize_occupy(torch.from_numpy(p).to(device), vs, ext, dims) for p in points], 0)[:, None]
+    trans = make_trans_matrices(batch_size, num_agent)
+    na = torch.tensor([[num_agent] * num_agent for _ in range(batch_size)], dtype=torch.int64)
+    out = {"bev_seq": bevs, "trans_matrices": trans, "num_agent": na, "gt_boxes": torch.from_numpy(gt_boxes),
+           "gt_count": torch.from_numpy(gt_count)}
+    if device is not None:
+        out = {k: v.to(device) for k, v in out.items()}
+    out["points"], out["world_boxes"] = points, world
+    return out

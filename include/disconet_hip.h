@@ -518,6 +518,39 @@ int dn_ap_match(const float* boxes, const float* scores, const int32_t* count, c
                 void* stream);
 int dn_ap_reset(long long* state, int n_agents, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Training targets from ground-truth boxes (disconet_amd/csrc/assign.hip): the anchor assignment that the reference runs
+ * on the CPU when it creates the dataset (upstream:tools/det/create_data_det.py; the SECOND / FaF rule, thresholds as
+ * parameters), here per training step on the GPU.  Graph-capturable beside the training step: kernel launches only, no
+ * host synchronisation, no allocation; the launch sequence depends on the shapes only.  Host reference:
+ * targets.host_assign_targets.
+ *   anchors [apl][6] = (x, y, w, h, sin, cos) as dn_decode_boxes; gt_boxes [n][g][6], gt_count [n]: padded ground truth,
+ *   the arrays dn_ap_match takes.  1 <= n <= 65535, 1 <= apl < 2^31 - 64, 1 <= g <= 1024, 0 < neg_thr <= pos_thr <= 1.
+ *   Counts are clamped to [0, g]; rows behind the count are never read.
+ *   Per (image, anchor):
+ *   - best_iou (fp64): the largest IoU over the rows j < count that pass the strict circumscribed-circle test, best: the
+ *     lowest j that attains it (IoU as dn_detect's NMS and dn_ap_match: inter / union, 0 when union <= 0, fp64 geometry,
+ *     the anchor's polygon clipped by the box's); 0 and -1 when no IoU is above 0;
+ *   - threshold match: positive with target row `best` when best_iou >= pos_thr; negative when best_iou < neg_thr;
+ *     don't care otherwise;
+ *   - force match (force_match != 0): every row j makes the anchor with the largest IoU against j over all anchors of the
+ *     image (the lowest anchor index among equals) positive with target row j, provided that IoU is above 0; this
+ *     overrides the anchor's threshold match; of several rows that force one anchor the lowest j wins;
+ *   - labels [n][apl][2]: (0, 1) positive, (1, 0) negative, (0, 0) don't care; reg_mask [n][apl]: 1 positive, else 0;
+ *     matched_gt [n][apl] (may be NULL): the target row, -1 when not positive; best_iou [n][apl] (may be NULL);
+ *   - reg_targets [n][apl][6]: for a positive anchor (xa, ya, wa, ha, sa, ca) with target box (x, y, w, h, sn, cs) and
+ *     (s, c) = (sn, cs) / max(hypot(sn, cs), 1e-12) the code dn_decode_boxes inverts,
+ *       ((x - xa) / wa, (y - ya) / ha, log(w / wa), log(h / ha), s ca - c sa, c ca + s sa),
+ *     computed in fp64 from the fp32 inputs and rounded once to fp32; all zero when not positive.
+ *   Every output element is written on every call.  workspace: dn_assign_targets_workspace_bytes(n, apl, g) bytes (0 for
+ *   arguments dn_assign_targets refuses).  Only integer atomics: two runs write the same bytes.
+ * ------------------------------------------------------------------------ */
+size_t dn_assign_targets_workspace_bytes(int n_images, long anchors_per_image, int g);
+int dn_assign_targets(const float* anchors, const float* gt_boxes, const int32_t* gt_count, int n_images,
+                      long anchors_per_image, int g, double pos_thr, double neg_thr, int force_match, float* labels,
+                      float* reg_targets, float* reg_mask, int32_t* matched_gt, double* best_iou, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,13 +4,16 @@ detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothi
 mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
 
     python tools/det/eval_codet.py --com disco [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
-        [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self]
+        [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
     have nothing to do with the synthetic occupancy (there is no V2X-Sim data here): the figure checks the plumbing, not
     the detector.
 --gt self: every frame's detections are their own ground truth.  At the default --iou_thr 0.01 every kept box has IoU 1
     with itself and at most 0.01 with every other, so both figures are 1.0000: a smoke check that needs no labels.
+--gt scene: frame f is synthetic.make_box_scene_batch(seed=f) -- occupancy that shows the scene's own boxes -- scored
+    against those boxes: after `train_codet.py --targets boxes --logpath L`, `--gt scene --resume L/epoch_N.pth` prints an
+    mAP that belongs to the detector.
 """
 import os
 import sys
@@ -22,19 +25,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
 from disconet_amd import Config, DiscoNet, postprocess  # noqa: E402
-from disconet_amd.synthetic import make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
+from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
 
 
-def main(argv=None):
+def build_eval_parser():
     ap = build_parser()
     ap.add_argument("--pre_nms_top_k", type=int, default=300)
     ap.add_argument("--iou_thr", type=float, default=0.01)
     ap.add_argument("--score_thr", type=float, default=None)
-    ap.add_argument("--gt", choices=("synthetic", "self"), default="synthetic")
-    args = ap.parse_args(argv)
+    ap.add_argument("--gt", choices=("synthetic", "self", "scene"), default="synthetic")
+    return ap
+
+
+def main(argv=None):
+    args = build_eval_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
     if args.com != "disco":
@@ -57,19 +64,27 @@ def main(argv=None):
     metric = postprocess.MeanAP(args.batch, capacity=max(1, args.frames * n_images * args.pre_nms_top_k))
 
     for frame in range(args.frames):
-        bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
+        if args.gt == "scene":
+            scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=frame, boxes_per_scene=GT_MAX_BOXES,
+                                         device="cuda")
+            bevs, trans, na = scene["bev_seq"], scene["trans_matrices"], scene["num_agent"]
+        else:
+            bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
         with torch.no_grad():
             out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
         det = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors, pre_nms_top_k=args.pre_nms_top_k,
                                  iou_thr=args.iou_thr, score_thr=args.score_thr)
         if args.gt == "self":
             gt_boxes, gt_count = det["boxes"], det["count"]
+        elif args.gt == "scene":
+            gt_boxes, gt_count = scene["gt_boxes"], scene["gt_count"]
         else:
             gt_boxes, gt_count = (t.cuda() for t in make_gt_boxes(n_images, seed=frame, max_boxes=GT_MAX_BOXES))
         metric.update(det, gt_boxes, gt_count)
 
     res = metric.compute()
     what = ("ground truth = the detections themselves" if args.gt == "self" else
+            "ground truth = the boxes of the scenes%s" % ("" if args.resume else ", random weights") if args.gt == "scene" else
             "synthetic ground truth%s: plumbing, not accuracy" % ("" if args.resume else " and random weights"))
     print("%d frames x %d images (%s)" % (args.frames, n_images, what))
     for a, row in enumerate(res["per_agent"]):

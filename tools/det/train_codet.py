@@ -9,7 +9,14 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
 
     python tools/det/train_codet.py --com disco [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
-        [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0]
+        [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
+        [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4]
+
+--targets synthetic (default): random occupancy and synthetic.make_train_targets (Bernoulli noise per anchor).
+--targets boxes: synthetic.make_box_scene_batch -- scenes whose occupancy shows their ground-truth boxes -- with
+    targets.assign_targets (dn_assign_targets, on the GPU) called every step: the anchor assignment the reference runs
+    when it creates the dataset.  The steps cycle through the scene seeds 0 .. --scenes - 1, the frames that
+    `eval_codet.py --gt scene --resume <logpath>/epoch_N.pth` then scores against their own boxes.
 
 Data-parallel: one process per GPU under torch.distributed.run; every rank trains its own
 scenes and the flat gradient buffer is averaged by one RCCL all-reduce per step.
@@ -24,7 +31,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 from disconet_amd import CoDetModule, Config, DiscoNet, TeacherNet  # noqa: E402
-from disconet_amd.synthetic import make_bevs, make_scene_batch, make_train_targets  # noqa: E402
+from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
+
+
+SCENE_BOXES = 64      # --targets boxes: boxes per scene (eval_codet.py --gt scene builds the same scenes)
 
 
 def _rsu_from_leftovers(args, rest):
@@ -78,12 +88,38 @@ def build_parser():
     ap.add_argument("--only_v2i", type=int, default=0)
     ap.add_argument("--auto_resume_path", default="",
                     help="resume from the newest epoch_N.pth under this directory, if any")
+    ap.add_argument("--targets", choices=("synthetic", "boxes"), default="synthetic",
+                    help="boxes: scenes with ground-truth boxes, targets assigned on the GPU every step")
+    ap.add_argument("--pos_thr", type=float, default=0.6, help="--targets boxes: an anchor is positive from this IoU")
+    ap.add_argument("--neg_thr", type=float, default=0.45, help="--targets boxes: an anchor is negative below this IoU")
+    ap.add_argument("--scenes", type=int, default=4, help="--targets boxes: the steps cycle through this many scene seeds")
     return ap
 
 
 def parse_args(argv=None):
     args, rest = build_parser().parse_known_args(argv)
     return _rsu_from_leftovers(args, rest)
+
+
+def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, device="cuda"):
+    """The `data` dict of one CoDetModule.step."""
+    n_img = num_agent * args.batch
+    if args.targets == "boxes":
+        from disconet_amd import targets
+        scene = make_box_scene_batch(args.batch, num_agent, hw, seed=((epoch * 1000 + it) * world + rank) % max(1, args.scenes),
+                                     boxes_per_scene=SCENE_BOXES, device=device)
+        data = {k: scene[k] for k in ("bev_seq", "trans_matrices", "num_agent")}
+        data.update(targets.assign_targets(anchors, scene["gt_boxes"], scene["gt_count"], args.pos_thr, args.neg_thr))
+        return data
+    seed = (epoch * 1000 + it) * world + rank
+    bevs, trans, na = make_scene_batch(args.batch, num_agent, hw, jitter_seed=seed)
+    labels, targets, mask = make_train_targets(n_img, hw, seed=seed)
+    data = {"bev_seq": bevs.to(device), "trans_matrices": trans.to(device), "num_agent": na.to(device),
+            "labels": labels.to(device), "reg_targets": targets.to(device), "reg_loss_mask": mask.to(device)}
+    if args.kd_flag:
+        data["bev_seq_teacher"] = make_bevs(args.batch, num_agent, hw, p=0.05).to(device)
+        data["kd_weight"] = args.kd_weight
+    return data
 
 
 def main(argv=None):
@@ -126,18 +162,16 @@ def main(argv=None):
     if optimizer_state is not None:
         fafmodule.engine.load_state_dict(optimizer_state)
 
-    n_img = num_agent * args.batch
+    anchors = None
+    if args.targets == "boxes":
+        if args.kd_flag:
+            raise SystemExit("--targets boxes has no teacher view of its scenes: run it with --kd_flag 0")
+        from disconet_amd import postprocess
+        anchors = postprocess.make_anchors(config)
     for epoch in range(start_epoch, start_epoch + args.nepoch):
         t0, running = time.perf_counter(), 0.0
         for it in range(args.steps_per_epoch):
-            seed = (epoch * 1000 + it) * world + rank
-            bevs, trans, na = make_scene_batch(args.batch, num_agent, hw, jitter_seed=seed)
-            labels, targets, mask = make_train_targets(n_img, hw, seed=seed)
-            data = {"bev_seq": bevs.cuda(), "trans_matrices": trans.cuda(), "num_agent": na.cuda(),
-                    "labels": labels.cuda(), "reg_targets": targets.cuda(), "reg_loss_mask": mask.cuda()}
-            if args.kd_flag:
-                data["bev_seq_teacher"] = make_bevs(args.batch, num_agent, hw, p=0.05).cuda()
-                data["kd_weight"] = args.kd_weight
+            data = step_data(args, num_agent, hw, epoch, it, world, rank, anchors)
             out = fafmodule.step(data, args.batch)
             running += out["loss"]
         torch.cuda.synchronize()
