@@ -6,11 +6,12 @@ include/disconet_hip.h).  See DESIGN.md.
 """
 from .config import Config
 from .model import DiscoNet
-from . import targets
+from . import holistic, targets
 from .seg import SegDiscoNet, SegModule
+from .holistic import holistic_views
 from .teacher import TeacherNet
 from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
 __all__ = ["Config", "DiscoNet", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "targets",
-           "assign_targets"]
+           "assign_targets", "holistic", "holistic_views"]

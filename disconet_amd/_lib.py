@@ -75,6 +75,8 @@ SIGNATURES = {
     "dn_sp_range_flags_async": (c_int, [c_void_p, c_int, c_void_p]),
     "dn_voxelize_occupy": (c_int, [c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double),
                                    POINTER(c_int), c_void_p, c_void_p]),
+    "dn_voxelize_views": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     "dn_voxel_compact_workspace": (c_size_t, [POINTER(c_int)]),
     "dn_voxel_compact": (c_int, [c_void_p, POINTER(c_int), c_void_p, c_int, c_void_p, c_void_p,
                                  c_void_p]),

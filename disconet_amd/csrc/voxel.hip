@@ -33,6 +33,55 @@ __global__ void voxelize_kernel(const float* __restrict__ pts, int n, int stride
   }
 }
 
+// Many clouds under many poses into many grids, one launch (dn_voxelize_views; the contract is in disconet_hip.h).
+// blockIdx.y walks the sources, blockIdx.x / threadIdx.x a source's points: the source's row range, view and pose are
+// uniform over a workgroup.  A source with pose T maps (x, y, z) to c_r = float32(((T[r][0] x + T[r][1] y) + T[r][2] z)
+// + T[r][3]) with every operand widened to float64: a product of two float32 values is exact in float64, so a product
+// fused into the add that follows rounds exactly as the separate one does; only the order of the three additions counts.
+// The float32 coordinates then take voxelize_kernel's rule, line for line.  A source whose indices point outside the
+// buffers it was given (rows, view, pose) writes nothing.
+__global__ void __launch_bounds__(256) voxelize_views_kernel(
+    const float* __restrict__ pts, long n_pts, int stride, const int32_t* __restrict__ src_begin,
+    const int32_t* __restrict__ src_count, const int32_t* __restrict__ src_view, const int32_t* __restrict__ src_pose,
+    const float* __restrict__ poses, int n_pose, int n_src, int n_views, VoxelGeom g, float* __restrict__ dense,
+    unsigned* __restrict__ bits) {
+  for (int s = blockIdx.y; s < n_src; s += gridDim.y) {
+    const long begin = src_begin[s], count = src_count[s];
+    const int view = src_view[s], pi = src_pose[s];
+    if (begin < 0 || count <= 0 || begin + count > n_pts || (unsigned)view >= (unsigned)n_views || pi < -1 || pi >= n_pose)
+      continue;
+    double T[3][4] = {};
+    if (pi >= 0) {
+      const float* t = poses + (size_t)pi * 16;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) T[r][c] = (double)t[4 * r + c];
+    }
+    const size_t pix0 = (size_t)view * g.dx * g.dy;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
+      const float* p = pts + (size_t)(begin + i) * stride;
+      float fx = p[0], fy = p[1], fz = p[2];
+      if (pi >= 0) {
+        const double px = (double)fx, py = (double)fy, pz = (double)fz;
+        fx = (float)(((T[0][0] * px + T[0][1] * py) + T[0][2] * pz) + T[0][3]);
+        fy = (float)(((T[1][0] * px + T[1][1] * py) + T[1][2] * pz) + T[1][3]);
+        fz = (float)(((T[2][0] * px + T[2][1] * py) + T[2][2] * pz) + T[2][3]);
+      }
+      const double x = (double)fx, y = (double)fy, z = (double)fz;
+      if (!(g.xlo < x && x < g.xhi && g.ylo < y && y < g.yhi && g.zlo < z && z < g.zhi)) continue;
+      const int qx = (int)floor(x / g.vx) - g.minx;
+      const int qy = (int)floor(y / g.vy) - g.miny;
+      const int qz = (int)floor(z / g.vz) - g.minz;
+      if ((unsigned)qx < (unsigned)g.dx && (unsigned)qy < (unsigned)g.dy && (unsigned)qz < (unsigned)g.dz) {
+        const size_t pix = pix0 + (size_t)qx * g.dy + qy;
+        if (dense) dense[pix * g.dz + qz] = 1.0f;
+        if (bits) atomicOr(&bits[pix], 1u << qz);
+      }
+    }
+  }
+}
+
 constexpr int COMPACT_BLOCK = 256;
 constexpr int COMPACT_ITEMS = 4;
 constexpr int COMPACT_TILE = COMPACT_BLOCK * COMPACT_ITEMS;
@@ -209,6 +258,52 @@ extern "C" int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
   const int blocks = (n_pts + 255) / 256 < 2048 ? (n_pts + 255) / 256 : 2048;
   hipLaunchKernelGGL(voxelize_kernel, dim3(blocks), dim3(256), 0, s, pts, n_pts, pt_stride, g, dense);
   return dn::check_launch("voxelize_kernel");
+}
+
+extern "C" int dn_voxelize_views(const float* pts, long n_pts, int pt_stride, const int32_t* src_begin,
+                                 const int32_t* src_count, const int32_t* src_view, const int32_t* src_pose,
+                                 const float* poses, int n_pose, int n_src, int max_count, int n_views,
+                                 const double* vs, const double* ext, const int* dims, float* dense, uint32_t* bits,
+                                 void* stream) {
+  DN_REQUIRE(vs && ext && dims, "voxelize_views: null pointer (voxel size, extents or dims)");
+  DN_REQUIRE(dense || bits, "voxelize_views: null outputs: one of dense / bits is needed");
+  DN_REQUIRE(n_views >= 1, "voxelize_views: %d views (at least one is needed)", n_views);
+  DN_REQUIRE(n_src >= 0, "voxelize_views: %d sources", n_src);
+  DN_REQUIRE(n_src == 0 || (src_begin && src_count && src_view && src_pose),
+             "voxelize_views: null pointer in the source lists of %d sources", n_src);
+  DN_REQUIRE(n_pts >= 0 && (n_pts == 0 || pts), "voxelize_views: bad point buffer (%ld rows)", n_pts);
+  DN_REQUIRE(n_pose >= 0 && (n_pose == 0 || poses), "voxelize_views: bad pose buffer (%d poses)", n_pose);
+  DN_REQUIRE(max_count >= 0, "voxelize_views: max_count %d", max_count);
+  DN_REQUIRE(pt_stride >= 3, "voxelize_views: points need >= 3 columns (got %d)", pt_stride);
+  DN_REQUIRE(vs[0] > 0 && vs[1] > 0 && vs[2] > 0, "voxelize_views: voxel size must be positive");
+  VoxelGeom g;
+  g.vx = vs[0]; g.vy = vs[1]; g.vz = vs[2];
+  g.xlo = ext[0]; g.xhi = ext[1]; g.ylo = ext[2]; g.yhi = ext[3]; g.zlo = ext[4]; g.zhi = ext[5];
+  g.minx = (int)floor(ext[0] / vs[0]); g.miny = (int)floor(ext[2] / vs[1]);
+  g.minz = (int)floor(ext[4] / vs[2]);
+  const int ex = (int)ceil(ext[1] / vs[0]) - g.minx, ey = (int)ceil(ext[3] / vs[1]) - g.miny,
+            ez = (int)ceil(ext[5] / vs[2]) - g.minz;
+  DN_REQUIRE(dims[0] == ex && dims[1] == ey && dims[2] == ez,
+             "voxelize_views: dims (%d,%d,%d) do not match extents/voxel_size (%d,%d,%d)", dims[0],
+             dims[1], dims[2], ex, ey, ez);
+  DN_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "voxelize_views: empty grid (%d,%d,%d)", dims[0], dims[1], dims[2]);
+  DN_REQUIRE(!bits || dims[2] <= 32, "voxelize_views: %d height bins do not fit one word per pixel", dims[2]);
+  g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
+  hipStream_t s = (hipStream_t)stream;
+  const size_t pixels = (size_t)n_views * g.dx * g.dy;
+  hipError_t e = hipSuccess;
+  if (dense) e = dn::zero_fill(dense, pixels * g.dz * sizeof(float), s);
+  if (e == hipSuccess && bits) e = dn::zero_fill(bits, pixels * sizeof(uint32_t), s);
+  if (e != hipSuccess) return dn::fail(DN_ERR_LAUNCH, "voxelize_views: memset: %s", hipGetErrorString(e));
+  if (n_src == 0 || n_pts == 0 || max_count == 0) return DN_OK;
+  // max_count only sizes the grid: both loops stride, a longer source is still read to its end
+  // about 4096 workgroups at most (16 per CU); the threads stride over what is left
+  const int by = n_src < 4096 ? n_src : 4096;
+  const int cap = 4096 / by, need = (max_count + 255) / 256;
+  const int bx = need < cap ? need : cap;
+  hipLaunchKernelGGL(voxelize_views_kernel, dim3(bx, by), dim3(256), 0, s, pts, n_pts, pt_stride, src_begin, src_count,
+                     src_view, src_pose, poses, n_pose, n_src, n_views, g, dense, bits);
+  return dn::check_launch("voxelize_views_kernel");
 }
 
 extern "C" size_t dn_voxel_compact_workspace(const int* dims) {

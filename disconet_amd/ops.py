@@ -82,6 +82,55 @@ def voxelize_occupy(pts, voxel_size, extents, dims):
     return dense
 
 
+def voxelize_views(pts, src_begin, src_count, src_view, src_pose, poses, n_views, max_count, voxel_size, extents, dims,
+                   want=("dense",), out=None):
+    """Many clouds under many poses into many grids, one launch (dn_voxelize_views; include/disconet_hip.h states the
+    arithmetic).  pts [P, >=3] float32: every cloud, concatenated; src_begin / src_count / src_view / src_pose [S] int32
+    device tensors: a source's rows of pts, the view that receives it and its index into poses (-1: the points as they are);
+    poses [..., 4, 4] float32 (trans_matrices as it is: flattened, not gathered); max_count: the largest src_count, a host
+    int.  -> {"dense": [n_views, 1, X, Y, Z] float32, "bits": SpTensor(bits=True) [n_views, X, Y, Z <= 32]}, the keys of
+    `want`.  Runs on torch's current stream, takes its outputs from the caching allocator (or from `out`, a dict of the
+    same form, for a caller that keeps them) and never waits for the device: it can be captured into a graph."""
+    lists = (src_begin, src_count, src_view, src_pose)
+    _need_gpu(pts, poses, *lists)
+    _f32c(pts, "pts")
+    _f32c(poses, "poses")
+    want = tuple(want)
+    if not want or any(k not in ("dense", "bits") for k in want):
+        raise _lib.DnError("voxelize_views: want = %r; 'dense' and / or 'bits' are the outputs" % (want,))
+    if pts.dim() != 2 or poses.dim() < 2 or tuple(poses.shape[-2:]) != (4, 4):
+        raise _lib.DnError("voxelize_views: pts %s must be [P, >=3], poses %s [..., 4, 4]" % (tuple(pts.shape), tuple(poses.shape)))
+    n_src = int(src_begin.numel())
+    for t in lists:
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n_src:
+            raise _lib.DnError("voxelize_views needs four contiguous int32 source lists of one length")
+    vs, ext = _geom(voxel_size, extents)
+    x, y, z = (int(v) for v in dims)
+    d = (ctypes.c_int * 3)(x, y, z)
+    n_views = int(n_views)
+    out = dict(out or {})
+    dense = bits = None
+    if "dense" in want:
+        dense = out.get("dense")
+        if dense is None:
+            dense = torch.empty((max(n_views, 0), 1, x, y, z), dtype=torch.float32, device=pts.device)
+    if "bits" in want:
+        bits = out.get("bits")
+        if bits is None and z <= 32:
+            bits = SpTensor(max(n_views, 0), x, y, z, device=pts.device, bits=True)
+    # (more than 32 height bins with "bits": the library refuses it by name, with a pointer that is never dereferenced)
+    bits_ptr = _ptr(bits.data) if bits is not None else (ctypes.c_void_p(16) if "bits" in want else None)
+    check(_lib.load().dn_voxelize_views(_ptr(pts), pts.shape[0], pts.shape[1], *[_ptr(t) for t in lists], _ptr(poses),
+                                        poses.numel() // 16, n_src, int(max_count), n_views, vs, ext, d, _ptr(dense),
+                                        bits_ptr, _stream()), "dn_voxelize_views")
+    res = {}
+    if dense is not None:
+        res["dense"] = dense
+    if bits is not None:
+        res["bits"] = bits
+    return res
+
+
 def voxel_compact(dense, capacity=None):
     """dense [X, Y, Z] -> (indices [M, 3] int32 in lexsort(x, y, z) order)."""
     _need_gpu(dense)

@@ -218,7 +218,8 @@ def host_occupancy(pts, voxel_size, extents, dims):
     return dense
 
 
-def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_per_scene=24, clutter=200, device=None):
+def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_per_scene=24, clutter=200, device=None,
+                         teacher=False):
     """Seeded scenes in which the ground truth and the occupancy describe the same boxes.  Per scene up to
     `boxes_per_scene` car-sized world boxes (w ~ U(1.6, 2.4), l ~ U(3.5, 5.5), any yaw) sit on a grid of pitch 8 m over
     agent 0's extents, centres jittered by at most 1 m: two centres are at least 6 m apart, the boxes' circumscribed
@@ -228,7 +229,9 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
     numpy form host_occupancy, tensors stay on the host).  Images are agent-major (image = agent * B + b).  Returns
     {"bev_seq" [A*B, 1, H, W, Z], "trans_matrices", "num_agent" (as make_scene_batch), "gt_boxes" [A*B, boxes_per_scene, 6]
     float32, "gt_count" [A*B] int32 (rows >= count zero), "points": per image [P, 4] float32, "world_boxes": per scene
-    [K, 6] float64}."""
+    [K, 6] float64}.  teacher: also "bev_seq_teacher" [A*B, 1, H, W, Z], the holistic view of every image -- all agents'
+    clouds carried into the image's frame by trans_matrices, merged and voxelised (holistic.holistic_views, one launch, on
+    `device`; device = None: the numpy form holistic.host_holistic_views)."""
     from .config import Config
     cfg = Config(map_hw=map_hw)
     ext, vs, dims = cfg.area_extents, cfg.voxel_size, cfg.map_dims
@@ -276,5 +279,13 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
            "gt_count": torch.from_numpy(gt_count)}
     if device is not None:
         out = {k: v.to(device) for k, v in out.items()}
+    if teacher:
+        from . import holistic
+        live = [num_agent] * batch_size
+        if device is None:
+            out["bev_seq_teacher"] = torch.from_numpy(holistic.host_holistic_views(points, trans, live, batch_size, cfg)["dense"])
+        else:
+            out["bev_seq_teacher"] = holistic.holistic_views(points, out["trans_matrices"], live, batch_size, cfg,
+                                                             device=device)["dense"]
     out["points"], out["world_boxes"] = points, world
     return out

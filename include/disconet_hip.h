@@ -99,6 +99,46 @@ int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
                        const double* voxel_size_host, const double* extents_host,
                        const int* dims_host, float* dense, void* stream);
 
+/* Many clouds under many poses into many grids, ONE launch: the distillation teacher's holistic views (every agent's
+ * cloud merged into each ego's frame; the reference's bev_seq_teacher) and, with them or alone, the students' own views.
+ * A SOURCE is one cloud under one pose, a VIEW (one output image) the union of its sources.
+ *   pts        [n_pts][pt_stride] float32: every cloud, concatenated; x, y, z in columns 0..2, pt_stride >= 3
+ *   src_begin, src_count  [n_src] int32 (device): the rows of pts a source reads
+ *   src_view   [n_src] int32 (device): the view that receives the source, in [0, n_views)
+ *   src_pose   [n_src] int32 (device): index into poses, or -1 = the points are taken as they are
+ *   poses      [n_pose][4][4] float32 row-major (trans_matrices [B][A][A][4][4] flattened: no gather is needed)
+ *   max_count  the largest src_count (host): it sizes the grid only, a longer source is still read to its end
+ *   voxel_size_host, extents_host, dims_host: as dn_voxelize_occupy, with the same dims check
+ *   dense      nullable: [n_views][X][Y][Z] float32, 0/1
+ *   bits       nullable: [n_views][X][Y] uint32, bit z = height bin z holds a point (dn_scatter_dense_bits' form, Z <= 32)
+ * At least one of dense / bits is given; the call zero-fills what it was given, then runs one kernel over all (source,
+ * point) pairs: a plain idempotent store into dense, an atomic OR into bits, so duplicated sources, their order and the
+ * order of the points cannot change a byte.  No host synchronisation and no allocation: it can be captured into a graph.
+ * n_src == 0 zero-fills and returns DN_OK.  A view without sources is all zero.  The lists live on the device, so the
+ * host cannot refuse a bad entry: a source whose rows, view or pose index point outside [0, n_pts) / [0, n_views) /
+ * [-1, n_pose) writes nothing.
+ *
+ * THE ARITHMETIC (the contract; the tests are bit-exact against it).  A source with pose T maps a point (x, y, z)
+ * (float32) to three coordinates, r = 0, 1, 2:
+ *     c_r = float32( ((T[r][0]*x + T[r][1]*y) + T[r][2]*z) + T[r][3] )
+ * every operand widened to float64, the sums taken in that order in float64.  A product of two float32 values is exact
+ * in float64, so whether the compiler fuses a product into the add that follows cannot change a bit: only the order of
+ * the three additions matters (the build has no fast-math flag; keep it that way).  The result is rounded ONCE to
+ * float32 -- deliberately: a stored cloud is float32 and the voxel rule compares float32 coordinates.  The float32
+ * coordinates then go through exactly dn_voxelize_occupy's rule: strict extent test against the float64 extents,
+ * floor(c / voxel) with a float64 divide, minus floor(lo / voxel).  A source with pose -1 skips the transform: a view
+ * with that single source is bit for bit dn_voxelize_occupy of its cloud.  NaN and infinite coordinates fail the strict
+ * test and are dropped, as in numpy.
+ *
+ * NOT PINNED to the upstream dataset builder's merge (create_data_det.py is not among the sources this project was
+ * written from; what follows is recollection): which poses it uses, whether the ego's own points go through an identity
+ * transform, and whether it transforms in float32 or float64.  The contract above is this project's own, in the spirit
+ * of SURVEY.md Appendix C; disconet_amd/holistic.py :: host_holistic_views is its numpy statement. */
+int dn_voxelize_views(const float* pts, long n_pts, int pt_stride, const int32_t* src_begin, const int32_t* src_count,
+                      const int32_t* src_view, const int32_t* src_pose, const float* poses, int n_pose, int n_src,
+                      int max_count, int n_views, const double* voxel_size_host, const double* extents_host,
+                      const int* dims_host, float* dense, uint32_t* bits, void* stream);
+
 /* Sorted-unique voxel index list of a dense grid, in the reference's
  * lexsort(x, then y, then z) order (= linear order of the [X][Y][Z] grid).
  *   indices   [capacity][3] int32 out;  count: int32 out (device)

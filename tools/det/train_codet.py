@@ -17,6 +17,13 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
     targets.assign_targets (dn_assign_targets, on the GPU) called every step: the anchor assignment the reference runs
     when it creates the dataset.  The steps cycle through the scene seeds 0 .. --scenes - 1, the frames that
     `eval_codet.py --gt scene --resume <logpath>/epoch_N.pth` then scores against their own boxes.
+    With --kd_flag 1 the scenes also carry the teacher's holistic view (every agent's cloud merged into each ego's frame and
+    voxelised: holistic.holistic_views, dn_voxelize_views, one launch per step) as data["bev_seq_teacher"]:
+
+        python tools/det/train_codet.py --com disco --targets boxes --kd_flag 1 --resume_teacher teacher.pth
+
+    Without --resume_teacher the teacher keeps its initial weights: the distillation target is then meaningless and only
+    the plumbing is exercised (the tool says so).  Training the teacher itself is not built yet (TeacherNet is eval() only).
 
 Data-parallel: one process per GPU under torch.distributed.run; every rank trains its own
 scenes and the flat gradient buffer is averaged by one RCCL all-reduce per step.
@@ -107,9 +114,12 @@ def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, dev
     if args.targets == "boxes":
         from disconet_amd import targets
         scene = make_box_scene_batch(args.batch, num_agent, hw, seed=((epoch * 1000 + it) * world + rank) % max(1, args.scenes),
-                                     boxes_per_scene=SCENE_BOXES, device=device)
+                                     boxes_per_scene=SCENE_BOXES, device=device, teacher=bool(args.kd_flag))
         data = {k: scene[k] for k in ("bev_seq", "trans_matrices", "num_agent")}
         data.update(targets.assign_targets(anchors, scene["gt_boxes"], scene["gt_count"], args.pos_thr, args.neg_thr))
+        if args.kd_flag:
+            data["bev_seq_teacher"] = scene["bev_seq_teacher"]
+            data["kd_weight"] = args.kd_weight
         return data
     seed = (epoch * 1000 + it) * world + rank
     bevs, trans, na = make_scene_batch(args.batch, num_agent, hw, jitter_seed=seed)
@@ -149,6 +159,11 @@ def main(argv=None):
         teacher = TeacherNet(config).cuda()
         if args.resume_teacher:
             teacher.load_state_dict(torch.load(args.resume_teacher, map_location="cpu")["model_state_dict"])
+            if rank == 0:
+                print("teacher: resumed from", args.resume_teacher)
+        elif rank == 0:
+            print("teacher: no --resume_teacher, the teacher has its INITIAL weights: the distillation target is meaningless, "
+                  "this run exercises the plumbing only")
         teacher.eval()
     start_epoch = 1
     optimizer_state = None
@@ -164,8 +179,6 @@ def main(argv=None):
 
     anchors = None
     if args.targets == "boxes":
-        if args.kd_flag:
-            raise SystemExit("--targets boxes has no teacher view of its scenes: run it with --kd_flag 0")
         from disconet_amd import postprocess
         anchors = postprocess.make_anchors(config)
     for epoch in range(start_epoch, start_epoch + args.nepoch):
