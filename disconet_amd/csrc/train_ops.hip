@@ -916,6 +916,35 @@ fuse_combine_bwd_kernel(const float* __restrict__ dfused, int ld_df, const float
 // ---------------------------------------------------------------------------------
 // loss and optimiser
 // ---------------------------------------------------------------------------------
+// Softmax focal loss of one anchor, L = -a (1 - q)^gamma log q with q the softmax probability of the labelled class, in the
+// log-softmax form of oracle/train_ref.py :: focal_loss: with x = z_other - z_target, log q = -softplus(x), q = sigmoid(-x) and
+// 1 - q = sigmoid(x) -- each from e = exp(-|x|) <= 1, so nothing is clamped, nothing is divided by q and 1 - q does not cancel.
+// (Up to dn_version 139 log q was logf(max(q, 1e-30)) of a float quotient and the gradient divided by that clamp: past a
+// wrong-side gap of ln 1e30 = 69 the loss stopped growing and the gradient of a confidently wrong anchor fell to zero.)
+//   dL/dz_target = a [gamma (1 - q)^gamma q log q - (1 - q)^(gamma + 1)],  dL/dz_other = -dL/dz_target
+// The one formula of both loss kernels: their dcls agree bit for bit.
+__device__ inline void focal_one(float z0, float z1, float lb0, float lb1, float alpha, float gamma, float inv_norm,
+                                 float& d0, float& d1, double& l_cls) {
+  const bool fg = lb1 > 0.5f;
+  const bool any = fg || lb0 > 0.5f;      // an all-zero row is "don't care"
+  d0 = 0.f; d1 = 0.f;
+  if (any) {
+    const float x = fg ? z0 - z1 : z1 - z0;
+    const float a = fg ? alpha : 1.f - alpha;
+    const float e = expf(-fabsf(x));
+    const float big = 1.f / (1.f + e), small = e / (1.f + e);
+    const float q = x > 0.f ? small : big;
+    const float om = x > 0.f ? big : small;
+    const float lq = -(fmaxf(x, 0.f) + log1pf(e));
+    const float mod = gamma == 0.f ? 1.f : powf(om, gamma);
+    const float dmod = gamma == 0.f ? 0.f : gamma * mod;      // (1 - q) d(mod)/d(1 - q)
+    l_cls += (double)(-a * mod * lq);
+    const float dt = a * (dmod * q * lq - mod * om) * inv_norm;
+    d0 = fg ? -dt : dt;
+    d1 = fg ? dt : -dt;
+  }
+}
+
 __global__ void __launch_bounds__(256)
 det_loss_kernel(const float* __restrict__ cls, const float* __restrict__ labels,
                 const float* __restrict__ loc, const float* __restrict__ targets,
@@ -925,28 +954,8 @@ det_loss_kernel(const float* __restrict__ cls, const float* __restrict__ labels,
   double l_cls = 0.0, l_loc = 0.0;
   const float s2 = sigma * sigma;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    // two-class softmax, target = the one-hot column
-    const float z0 = cls[2 * i], z1 = cls[2 * i + 1];
-    const float mx = fmaxf(z0, z1);
-    const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
-    const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-    const bool fg = labels[2 * i + 1] > 0.5f;
-    const bool any = fg || labels[2 * i] > 0.5f;      // an all-zero row is "don't care"
-    float d0 = 0.f, d1 = 0.f;
-    if (any) {
-      const float q = fg ? p1 : p0;
-      const float a = fg ? alpha : 1.f - alpha;
-      const float lq = logf(fmaxf(q, 1e-30f));
-      const float om = 1.f - q;
-      const float mod = powf(om, gamma);
-      l_cls += (double)(-a * mod * lq);
-      // dL/dq, then dq/dz_c = q (delta_ct - p_c)
-      const float dmod = gamma == 0.f ? 0.f : gamma * powf(om, gamma - 1.f);
-      const float dl_dq = a * (dmod * lq - mod / fmaxf(q, 1e-30f));
-      const float t0 = fg ? 0.f : 1.f, t1 = fg ? 1.f : 0.f;
-      d0 = dl_dq * q * (t0 - p0) * inv_norm;
-      d1 = dl_dq * q * (t1 - p1) * inv_norm;
-    }
+    float d0, d1;
+    focal_one(cls[2 * i], cls[2 * i + 1], labels[2 * i], labels[2 * i + 1], alpha, gamma, inv_norm, d0, d1, l_cls);
     dcls[2 * i] = d0;
     dcls[2 * i + 1] = d1;
     const float mk = mask[i];
@@ -987,31 +996,9 @@ det_loss_kernel(const float* __restrict__ cls, const float* __restrict__ labels,
 // The same loss on FLAT float4 streams (round 6: the per-anchor form moved 786 MB per step at 54 % of the HBM rate -- every lane
 // read its anchor's six box codes at a 24-byte stride).  Loop A: two anchors' class logits / labels per float4; loop B: four
 // consecutive elements of loc / targets per float4, the anchor of element e is e / code (mask gather).  The per-element formulas
-// are det_loss_kernel's, so dcls / dloc are bit for bit its values; the loss VALUES are summed in another order (they already
-// leave through one f64 atomic per workgroup).  n even, code * n % 4 == 0, 16-byte aligned tensors.
-__device__ inline void focal_one(float z0, float z1, float lb0, float lb1, float alpha, float gamma, float inv_norm,
-                                 float& d0, float& d1, double& l_cls) {
-  const float mx = fmaxf(z0, z1);
-  const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
-  const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-  const bool fg = lb1 > 0.5f;
-  const bool any = fg || lb0 > 0.5f;
-  d0 = 0.f; d1 = 0.f;
-  if (any) {
-    const float q = fg ? p1 : p0;
-    const float a = fg ? alpha : 1.f - alpha;
-    const float lq = logf(fmaxf(q, 1e-30f));
-    const float om = 1.f - q;
-    const float mod = powf(om, gamma);
-    l_cls += (double)(-a * mod * lq);
-    const float dmod = gamma == 0.f ? 0.f : gamma * powf(om, gamma - 1.f);
-    const float dl_dq = a * (dmod * lq - mod / fmaxf(q, 1e-30f));
-    const float t0 = fg ? 0.f : 1.f, t1 = fg ? 1.f : 0.f;
-    d0 = dl_dq * q * (t0 - p0) * inv_norm;
-    d1 = dl_dq * q * (t1 - p1) * inv_norm;
-  }
-}
-
+// are det_loss_kernel's (focal_one above, the same smooth-L1 lines), so dcls / dloc are bit for bit its values; the loss VALUES
+// are summed in another order (they already leave through one f64 atomic per workgroup).  n even, code * n % 4 == 0, 16-byte
+// aligned tensors.
 __global__ void __launch_bounds__(256)
 det_loss_v4_kernel(const float* __restrict__ cls, const float* __restrict__ labels, const float* __restrict__ loc,
                    const float* __restrict__ targets, const float* __restrict__ mask, long n, int code, float alpha, float gamma,
@@ -1065,18 +1052,20 @@ det_loss_v4_kernel(const float* __restrict__ cls, const float* __restrict__ labe
   }
 }
 
+// b1 / b2 and their complements c1 = 1 - b1, c2 = 1 - b2 arrive rounded from double each on its own (dn_adam_step): 1.f - b2 of a
+// float-rounded 0.999 is off by 1.3e-5 of itself, which reached the update at ~3e-6 of its size.
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                            float wd, float bc1, float bc2_sqrt) {
+                            float* __restrict__ v, long n, float step_size, float b1, float c1, float b2, float c2, float eps,
+                            float wd, float bc2_sqrt) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float gi = g[i];
     if (wd != 0.f) gi += wd * p[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + c1 * gi;
+    const float vi = b2 * v[i] + c2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
     // torch: denom = sqrt(v) / sqrt(bias_correction2) + eps; p -= (lr / bias_correction1) * m / denom
-    p[i] -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+    p[i] -= step_size * mi / (sqrtf(vi) / bc2_sqrt + eps);
   }
 }
 
@@ -1525,14 +1514,16 @@ extern "C" int dn_det_loss(const float* cls, const float* labels, const float* l
   return dn::check_launch("det_loss_kernel");
 }
 
-extern "C" int dn_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
-                            float beta1, float beta2, float eps, float weight_decay, int step,
+extern "C" int dn_adam_step(float* p, const float* g, float* m, float* v, long n, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int step,
                             void* stream) {
   DN_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam: bad arguments");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2 = 1.f - powf(beta2, (float)step);
+  // the scalars of the update in double, as torch.optim.Adam keeps them, each rounded to float once
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2));
+                     n, (float)(lr / bc1), (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                     (float)weight_decay, (float)sqrt(bc2));
   return dn::check_launch("adam_kernel");
 }
 

@@ -29,8 +29,10 @@ int dn_sp_maxpool2(const void* src_sp, int n_images, int h, int w, int channels,
                    void* stream);
 
 /* nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) of the Up blocks
- * (upstream SegModelBase.py :: Up.up), SP in -> SP out [n][..][4][2h][2w]; ATen's arithmetic:
- * src = dst * (in - 1) / (out - 1), fp32 lerp weights. */
+ * (upstream SegModelBase.py :: Up.up), SP in -> SP out [n][..][4][2h][2w]; ATen's lerp order with
+ * src = dst * (in - 1) / (out - 1) taken as the exact rational (quotient = tap, remainder = weight,
+ * one rounding; dn_version 140), fp32 lerp weights.  The fp32 NHWC forms of the training step
+ * (dn_upsample2_bilinear_nhwc / _backward) use the same coordinates. */
 int dn_sp_upsample2_bilinear(const void* src_sp, int n_images, int h, int w, int channels,
                              void* dst_sp, void* stream);
 

@@ -246,7 +246,9 @@ int dn_pair_sum_ego(const float* dz1, const int* first, const int* pairs, int n_
 /* Softmax over a scene-agent's neighbour list and the weighted sum (forward), per pixel:
  *   s_k = relu(z4[pair_k]);  w_k = exp(s_k) / sum_j exp(s_j);  fused = sum_k w_k * maps[nbr_k]
  * lists: for ego e in [0, n_egos): entries first[e] .. first[e+1) of (pair_index, map_image);
- * ego_out[e] = image of `fused` to write.  maps holds own and warped maps in one buffer. */
+ * ego_out[e] = image of `fused` to write.  maps holds own and warped maps in one buffer.
+ * pair_index < 0: an entry without a logit (s = 0, no weight written) -- an ego that is not live; it must be its list's only
+ * entry (weight 1): the backward takes that weight as 1. */
 int dn_fuse_combine(const float* z4, const float* maps, const int* first, const int* pair_index,
                     const int* map_image, const int* ego_out, int n_egos, int hw, int c,
                     float* weights, float* fused, void* stream);
@@ -288,9 +290,11 @@ int dn_det_loss(const float* cls, const float* labels, const float* loc, const f
 int dn_kd_kl_loss(const float* student, const float* teacher, long rows, int c, float scale,
                   double* loss, float* dstudent, int zero_loss, void* stream);
 
-/* torch.optim.Adam (no amsgrad) on a flat parameter buffer; step counts from 1 */
-int dn_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
-                 float beta2, float eps, float weight_decay, int step, void* stream);
+/* torch.optim.Adam (no amsgrad) on a flat parameter buffer; step counts from 1.  The hyper-parameters are doubles, as
+ * torch keeps them: 1 - beta, the bias corrections and lr / bias_correction1 are formed in double and rounded to float once
+ * (dn_version 140; as floats, 1 - 0.999f was 1.3e-5 off). */
+int dn_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1,
+                 double beta2, double eps, double weight_decay, int step, void* stream);
 
 #ifdef __cplusplus
 }

@@ -49,7 +49,7 @@ static int errors_only(void) {
   d.stride = 2;
   CHECK(dn_conv_wgrad_sp_supported(&d) == 0 && dn_conv_wgrad_sp_workspace(&d) == 0, "wgrad_sp: stride 2");
   d.stride = 1; d.c0 = 32; d.ld0 = 32;
-  CHECK(dn_adam_step(NULL, NULL, NULL, NULL, 10, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1, NULL) == DN_ERR_ARG,
+  CHECK(dn_adam_step(NULL, NULL, NULL, NULL, 10, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, NULL) == DN_ERR_ARG,
         "adam null");
   CHECK(dn_bn_train_stats(NULL, 1, 10, 600, 600, NULL, 0, NULL, NULL, NULL, NULL, 0.f, NULL) == DN_ERR_ARG, "bn null");
   /* round 5: two-phase BatchNorm reductions (agent-parallel training) and the K-slice query */
