@@ -333,6 +333,7 @@ extern "C" int dn_spconv2d_pre_pair(const dn_conv_desc* d1, const dn_conv_desc* 
     attr_set = true;
   }
   const int grid = a.items < kCUs ? a.items : kCUs;
+  dn::g_sp_last_form = dn::SpLastForm{2, 3, 1, pp::TH, pp::TW, 32, 0, 0, 0, 1, 0, 2, 0, 0, 0, grid, a.items, a.items, 0, 0};
   hipLaunchKernelGGL(conv_pre_pair_kernel, dim3(grid), dim3(pp::NTHR), pp::LDS_BYTES, (hipStream_t)stream, a);
   return dn::check_launch("conv_pre_pair_kernel");
 }

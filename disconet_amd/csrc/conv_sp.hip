@@ -1543,6 +1543,8 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   a.n_cb = (d.c_out + BN - 1) / BN;
   a.rcp_ncb = 1.0f / (float)a.n_cb; a.rcp_tx = 1.0f / (float)a.tiles_x; a.rcp_ty = 1.0f / (float)a.tiles_y;
   const long resident = (long)occupancy * kCUs;
+  // what dn_spconv_last_form reports: the template parameters of this very instantiation
+  dn::SpLastForm form = {0, KS, STRIDE, TH, TW, BN, TG, CA, POST, BSTAT, UPM, AHI, KSL, NB, 0, 0, 0, 0, 0, 0};
   if constexpr (KSL != 0) {
     const int S = a.ks.count;
     DN_REQUIRE(S == 2 || S == 4, "spconv: %d K slices (1, 2 or 4)", S);
@@ -1557,6 +1559,10 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
     k.fixup = 0;
     const long work = k.n_whole + (long)k.n_split * S;
     a.total_items = (int)work;
+    form.grid = (int)(work > resident ? resident : work); form.total_items = (int)work;
+    form.n_whole = k.n_whole; form.n_split = k.n_split;
+    form.fixup_grid = k.n_split ? (int)(k.n_split > 4 * kCUs ? 4 * kCUs : k.n_split) : 0;
+    dn::g_sp_last_form = form;
     hipLaunchKernelGGL(kern, dim3((unsigned)(work > resident ? resident : work)), dim3(T::NT), lds_bytes, stream, a);
     if (k.n_split) {     // the split tiles' slices added in slice order + their epilogue: same kernel, no operands
       k.fixup = 1;
@@ -1566,6 +1572,8 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
     return dn::check_launch("conv_sp_kernel (K slices)");
   }
   dim3 grid((unsigned)(total > resident ? resident : total));
+  form.grid = (int)grid.x; form.total_items = (int)total; form.n_whole = (int)total;
+  dn::g_sp_last_form = form;
   hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds_bytes, stream, a);
   return dn::check_launch("conv_sp_kernel");
 }
@@ -1772,6 +1780,17 @@ extern "C" int dn_spconv_force_config(int cfg) {
 extern "C" int dn_spconv_set_upmode(int mode) {
   g_sp_upmode = mode;
   return DN_OK;
+}
+
+namespace dn { SpLastForm g_sp_last_form = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+
+extern "C" int dn_spconv_last_form(int* out, int n) {
+  constexpr int kInts = (int)(sizeof(dn::SpLastForm) / sizeof(int));
+  static_assert(sizeof(dn::SpLastForm) == 20 * sizeof(int), "dn_spconv_last_form: the record is 20 ints");
+  DN_REQUIRE(out && n > 0, "spconv last form: null pointer / no room");
+  const int* f = reinterpret_cast<const int*>(&dn::g_sp_last_form);
+  for (int i = 0; i < n && i < kInts; ++i) out[i] = f[i];
+  return kInts;
 }
 
 namespace {

@@ -721,6 +721,8 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
   a.n_cb = (a.c_out + BN - 1) / BN;
   a.rcp_ncb = 1.0f / (float)a.n_cb; a.rcp_tx = 1.0f / (float)a.tiles_x; a.rcp_ty = 1.0f / (float)a.tiles_y;
   const long resident = (DEEP ? 1L : 2L) * kCUs;
+  // what dn_spconv_last_form reports (family 1): the pixel tile, BN, DEEP and KSL of this instantiation
+  dn::SpLastForm form = {1, 3, 1, QTH, QTW, BN, 0, 1, 0, 0, 2, 0, KSL, 0, DEEP, 0, 0, 0, 0, 0};
   if constexpr (KSL != 0) {
     KSlices& k = a.ks;
     const int S = k.count, ng = a.c0g + a.c1g;
@@ -743,6 +745,10 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
     k.fixup = 0;
     const long work = k.n_whole + (long)k.n_split * S;
     a.total_items = (int)work;
+    form.grid = (int)(work > resident ? resident : work); form.total_items = (int)work;
+    form.n_whole = k.n_whole; form.n_split = k.n_split;
+    form.fixup_grid = k.n_split ? (int)(k.n_split > 2 * kCUs ? 2 * kCUs : k.n_split) : 0;
+    dn::g_sp_last_form = form;
     hipLaunchKernelGGL(kern, dim3((unsigned)(work > resident ? resident : work)), dim3(QNT), T::LDS_BYTES, stream, a);
     if (k.n_split) {
       k.fixup = 1;
@@ -753,6 +759,8 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
     return dn::check_launch("conv_spq_kernel (K slices)");
   }
   dim3 grid((unsigned)(total > resident ? resident : total));
+  form.grid = (int)grid.x; form.total_items = (int)total; form.n_whole = (int)total;
+  dn::g_sp_last_form = form;
   hipLaunchKernelGGL(kern, grid, dim3(QNT), T::LDS_BYTES, stream, a);
   return dn::check_launch("conv_spq_kernel");
 }

@@ -56,6 +56,18 @@ void range_collect_fuse_mlp(unsigned* dst, bool reset, hipStream_t stream);
 void range_collect_conv_wgrad(unsigned* dst, bool reset, hipStream_t stream);
 unsigned* sp_range_word();   // conv_sp.hip's word on the current device (nullptr on error)
 
+// The form of the last SP conv launch of the process (dn_spconv_last_form: tools and tests), written by the three
+// launchers themselves -- launch<>() of conv_sp.hip, launch_spq<>() of conv_spq.hip, dn_spconv2d_pre_pair -- so that
+// it names the kernel that ran and not a copy of the dispatch.  Host side only; process-wide, not thread-safe.
+struct SpLastForm {
+  int family;                     // 0 = conv_sp_kernel, 1 = conv_spq_kernel, 2 = conv_pre_pair_kernel, -1 = none yet
+  int ks, stride, th, tw, bn, tg, ca, post, bstat, upm, ahi, ksl, nb, deep;
+  int grid, total_items;          // workgroups and work items of the (main) launch
+  int n_whole, n_split;           // K-sliced launches: tiles run whole / split into slices (else total_items, 0)
+  int fixup_grid;                 // workgroups of the K-sliced fix-up launch (0: none)
+};
+extern SpLastForm g_sp_last_form;
+
 }  // namespace dn
 
 #define DN_REQUIRE(cond, ...) \

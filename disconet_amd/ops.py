@@ -591,6 +591,21 @@ def sp_conv2d_nhwc(d, src0, packed, scale, shift, out, src1=None):
     return out
 
 
+SP_FORM_FIELDS = ("family", "KS", "STRIDE", "TH", "TW", "BN", "TG", "CA", "POST", "BSTAT", "UPM", "AHI", "KSL", "NB", "DEEP",
+                  "grid", "total_items", "n_whole", "n_split", "fixup_grid")
+
+
+def sp_last_form():
+    """-> dict: which kernel the last SP conv launch of this process ran (dn_spconv_last_form; tools and tests): family
+    (0 conv_sp, 1 conv_spq, 2 stem pair), the template parameters, the grid and the K-slice plan.  Host-side record,
+    not thread-safe."""
+    buf = (ctypes.c_int * len(SP_FORM_FIELDS))()
+    n = _lib.load().dn_spconv_last_form(buf, len(SP_FORM_FIELDS))
+    if n != len(SP_FORM_FIELDS):
+        raise _lib.DnError("dn_spconv_last_form: %d fields, expected %d" % (n, len(SP_FORM_FIELDS)))
+    return dict(zip(SP_FORM_FIELDS, (int(v) for v in buf)))
+
+
 def sp_conv2d_pre_pair_supported(d1, d2):
     return bool(_lib.load().dn_spconv2d_pre_pair_supported(ctypes.byref(d1), ctypes.byref(d2)))
 

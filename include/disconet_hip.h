@@ -29,7 +29,7 @@
  *     thread-local message for the last failing call on this thread;
  *   - re-entrant.  Process-wide state is limited to launch-time caches filled on first use
  *     (kernel attributes / occupancy per instantiation), the tools-only hooks dn_spconv_force_config(),
- *     dn_spconv_set_upmode() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
+ *     dn_spconv_set_upmode(), dn_spconv_last_form() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
  *     DN_WARP_GATHER_LEGACY (environment, read once: the other side of a bitwise / agreement test).
  */
 #ifndef DISCONET_HIP_H
@@ -381,6 +381,20 @@ int dn_spconv_force_config(int cfg);
 /* tools only: form of the packed image / kernel of layers whose first source is upsampled: 0 = plain taps,
  * 1 = row-merged, 2 = row- and column-merged per parity class, -1 = the default (2).  Process-wide; weights packed under one mode must run under the same mode. */
 int dn_spconv_set_upmode(int mode);
+/* tools and tests only: which kernel did the last SP conv launch of this process run?  Written by the launchers
+ * themselves (host side; nothing on the device knows of it).  Fills out[0 .. min(n, 20)) with
+ *   0 family (0 = conv_sp_kernel, 1 = conv_spq_kernel: the quad-merged up-conv, 2 = conv_pre_pair_kernel: the stem
+ *     pair; -1 = no launch yet)
+ *   1..13  KS, STRIDE, TH, TW, BN, TG, CA, POST, BSTAT, UPM, AHI, KSL, NB -- the template parameters of conv_sp.hip's
+ *     SpTile (family 1: KS = 3, STRIDE = 1, the 8 x 32 tile, BN, UPM = 2, KSL; family 2: the 16 x 32 tile, BN = 32,
+ *     BSTAT = 1, AHI = 2; what a family has no such parameter for is 0)
+ *   14 DEEP (family 1: the one-step-per-chunk form)
+ *   15 grid, 16 total_items  -- workgroups and work items of the launch (K-sliced: whole tiles + slices)
+ *   17 n_whole, 18 n_split   -- K-sliced launches: tiles run whole / handed out slice by slice (else total_items, 0)
+ *   19 fixup_grid            -- workgroups of the K-sliced fix-up launch, which belongs to the same record (0: none)
+ * and returns 20.  A call that fails its argument checks before the launch leaves the record as it was.
+ * Process-wide, not thread-safe (like dn_spconv_force_config). */
+int dn_spconv_last_form(int* out, int n);
 
 /* ------------------------------------------------------------------------
  * K4 -- pose-based two-pass bilinear warp of neighbour feature maps.
