@@ -144,6 +144,10 @@ SIGNATURES = {
     "dn_assign_targets_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "dn_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_double, c_double, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dn_track_state_bytes": (c_size_t, [c_int, c_int]),
+    "dn_track_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "dn_track_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -289,3 +289,61 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
                                                              device=device)["dense"]
     out["points"], out["world_boxes"] = points, world
     return out
+
+
+# ---------------------------------------------------------------------------
+# detection sequences for the tracker (tracking.Sort / HostSort)
+# ---------------------------------------------------------------------------
+def make_track_sequence(frames, n_images, seed=0, objects=6, width=None, noise=0.05, p_miss=0.1, false_positives=1,
+                        extent=24.0, speed=0.4, spread=0.05):
+    """Seeded detections of moving boxes, frame by frame: per image `objects` car-sized boxes (w ~ U(1.6, 2.4),
+    l ~ U(3.5, 5.5), any yaw) start on a grid of pitch 8 m (centres jittered by at most 1 m) and move at constant
+    velocity -- a flow of at most `speed` m per frame shared by the image plus at most `spread` m per frame of their own,
+    so that two of them never come close in a few dozen frames.  Every frame, every object is detected with probability
+    1 - p_miss at its true box plus N(0, noise) m on the centre and N(0, noise / 2) m on the size, with a score in
+    (0.5, 1); `false_positives` boxes per frame are drawn uniformly over the extent with a score in (0.1, 0.5).  Rows are
+    the objects in identity order, then the false positives.  Returns a list of `frames` pairs (det, ident):
+    det = postprocess.pad_detections' dict {"boxes" [N, K, 6] float32, "scores" [N, K] float32, "count" [N] int32} (numpy;
+    K = `width`, default objects + false_positives, at least 1), ident [N, K] int32 = the true identity of each row
+    (0 .. objects - 1), -1 for a false positive and for the padding."""
+    from .postprocess import pad_detections
+    rng = np.random.RandomState(int(seed))
+    k = max(1, int(objects) + int(false_positives)) if width is None else int(width)
+    cells = max(1, int(2 * extent // 8.0))
+    if objects > cells * cells:
+        raise ValueError("%d objects do not fit the %d x %d grid of pitch 8 m over +-%g m" % (objects, cells, cells, extent))
+    start, vel, size, yaw = [], [], [], []
+    for _ in range(n_images):
+        cell = rng.permutation(cells * cells)[:objects]
+        xy = np.stack([(cell // cells + 0.5) * 8.0 - cells * 4.0, (cell % cells + 0.5) * 8.0 - cells * 4.0], 1)
+        start.append(xy + rng.uniform(-1.0, 1.0, (objects, 2)))
+        flow = rng.uniform(-speed, speed, 2) / math.sqrt(2.0)
+        vel.append(flow[None, :] + rng.uniform(-spread, spread, (objects, 2)) / math.sqrt(2.0))
+        size.append(np.stack([rng.uniform(1.6, 2.4, objects), rng.uniform(3.5, 5.5, objects)], 1))
+        yaw.append(rng.uniform(-math.pi, math.pi, objects))
+    out = []
+    for f in range(int(frames)):
+        boxes, scores, idents = [], [], []
+        for i in range(n_images):
+            seen = rng.uniform(size=objects) >= p_miss
+            n_seen = int(seen.sum())
+            b = np.zeros((n_seen + int(false_positives), 6), dtype=np.float64)
+            b[:n_seen, 0:2] = (start[i] + f * vel[i])[seen] + noise * rng.standard_normal((n_seen, 2))
+            b[:n_seen, 2:4] = size[i][seen] + 0.5 * noise * rng.standard_normal((n_seen, 2))
+            b[:n_seen, 4], b[:n_seen, 5] = np.sin(yaw[i][seen]), np.cos(yaw[i][seen])
+            fy = rng.uniform(-math.pi, math.pi, int(false_positives))
+            b[n_seen:, 0:2] = rng.uniform(-extent, extent, (int(false_positives), 2))
+            b[n_seen:, 2] = rng.uniform(1.6, 2.4, int(false_positives))
+            b[n_seen:, 3] = rng.uniform(3.5, 5.5, int(false_positives))
+            b[n_seen:, 4], b[n_seen:, 5] = np.sin(fy), np.cos(fy)
+            s = np.concatenate([rng.uniform(0.5, 1.0, n_seen), rng.uniform(0.1, 0.5, int(false_positives))])
+            ident = np.concatenate([np.nonzero(seen)[0], np.full(int(false_positives), -1)])
+            boxes.append(b[:k])
+            scores.append(s[:k])
+            idents.append(ident[:k])
+        det = pad_detections(boxes, scores, k)
+        ident = np.full((n_images, k), -1, dtype=np.int32)
+        for i, row in enumerate(idents):
+            ident[i, :len(row)] = row
+        out.append((det, ident))
+    return out

@@ -1,0 +1,505 @@
+"""Multi-object tracking behind the detection tail: the last stage of the reference's det pipeline (train -> test ->
+track; its tools dump each agent's detections with --tracking and hand them to a SORT tracker, `make sort`).
+
+What the reference's tracker computes is RECALLED, NOT PINNED: the reference checkout holds no source.  The
+contract is this project's own -- SORT (Bewley et al., "Simple online and realtime tracking") with filterpy's
+constant-velocity Kalman filter as recalled -- and HostSort below is its normative statement: numpy / float64, every
+sum written out in a fixed order, only + - * / and sqrt (the hypot of postprocess._corners is written sqrt(s s + c c) here), so that the GPU
+kernel (dn_track_step, csrc/track.hip, built without contraction) reproduces it bit for bit.  Sort runs the same
+contract on the GPU, one workgroup per image, graph-capturable behind detect(); the full text of the contract is in
+include/disconet_hip.h.
+
+Every image of the agent-major batch (image = agent * B + b) is its own sequence with its own tracker.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .postprocess import MAX_TOP_K, _host
+
+MAX_TRACKS = 128          # track slots per image (M)
+MAX_DETS = 128            # valid detection rows considered per image and frame
+HEADER_BYTES = 64         # per image: int32 frame_count, next_id, n_tracks, status, 12 spare words (zero)
+RECORD_BYTES = 480        # per slot: float64 x[7], P[7][7]; int32 id, age, hits, hit_streak, time_since_update, 3 spare
+STATUS_BITS = ((1, "a birth found all max_tracks slots taken and was dropped"),
+               (2, "a detection row below its count was invalid (non-finite score or rectangle, or no positive width / "
+                   "height) and was ignored"),
+               (4, "more than %d valid detection rows in one image; the rows past the first %d were ignored"
+                   % (MAX_DETS, MAX_DETS)))
+
+_R = (1.0, 1.0, 10.0, 10.0)
+_Q = (1.0, 1.0, 1.0, 1.0, 0.01, 0.01, 0.0001)
+_P0 = (10.0, 10.0, 10.0, 10.0, 1e4, 1e4, 1e4)
+
+
+def _check_params(max_age, min_hits, iou_threshold, scale, max_tracks):
+    max_age, min_hits, max_tracks = int(max_age), int(min_hits), int(max_tracks)
+    iou_threshold, scale = float(iou_threshold), float(scale)
+    if max_age < 0 or min_hits < 0:
+        raise ValueError("max_age = %d, min_hits = %d: both must be >= 0" % (max_age, min_hits))
+    if not (np.isfinite(iou_threshold) and iou_threshold >= 0):
+        raise ValueError("iou_threshold = %r: must be finite and >= 0" % iou_threshold)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("scale = %r: must be finite and > 0" % scale)
+    if not 1 <= max_tracks <= MAX_TRACKS:
+        raise ValueError("max_tracks = %d: 1..%d are supported" % (max_tracks, MAX_TRACKS))
+    return max_age, min_hits, iou_threshold, scale, max_tracks
+
+
+def state_bytes(n_images, max_tracks):
+    """Bytes of the tracker state of n_images images (what dn_track_state_bytes returns)."""
+    return int(n_images) * (HEADER_BYTES + RECORD_BYTES * int(max_tracks))
+
+
+def _status_text(words):
+    out = []
+    for img, w in enumerate(words):
+        for bit, text in STATUS_BITS:
+            if int(w) & bit:
+                out.append("image %d: %s" % (img, text))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# the host reference: every operation in the order the kernel runs it
+# ---------------------------------------------------------------------------
+def _rect_of_state(x):
+    """(u, v, s, r, ...) -> (x1, y1, x2, y2): w = sqrt(s r), h = s / w."""
+    with np.errstate(all="ignore"):
+        w = np.sqrt(x[2] * x[3])
+        h = x[2] / w
+        return np.array([x[0] - w / 2.0, x[1] - h / 2.0, x[0] + w / 2.0, x[1] + h / 2.0], dtype=np.float64)
+
+
+def iou_rect(a, b):
+    """Axis-aligned IoU of (x1, y1, x2, y2) rectangles: 0 when the intersection is empty or the union <= 0."""
+    w = min(a[2], b[2]) - max(a[0], b[0])
+    h = min(a[3], b[3]) - max(a[1], b[1])
+    if not (w > 0 and h > 0):
+        return 0.0
+    inter = w * h
+    union = (a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - inter
+    return float(inter / union) if union > 0 else 0.0
+
+
+def hungarian_max(iou):
+    """The assignment that maximises the total of `iou` [T, D] (float64): shortest augmenting paths on cost = -iou.
+    Rows are the smaller side (the tracks when T <= D), processed in ascending order; potentials start at 0; the next
+    column is the unused one with the smallest reduced cost, the lowest index among equals; a row's search takes at
+    most (columns + 1) steps, so everything ends after rows x (columns + 1) steps whatever the numbers are.  Returns
+    the pairs [(t, d)] in column order."""
+    iou = np.asarray(iou, dtype=np.float64)
+    t_n, d_n = iou.shape
+    if t_n == 0 or d_n == 0:
+        return []
+    transposed = t_n > d_n
+    cost = -(iou.T if transposed else iou)
+    n, m = cost.shape
+    inf = np.inf
+    u = np.zeros(n + 1)
+    v = np.zeros(m + 1)
+    p = np.zeros(m + 1, dtype=np.int64)          # p[j] = row (1-based) that holds column j; column 0 is virtual
+    way = np.zeros(m + 1, dtype=np.int64)
+    for i in range(1, n + 1):
+        p[0] = i
+        j0 = 0
+        minv = np.full(m + 1, inf)
+        used = np.zeros(m + 1, dtype=bool)
+        found = False
+        for _ in range(m + 1):
+            used[j0] = True
+            i0 = p[j0]
+            free = ~used[1:]
+            cur = (cost[i0 - 1] - u[i0]) - v[1:]
+            better = free & (cur < minv[1:])
+            minv[1:][better] = cur[better]
+            way[1:][better] = j0
+            cand = np.where(free, minv[1:], inf)
+            j1 = int(np.argmin(cand)) + 1          # the first (lowest) column among equal minima
+            delta = cand[j1 - 1]
+            if not delta < inf:
+                break                              # nothing to reach (only with non-finite input): the row stays free
+            up = np.nonzero(used)[0]
+            u[p[up]] = u[p[up]] + delta
+            v[up] = v[up] - delta
+            minv[~used] = minv[~used] - delta
+            j0 = j1
+            if p[j0] == 0:
+                found = True
+                break
+        if not found:
+            p[0] = 0
+            continue
+        for _ in range(m + 1):
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+            if j0 == 0:
+                break
+    pairs = []
+    for j in range(1, m + 1):
+        if p[j] > 0:
+            pairs.append((j - 1, int(p[j]) - 1) if transposed else (int(p[j]) - 1, j - 1))
+    return pairs
+
+
+def associate(iou, iou_threshold):
+    """SORT's association on an IoU matrix [T, D] -> (track -> detection or -1 [T], path): "shortcut" when every row and
+    column holds at most one entry above the threshold (those entries are the matches), "hungarian" otherwise; either
+    way a pair with iou < iou_threshold is unmatched.  path is "none" when there is nothing to associate."""
+    iou = np.asarray(iou, dtype=np.float64)
+    t_n, d_n = iou.shape
+    match = np.full(t_n, -1, dtype=np.int64)
+    if t_n == 0 or d_n == 0:
+        return match, "none"
+    a = iou > iou_threshold
+    if a.sum(1).max() <= 1 and a.sum(0).max() <= 1:
+        for t, d in zip(*np.nonzero(a)):
+            match[t] = d
+        return match, "shortcut"
+    for t, d in hungarian_max(iou):
+        if not iou[t, d] < iou_threshold:
+            match[t] = d
+    return match, "hungarian"
+
+
+def _predict(trk):
+    x, P = trk["x"], trk["P"]
+    if x[6] + x[2] <= 0:
+        x[6] = 0.0
+    for i in range(3):                       # x = F x, F = I + ones at (0,4), (1,5), (2,6), in its sparse form
+        x[i] = x[i] + x[i + 4]
+    A = P.copy()                             # A = F P
+    A[0:3, :] = P[0:3, :] + P[4:7, :]
+    B = A.copy()                             # B = A F^T
+    B[:, 0:3] = A[:, 0:3] + A[:, 4:7]
+    for i in range(7):                       # + Q
+        B[i, i] = B[i, i] + _Q[i]
+    trk["P"] = B
+    trk["age"] += 1
+    if trk["tsu"] > 0:
+        trk["streak"] = 0
+    trk["tsu"] += 1
+
+
+def _update(trk, z):
+    x, P = trk["x"], trk["P"]
+    trk["tsu"] = 0
+    trk["hits"] += 1
+    trk["streak"] += 1
+    with np.errstate(all="ignore"):
+        y = [z[i] - x[i] for i in range(4)]
+        # S = P[:4, :4] + R: its lower triangle, factored L L^T in place
+        L = np.zeros((4, 4))
+        for i in range(4):
+            for j in range(i + 1):
+                s = P[i, j] + _R[i] if i == j else P[i, j]
+                for k in range(j):
+                    s = s - L[i, k] * L[j, k]
+                L[i, j] = np.sqrt(s) if i == j else s / L[j, j]
+        # K = P[:, :4] S^-1: per row r, L w = P[r, :4], then L^T k = w
+        K = np.zeros((7, 4))
+        for r in range(7):
+            w = [0.0] * 4
+            for i in range(4):
+                s = P[r, i]
+                for k in range(i):
+                    s = s - L[i, k] * w[k]
+                w[i] = s / L[i, i]
+            for i in (3, 2, 1, 0):
+                s = w[i]
+                for k in range(i + 1, 4):
+                    s = s - L[k, i] * K[r, k]
+                K[r, i] = s / L[i, i]
+        for r in range(7):
+            s = K[r, 0] * y[0]
+            for j in range(1, 4):
+                s = s + K[r, j] * y[j]
+            x[r] = x[r] + s
+        A = np.eye(7)                        # I - K H
+        A[:, 0:4] = A[:, 0:4] - K
+        AP = A[:, 0:1] * P[0:1, :]           # (A P)[r][c] = sum over k, left to right
+        for k in range(1, 7):
+            AP = AP + A[:, k:k + 1] * P[k:k + 1, :]
+        J = AP[:, 0:1] * A[:, 0][None, :]    # (AP A^T)[r][c] = sum over k of AP[r][k] A[c][k]
+        for k in range(1, 7):
+            J = J + AP[:, k:k + 1] * A[:, k][None, :]
+        KR = K * np.asarray(_R)[None, :]
+        G = KR[:, 0:1] * K[:, 0][None, :]    # (K R K^T)[r][c]
+        for j in range(1, 4):
+            G = G + KR[:, j:j + 1] * K[:, j][None, :]
+        trk["P"] = J + G
+
+
+def _corners(b):
+    """[K, 6] rows (x, y, w, h, sin, cos), float64 -> [K, 4, 2] corners: postprocess._corners operation for operation,
+    but for its hypot, written sqrt(s s + c c) -- a library hypot is not the same bits on every platform, sqrt is."""
+    n = np.maximum(np.sqrt(b[:, 4] * b[:, 4] + b[:, 5] * b[:, 5]), 1e-12)
+    s, c = b[:, 4] / n, b[:, 5] / n
+    dx, dy = b[:, 2] / 2.0, b[:, 3] / 2.0
+    lx, ly = np.stack([-dx, dx, dx, -dx], 1), np.stack([-dy, -dy, dy, dy], 1)
+    x = lx * c[:, None] - ly * s[:, None] + b[:, None, 0]
+    y = lx * s[:, None] + ly * c[:, None] + b[:, None, 1]
+    return np.stack([x, y], -1)
+
+
+def _measure(boxes, scores, count, scale):
+    """One image's rows -> (rows [D] of the valid detections used, rect [D, 4], z [D, 4], status bits)."""
+    k = boxes.shape[0]
+    c = min(max(int(count), 0), k)
+    status = 0
+    rows, rects, zs = [], [], []
+    if c:
+        with np.errstate(all="ignore"):
+            cr = _corners(np.asarray(boxes[:c], dtype=np.float64)) * scale       # [c, 4, 2]
+            x1, y1 = cr[:, :, 0].min(1), cr[:, :, 1].min(1)
+            x2, y2 = cr[:, :, 0].max(1), cr[:, :, 1].max(1)
+            w, h = x2 - x1, y2 - y1
+            ok = (np.isfinite(scores[:c]) & np.isfinite(x1) & np.isfinite(y1) & np.isfinite(x2) & np.isfinite(y2)
+                  & (w > 0) & (h > 0))
+            if not ok.all():
+                status |= 2
+            valid = np.nonzero(ok)[0]
+            if len(valid) > MAX_DETS:
+                status |= 4
+                valid = valid[:MAX_DETS]
+            for i in valid:
+                rows.append(int(i))
+                rects.append((x1[i], y1[i], x2[i], y2[i]))
+                zs.append((x1[i] + w[i] / 2.0, y1[i] + h[i] / 2.0, w[i] * h[i], w[i] / h[i]))
+    return rows, np.asarray(rects, dtype=np.float64).reshape(-1, 4), np.asarray(zs, dtype=np.float64).reshape(-1, 4), status
+
+
+class HostSort:
+    """The numpy / float64 reference of Sort: the same interface on host arrays, and the statement of the contract.
+
+    update(det): det = {"boxes" [N, K, 6], "scores" [N, K], "count" [N]} (numpy or tensors) -> numpy
+    {"rect" [N, M, 4] float64 (x1, y1, x2, y2 in scaled units), "id" [N, M] int32, "det" [N, M] int32 (the detection row
+    the track took this frame), "score" [N, M] float32, "count" [N] int32, "det_track" [N, K] int32}; rows at or past
+    count are 0 with id and det -1.  last_path[image] names the association path of the last frame ("none", "shortcut",
+    "hungarian")."""
+
+    def __init__(self, max_age=1, min_hits=3, iou_threshold=0.3, scale=1.0, max_tracks=MAX_TRACKS):
+        (self.max_age, self.min_hits, self.iou_threshold, self.scale,
+         self.max_tracks) = _check_params(max_age, min_hits, iou_threshold, scale, max_tracks)
+        self.images = None
+        self.last_path = []
+
+    def reset(self):
+        if self.images is not None:
+            self.images = [self._fresh() for _ in self.images]
+
+    @staticmethod
+    def _fresh():
+        return {"frame_count": 0, "next_id": 1, "status": 0, "tracks": []}
+
+    def update(self, det):
+        boxes = np.asarray(_host(det["boxes"]), dtype=np.float32)
+        scores = np.asarray(_host(det["scores"]), dtype=np.float32)
+        count = np.asarray(_host(det["count"])).reshape(-1)
+        n, k = scores.shape
+        if not 1 <= k <= MAX_TOP_K or tuple(boxes.shape) != (n, k, 6) or count.shape[0] != n:
+            raise ValueError("shapes: boxes %s scores %s count %s" % (boxes.shape, scores.shape, count.shape))
+        if self.images is None:
+            self.images = [self._fresh() for _ in range(n)]
+        if len(self.images) != n:
+            raise ValueError("the tracker holds %d images, this call has %d (reset() keeps the count)" % (len(self.images), n))
+        m = self.max_tracks
+        out = {"rect": np.zeros((n, m, 4), dtype=np.float64), "id": np.full((n, m), -1, dtype=np.int32),
+               "det": np.full((n, m), -1, dtype=np.int32), "score": np.zeros((n, m), dtype=np.float32),
+               "count": np.zeros(n, dtype=np.int32), "det_track": np.full((n, k), -1, dtype=np.int32)}
+        self.last_path = []
+        for img in range(n):
+            self.last_path.append(self._step(self.images[img], boxes[img], scores[img], count[img], img, out))
+        return out
+
+    def _step(self, st, boxes, scores, count, img, out):
+        m = self.max_tracks
+        st["frame_count"] += 1
+        rows, rects, zs, status = _measure(boxes, scores, count, self.scale)
+        st["status"] |= status
+        # predict; a track whose rectangle is not finite is deleted here
+        alive, trects = [], []
+        for trk in st["tracks"]:
+            _predict(trk)
+            r = _rect_of_state(trk["x"])
+            if np.isfinite(r).all():
+                alive.append(trk)
+                trects.append(r)
+        iou = np.zeros((len(alive), len(rows)), dtype=np.float64)
+        for t in range(len(alive)):
+            for d in range(len(rows)):
+                iou[t, d] = iou_rect(trects[t], rects[d])
+        match, path = associate(iou, self.iou_threshold)
+        taken = np.zeros(len(rows), dtype=bool)
+        for t, trk in enumerate(alive):
+            trk["det"] = -1
+            if match[t] >= 0:
+                d = int(match[t])
+                taken[d] = True
+                _update(trk, zs[d])
+                trk["det"] = rows[d]
+                out["det_track"][img, rows[d]] = trk["id"]
+        # deletions are decided first, then the births fill what is free, then the report
+        tracks = [trk for trk in alive if not trk["tsu"] > self.max_age]
+        for d in range(len(rows)):
+            if taken[d]:
+                continue
+            if len(tracks) >= m:
+                st["status"] |= 1
+                continue
+            P = np.zeros((7, 7), dtype=np.float64)
+            for i in range(7):
+                P[i, i] = _P0[i]
+            trk = {"x": np.array(list(zs[d]) + [0.0, 0.0, 0.0], dtype=np.float64), "P": P, "id": st["next_id"], "age": 0,
+                   "hits": 0, "streak": 0, "tsu": 0, "det": rows[d]}
+            st["next_id"] += 1
+            tracks.append(trk)
+            out["det_track"][img, rows[d]] = trk["id"]
+        c = 0
+        for trk in tracks:
+            if trk["tsu"] < 1 and (trk["streak"] >= self.min_hits or st["frame_count"] <= self.min_hits):
+                out["rect"][img, c] = _rect_of_state(trk["x"])
+                out["id"][img, c] = trk["id"]
+                out["det"][img, c] = trk["det"]
+                out["score"][img, c] = scores[trk["det"]]
+                c += 1
+        out["count"][img] = c
+        st["tracks"] = tracks
+        return path
+
+    def status_words(self):
+        """The status word of every image (numpy int32), without raising."""
+        return np.asarray([st["status"] for st in (self.images or [])], dtype=np.int32)
+
+    def status(self):
+        """Raise DnError naming the set status bits (a run is never silently truncated); returns 0 otherwise."""
+        text = _status_text(self.status_words())
+        if text:
+            raise _lib.DnError("Sort: " + "; ".join(text))
+        return 0
+
+    def state_bytes(self):
+        """The state in the device layout (numpy uint8), byte for byte what Sort.state_bytes() returns for the same run."""
+        m = self.max_tracks
+        imgs = self.images or []
+        buf = np.zeros((len(imgs), HEADER_BYTES + RECORD_BYTES * m), dtype=np.uint8)
+        for i, st in enumerate(imgs):
+            buf[i, :16] = np.asarray([st["frame_count"], st["next_id"], len(st["tracks"]), st["status"]],
+                                     dtype=np.int32).view(np.uint8)
+            for s, trk in enumerate(st["tracks"]):
+                o = HEADER_BYTES + RECORD_BYTES * s
+                buf[i, o:o + 56] = np.asarray(trk["x"], dtype=np.float64).view(np.uint8)
+                buf[i, o + 56:o + 448] = np.ascontiguousarray(trk["P"], dtype=np.float64).reshape(-1).view(np.uint8)
+                buf[i, o + 448:o + 468] = np.asarray([trk["id"], trk["age"], trk["hits"], trk["streak"], trk["tsu"]],
+                                                     dtype=np.int32).view(np.uint8)
+        return buf.reshape(-1)
+
+
+# ---------------------------------------------------------------------------
+# the same contract on the GPU (dn_track_step): one workgroup per image, kernel launches only
+# ---------------------------------------------------------------------------
+class Sort:
+    """SORT on the GPU behind detect(): update() after every frame enqueues dn_track_step on torch's current stream
+    (the state -- per image a header and max_tracks track records -- lives on the device, is allocated on first use and
+    is never read back), so forward + detect() + update() can be one captured graph (graph.GraphedStep).  HostSort is
+    the reference it equals bit for bit.
+
+    update(det) takes detect()'s dict (device tensors "boxes" [N, K, 6], "scores" [N, K], "count" [N]; K <= 1024, at
+    most 128 valid rows per image are used) and returns device tensors {"rect" [N, M, 4] float64, "id", "det" [N, M]
+    int32, "score" [N, M] float32, "count" [N] int32, "det_track" [N, K] int32} as HostSort does.  `scale` multiplies the
+    corners before the rectangle is taken (the tools pass 1 / voxel_size[0] = 4 px/m).  status() makes one small copy
+    and raises DnError naming the sticky status bits.
+
+    GraphedStep runs its step three times to warm up before it captures and those runs advance the tracker: call
+    reset() after constructing the GraphedStep, before the first replay that counts (as with MeanAP)."""
+
+    def __init__(self, max_age=1, min_hits=3, iou_threshold=0.3, scale=1.0, max_tracks=MAX_TRACKS):
+        (self.max_age, self.min_hits, self.iou_threshold, self.scale,
+         self.max_tracks) = _check_params(max_age, min_hits, iou_threshold, scale, max_tracks)
+        self.state = None            # uint8 [N * (HEADER_BYTES + RECORD_BYTES * M)] on the device
+        self.n_images = 0
+
+    def _inputs(self, det):
+        from .ops import _need_gpu
+        boxes, scores, count = det["boxes"], det["scores"], det["count"]
+        for t in (boxes, scores, count):
+            if not isinstance(t, torch.Tensor):
+                raise _lib.DnError("Sort.update needs device tensors (got %s); HostSort is the numpy reference"
+                                   % type(t).__name__)
+        _need_gpu(boxes, scores, count)
+        n, k = scores.shape
+        if not 1 <= k <= MAX_TOP_K:
+            raise ValueError("K = %d detection rows: 1..%d are supported" % (k, MAX_TOP_K))
+        if tuple(boxes.shape) != (n, k, 6) or count.numel() != n:
+            raise ValueError("shapes: boxes %s scores %s count %s" % (tuple(boxes.shape), tuple(scores.shape),
+                                                                      tuple(count.shape)))
+        return (boxes.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous(),
+                count.to(torch.int32).contiguous(), n, k)
+
+    def reset(self):
+        """Forget every track: frame_count 0, ids from 1 again, status 0 (one launch on the current stream)."""
+        if self.state is not None:
+            from .ops import _ptr, _stream
+            _lib.check(_lib.load().dn_track_reset(_ptr(self.state), self.n_images, self.max_tracks, _stream()),
+                       "dn_track_reset")
+
+    def update(self, det):
+        from .ops import _ptr, _stream
+        boxes, scores, count, n, k = self._inputs(det)
+        lib = _lib.load()
+        dev = scores.device
+        if self.state is None:
+            nbytes = int(lib.dn_track_state_bytes(n, self.max_tracks))
+            if nbytes != state_bytes(n, self.max_tracks):
+                raise _lib.DnError("dn_track_state_bytes(%d, %d) = %d" % (n, self.max_tracks, nbytes))
+            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.n_images = n
+            self.reset()
+        if n != self.n_images:
+            raise ValueError("the tracker holds %d images, this call has %d" % (self.n_images, n))
+        m = self.max_tracks
+        out = {"rect": torch.empty((n, m, 4), dtype=torch.float64, device=dev),
+               "id": torch.empty((n, m), dtype=torch.int32, device=dev),
+               "det": torch.empty((n, m), dtype=torch.int32, device=dev),
+               "score": torch.empty((n, m), dtype=torch.float32, device=dev),
+               "count": torch.empty((n,), dtype=torch.int32, device=dev),
+               "det_track": torch.empty((n, k), dtype=torch.int32, device=dev)}
+        _lib.check(lib.dn_track_step(_ptr(boxes), _ptr(scores), _ptr(count), n, k, m, self.max_age, self.min_hits,
+                                     self.iou_threshold, self.scale, _ptr(self.state), _ptr(out["rect"]), _ptr(out["id"]),
+                                     _ptr(out["det"]), _ptr(out["score"]), _ptr(out["count"]), _ptr(out["det_track"]),
+                                     _stream()), "dn_track_step")
+        return out
+
+    def status_words(self):
+        """The status word of every image (numpy int32): one small copy, waits for the device."""
+        if self.state is None:
+            return np.zeros(0, dtype=np.int32)
+        words = self.state.view(self.n_images, -1)[:, 12:16].contiguous().cpu().numpy()
+        return words.view(np.int32).reshape(-1).copy()
+
+    def status(self):
+        """Raise DnError naming the set status bits (a run is never silently truncated); returns 0 otherwise."""
+        text = _status_text(self.status_words())
+        if text:
+            raise _lib.DnError("Sort: " + "; ".join(text))
+        return 0
+
+    def state_bytes(self):
+        """A host copy of the whole state (numpy uint8); HostSort.state_bytes() is its reference."""
+        return self.state.cpu().numpy().copy() if self.state is not None else np.zeros(0, dtype=np.uint8)
+
+
+def mot_rows(out, frame):
+    """update()'s dict (host or device) -> per image the list of MOT lines `frame,id,x1,y1,w,h,score,-1,-1,-1` of the
+    reported tracks, in ascending id: the form the reference's tracking dump is recalled to have."""
+    rect, ids, score, count = _host(out["rect"]), _host(out["id"]), _host(out["score"]), _host(out["count"])
+    lines = []
+    for img in range(rect.shape[0]):
+        rows = []
+        for r in range(int(count[img])):
+            x1, y1, x2, y2 = (float(v) for v in rect[img, r])
+            rows.append("%d,%d,%.4f,%.4f,%.4f,%.4f,%.6f,-1,-1,-1" % (int(frame), int(ids[img, r]), x1, y1, x2 - x1,
+                                                                    y2 - y1, float(score[img, r])))
+        lines.append(rows)
+    return lines

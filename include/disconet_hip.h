@@ -605,6 +605,69 @@ int dn_assign_targets(const float* anchors, const float* gt_boxes, const int32_t
                       float* reg_targets, float* reg_mask, int32_t* matched_gt, double* best_iou, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Multi-object tracking behind the detection tail (disconet_amd/csrc/track.hip): one SORT step per image and call --
+ * Sort.update of Bewley et al.'s tracker with filterpy's constant-velocity Kalman filter.  What the reference's own
+ * tracker computes is recalled, not pinned: this contract is the project's own and
+ * tracking.HostSort (numpy / float64) is its normative statement, which the kernel equals bit for bit.
+ * Graph-capturable behind dn_detect: one kernel launch, no host synchronisation, no allocation; the launch depends on
+ * the shapes only.  Every image of the agent-major batch is its own sequence with its own tracker.
+ *   boxes [n][k][6], scores [n][k], count [n]: dn_detect's outputs, 1 <= k <= 1024; counts are clamped to [0, k].
+ *   1 <= max_tracks (M) <= 128, max_age >= 0, min_hits >= 0, iou_threshold finite and >= 0, scale finite and > 0.
+ *   All arithmetic is fp64 in the order written here, + - * / and sqrt only, never
+ *   contracted; a sum over an index runs left to right and starts from its first term.
+ *   Measurement.  The four corners of a row (x, y, w, h, sin, cos) as dn_detect's NMS takes them, in fp64 from the fp32
+ *   row, with (sin, cos) / max(sqrt(sin sin + cos cos), 1e-12) -- sqrt where postprocess._corners calls hypot, because a
+ *   library hypot does not round alike on the host and the device --, each multiplied by `scale`; x1, y1, x2, y2 = their
+ *   min / max; w = x2 - x1, h = y2 - y1; z = (x1 + w / 2, y1 + h / 2, w h, w / h).  A row is valid when it is below its
+ *   image's count, its score is finite, x1 .. y2 are finite and w > 0, h > 0.  An invalid row below count sets status
+ *   bit 1 and is ignored; only the first 128 valid rows in row order are used, a 129th sets status bit 2.
+ *   Track: x[7] = (u, v, s, r, u', v', s'), P[7][7], id, age, hits, hit_streak, time_since_update.
+ *   R = diag(1, 1, 10, 10), Q = diag(1, 1, 1, 1, .01, .01, .0001), initial P = diag(10, 10, 10, 10, 1e4, 1e4, 1e4),
+ *   initial x = (z, 0, 0, 0); rectangle of a state: w = sqrt(s r), h = s / w, (u - w/2, v - h/2, u + w/2, v + h/2).
+ *   Per image and call, in this order:
+ *   1. frame_count += 1.
+ *   2. Predict every track: if x[6] + x[2] <= 0 then x[6] = 0; x[i] += x[i + 4] (i < 3); P: rows 0..2 += rows 4..6,
+ *      then columns 0..2 += columns 4..6, then the diagonal += Q (F P F^T + Q in F's sparse form); age += 1; if
+ *      time_since_update > 0 then hit_streak = 0; time_since_update += 1.  A track whose rectangle has a non-finite member
+ *      is deleted here (the others keep their order).
+ *   3. IoU of every surviving track's rectangle a with every valid detection's b: w = min(a2, b2) - max(a0, b0),
+ *      h = min(a3, b3) - max(a1, b1); 0 unless w > 0 and h > 0; inter = w h;
+ *      union = (a2 - a0)(a3 - a1) + (b2 - b0)(b3 - b1) - inter; inter / union when union > 0, else 0.
+ *   4. Associate.  If every row and every column of (iou > iou_threshold) holds at most one true entry, those entries
+ *      are the matches.  Otherwise the assignment that maximises the total IoU, by shortest augmenting paths on
+ *      cost = -iou: rows are the smaller side (the tracks when T <= D), taken in ascending order; potentials start at 0;
+ *      reduced cost = (cost - u[row]) - v[column]; the next column is the unused one with the smallest reduced cost, the
+ *      lowest index among equals; a row's search ends after columns + 1 steps at the latest (and leaves the row free),
+ *      so the whole takes at most rows x (columns + 1) steps whatever the numbers are.  Either way a pair with
+ *      iou < iou_threshold is unmatched.
+ *   5. Update each matched track with its detection's z: time_since_update = 0, hits += 1, hit_streak += 1;
+ *      y = z - x[:4]; S = P[:4][:4] + R, of which the lower triangle is factored S = L L^T (row by row, column by column,
+ *      s = S[i][j] - sum_k<j L[i][k] L[j][k], subtracted one by one; L[i][i] = sqrt(s), L[i][j] = s / L[j][j]);
+ *      K = P[:][:4] S^-1 row by row: L w = P[r][:4] forwards, L^T k = w backwards (terms subtracted in ascending k, then
+ *      the division); x += K y; A = I - K H; P = (A P) A^T + (K R) K^T (Joseph form), every product a dense sum over
+ *      the inner index, (K R)[r][j] = K[r][j] R[j].
+ *   6. Deletions are decided: a track with time_since_update > max_age leaves, the others keep their order.  THEN every
+ *      unmatched valid detection, in row order, starts a track in the next free slot with id = next_id++ (ids start at
+ *      1 per image), hits = hit_streak = age = time_since_update = 0; a birth that finds all M slots taken sets status
+ *      bit 0, is dropped and takes no id.  So the slots a frame's deletions free are open to the same frame's births.
+ *   7. Report every track of the list with time_since_update < 1 and (hit_streak >= min_hits or frame_count <=
+ *      min_hits), in list order (ascending id): out_rect [n][M][4] (fp64, the state's rectangle, scaled units),
+ *      out_id [n][M], out_det [n][M] (the detection row it took or was born from this frame), out_score [n][M] (that
+ *      row's score), out_count [n].  Rows at or past out_count are 0 with id and det -1, on every call.
+ *      det_track [n][k]: the id each detection row was matched to or born as, -1 otherwise.
+ *   State (caller-owned, on the device, dn_track_state_bytes(n, M) = n (64 + 480 M) bytes, 0 for refused arguments): per
+ *   image 16 int32 {frame_count, next_id, n_tracks, status, 12 x 0}, then M records of 480 bytes {fp64 x[7], P[7][7] row
+ *   major; int32 id, age, hits, hit_streak, time_since_update, 3 x 0}; records at or past n_tracks are all zero.  Status
+ *   bits are sticky until dn_track_reset, which zeroes everything and sets next_id = 1.  Two runs write the same bytes.
+ * ------------------------------------------------------------------------ */
+size_t dn_track_state_bytes(int n_images, int max_tracks);
+int dn_track_reset(void* state, int n_images, int max_tracks, void* stream);
+int dn_track_step(const float* boxes, const float* scores, const int32_t* count, int n_images, int k, int max_tracks,
+                  int max_age, int min_hits, double iou_threshold, double scale, void* state, double* out_rect,
+                  int32_t* out_id, int32_t* out_det, float* out_score, int32_t* out_count, int32_t* det_track,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
