@@ -700,6 +700,15 @@ inline int out_dim(int in, int ksize, int stride) {
   return (in + 2 * pad - ksize) / stride + 1;
 }
 
+// tools and tests only (dn_conv_force_config / dn_conv_last_form): the forced tile id and the record launch<>() writes.
+// Host side, process-wide, not thread-safe.
+int g_force_cfg = -1;
+int g_entry = 0;            // the entry point about to launch: 0 dn_conv2d, 1 dn_conv2d_taps, 2 dn_conv2d_post1x1
+struct LastForm {
+  int entry, ks, stride, th, tw, bn, kc, math, post, grid, total_items;
+};
+LastForm g_last_form = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
 // MFMA-bound cost model: workgroups are dealt round-robin to the 256 CUs and a
 // CU runs its workgroups' MFMAs on the same 4 SIMDs, so time ~ ceil(blocks/256)
 // x (pixels x channels per tile) x the tile's measured bias; ties go to the
@@ -717,6 +726,10 @@ Cfg select_cfg(const dn_conv_desc& d) {
   if (d.ksize == 3 && d.stride == 2) { cand = c3s2; ncand = 1; }
   else if (d.ksize == 3) { cand = c3; ncand = 4; }
   else { cand = c1; ncand = 4; }
+  // a forced id is honoured only inside the layer's own candidate list: packed weights are tile-independent, so any
+  // candidate is legal for any shape of its family
+  for (int k = 0; k < ncand; ++k)
+    if ((int)cand[k] == g_force_cfg) return kCfgs[cand[k]];
   Cfg best = kCfgs[cand[0]];
   double best_cost = 1e300;
   for (int k = 0; k < ncand; ++k) {
@@ -904,6 +917,8 @@ int launch(ConvArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   // 256-pixel / fused tiles with 2-4 chunks (split-f16) and 3.4 % (exact fp32); "never" lands within 0.5 %.
   const long resident = (long)occupancy * kNumCUs;
   dim3 grid((unsigned)(total > resident ? resident : total));
+  // what dn_conv_last_form reports: the template parameters of this very instantiation
+  g_last_form = LastForm{g_entry, KS, STRIDE, TH, TW, BN, KC, MATH, POST, (int)grid.x, a.total_items};
   hipLaunchKernelGGL(kern, grid, dim3(T::NT), T::LDS_BYTES, stream, a);
   return dn::check_launch("conv_mfma_kernel");
 }
@@ -1039,6 +1054,7 @@ extern "C" int dn_conv2d_post1x1(const dn_conv_desc* d, const dn_post1x1_desc* p
   a.c_out2 = p->c_out2; a.relu2 = p->relu2; a.split2 = p->split; a.ldo_b = p->ldo_b;
   // 8x32-pixel workgroups (4 MFMA tiles per wave): +2.9 % per step over 8x16 (weights staged and
   // barriers paid half as often per pixel)
+  g_entry = 2;
   return launch<3, 1, 8, 32, 64, 16, 2, 2, 4, 1, 0, 1, 1>(a, *d, (hipStream_t)stream);
 }
 
@@ -1079,6 +1095,21 @@ int conv2d_impl(const dn_conv_desc* d, const float* src0, const float* src1, con
                 const float* shift, float* out, int tap_mask, long out_img, int out_row, int out_px, void* stream);
 }
 
+extern "C" int dn_conv_force_config(int cfg) {
+  DN_REQUIRE(cfg >= -1 && cfg < CFG_COUNT, "conv force config: id %d (-1 = off, 0..%d)", cfg, CFG_COUNT - 1);
+  g_force_cfg = cfg;
+  return DN_OK;
+}
+
+extern "C" int dn_conv_last_form(int* out, int n) {
+  constexpr int kInts = (int)(sizeof(LastForm) / sizeof(int));
+  static_assert(sizeof(LastForm) == 11 * sizeof(int), "dn_conv_last_form: the record is 11 ints");
+  DN_REQUIRE(out && n > 0, "conv last form: null pointer / no room");
+  const int* f = reinterpret_cast<const int*>(&g_last_form);
+  for (int i = 0; i < n && i < kInts; ++i) out[i] = f[i];
+  return kInts;
+}
+
 extern "C" int dn_conv2d(const dn_conv_desc* d, const float* src0, const float* src1,
                          const float* packed, const float* scale, const float* shift,
                          float* out, void* stream) {
@@ -1104,6 +1135,7 @@ int conv2d_impl(const dn_conv_desc* d, const float* src0, const float* src1, con
   ConvArgs a;
   if (int rc = fill_args(d, src0, src1, packed, scale, shift, out, a)) return rc;
   a.tap_mask = tap_mask;
+  g_entry = out_img > 0 ? 1 : 0;
   if (out_img > 0) {
     a.out_img = out_img; a.out_row = out_row; a.out_px = out_px;
     a.vec_out = a.vec_out && out_px % 4 == 0 && out_row % 4 == 0 && out_img % 4 == 0;

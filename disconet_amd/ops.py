@@ -253,6 +253,29 @@ def conv2d_taps(d, src0, packed, scale, shift, out_view, tap_mask):
     return out_view
 
 
+NHWC_CFG = {"T3_256x32": 0, "T3_256x64": 1, "T3_128x64": 2, "T3_64x64": 3, "T3S2_64x64": 4, "T1_256x32": 5, "T1_256x64": 6,
+            "T1_128x128": 7, "T1_64x64": 8}      # enum CfgId of conv_mfma.hip
+NHWC_FORM_FIELDS = ("entry", "KS", "STRIDE", "TH", "TW", "BN", "KC", "MATH", "POST", "grid", "total_items")
+
+
+def nhwc_force_config(cfg):
+    """tools and tests: run tile `cfg` (a key or value of NHWC_CFG; None / -1 = off) in dn_conv2d / dn_conv2d_taps wherever
+    it is one of the layer's own candidates (dn_conv_force_config).  Process-wide, not thread-safe."""
+    cfg = -1 if cfg is None else NHWC_CFG.get(cfg, cfg)
+    check(_lib.load().dn_conv_force_config(int(cfg)), "dn_conv_force_config")
+
+
+def nhwc_last_form():
+    """-> dict: which kernel the last launch of the fp32-NHWC engine ran (dn_conv_last_form; tools and tests): the entry
+    point (0 dn_conv2d, 1 dn_conv2d_taps, 2 dn_conv2d_post1x1), the template parameters, grid and work items.  Host-side
+    record, not thread-safe."""
+    buf = (ctypes.c_int * len(NHWC_FORM_FIELDS))()
+    n = _lib.load().dn_conv_last_form(buf, len(NHWC_FORM_FIELDS))
+    if n != len(NHWC_FORM_FIELDS):
+        raise _lib.DnError("dn_conv_last_form: %d fields, expected %d" % (n, len(NHWC_FORM_FIELDS)))
+    return dict(zip(NHWC_FORM_FIELDS, (int(v) for v in buf)))
+
+
 # ---------------------------------------------------------------------------
 # split-planar (SP) activations and the SP conv engine
 # ---------------------------------------------------------------------------

@@ -29,7 +29,7 @@
  *     thread-local message for the last failing call on this thread;
  *   - re-entrant.  Process-wide state is limited to launch-time caches filled on first use
  *     (kernel attributes / occupancy per instantiation), the tools-only hooks dn_spconv_force_config(),
- *     dn_spconv_set_upmode(), dn_spconv_last_form() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
+ *     dn_spconv_set_upmode(), dn_spconv_last_form(), dn_conv_force_config(), dn_conv_last_form() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
  *     DN_WARP_GATHER_LEGACY (environment, read once: the other side of a bitwise / agreement test).
  */
 #ifndef DISCONET_HIP_H
@@ -190,7 +190,9 @@ typedef struct dn_conv_desc {
   int32_t ksize;         /* 1 or 3 (padding = ksize/2) */
   int32_t stride;        /* 1 or 2 */
   int32_t relu;          /* apply ReLU after the affine */
-  int32_t ld0, ld1, ldo; /* floats per pixel of src0 / src1 / out (>= channels) */
+  int32_t ld0, ld1, ldo; /* floats per pixel of src0 / src1 / out (>= channels).  With ld > channels the
+                            columns beyond a source's own must hold finite values in math 0: the last
+                            chunk reads them against zero weights. */
   int32_t math;          /* 0 = exact fp32 MFMA; 1 = split-f16 (x = hi + lo halves, hi*hi + hi*lo +
                             lo*hi on the f16 MFMA, fp32 accumulate, ~2^-22 per product).  The
                             packed weights are math-specific: pack and run with the same value. */
@@ -395,6 +397,22 @@ int dn_spconv_set_upmode(int mode);
  * and returns 20.  A call that fails its argument checks before the launch leaves the record as it was.
  * Process-wide, not thread-safe (like dn_spconv_force_config). */
 int dn_spconv_last_form(int* out, int n);
+
+/* tools and tests only, the fp32-NHWC engine (dn_conv2d, dn_conv2d_taps): run tile configuration `cfg` -- a CfgId of
+ * conv_mfma.hip: 0 T3_256x32, 1 T3_256x64, 2 T3_128x64, 3 T3_64x64, 4 T3S2_64x64, 5 T1_256x32, 6 T1_256x64,
+ * 7 T1_128x128, 8 T1_64x64 -- instead of the cost model's choice; -1 = off.  Honoured only where the id is one of the
+ * layer's own candidates (3x3 stride 1: 0..3, 3x3 stride 2: 4, 1x1: 5..8), otherwise the cost model decides as without
+ * it; packed weights do not depend on the tile.  dn_conv2d_post1x1 has one form and ignores it.
+ * Process-wide, not thread-safe. */
+int dn_conv_force_config(int cfg);
+/* tools and tests only: which kernel did the last launch of the fp32-NHWC engine run?  Written by the launcher itself
+ * (host side).  Fills out[0 .. min(n, 11)) with
+ *   0 entry (0 = dn_conv2d, 1 = dn_conv2d_taps, 2 = dn_conv2d_post1x1; -1 = no launch yet)
+ *   1..8  KS, STRIDE, TH, TW, BN, KC, MATH, POST -- the template parameters of the conv_mfma_kernel instantiation
+ *   9 grid, 10 total_items -- workgroups and work items of the launch (grid < total_items: the persistent loop ran)
+ * and returns 11.  A call that fails its argument checks before the launch leaves the record as it was.
+ * Process-wide, not thread-safe. */
+int dn_conv_last_form(int* out, int n);
 
 /* ------------------------------------------------------------------------
  * K4 -- pose-based two-pass bilinear warp of neighbour feature maps.

@@ -37,6 +37,14 @@ static int errors_only(void) {
   int dims[3] = {256, 256, 13};
   CHECK(dn_voxel_compact_workspace(dims) == ((256 * 256 * 13 + 1023) / 1024) * sizeof(int), "workspace");
   CHECK(dn_post1x1_packed_floats() == 64 * 64, "post1x1 size");
+  /* the fp32-NHWC engine's tools hooks: ids -1 .. 8, an 11-int record */
+  {
+    int form[11];
+    CHECK(dn_conv_force_config(9) == DN_ERR_ARG && dn_conv_force_config(-2) == DN_ERR_ARG, "force config: bad id accepted");
+    CHECK(dn_conv_force_config(3) == DN_OK && dn_conv_force_config(-1) == DN_OK, "force config: %s", dn_last_error());
+    CHECK(dn_conv_last_form(NULL, 11) == DN_ERR_ARG, "last form: null accepted");
+    CHECK(dn_conv_last_form(form, 11) == 11, "last form: 11 fields");
+  }
   /* training header: plain C as well, same error convention */
   d.math = 0;
   CHECK(dn_conv_wgrad_workspace(&d) > 0, "wgrad workspace");
@@ -143,6 +151,30 @@ static int gpu_conv(int math) {
   for (size_t i = 0; i < ny; ++i) { const double e = fabs((double)y[i] - ref[i]); if (e > err) err = e; }
   printf("C ABI conv3x3 math=%d: max abs err %.3e\n", math, err);
   CHECK(err <= 1e-4, "conv error too large");
+  /* dn_conv_last_form names that launch; dn_conv_force_config(2 = T3_128x64) moves it onto the 8 x 16 x 64 tile, whose
+   * result is held to the same reference; an id of another family (4 = T3S2_64x64) leaves the choice to the cost model */
+  {
+    int form[11];
+    CHECK(dn_conv_last_form(form, 11) == 11 && form[0] == 0 && form[1] == 3 && form[2] == 1 && form[7] == math && form[8] == 0 &&
+          form[9] > 0 && form[9] <= form[10], "last form after dn_conv2d: entry %d KS %d", form[0], form[1]);
+    CHECK(dn_conv_force_config(2) == DN_OK, "force: %s", dn_last_error());
+    const int rc = dn_conv2d(&d, dx_, NULL, dp, dsc, dsh, dy_, NULL);
+    dn_conv_force_config(-1);
+    CHECK(rc == DN_OK, "conv (forced): %s", dn_last_error());
+    HIP(hipDeviceSynchronize());
+    HIP(hipMemcpy(y, dy_, ny * 4, hipMemcpyDeviceToHost));
+    CHECK(dn_conv_last_form(form, 11) == 11 && form[3] == 8 && form[4] == 16 && form[5] == 64, "forced T3_128x64 ran %dx%dx%d", form[3], form[4], form[5]);
+    double e3 = 0;
+    for (size_t i = 0; i < ny; ++i) { const double e = fabs((double)y[i] - ref[i]); if (e > e3) e3 = e; }
+    CHECK(e3 <= 1e-4, "forced-tile conv error too large");
+    CHECK(dn_conv_force_config(4) == DN_OK, "force: %s", dn_last_error());      /* a stride-2 id: not a candidate here */
+    const int rc2 = dn_conv2d(&d, dx_, NULL, dp, dsc, dsh, dy_, NULL);
+    dn_conv_force_config(-1);
+    CHECK(rc2 == DN_OK, "conv (foreign id): %s", dn_last_error());
+    HIP(hipDeviceSynchronize());
+    HIP(hipMemcpy(y, dy_, ny * 4, hipMemcpyDeviceToHost));
+    CHECK(dn_conv_last_form(form, 11) == 11 && form[2] == 1, "a foreign forced id changed the stride");
+  }
   /* dn_conv2d_taps: every tap enabled and the dense output strides == dn_conv2d, bit for bit; the centre tap alone
    * (mask 1 << 4) into every other pixel column of a twice-as-wide buffer == the 1x1 conv of the centre weights */
   {
