@@ -150,6 +150,10 @@ SIGNATURES = {
     "dn_track_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "dn_track_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dn_mot_state_bytes": (c_size_t, [c_int, c_int]),
+    "dn_mot_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "dn_mot_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                            c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -295,7 +295,7 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
 # detection sequences for the tracker (tracking.Sort / HostSort)
 # ---------------------------------------------------------------------------
 def make_track_sequence(frames, n_images, seed=0, objects=6, width=None, noise=0.05, p_miss=0.1, false_positives=1,
-                        extent=24.0, speed=0.4, spread=0.05):
+                        extent=24.0, speed=0.4, spread=0.05, truth=False):
     """Seeded detections of moving boxes, frame by frame: per image `objects` car-sized boxes (w ~ U(1.6, 2.4),
     l ~ U(3.5, 5.5), any yaw) start on a grid of pitch 8 m (centres jittered by at most 1 m) and move at constant
     velocity -- a flow of at most `speed` m per frame shared by the image plus at most `spread` m per frame of their own,
@@ -305,8 +305,12 @@ def make_track_sequence(frames, n_images, seed=0, objects=6, width=None, noise=0
     the objects in identity order, then the false positives.  Returns a list of `frames` pairs (det, ident):
     det = postprocess.pad_detections' dict {"boxes" [N, K, 6] float32, "scores" [N, K] float32, "count" [N] int32} (numpy;
     K = `width`, default objects + false_positives, at least 1), ident [N, K] int32 = the true identity of each row
-    (0 .. objects - 1), -1 for a false positive and for the padding."""
-    from .postprocess import pad_detections
+    (0 .. objects - 1), -1 for a false positive and for the padding.
+    With truth=True the list holds triples (det, ident, gt): gt = {"boxes" [N, G, 6] float32, "ids" [N, G] int32, "count"
+    [N] int32} (G = max(objects, 1)), the noise-free boxes of ALL objects that frame in identity order, ids
+    0 .. objects - 1 -- what tracking.ClearMot takes as ground truth.  They follow from the start / velocity / size / yaw
+    already drawn: no extra random draw, so det and ident are the same arrays either way."""
+    from .postprocess import pad_boxes, pad_detections
     rng = np.random.RandomState(int(seed))
     k = max(1, int(objects) + int(false_positives)) if width is None else int(width)
     cells = max(1, int(2 * extent // 8.0))
@@ -345,5 +349,18 @@ def make_track_sequence(frames, n_images, seed=0, objects=6, width=None, noise=0
         ident = np.full((n_images, k), -1, dtype=np.int32)
         for i, row in enumerate(idents):
             ident[i, :len(row)] = row
-        out.append((det, ident))
+        if not truth:
+            out.append((det, ident))
+            continue
+        true = []
+        for i in range(n_images):
+            b = np.zeros((int(objects), 6), dtype=np.float64)
+            b[:, 0:2] = start[i] + f * vel[i]
+            b[:, 2:4] = size[i]
+            b[:, 4], b[:, 5] = np.sin(yaw[i]), np.cos(yaw[i])
+            true.append(b)
+        gt_boxes, gt_count = pad_boxes(true, max(1, int(objects)))
+        gt_ids = np.zeros((n_images, max(1, int(objects))), dtype=np.int32)
+        gt_ids[:, :int(objects)] = np.arange(int(objects), dtype=np.int32)[None, :]
+        out.append((det, ident, {"boxes": gt_boxes, "ids": gt_ids, "count": gt_count}))
     return out

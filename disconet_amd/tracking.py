@@ -10,6 +10,10 @@ contract on the GPU, one workgroup per image, graph-capturable behind detect(); 
 include/disconet_hip.h.
 
 Every image of the agent-major batch (image = agent * B + b) is its own sequence with its own tracker.
+
+The stage behind it (`make eval`) is here too: the CLEAR MOT figures of the tracks against ground-truth boxes with
+identities -- HostClearMot states that contract in the same way, ClearMot runs it on the GPU (dn_mot_step,
+csrc/mot_eval.hip), graph-capturable behind Sort.update().
 """
 import numpy as np
 import torch
@@ -503,3 +507,353 @@ def mot_rows(out, frame):
                                                                     y2 - y1, float(score[img, r])))
         lines.append(rows)
     return lines
+
+
+# ---------------------------------------------------------------------------
+# CLEAR MOT evaluation of the tracks (dn_mot_step, csrc/mot_eval.hip): the stage behind the tracker
+# ---------------------------------------------------------------------------
+MAX_GT_ROWS = 1024        # ground-truth rows per image (G)
+MAX_GT_USED = 128         # valid ground-truth rows used per image and frame
+MAX_GT_IDS = 1024         # upper limit of max_gt_ids
+MOT_HEADER_BYTES = 64     # per image: int64 frames, TP, FP, FN, IDSW; float64 motp_sum; int32 status; 12 spare bytes (zero)
+MOT_RECORD_BYTES = 32     # per identity: int32 last, pst, frames_present, frames_matched, segments, 3 spare (zero)
+MOT_CONTINUITY = 1000.0   # added to the score of the pair an identity held in the previous frame
+MOT_STATUS_BITS = ((1, "more than %d valid ground-truth rows in one image; the rows past the first %d were ignored"
+                       % (MAX_GT_USED, MAX_GT_USED)),
+                   (2, "a ground-truth row below its count was invalid (non-finite rectangle, or no positive width / "
+                       "height) and was ignored"),
+                   (4, "a ground-truth id was outside 0 .. max_gt_ids - 1 and its row was ignored"),
+                   (8, "a ground-truth id came twice in one frame; the lower row was kept"))
+MOT_FIGURES = ("MOTA", "MOTP", "TP", "FP", "FN", "IDSW", "Frag", "MT", "PT", "ML")
+
+
+def _check_mot_params(batch_size, iou_threshold, scale, max_gt_ids):
+    batch_size, max_gt_ids = int(batch_size), int(max_gt_ids)
+    iou_threshold, scale = float(iou_threshold), float(scale)
+    if batch_size < 1:
+        raise ValueError("batch_size = %d: must be positive" % batch_size)
+    if not (np.isfinite(iou_threshold) and 0.0 < iou_threshold <= 1.0):
+        raise ValueError("iou_threshold = %r: must be in (0, 1]" % iou_threshold)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("scale = %r: must be finite and > 0" % scale)
+    if not 1 <= max_gt_ids <= MAX_GT_IDS:
+        raise ValueError("max_gt_ids = %d: 1..%d are supported" % (max_gt_ids, MAX_GT_IDS))
+    return batch_size, iou_threshold, scale, max_gt_ids
+
+
+def mot_state_bytes(n_images, max_gt_ids):
+    """Bytes of the evaluation state of n_images images (what dn_mot_state_bytes returns)."""
+    return int(n_images) * (MOT_HEADER_BYTES + MOT_RECORD_BYTES * int(max_gt_ids))
+
+
+def _mot_status_text(words):
+    out = []
+    for img, w in enumerate(words):
+        for bit, text in MOT_STATUS_BITS:
+            if int(w) & bit:
+                out.append("image %d: %s" % (img, text))
+    return out
+
+
+def _mot_figures(c):
+    """Counters {"TP", "FP", "FN", "IDSW", "Frag", "MT", "PT", "ML", "motp_sum", "frames"} -> the CLEAR figures."""
+    tp, fp, fn, idsw = c["TP"], c["FP"], c["FN"], c["IDSW"]
+    out = {"MOTA": float(tp - fp - idsw) / float(max(1, tp + fn)), "MOTP": float(c["motp_sum"]) / float(max(1, tp)),
+           "Recall": float(tp) / float(max(1, tp + fn)), "Precision": float(tp) / float(max(1, tp + fp))}
+    out.update({key: int(c[key]) for key in ("TP", "FP", "FN", "IDSW", "Frag", "MT", "PT", "ML", "frames")})
+    return out
+
+
+def mot_figures_from_state(buf, n_images, max_gt_ids, batch_size, who="ClearMot"):
+    """The state bytes (numpy uint8, device layout) -> {"overall": figures, "per_agent": [figures], "per_image":
+    [figures]}; float64 on the host, sums over images taken in image order.  Raises DnError naming any status bit."""
+    per = MOT_HEADER_BYTES + MOT_RECORD_BYTES * max_gt_ids
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(n_images, per)
+    text = _mot_status_text(buf[:, 48:52].copy().view(np.int32).reshape(-1))
+    if text:
+        raise _lib.DnError("%s: %s" % (who, "; ".join(text)))
+    images = []
+    for i in range(n_images):
+        ints = buf[i, :40].copy().view(np.int64)
+        rec = buf[i, MOT_HEADER_BYTES:].copy().view(np.int32).reshape(max_gt_ids, 8)
+        c = {"frames": int(ints[0]), "TP": int(ints[1]), "FP": int(ints[2]), "FN": int(ints[3]), "IDSW": int(ints[4]),
+             "motp_sum": float(buf[i, 40:48].copy().view(np.float64)[0]), "Frag": 0, "MT": 0, "PT": 0, "ML": 0}
+        for last, pst, present, matched, segments in rec[:, :5].tolist():
+            c["Frag"] += max(segments - 1, 0)
+            if present > 0:
+                ratio = float(matched) / float(present)
+                c["MT" if ratio > 0.8 else ("ML" if ratio < 0.2 else "PT")] += 1
+        images.append(c)
+
+    def total(group):
+        s = {key: 0 for key in ("frames", "TP", "FP", "FN", "IDSW", "Frag", "MT", "PT", "ML")}
+        s["motp_sum"] = 0.0
+        for c in group:
+            for key in s:
+                s[key] = s[key] + c[key]
+        return s
+
+    agents = -(-n_images // batch_size)
+    return {"overall": _mot_figures(total(images)),
+            "per_agent": [_mot_figures(total(images[a * batch_size:(a + 1) * batch_size])) for a in range(agents)],
+            "per_image": [_mot_figures(c) for c in images]}
+
+
+def mot_line(name, figures):
+    """One line of the evaluation tool: the CLEAR figures of `name`."""
+    return "%s: MOTA %.4f MOTP %.4f TP %d FP %d FN %d IDSW %d Frag %d MT %d PT %d ML %d" % (
+        (name,) + tuple(figures[key] for key in MOT_FIGURES))
+
+
+def _gt_measure(boxes, ids, count, scale, max_gt_ids):
+    """One image's ground truth -> (rows, rect [V, 4], ids) of the rows used, status bits.  In this order: the rectangle
+    of the scaled corners (_measure's rule) must be finite with positive width and height (else bit 2); the id must be in
+    0 .. max_gt_ids - 1 (else bit 4); the first 128 such rows are kept (a 129th sets bit 1); of the kept rows, one whose id
+    a lower kept row carries is dropped (bit 8)."""
+    g = boxes.shape[0]
+    c = min(max(int(count), 0), g)
+    status = 0
+    rows, rects, idents = [], [], []
+    if c:
+        with np.errstate(all="ignore"):
+            cr = _corners(np.asarray(boxes[:c], dtype=np.float64)) * scale
+            x1, y1 = cr[:, :, 0].min(1), cr[:, :, 1].min(1)
+            x2, y2 = cr[:, :, 0].max(1), cr[:, :, 1].max(1)
+            ok = (np.isfinite(x1) & np.isfinite(y1) & np.isfinite(x2) & np.isfinite(y2) & (x2 - x1 > 0) & (y2 - y1 > 0))
+        kept = 0
+        for r in range(c):
+            if not ok[r]:
+                status |= 2
+                continue
+            ident = int(ids[r])
+            if not 0 <= ident < max_gt_ids:
+                status |= 4
+                continue
+            if kept >= MAX_GT_USED:
+                status |= 1
+                continue
+            kept += 1
+            if ident in idents:
+                status |= 8
+                continue
+            rows.append(r)
+            rects.append((x1[r], y1[r], x2[r], y2[r]))
+            idents.append(ident)
+    return rows, np.asarray(rects, dtype=np.float64).reshape(-1, 4), idents, status
+
+
+def _mot_tracks(tracks):
+    rect = np.asarray(_host(tracks["rect"]), dtype=np.float64)
+    ids = np.asarray(_host(tracks["id"]), dtype=np.int32)
+    count = np.asarray(_host(tracks["count"])).reshape(-1)
+    return rect, ids, count
+
+
+class HostClearMot:
+    """The numpy / float64 reference of ClearMot and the statement of its contract (the CLEAR MOT metrics as the MOT
+    benchmark's evaluation kit computes them, recalled, not pinned; the full text is in include/disconet_hip.h).
+
+    update(tracks, gt): tracks = Sort.update()'s dict (the first `count` rows of "rect" [N, M, 4] and "id" [N, M], M <=
+    128), gt = {"boxes" [N, G, 6] float32 (MeanAP's ground-truth rows), "ids" [N, G] int32, "count" [N]}, G <= 1024 ->
+    numpy {"match" [N, G] int32 (the track id a ground-truth row took, else -1), "iou" [N, G] float64 (that pair's IoU,
+    else 0), "flags" [N, G] int32 (bit 0 matched, bit 1 id switch, bit 2 segment start)}.  Every image is its own
+    sequence.  A reported track whose rectangle has a non-finite member overlaps nothing (IoU 0: a false positive)."""
+
+    def __init__(self, batch_size, iou_threshold=0.5, scale=1.0, max_gt_ids=256):
+        self.batch_size, self.iou_threshold, self.scale, self.max_gt_ids = _check_mot_params(batch_size, iou_threshold,
+                                                                                             scale, max_gt_ids)
+        self.images = None
+        self.last_score = []         # per image the score matrix [valid ground truths, tracks] of the last frame
+
+    def _fresh(self):
+        return {"frames": 0, "TP": 0, "FP": 0, "FN": 0, "IDSW": 0, "motp_sum": 0.0, "status": 0,
+                "rec": np.zeros((self.max_gt_ids, 8), dtype=np.int32)}
+
+    def reset(self):
+        if self.images is not None:
+            self.images = [self._fresh() for _ in self.images]
+
+    def update(self, tracks, gt):
+        rect, tid, tcount = _mot_tracks(tracks)
+        boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
+        gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
+        gcount = np.asarray(_host(gt["count"])).reshape(-1)
+        n, m = tid.shape
+        g = gids.shape[1] if gids.ndim == 2 else 0
+        if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
+                or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
+            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
+                rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+        if self.images is None:
+            self.images = [self._fresh() for _ in range(n)]
+        if len(self.images) != n:
+            raise ValueError("the evaluation holds %d images, this call has %d (reset() keeps the count)"
+                             % (len(self.images), n))
+        out = {"match": np.full((n, g), -1, dtype=np.int32), "iou": np.zeros((n, g), dtype=np.float64),
+               "flags": np.zeros((n, g), dtype=np.int32)}
+        self.last_score = []
+        for img in range(n):
+            self._step(self.images[img], rect[img], tid[img], tcount[img], boxes[img], gids[img], gcount[img], img, out)
+        return out
+
+    def _step(self, st, rect, tid, tcount, boxes, gids, gcount, img, out):
+        m = tid.shape[0]
+        k = min(max(int(tcount), 0), m)
+        rec = st["rec"]
+        st["frames"] += 1
+        rows, rects, idents, status = _gt_measure(boxes, gids, gcount, self.scale, self.max_gt_ids)
+        st["status"] |= status
+        v = len(rows)
+        finite = [bool(np.isfinite(rect[t]).all()) for t in range(k)]
+        score = np.zeros((v, k), dtype=np.float64)
+        for a in range(v):
+            pst = int(rec[idents[a], 1])
+            for t in range(k):
+                iou = iou_rect(rects[a], rect[t]) if finite[t] else 0.0
+                if iou < self.iou_threshold:
+                    continue
+                score[a, t] = iou + MOT_CONTINUITY if int(tid[t]) == pst else iou
+        self.last_score.append(score)
+        took = [-1] * v
+        for a, t in hungarian_max(score):
+            if score[a, t] > 0:
+                took[a] = t
+        was = rec[:, 1].copy()
+        rec[:, 1] = 0                                   # pst: this frame's matches only
+        matched = 0
+        for a in range(v):                              # ascending ground-truth row: the order of motp_sum
+            ident = idents[a]
+            rec[ident, 2] += 1
+            if took[a] < 0:
+                continue
+            t = took[a]
+            track = int(tid[t])
+            iou = iou_rect(rects[a], rect[t])
+            flags = 1
+            if rec[ident, 0] != 0 and rec[ident, 0] != track:
+                flags |= 2
+                st["IDSW"] += 1
+            if was[ident] == 0:
+                flags |= 4
+                rec[ident, 4] += 1
+            rec[ident, 0] = track
+            rec[ident, 1] = track
+            rec[ident, 3] += 1
+            st["motp_sum"] = st["motp_sum"] + iou
+            matched += 1
+            out["match"][img, rows[a]] = track
+            out["iou"][img, rows[a]] = iou
+            out["flags"][img, rows[a]] = flags
+        st["TP"] += matched
+        st["FN"] += v - matched
+        st["FP"] += k - matched
+
+    def status_words(self):
+        """The status word of every image (numpy int32), without raising."""
+        return np.asarray([st["status"] for st in (self.images or [])], dtype=np.int32)
+
+    def state_bytes(self):
+        """The state in the device layout (numpy uint8), byte for byte what ClearMot.state_bytes() returns."""
+        imgs = self.images or []
+        buf = np.zeros((len(imgs), MOT_HEADER_BYTES + MOT_RECORD_BYTES * self.max_gt_ids), dtype=np.uint8)
+        for i, st in enumerate(imgs):
+            buf[i, :40] = np.asarray([st["frames"], st["TP"], st["FP"], st["FN"], st["IDSW"]], dtype=np.int64).view(np.uint8)
+            buf[i, 40:48] = np.asarray([st["motp_sum"]], dtype=np.float64).view(np.uint8)
+            buf[i, 48:52] = np.asarray([st["status"]], dtype=np.int32).view(np.uint8)
+            buf[i, MOT_HEADER_BYTES:] = np.ascontiguousarray(st["rec"]).reshape(-1).view(np.uint8)
+        return buf.reshape(-1)
+
+    def compute(self):
+        """{"overall", "per_agent", "per_image"}: per entry MOTA, MOTP, Recall, Precision, TP, FP, FN, IDSW, Frag, MT, PT,
+        ML, frames.  Raises DnError naming any sticky status bit."""
+        return mot_figures_from_state(self.state_bytes(), len(self.images or []), self.max_gt_ids, self.batch_size,
+                                      "HostClearMot")
+
+
+class ClearMot:
+    """CLEAR MOT evaluation on the GPU behind Sort.update(): update() after every frame enqueues dn_mot_step on torch's
+    current stream (the state -- per image a header of counters and max_gt_ids identity records -- lives on the device,
+    is allocated on first use and is never read back before compute()), so forward + detect() + Sort.update() +
+    ClearMot.update() can be one captured graph (graph.GraphedStep).  HostClearMot is the reference it equals bit for
+    bit, and states the contract.
+
+    update(tracks, gt) takes Sort.update()'s dict and gt = {"boxes" [N, G, 6], "ids" [N, G], "count" [N]} (device
+    tensors; G <= 1024, at most 128 valid rows per image are used, ids in 0 .. max_gt_ids - 1) and returns device
+    tensors {"match" [N, G] int32, "iou" [N, G] float64, "flags" [N, G] int32} as HostClearMot does.  `scale` multiplies
+    the ground truth's corners as Sort's does the detections' (pass the tracker's).  Images are agent-major,
+    `batch_size` per agent, as in MeanAP.  compute() makes one copy of the state and raises DnError naming the sticky
+    status bits -- never a silently truncated metric.
+
+    GraphedStep runs its step three times to warm up before it captures and those runs are counted: call reset() after
+    constructing the GraphedStep, before the first replay that counts (as with Sort and MeanAP)."""
+
+    def __init__(self, batch_size, iou_threshold=0.5, scale=1.0, max_gt_ids=256):
+        self.batch_size, self.iou_threshold, self.scale, self.max_gt_ids = _check_mot_params(batch_size, iou_threshold,
+                                                                                             scale, max_gt_ids)
+        self.state = None            # uint8 [N * (MOT_HEADER_BYTES + MOT_RECORD_BYTES * max_gt_ids)] on the device
+        self.n_images = 0
+
+    def reset(self):
+        """Zero every counter, identity record and status word (one launch on the current stream)."""
+        if self.state is not None:
+            from .ops import _ptr, _stream
+            _lib.check(_lib.load().dn_mot_reset(_ptr(self.state), self.n_images, self.max_gt_ids, _stream()),
+                       "dn_mot_reset")
+
+    def update(self, tracks, gt):
+        from .ops import _need_gpu, _ptr, _stream
+        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
+                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise _lib.DnError("ClearMot.update needs device tensors (%s is %s); HostClearMot is the numpy reference"
+                                   % (name, type(t).__name__))
+        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
+        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
+        if tid.dim() != 2 or gids.dim() != 2:
+            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
+        (n, m), g = tid.shape, gids.shape[1]
+        if not 1 <= m <= MAX_TRACKS:
+            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
+        if not 1 <= g <= MAX_GT_ROWS:
+            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
+        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
+                or gcount.numel() != n):
+            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
+                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
+        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
+        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        lib = _lib.load()
+        dev = rect.device
+        if self.state is None:
+            nbytes = int(lib.dn_mot_state_bytes(n, self.max_gt_ids))
+            if nbytes != mot_state_bytes(n, self.max_gt_ids):
+                raise _lib.DnError("dn_mot_state_bytes(%d, %d) = %d" % (n, self.max_gt_ids, nbytes))
+            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.n_images = n
+            self.reset()
+        if n != self.n_images:
+            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        out = {"match": torch.empty((n, g), dtype=torch.int32, device=dev),
+               "iou": torch.empty((n, g), dtype=torch.float64, device=dev),
+               "flags": torch.empty((n, g), dtype=torch.int32, device=dev)}
+        _lib.check(lib.dn_mot_step(_ptr(rect), _ptr(tid), _ptr(tcount), n, m, _ptr(boxes), _ptr(gids), _ptr(gcount), g,
+                                   self.scale, self.iou_threshold, self.max_gt_ids, _ptr(self.state), _ptr(out["match"]),
+                                   _ptr(out["iou"]), _ptr(out["flags"]), _stream()), "dn_mot_step")
+        return out
+
+    def status_words(self):
+        """The status word of every image (numpy int32): one small copy, waits for the device."""
+        if self.state is None:
+            return np.zeros(0, dtype=np.int32)
+        words = self.state.view(self.n_images, -1)[:, 48:52].contiguous().cpu().numpy()
+        return words.view(np.int32).reshape(-1).copy()
+
+    def state_bytes(self):
+        """A host copy of the whole state (numpy uint8); HostClearMot.state_bytes() is its reference."""
+        return self.state.cpu().numpy().copy() if self.state is not None else np.zeros(0, dtype=np.uint8)
+
+    def compute(self):
+        """One copy of the state, then HostClearMot.compute()'s dict in float64 on the host.  Raises DnError naming any
+        sticky status bit."""
+        return mot_figures_from_state(self.state_bytes(), self.n_images, self.max_gt_ids, self.batch_size, "ClearMot")

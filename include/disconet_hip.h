@@ -686,6 +686,56 @@ int dn_track_step(const float* boxes, const float* scores, const int32_t* count,
                   int32_t* out_id, int32_t* out_det, float* out_score, int32_t* out_count, int32_t* det_track,
                   void* stream);
 
+/* ------------------------------------------------------------------------
+ * CLEAR MOT evaluation of the tracks (disconet_amd/csrc/mot_eval.hip): the stage behind dn_track_step -- per image and
+ * call one evaluation step of the CLEAR metrics (Bernardin & Stiefelhagen) as the MOT benchmark's evaluation kit computes
+ * them.  What the reference's own evaluation computes is recalled, not pinned: this contract is the
+ * project's own and tracking.HostClearMot (numpy / float64) is its normative statement, which the kernel equals bit for
+ * bit.  Graph-capturable behind dn_track_step: one kernel launch, no host synchronisation, no allocation; the launch
+ * depends on the shapes only.  Every image of the agent-major batch is its own sequence.
+ *   rect [n][m][4] fp64, id [n][m], count [n]: dn_track_step's report (out_rect, out_id, out_count), 1 <= m <= 128; counts
+ *   are clamped to [0, m]; ids are the tracker's (>= 1: the words last and pst below use 0 for "none").
+ *   gt_boxes [n][g][6] fp32 rows (x, y, w, h, sin, cos), gt_ids [n][g], gt_count [n], 1 <= g <= 1024; counts are clamped
+ *   to [0, g].  scale finite and > 0, iou_threshold in (0, 1], 1 <= max_gt_ids <= 1024.
+ *   All arithmetic is fp64 in the order written here, + - * / and sqrt only, never contracted.
+ *   Per image and call, in this order:
+ *   1. frames += 1.
+ *   2. Ground truth, rows below the count in row order.  A row's rectangle is dn_track_step's measurement: the corners
+ *      with (sin, cos) / max(sqrt(sin sin + cos cos), 1e-12), each multiplied by `scale`, x1, y1, x2, y2 = their min /
+ *      max.  A row whose corners are not all finite or with not (x2 - x1 > 0 and y2 - y1 > 0) is ignored and sets status
+ *      bit 2 (value 2).  Else a row whose id is outside 0 .. max_gt_ids - 1 is ignored and sets status bit 4.  Of the
+ *      rows left the first 128 are kept; a 129th sets status bit 1.  Of the kept rows, one whose id a lower kept row
+ *      carries is dropped and sets status bit 8.  The V rows that remain are the frame's valid ground truth.
+ *   3. iou[a][t] of valid ground truth a's rectangle with reported track t's (t < count), dn_track_step's step 3 with the
+ *      ground truth as its first rectangle; 0 for a track whose rectangle has a non-finite member.
+ *   4. score[a][t] = 0 where iou < iou_threshold (so an IoU equal to the threshold counts); elsewhere iou + 1000.0 when
+ *      id[t] equals pst of a's identity, else iou.
+ *   5. The assignment that maximises the total score: dn_track_step's shortest-augmenting-path step on cost = -score
+ *      (rows the smaller side -- the ground truths when V <= count --, ascending; potentials from 0; the unused column of
+ *      smallest reduced cost, the lowest index among equals; a row's search ends after columns + 1 steps).  A pair is
+ *      kept only when its score is > 0.
+ *   6. Every identity of the image: pst = 0.  Every valid ground truth, in ascending row order: frames_present += 1;
+ *      if it holds a kept pair with track t: TP += 1; motp_sum = motp_sum + iou (step 3's value, one pair after the
+ *      other in this order); an id switch (IDSW += 1, flag bit 1) when last != 0 and last != id[t]; a segment start
+ *      (segments += 1, flag bit 2) when pst was 0 before this call; last = pst = id[t]; frames_matched += 1.
+ *   7. FN += V - pairs kept; FP += count - pairs kept.
+ *   out_match [n][g]: the track id a ground-truth row took, else -1; out_iou [n][g] fp64: that pair's IoU, else 0;
+ *   out_flags [n][g]: bit 0 matched, bit 1 id switch, bit 2 segment start, else 0.  Every word is written on every call.
+ *   State (caller-owned, on the device, dn_mot_state_bytes(n, max_gt_ids) = n (64 + 32 max_gt_ids) bytes, 0 for refused
+ *   arguments; 8-byte aligned): per image {int64 frames, TP, FP, FN, IDSW; fp64 motp_sum; int32 status; 12 bytes 0}, then
+ *   max_gt_ids records of 32 bytes {int32 last, pst, frames_present, frames_matched, segments, 3 x 0}.  Status bits are
+ *   sticky until dn_mot_reset, which zeroes everything.  Two runs write the same bytes.
+ *   From the state, on the host (tracking.ClearMot.compute): Frag = sum over identities of max(segments - 1, 0); of the
+ *   identities with frames_present > 0, frames_matched / frames_present > 0.8 is mostly tracked, < 0.2 mostly lost, else
+ *   partly tracked; MOTA = (TP - FP - IDSW) / max(1, TP + FN); MOTP = motp_sum / max(1, TP).
+ *   A launch whose score matrix (8 min(g, 128) (m | 1) bytes of LDS) would not fit beside the work arrays is refused.
+ * ------------------------------------------------------------------------ */
+size_t dn_mot_state_bytes(int n_images, int max_gt_ids);
+int dn_mot_reset(void* state, int n_images, int max_gt_ids, void* stream);
+int dn_mot_step(const double* rect, const int32_t* id, const int32_t* count, int n_images, int m, const float* gt_boxes,
+                const int32_t* gt_ids, const int32_t* gt_count, int g, double scale, double iou_threshold, int max_gt_ids,
+                void* state, int32_t* out_match, double* out_iou, int32_t* out_flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

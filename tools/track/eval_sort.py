@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""The stage behind the tracker in the reference's det pipeline (train -> test -> track -> evaluate the tracks: `make
+sort`, then `make eval`): the CLEAR MOT figures of SORT's tracks, on the GPU.  Per frame, tracking.Sort.update() and
+tracking.ClearMot.update() (behind forward -> postprocess.detect() with --source net) replay as ONE captured graph
+(graph.GraphedStep); nothing is copied to the host before the end, where ClearMot.compute() makes one copy of the
+counters.  Prints one line per agent and one overall: MOTA, MOTP, TP, FP, FN, IDSW, Frag, MT / PT / ML.
+
+    python tools/track/eval_sort.py --com disco [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+        [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5]
+
+--source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
+noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
+--source net runs test_codet.py's model on synthetic.make_box_scene_batch(seed = --seed), the same standing scene every
+frame, with the scene's boxes as ground truth and their rows as identities.  With untrained weights the detections have
+little to do with the boxes: the run shows the plumbing only; after `train_codet.py --targets boxes --logpath L`,
+`--resume L/epoch_N.pth` gives figures that belong to the detector.
+"""
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
+
+from disconet_amd import Config, DiscoNet, graph, postprocess, tracking  # noqa: E402
+from disconet_amd.synthetic import make_box_scene_batch, make_track_sequence, randomize_bn_stats  # noqa: E402
+from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
+
+
+def main(argv=None):
+    ap = build_parser()
+    ap.add_argument("--source", choices=("net", "boxes"), default="boxes",
+                    help="net: the model on a standing box scene (with untrained weights it shows the plumbing only)")
+    ap.add_argument("--seed", type=int, default=0, help="make_track_sequence's / make_box_scene_batch's seed")
+    ap.add_argument("--pre_nms_top_k", type=int, default=128)
+    ap.add_argument("--iou_thr", type=float, default=0.01, help="the NMS threshold of detect()")
+    ap.add_argument("--score_thr", type=float, default=None)
+    ap.add_argument("--max_age", type=int, default=1)
+    ap.add_argument("--min_hits", type=int, default=3)
+    ap.add_argument("--iou_threshold", type=float, default=0.3, help="SORT's association threshold")
+    ap.add_argument("--max_tracks", type=int, default=128)
+    ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
+    ap.add_argument("--max_gt_ids", type=int, default=256)
+    ap.set_defaults(frames=8)
+    args = ap.parse_args(argv)
+    if args.com != "disco":
+        raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
+    num_agent = args.num_agent + (1 if args.rsu else 0)
+    n = num_agent * args.batch
+    config = Config("test", binary=True, only_det=True)
+    scale = 1.0 / config.voxel_size[0]
+    sort = tracking.Sort(max_age=args.max_age, min_hits=args.min_hits, iou_threshold=args.iou_threshold, scale=scale,
+                         max_tracks=args.max_tracks)
+    mot = tracking.ClearMot(args.batch, iou_threshold=args.eval_iou, scale=scale, max_gt_ids=args.max_gt_ids)
+
+    if args.source == "boxes":
+        seq = make_track_sequence(args.frames, n, seed=args.seed, truth=True)
+        det = {key: torch.from_numpy(seq[0][0][key]).cuda() for key in ("boxes", "scores", "count")}
+        gt = {key: torch.from_numpy(seq[0][2][key]).cuda() for key in ("boxes", "ids", "count")}
+
+        def load(frame):
+            for key in det:
+                det[key].copy_(torch.from_numpy(seq[frame][0][key]))
+            for key in gt:
+                gt[key].copy_(torch.from_numpy(seq[frame][2][key]))
+
+        step = graph.GraphedStep(lambda: mot.update(sort.update(det), gt))
+    else:
+        model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
+                         compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
+        if args.resume:
+            checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
+            model.load_state_dict(checkpoint["model_state_dict"])
+            print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
+        else:
+            torch.manual_seed(0)
+            randomize_bn_stats(model)
+            print("note: untrained weights -- the figures below show the plumbing, not a detector")
+        model.eval().cuda()
+        anchors = postprocess.make_anchors(config)
+        scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=args.seed, device="cuda")
+        bevs, trans, na = (scene[key].cuda() for key in ("bev_seq", "trans_matrices", "num_agent"))
+        rows = scene["gt_boxes"].shape[1]
+        gt = {"boxes": torch.as_tensor(scene["gt_boxes"]).cuda(), "count": torch.as_tensor(scene["gt_count"]).cuda(),
+              "ids": torch.arange(rows, dtype=torch.int32).repeat(n, 1).cuda()}
+
+        def load(frame):
+            pass                       # a standing scene: every frame sees the same boxes
+
+        def forward_detect_track_evaluate():
+            with torch.no_grad():
+                out = model(bevs, trans, na, args.batch)
+            found = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors,
+                                       pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr, score_thr=args.score_thr)
+            return mot.update(sort.update(found), gt)
+
+        step = graph.GraphedStep(forward_detect_track_evaluate)
+    sort.reset()                       # the warm-up runs of the capture advanced the tracker ...
+    mot.reset()                        # ... and were counted
+
+    for frame in range(args.frames):
+        load(frame)
+        step()
+    step.drain()
+    sort.status()                      # raises when a frame was truncated (more than 128 valid rows, no free slot, ...)
+    figures = mot.compute()            # the one copy; raises on a sticky status bit of the evaluation
+    print("%d frames, %d images (%d agents x batch %d), tracks need IoU >= %g" % (args.frames, n, num_agent, args.batch,
+                                                                                  args.eval_iou))
+    for a, row in enumerate(figures["per_agent"]):
+        print(tracking.mot_line("agent %d" % a, row))
+    print(tracking.mot_line("overall", figures["overall"]))
+
+
+if __name__ == "__main__":
+    main()
