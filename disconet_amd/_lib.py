@@ -154,6 +154,11 @@ SIGNATURES = {
     "dn_mot_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "dn_mot_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
                             c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dn_idf_state_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dn_idf_reset": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dn_idf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                            c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dn_idf_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

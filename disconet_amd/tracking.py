@@ -13,7 +13,10 @@ Every image of the agent-major batch (image = agent * B + b) is its own sequence
 
 The stage behind it (`make eval`) is here too: the CLEAR MOT figures of the tracks against ground-truth boxes with
 identities -- HostClearMot states that contract in the same way, ClearMot runs it on the GPU (dn_mot_step,
-csrc/mot_eval.hip), graph-capturable behind Sort.update().
+csrc/mot_eval.hip), graph-capturable behind Sort.update().  Beside them the identity figures (IDF1, IDP, IDR and the
+counts) of the same kit, again recalled, not pinned: HostIdentity states that contract, Identity runs it on the GPU --
+per frame dn_idf_step counts the overlapping (identity, track id) pairs into a matrix that stays on the device, at the
+end dn_idf_finish solves the one global assignment over it there (csrc/idf_eval.hip).
 """
 import numpy as np
 import torch
@@ -857,3 +860,321 @@ class ClearMot:
         """One copy of the state, then HostClearMot.compute()'s dict in float64 on the host.  Raises DnError naming any
         sticky status bit."""
         return mot_figures_from_state(self.state_bytes(), self.n_images, self.max_gt_ids, self.batch_size, "ClearMot")
+
+
+# ---------------------------------------------------------------------------
+# Identity metrics of the tracks (dn_idf_step / dn_idf_finish, csrc/idf_eval.hip): IDF1 beside CLEAR
+# ---------------------------------------------------------------------------
+MAX_TRACK_IDS = 2048      # upper limit of max_track_ids
+IDF_HEADER_BYTES = 64     # per image: int64 frames, gt_dets, dets; int32 status; 36 spare bytes (zero)
+IDF_STATUS_BITS = MOT_STATUS_BITS + ((16, "a reported track id was outside 1 .. max_track_ids and its row was ignored"),)
+IDF_FIGURES = ("IDF1", "IDP", "IDR", "IDTP", "IDFP", "IDFN", "Dets", "GT_Dets", "IDs", "GT_IDs")
+
+
+def _check_idf_params(batch_size, iou_threshold, scale, max_gt_ids, max_track_ids):
+    batch_size, iou_threshold, scale, max_gt_ids = _check_mot_params(batch_size, iou_threshold, scale, max_gt_ids)
+    max_track_ids = int(max_track_ids)
+    if not 1 <= max_track_ids <= MAX_TRACK_IDS:
+        raise ValueError("max_track_ids = %d: 1..%d are supported" % (max_track_ids, MAX_TRACK_IDS))
+    return batch_size, iou_threshold, scale, max_gt_ids, max_track_ids
+
+
+def idf_state_bytes(n_images, max_gt_ids, max_track_ids):
+    """Bytes of the identity state of n_images images (what dn_idf_state_bytes returns)."""
+    g, t = int(max_gt_ids), int(max_track_ids)
+    return int(n_images) * (IDF_HEADER_BYTES + 4 * (g + t + g * t))
+
+
+def _idf_status_text(words):
+    out = []
+    for img, w in enumerate(words):
+        for bit, text in IDF_STATUS_BITS:
+            if int(w) & bit:
+                out.append("image %d: %s" % (img, text))
+    return out
+
+
+def _idf_level(group):
+    """Rows of `counts` (lists of ints), summed in the order given -> the identity figures of that level."""
+    s = [0] * 6
+    for row in group:
+        for k in range(6):
+            s[k] = s[k] + int(row[k])
+    frames, gt_dets, dets, idtp, gt_ids, ids = s
+    idfn, idfp = gt_dets - idtp, dets - idtp
+    return {"IDF1": float(2 * idtp) / float(max(1, 2 * idtp + idfp + idfn)),
+            "IDP": float(idtp) / float(max(1, idtp + idfp)), "IDR": float(idtp) / float(max(1, idtp + idfn)),
+            "IDTP": idtp, "IDFP": idfp, "IDFN": idfn, "Dets": dets, "GT_Dets": gt_dets, "IDs": ids, "GT_IDs": gt_ids,
+            "frames": frames}
+
+
+def idf_figures(counts, batch_size, who="Identity"):
+    """finish()'s `counts` [N, 8] int64 (frames, GT_Dets, Dets, IDTP, GT_IDs, IDs, status, 0) -> {"overall": figures,
+    "per_agent": [figures], "per_image": [figures]}, each with IDF1, IDP, IDR, IDTP, IDFP, IDFN, Dets, GT_Dets, IDs, GT_IDs
+    and frames; sums over images are taken in image order.  Raises DnError naming any status bit."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 8)
+    text = _idf_status_text(counts[:, 6])
+    if text:
+        raise _lib.DnError("%s: %s" % (who, "; ".join(text)))
+    rows = counts.tolist()
+    n_images, batch_size = len(rows), int(batch_size)
+    agents = -(-n_images // batch_size)
+    return {"overall": _idf_level(rows),
+            "per_agent": [_idf_level(rows[a * batch_size:(a + 1) * batch_size]) for a in range(agents)],
+            "per_image": [_idf_level([row]) for row in rows]}
+
+
+def idf_line(name, figures):
+    """One line of the evaluation tool: the identity figures of `name`."""
+    return "%s: IDF1 %.4f IDP %.4f IDR %.4f IDTP %d IDFP %d IDFN %d Dets %d GT_Dets %d IDs %d GT_IDs %d" % (
+        (name,) + tuple(figures[key] for key in IDF_FIGURES))
+
+
+def _idf_assignment(match, weight_of):
+    """finish()'s `match` [N, max_gt_ids] -> per image [(identity, track id, frames)], ascending identity."""
+    out = []
+    for img in range(match.shape[0]):
+        out.append([(int(i), int(match[img, i]), int(weight_of(img, int(i), int(match[img, i]))))
+                    for i in np.nonzero(match[img])[0]])
+    return out
+
+
+class HostIdentity:
+    """The numpy reference of Identity and the statement of its contract: the identity metrics (IDF1, IDP, IDR; Ristani
+    et al., "Performance measures and a data set for multi-target, multi-camera tracking") as the MOT benchmark's
+    evaluation kit computes them, recalled, not pinned; the full text is in include/disconet_hip.h.
+
+    update(tracks, gt) takes exactly ClearMot.update()'s inputs -- tracks = Sort.update()'s dict (the first `count` rows
+    of "rect" [N, M, 4] and "id" [N, M], M <= 128), gt = {"boxes" [N, G, 6] float32, "ids" [N, G] int32, "count" [N]}, G
+    <= 1024 -- and returns numpy {"overlaps" [N, G] int32}: per ground-truth row the number of reported rows that overlap
+    it at the threshold (`not iou < iou_threshold`), 0 for a row that was not kept.  Every such pair adds 1 to
+    pairs[identity][track id - 1]; a reported row whose id is outside 1 .. max_track_ids sets status bit 16 and is counted
+    nowhere; one with a non-finite rectangle is counted as reported and overlaps nothing.  Every image is its own
+    sequence.  finish() reads the state and leaves it: over the identities and track ids seen so far, hungarian_max on
+    the pairs matrix as float64 picks the identity-to-track mapping with the most matched frames (IDTP)."""
+
+    def __init__(self, batch_size, iou_threshold=0.5, scale=1.0, max_gt_ids=256, max_track_ids=1024):
+        (self.batch_size, self.iou_threshold, self.scale, self.max_gt_ids,
+         self.max_track_ids) = _check_idf_params(batch_size, iou_threshold, scale, max_gt_ids, max_track_ids)
+        self.images = None
+
+    def _fresh(self):
+        return {"frames": 0, "gt_dets": 0, "dets": 0, "status": 0,
+                "gt_count": np.zeros(self.max_gt_ids, dtype=np.int32),
+                "track_count": np.zeros(self.max_track_ids, dtype=np.int32),
+                "pairs": np.zeros((self.max_gt_ids, self.max_track_ids), dtype=np.int32)}
+
+    def reset(self):
+        if self.images is not None:
+            self.images = [self._fresh() for _ in self.images]
+
+    def update(self, tracks, gt):
+        rect, tid, tcount = _mot_tracks(tracks)
+        boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
+        gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
+        gcount = np.asarray(_host(gt["count"])).reshape(-1)
+        if tid.ndim != 2:
+            raise ValueError("shapes: id %s" % (tid.shape,))
+        n, m = tid.shape
+        g = gids.shape[1] if gids.ndim == 2 else 0
+        if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
+                or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
+            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
+                rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+        if self.images is None:
+            self.images = [self._fresh() for _ in range(n)]
+        if len(self.images) != n:
+            raise ValueError("the evaluation holds %d images, this call has %d (reset() keeps the count)"
+                             % (len(self.images), n))
+        out = {"overlaps": np.zeros((n, g), dtype=np.int32)}
+        for img in range(n):
+            self._step(self.images[img], rect[img], tid[img], tcount[img], boxes[img], gids[img], gcount[img], img, out)
+        return out
+
+    def _step(self, st, rect, tid, tcount, boxes, gids, gcount, img, out):
+        m = tid.shape[0]
+        k = min(max(int(tcount), 0), m)
+        st["frames"] += 1
+        rows, rects, idents, status = _gt_measure(boxes, gids, gcount, self.scale, self.max_gt_ids)
+        reported = []                                   # (row, column) of the reported rows that are counted
+        for t in range(k):
+            track = int(tid[t])
+            if not 1 <= track <= self.max_track_ids:
+                status |= 16
+                continue
+            st["track_count"][track - 1] += 1
+            st["dets"] += 1
+            if bool(np.isfinite(rect[t]).all()):
+                reported.append((t, track - 1))
+        st["status"] |= status
+        for a, ident in enumerate(idents):
+            st["gt_count"][ident] += 1
+            st["gt_dets"] += 1
+            hits = 0
+            for t, col in reported:
+                if not iou_rect(rects[a], rect[t]) < self.iou_threshold:
+                    st["pairs"][ident, col] += 1
+                    hits += 1
+            out["overlaps"][img, rows[a]] = hits
+
+    def status_words(self):
+        """The status word of every image (numpy int32), without raising."""
+        return np.asarray([st["status"] for st in (self.images or [])], dtype=np.int32)
+
+    def state_bytes(self):
+        """The state in the device layout (numpy uint8), byte for byte what Identity.state_bytes() returns."""
+        imgs = self.images or []
+        g, t = self.max_gt_ids, self.max_track_ids
+        buf = np.zeros((len(imgs), IDF_HEADER_BYTES + 4 * (g + t + g * t)), dtype=np.uint8)
+        for i, st in enumerate(imgs):
+            buf[i, :24] = np.asarray([st["frames"], st["gt_dets"], st["dets"]], dtype=np.int64).view(np.uint8)
+            buf[i, 24:28] = np.asarray([st["status"]], dtype=np.int32).view(np.uint8)
+            o = IDF_HEADER_BYTES
+            buf[i, o:o + 4 * g] = st["gt_count"].view(np.uint8)
+            buf[i, o + 4 * g:o + 4 * (g + t)] = st["track_count"].view(np.uint8)
+            buf[i, o + 4 * (g + t):] = np.ascontiguousarray(st["pairs"]).reshape(-1).view(np.uint8)
+        return buf.reshape(-1)
+
+    def counts_matrix(self, image):
+        """The pairs block of one image, [max_gt_ids, max_track_ids] int32 (a copy)."""
+        return self.images[image]["pairs"].copy()
+
+    def finish(self):
+        """{"counts" [N, 8] int64: frames, GT_Dets, Dets, IDTP, GT_IDs, IDs, status, 0; "match" [N, max_gt_ids] int32: the
+        track id an identity was given, else 0}.  Reads the state only: the sequence may go on."""
+        imgs = self.images or []
+        counts = np.zeros((len(imgs), 8), dtype=np.int64)
+        match = np.zeros((len(imgs), self.max_gt_ids), dtype=np.int32)
+        for i, st in enumerate(imgs):
+            rows, cols = np.nonzero(st["gt_count"] > 0)[0], np.nonzero(st["track_count"] > 0)[0]
+            weight = st["pairs"][np.ix_(rows, cols)].astype(np.float64)
+            idtp = 0
+            for a, t in hungarian_max(weight):
+                if weight[a, t] > 0:
+                    idtp += int(st["pairs"][rows[a], cols[t]])
+                    match[i, rows[a]] = cols[t] + 1
+            counts[i] = (st["frames"], st["gt_dets"], st["dets"], idtp, len(rows), len(cols), st["status"], 0)
+        return {"counts": counts, "match": match}
+
+    def compute(self):
+        """{"overall", "per_agent", "per_image"}: idf_figures() of finish()'s counts.  Raises DnError naming any sticky
+        status bit."""
+        return idf_figures(self.finish()["counts"], self.batch_size, "HostIdentity")
+
+    def assignment(self):
+        """Per image the list of (identity, track id, frames) of the kept pairs, in ascending identity."""
+        return _idf_assignment(self.finish()["match"], lambda img, i, t: self.images[img]["pairs"][i, t - 1])
+
+
+class Identity:
+    """The identity metrics on the GPU beside ClearMot: update() after every frame enqueues dn_idf_step on torch's
+    current stream (the state -- per image a header, the two per-id counts and the max_gt_ids x max_track_ids pairs
+    matrix -- lives on the device, is allocated on first use and is never read back), so forward + detect() +
+    Sort.update() + ClearMot.update() + Identity.update() can be one captured graph (graph.GraphedStep).  finish()
+    enqueues dn_idf_finish -- the global assignment over the pairs matrix, on the device -- and returns device tensors, so
+    it may be captured too; it reads the state only and the sequence may go on.  HostIdentity is the reference both equal
+    bit for bit, and states the contract.
+
+    update(tracks, gt) takes ClearMot.update()'s inputs (device tensors) and returns {"overlaps" [N, G] int32}.  compute()
+    is finish() plus the copy of `counts` (8 words per image) and raises DnError naming the sticky status bits -- never a
+    silently truncated metric; assignment() also copies `match`.
+
+    GraphedStep runs its step three times to warm up before it captures and those runs are counted: call reset() after
+    constructing the GraphedStep, before the first replay that counts (as with ClearMot, Sort and MeanAP)."""
+
+    def __init__(self, batch_size, iou_threshold=0.5, scale=1.0, max_gt_ids=256, max_track_ids=1024):
+        (self.batch_size, self.iou_threshold, self.scale, self.max_gt_ids,
+         self.max_track_ids) = _check_idf_params(batch_size, iou_threshold, scale, max_gt_ids, max_track_ids)
+        self.state = None            # uint8 [idf_state_bytes(N, max_gt_ids, max_track_ids)] on the device
+        self.n_images = 0
+
+    def reset(self):
+        """Zero every count, the pairs matrix and the status words (one launch on the current stream)."""
+        if self.state is not None:
+            from .ops import _ptr, _stream
+            _lib.check(_lib.load().dn_idf_reset(_ptr(self.state), self.n_images, self.max_gt_ids, self.max_track_ids,
+                                                _stream()), "dn_idf_reset")
+
+    def update(self, tracks, gt):
+        from .ops import _need_gpu, _ptr, _stream
+        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
+                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise _lib.DnError("Identity.update needs device tensors (%s is %s); HostIdentity is the numpy reference"
+                                   % (name, type(t).__name__))
+        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
+        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
+        if tid.dim() != 2 or gids.dim() != 2:
+            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
+        (n, m), g = tid.shape, gids.shape[1]
+        if not 1 <= m <= MAX_TRACKS:
+            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
+        if not 1 <= g <= MAX_GT_ROWS:
+            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
+        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
+                or gcount.numel() != n):
+            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
+                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
+        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
+        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        lib = _lib.load()
+        dev = rect.device
+        if self.state is None:
+            nbytes = int(lib.dn_idf_state_bytes(n, self.max_gt_ids, self.max_track_ids))
+            if nbytes != idf_state_bytes(n, self.max_gt_ids, self.max_track_ids):
+                raise _lib.DnError("dn_idf_state_bytes(%d, %d, %d) = %d" % (n, self.max_gt_ids, self.max_track_ids, nbytes))
+            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.n_images = n
+            self.reset()
+        if n != self.n_images:
+            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        out = {"overlaps": torch.empty((n, g), dtype=torch.int32, device=dev)}
+        _lib.check(lib.dn_idf_step(_ptr(rect), _ptr(tid), _ptr(tcount), n, m, _ptr(boxes), _ptr(gids), _ptr(gcount), g,
+                                   self.scale, self.iou_threshold, self.max_gt_ids, self.max_track_ids, _ptr(self.state),
+                                   _ptr(out["overlaps"]), _stream()), "dn_idf_step")
+        return out
+
+    def finish(self):
+        """Enqueue dn_idf_finish on the current stream -> device tensors {"counts" [N, 8] int64, "match" [N, max_gt_ids]
+        int32} as HostIdentity.finish() returns them.  Reads the state only."""
+        from .ops import _ptr, _stream
+        if self.state is None:
+            raise _lib.DnError("Identity.finish: no frame was evaluated yet")
+        dev = self.state.device
+        out = {"counts": torch.empty((self.n_images, 8), dtype=torch.int64, device=dev),
+               "match": torch.empty((self.n_images, self.max_gt_ids), dtype=torch.int32, device=dev)}
+        _lib.check(_lib.load().dn_idf_finish(_ptr(self.state), self.n_images, self.max_gt_ids, self.max_track_ids,
+                                             _ptr(out["counts"]), _ptr(out["match"]), _stream()), "dn_idf_finish")
+        return out
+
+    def status_words(self):
+        """The status word of every image (numpy int32): one small copy, waits for the device."""
+        if self.state is None:
+            return np.zeros(0, dtype=np.int32)
+        words = self.state.view(self.n_images, -1)[:, 24:28].contiguous().cpu().numpy()
+        return words.view(np.int32).reshape(-1).copy()
+
+    def state_bytes(self):
+        """A host copy of the whole state (numpy uint8); HostIdentity.state_bytes() is its reference."""
+        return self.state.cpu().numpy().copy() if self.state is not None else np.zeros(0, dtype=np.uint8)
+
+    def counts_matrix(self, image):
+        """A host copy of the pairs block of one image, [max_gt_ids, max_track_ids] int32."""
+        g, t = self.max_gt_ids, self.max_track_ids
+        block = self.state.view(self.n_images, -1)[image, IDF_HEADER_BYTES + 4 * (g + t):].contiguous().cpu().numpy()
+        return block.view(np.int32).reshape(g, t).copy()
+
+    def compute(self):
+        """finish() and the copy of its counts, then HostIdentity.compute()'s dict on the host.  Raises DnError naming
+        any sticky status bit."""
+        return idf_figures(self.finish()["counts"].cpu().numpy(), self.batch_size, "Identity")
+
+    def assignment(self):
+        """finish(), the copy of `match` and of the matched pairs' words -> HostIdentity.assignment()'s lists."""
+        match = self.finish()["match"]
+        g, t = self.max_gt_ids, self.max_track_ids
+        pairs = self.state.view(self.n_images, -1)[:, IDF_HEADER_BYTES + 4 * (g + t):].view(torch.int32)
+        pairs = pairs.view(self.n_images, g, t)
+        frames = torch.gather(pairs, 2, (match.to(torch.int64) - 1).clamp_(min=0).unsqueeze(2)).squeeze(2).cpu().numpy()
+        return _idf_assignment(match.cpu().numpy(), lambda img, i, _t: frames[img, i])

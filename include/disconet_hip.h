@@ -736,6 +736,59 @@ int dn_mot_step(const double* rect, const int32_t* id, const int32_t* count, int
                 const int32_t* gt_ids, const int32_t* gt_count, int g, double scale, double iou_threshold, int max_gt_ids,
                 void* state, int32_t* out_match, double* out_iou, int32_t* out_flags, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Identity metrics of the tracks (disconet_amd/csrc/idf_eval.hip): IDF1, IDP, IDR (Ristani et al., "Performance measures
+ * and a data set for multi-target, multi-camera tracking") and the Count family beside them, as the MOT benchmark's
+ * evaluation kit prints them next to CLEAR.  What the reference's own evaluation computes is recalled, not pinned
+ * (SURVEY.md section 0): this contract is the project's own and tracking.HostIdentity (numpy) is its normative statement,
+ * which the kernels equal bit for bit.  dn_idf_step is graph-capturable behind dn_track_step / dn_mot_step and
+ * dn_idf_finish behind it: one kernel launch each, no host synchronisation, no allocation; a launch depends on the
+ * shapes only.  Every image of the agent-major batch is its own sequence.
+ *   Inputs of dn_idf_step: exactly dn_mot_step's (rect [n][m][4] fp64, id [n][m], count [n], 1 <= m <= 128; gt_boxes
+ *   [n][g][6] fp32, gt_ids [n][g], gt_count [n], 1 <= g <= 1024; counts clamped; scale finite and > 0; iou_threshold in
+ *   (0, 1]; 1 <= max_gt_ids <= 1024) and 1 <= max_track_ids <= 2048.  Ground-truth ids are 0 .. max_gt_ids - 1, track ids
+ *   1 .. max_track_ids (the tracker counts from 1); track id t owns column t - 1.
+ *   Per image and call:
+ *   1. frames += 1.
+ *   2. Ground truth: the V kept rows of dn_mot_step's step 2, by the same rule in the same order (status bits 2, 4, 1, 8
+ *      with the same meanings).  Every kept row: gt_count[id] += 1, gt_dets += 1.
+ *   3. Reported rows (below the count): a row whose id is outside 1 .. max_track_ids sets status bit 16 and is ignored --
+ *      it is counted nowhere.  Every other row: track_count[id - 1] += 1, dets += 1, also when its rectangle has a
+ *      non-finite member (a reported box that matches nothing).  The same id on two rows of a frame is counted twice.
+ *   4. Every pair (kept ground-truth row a, counted reported row t with a finite rectangle): iou as dn_mot_step's step 3,
+ *      fp64, never contracted; when not (iou < iou_threshold): pairs[id_a][id_t - 1] += 1.
+ *   out_overlaps [n][g] int32: per ground-truth row the number of such pairs, 0 for a row that was not kept.  Every word
+ *   is written on every call.
+ *   State (caller-owned, on the device, 4-byte aligned; dn_idf_state_bytes(n, G_ids, T_ids) = n (64 + 4 (G_ids + T_ids +
+ *   G_ids T_ids)) bytes, 0 for refused arguments), per image in this order: a 64-byte header {int64 frames, gt_dets, dets
+ *   at bytes 0..23; int32 status at bytes 24..27; the rest 0}, int32 gt_count[max_gt_ids], int32
+ *   track_count[max_track_ids], int32 pairs[max_gt_ids][max_track_ids] row-major.  All adds are integer adds (the matrix
+ *   and track_count by atomics): their result does not depend on the order, two runs write the same bytes.  Status bits
+ *   are sticky until dn_idf_reset, which zeroes everything.
+ *   dn_idf_finish reads the state and does not write it: it may run after any frame and the sequence may go on.  Rows =
+ *   the identities with gt_count > 0, columns = the track ids with track_count > 0, both ascending; the weight of a cell
+ *   is its pairs word.  The assignment that maximises the total weight is dn_track_step's shortest-augmenting-path step on
+ *   cost = -weight as fp64 (rows the smaller side -- the identities when there are no more of them than track ids --,
+ *   ascending; potentials from 0; the unused column of smallest reduced cost, the lowest index among equals; a row's
+ *   search ends after columns + 1 steps).  All values are integers below 2^31: every sum is exact.  A pair is kept only
+ *   when its weight is > 0; IDTP = the sum of the kept weights.
+ *   out_counts [n][8] int64: frames, GT_Dets, Dets, IDTP, GT_IDs (rows), IDs (columns), status, 0.
+ *   out_match [n][max_gt_ids] int32: the track id an identity was given, else 0.
+ *   From the counts, on the host (tracking.idf_figures), per image, agent and overall, sums in image order: IDFN = GT_Dets
+ *   - IDTP, IDFP = Dets - IDTP, IDR = IDTP / max(1, IDTP + IDFN), IDP = IDTP / max(1, IDTP + IDFP), IDF1 = 2 IDTP /
+ *   max(1, 2 IDTP + IDFP + IDFN).  The kit's (GT_IDs + IDs)^2 cost matrix with its false-negative / false-positive halves
+ *   has the minimum GT_Dets + Dets - 2 IDTP: the plain rectangular matrix gives the same figures.
+ *   The finish kernel's work arrays (58.1 KB of LDS, sized for 2049 columns) do not depend on the arguments; a launch
+ *   that would not fit 160 KB is refused.
+ * ------------------------------------------------------------------------ */
+size_t dn_idf_state_bytes(int n_images, int max_gt_ids, int max_track_ids);
+int dn_idf_reset(void* state, int n_images, int max_gt_ids, int max_track_ids, void* stream);
+int dn_idf_step(const double* rect, const int32_t* id, const int32_t* count, int n_images, int m, const float* gt_boxes,
+                const int32_t* gt_ids, const int32_t* gt_count, int g, double scale, double iou_threshold, int max_gt_ids,
+                int max_track_ids, void* state, int32_t* out_overlaps, void* stream);
+int dn_idf_finish(const void* state, int n_images, int max_gt_ids, int max_track_ids, int64_t* out_counts,
+                  int32_t* out_match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,14 @@
 sort`, then `make eval`): the CLEAR MOT figures of SORT's tracks, on the GPU.  Per frame, tracking.Sort.update() and
 tracking.ClearMot.update() (behind forward -> postprocess.detect() with --source net) replay as ONE captured graph
 (graph.GraphedStep); nothing is copied to the host before the end, where ClearMot.compute() makes one copy of the
-counters.  Prints one line per agent and one overall: MOTA, MOTP, TP, FP, FN, IDSW, Frag, MT / PT / ML.
+counters.  Prints one line per agent and one overall: MOTA, MOTP, TP, FP, FN, IDSW, Frag, MT / PT / ML.  Behind them, the
+identity figures in the same form (IDF1, IDP, IDR, IDTP / IDFP / IDFN, Dets, GT_Dets, IDs, GT_IDs): tracking.Identity.update()
+runs in the same captured step, and Identity.compute() solves the one global assignment on the device and copies 8 words
+per image.
 
     python tools/track/eval_sort.py --com disco [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
-        [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5]
+        [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
+        [--max_gt_ids 256] [--max_track_ids 1024]
 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
 noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
@@ -44,6 +48,7 @@ def main(argv=None):
     ap.add_argument("--max_tracks", type=int, default=128)
     ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
     ap.add_argument("--max_gt_ids", type=int, default=256)
+    ap.add_argument("--max_track_ids", type=int, default=1024, help="the identity figures count track ids 1 .. this")
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
     if args.com != "disco":
@@ -55,6 +60,11 @@ def main(argv=None):
     sort = tracking.Sort(max_age=args.max_age, min_hits=args.min_hits, iou_threshold=args.iou_threshold, scale=scale,
                          max_tracks=args.max_tracks)
     mot = tracking.ClearMot(args.batch, iou_threshold=args.eval_iou, scale=scale, max_gt_ids=args.max_gt_ids)
+    idf = tracking.Identity(args.batch, iou_threshold=args.eval_iou, scale=scale, max_gt_ids=args.max_gt_ids,
+                            max_track_ids=args.max_track_ids)
+
+    def evaluate(tracks):
+        return mot.update(tracks, gt), idf.update(tracks, gt)
 
     if args.source == "boxes":
         seq = make_track_sequence(args.frames, n, seed=args.seed, truth=True)
@@ -67,7 +77,7 @@ def main(argv=None):
             for key in gt:
                 gt[key].copy_(torch.from_numpy(seq[frame][2][key]))
 
-        step = graph.GraphedStep(lambda: mot.update(sort.update(det), gt))
+        step = graph.GraphedStep(lambda: evaluate(sort.update(det)))
     else:
         model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
                          compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
@@ -95,11 +105,12 @@ def main(argv=None):
                 out = model(bevs, trans, na, args.batch)
             found = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors,
                                        pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr, score_thr=args.score_thr)
-            return mot.update(sort.update(found), gt)
+            return evaluate(sort.update(found))
 
         step = graph.GraphedStep(forward_detect_track_evaluate)
     sort.reset()                       # the warm-up runs of the capture advanced the tracker ...
     mot.reset()                        # ... and were counted
+    idf.reset()
 
     for frame in range(args.frames):
         load(frame)
@@ -112,6 +123,10 @@ def main(argv=None):
     for a, row in enumerate(figures["per_agent"]):
         print(tracking.mot_line("agent %d" % a, row))
     print(tracking.mot_line("overall", figures["overall"]))
+    identity = idf.compute()           # the assignment on the device, then 8 words per image; raises on a status bit
+    for a, row in enumerate(identity["per_agent"]):
+        print(tracking.idf_line("agent %d" % a, row))
+    print(tracking.idf_line("overall", identity["overall"]))
 
 
 if __name__ == "__main__":
