@@ -159,6 +159,13 @@ SIGNATURES = {
     "dn_idf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
                             c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dn_idf_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dn_hota_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_hota_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_hota_reset": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dn_hota_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                             c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dn_hota_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "dn_warp_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

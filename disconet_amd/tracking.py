@@ -16,7 +16,10 @@ identities -- HostClearMot states that contract in the same way, ClearMot runs i
 csrc/mot_eval.hip), graph-capturable behind Sort.update().  Beside them the identity figures (IDF1, IDP, IDR and the
 counts) of the same kit, again recalled, not pinned: HostIdentity states that contract, Identity runs it on the GPU --
 per frame dn_idf_step counts the overlapping (identity, track id) pairs into a matrix that stays on the device, at the
-end dn_idf_finish solves the one global assignment over it there (csrc/idf_eval.hip).
+end dn_idf_finish solves the one global assignment over it there (csrc/idf_eval.hip).  And the third family, HOTA with
+its detection, association and localisation parts: HostHota states that contract, Hota runs it on the GPU -- per frame
+dn_hota_step adds to the potential-match matrix and logs the frame on the device, at the end dn_hota_finish matches every
+logged frame of every image at once under the global alignment score (csrc/hota_eval.hip).
 """
 import numpy as np
 import torch
@@ -1178,3 +1181,484 @@ class Identity:
         pairs = pairs.view(self.n_images, g, t)
         frames = torch.gather(pairs, 2, (match.to(torch.int64) - 1).clamp_(min=0).unsqueeze(2)).squeeze(2).cpu().numpy()
         return _idf_assignment(match.cpu().numpy(), lambda img, i, _t: frames[img, i])
+
+
+# ---------------------------------------------------------------------------
+# HOTA of the tracks (dn_hota_step / dn_hota_finish, csrc/hota_eval.hip): detection, association and localisation
+# ---------------------------------------------------------------------------
+MAX_HOTA_FRAMES = 4096    # upper limit of max_frames
+HOTA_HEADER_BYTES = 64    # per image: int64 frames, logged, gt_dets, dets; int32 status; 28 spare bytes (zero)
+HOTA_SLOT_BYTES = 9232    # per logged frame: int32 V, C, 8 bytes 0; int32 gid[128], tid[128]; fp64 gt_rect[128][4], track_rect[128][4]
+HOTA_ALPHAS = 19          # alpha_k = 0.05 (k + 1)
+HOTA_BINS = 20            # a kept pair counts at K = 0 .. 19 alphas
+HOTA_EPS = 2.0 ** -52     # the kit's epsilon: a pair counts at alpha when not (iou < alpha - HOTA_EPS)
+HOTA_STATUS_BITS = IDF_STATUS_BITS + (
+    (32, "the frame log was full (max_frames frames); the frames past it were counted in `frames` and left out of every figure"),
+    (64, "a reported track id came twice in one frame; the lower row was kept"))
+HOTA_FIGURES = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA", "HOTA(0)", "LocA(0)", "HOTALocA(0)")
+HOTA_COUNTS = ("Dets", "GT_Dets", "IDs", "GT_IDs")
+
+
+def hota_alphas():
+    """The 19 alphas as the contract writes them: 0.05 * (k + 1), an fp64 product."""
+    return [0.05 * (k + 1) for k in range(HOTA_ALPHAS)]
+
+
+def _check_hota_params(batch_size, scale, max_gt_ids, max_track_ids, max_frames):
+    batch_size, _, scale, max_gt_ids, max_track_ids = _check_idf_params(batch_size, 0.5, scale, max_gt_ids, max_track_ids)
+    max_frames = int(max_frames)
+    if not 1 <= max_frames <= MAX_HOTA_FRAMES:
+        raise ValueError("max_frames = %d: 1..%d are supported" % (max_frames, MAX_HOTA_FRAMES))
+    return batch_size, scale, max_gt_ids, max_track_ids, max_frames
+
+
+def _hota_image_bytes(max_gt_ids, max_track_ids, max_frames):
+    g, t, f = int(max_gt_ids), int(max_track_ids), int(max_frames)
+    return (HOTA_HEADER_BYTES + 8 * g * t + HOTA_SLOT_BYTES * f + 4 * (g + t) + 7) // 8 * 8
+
+
+def hota_state_bytes(n_images, max_gt_ids, max_track_ids, max_frames):
+    """Bytes of the HOTA state of n_images images (what dn_hota_state_bytes returns)."""
+    return int(n_images) * _hota_image_bytes(max_gt_ids, max_track_ids, max_frames)
+
+
+def hota_work_bytes(n_images, max_gt_ids, max_track_ids, max_frames):
+    """Bytes of dn_hota_finish's scratch (what dn_hota_work_bytes returns): per image the per-alpha TP words, the
+    per-frame loc partials and 20 int32 bins per (identity, track id) cell."""
+    g, t, f = int(max_gt_ids), int(max_track_ids), int(max_frames)
+    return int(n_images) * (8 * HOTA_BINS * (1 + f) + 4 * HOTA_BINS * g * t)
+
+
+def _hota_status_text(words):
+    out = []
+    for img, w in enumerate(words):
+        for bit, text in HOTA_STATUS_BITS:
+            if int(w) & bit:
+                out.append("image %d: %s" % (img, text))
+    return out
+
+
+def _hota_level(counts, alpha_counts, alpha_sums):
+    """Rows of one level (lists per image), added in the order given -> the HOTA figures of that level."""
+    c = [0] * 6
+    tp, fn, fp = [0] * HOTA_ALPHAS, [0] * HOTA_ALPHAS, [0] * HOTA_ALPHAS
+    sums = [[0.0] * 4 for _ in range(HOTA_ALPHAS)]
+    for row, ac, asum in zip(counts, alpha_counts, alpha_sums):
+        for k in range(6):
+            c[k] = c[k] + int(row[k])
+        for k in range(HOTA_ALPHAS):
+            tp[k], fn[k], fp[k] = tp[k] + int(ac[k][0]), fn[k] + int(ac[k][1]), fp[k] + int(ac[k][2])
+            for q in range(4):
+                sums[k][q] = sums[k][q] + float(asum[k][q])
+    per = {key: [] for key in ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")}
+    for k in range(HOTA_ALPHAS):
+        loc, assa, assre, asspr = sums[k]
+        det_a = float(tp[k]) / float(max(1, tp[k] + fn[k] + fp[k]))
+        ass_a = assa / float(max(1, tp[k]))
+        per["DetA"].append(det_a)
+        per["DetRe"].append(float(tp[k]) / float(max(1, tp[k] + fn[k])))
+        per["DetPr"].append(float(tp[k]) / float(max(1, tp[k] + fp[k])))
+        per["AssA"].append(ass_a)
+        per["AssRe"].append(assre / float(max(1, tp[k])))
+        per["AssPr"].append(asspr / float(max(1, tp[k])))
+        per["LocA"].append(loc / float(tp[k]) if tp[k] > 0 else 1.0)
+        per["HOTA"].append(float(np.sqrt(det_a * ass_a)))
+    out = {}
+    for key, values in per.items():
+        x = 0.0
+        for v in values:
+            x = x + v
+        out[key] = x / float(HOTA_ALPHAS)
+    out["HOTA(0)"], out["LocA(0)"] = per["HOTA"][0], per["LocA"][0]
+    out["HOTALocA(0)"] = per["HOTA"][0] * per["LocA"][0]
+    out.update({"frames": c[0], "logged": c[1], "GT_Dets": c[2], "Dets": c[3], "GT_IDs": c[4], "IDs": c[5],
+                "TP": tp, "FN": fn, "FP": fp, "loc": [s[0] for s in sums], "assa": [s[1] for s in sums],
+                "assre": [s[2] for s in sums], "asspr": [s[3] for s in sums], "per_alpha": per})
+    return out
+
+
+def hota_figures(fin, batch_size, who="Hota"):
+    """finish()'s dict on the host ("counts" [N, 8] int64: frames, logged, GT_Dets, Dets, GT_IDs, IDs, status, 0;
+    "alpha_counts" [N, 19, 4] int64: TP, FN, FP, 0; "alpha_sums" [N, 19, 4] float64: loc, assa, assre, asspr) ->
+    {"overall": figures, "per_agent": [figures], "per_image": [figures]}.  Counts and sums are added in image order (adding
+    the numerators is the kit's TP-weighted combination).  Per alpha DetA = TP / max(1, TP + FN + FP), DetRe, DetPr, AssA =
+    assa / max(1, TP), AssRe, AssPr, LocA = loc / TP (1.0 when TP = 0), HOTA = sqrt(DetA AssA); every figure is its mean
+    over the 19 alphas, beside them HOTA(0), LocA(0), HOTALocA(0) at alpha 0.05, the counts, the per-alpha lists TP, FN,
+    FP, loc, assa, assre, asspr and "per_alpha".  Raises DnError naming any status bit."""
+    counts = np.asarray(fin["counts"], dtype=np.int64).reshape(-1, 8)
+    text = _hota_status_text(counts[:, 6])
+    if text:
+        raise _lib.DnError("%s: %s" % (who, "; ".join(text)))
+    n_images, batch_size = counts.shape[0], int(batch_size)
+    rows = counts.tolist()
+    ac = np.asarray(fin["alpha_counts"], dtype=np.int64).reshape(n_images, HOTA_ALPHAS, 4).tolist()
+    asum = np.asarray(fin["alpha_sums"], dtype=np.float64).reshape(n_images, HOTA_ALPHAS, 4).tolist()
+    agents = -(-n_images // batch_size)
+
+    def level(lo, hi):
+        return _hota_level(rows[lo:hi], ac[lo:hi], asum[lo:hi])
+
+    return {"overall": level(0, n_images),
+            "per_agent": [level(a * batch_size, (a + 1) * batch_size) for a in range(agents)],
+            "per_image": [level(i, i + 1) for i in range(n_images)]}
+
+
+def hota_line(name, figures):
+    """One line of the evaluation tool: the HOTA figures of `name`."""
+    return ("%s: HOTA %.4f DetA %.4f AssA %.4f DetRe %.4f DetPr %.4f AssRe %.4f AssPr %.4f LocA %.4f HOTA(0) %.4f LocA(0) %.4f "
+            "HOTALocA(0) %.4f Dets %d GT_Dets %d IDs %d GT_IDs %d" % (
+                (name,) + tuple(figures[key] for key in HOTA_FIGURES + HOTA_COUNTS)))
+
+
+def _iou_matrix(grect, trect):
+    """iou_rect of every (ground truth [V, 4], column [C, 4]) pair, element for element the same operations; a column with
+    a non-finite member overlaps nothing.  The ground-truth rectangles are finite."""
+    g, t = np.asarray(grect, dtype=np.float64).reshape(-1, 4), np.asarray(trect, dtype=np.float64).reshape(-1, 4)
+    fin = np.isfinite(t).all(1)
+    t = np.where(fin[:, None], t, 0.0)
+    with np.errstate(all="ignore"):
+        w = np.minimum(g[:, None, 2], t[None, :, 2]) - np.maximum(g[:, None, 0], t[None, :, 0])
+        h = np.minimum(g[:, None, 3], t[None, :, 3]) - np.maximum(g[:, None, 1], t[None, :, 1])
+        inter = w * h
+        union = ((g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1]))[:, None] + ((t[:, 2] - t[:, 0]) * (t[:, 3] - t[:, 1]))[None, :] - inter
+        ok = (w > 0) & (h > 0) & (union > 0) & fin[None, :]
+        return np.where(ok, inter / np.where(ok, union, 1.0), 0.0)
+
+
+def _eval_inputs_host(tracks, gt):
+    """ClearMot.update()'s inputs as host arrays, shapes checked -> (rect, tid, tcount, boxes, gids, gcount, n, m, g)."""
+    rect, tid, tcount = _mot_tracks(tracks)
+    boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
+    gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
+    gcount = np.asarray(_host(gt["count"])).reshape(-1)
+    if tid.ndim != 2:
+        raise ValueError("shapes: id %s" % (tid.shape,))
+    n, m = tid.shape
+    g = gids.shape[1] if gids.ndim == 2 else 0
+    if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
+            or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
+        raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
+            rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+    return rect, tid, tcount, boxes, gids, gcount, n, m, g
+
+
+class HostHota:
+    """The numpy / float64 reference of Hota and the statement of its contract: HOTA (Luiten et al., "HOTA: A Higher Order
+    Metric for Evaluating Multi-Object Tracking") with DetA / AssA / LocA and their recall and precision parts, as the MOT
+    benchmark's evaluation kit computes them, recalled, not pinned; the full text is in include/disconet_hip.h.
+
+    update(tracks, gt) takes ClearMot.update()'s inputs (there is no IoU threshold: HOTA averages over 19 of them) and
+    returns numpy {"potential" [N, G] float64}: per ground-truth row the sum of s / (rs + cs - s) over the columns it
+    overlaps, which is what the frame added to that identity's row of the potential-match matrix.  The frame's measured
+    rectangles and ids are logged (max_frames frames per image; a frame past that sets status bit 32 and is left out).
+    finish() reads the state and leaves it: the global alignment score A = pot / (gt_count + track_count - pot) weights a
+    second pass over the logged frames -- per frame hungarian_max on A * IoU -- from which the per-alpha TP / FN / FP, the
+    localisation sums and the association sums come.  Every image is its own sequence."""
+
+    def __init__(self, batch_size, scale=1.0, max_gt_ids=256, max_track_ids=1024, max_frames=256):
+        (self.batch_size, self.scale, self.max_gt_ids, self.max_track_ids,
+         self.max_frames) = _check_hota_params(batch_size, scale, max_gt_ids, max_track_ids, max_frames)
+        self.images = None
+
+    def _fresh(self):
+        return {"frames": 0, "gt_dets": 0, "dets": 0, "status": 0, "log": [],
+                "gt_count": np.zeros(self.max_gt_ids, dtype=np.int32),
+                "track_count": np.zeros(self.max_track_ids, dtype=np.int32),
+                "pot": np.zeros((self.max_gt_ids, self.max_track_ids), dtype=np.float64)}
+
+    def reset(self):
+        if self.images is not None:
+            self.images = [self._fresh() for _ in self.images]
+
+    def update(self, tracks, gt):
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_host(tracks, gt)
+        if self.images is None:
+            self.images = [self._fresh() for _ in range(n)]
+        if len(self.images) != n:
+            raise ValueError("the evaluation holds %d images, this call has %d (reset() keeps the count)"
+                             % (len(self.images), n))
+        out = {"potential": np.zeros((n, g), dtype=np.float64)}
+        for img in range(n):
+            self._step(self.images[img], rect[img], tid[img], tcount[img], boxes[img], gids[img], gcount[img], img, out)
+        return out
+
+    def _step(self, st, rect, tid, tcount, boxes, gids, gcount, img, out):
+        st["frames"] += 1
+        if len(st["log"]) == self.max_frames:
+            st["status"] |= 32
+            return
+        k = min(max(int(tcount), 0), tid.shape[0])
+        rows, rects, idents, status = _gt_measure(boxes, gids, gcount, self.scale, self.max_gt_ids)
+        cols, tids = [], []
+        for t in range(k):
+            track = int(tid[t])
+            if not 1 <= track <= self.max_track_ids:
+                status |= 16
+                continue
+            if track in tids:
+                status |= 64
+                continue
+            cols.append(t)
+            tids.append(track)
+        st["status"] |= status
+        v, c = len(rows), len(cols)
+        gid, col = np.asarray(idents, dtype=np.int64), np.asarray(tids, dtype=np.int64) - 1
+        trects = np.asarray(rect[cols], dtype=np.float64).reshape(c, 4)
+        st["gt_count"][gid] += 1
+        st["gt_dets"] += v
+        st["track_count"][col] += 1
+        st["dets"] += c
+        s = _iou_matrix(rects, trects)                                   # [v, c]
+        rs, cs = np.zeros(v), np.zeros(c)
+        for t in range(c):                                               # ascending, from 0.0
+            rs = rs + s[:, t]
+        for a in range(v):
+            cs = cs + s[a, :]
+        with np.errstate(all="ignore"):
+            term = np.where(s > 0, s / np.where(s > 0, (rs[:, None] + cs[None, :]) - s, 1.0), 0.0)
+        if v and c:
+            st["pot"][np.ix_(gid, col)] += term                          # ids are unique: one add per cell; + 0.0 changes nothing
+        total = np.zeros(v)
+        for t in range(c):
+            total = total + term[:, t]
+        out["potential"][img, rows] = total
+        st["log"].append({"gid": np.asarray(idents, dtype=np.int32), "tid": np.asarray(tids, dtype=np.int32),
+                          "grect": np.asarray(rects, dtype=np.float64).reshape(v, 4), "trect": trects.copy()})
+
+    def status_words(self):
+        """The status word of every image (numpy int32), without raising."""
+        return np.asarray([st["status"] for st in (self.images or [])], dtype=np.int32)
+
+    def state_bytes(self):
+        """The state in the device layout (numpy uint8), byte for byte what Hota.state_bytes() returns."""
+        imgs = self.images or []
+        g, t, f = self.max_gt_ids, self.max_track_ids, self.max_frames
+        buf = np.zeros((len(imgs), _hota_image_bytes(g, t, f)), dtype=np.uint8)
+        for i, st in enumerate(imgs):
+            buf[i, :32] = np.asarray([st["frames"], len(st["log"]), st["gt_dets"], st["dets"]], dtype=np.int64).view(np.uint8)
+            buf[i, 32:36] = np.asarray([st["status"]], dtype=np.int32).view(np.uint8)
+            o = HOTA_HEADER_BYTES
+            buf[i, o:o + 8 * g * t] = np.ascontiguousarray(st["pot"]).reshape(-1).view(np.uint8)
+            o += 8 * g * t
+            for slot in st["log"]:
+                v, c = len(slot["gid"]), len(slot["tid"])
+                buf[i, o:o + 8] = np.asarray([v, c], dtype=np.int32).view(np.uint8)
+                buf[i, o + 16:o + 16 + 4 * v] = slot["gid"].view(np.uint8)
+                buf[i, o + 528:o + 528 + 4 * c] = slot["tid"].view(np.uint8)
+                buf[i, o + 1040:o + 1040 + 32 * v] = np.ascontiguousarray(slot["grect"]).reshape(-1).view(np.uint8)
+                buf[i, o + 5136:o + 5136 + 32 * c] = np.ascontiguousarray(slot["trect"]).reshape(-1).view(np.uint8)
+                o += HOTA_SLOT_BYTES
+            o = HOTA_HEADER_BYTES + 8 * g * t + HOTA_SLOT_BYTES * f
+            buf[i, o:o + 4 * g] = st["gt_count"].view(np.uint8)
+            buf[i, o + 4 * g:o + 4 * (g + t)] = st["track_count"].view(np.uint8)
+        return buf.reshape(-1)
+
+    def potential_matrix(self, image):
+        """The pot block of one image, [max_gt_ids, max_track_ids] float64 (a copy)."""
+        return self.images[image]["pot"].copy()
+
+    def finish(self):
+        """{"counts" [N, 8] int64, "alpha_counts" [N, 19, 4] int64, "alpha_sums" [N, 19, 4] float64, "match" [N, max_frames,
+        128] int32: per logged frame and kept ground-truth row the track id taken, else 0}.  Reads the state only: the
+        sequence may go on."""
+        imgs = self.images or []
+        n = len(imgs)
+        counts = np.zeros((n, 8), dtype=np.int64)
+        alpha_counts = np.zeros((n, HOTA_ALPHAS, 4), dtype=np.int64)
+        alpha_sums = np.zeros((n, HOTA_ALPHAS, 4), dtype=np.float64)
+        match = np.zeros((n, self.max_frames, MAX_GT_USED), dtype=np.int32)
+        thresholds = [alpha - HOTA_EPS for alpha in hota_alphas()]
+        for i, st in enumerate(imgs):
+            gc, tc, pot = st["gt_count"], st["track_count"], st["pot"]
+            with np.errstate(all="ignore"):
+                both = (gc[:, None].astype(np.int64) + tc[None, :].astype(np.int64)).astype(np.float64)
+                align = np.where(pot > 0, pot / np.where(pot > 0, both - pot, 1.0), 0.0)
+            tp = [0] * HOTA_ALPHAS
+            loc = [0.0] * HOTA_ALPHAS
+            hist = {}                                                    # (identity, column) -> 20 bins
+            for f, slot in enumerate(st["log"]):
+                gid, col = slot["gid"].astype(np.int64), slot["tid"].astype(np.int64) - 1
+                s = _iou_matrix(slot["grect"], slot["trect"])
+                score = align[np.ix_(gid, col)] * s if len(gid) and len(col) else np.zeros((len(gid), len(col)))
+                took = [-1] * len(gid)
+                for a, t in hungarian_max(score):
+                    if score[a, t] > 0:
+                        took[a] = t
+                part = [0.0] * HOTA_ALPHAS
+                for a, t in enumerate(took):                             # ascending ground-truth row
+                    if t < 0:
+                        continue
+                    iou = float(s[a, t])
+                    reach = sum(1 for thr in thresholds if not iou < thr)
+                    hist.setdefault((int(gid[a]), int(col[t])), [0] * HOTA_BINS)[reach] += 1
+                    for k in range(reach):
+                        tp[k] += 1
+                        part[k] = part[k] + iou
+                    match[i, f, a] = col[t] + 1
+                for k in range(HOTA_ALPHAS):
+                    loc[k] = loc[k] + part[k]
+            sums = np.zeros((HOTA_ALPHAS, 3))
+            cells = {}
+            for (ident, column), bins in hist.items():
+                cells.setdefault(ident, []).append((column, bins))
+            for ident in sorted(cells):                                  # identities ascending, each from 0.0
+                row = np.zeros((HOTA_ALPHAS, 3))
+                for column, bins in sorted(cells[ident]):                # track ids ascending
+                    for k in range(HOTA_ALPHAS):
+                        cnt = sum(bins[k + 1:])
+                        if cnt == 0:
+                            continue
+                        cd = float(cnt)
+                        row[k, 0] = row[k, 0] + cd * (cd / (float(int(gc[ident]) + int(tc[column])) - cd))
+                        row[k, 1] = row[k, 1] + cd * (cd / float(gc[ident]))
+                        row[k, 2] = row[k, 2] + cd * (cd / float(tc[column]))
+                sums = sums + row
+            counts[i] = (st["frames"], len(st["log"]), st["gt_dets"], st["dets"], int((gc > 0).sum()), int((tc > 0).sum()),
+                         st["status"], 0)
+            for k in range(HOTA_ALPHAS):
+                alpha_counts[i, k] = (tp[k], st["gt_dets"] - tp[k], st["dets"] - tp[k], 0)
+                alpha_sums[i, k] = (loc[k], sums[k, 0], sums[k, 1], sums[k, 2])
+        return {"counts": counts, "alpha_counts": alpha_counts, "alpha_sums": alpha_sums, "match": match}
+
+    def compute(self):
+        """{"overall", "per_agent", "per_image"}: hota_figures() of finish().  Raises DnError naming any sticky status bit."""
+        return hota_figures(self.finish(), self.batch_size, "HostHota")
+
+    def matches(self, image):
+        """finish()'s match rows of one image, [logged, 128] int32: per logged frame and kept ground-truth row (in kept
+        order) the track id taken, else 0."""
+        return self.finish()["match"][image, :len(self.images[image]["log"])].copy()
+
+
+class Hota:
+    """HOTA on the GPU beside ClearMot and Identity: update() after every frame enqueues dn_hota_step on torch's current
+    stream (the state -- per image a header, the fp64 potential-match matrix, max_frames log slots of 9232 bytes and the two
+    per-id counts -- lives on the device, is allocated on first use and is never read back), so forward + detect() +
+    Sort.update() + ClearMot.update() + Identity.update() + Hota.update() can be one captured graph (graph.GraphedStep).
+    finish() enqueues dn_hota_finish -- every logged frame of every image matched at once, one wave per frame, then one
+    fold per image -- and returns device tensors, so it may be captured too; it reads the state only and the sequence may
+    go on.  HostHota is the reference both equal bit for bit, and states the contract.
+
+    What it costs: the state is 8 max_gt_ids max_track_ids + 9232 max_frames bytes per image (4.5 MB at the defaults), and
+    Hota owns the scratch of finish(), allocated at the first finish(): 80 bytes per (identity, track id) cell, about 20 MB
+    per image at the defaults (256 x 1024), zeroed by every finish().  The tools pass smaller ids where they know the
+    sequence (tools/hota_probe.py: 64 x 512 -- a sequence has tens of identities and a few hundred track ids;
+    tools/track/eval_sort.py: its --max_gt_ids / --max_track_ids) and max_frames = the frames they run.
+
+    update(tracks, gt) takes ClearMot.update()'s inputs (device tensors) and returns {"potential" [N, G] float64}.
+    compute() is finish() plus the copy of three small tensors and raises DnError naming the sticky status bits -- never a
+    silently truncated metric.
+
+    GraphedStep runs its step three times to warm up before it captures and those runs are counted and logged: call
+    reset() after constructing the GraphedStep, before the first replay that counts (as with Identity and ClearMot)."""
+
+    def __init__(self, batch_size, scale=1.0, max_gt_ids=256, max_track_ids=1024, max_frames=256):
+        (self.batch_size, self.scale, self.max_gt_ids, self.max_track_ids,
+         self.max_frames) = _check_hota_params(batch_size, scale, max_gt_ids, max_track_ids, max_frames)
+        self.state = None            # uint8 [hota_state_bytes(N, ...)] on the device, viewed from an int64 allocation
+        self.work = None             # finish()'s scratch, allocated by the first finish()
+        self.n_images = 0
+
+    def _sizes(self):
+        return self.n_images, self.max_gt_ids, self.max_track_ids, self.max_frames
+
+    def reset(self):
+        """Zero every count, the potential matrix, the log and the status words (one launch on the current stream)."""
+        if self.state is not None:
+            from .ops import _ptr, _stream
+            _lib.check(_lib.load().dn_hota_reset(_ptr(self.state), *self._sizes(), _stream()), "dn_hota_reset")
+
+    def update(self, tracks, gt):
+        from .ops import _need_gpu, _ptr, _stream
+        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
+                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise _lib.DnError("Hota.update needs device tensors (%s is %s); HostHota is the numpy reference"
+                                   % (name, type(t).__name__))
+        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
+        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
+        if tid.dim() != 2 or gids.dim() != 2:
+            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
+        (n, m), g = tid.shape, gids.shape[1]
+        if not 1 <= m <= MAX_TRACKS:
+            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
+        if not 1 <= g <= MAX_GT_ROWS:
+            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
+        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
+                or gcount.numel() != n):
+            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
+                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
+        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
+        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        lib = _lib.load()
+        dev = rect.device
+        if self.state is None:
+            nbytes = int(lib.dn_hota_state_bytes(n, self.max_gt_ids, self.max_track_ids, self.max_frames))
+            if nbytes != hota_state_bytes(n, self.max_gt_ids, self.max_track_ids, self.max_frames) or nbytes % 8:
+                raise _lib.DnError("dn_hota_state_bytes(%d, %d, %d, %d) = %d" % (n, self.max_gt_ids, self.max_track_ids,
+                                                                                self.max_frames, nbytes))
+            self.state = torch.empty(nbytes // 8, dtype=torch.int64, device=dev).view(torch.uint8)
+            self.n_images = n
+            self.reset()
+        if n != self.n_images:
+            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        out = {"potential": torch.empty((n, g), dtype=torch.float64, device=dev)}
+        _lib.check(lib.dn_hota_step(_ptr(rect), _ptr(tid), _ptr(tcount), n, m, _ptr(boxes), _ptr(gids), _ptr(gcount), g,
+                                    self.scale, self.max_gt_ids, self.max_track_ids, self.max_frames, _ptr(self.state),
+                                    _ptr(out["potential"]), _stream()), "dn_hota_step")
+        return out
+
+    def finish(self):
+        """Enqueue dn_hota_finish on the current stream (three launches) -> device tensors {"counts" [N, 8] int64,
+        "alpha_counts" [N, 19, 4] int64, "alpha_sums" [N, 19, 4] float64, "match" [N, max_frames, 128] int32} as
+        HostHota.finish() returns them.  Reads the state only."""
+        from .ops import _ptr, _stream
+        if self.state is None:
+            raise _lib.DnError("Hota.finish: no frame was evaluated yet")
+        lib = _lib.load()
+        dev = self.state.device
+        if self.work is None:
+            nbytes = int(lib.dn_hota_work_bytes(*self._sizes()))
+            if nbytes != hota_work_bytes(*self._sizes()) or nbytes % 8:
+                raise _lib.DnError("dn_hota_work_bytes%r = %d" % (self._sizes(), nbytes))
+            self.work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        n = self.n_images
+        out = {"counts": torch.empty((n, 8), dtype=torch.int64, device=dev),
+               "alpha_counts": torch.empty((n, HOTA_ALPHAS, 4), dtype=torch.int64, device=dev),
+               "alpha_sums": torch.empty((n, HOTA_ALPHAS, 4), dtype=torch.float64, device=dev),
+               "match": torch.empty((n, self.max_frames, MAX_GT_USED), dtype=torch.int32, device=dev)}
+        _lib.check(lib.dn_hota_finish(_ptr(self.state), *self._sizes(), _ptr(self.work), _ptr(out["counts"]),
+                                      _ptr(out["alpha_counts"]), _ptr(out["alpha_sums"]), _ptr(out["match"]), _stream()),
+                   "dn_hota_finish")
+        return out
+
+    def status_words(self):
+        """The status word of every image (numpy int32): one small copy, waits for the device."""
+        if self.state is None:
+            return np.zeros(0, dtype=np.int32)
+        words = self.state.view(self.n_images, -1)[:, 32:36].contiguous().cpu().numpy()
+        return words.view(np.int32).reshape(-1).copy()
+
+    def state_bytes(self):
+        """A host copy of the whole state (numpy uint8); HostHota.state_bytes() is its reference."""
+        return self.state.cpu().numpy().copy() if self.state is not None else np.zeros(0, dtype=np.uint8)
+
+    def potential_matrix(self, image):
+        """A host copy of the pot block of one image, [max_gt_ids, max_track_ids] float64."""
+        g, t = self.max_gt_ids, self.max_track_ids
+        block = self.state.view(self.n_images, -1)[image, HOTA_HEADER_BYTES:HOTA_HEADER_BYTES + 8 * g * t]
+        return block.contiguous().cpu().numpy().view(np.float64).reshape(g, t).copy()
+
+    def compute(self):
+        """finish() and the copy of its three small tensors, then HostHota.compute()'s dict on the host.  Raises DnError
+        naming any sticky status bit."""
+        fin = self.finish()
+        return hota_figures({key: fin[key].cpu().numpy() for key in ("counts", "alpha_counts", "alpha_sums")},
+                            self.batch_size, "Hota")
+
+    def matches(self, image):
+        """finish() and the copy of one image's match rows, [logged, 128] int32, as HostHota.matches()."""
+        fin = self.finish()
+        logged = int(fin["counts"][image, 1])
+        return fin["match"][image, :logged].cpu().numpy().copy()

@@ -789,6 +789,82 @@ int dn_idf_step(const double* rect, const int32_t* id, const int32_t* count, int
 int dn_idf_finish(const void* state, int n_images, int max_gt_ids, int max_track_ids, int64_t* out_counts,
                   int32_t* out_match, void* stream);
 
+/* ------------------------------------------------------------------------
+ * HOTA of the tracks (disconet_amd/csrc/hota_eval.hip): the higher-order tracking accuracy (Luiten et al., "HOTA: A Higher
+ * Order Metric for Evaluating Multi-Object Tracking") with its detection, association and localisation parts, the third
+ * family the MOT benchmark's evaluation kit prints beside CLEAR and identity.  What the kit computes is recalled, not
+ * pinned: this contract is the project's own and tracking.HostHota (numpy / float64) is its
+ * normative statement, which the kernels equal bit for bit.  The frame matching is weighted by a global alignment score
+ * that is known only after the last frame, so the sequence is seen twice: dn_hota_step (graph-capturable behind
+ * dn_track_step, one launch) adds the frame to the potential-match matrix and logs its rectangles in the state;
+ * dn_hota_finish (graph-capturable, three launches: the zeroing of `work`, the match over a (max_frames, n_images) grid,
+ * the fold) matches every logged frame.  No host synchronisation, no allocation; a launch depends on the shapes only.
+ *   Inputs of dn_hota_step: dn_idf_step's without a threshold (HOTA has no single IoU threshold), and 1 <= max_frames <=
+ *   4096.  Ground-truth ids are 0 .. max_gt_ids - 1, track ids 1 .. max_track_ids; track id t owns column t - 1.
+ *   All arithmetic is fp64 in the order written here, + - * / and sqrt only, never contracted.
+ *   Alphas: alpha_k = 0.05 * (k + 1) as an fp64 product, k = 0 .. 18.  A pair with IoU s counts at alpha k when
+ *   not (s < alpha_k - 2^-52) (the kit's epsilon: without it an IoU of 3/20 misses 0.05 * 3 = 0.15000000000000002).
+ *   dn_hota_step, per image and call:
+ *   1. frames += 1.  If logged == max_frames: status bit 32 is set and nothing else of this image changes (its
+ *      out_potential row is 0); the figures are then those of the first max_frames frames.
+ *   2. Ground truth: the V kept rows of dn_mot_step's step 2, by the same rule in the same order (status bits 2, 4, 1, 8).
+ *   3. Reported rows below the count, ascending: an id outside 1 .. max_track_ids sets status bit 16 and the row is
+ *      ignored; an id that a lower counted row of this frame carries sets status bit 64 and the row is ignored (HOTA matches
+ *      one-to-one per id: unlike dn_idf_step a second row is not counted).  The rest are the C <= 128 columns; a column
+ *      whose rectangle has a non-finite member stays a column with IoU 0 to everything (a false positive).
+ *   4. gt_count[id] += 1 and gt_dets += 1 per kept row; track_count[id - 1] += 1 and dets += 1 per column.
+ *   5. s[a][t] is dn_mot_step's step 3.  rs[a] = the sum of s[a][.] over t ascending, cs[t] = the sum of s[.][t] over a
+ *      ascending, both from 0.0.  For every pair with s > 0, in (a, t) row-major order:
+ *      pot[id_a][id_t - 1] += s / ((rs[a] + cs[t]) - s).  Ids are unique within a frame after steps 2 and 3, so a cell
+ *      gets at most one add per call: no atomics, a deterministic result.
+ *   6. Log slot `logged` is written, then logged += 1.  A slot is 9232 bytes: int32 V, C and 8 bytes of 0; int32 gid[128],
+ *      int32 tid[128]; fp64 gt_rect[128][4], fp64 track_rect[128][4] (the measured rectangles, their bits copied).  Unused
+ *      entries stay 0.
+ *   out_potential [n][g] fp64: per ground-truth row the sum over t ascending (from 0.0) of the terms it added, 0 for a row
+ *   that was not kept.  Every word is written on every call.
+ *   State (caller-owned, on the device, 8-byte aligned), per image in this order: a 64-byte header {int64 frames, logged,
+ *   gt_dets, dets at bytes 0..31; int32 status at bytes 32..35; the rest 0}, fp64 pot[max_gt_ids][max_track_ids] row-major,
+ *   max_frames log slots, int32 gt_count[max_gt_ids], int32 track_count[max_track_ids], padded to a multiple of 8 bytes.
+ *   dn_hota_state_bytes is n times that, 0 for refused arguments.  Status bits are sticky until dn_hota_reset, which
+ *   zeroes everything.  Two runs write the same bytes.
+ *   dn_hota_finish reads the state and never writes it: it may run after any frame and the sequence may go on.  `work` is
+ *   scratch of dn_hota_work_bytes (per image 160 + 160 max_frames + 80 max_gt_ids max_track_ids bytes: the per-alpha
+ *   TP words, the per-frame loc partials and a 20-bin histogram per cell; 0 for refused arguments), 8-byte aligned; its
+ *   contents are unspecified and the call zeroes it itself.  Per image:
+ *   1. A[i][j] = pot / ((gt_count[i] + track_count[j]) - pot) where pot > 0, else 0.
+ *   2. Every logged frame, independently of the others: s is taken again from the logged rectangles (the same function,
+ *      the same bits); score[a][t] = A[gid_a][tid_t - 1] * s[a][t]; dn_track_step's shortest-augmenting-path step on
+ *      cost = -score with the row side, the tie rules and the step limit of dn_mot_step's step 5; a pair is kept only when
+ *      its score is > 0.  For a kept pair let K be the number of alphas at which it counts (a prefix, the alphas ascend):
+ *      hist[gid][tid - 1][K] += 1 (an integer atomic), and for k < K: TP_k += 1, loc_k += s.  Per frame and alpha:
+ *      FN_k += V - TP_k(frame), FP_k += C - TP_k(frame).
+ *   3. The order of loc_k is two-level so that frames can run in parallel: a frame's partial sum over its kept pairs in
+ *      ascending ground-truth row order from 0.0, then the frame partials in ascending slot order from 0.0.
+ *   4. Per alpha k the matched count of a cell is c = the sum of its hist bins > k; assa_k = sum of c * (c / ((gt_count +
+ *      track_count) - c)), assre_k = sum of c * (c / gt_count), asspr_k = sum of c * (c / track_count): each per identity
+ *      over ascending track id from 0.0, then over the identities ascending from 0.0 (a cell with c = 0 adds +0.0).
+ *   out_counts [n][8] int64: frames, logged, GT_Dets, Dets, GT_IDs (gt_count > 0), IDs (track_count > 0), status, 0.
+ *   out_alpha_counts [n][19][4] int64: TP, FN, FP, 0.  out_alpha_sums [n][19][4] fp64: loc, assa, assre, asspr.
+ *   out_match [n][max_frames][128] int32 (may be null): per logged frame and kept ground-truth row, in kept order, the
+ *   track id taken, else 0; slots that are not logged hold 0.
+ *   From these, on the host (tracking.hota_figures), per image, agent and overall, counts and sums added in image order
+ *   (adding the numerators is the kit's TP-weighted combination), per alpha: DetA = TP / max(1, TP + FN + FP), DetRe = TP
+ *   / max(1, TP + FN), DetPr = TP / max(1, TP + FP); AssA = assa / max(1, TP), AssRe, AssPr alike; LocA = loc / TP, 1.0
+ *   when TP = 0; HOTA = sqrt(DetA * AssA).  Each figure is its mean over the 19 alphas (the fold x = x + v from 0.0,
+ *   divided by 19); beside them HOTA(0), LocA(0) and HOTALocA(0) = HOTA(0) * LocA(0) at k = 0.
+ *   The match kernel keeps a frame's score matrix in LDS (8 * 128 * 129 bytes beside 17 KB of work arrays, whatever the
+ *   arguments are: V and C are read from the log); a launch that would not fit 160 KB is refused.
+ * ------------------------------------------------------------------------ */
+size_t dn_hota_state_bytes(int n_images, int max_gt_ids, int max_track_ids, int max_frames);
+size_t dn_hota_work_bytes(int n_images, int max_gt_ids, int max_track_ids, int max_frames);
+int dn_hota_reset(void* state, int n_images, int max_gt_ids, int max_track_ids, int max_frames, void* stream);
+int dn_hota_step(const double* rect, const int32_t* id, const int32_t* count, int n_images, int m, const float* gt_boxes,
+                 const int32_t* gt_ids, const int32_t* gt_count, int g, double scale, int max_gt_ids, int max_track_ids,
+                 int max_frames, void* state, double* out_potential, void* stream);
+int dn_hota_finish(const void* state, int n_images, int max_gt_ids, int max_track_ids, int max_frames, void* work,
+                   int64_t* out_counts, int64_t* out_alpha_counts, double* out_alpha_sums, int32_t* out_match,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

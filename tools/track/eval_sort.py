@@ -6,11 +6,13 @@ tracking.ClearMot.update() (behind forward -> postprocess.detect() with --source
 counters.  Prints one line per agent and one overall: MOTA, MOTP, TP, FP, FN, IDSW, Frag, MT / PT / ML.  Behind them, the
 identity figures in the same form (IDF1, IDP, IDR, IDTP / IDFP / IDFN, Dets, GT_Dets, IDs, GT_IDs): tracking.Identity.update()
 runs in the same captured step, and Identity.compute() solves the one global assignment on the device and copies 8 words
-per image.
+per image.  Behind those, HOTA with its detection, association and localisation parts (HOTA, DetA, AssA, DetRe, DetPr,
+AssRe, AssPr, LocA, HOTA(0), LocA(0), HOTALocA(0)): tracking.Hota.update() runs in the same captured step and logs every
+frame on the device (--max_frames slots), and Hota.compute() matches all logged frames of all images at once there.
 
     python tools/track/eval_sort.py --com disco [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
-        [--max_gt_ids 256] [--max_track_ids 1024]
+        [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES]
 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
 noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
@@ -49,8 +51,11 @@ def main(argv=None):
     ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
     ap.add_argument("--max_gt_ids", type=int, default=256)
     ap.add_argument("--max_track_ids", type=int, default=1024, help="the identity figures count track ids 1 .. this")
+    ap.add_argument("--max_frames", type=int, default=None, help="frames HOTA logs per image (default: max(--frames, 1))")
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
+    if args.max_frames is None:
+        args.max_frames = max(args.frames, 1)
     if args.com != "disco":
         raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
@@ -62,9 +67,11 @@ def main(argv=None):
     mot = tracking.ClearMot(args.batch, iou_threshold=args.eval_iou, scale=scale, max_gt_ids=args.max_gt_ids)
     idf = tracking.Identity(args.batch, iou_threshold=args.eval_iou, scale=scale, max_gt_ids=args.max_gt_ids,
                             max_track_ids=args.max_track_ids)
+    hota = tracking.Hota(args.batch, scale=scale, max_gt_ids=args.max_gt_ids, max_track_ids=args.max_track_ids,
+                         max_frames=args.max_frames)
 
     def evaluate(tracks):
-        return mot.update(tracks, gt), idf.update(tracks, gt)
+        return mot.update(tracks, gt), idf.update(tracks, gt), hota.update(tracks, gt)
 
     if args.source == "boxes":
         seq = make_track_sequence(args.frames, n, seed=args.seed, truth=True)
@@ -111,6 +118,7 @@ def main(argv=None):
     sort.reset()                       # the warm-up runs of the capture advanced the tracker ...
     mot.reset()                        # ... and were counted
     idf.reset()
+    hota.reset()                       # ... and logged
 
     for frame in range(args.frames):
         load(frame)
@@ -127,6 +135,10 @@ def main(argv=None):
     for a, row in enumerate(identity["per_agent"]):
         print(tracking.idf_line("agent %d" % a, row))
     print(tracking.idf_line("overall", identity["overall"]))
+    higher = hota.compute()            # every logged frame matched on the device; raises on a status bit (a full log too)
+    for a, row in enumerate(higher["per_agent"]):
+        print(tracking.hota_line("agent %d" % a, row))
+    print(tracking.hota_line("overall", higher["overall"]))
 
 
 if __name__ == "__main__":
