@@ -34,6 +34,25 @@ struct PerDeviceFlag {
   }
 };
 
+// The kernel's static LDS in bytes, read once per device; with dynamic_most > 0 the same first call reserves that much
+// dynamic LDS for it.  `flag` and `cache` (64 words) are function-local statics of the caller.  -1: the attributes cannot
+// be read, -2: the dynamic LDS cannot be reserved.
+inline int static_lds_of(const void* kernel, PerDeviceFlag& flag, int* cache, int dynamic_most) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  bool& ready = flag.done[dev & 63];
+  if (!ready) {
+    hipFuncAttributes attr;
+    if (hipFuncGetAttributes(&attr, kernel) != hipSuccess) return -1;
+    if (dynamic_most > 0 &&
+        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dynamic_most) != hipSuccess)
+      return -2;
+    cache[dev & 63] = (int)attr.sharedSizeBytes;
+    ready = true;
+  }
+  return cache[dev & 63];
+}
+
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(DN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
@@ -72,3 +91,17 @@ extern SpLastForm g_sp_last_form;
 
 #define DN_REQUIRE(cond, ...) \
   do { if (!(cond)) return dn::fail(DN_ERR_ARG, __VA_ARGS__); } while (0)
+
+// The arguments that the evaluation steps behind the tracker share (dn_mot_step, dn_idf_step, dn_hota_step): the reported
+// tracks, the ground truth, the state, M, G and scale, under the names of include/disconet_hip.h.
+#define DN_REQUIRE_EVAL_STEP(who, max_m, max_g)                                                                \
+  DN_REQUIRE(rect, who ": null rect");                                                                         \
+  DN_REQUIRE(id, who ": null id");                                                                             \
+  DN_REQUIRE(count, who ": null count");                                                                       \
+  DN_REQUIRE(gt_boxes, who ": null gt_boxes");                                                                 \
+  DN_REQUIRE(gt_ids, who ": null gt_ids");                                                                     \
+  DN_REQUIRE(gt_count, who ": null gt_count");                                                                 \
+  DN_REQUIRE(state, who ": null state");                                                                       \
+  DN_REQUIRE(m >= 1 && m <= (max_m), who ": M = %d track rows, must be in [1, %d]", m, (max_m));              \
+  DN_REQUIRE(g >= 1 && g <= (max_g), who ": G = %d ground-truth rows, must be in [1, %d]", g, (max_g));       \
+  DN_REQUIRE(std::isfinite(scale) && scale > 0, who ": scale = %g, must be finite and > 0", scale)

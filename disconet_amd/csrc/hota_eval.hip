@@ -5,12 +5,12 @@
 // include/disconet_hip.h; the host reference that defines the bits is tracking.HostHota.  All arithmetic is fp64 in a fixed
 // order, + - * / and sqrt only, and every function that touches fp64 carries `#pragma clang fp contract(off)`.
 //
-// hota_step_kernel: one launch per frame, one workgroup of ONE wave per image, as mot_step_kernel and idf_step_kernel (the
-// measure and dedupe phases and row_rect / rect_iou are copied here; mot_eval.hip and idf_eval.hip are not touched):
-//   measure    lanes over ground-truth rows, 64 at a time in row order -> the first 128 valid rows in LDS
-//   dedupe     a kept row whose id a lower kept row carries leaves (stable compaction)
+// hota_step_kernel: one launch per frame, one workgroup of ONE wave per image, as mot_step_kernel and idf_step_kernel; the
+// single-wave form, the ground-truth phase, rect_iou, the assignment, the kept-slot lookup and the compaction of the ids
+// present are track_eval_device.h's:
 //   tracks     lanes over reported rows: the id's range (status bit 16), an id a lower row carries (bit 64), ballot prefix
 //              -> the columns in LDS, in row order
+//   measure    measure_ground_truth -> the rows used
 //   iou        lanes over (ground truth, column) pairs -> the matrix in LDS, [ground truths][ld], ld odd as in mot_eval.hip
 //   sums       lanes over rows (rs) and over columns (cs), each a serial walk in ascending order
 //   potential  lanes over rows, each walks its columns in ascending order: one term per overlapping pair into the cell of
@@ -23,39 +23,34 @@
 // hota_match_kernel: a grid of (max_frames, n_images) workgroups of ONE wave; a block whose slot is not logged clears its
 // row of out_match and returns.  The slot's ids and rectangles -> LDS; lanes over pairs: the IoU again (same function, same
 // bits), times the alignment score A of the pair's cell (read from pot, gt_count, track_count in place) -> the score matrix
-// in LDS, [V][C | 1]; the shortest-augmenting-path step of mot_eval.hip (its own copy, lanes over columns); per kept pair
+// in LDS, [V][C | 1]; assign_rows on it (lanes over columns); per kept pair
 // the IoU once more and K, the number of alphas it counts at; one integer atomic per kept pair into the cell's 20-bin
 // histogram in `work`; lane k < 19 walks the rows in ascending order for the frame's TP_k (one integer atomic per alpha
 // into `work`) and its loc partial (written to the frame's own words of `work`, never added atomically).
 // V and C come from the log, so the launch reserves the largest matrix whatever the arguments are: 8 * 128 * 129 B of
 // dynamic LDS beside 17 KB of work arrays, one workgroup per CU.
 //
-// hota_fold_kernel: one workgroup of one wave per image.  The track ids present are compacted into LDS (ballot prefix);
+// hota_fold_kernel: one workgroup of one wave per image.  The track ids present are compacted into LDS (compact_present);
 // the identities present are taken 64 at a time in ascending order, one per lane: the lane walks the present track ids in
 // ascending order, turns a cell's bins into the 19 matched counts (suffix sums) and adds the cell's three terms per alpha
 // to its row sums; the row sums go to LDS and lanes 0..56 (one per alpha and sum) add the chunk's rows to their running
 // totals in ascending identity order.  Lane k < 19 adds the frames' loc partials in slot order and writes the alpha's
 // words.  Nothing is read back, nothing is allocated; two runs write the same bytes.
-#include <climits>
 #include <cmath>
 
 #include "dn_internal.h"
+#include "track_eval_device.h"
 
 namespace {
 
-constexpr int kThreads = 64;
-constexpr int kMaxM = 128;          // reported track rows per image
-constexpr int kMaxV = 128;          // valid ground-truth rows used per image
-constexpr int kMaxG = 1024;         // ground-truth rows per image
-constexpr int kMaxGtIds = 1024;     // identities per image
-constexpr int kMaxTrackIds = 2048;  // track ids per image
+using namespace dn::trk;
+
 constexpr int kMaxFrames = 4096;    // log slots per image
 constexpr int kHeaderBytes = 64;    // int64 frames, logged, gt_dets, dets; int32 status; 28 spare bytes
 constexpr int kSlotBytes = 16 + 4 * (kMaxV + kMaxM) + 32 * (kMaxV + kMaxM);   // 9232
 constexpr int kAlphas = 19;
 constexpr int kBins = 20;           // K = 0 .. 19 of a kept pair
 constexpr int kMatchLd = kMaxM | 1;
-constexpr int kLdsPerCu = 160 * 1024;
 constexpr double kEps = 2.220446049250313e-16;   // 2^-52
 
 struct Params {
@@ -71,47 +66,6 @@ __host__ __device__ inline size_t image_bytes(int ids, int tids, int frames) {
 // work, per image: int64 tp[20]; fp64 loc partial [frames][20]; int32 hist[ids][tids][20]
 __host__ __device__ inline size_t work_image_bytes(int ids, int tids, int frames) {
   return 8 * (size_t)kBins + 8 * (size_t)kBins * (size_t)frames + 4 * (size_t)kBins * (size_t)ids * (size_t)tids;
-}
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ int below(unsigned long long mask, int lane) {
-  return __popcll(mask & ((1ull << lane) - 1ull));
-}
-
-// The rectangle of a row (x, y, w, h, sin, cos): its four corners in the order and arithmetic of tracking._corners (the
-// hypot written sqrt(s s + c c)), each multiplied by scale, then min / max.  Returns whether every corner is finite.
-__device__ __forceinline__ bool row_rect(const float* __restrict__ b, double scale, double* r) {
-#pragma clang fp contract(off)
-  const double bx = b[0], by = b[1], w = b[2], h = b[3], sn = b[4], cs = b[5];
-  const double len = sqrt(sn * sn + cs * cs);
-  const double n = len > 1e-12 ? len : (len != len ? len : 1e-12);
-  const double s = sn / n, c = cs / n;
-  const double dx = w / 2.0, dy = h / 2.0;
-  const double lx[4] = {-dx, dx, dx, -dx}, ly[4] = {-dy, -dy, dy, dy};
-  double x[4], y[4];
-  bool fin = true;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    x[k] = (lx[k] * c - ly[k] * s + bx) * scale;
-    y[k] = (lx[k] * s + ly[k] * c + by) * scale;
-    fin = fin && isfinite(x[k]) && isfinite(y[k]);
-  }
-  r[0] = fmin(fmin(x[0], x[1]), fmin(x[2], x[3]));
-  r[1] = fmin(fmin(y[0], y[1]), fmin(y[2], y[3]));
-  r[2] = fmax(fmax(x[0], x[1]), fmax(x[2], x[3]));
-  r[3] = fmax(fmax(y[0], y[1]), fmax(y[2], y[3]));
-  return fin;
-}
-
-__device__ __forceinline__ double rect_iou(double a0, double a1, double a2, double a3, double b0, double b1, double b2,
-                                           double b3) {
-#pragma clang fp contract(off)
-  const double w = fmin(a2, b2) - fmax(a0, b0);
-  const double h = fmin(a3, b3) - fmax(a1, b1);
-  if (!(w > 0 && h > 0)) return 0.0;
-  const double inter = w * h;
-  const double uni = (a2 - a0) * (a3 - a1) + (b2 - b0) * (b3 - b1) - inter;
-  return uni > 0 ? inter / uni : 0.0;
 }
 
 __global__ void __launch_bounds__(kThreads) hota_step_kernel(const double* __restrict__ rect, const int* __restrict__ tid,
@@ -149,38 +103,6 @@ __global__ void __launch_bounds__(kThreads) hota_step_kernel(const double* __res
     return;
   }
 
-  // ---- measure: the first kMaxV valid ground-truth rows, in row order
-  const int c = clampi(gt_count[img], g);
-  int nv = 0;
-  for (int base = 0; base < c; base += kThreads) {
-    const int r = base + lane;
-    bool ok = false;
-    double q[4] = {0, 0, 0, 0};
-    int ident = 0;
-    if (r < c) {
-      const bool fin = row_rect(gt_boxes + 6 * ((size_t)img * g + r), p.scale, q);
-      if (!(fin && q[2] - q[0] > 0 && q[3] - q[1] > 0)) {
-        flags |= 2u;
-      } else {
-        ident = gt_ids[(size_t)img * g + r];
-        if (ident < 0 || ident >= ids) flags |= 4u;
-        else ok = true;
-      }
-    }
-    const unsigned long long mask = __ballot(ok);
-    const int pos = nv + below(mask, lane);
-    if (ok) {
-      if (pos < kMaxV) {
-        grect[0][pos] = q[0]; grect[1][pos] = q[1]; grect[2][pos] = q[2]; grect[3][pos] = q[3];
-        grow[pos] = r;
-        gident[pos] = ident;
-      } else {
-        flags |= 1u;
-      }
-    }
-    nv += __popcll(mask);
-  }
-  const int V0 = nv < kMaxV ? nv : kMaxV;
   // the reported rows' ids
   const int K = clampi(tcount[img], m);
   for (int t = lane; t < K; t += kThreads) traw[t] = tid[(size_t)img * m + t];
@@ -218,42 +140,9 @@ __global__ void __launch_bounds__(kThreads) hota_step_kernel(const double* __res
     C += __popcll(mask);
   }
 
-  // ---- dedupe: a kept row whose id a lower kept row carries leaves; the others close ranks
-  bool keep[kMaxV / kThreads];
-  double kq[kMaxV / kThreads][4];
-  int krow[kMaxV / kThreads], kid[kMaxV / kThreads];
-#pragma unroll
-  for (int h = 0; h < kMaxV / kThreads; ++h) {
-    const int j = h * kThreads + lane;
-    keep[h] = j < V0;
-    krow[h] = 0; kid[h] = 0;
-    kq[h][0] = 0; kq[h][1] = 0; kq[h][2] = 0; kq[h][3] = 0;
-    if (j < V0) {
-      kid[h] = gident[j];
-      krow[h] = grow[j];
-      kq[h][0] = grect[0][j]; kq[h][1] = grect[1][j]; kq[h][2] = grect[2][j]; kq[h][3] = grect[3][j];
-      for (int i = 0; i < j; ++i)
-        if (gident[i] == kid[h]) {
-          keep[h] = false;
-          flags |= 8u;
-          break;
-        }
-    }
-  }
-  __syncthreads();                                 // every kept row is in registers before a slot is rewritten
-  int V = 0;
-#pragma unroll
-  for (int h = 0; h < kMaxV / kThreads; ++h) {
-    const unsigned long long mask = __ballot(keep[h]);
-    const int dst = V + below(mask, lane);
-    if (keep[h]) {
-      grect[0][dst] = kq[h][0]; grect[1][dst] = kq[h][1]; grect[2][dst] = kq[h][2]; grect[3][dst] = kq[h][3];
-      grow[dst] = krow[h];
-      gident[dst] = kid[h];
-    }
-    V += __popcll(mask);
-  }
-  __syncthreads();
+  // ---- measure: the ground-truth rows used (its barriers stand between the columns above and the pairs)
+  const int V = measure_ground_truth(gt_boxes + 6 * (size_t)img * g, gt_ids + (size_t)img * g, clampi(gt_count[img], g), ids,
+                                     p.scale, lane, grect, grow, gident, flags, [] {});
 
   // ---- iou: lanes over (ground truth, column)
   for (int e = lane; e < V * C; e += kThreads) {
@@ -307,8 +196,7 @@ __global__ void __launch_bounds__(kThreads) hota_step_kernel(const double* __res
     d[0] = trect[0][t]; d[1] = trect[1][t]; d[2] = trect[2][t]; d[3] = trect[3][t];
     tcnt[ctid[t] - 1] = tcnt[ctid[t] - 1] + 1;
   }
-  const unsigned all = (__any(flags & 1u) ? 1u : 0u) | (__any(flags & 2u) ? 2u : 0u) | (__any(flags & 4u) ? 4u : 0u) |
-                       (__any(flags & 8u) ? 8u : 0u) | (__any(flags & 16u) ? 16u : 0u) | (__any(flags & 64u) ? 64u : 0u);
+  const unsigned all = wave_or(flags);
   if (lane == 0) {
     sint[0] = V;
     sint[1] = C;
@@ -322,13 +210,8 @@ __global__ void __launch_bounds__(kThreads) hota_step_kernel(const double* __res
 
   // ---- outputs: every row once; a kept row is found in the ascending list of the rows kept
   for (int r = lane; r < g; r += kThreads) {
-    int lo = 0, hi = V;                            // first slot with grow >= r
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (grow[mid] < r) lo = mid + 1;
-      else hi = mid;
-    }
-    out_potential[(size_t)img * g + r] = lo < V && grow[lo] == r ? prow[lo] : 0.0;
+    const int a = kept_slot(grow, V, r);
+    out_potential[(size_t)img * g + r] = a >= 0 ? prow[a] : 0.0;
   }
 }
 
@@ -398,80 +281,9 @@ __global__ void __launch_bounds__(kThreads) hota_match_kernel(const unsigned cha
   if (V > 0 && K > 0) {   // wave-uniform
     const bool tp_ = V > K;                        // rows are the tracks when there are more ground truths
     const int n = tp_ ? K : V, mm = tp_ ? V : K;
-    const double inf = HUGE_VAL;
-    for (int j = lane; j <= mm; j += kThreads) {
-      hv[j] = 0.0; hp[j] = 0; hway[j] = 0;
-    }
-    for (int i = lane; i <= n; i += kThreads) hu[i] = 0.0;
-    __syncthreads();
-    for (int i = 1; i <= n; ++i) {
-      for (int j = lane; j <= mm; j += kThreads) {
-        hminv[j] = inf; hused[j] = 0;
-      }
-      if (lane == 0) hp[0] = i;
-      __syncthreads();
-      int j0 = 0;
-      bool found = false;
-      for (int step = 0; step <= mm; ++step) {
-        if (lane == 0) hused[j0] = 1;
-        __syncthreads();
-        const int i0 = hp[j0] < 1 ? 1 : (hp[j0] > n ? n : hp[j0]);
-        const double ui0 = hu[i0];
-        double best = inf;
-        int bj = INT_MAX;
-        for (int j = 1 + lane; j <= mm; j += kThreads) {
-          if (hused[j]) continue;
-          const double cost = -(tp_ ? score_m[(j - 1) * ld + (i0 - 1)] : score_m[(i0 - 1) * ld + (j - 1)]);
-          const double cur = (cost - ui0) - hv[j];
-          double mv = hminv[j];
-          if (cur < mv) {
-            mv = cur; hminv[j] = cur; hway[j] = j0;
-          }
-          if (mv < best) {
-            best = mv; bj = j;
-          }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double ob = __shfl_xor(best, o);
-          const int oj = __shfl_xor(bj, o);
-          if (ob < best || (ob == best && oj < bj)) {
-            best = ob; bj = oj;
-          }
-        }
-        if (bj == INT_MAX) break;                  // nothing to reach (non-finite input only): the row stays free
-        __syncthreads();
-        for (int j = lane; j <= mm; j += kThreads) {
-          if (hused[j]) {
-            const int row = clampi(hp[j], n);
-            hu[row] = hu[row] + best;
-            hv[j] = hv[j] - best;
-          } else {
-            hminv[j] = hminv[j] - best;
-          }
-        }
-        j0 = bj;
-        __syncthreads();
-        if (hp[j0] == 0) {
-          found = true;
-          break;
-        }
-      }
-      __syncthreads();                             // every lane has read hp[j0] before the path is rewritten
-      if (lane == 0) {
-        if (found) {
-          for (int s = 0; s <= mm; ++s) {
-            const int j1 = clampi(hway[j0], mm);
-            hp[j0] = hp[j1];
-            j0 = j1;
-            if (j0 == 0) break;
-          }
-        } else {
-          hp[0] = 0;
-        }
-      }
-      __syncthreads();
-    }
+    assign_rows(n, mm, lane, hu, hv, hminv, hp, hway, hused, [&](int row, int col) {
+      return -(tp_ ? score_m[col * ld + row] : score_m[row * ld + col]);
+    });
     for (int j = 1 + lane; j <= mm; j += kThreads) {
       const int i = clampi(hp[j], n);
       if (i > 0) took[tp_ ? j - 1 : i - 1] = tp_ ? i - 1 : j - 1;
@@ -539,14 +351,7 @@ __global__ void __launch_bounds__(kThreads) hota_fold_kernel(const unsigned char
   const int* hist = reinterpret_cast<const int*>(wk + 8 * (size_t)kBins * (1 + (size_t)frames));
 
   // ---- the track ids present, ascending
-  int C = 0;
-  for (int base = 0; base < tids; base += kThreads) {
-    const int i = base + lane;
-    const bool on = i < tids && tcnt[i] > 0;
-    const unsigned long long mask = __ballot(on);
-    if (on) colid[C + below(mask, lane)] = (unsigned short)i;
-    C += __popcll(mask);
-  }
+  const int C = compact_present(tcnt, tids, lane, colid);
   __syncthreads();
 
   // ---- the association sums: identities 64 at a time, one per lane; lanes 0..56 keep the running totals
@@ -630,23 +435,6 @@ bool shapes_ok(int n, int ids, int tids, int frames) {
          frames <= kMaxFrames;
 }
 
-// the kernel's static LDS, read once per device
-int static_lds_of(const void* kernel, dn::PerDeviceFlag& flag, int* cache, int dynamic_most) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool& ready = flag.here();
-  if (!ready) {
-    hipFuncAttributes attr;
-    if (hipFuncGetAttributes(&attr, kernel) != hipSuccess) return -1;
-    if (dynamic_most > 0 &&
-        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dynamic_most) != hipSuccess)
-      return -2;
-    cache[dev & 63] = (int)attr.sharedSizeBytes;
-    ready = true;
-  }
-  return cache[dev & 63];
-}
-
 }  // namespace
 
 #define DN_HOTA_SIZES(who)                                                                                             \
@@ -681,18 +469,9 @@ extern "C" int dn_hota_step(const double* rect, const int32_t* id, const int32_t
                             const float* gt_boxes, const int32_t* gt_ids, const int32_t* gt_count, int g, double scale,
                             int max_gt_ids, int max_track_ids, int max_frames, void* state, double* out_potential,
                             void* stream) {
-  DN_REQUIRE(rect, "hota_step: null rect");
-  DN_REQUIRE(id, "hota_step: null id");
-  DN_REQUIRE(count, "hota_step: null count");
-  DN_REQUIRE(gt_boxes, "hota_step: null gt_boxes");
-  DN_REQUIRE(gt_ids, "hota_step: null gt_ids");
-  DN_REQUIRE(gt_count, "hota_step: null gt_count");
-  DN_REQUIRE(state, "hota_step: null state");
+  DN_REQUIRE_EVAL_STEP("hota_step", kMaxM, kMaxG);
   DN_REQUIRE(out_potential, "hota_step: null out_potential");
   DN_HOTA_SIZES("hota_step");
-  DN_REQUIRE(m >= 1 && m <= kMaxM, "hota_step: M = %d track rows, must be in [1, %d]", m, kMaxM);
-  DN_REQUIRE(g >= 1 && g <= kMaxG, "hota_step: G = %d ground-truth rows, must be in [1, %d]", g, kMaxG);
-  DN_REQUIRE(std::isfinite(scale) && scale > 0, "hota_step: scale = %g, must be finite and > 0", scale);
   DN_REQUIRE((reinterpret_cast<size_t>(state) & 7) == 0, "hota_step: the state is not 8-byte aligned");
   Params p;
   p.m = m; p.g = g; p.ids = max_gt_ids; p.tids = max_track_ids; p.frames = max_frames;
@@ -701,7 +480,7 @@ extern "C" int dn_hota_step(const double* rect, const int32_t* id, const int32_t
   const int lds = (int)(sizeof(double) * (size_t)(g < kMaxV ? g : kMaxV) * p.ld);
   static dn::PerDeviceFlag flag;
   static int cache[64];
-  const int fixed = static_lds_of(reinterpret_cast<const void*>(hota_step_kernel), flag, cache,
+  const int fixed = dn::static_lds_of(reinterpret_cast<const void*>(hota_step_kernel), flag, cache,
                                   (int)(sizeof(double) * (size_t)kMaxV * (kMaxM | 1)));
   if (fixed < 0) return dn::fail(DN_ERR_LAUNCH, "hota_step: cannot read or set the kernel's attributes");
   if (fixed + lds > kLdsPerCu)                     // never spill: a launch that does not fit is refused
@@ -726,8 +505,8 @@ extern "C" int dn_hota_finish(const void* state, int n_images, int max_gt_ids, i
   const int lds = (int)(sizeof(double) * (size_t)kMaxV * kMatchLd);
   static dn::PerDeviceFlag match_flag, fold_flag;
   static int match_cache[64], fold_cache[64];
-  const int fixed = static_lds_of(reinterpret_cast<const void*>(hota_match_kernel), match_flag, match_cache, lds);
-  const int fold = static_lds_of(reinterpret_cast<const void*>(hota_fold_kernel), fold_flag, fold_cache, 0);
+  const int fixed = dn::static_lds_of(reinterpret_cast<const void*>(hota_match_kernel), match_flag, match_cache, lds);
+  const int fold = dn::static_lds_of(reinterpret_cast<const void*>(hota_fold_kernel), fold_flag, fold_cache, 0);
   if (fixed < 0 || fold < 0) return dn::fail(DN_ERR_LAUNCH, "hota_finish: cannot read or set the kernels' attributes");
   if (fixed + lds > kLdsPerCu || fold > kLdsPerCu) // never spill: a launch that does not fit is refused
     return dn::fail(DN_ERR_LAUNCH, "hota_finish: %d B of work arrays + %d B of score matrix do not fit %d B of LDS", fixed,

@@ -3,33 +3,31 @@
 // host reference that defines the bits is tracking.HostSort.  All arithmetic is fp64 in a fixed order, + - * / and sqrt
 // only (the corners' hypot of postprocess._corners is written sqrt(s s + c c)), and every function carries `#pragma clang fp contract(off)`.
 //
-// One launch per step (track_step_kernel), one workgroup of ONE wave per image -- 64 lanes, every phase a lane-strided
-// loop, so the phases hand over through LDS with single-wave barriers and every reduction is a wave shuffle:
-//   measure    lanes over detection rows, 64 at a time in row order: rectangle of the scaled corners, validity, ballot
+// One launch per step (track_step_kernel), one workgroup of ONE wave per image, every phase a lane-strided loop; the
+// single-wave form, row_rect / rect_iou and the assignment are track_eval_device.h's, shared with the evaluations:
+//   measure    lanes over detection rows, 64 at a time in row order: row_rect, validity (a finite score too), ballot
 //              prefix -> the first 128 valid rows in LDS
 //   predict    lanes over tracks: record (x[7], P[7][7], counters) from the state to registers, predicted, stored to its
 //              slot after the wave-level prefix that drops tracks with a non-finite rectangle (stable compaction)
 //   iou        lanes over (track, detection) pairs -> the matrix in LDS, [tracks][ld], ld odd so that a column walk
 //              (lanes over tracks) is as free of bank conflicts as a row walk
-//   associate  SORT's shortcut (<= 1 entry above the threshold in every row and column) or the shortest-augmenting-path
-//              Hungarian step with lanes over columns: each step one LDS read per lane and one wave arg-min (lowest index
-//              among equals); a row's search is cut after columns + 1 steps whatever the numbers are
+//   associate  SORT's shortcut (<= 1 entry above the threshold in every row and column) or assign_rows on the matrix
 //   update     lanes over tracks: Kalman update (Cholesky of S, Joseph form) in registers, deletions decided, stable
 //              compaction, the report rows of the surviving tracks
 //   birth      lanes over unmatched detections in row order -> free slots, new ids, their report rows
 //   tail       output rows past the count and state slots past the list cleared; the header written by one lane
 // The matrix lives in LDS: 8 * max_tracks * (min(k, 128) | 1) bytes of dynamic LDS, 132 KB at 128 x 128 (one workgroup per
 // CU there, several at the usual sizes).  Nothing is read back, nothing is allocated; two runs write the same bytes.
-#include <climits>
 #include <cmath>
 
 #include "dn_internal.h"
+#include "track_eval_device.h"
 
 namespace {
 
-constexpr int kThreads = 64;
-constexpr int kMaxM = 128;        // track slots per image
-constexpr int kMaxD = 128;        // valid detection rows used per image
+using namespace dn::trk;
+
+constexpr int kMaxD = kMaxV;      // valid detection rows used per image
 constexpr int kMaxK = 1024;       // detection rows per image (dn_detect's limit for top_k)
 constexpr int kHeaderBytes = 64;  // int32 frame_count, next_id, n_tracks, status, 12 spare words
 constexpr int kRecDoubles = 56;   // x[7], P[7][7]
@@ -40,11 +38,6 @@ struct Params {
   int k, m, max_age, min_hits, ld;
   double thr, scale;
 };
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ int below(unsigned long long mask, int lane) {
-  return __popcll(mask & ((1ull << lane) - 1ull));
-}
 
 struct Track {
   double x[7], P[49];
@@ -76,27 +69,6 @@ __device__ __forceinline__ void store_track(unsigned char* rec, const Track& t) 
   w[5] = 0; w[6] = 0; w[7] = 0;
 }
 
-// The four corners of a row (x, y, w, h, sin, cos) in the order and arithmetic of postprocess._corners, its hypot written
-// as sqrt(s s + c c): ocml's hypot and the host's do not round alike, sqrt and the four operations do.
-struct Corners {
-  double x[4], y[4];
-};
-
-__device__ __forceinline__ void corners(const float* __restrict__ b, Corners& o) {
-#pragma clang fp contract(off)
-  const double bx = b[0], by = b[1], w = b[2], h = b[3], sn = b[4], cs = b[5];
-  const double len = sqrt(sn * sn + cs * cs);
-  const double n = len > 1e-12 ? len : (len != len ? len : 1e-12);
-  const double s = sn / n, c = cs / n;
-  const double dx = w / 2.0, dy = h / 2.0;
-  const double lx[4] = {-dx, dx, dx, -dx}, ly[4] = {-dy, -dy, dy, dy};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    o.x[k] = lx[k] * c - ly[k] * s + bx;
-    o.y[k] = lx[k] * s + ly[k] * c + by;
-  }
-}
-
 // (u, v, s, r, ...) -> (x1, y1, x2, y2): w = sqrt(s r), h = s / w
 __device__ __forceinline__ void state_rect(const double* x, double* r) {
 #pragma clang fp contract(off)
@@ -106,17 +78,6 @@ __device__ __forceinline__ void state_rect(const double* x, double* r) {
   r[1] = x[1] - h / 2.0;
   r[2] = x[0] + w / 2.0;
   r[3] = x[1] + h / 2.0;
-}
-
-__device__ __forceinline__ double rect_iou(double a0, double a1, double a2, double a3, double b0, double b1, double b2,
-                                           double b3) {
-#pragma clang fp contract(off)
-  const double w = fmin(a2, b2) - fmax(a0, b0);
-  const double h = fmin(a3, b3) - fmax(a1, b1);
-  if (!(w > 0 && h > 0)) return 0.0;
-  const double inter = w * h;
-  const double uni = (a2 - a0) * (a3 - a1) + (b2 - b0) * (b3 - b1) - inter;
-  return uni > 0 ? inter / uni : 0.0;
 }
 
 __device__ __forceinline__ void predict(Track& t) {
@@ -248,30 +209,18 @@ __global__ void __launch_bounds__(kThreads) track_step_kernel(const float* __res
   for (int base = 0; base < k; base += kThreads) {
     const int r = base + lane;
     bool ok = false;
-    double x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+    double q[4] = {0, 0, 0, 0};
     if (r < k) dtrk[r] = -1;
     if (r < c) {
-      Corners b;
-      corners(boxes + 6 * ((size_t)img * k + r), b);
-      bool fin = true;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        b.x[q] = b.x[q] * p.scale;
-        b.y[q] = b.y[q] * p.scale;
-        fin = fin && isfinite(b.x[q]) && isfinite(b.y[q]);
-      }
-      x1 = fmin(fmin(b.x[0], b.x[1]), fmin(b.x[2], b.x[3]));
-      x2 = fmax(fmax(b.x[0], b.x[1]), fmax(b.x[2], b.x[3]));
-      y1 = fmin(fmin(b.y[0], b.y[1]), fmin(b.y[2], b.y[3]));
-      y2 = fmax(fmax(b.y[0], b.y[1]), fmax(b.y[2], b.y[3]));
-      ok = fin && isfinite(sc[r]) && x2 - x1 > 0 && y2 - y1 > 0;
+      const bool fin = row_rect(boxes + 6 * ((size_t)img * k + r), p.scale, q);
+      ok = fin && isfinite(sc[r]) && q[2] - q[0] > 0 && q[3] - q[1] > 0;
       if (!ok) flags |= 2u;
     }
     const unsigned long long mask = __ballot(ok);
     const int pos = nd + below(mask, lane);
     if (ok) {
       if (pos < kMaxD) {
-        drect[0][pos] = x1; drect[1][pos] = y1; drect[2][pos] = x2; drect[3][pos] = y2;
+        drect[0][pos] = q[0]; drect[1][pos] = q[1]; drect[2][pos] = q[2]; drect[3][pos] = q[3];
         drow[pos] = r;
       } else {
         flags |= 4u;
@@ -336,77 +285,10 @@ __global__ void __launch_bounds__(kThreads) track_step_kernel(const float* __res
   if (hungarian) {   // wave-uniform
     const bool tp = T > D;                         // rows are the smaller side: the detections when T > D
     const int n = tp ? D : T, mm = tp ? T : D;
-    const double inf = HUGE_VAL;
-    for (int j = lane; j <= mm; j += kThreads) {
-      hv[j] = 0.0; hp[j] = 0; hway[j] = 0;
-    }
-    for (int i = lane; i <= n; i += kThreads) hu[i] = 0.0;
     for (int t = lane; t < T; t += kThreads) match_t[t] = -1;
-    __syncthreads();
-    for (int i = 1; i <= n; ++i) {
-      for (int j = lane; j <= mm; j += kThreads) {
-        hminv[j] = inf; hused[j] = 0;
-      }
-      if (lane == 0) hp[0] = i;
-      __syncthreads();
-      int j0 = 0;
-      bool found = false;
-      for (int step = 0; step <= mm; ++step) {
-        if (lane == 0) hused[j0] = 1;
-        __syncthreads();
-        const int i0 = hp[j0] < 1 ? 1 : (hp[j0] > n ? n : hp[j0]);
-        const double ui0 = hu[i0];
-        double best = inf;
-        int bj = INT_MAX;
-        for (int j = 1 + lane; j <= mm; j += kThreads) {
-          if (hused[j]) continue;
-          const double cost = -(tp ? iou_m[(j - 1) * ld + (i0 - 1)] : iou_m[(i0 - 1) * ld + (j - 1)]);
-          const double cur = (cost - ui0) - hv[j];
-          double mv = hminv[j];
-          if (cur < mv) {
-            mv = cur; hminv[j] = cur; hway[j] = j0;
-          }
-          if (mv < best) {
-            best = mv; bj = j;
-          }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double ob = __shfl_xor(best, o);
-          const int oj = __shfl_xor(bj, o);
-          if (ob < best || (ob == best && oj < bj)) {
-            best = ob; bj = oj;
-          }
-        }
-        if (bj == INT_MAX) break;                  // nothing to reach (non-finite input only): the row stays free
-        __syncthreads();
-        for (int j = lane; j <= mm; j += kThreads) {
-          if (hused[j]) {
-            const int row = clampi(hp[j], n);
-            hu[row] = hu[row] + best;
-            hv[j] = hv[j] - best;
-          } else {
-            hminv[j] = hminv[j] - best;
-          }
-        }
-        j0 = bj;
-        __syncthreads();
-        if (hp[j0] == 0) {
-          found = true;
-          break;
-        }
-      }
-      __syncthreads();                             // every lane has read hp[j0] before the path is rewritten
-      if (found && lane == 0) {
-        for (int s = 0; s <= mm; ++s) {
-          const int j1 = clampi(hway[j0], mm);
-          hp[j0] = hp[j1];
-          j0 = j1;
-          if (j0 == 0) break;
-        }
-      }
-      __syncthreads();
-    }
+    assign_rows(n, mm, lane, hu, hv, hminv, hp, hway, hused, [&](int row, int col) {
+      return -(tp ? iou_m[col * ld + row] : iou_m[row * ld + col]);
+    });
     for (int j = 1 + lane; j <= mm; j += kThreads) {
       const int i = clampi(hp[j], n);
       if (i > 0) match_t[tp ? j - 1 : i - 1] = tp ? i - 1 : j - 1;
@@ -517,7 +399,7 @@ __global__ void __launch_bounds__(kThreads) track_step_kernel(const float* __res
     const int s = nfinal + e / kRecWords, w = e % kRecWords;
     reinterpret_cast<unsigned long long*>(record(st, s))[w] = 0ull;
   }
-  const unsigned all = (__any(flags & 1u) ? 1u : 0u) | (__any(flags & 2u) ? 2u : 0u) | (__any(flags & 4u) ? 4u : 0u);
+  const unsigned all = wave_or(flags);
   if (lane == 0) {
     hdr[0] = fc;
     hdr[1] = next_id + nborn;
@@ -571,15 +453,12 @@ extern "C" int dn_track_step(const float* boxes, const float* scores, const int3
   p.ld = (k < kMaxD ? k : kMaxD) | 1;
   p.thr = iou_threshold; p.scale = scale;
   const int lds = (int)(sizeof(double) * (size_t)max_tracks * p.ld);
+  const int most = (int)(sizeof(double) * (size_t)kMaxM * (kMaxD | 1));
   static dn::PerDeviceFlag lds_flag;
-  bool& lds_ready = lds_flag.here();
-  if (!lds_ready) {
-    const int most = (int)(sizeof(double) * (size_t)kMaxM * (kMaxD | 1));
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(track_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            most) != hipSuccess)
-      return dn::fail(DN_ERR_LAUNCH, "track_step: cannot reserve %d B of dynamic LDS", most);
-    lds_ready = true;
-  }
+  static int static_lds[64];
+  const int fixed = dn::static_lds_of(reinterpret_cast<const void*>(track_step_kernel), lds_flag, static_lds, most);
+  if (fixed == -1) return dn::fail(DN_ERR_LAUNCH, "track_step: cannot read the kernel's attributes");
+  if (fixed < 0) return dn::fail(DN_ERR_LAUNCH, "track_step: cannot reserve %d B of dynamic LDS", most);
   hipLaunchKernelGGL(track_step_kernel, dim3(n_images), dim3(kThreads), lds, (hipStream_t)stream, boxes, scores, count, p,
                      static_cast<unsigned char*>(state), out_rect, out_id, out_det, out_score, out_count, det_track);
   return dn::check_launch("track_step");

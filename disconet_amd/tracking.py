@@ -459,15 +459,7 @@ class Sort:
         boxes, scores, count, n, k = self._inputs(det)
         lib = _lib.load()
         dev = scores.device
-        if self.state is None:
-            nbytes = int(lib.dn_track_state_bytes(n, self.max_tracks))
-            if nbytes != state_bytes(n, self.max_tracks):
-                raise _lib.DnError("dn_track_state_bytes(%d, %d) = %d" % (n, self.max_tracks, nbytes))
-            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.n_images = n
-            self.reset()
-        if n != self.n_images:
-            raise ValueError("the tracker holds %d images, this call has %d" % (self.n_images, n))
+        _hold_state(self, "tracker", "dn_track_state_bytes", state_bytes, (n, self.max_tracks), dev)
         m = self.max_tracks
         out = {"rect": torch.empty((n, m, 4), dtype=torch.float64, device=dev),
                "id": torch.empty((n, m), dtype=torch.int32, device=dev),
@@ -483,10 +475,7 @@ class Sort:
 
     def status_words(self):
         """The status word of every image (numpy int32): one small copy, waits for the device."""
-        if self.state is None:
-            return np.zeros(0, dtype=np.int32)
-        words = self.state.view(self.n_images, -1)[:, 12:16].contiguous().cpu().numpy()
-        return words.view(np.int32).reshape(-1).copy()
+        return _status_words(self.state, self.n_images, 12)
 
     def status(self):
         """Raise DnError naming the set status bits (a run is never silently truncated); returns 0 otherwise."""
@@ -655,6 +644,75 @@ def _mot_tracks(tracks):
     return rect, ids, count
 
 
+def _eval_inputs_host(tracks, gt):
+    """ClearMot.update()'s inputs as host arrays, shapes checked -> (rect, tid, tcount, boxes, gids, gcount, n, m, g)."""
+    rect, tid, tcount = _mot_tracks(tracks)
+    boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
+    gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
+    gcount = np.asarray(_host(gt["count"])).reshape(-1)
+    if tid.ndim != 2:
+        raise ValueError("shapes: id %s" % (tid.shape,))
+    n, m = tid.shape
+    g = gids.shape[1] if gids.ndim == 2 else 0
+    if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
+            or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
+        raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
+            rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+    return rect, tid, tcount, boxes, gids, gcount, n, m, g
+
+
+def _eval_inputs_device(who, host_name, tracks, gt):
+    """ClearMot.update()'s inputs as contiguous device tensors of the library's types, shapes checked -> (rect, tid,
+    tcount, boxes, gids, gcount, n, m, g).  `who` and `host_name` name the class and its numpy reference in the errors."""
+    from .ops import _need_gpu
+    named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
+             ("gt ids", gt["ids"]), ("gt count", gt["count"]))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise _lib.DnError("%s.update needs device tensors (%s is %s); %s is the numpy reference"
+                               % (who, name, type(t).__name__, host_name))
+    rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
+    _need_gpu(rect, tid, tcount, boxes, gids, gcount)
+    if tid.dim() != 2 or gids.dim() != 2:
+        raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
+    (n, m), g = tid.shape, gids.shape[1]
+    if not 1 <= m <= MAX_TRACKS:
+        raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
+    if not 1 <= g <= MAX_GT_ROWS:
+        raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
+    if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
+            or gcount.numel() != n):
+        raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
+            tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
+    rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
+    tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+    return rect, tid, tcount, boxes, gids, gcount, n, m, g
+
+
+def _hold_state(ev, what, lib_name, formula, sizes, device):
+    """The head of a device class's update(): on first use allocate ev.state (uint8, 8-byte aligned: viewed from an int64
+    allocation) after checking the library's byte count `lib_name`(*sizes) against the module's `formula`(*sizes), set
+    ev.n_images = sizes[0] and reset(); afterwards hold every call to that many images."""
+    n = sizes[0]
+    if ev.state is None:
+        nbytes = int(getattr(_lib.load(), lib_name)(*sizes))
+        if nbytes != formula(*sizes):
+            raise _lib.DnError("%s%r = %d" % (lib_name, tuple(sizes), nbytes))
+        ev.state = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device).view(torch.uint8)[:nbytes]
+        ev.n_images = n
+        ev.reset()
+    if n != ev.n_images:
+        raise ValueError("the %s holds %d images, this call has %d" % (what, ev.n_images, n))
+
+
+def _status_words(state, n_images, offset):
+    """The int32 status word at byte `offset` of every image's state (numpy int32): one small copy, waits for the device."""
+    if state is None:
+        return np.zeros(0, dtype=np.int32)
+    words = state.view(n_images, -1)[:, offset:offset + 4].contiguous().cpu().numpy()
+    return words.view(np.int32).reshape(-1).copy()
+
+
 class HostClearMot:
     """The numpy / float64 reference of ClearMot and the statement of its contract (the CLEAR MOT metrics as the MOT
     benchmark's evaluation kit computes them, recalled, not pinned; the full text is in include/disconet_hip.h).
@@ -680,16 +738,7 @@ class HostClearMot:
             self.images = [self._fresh() for _ in self.images]
 
     def update(self, tracks, gt):
-        rect, tid, tcount = _mot_tracks(tracks)
-        boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
-        gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
-        gcount = np.asarray(_host(gt["count"])).reshape(-1)
-        n, m = tid.shape
-        g = gids.shape[1] if gids.ndim == 2 else 0
-        if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
-                or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
-            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
-                rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_host(tracks, gt)
         if self.images is None:
             self.images = [self._fresh() for _ in range(n)]
         if len(self.images) != n:
@@ -807,39 +856,11 @@ class ClearMot:
                        "dn_mot_reset")
 
     def update(self, tracks, gt):
-        from .ops import _need_gpu, _ptr, _stream
-        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
-                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise _lib.DnError("ClearMot.update needs device tensors (%s is %s); HostClearMot is the numpy reference"
-                                   % (name, type(t).__name__))
-        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
-        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
-        if tid.dim() != 2 or gids.dim() != 2:
-            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
-        (n, m), g = tid.shape, gids.shape[1]
-        if not 1 <= m <= MAX_TRACKS:
-            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
-        if not 1 <= g <= MAX_GT_ROWS:
-            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
-        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
-                or gcount.numel() != n):
-            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
-                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
-        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
-        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        from .ops import _ptr, _stream
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_device("ClearMot", "HostClearMot", tracks, gt)
         lib = _lib.load()
         dev = rect.device
-        if self.state is None:
-            nbytes = int(lib.dn_mot_state_bytes(n, self.max_gt_ids))
-            if nbytes != mot_state_bytes(n, self.max_gt_ids):
-                raise _lib.DnError("dn_mot_state_bytes(%d, %d) = %d" % (n, self.max_gt_ids, nbytes))
-            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.n_images = n
-            self.reset()
-        if n != self.n_images:
-            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        _hold_state(self, "evaluation", "dn_mot_state_bytes", mot_state_bytes, (n, self.max_gt_ids), dev)
         out = {"match": torch.empty((n, g), dtype=torch.int32, device=dev),
                "iou": torch.empty((n, g), dtype=torch.float64, device=dev),
                "flags": torch.empty((n, g), dtype=torch.int32, device=dev)}
@@ -850,10 +871,7 @@ class ClearMot:
 
     def status_words(self):
         """The status word of every image (numpy int32): one small copy, waits for the device."""
-        if self.state is None:
-            return np.zeros(0, dtype=np.int32)
-        words = self.state.view(self.n_images, -1)[:, 48:52].contiguous().cpu().numpy()
-        return words.view(np.int32).reshape(-1).copy()
+        return _status_words(self.state, self.n_images, 48)
 
     def state_bytes(self):
         """A host copy of the whole state (numpy uint8); HostClearMot.state_bytes() is its reference."""
@@ -972,18 +990,7 @@ class HostIdentity:
             self.images = [self._fresh() for _ in self.images]
 
     def update(self, tracks, gt):
-        rect, tid, tcount = _mot_tracks(tracks)
-        boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
-        gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
-        gcount = np.asarray(_host(gt["count"])).reshape(-1)
-        if tid.ndim != 2:
-            raise ValueError("shapes: id %s" % (tid.shape,))
-        n, m = tid.shape
-        g = gids.shape[1] if gids.ndim == 2 else 0
-        if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
-                or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
-            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
-                rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_host(tracks, gt)
         if self.images is None:
             self.images = [self._fresh() for _ in range(n)]
         if len(self.images) != n:
@@ -1099,39 +1106,12 @@ class Identity:
                                                 _stream()), "dn_idf_reset")
 
     def update(self, tracks, gt):
-        from .ops import _need_gpu, _ptr, _stream
-        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
-                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise _lib.DnError("Identity.update needs device tensors (%s is %s); HostIdentity is the numpy reference"
-                                   % (name, type(t).__name__))
-        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
-        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
-        if tid.dim() != 2 or gids.dim() != 2:
-            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
-        (n, m), g = tid.shape, gids.shape[1]
-        if not 1 <= m <= MAX_TRACKS:
-            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
-        if not 1 <= g <= MAX_GT_ROWS:
-            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
-        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
-                or gcount.numel() != n):
-            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
-                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
-        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
-        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        from .ops import _ptr, _stream
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_device("Identity", "HostIdentity", tracks, gt)
         lib = _lib.load()
         dev = rect.device
-        if self.state is None:
-            nbytes = int(lib.dn_idf_state_bytes(n, self.max_gt_ids, self.max_track_ids))
-            if nbytes != idf_state_bytes(n, self.max_gt_ids, self.max_track_ids):
-                raise _lib.DnError("dn_idf_state_bytes(%d, %d, %d) = %d" % (n, self.max_gt_ids, self.max_track_ids, nbytes))
-            self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.n_images = n
-            self.reset()
-        if n != self.n_images:
-            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        _hold_state(self, "evaluation", "dn_idf_state_bytes", idf_state_bytes,
+                    (n, self.max_gt_ids, self.max_track_ids), dev)
         out = {"overlaps": torch.empty((n, g), dtype=torch.int32, device=dev)}
         _lib.check(lib.dn_idf_step(_ptr(rect), _ptr(tid), _ptr(tcount), n, m, _ptr(boxes), _ptr(gids), _ptr(gcount), g,
                                    self.scale, self.iou_threshold, self.max_gt_ids, self.max_track_ids, _ptr(self.state),
@@ -1153,10 +1133,7 @@ class Identity:
 
     def status_words(self):
         """The status word of every image (numpy int32): one small copy, waits for the device."""
-        if self.state is None:
-            return np.zeros(0, dtype=np.int32)
-        words = self.state.view(self.n_images, -1)[:, 24:28].contiguous().cpu().numpy()
-        return words.view(np.int32).reshape(-1).copy()
+        return _status_words(self.state, self.n_images, 24)
 
     def state_bytes(self):
         """A host copy of the whole state (numpy uint8); HostIdentity.state_bytes() is its reference."""
@@ -1323,23 +1300,6 @@ def _iou_matrix(grect, trect):
         union = ((g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1]))[:, None] + ((t[:, 2] - t[:, 0]) * (t[:, 3] - t[:, 1]))[None, :] - inter
         ok = (w > 0) & (h > 0) & (union > 0) & fin[None, :]
         return np.where(ok, inter / np.where(ok, union, 1.0), 0.0)
-
-
-def _eval_inputs_host(tracks, gt):
-    """ClearMot.update()'s inputs as host arrays, shapes checked -> (rect, tid, tcount, boxes, gids, gcount, n, m, g)."""
-    rect, tid, tcount = _mot_tracks(tracks)
-    boxes = np.asarray(_host(gt["boxes"]), dtype=np.float32)
-    gids = np.asarray(_host(gt["ids"]), dtype=np.int32)
-    gcount = np.asarray(_host(gt["count"])).reshape(-1)
-    if tid.ndim != 2:
-        raise ValueError("shapes: id %s" % (tid.shape,))
-    n, m = tid.shape
-    g = gids.shape[1] if gids.ndim == 2 else 0
-    if (not 1 <= m <= MAX_TRACKS or not 1 <= g <= MAX_GT_ROWS or tuple(rect.shape) != (n, m, 4) or gids.shape[0] != n
-            or tuple(boxes.shape) != (n, g, 6) or tcount.shape[0] != n or gcount.shape[0] != n):
-        raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % (
-            rect.shape, tid.shape, tcount.shape, boxes.shape, gids.shape, gcount.shape))
-    return rect, tid, tcount, boxes, gids, gcount, n, m, g
 
 
 class HostHota:
@@ -1569,40 +1529,12 @@ class Hota:
             _lib.check(_lib.load().dn_hota_reset(_ptr(self.state), *self._sizes(), _stream()), "dn_hota_reset")
 
     def update(self, tracks, gt):
-        from .ops import _need_gpu, _ptr, _stream
-        named = (("rect", tracks["rect"]), ("id", tracks["id"]), ("count", tracks["count"]), ("gt boxes", gt["boxes"]),
-                 ("gt ids", gt["ids"]), ("gt count", gt["count"]))
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise _lib.DnError("Hota.update needs device tensors (%s is %s); HostHota is the numpy reference"
-                                   % (name, type(t).__name__))
-        rect, tid, tcount, boxes, gids, gcount = (t for _, t in named)
-        _need_gpu(rect, tid, tcount, boxes, gids, gcount)
-        if tid.dim() != 2 or gids.dim() != 2:
-            raise ValueError("shapes: id %s, gt ids %s" % (tuple(tid.shape), tuple(gids.shape)))
-        (n, m), g = tid.shape, gids.shape[1]
-        if not 1 <= m <= MAX_TRACKS:
-            raise ValueError("M = %d track rows: 1..%d are supported" % (m, MAX_TRACKS))
-        if not 1 <= g <= MAX_GT_ROWS:
-            raise ValueError("G = %d ground-truth rows: 1..%d are supported" % (g, MAX_GT_ROWS))
-        if (tuple(rect.shape) != (n, m, 4) or tcount.numel() != n or tuple(boxes.shape) != (n, g, 6) or gids.shape[0] != n
-                or gcount.numel() != n):
-            raise ValueError("shapes: rect %s id %s count %s, gt boxes %s ids %s count %s" % tuple(
-                tuple(t.shape) for t in (rect, tid, tcount, boxes, gids, gcount)))
-        rect, boxes = rect.to(torch.float64).contiguous(), boxes.to(torch.float32).contiguous()
-        tid, tcount, gids, gcount = (t.to(torch.int32).contiguous() for t in (tid, tcount, gids, gcount))
+        from .ops import _ptr, _stream
+        rect, tid, tcount, boxes, gids, gcount, n, m, g = _eval_inputs_device("Hota", "HostHota", tracks, gt)
         lib = _lib.load()
         dev = rect.device
-        if self.state is None:
-            nbytes = int(lib.dn_hota_state_bytes(n, self.max_gt_ids, self.max_track_ids, self.max_frames))
-            if nbytes != hota_state_bytes(n, self.max_gt_ids, self.max_track_ids, self.max_frames) or nbytes % 8:
-                raise _lib.DnError("dn_hota_state_bytes(%d, %d, %d, %d) = %d" % (n, self.max_gt_ids, self.max_track_ids,
-                                                                                self.max_frames, nbytes))
-            self.state = torch.empty(nbytes // 8, dtype=torch.int64, device=dev).view(torch.uint8)
-            self.n_images = n
-            self.reset()
-        if n != self.n_images:
-            raise ValueError("the evaluation holds %d images, this call has %d" % (self.n_images, n))
+        _hold_state(self, "evaluation", "dn_hota_state_bytes", hota_state_bytes,
+                    (n, self.max_gt_ids, self.max_track_ids, self.max_frames), dev)
         out = {"potential": torch.empty((n, g), dtype=torch.float64, device=dev)}
         _lib.check(lib.dn_hota_step(_ptr(rect), _ptr(tid), _ptr(tcount), n, m, _ptr(boxes), _ptr(gids), _ptr(gcount), g,
                                     self.scale, self.max_gt_ids, self.max_track_ids, self.max_frames, _ptr(self.state),
@@ -1635,10 +1567,7 @@ class Hota:
 
     def status_words(self):
         """The status word of every image (numpy int32): one small copy, waits for the device."""
-        if self.state is None:
-            return np.zeros(0, dtype=np.int32)
-        words = self.state.view(self.n_images, -1)[:, 32:36].contiguous().cpu().numpy()
-        return words.view(np.int32).reshape(-1).copy()
+        return _status_words(self.state, self.n_images, 32)
 
     def state_bytes(self):
         """A host copy of the whole state (numpy uint8); HostHota.state_bytes() is its reference."""

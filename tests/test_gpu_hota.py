@@ -73,6 +73,24 @@ def test_128_tracks_and_128_ground_truths():
     assert level["TP"][0] > 200 and level["TP"][18] == 0 and 0.0 < level["HOTA"] < 1.0
 
 
+def test_assignment_past_one_wave_in_both_orientations():
+    """mot_cases.chain_frames(): 70 ground truths x 65 tracks (the match kernel's rows are the tracks, its 70 columns the
+    ground truths), then 65 x 70 -- the smallest frames whose columns cross a wave in either orientation."""
+    from disconet_amd import tracking
+    frames = C.chain_frames()
+    sizes = dict(scale=C.SCALE, max_gt_ids=128, max_track_ids=256, max_frames=2)
+    alone = tracking.HostHota(1, **sizes)                  # the conditions of the test, from the host reference alone
+    for tracks, gt in frames:
+        alone.update(tracks, gt)
+    assert alone.status_words().tolist() == [0]
+    log = alone.images[0]["log"]
+    assert [(len(slot["gid"]), len(slot["tid"])) for slot in log] == [(70, 65), (65, 70)]
+    for slot in log:                                       # some row holds two or more overlaps: the assignment is not trivial
+        assert ((tracking._iou_matrix(slot["grect"], slot["trect"]) > 0).sum(1) >= 2).any()
+    dev, host, _ = H.run_both(frames, **sizes)
+    assert host.status_words().tolist() == [0]
+
+
 # ---- 4. the rows that are ignored ------------------------------------------------------------------------------------
 def test_duplicate_track_id_is_counted_nowhere():
     dev, host, outs = H.run_both([H.twice_frame()], scale=1.0, **H.SIZES)
