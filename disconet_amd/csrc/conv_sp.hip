@@ -32,12 +32,14 @@
 #endif
 #ifndef DN_SP_ABL
 #define DN_SP_ABL 0      // 1 = instantiate the timing-only ablation kernels that dn_spconv_force_config(101..105, 201..207, 400..407)
-#endif                   // selects (tools/sp_conv_check.cpp).  Never in the shipped build.
+#endif                   // selects (SpForceId; tools/sp_conv_check.cpp).  Never in the shipped build.
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
+#include <array>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #if DN_PHASE_TIMING
 __device__ unsigned long long g_phase_cycles[8];
@@ -1414,34 +1416,62 @@ inline size_t packed_blocks(const dn_conv_desc& d) {   // 16-byte-piece blocks o
 enum SpCfgId { S3_256x64, S3_256x32, S3_128x64, S3_64x64, S3S2_128x64, S3S2_64x64, S1_256x64, S1_64x64,
                S3_256x64_T9, S3_512x64, S3_256x128, S1_256x64_C1, S3_256x32_ST, S3_64x64_T9, S3_128x64_T9,
                S3S2_64x64_T9, S3S2_128x64_T9, SP_CFG_COUNT };
-// chunks per A stage of the 1x1 tiles: the chunk count of the input must be a multiple
-inline int ca_of(SpCfgId id) { return id == S1_256x64 ? 2 : id == S1_64x64 ? 4 : 1; }
-struct SpCfg { SpCfgId id; int th, tw, bn; float bias; };
-// biases: measured time per unit of tile area relative to 256x64 (tools/sp_conv_check.hip sweep)
-float g_sp_bias[SP_CFG_COUNT] = {1.00f, 1.15f, 1.10f, 1.40f, 1.45f, 1.00f, 1.00f, 1.30f, 1.f, 1.f, 1.f, 1.2f,
-                                 1.f, 1.f, 1.f, 1.f, 1.f};
-const SpCfg kSpCfgs[SP_CFG_COUNT] = {
-    {S3_256x64, 8, 32, 64, 0},   {S3_256x32, 8, 32, 32, 0},   {S3_128x64, 8, 16, 64, 0},
-    {S3_64x64, 8, 8, 64, 0},     {S3S2_128x64, 8, 16, 64, 0}, {S3S2_64x64, 8, 8, 64, 0},
-    {S1_256x64, 8, 32, 64, 0},   {S1_64x64, 8, 8, 64, 0},
-    {S3_256x64_T9, 8, 32, 64, 0}, {S3_512x64, 16, 32, 64, 0}, {S3_256x128, 8, 32, 128, 0},
-    {S1_256x64_C1, 8, 32, 64, 0}, {S3_256x32_ST, 8, 32, 32, 0},
-    {S3_64x64_T9, 8, 8, 64, 0},  {S3_128x64_T9, 8, 16, 64, 0}, {S3S2_64x64_T9, 8, 8, 64, 0},
-    {S3S2_128x64_T9, 8, 16, 64, 0},
+// What dn_spconv_force_config takes beyond a SpCfgId (tools/sp_conv_check.cpp, tests): the forms of conv_spq.hip, and base + n =
+// timing-only ablation n of one tile (conv_sp_kernel ABL).  From FORCE_TOOLS on, results are wrong by construction.
+enum SpForceId {
+  FORCE_SPQ_BN32 = 20, FORCE_SPQ_BN64 = 21, FORCE_SPQ_DEEP = 22,   // conv_spq.hip: BN 32 / 64 / the one-step-per-chunk form
+  FORCE_SPQ_ABL = 22,                                // 23..25: ablations 1..3 of its BN = 32 form (DN_SP_ABL)
+  FORCE_TOOLS = 100,
+  FORCE_ABL_256x64 = 100, FORCE_ABL_256x32 = 200,    // 101..105, 201..207 (DN_SP_ABL)
+  FORCE_ABL_64x64_T9 = 300,                          // 301..305, in every build
+  FORCE_ABL_S2_64x64 = 400,                          // 400 = the tile as shipped in round 4 (two weight stages), 401..405, 407 (DN_SP_ABL)
 };
-// Launches that leave most CUs with one workgroup or none (the deep layers of a 4-image agent share) run at the
+
+// ---- the tile table: every tile's geometry, cost bias and deep variant, written ONCE.  A new tile is a row here (and an
+// enumerator above, a name in tools/sp_conv_check.cpp :: kCfgName and tests/test_gpu_conv_fp64.py :: CFG) plus its id in
+// the launch_form<> lists of the forms it is built for.
+template <int KS_, int STRIDE_, int TH_, int TW_, int BN_, int TG_, int CA_, int WAVES_M_, int WAVES_N_, int WTM_, int WTN_>
+struct Geom {
+  using G = Geom;   // the geometry alone: what launch<> is instantiated on, whichever id names it
+  static constexpr int KS = KS_, STRIDE = STRIDE_, TH = TH_, TW = TW_, BN = BN_, TG = TG_, CA = CA_, WAVES_M = WAVES_M_,
+                       WAVES_N = WAVES_N_, WTM = WTM_, WTN = WTN_;
+};
+template <SpCfgId ID> struct Tile;
+#define SP_TILE(id, bias_, deep_, ...) \
+  template <> struct Tile<id> : __VA_ARGS__ { static constexpr float bias = bias_; static constexpr SpCfgId deep = deep_; }
+// bias: measured time per unit of tile area relative to 256x64 (tools/sp_conv_check.cpp sweep).
+// deep: launches that leave most CUs with one workgroup or none (the deep layers of a 4-image agent share) run at the
 // latency of one K step, not at MFMA throughput: the all-nine-taps-per-step variant of the same tile has a third
-// of the steps (one 36 KB weight stage per 16-channel chunk instead of three 12 KB ones)
-inline SpCfgId deep_variant(SpCfgId id) {
-  switch (id) {
-    case S3_256x64: return S3_256x64_T9;
-    case S3_128x64: return S3_128x64_T9;
-    case S3_64x64: return S3_64x64_T9;
-    case S3S2_64x64: return S3S2_64x64_T9;
-    case S3S2_128x64: return S3S2_128x64_T9;
-    default: return id;
-  }
+// of the steps (one 36 KB weight stage per 16-channel chunk instead of three 12 KB ones).  Tiles without one name themselves.
+// CA: chunks per A stage -- the chunk count of a 1x1 tile's input must be a multiple.
+//      id              bias   deep variant         KS S  TH  TW  BN  TG CA WM WN WTM WTN
+SP_TILE(S3_256x64,      1.00f, S3_256x64_T9,   Geom<3, 1, 8,  32, 64,  3, 1, 4, 1, 2, 2>);
+SP_TILE(S3_256x32,      1.15f, S3_256x32,      Geom<3, 1, 8,  32, 32,  3, 1, 4, 1, 2, 1>);
+SP_TILE(S3_128x64,      1.10f, S3_128x64_T9,   Geom<3, 1, 8,  16, 64,  3, 1, 2, 2, 2, 1>);
+SP_TILE(S3_64x64,       1.40f, S3_64x64_T9,    Geom<3, 1, 8,  8,  64,  3, 1, 2, 2, 1, 1>);
+SP_TILE(S3S2_128x64,    1.45f, S3S2_128x64_T9, Geom<3, 2, 8,  16, 64,  3, 1, 2, 2, 2, 1>);
+SP_TILE(S3S2_64x64,     1.00f, S3S2_64x64_T9,  Geom<3, 2, 8,  8,  64,  3, 1, 2, 2, 1, 1>);
+SP_TILE(S1_256x64,      1.00f, S1_256x64,      Geom<1, 1, 8,  32, 64,  1, 2, 4, 1, 2, 2>);
+SP_TILE(S1_64x64,       1.30f, S1_64x64,       Geom<1, 1, 8,  8,  64,  1, 4, 2, 2, 1, 1>);
+SP_TILE(S3_256x64_T9,   1.f,   S3_256x64_T9,   Geom<3, 1, 8,  32, 64,  9, 1, 4, 1, 2, 2>);
+SP_TILE(S3_512x64,      1.f,   S3_512x64,      Geom<3, 1, 16, 32, 64,  3, 1, 8, 1, 2, 2>);
+SP_TILE(S3_256x128,     1.f,   S3_256x128,     Geom<3, 1, 8,  32, 128, 3, 1, 4, 2, 2, 2>);
+SP_TILE(S1_256x64_C1,   1.2f,  S1_256x64_C1,   Geom<1, 1, 8,  32, 64,  1, 1, 4, 1, 2, 2>);
+SP_TILE(S3_256x32_ST,   1.f,   S3_256x32_ST,   Tile<S3_256x32>::G);   // tools: S3_256x32, always in the Stationary form
+SP_TILE(S3_64x64_T9,    1.f,   S3_64x64_T9,    Geom<3, 1, 8,  8,  64,  9, 1, 2, 2, 1, 1>);
+SP_TILE(S3_128x64_T9,   1.f,   S3_128x64_T9,   Geom<3, 1, 8,  16, 64,  9, 1, 2, 2, 2, 1>);
+SP_TILE(S3S2_64x64_T9,  1.f,   S3S2_64x64_T9,  Geom<3, 2, 8,  8,  64,  9, 1, 2, 2, 1, 1>);
+SP_TILE(S3S2_128x64_T9, 1.f,   S3S2_128x64_T9, Geom<3, 2, 8,  16, 64,  9, 1, 2, 2, 2, 1>);
+#undef SP_TILE
+
+// the table's rows as values, in enum order: what the cost model reads
+struct SpCfg { SpCfgId id; int th, tw, bn, ca; float bias; SpCfgId deep; };
+template <int... I>
+constexpr std::array<SpCfg, sizeof...(I)> sp_cfgs(std::integer_sequence<int, I...>) {
+  return {{{(SpCfgId)I, Tile<(SpCfgId)I>::TH, Tile<(SpCfgId)I>::TW, Tile<(SpCfgId)I>::BN, Tile<(SpCfgId)I>::CA,
+            Tile<(SpCfgId)I>::bias, Tile<(SpCfgId)I>::deep}...}};
 }
+constexpr std::array<SpCfg, SP_CFG_COUNT> kSpCfgs = sp_cfgs(std::make_integer_sequence<int, SP_CFG_COUNT>{});
 int g_sp_force = -1;   // tools: force one configuration
 
 SpCfg select_cfg(const dn_conv_desc& d, int kslices = 1, bool can_split = false) {
@@ -1460,7 +1490,7 @@ SpCfg select_cfg(const dn_conv_desc& d, int kslices = 1, bool can_split = false)
   const int nchunks = chunks_of(d.c0) + chunks_of(d.c1);
   if (g_sp_force >= 0) {
     for (int k = 0; k < ncand; ++k)
-      if (cand[k] == g_sp_force && nchunks % ca_of(cand[k]) == 0) return kSpCfgs[cand[k]];
+      if (cand[k] == g_sp_force && nchunks % kSpCfgs[cand[k]].ca == 0) return kSpCfgs[cand[k]];
     if (d.ksize == 3 && d.stride == 1 && !upm && g_sp_force >= S3_256x64_T9 && g_sp_force <= S3_128x64_T9 &&
         g_sp_force != S1_256x64_C1)
       return kSpCfgs[g_sp_force];
@@ -1472,37 +1502,62 @@ SpCfg select_cfg(const dn_conv_desc& d, int kslices = 1, bool can_split = false)
   long best_blocks = 0;
   for (int k = 0; k < ncand; ++k) {
     const SpCfg& c = kSpCfgs[cand[k]];
-    if (nchunks % ca_of(c.id) != 0) continue;
+    if (nchunks % c.ca != 0) continue;
     const long tiles = (long)d.n_images * ((ho + c.th - 1) / c.th) * ((wo + c.tw - 1) / c.tw);
     const long blocks = tiles * ((d.c_out + c.bn - 1) / c.bn);
     // a K-sliced launch fills its last round with slices: rounds in units of 1 / kslices
     const double rounds = ksl && can_split ? (double)((blocks * kslices + kCUs - 1) / kCUs) / kslices
                               : (double)((blocks + kCUs - 1) / kCUs);
-    const double cost = rounds * c.th * c.tw * c.bn * g_sp_bias[c.id];
+    const double cost = rounds * c.th * c.tw * c.bn * c.bias;
     if (cost < best_cost * 0.999) { best_cost = cost; best = c; best_blocks = blocks; }
   }
-  if (g_sp_force < 0 && !upm && best_blocks * (ksl && can_split ? kslices : 1) <= kCUs) best = kSpCfgs[deep_variant(best.id)];
+  if (g_sp_force < 0 && !upm && best_blocks * (ksl && can_split ? kslices : 1) <= kCUs) best = kSpCfgs[best.deep];
   return best;
 }
 
-// Which tiles of a K-sliced launch are split (sp_device.h :: KSlices).  T whole-tile items on R resident workgroups run
-// floor(T / R) full rounds and a last one that leaves CUs idle (or, T < R, never fills the chip): the tiles of that
-// round are handed out slice by slice when that shortens the launch by a fifth of a round or more, as far as the
-// workspace reaches.  -> number of whole tiles.
-inline long ks_plan(long T, long R, int S, size_t ws_bytes, size_t bytes_per_tile) {
-  if (S <= 1 || ws_bytes < bytes_per_tile) return T;
-  const long full = T / R, tail = T - full * R;
-  if (tail == 0) return T;
-  const double cost_split = (double)full + (double)((tail * S + R - 1) / R) / S;
-  if (cost_split > (double)(full + 1) - 0.2) return T;
-  const long max_split = (long)(ws_bytes / bytes_per_tile);
-  return tail > max_split ? T - max_split : full * R;
-}
+// ---- the kernel forms: every combination of conv_sp_kernel's POST / ABL / BSTAT / UPM / AHI / KSL / NB parameters (described
+// above SpTile) that the dispatch uses, written ONCE and by name.  A form says only what it changes.
+struct Plain { static constexpr int POST = 0, ABL = 0, BSTAT = 0, UPM = 0, AHI = 0, KSL = 0, NB = 2; };
+// K-sliced layers (dn_spconv2d_ks): tiles with at most two accumulator tiles per wave (the slices' running sum is a second set)
+struct KSliced : Plain { static constexpr int KSL = 1; };
+// weight-stationary form (short-K full-resolution layers): two workgroups per CU
+// (a 16x32-pixel stationary tile -- four MFMA tiles per wave, ONE workgroup per CU -- measured
+// 14 % slower on conv8_2 and 33 % slower on the heads than 8x32 with two workgroups per CU, and
+// weights held in registers instead of LDS spilled at the 256-VGPR budget of two workgroups: what
+// these short-K layers need is a second workgroup to run under the first one's waits)
+struct Stationary : Plain { static constexpr int BSTAT = 1; };
+// the packed image is the row-merged one (dn_spconv_set_upmode(1)): only the tiles that implement it
+struct RowMerged : Plain { static constexpr int UPM = 1; };
+// hi-only source 0 (math = 3): the 8 x 32 x 32 tile, weight-stationary when the layer fits
+struct HiOnly : Plain { static constexpr int AHI = 1; };
+struct HiOnlyStationary : Stationary { static constexpr int AHI = 1; };
+// bit-grid source 0 (math = 4): the same tile, staged by expansion; weight-stationary only
+struct BitGrid : Stationary { static constexpr int AHI = 2; };
+// Three weight stages (round 5) on the 8 x 8-pixel tiles, whose steps (9 MFMAs per wave) are far shorter than the loaded L2 latency
+// and whose LDS has the room (stride 2: 78 KB, two workgroups per CU as before; stride 1: 53 KB, three as before).
+struct ThreeStages : Plain { static constexpr int NB = 3; };
+// fused 1x1 stage behind a 64-channel 3x3 (dn_spconv2d_post1x1), weights streamed / resident
+struct Fused1x1 : Plain { static constexpr int POST = 1; };
+struct Fused1x1Stationary : Stationary { static constexpr int POST = 1; };
+// block-diagonal second stage (the two detection heads): both heads in one workgroup, weights streamed: the input patch is
+// staged once (-4 % on the heads launch)
+struct Heads : Plain { static constexpr int POST = 2; };
+// tools: timing-only ablation n (results wrong by construction; tools/sp_conv_check.cpp): 1 = no weight DMA after the first step,
+// 2 = no patch DMA after the first chunk, 3 = neither, 4 = no epilogue stores, 5 = 3 + operands from registers (the MFMA stream
+// alone), 6 = 5 + no stores, 7 = 6 + no barriers
+template <int N> struct Ablation : Plain { static constexpr int ABL = N; };
 
-template <int KS, int STRIDE, int TH, int TW, int BN, int TG, int CA, int WAVES_M, int WAVES_N,
-          int WTM, int WTN, int POST = 0, int ABL = 0, int BSTAT = 0, int UPM = 0, int AHI = 0, int KSL = 0, int NB = 2>
+template <class G, class F>
+using TileOf = SpTile<G::KS, G::STRIDE, G::TH, G::TW, G::BN, G::TG, G::CA, G::WAVES_M, G::WAVES_N, G::WTM, G::WTN, F::POST, F::BSTAT,
+                      F::UPM, F::AHI, F::KSL, F::NB>;
+
+// G: a tile's geometry (Tile<id>::G), F: a form
+template <class G, class F>
 int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
-  using T = SpTile<KS, STRIDE, TH, TW, BN, TG, CA, WAVES_M, WAVES_N, WTM, WTN, POST, BSTAT, UPM, AHI, KSL, NB>;
+  constexpr int KS = G::KS, STRIDE = G::STRIDE, TH = G::TH, TW = G::TW, BN = G::BN, TG = G::TG, CA = G::CA, WAVES_M = G::WAVES_M,
+                WAVES_N = G::WAVES_N, WTM = G::WTM, WTN = G::WTN;
+  constexpr int POST = F::POST, ABL = F::ABL, BSTAT = F::BSTAT, UPM = F::UPM, AHI = F::AHI, KSL = F::KSL, NB = F::NB;
+  using T = TileOf<G, F>;
   auto kern = conv_sp_kernel<KS, STRIDE, TH, TW, BN, TG, CA, WAVES_M, WAVES_N, WTM, WTN, POST, ABL, BSTAT, UPM, AHI, KSL, NB>;
   const int nchunks = a.c0g + a.c1g;
   DN_REQUIRE(nchunks % CA == 0, "spconv: chunk count %d not a multiple of %d", nchunks, CA);
@@ -1578,12 +1633,35 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   return dn::check_launch("conv_sp_kernel");
 }
 
-// does the layer fit the weight-stationary form of tile <BN, TG> beside `wgs` workgroups per CU?
-inline bool fits_stationary(const dn_conv_desc& d, int bn, int a_stage, int extra, int wgs,
-                            bool any_blocks = false) {
-  if (d.ksize != 3 || d.stride != 1 || (d.c_out > bn && !any_blocks)) return false;
+// The dispatch names a form and the tiles it is built for: only what is listed is instantiated (SpTile's static_asserts
+// forbid most of the cross product, and hipcc schedules the shipped kernels differently when the set changes).
+// One tile:
+template <class F, SpCfgId ID>
+int launch_form(SpArgs& a, const dn_conv_desc& d, hipStream_t s) { return launch<typename Tile<ID>::G, F>(a, d, s); }
+// the tile with the runtime id `id`; kNotListed when the form is not built for it
+constexpr int kNotListed = -0x7fffffff;
+template <class F, SpCfgId... IDS>
+int launch_form(int id, SpArgs& a, const dn_conv_desc& d, hipStream_t s) {
+  int rc = kNotListed;
+  (void)(... || (id == IDS && ((rc = launch_form<F, IDS>(a, d, s)), true)));   // (a left fold: instantiated in list order)
+  return rc;
+}
+// ablation n of the listed ones of one tile
+template <SpCfgId ID, int... N>
+int launch_ablation(int n, SpArgs& a, const dn_conv_desc& d, hipStream_t s) {
+  int rc = kNotListed;
+  (void)(... || (n == N && ((rc = launch_form<Ablation<N>, ID>(a, d, s)), true)));
+  return rc;
+}
+
+// does the layer fit form F (a weight-stationary one) of tile ID beside `wgs` workgroups per CU, with `extra` bytes of LDS?
+template <class F, SpCfgId ID>
+inline bool fits_stationary(const dn_conv_desc& d, int extra, int wgs) {
+  constexpr int bn = Tile<ID>::BN;
+  static_assert(F::BSTAT != 0, "fits_stationary: a weight-stationary form");
+  if (d.ksize != 3 || d.stride != 1 || d.c_out > bn) return false;
   const int nchunks = chunks_of(d.c0) + chunks_of(d.c1);
-  const int bytes = 2 * a_stage + nchunks * 9 * 4 * bn * 16 + extra;
+  const int bytes = 2 * TileOf<Tile<ID>, F>::A_STAGE + nchunks * 9 * 4 * bn * 16 + extra;
   return bytes * wgs <= 160 * 1024;
 }
 
@@ -1863,143 +1941,76 @@ int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, con
   SpArgs a;
   if (int rc = fill_args(d, src0, src1, packed, scale, shift, out, a)) return rc;
   a.out_b = out_nhwc; a.ldo_b = ld_nhwc;      // POST 0: optional fp32 NHWC copy of the output
-  DN_REQUIRE(!out_nhwc || g_sp_force < 100, "spconv dual: not with a forced tools configuration");
+  DN_REQUIRE(!out_nhwc || g_sp_force < FORCE_TOOLS, "spconv dual: not with a forced tools configuration");
   hipStream_t s = (hipStream_t)stream;
   // K slices: a property of the LAYER (the caller passes the same count whatever the batch): results do not depend
   // on how a launch distributes the slices.  Layers with fewer chunks than slices, 1x1 layers, the row-merged image
   // and hi-only sources are refused rather than silently computed in another order.
   DN_REQUIRE(kslices == 1 || (ks_layer(*d) && a.c0g + a.c1g >= kslices),
              "spconv: %d K slices need a 3x3 layer of at least that many 16-channel chunks", kslices);
-  if (up_mode(*d) == 2) {   // the packed image is the quad-merged one: conv_spq.hip (tools: 20 / 21 force BN = 32 / 64)
+  if (up_mode(*d) == 2) {   // the packed image is the quad-merged one: conv_spq.hip, which takes its own codes for a forced form
     DN_REQUIRE(a.c1g == 0 || d->c0 % 16 == 0, "spconv: concat needs c0 %% 16 == 0");
-    return dn::spq_conv(d, src0, src1, packed, (size_t)a.wpk_bytes, scale, shift, out, a.cout_pad,
-                        g_sp_force == 20 ? 32 : g_sp_force == 21 ? 64 : g_sp_force == 22 ? 33 :
-                        (g_sp_force >= 23 && g_sp_force <= 25) ? 78 + g_sp_force : 0, s, kslices, (float*)workspace,
-                        workspace_bytes, out_nhwc, ld_nhwc);
+    const int f = g_sp_force;
+    const int bn = f == FORCE_SPQ_BN32 ? 32 : f == FORCE_SPQ_BN64 ? 64 : f == FORCE_SPQ_DEEP ? 33 :
+                   (f > FORCE_SPQ_ABL && f <= FORCE_SPQ_ABL + 3) ? 100 + (f - FORCE_SPQ_ABL) : 0;
+    return dn::spq_conv(d, src0, src1, packed, (size_t)a.wpk_bytes, scale, shift, out, a.cout_pad, bn, s, kslices,
+                        (float*)workspace, workspace_bytes, out_nhwc, ld_nhwc);
   }
   if (kslices > 1) {
     a.ks.count = kslices;
     a.ks.partial = (float*)workspace;
     a.ks_ws_bytes = workspace_bytes;
     const SpCfg c = select_cfg(*d, kslices, workspace != nullptr && workspace_bytes > 0);
-    switch (c.id) {
-      //                                   KS S  TH TW  BN TG CA WM WN WTM WTN          KSL
-      case S3_256x32:      return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3_128x64:      return launch<3, 1, 8, 16, 64, 3, 1, 2, 2, 2, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3_64x64:       return launch<3, 1, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3S2_128x64:    return launch<3, 2, 8, 16, 64, 3, 1, 2, 2, 2, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3S2_64x64:     return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3_64x64_T9:    return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3_128x64_T9:   return launch<3, 1, 8, 16, 64, 9, 1, 2, 2, 2, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3S2_64x64_T9:  return launch<3, 2, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      case S3S2_128x64_T9: return launch<3, 2, 8, 16, 64, 9, 1, 2, 2, 2, 1, 0, 0, 0, 0, 0, 1>(a, *d, s);
-      default: return dn::fail(DN_ERR_UNSUPPORTED, "spconv: tile configuration %d has no K-sliced form", (int)c.id);
-    }
+    const int rc = launch_form<KSliced, S3_256x32, S3_128x64, S3_64x64, S3S2_128x64, S3S2_64x64, S3_64x64_T9, S3_128x64_T9,
+                               S3S2_64x64_T9, S3S2_128x64_T9>(c.id, a, *d, s);
+    return rc != kNotListed ? rc : dn::fail(DN_ERR_UNSUPPORTED, "spconv: tile configuration %d has no K-sliced form", (int)c.id);
   }
-  if (d->math == 3) {   // hi-only source 0: the 8 x 32 x 32 tile, weight-stationary when the layer fits
-    using T32 = SpTile<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 1, 0, 1>;
-    if (fits_stationary(*d, 32, T32::A_STAGE, 0, 2)) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 1, 0, 1>(a, *d, s);
-    return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 0, 0, 1>(a, *d, s);
+  if (d->math == 3) {
+    if (fits_stationary<HiOnlyStationary, S3_256x32>(*d, 0, 2)) return launch_form<HiOnlyStationary, S3_256x32>(a, *d, s);
+    return launch_form<HiOnly, S3_256x32>(a, *d, s);
   }
-  if (d->math == 4) {   // bit-grid source 0: the same tile, staged by expansion; weight-stationary only
-    using T32 = SpTile<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 1, 0, 2>;
-    if (fits_stationary(*d, 32, T32::A_STAGE, 0, 2)) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 1, 0, 2>(a, *d, s);
+  if (d->math == 4) {
+    if (fits_stationary<BitGrid, S3_256x32>(*d, 0, 2)) return launch_form<BitGrid, S3_256x32>(a, *d, s);
     return dn::fail(DN_ERR_UNSUPPORTED, "spconv: a bit-grid source needs a layer whose weights fit the LDS (c_out <= 32)");
   }
   const SpCfg c = select_cfg(*d);
-  if (up_merged(*d)) {   // the packed image is the row-merged one: only the tiles that implement it
-    switch (c.id) {
-      case S3_256x64: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 0, 0, 1>(a, *d, s);
-      case S3_256x32: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 0, 1>(a, *d, s);
-      case S3_128x64: return launch<3, 1, 8, 16, 64, 3, 1, 2, 2, 2, 1, 0, 0, 0, 1>(a, *d, s);
-      default: return dn::fail(DN_ERR_UNSUPPORTED, "spconv: tile configuration %d has no row-merged form", (int)c.id);
-    }
+  if (up_merged(*d)) {
+    // (S3_256x64 is built although select_cfg never returns it for a row-merged layer: without it the set of kernels, and with
+    // it hipcc's schedule of the shipped ones, would change)
+    const int rc = launch_form<RowMerged, S3_256x64, S3_256x32, S3_128x64>(c.id, a, *d, s);
+    return rc != kNotListed ? rc : dn::fail(DN_ERR_UNSUPPORTED, "spconv: tile configuration %d has no row-merged form", (int)c.id);
   }
-  // tools: timing-only ablations (results wrong by construction; tools/sp_conv_check.cpp).  Those of the deep-regime tile are
-  // in every build: without them hipcc schedules the shipped 8 x 8 and 8 x 16 tiles' prologues differently (same registers,
-  // a few instructions moved), and the shipped kernels are to stay as measured.  The others only with DN_SP_ABL; without
-  // it a forced id 101.. falls through like any other.
-  if (g_sp_force >= 300 && d->ksize == 3 && d->stride == 1) {
-    switch (g_sp_force) {
-      case 301: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 1>(a, *d, s);   // the deep-regime tile
-      case 302: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 2>(a, *d, s);
-      case 303: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 3>(a, *d, s);
-      case 304: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 4>(a, *d, s);
-      case 305: return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1, 0, 5>(a, *d, s);
-      default: break;
-    }
+  // tools: the timing-only ablations.  Those of the deep-regime tile are in every build: without them hipcc schedules the
+  // shipped 8 x 8 and 8 x 16 tiles' prologues differently (same registers, a few instructions moved), and the shipped kernels
+  // are to stay as measured.  The others only with DN_SP_ABL; without it a forced id 101.. falls through like any other.
+  if (d->ksize == 3 && d->stride == 1) {
+    const int rc = launch_ablation<S3_64x64_T9, 1, 2, 3, 4, 5>(g_sp_force - FORCE_ABL_64x64_T9, a, *d, s);
+    if (rc != kNotListed) return rc;
   }
 #if DN_SP_ABL
-  if (g_sp_force >= 100 && d->ksize == 3 && d->stride == 1) {
-    switch (g_sp_force) {
-      case 101: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 1>(a, *d, s);
-      case 102: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 2>(a, *d, s);
-      case 103: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 3>(a, *d, s);
-      case 104: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 4>(a, *d, s);
-      case 105: return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 0, 5>(a, *d, s);
-      case 201: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 1>(a, *d, s);
-      case 202: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 2>(a, *d, s);
-      case 203: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 3>(a, *d, s);
-      case 204: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 4>(a, *d, s);
-      case 205: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 5>(a, *d, s);
-      case 206: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 6>(a, *d, s);
-      case 207: return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 7>(a, *d, s);
-      default: break;
-    }
+  if (d->ksize == 3 && d->stride == 1) {
+    int rc = launch_ablation<S3_256x64, 1, 2, 3, 4, 5>(g_sp_force - FORCE_ABL_256x64, a, *d, s);
+    if (rc == kNotListed) rc = launch_ablation<S3_256x32, 1, 2, 3, 4, 5, 6, 7>(g_sp_force - FORCE_ABL_256x32, a, *d, s);
+    if (rc != kNotListed) return rc;
   }
-  if (g_sp_force >= 400 && d->ksize == 3 && d->stride == 2) {
-    switch (g_sp_force) {
-      case 400: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0>(a, *d, s);   // as shipped in round 4 (two weight stages)
-      case 401: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 1>(a, *d, s);   // no weight DMA after the first step
-      case 402: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 2>(a, *d, s);   // no patch DMA after the first chunk
-      case 403: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 3>(a, *d, s);   // neither
-      case 404: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 4>(a, *d, s);   // no epilogue stores
-      case 405: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 5>(a, *d, s);   // 3 + operands from registers: the MFMA stream alone
-      case 407: return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 7>(a, *d, s);   // 5 + no stores, no barriers
-      default: break;
-    }
+  if (d->ksize == 3 && d->stride == 2) {
+    if (g_sp_force == FORCE_ABL_S2_64x64) return launch_form<Plain, S3S2_64x64>(a, *d, s);
+    const int rc = launch_ablation<S3S2_64x64, 1, 2, 3, 4, 5, 7>(g_sp_force - FORCE_ABL_S2_64x64, a, *d, s);
+    if (rc != kNotListed) return rc;
   }
 #endif
-  // weight-stationary forms (short-K full-resolution layers): two workgroups per CU
-  // (a 16x32-pixel stationary tile -- four MFMA tiles per wave, ONE workgroup per CU -- measured
-  // 14 % slower on conv8_2 and 33 % slower on the heads than 8x32 with two workgroups per CU, and
-  // weights held in registers instead of LDS spilled at the 256-VGPR budget of two workgroups: what
-  // these short-K layers need is a second workgroup to run under the first one's waits)
-  if (g_sp_force < 0 && c.id == S3_256x32) {
-    using T32 = SpTile<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 1>;
-    if (fits_stationary(*d, 32, T32::A_STAGE, 0, 2))
-      return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 1>(a, *d, s);
-  }
-  if (g_sp_force == S3_256x32_ST) return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1, 0, 0, 1>(a, *d, s);
-  // Three weight stages (round 5) on the 8 x 8-pixel tiles, whose steps (9 MFMAs per wave) are far shorter than the loaded L2 latency
-  // and whose LDS has the room (stride 2: 78 KB, two workgroups per CU as before; stride 1: 53 KB, three as before).  DN_SP_B3: bit 0 =
-  // the stride-2 tile, bit 1 = the stride-1 tile (A/B runs; the results are bit-identical -- same operands, same MFMA order).
+  if (g_sp_force < 0 && c.id == S3_256x32 && fits_stationary<Stationary, S3_256x32>(*d, 0, 2))
+    return launch_form<Stationary, S3_256x32>(a, *d, s);
+  if (g_sp_force == S3_256x32_ST) return launch_form<Stationary, S3_256x32_ST>(a, *d, s);
+  // DN_SP_B3: bit 0 = the stride-2 tile, bit 1 = the stride-1 tile (A/B runs; the results are bit-identical -- same operands,
+  // same MFMA order)
   static const int b3_env = [] { const char* e = getenv("DN_SP_B3"); return e ? atoi(e) : 3; }();
-  if (g_sp_force < 0 && c.id == S3S2_64x64 && (b3_env & 1))
-    return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 0, 3>(a, *d, s);
-  if (g_sp_force < 0 && c.id == S3_64x64 && (b3_env & 2))
-    return launch<3, 1, 8, 8, 64, 3, 1, 2, 2, 1, 1, 0, 0, 0, 0, 0, 0, 3>(a, *d, s);
-  switch (c.id) {
-    //                               KS S  TH TW  BN TG CA WM WN WTM WTN
-    case S3_256x64:   return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2>(a, *d, s);
-    case S3_256x32:   return launch<3, 1, 8, 32, 32, 3, 1, 4, 1, 2, 1>(a, *d, s);
-    case S3_128x64:   return launch<3, 1, 8, 16, 64, 3, 1, 2, 2, 2, 1>(a, *d, s);
-    case S3_64x64:    return launch<3, 1, 8, 8, 64, 3, 1, 2, 2, 1, 1>(a, *d, s);
-    case S3S2_128x64: return launch<3, 2, 8, 16, 64, 3, 1, 2, 2, 2, 1>(a, *d, s);
-    case S3S2_64x64:  return launch<3, 2, 8, 8, 64, 3, 1, 2, 2, 1, 1>(a, *d, s);
-    case S1_256x64:   return launch<1, 1, 8, 32, 64, 1, 2, 4, 1, 2, 2>(a, *d, s);
-    case S1_64x64:    return launch<1, 1, 8, 8, 64, 1, 4, 2, 2, 1, 1>(a, *d, s);
-    case S3_256x64_T9: return launch<3, 1, 8, 32, 64, 9, 1, 4, 1, 2, 2>(a, *d, s);
-    case S3_512x64:   return launch<3, 1, 16, 32, 64, 3, 1, 8, 1, 2, 2>(a, *d, s);
-    case S3_256x128:  return launch<3, 1, 8, 32, 128, 3, 1, 4, 2, 2, 2>(a, *d, s);
-    case S1_256x64_C1: return launch<1, 1, 8, 32, 64, 1, 1, 4, 1, 2, 2>(a, *d, s);
-    case S3_64x64_T9:  return launch<3, 1, 8, 8, 64, 9, 1, 2, 2, 1, 1>(a, *d, s);
-    case S3_128x64_T9: return launch<3, 1, 8, 16, 64, 9, 1, 2, 2, 2, 1>(a, *d, s);
-    case S3S2_64x64_T9: return launch<3, 2, 8, 8, 64, 9, 1, 2, 2, 1, 1>(a, *d, s);
-    case S3S2_128x64_T9: return launch<3, 2, 8, 16, 64, 9, 1, 2, 2, 2, 1>(a, *d, s);
-    default: break;
-  }
-  return dn::fail(DN_ERR_UNSUPPORTED, "spconv: no tile configuration");
+  if (g_sp_force < 0 && c.id == S3S2_64x64 && (b3_env & 1)) return launch_form<ThreeStages, S3S2_64x64>(a, *d, s);
+  if (g_sp_force < 0 && c.id == S3_64x64 && (b3_env & 2)) return launch_form<ThreeStages, S3_64x64>(a, *d, s);
+  const int rc = launch_form<Plain, S3_256x64, S3_256x32, S3_128x64, S3_64x64, S3S2_128x64, S3S2_64x64, S1_256x64, S1_64x64,
+                             S3_256x64_T9, S3_512x64, S3_256x128, S1_256x64_C1, S3_64x64_T9, S3_128x64_T9, S3S2_64x64_T9,
+                             S3S2_128x64_T9>(c.id, a, *d, s);
+  return rc != kNotListed ? rc : dn::fail(DN_ERR_UNSUPPORTED, "spconv: no tile configuration");
 }
 }  // namespace
 
@@ -2034,16 +2045,13 @@ extern "C" int dn_spconv2d_post1x1(const dn_conv_desc* d, const dn_post1x1_desc*
     DN_REQUIRE(out_f32 && p->split < p->c_out2 && p->split <= 64 &&
                    p->c_out2 - p->split <= 64,
                "spconv+1x1: the block-diagonal form needs two fp32 outputs of <= 64 columns each");
-    // both heads in one workgroup, weights streamed: the input patch is staged once (-4 % on the heads launch)
-    return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 2>(a, *d, (hipStream_t)stream);
+    return launch_form<Heads, S3_256x64>(a, *d, (hipStream_t)stream);
   }
-  {
-    using TP = SpTile<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1, 1>;
-    const int extra = TP::W2_BYTES + (out_f32 ? TP::NW * 32 * (p->c_out2 + 4) * 4 : 0) + 1024;   // + the static affine block
-    if (g_sp_force != 0 && fits_stationary(*d, 64, TP::A_STAGE, extra, 1))
-      return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1, 0, 1>(a, *d, (hipStream_t)stream);
-  }
-  return launch<3, 1, 8, 32, 64, 3, 1, 4, 1, 2, 2, 1>(a, *d, (hipStream_t)stream);
+  using TP = TileOf<Tile<S3_256x64>, Fused1x1Stationary>;
+  const int extra = TP::W2_BYTES + (out_f32 ? TP::NW * 32 * (p->c_out2 + 4) * 4 : 0) + 1024;   // + the static affine block
+  if (g_sp_force != 0 && fits_stationary<Fused1x1Stationary, S3_256x64>(*d, extra, 1))
+    return launch_form<Fused1x1Stationary, S3_256x64>(a, *d, (hipStream_t)stream);
+  return launch_form<Fused1x1, S3_256x64>(a, *d, (hipStream_t)stream);
 }
 
 #include "conv_pre_pair.inl"

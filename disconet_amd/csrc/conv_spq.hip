@@ -687,17 +687,6 @@ __global__ void spq_pack_weights_kernel(const float* __restrict__ w, unsigned ch
   }
 }
 
-// whole tiles of a K-sliced launch (as conv_sp.hip :: ks_plan): split the tiles of the last, under-filled round
-inline long spq_ks_plan(long T, long R, int S, size_t ws_bytes, size_t bytes_per_tile) {
-  if (S <= 1 || ws_bytes < bytes_per_tile) return T;
-  const long full = T / R, tail = T - full * R;
-  if (tail == 0) return T;
-  const double cost_split = (double)full + (double)((tail * S + R - 1) / R) / S;
-  if (cost_split > (double)(full + 1) - 0.2) return T;
-  const long max_split = (long)(ws_bytes / bytes_per_tile);
-  return tail > max_split ? T - max_split : full * R;
-}
-
 template <int BN, int DEEP = 0, int ABL = 0, int KSL = 0>
 int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
   using T = SpqTile<BN, DEEP>;
@@ -740,7 +729,7 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
     k.log2 = S == 4 ? 2 : 1; k.ngroups = ng;
     k.b1 = b[1]; k.b2 = S == 2 ? ng : b[2]; k.b3 = S == 2 ? ng : b[3];
     const size_t per_tile = (size_t)S * QNW * 2 * (BN / 32) * 16 * 64 * sizeof(float);
-    k.n_whole = (int)spq_ks_plan(total, resident, S, k.partial ? ws_bytes : 0, per_tile);
+    k.n_whole = (int)ks_plan(total, resident, S, k.partial ? ws_bytes : 0, per_tile);
     k.n_split = (int)(total - k.n_whole);
     k.fixup = 0;
     const long work = k.n_whole + (long)k.n_split * S;

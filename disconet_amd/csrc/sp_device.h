@@ -149,6 +149,19 @@ struct KSlices {
   int fixup;           // this launch only adds the partials of the split tiles and runs their epilogue
   __host__ __device__ int bound(int s) const { return s <= 0 ? 0 : s == 1 ? b1 : s == 2 ? b2 : s == 3 ? b3 : ngroups; }
 };
+// Which tiles of a K-sliced launch are split (host side: the launchers of conv_sp.hip and conv_spq.hip).  T whole-tile
+// items on R resident workgroups run floor(T / R) full rounds and a last one that leaves CUs idle (or, T < R, never fills the chip): the tiles of that
+// round are handed out slice by slice when that shortens the launch by a fifth of a round or more, as far as the
+// workspace reaches.  -> number of whole tiles.
+inline long ks_plan(long T, long R, int S, size_t ws_bytes, size_t bytes_per_tile) {
+  if (S <= 1 || ws_bytes < bytes_per_tile) return T;
+  const long full = T / R, tail = T - full * R;
+  if (tail == 0) return T;
+  const double cost_split = (double)full + (double)((tail * S + R - 1) / R) / S;
+  if (cost_split > (double)(full + 1) - 0.2) return T;
+  const long max_split = (long)(ws_bytes / bytes_per_tile);
+  return tail > max_split ? T - max_split : full * R;
+}
 
 // Lanes (j, 0) and (j, 1) hold channels 4h..4h+3 of octet X (x) and of octet Y (y).  After the
 // swaps lane (j, 0) holds octet X complete and lane (j, 1) octet Y complete, as 16 bytes.

@@ -305,17 +305,29 @@ UNREACHABLE = {sp(UPM=1)}
 
 # --- the guard on the table itself (no GPU) ---------------------------------------------------------------
 def _dispatch_forms():
-    """every non-ablation instantiation the three launchers are called with, read off the sources' launch<...> lists"""
+    """every non-ablation instantiation the three launchers are called with, read off the sources: conv_sp.hip's tile
+    table (the SP_TILE rows), its form definitions (struct NAME : BASE { static constexpr int FLAG = v; }) and the
+    launch_form<FORM, tiles...> call sites that pair them; conv_spq.hip's launch_spq<...> lists"""
     forms = set()
     csrc = os.path.join(ROOT, "disconet_amd", "csrc")
     with open(os.path.join(csrc, "conv_sp.hip")) as f:
         text = f.read()
-    for m in re.finditer(r"\blaunch<([0-9, ]+)>\(a, \*d", text):
-        v = [int(t) for t in m.group(1).split(",")]
-        ks, st, th, tw, bn, tg, ca = v[:7]
-        post, abl, bstat, upm, ahi, ksl, nb = (v[11:] + [0, 0, 0, 0, 0, 0, 2][len(v) - 11:])[:7]
-        if abl == 0:
-            forms.add(sp(ks, st, th, tw, bn, tg, ca, post, bstat, upm, ahi, ksl, nb))
+    tiles = {}
+    for m in re.finditer(r"^SP_TILE\((\w+),[^,]+,\s*\w+,\s*(?:Geom<([0-9, ]+)>|Tile<(\w+)>::G)\);", text, re.M):
+        tiles[m.group(1)] = [int(t) for t in m.group(2).split(",")] if m.group(2) else tiles[m.group(3)]
+    assert {k: i for i, k in enumerate(tiles)} == {k: v for k, v in CFG.items() if v < len(tiles)}, list(tiles)
+    flags = {}
+    for m in re.finditer(r"^struct (\w+)(?: : (\w+))? \{ static constexpr int ([^;]+); \};", text, re.M):
+        flags[m.group(1)] = dict(flags[m.group(2)]) if m.group(2) else {}
+        flags[m.group(1)].update((k.strip(), int(v)) for k, v in (kv.split("=") for kv in m.group(3).split(",")))
+    for m in re.finditer(r"\blaunch_form<(\w+), ([\w,\s]+)>\(", text):
+        if m.group(1) == "F":            # the helpers themselves; ablations go through launch_ablation<>
+            continue
+        f = flags[m.group(1)]
+        assert f["ABL"] == 0, m.group(0)
+        for tile in m.group(2).split(","):
+            ks, st, th, tw, bn, tg, ca = tiles[tile.strip()][:7]
+            forms.add(sp(ks, st, th, tw, bn, tg, ca, f["POST"], f["BSTAT"], f["UPM"], f["AHI"], f["KSL"], f["NB"]))
     with open(os.path.join(csrc, "conv_spq.hip")) as f:
         text = f.read()
     for m in re.finditer(r"\blaunch_spq<([0-9, ]+)>\(a, stream", text):
@@ -332,7 +344,7 @@ def test_table_lists_every_form_of_the_dispatch():
     every row holds both operand families"""
     table = {r.form for r in ROWS}
     found = _dispatch_forms()
-    assert len(found) >= 40, len(found)
+    assert len(found) == 43, len(found)
     missing = found - table - UNREACHABLE
     assert not missing, sorted(missing)
     assert not (table - found), sorted(table - found)
