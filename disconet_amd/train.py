@@ -21,7 +21,9 @@ Two ways in:
     DiscoNet.forward returns tensors attached to one autograd node whose backward is the
     explicit reverse pass (torch only routes d(loss)/d(cls, loc) in and parameter grads out).
 """
+import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -34,6 +36,9 @@ _WGRAD_MATH_DEFAULT = "sp"        # the weight gradients of the layers dn_conv_w
 _WGRAD_X_LIFT = 16.0              # power-of-two lift of the activations in that kernel (post-BatchNorm maps: |x| << 4094)
 _FWD_MATH_DEFAULT = "sp"          # round 6: the training forward's 3x3 / 1x1 convs on the inference engine's split-f16 LDS-DMA kernels
 _MOMENTUM = 0.1
+_LIFT_REFRESH_STEPS = 64          # a measured power-of-two lift (of a weight, of a layer's dz) is good for this many steps either way
+_LIFT_TEMPORARIES_MAX = 256       # entries of the weight-lift table beyond which a parentless temporary starts it over
+_PACK_KEEP_FORWARDS = 8           # a packed weight form nobody asked for in this many forwards leaves the one-launch set
 
 
 class _Layer:
@@ -209,6 +214,124 @@ def _fusion_index_lists(agents, only_v2i, num_agent_cpu, B, dev, ego_first=0, eg
                 order=i32(order), n_calls=len(order))
 
 
+class _Lifts:
+    """The measured power-of-two lifts of one engine and the one rule for their age.  Both tables hold (lift, step it was measured
+    at); measuring is a host read of a device maximum, so an entry is used until the step count has moved _LIFT_REFRESH_STEPS
+    either way (a resumed run may step backwards).
+    weights: the lift of a layer's weights for the split-f16 forward, per PARAMETER -- ("p", its offset in the flat buffer), a key
+      that survives allocator address reuse -- or per parentless temporary ("t", ...); dropped when the weights are replaced.
+    dz: layer name -> the lift of its dz for the split-f16 gradients; dropped when a dz outgrew its lift (TrainEngine.backward)."""
+
+    def __init__(self):
+        self.weights, self.dz = {}, {}
+
+    @staticmethod
+    def fresh(ent, step):
+        return ent is not None and abs(step - ent[1]) < _LIFT_REFRESH_STEPS
+
+    def set_weight(self, key, lift, step, temporary=False):
+        if temporary and len(self.weights) > _LIFT_TEMPORARIES_MAX:      # temporaries without a parent: do not let the table grow
+            self.weights.clear()
+        ent = self.weights[key] = (lift, step)
+        return ent
+
+    def set_dz(self, name, max_abs, step):
+        """max_abs = max |dz| as measured: its lift puts that near 2^8; nothing to lift (zero) or not finite: the layer has no lift"""
+        if not (max_abs > 0.0) or max_abs != max_abs or max_abs == float("inf"):
+            self.dz.pop(name, None)
+        else:
+            self.dz[name] = (float(2.0 ** max(-100, min(100, 8 - math.floor(math.log2(max_abs))))), step)
+
+    def drop_weights(self):
+        self.weights.clear()
+
+    def drop_dz(self):
+        self.dz.clear()
+
+
+class _PackJob(NamedTuple):
+    """one weight form of the one-launch packs: ops.PackSet's job (include/disconet_hip.h :: dn_pack_job) and whose lift it takes"""
+    desc: object          # a private copy of the conv descriptor (launch wrappers write into theirs)
+    weight: object        # [c_out, cin_total, taps] view of the forward weight, read in place
+    mode: int
+    cin_total: int
+    ci_first: int
+    n_in: int
+    lift: object          # the Parameter whose power-of-two lift is multiplied in (None: 1)
+
+
+class _EngineForms:
+    """the forms of one conv engine ("sp" / "nhwc"), keyed (flat offset, mode, ci_first, n_in, lifted) + the descriptor's fields"""
+
+    def __init__(self):
+        self.jobs, self.pending = {}, {}      # key -> _PackJob: in the set / asked for since the set was built
+        self.used = {}                        # key -> generation of the last forward that asked for it
+        self.single = set()                   # keys ops.PackSet does not take (a tap-merged layer: its own pack kernel)
+        self.set, self.image = None, {}       # the ops.PackSet of `jobs` (in their order), key -> its packed buffer
+        self.generation = -1                  # the forward whose weights the images hold
+
+
+class _PackedForms:
+    """The step's packed weights in one launch per conv engine.
+    A step packs every 3x3 layer's weights for the split-f16 engine twice -- as they are for the forward, flipped and transposed
+    (or as the four parity classes of a stride-2 layer) for the data gradient: ~70 launches of 4-7 us plus the flips' ~35, on a
+    stream with nothing to run beside them and a host that needs ~15 us per launch (profiles/r06_step_start_ab.txt).  A form
+    that was asked for in an earlier forward is a job of ops.PackSet: all jobs are packed by ONE launch at the start of each
+    forward (dn_spconv_pack_weights_multi: the same bytes), and get() hands the images out.  A form not in the set (yet), a
+    tap-merged layer, a weight outside the flat buffer, enabled = False (DN_TRAIN_PACK_MULTI=0): the single launches."""
+
+    def __init__(self, device, enabled=True):
+        self.device, self.enabled = device, enabled
+        self.generation = 0
+        self._engines = {}      # conv engine -> _EngineForms, in the order the forward first asked
+
+    def sizes(self):
+        """{conv engine: jobs of its set}"""
+        return {engine: fs.set.n for engine, fs in self._engines.items() if fs.set is not None}
+
+    def begin_forward(self, generation, wmul_of):
+        """at the start of forward `generation`: pack every known form from the parameters as they are now (wmul_of(Parameter)
+        -> its lift) -- one launch per conv engine"""
+        self.generation = generation
+        for engine, fs in self._engines.items():
+            if fs.pending:
+                fs.jobs.update(fs.pending)
+                fs.pending = {}
+                # forms nobody asked for in the last forwards leave the set (a change of dgrad_math, of the batch shape)
+                fs.jobs = {k: j for k, j in fs.jobs.items() if generation - fs.used.get(k, generation) <= _PACK_KEEP_FORWARDS}
+                jobs = list(fs.jobs.values())
+                fs.set = ops.PackSet([(j.desc, j.weight, j.mode, j.cin_total, j.ci_first, j.n_in) for j in jobs],
+                                     self.device, engine) if jobs else None
+                fs.image = dict(zip(fs.jobs, fs.set.buffers)) if jobs else {}
+            if fs.set is not None:
+                fs.set.run([wmul_of(j.lift) if j.lift is not None else 1.0 for j in fs.jobs.values()])
+                fs.generation = generation
+
+    def get(self, off, w, mode, dd, ci_first, n_in, lift, engine, single):
+        """the packed image, for the conv `dd` on `engine`, of the weight form (mode, ci_first, n_in: ops.PackSet) of `w`, which
+        lies at `off` in the flat buffer (None: elsewhere); lift: the Parameter whose power-of-two lift is multiplied in (None = 1).
+        This forward's one-launch image when the form is in the set, else `single()` (the per-layer launches) -- and a place in
+        the next set"""
+        if off is None or not self.enabled:
+            return single()
+        fs = self._engines.get(engine)
+        if fs is None:
+            fs = self._engines[engine] = _EngineForms()
+        key = (off, mode, ci_first, n_in, lift is not None) + _desc_key(dd)
+        fs.used[key] = self.generation
+        if fs.generation == self.generation:
+            img = fs.image.get(key)
+            if img is not None:
+                return img
+        if key not in fs.jobs and key not in fs.pending and key not in fs.single:
+            w3 = w.detach().reshape(w.shape[0], w.shape[1], -1)
+            if ops.PackSet.supported(dd, engine) and w3.is_contiguous() and w3.dtype == torch.float32:
+                fs.pending[key] = _PackJob(_desc_copy(dd), w3, mode, w3.shape[1], ci_first, n_in, lift)
+            else:
+                fs.single.add(key)
+        return single()
+
+
 class TrainEngine:
     # a second stream beside the conv kernels is refused unless DISCONET_UNSAFE_OVERLAP=1 (ops.check_overlap_request)
     overlap_streams = property(lambda self: self._overlap_streams,
@@ -248,7 +371,16 @@ class TrainEngine:
         self.fwd_math = fwd_math if fwd_math is not None else os.environ.get("DISCONET_FWD_MATH", _FWD_MATH_DEFAULT)
         if self.fwd_math not in ("nhwc", "sp"):
             raise ValueError("fwd_math must be 'nhwc' or 'sp' (got %r)" % (self.fwd_math,))
-        self._dz_lift = {}           # layer name -> (power-of-two lift of its dz, step it was measured at)
+        # reference paths of the bit-for-bit tests (tests/test_gpu_train_step.py), "0" = the older path; read here, once per engine
+        switch = lambda name: os.environ.get(name, "1") != "0"
+        self._dz_sp_only = switch("DN_TRAIN_DZ_SP_ONLY")      # a layer's fp32 dz is not written where nothing reads it (_layer_bwd)
+        self._wgrad_zsp = switch("DN_TRAIN_WGRAD_ZSP")        # the weight gradient reads dz from its SP copy (_conv_bwd)
+        # the bias gradients' folds of a pass launched together behind it (_pass_with_folds; DN_TRAIN_DEFER_FOLDS=0: None, a fold
+        # behind every sum); _folds_active: the same object while a pass runs
+        self._folds = T.DeferredFolds() if switch("DN_TRAIN_DEFER_FOLDS") else None
+        self._folds_active = None
+        self._lifts = _Lifts()
+        self._dz_lift = self._lifts.dz      # layer name -> (power-of-two lift of its dz, step it was measured at)
         self.f32_fallback_steps = 0  # backward passes that were re-run on the fp32 kernels after a clamped dz (backward())
         self.last_fallback_step = None
         self._force_range_flags = []  # tests: flag words OR-ed into the next range polls
@@ -256,6 +388,11 @@ class TrainEngine:
         self.step_count = 0
         self.generation = 0          # bumped by every forward(): the saved activations belong to it
         self._overlap_streams = False
+        self._side = None            # the second stream of overlap_streams (_side_stream)
+        self._range_word = None      # the device word the range flags are collected into (_range_flags)
+        # what a forward leaves for the backward and the running statistics
+        self._num_agent_cpu = self._batch = None
+        self.F = self.fctx = self.head1 = self.head_ctx = self.outs = self.last_result = None
         params = self._param_order(model)
         dev = params[0].device
         if dev.type != "cuda":
@@ -275,6 +412,7 @@ class TrainEngine:
             self.grad_of[id(p)] = (off, p.numel(), p.shape)
             off += n
         self.params = params
+        self._forms = _PackedForms(dev, enabled=switch("DN_TRAIN_PACK_MULTI"))      # one-launch weight packs (DN_TRAIN_PACK_MULTI=0: per layer)
         self._graph()
 
     # ------------------------------------------------------------------
@@ -282,13 +420,24 @@ class TrainEngine:
         return _param_order(model)
 
     def _side_stream(self, dev):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         return self._side
 
     def g(self, p, flat=None):
         off, n, shape = self.grad_of[id(p)]
         return (self.flat_g if flat is None else flat)[off:off + n].view(shape)
+
+    def _heads_merged(self, flat):
+        """the two heads' first convs / BatchNorms as ONE 64-channel layer: (weight [64, 32, 3, 3], bias, gamma, beta) as views of
+        `flat` (flat_p, or a gradient buffer) over the classification head's parameter and the regression head's behind it
+        (_param_order puts them side by side)"""
+        cls = self.model.classification
+
+        def view(p):
+            off = self.grad_of[id(p)][0]
+            return flat[off:off + 2 * p.numel()]
+        return view(cls.conv1.weight).view(64, 32, 3, 3), view(cls.conv1.bias), view(cls.bn1.weight), view(cls.bn1.bias)
 
     def _layers(self):      # the network's layer table (model.backbone_layers; the segmentation variant: seg.unet_layers)
         return backbone_layers(self.model.u_encoder, self.model.decoder)
@@ -323,21 +472,22 @@ class TrainEngine:
                           ld0=src0.stride(2), ld1=src1.stride(2) if src1 is not None else None,
                           ldo=out.stride(2) if out is not None else None, math=self._math())
         dev = src0.device
+        wmul = self._wmul_of(w if lift_of is None else lift_of) if d.math == 1 else 1.0
+        if out is None:
+            ho, wo = ops.conv_out_hw(d)
+            out = torch.empty((n, ho, wo, c_out), dtype=torch.float32, device=dev)
+        scale = self._const(dev, c_out, 1.0 / wmul)
+        shift = bias if bias is not None else self._const(dev, c_out, 0.0)
         sp0, sp1 = self._sp_copy(src0), (self._sp_copy(src1) if src1 is not None else None)
         if (self._sp_forward() and d.math == 1 and sp0 is not None and (src1 is None or sp1 is not None) and lift_of is None
                 and c_out % 4 == 0 and (c1 == 0 or c0 % 16 == 0)):
             # the inference engine's kernels on the SP copies the BatchNorm applies wrote (d stays the fp32 tensors' descriptor:
             # the backward's weight / data gradients read those)
             ds = ops.conv_desc(n, h_in, w_in, c0, c_out, ksize, stride, False, c1=c1, up0=up0)
-            wmul = self._wmul_of(w)
             packed = self._packed_form(w, 0, ds, 0, 0, lambda: ops.sp_pack_conv_weights(ds, w, wmul)[0], lift=w)
-            if out is None:
-                ho, wo = ops.conv_out_hw(ds)
-                out = torch.empty((n, ho, wo, c_out), dtype=torch.float32, device=dev)
-            ops.sp_conv2d_nhwc(ds, sp0, packed, self._const(dev, c_out, 1.0 / wmul),
-                               bias if bias is not None else self._const(dev, c_out, 0.0), out, src1=sp1)
+            ops.sp_conv2d_nhwc(ds, sp0, packed, scale, shift, out, src1=sp1)
             return out, d
-        wmul = self._wmul_of(w if lift_of is None else lift_of) if d.math == 1 else 1.0
+
         def single():
             wc = w if w is not None else cut[0].detach().reshape(c_out, -1)[:, cut[1]:cut[1] + c0].contiguous().view(c_out, c0, 1, 1)
             return ops.pack_conv_weights(d, wc if wmul == 1.0 else wc.detach() * wmul)
@@ -345,12 +495,7 @@ class TrainEngine:
             packed = self._packed_form(cut[0], 0, d, cut[1], 0, single, engine="nhwc", lift=lift_of if d.math == 1 else None)
         else:
             packed = self._packed_form(w, 0, d, 0, 0, single, engine="nhwc", lift=w if d.math == 1 else None)
-        one = self._const(dev, c_out, 1.0 / wmul)
-        shift = bias if bias is not None else self._const(dev, c_out, 0.0)
-        if out is None:
-            ho, wo = ops.conv_out_hw(d)
-            out = torch.empty((n, ho, wo, c_out), dtype=torch.float32, device=dev)
-        ops.conv2d(d, src0, packed, one, shift, src1=src1, out=out)
+        ops.conv2d(d, src0, packed, scale, shift, src1=src1, out=out)
         return out, d
 
     def _sp_forward(self):
@@ -372,17 +517,12 @@ class TrainEngine:
         of small weights out of the f16 subnormal range; 1 / wmul rides in the conv's scale vector).  The max |w|
         behind it is read back from the device (a host sync): cached per PARAMETER -- its offset in the flat buffer, a
         key that survives allocator address reuse; temporaries cut out of a parameter pass the parent (`lift_of`) --
-        and refreshed when the step count has moved 64 either way (a resumed run may step backwards); load_state_dict
-        drops the cache."""
+        and measured again once the entry is no longer fresh (_Lifts); load_state_dict drops the cache."""
         ent = self.grad_of.get(id(w))
         key = ("p", ent[0]) if ent is not None else ("t", w.data_ptr(), tuple(w.shape), w._version)
-        cache = self.__dict__.setdefault("_wmul_cache", {})
-        hit = cache.get(key)
-        if hit is None or abs(self.step_count - hit[1]) >= 64:
-            if ent is None and len(cache) > 256:      # temporaries without a parent: do not let the table grow
-                cache.clear()
-            hit = (ops._pow2_lift(w), self.step_count)
-            cache[key] = hit
+        hit = self._lifts.weights.get(key)
+        if not _Lifts.fresh(hit, self.step_count):
+            hit = self._lifts.set_weight(key, ops._pow2_lift(w), self.step_count, temporary=ent is None)
         return hit[0]
 
     def _const(self, dev, n, val, cache={}):
@@ -482,11 +622,11 @@ class TrainEngine:
         # the fp32 copy of dz is written only where something reads it: with the data gradient and the weight gradient on the SP
         # copy (dn_conv_wgrad_sp_z), the bias gradient out of the same launch and no re-measurement of the lift due this step,
         # nothing does -- a quarter of the launch's bytes (DN_TRAIN_DZ_SP_ONLY=0: always written)
-        sp_only = (sp is not None and fused_bias and wsp and ent is not None and abs(self.step_count - ent[1]) < 64
-                   and os.environ.get("DN_TRAIN_DZ_SP_ONLY", "1") != "0" and T.bn_form_supported(T.BN_FORM_DZ_NULL, c["z"], c["groups"]))
+        sp_only = (sp is not None and fused_bias and wsp and _Lifts.fresh(ent, self.step_count)
+                   and self._dz_sp_only and T.bn_form_supported(T.BN_FORM_DZ_NULL, c["z"], c["groups"]))
         dz = T.bn_backward(dy_a, c["y"], c["z"], c["mean"], c["var"], c["gamma"], _EPS, ggamma, gbeta,
                            relu=True, dy_b=dy_b, up_a=up_a, sp_out=sp, sp_lift=lift, relu_mask=c.get("mask"),
-                           dbias=gb if fused_bias else None, folds=self.__dict__.get("_folds_active") if fused_bias else None,
+                           dbias=gb if fused_bias else None, folds=self._folds_active if fused_bias else None,
                            want_dz=not sp_only, **self._bn_sync(c["z"], c["groups"]))
         if (lift is not None or wsp) and dz is not None:
             self._dz_lift_refresh(lay, dz)
@@ -504,7 +644,7 @@ class TrainEngine:
         only while 2^-3 <= |x| <= 65504, and a gradient's magnitude is anything -- so dz is LIFTED by a power of two that puts its
         largest element near 2^8 (19 binades of full precision below it, 256 x of head room above; include/disconet_train.h ::
         dn_bn_bwd_out.sp_lift).  The lift of a layer is measured (max |dz|, a host read) on the first step, which runs
-        that layer's data gradient in fp32, and again every 64 steps; a dz that outgrows it is clamped AND flagged (the range
+        that layer's data gradient in fp32, and again when it is no longer fresh (_Lifts); a dz that outgrows it is clamped AND flagged (the range
         guard polled at the end of the pass: backward() then drops the lifts and repeats the pass on the fp32 kernels)."""
         d = c["desc"]
         if (self.dgrad_math != "sp" or not need_dx or d.ksize != 3 or c["groups"] != 1
@@ -519,27 +659,22 @@ class TrainEngine:
         return ops.SpTensor(z.shape[0], z.shape[1], z.shape[2], z.shape[3], device=z.device), ent[0]
 
     def _dz_lift_refresh(self, lay, dz):
-        ent = self._dz_lift.get(lay.name)
-        if ent is not None and abs(self.step_count - ent[1]) < 64:
+        if _Lifts.fresh(self._dz_lift.get(lay.name), self.step_count):
             return
-        m = float(dz.abs().max())        # host read: first step and every 64th only
+        m = float(dz.abs().max())        # host read: the first step and each refresh only
         if self.shard is not None and self.shard.world > 1:
             t = torch.tensor([m], dtype=torch.float64, device=dz.device)
             m = float(self.shard.max_(t)[0])         # one lift for all ranks: the replicas must stay bit-identical
-        if not (m > 0.0) or m != m or m == float("inf"):
-            self._dz_lift.pop(lay.name, None)
-            return
-        import math
-        self._dz_lift[lay.name] = (float(2.0 ** max(-100, min(100, 8 - math.floor(math.log2(m))))), self.step_count)
+        self._lifts.set_dz(lay.name, m, self.step_count)
 
     def _conv_bwd(self, d, w, src0, src1, dz, gw, gb, need_dx=True, dw_cin_total=0, w_ci_first=0,
                   w_c_in=None, dx_out=None, dz_sp=None, dz_lift=None, wgrad_lift=None):
         # (the weight gradient reads dz from its SP copy where there is one with the same lift: the same bits, less staging work)
         T.conv_wgrad(d, src0, src1, dz, gw, dw_cin_total=dw_cin_total, sp_lift=wgrad_lift, x_lift=_WGRAD_X_LIFT,
                      dz_sp=dz_sp if (wgrad_lift is not None and dz_sp is not None and wgrad_lift == dz_lift and d.c_out % 16 == 0
-                                     and os.environ.get("DN_TRAIN_WGRAD_ZSP", "1") != "0") or dz is None else None)
+                                     and self._wgrad_zsp) or dz is None else None)
         if gb is not None:
-            T.channel_sum(dz, gb, folds=self.__dict__.get("_folds_active"))
+            T.channel_sum(dz, gb, folds=self._folds_active)
         if not need_dx:
             return None
         return self._dgrad(d, w, dz, w_ci_first, w_c_in, dx_out, dz_sp, dz_lift)
@@ -554,16 +689,25 @@ class TrainEngine:
         split-f16 form (dz_sp given: dz * dz_lift pre-split by the BatchNorm backward): the inference engine's LDS-DMA kernels
         (dn_spconv2d_nhwc), 1 / (dz_lift * wmul) in the scale vector."""
         w4 = w.reshape(w.shape[0], w.shape[1], d.ksize, d.ksize)
-        if dz_sp is not None and d.stride == 2:
+        n_in = (w4.shape[1] - ci_first) if c_in is None else c_in
+        sp = dz_sp is not None
+        s2d = sp and d.stride == 2            # the result is the space-to-depth image of dx
+        dev = dz_sp.data.device if sp else dz.device
+        assert dx_out is None or not s2d, "the space-to-depth form writes a buffer of its own"
+        if dx_out is None:
+            shape = (d.n_images, d.h_in // 2, d.w_in // 2, 4 * n_in) if s2d else (d.n_images, d.h_in, d.w_in, n_in)
+            dx_out = torch.empty(shape, dtype=torch.float32, device=dev)
+        c_dx = 4 * n_in if s2d else n_in
+        wmul = self._wmul_of(w) if sp else 1.0
+        scale = self._const(dev, c_dx, 1.0 / (dz_lift * wmul) if sp else 1.0)
+        zero = self._const(dev, c_dx, 0.0)
+        if s2d:
             # all four parity classes of the stride-2 layer's data gradient (include/disconet_train.h ::
             # dn_conv_dgrad_class_weights) as ONE stride-1 launch of the split-f16 engine over dz: the classes are the output
             # channel groups, [n, h_in / 2, w_in / 2, 4 c_in] -- the space-to-depth image of dx, read in place by the next
             # BatchNorm backward (up_a = 2).  27 of its 36 (class, tap) weight blocks are zero: 4 x the MFMAs the masked fp32
             # form runs, on an engine 16 x as fast per MFMA -- and dz is read once instead of four times.
-            n_in = (w4.shape[1] - ci_first) if c_in is None else c_in
-            dev = dz_sp.data.device
             dd = ops.conv_desc(d.n_images, d.h_in // 2, d.w_in // 2, d.c_out, 4 * n_in, 3, 1, False)
-            wmul = self._wmul_of(w)
 
             def pack_classes():
                 wt = torch.empty((4 * n_in, d.c_out, 3, 3), dtype=torch.float32, device=dev)
@@ -572,49 +716,29 @@ class TrainEngine:
                         k = py * 2 + px
                         T.dgrad_class_weights(w4, py, px, ci_first, n_in, out=wt[k * n_in:(k + 1) * n_in])
                 return ops.sp_pack_conv_weights(dd, wt, wmul)[0]
-            packed = self._packed_form(w, 2, dd, ci_first, n_in, pack_classes, lift=w)
-            out = torch.empty((d.n_images, d.h_in // 2, d.w_in // 2, 4 * n_in), dtype=torch.float32, device=dev)
-            ops.sp_conv2d_nhwc(dd, dz_sp, packed, self._const(dev, 4 * n_in, 1.0 / (dz_lift * wmul)),
-                               self._const(dev, 4 * n_in, 0.0), out)
-            out._dn_s2d = True
-            return out
-        if dz_sp is not None:
-            n_in = (w4.shape[1] - ci_first) if c_in is None else c_in
-            dev = dz_sp.data.device
+            ops.sp_conv2d_nhwc(dd, dz_sp, self._packed_form(w, 2, dd, ci_first, n_in, pack_classes, lift=w), scale, zero, dx_out)
+            dx_out._dn_s2d = True
+            return dx_out
+        if sp:
             dd = ops.conv_desc(d.n_images, d.h_in, d.w_in, d.c_out, n_in, 3, 1, False)
-            wmul = self._wmul_of(w)
             packed = self._packed_form(w, 1, dd, ci_first, n_in,
                                        lambda: ops.sp_pack_conv_weights(dd, T.dgrad_weights(w4, ci_first, n_in), wmul)[0], lift=w)
-            if dx_out is None:
-                dx_out = torch.empty((d.n_images, d.h_in, d.w_in, n_in), dtype=torch.float32, device=dev)
-            ops.sp_conv2d_nhwc(dd, dz_sp, packed, self._const(dev, n_in, 1.0 / (dz_lift * wmul)), self._const(dev, n_in, 0.0),
-                               dx_out)
+            ops.sp_conv2d_nhwc(dd, dz_sp, packed, scale, zero, dx_out)
             return dx_out
         if d.stride == 2 and d.ksize == 3 and d.h_in % 2 == 0 and d.w_in % 2 == 0:
             # parity-phase form: four stride-1 convs over dz of 1 / 2 / 2 / 4 taps, each writing one parity class of dx
             # (include/disconet_train.h :: dn_conv_dgrad_class_weights) -- a quarter of the zero-stuffed form's MFMAs
-            n_in = (w4.shape[1] - ci_first) if c_in is None else c_in
-            dev = dz.device
-            if dx_out is None:
-                dx_out = torch.empty((d.n_images, d.h_in, d.w_in, n_in), dtype=torch.float32, device=dev)
-            ho, wo = d.h_in // 2, d.w_in // 2
-            dd = ops.conv_desc(d.n_images, ho, wo, d.c_out, n_in, 3, 1, False, ld0=dz.stride(2), math=0)
-            one, zero = self._const(dev, n_in, 1.0), self._const(dev, n_in, 0.0)
+            dd = ops.conv_desc(d.n_images, d.h_in // 2, d.w_in // 2, d.c_out, n_in, 3, 1, False, ld0=dz.stride(2), math=0)
             for py in (0, 1):
                 for px in (0, 1):
                     v, mask = T.dgrad_class_weights(w4, py, px, ci_first, n_in)
-                    ops.conv2d_taps(dd, dz, ops.pack_conv_weights(dd, v), one, zero, dx_out[:, py::2, px::2, :], mask)
+                    ops.conv2d_taps(dd, dz, ops.pack_conv_weights(dd, v), scale, zero, dx_out[:, py::2, px::2, :], mask)
             return dx_out
-        c_in = (w4.shape[1] - ci_first) if c_in is None else c_in
-        dd = ops.conv_desc(d.n_images, d.h_in, d.w_in, d.c_out, c_in, d.ksize, 1, False,
-                           up0=2 if d.stride == 2 else 0, ld0=dz.stride(2),
-                           ldo=dx_out.stride(2) if dx_out is not None else None, math=0)
-        packed = self._packed_form(w, 1, dd, ci_first, c_in, lambda: ops.pack_conv_weights(dd, T.dgrad_weights(w4, ci_first, c_in)),
+        dd = ops.conv_desc(d.n_images, d.h_in, d.w_in, d.c_out, n_in, d.ksize, 1, False,
+                           up0=2 if d.stride == 2 else 0, ld0=dz.stride(2), ldo=dx_out.stride(2), math=0)
+        packed = self._packed_form(w, 1, dd, ci_first, n_in, lambda: ops.pack_conv_weights(dd, T.dgrad_weights(w4, ci_first, n_in)),
                                    engine="nhwc")
-        dev = dz.device
-        if dx_out is None:
-            dx_out = torch.empty((d.n_images, d.h_in, d.w_in, c_in), dtype=torch.float32, device=dev)
-        ops.conv2d(dd, dz, packed, self._const(dev, c_in, 1.0), self._const(dev, c_in, 0.0), out=dx_out)
+        ops.conv2d(dd, dz, packed, scale, zero, out=dx_out)
         return dx_out
 
     # ------------------------------------------------------------------
@@ -625,62 +749,11 @@ class TrainEngine:
         return fusion_lists(self.model.agent_num, self.model.only_v2i, trans, num_agent_cpu, B, dev,
                             ego_first=sh.first if sh is not None else 0, ego_count=sh.count if sh is not None else None, poses=poses)
 
-    # ------------------------------------------------------------------
-    # the step's packed weights in one launch
-    # ------------------------------------------------------------------
-    # A step packs every 3x3 layer's weights for the split-f16 engine twice -- as they are for the forward, flipped and transposed
-    # (or as the four parity classes of a stride-2 layer) for the data gradient: ~70 launches of 4-7 us plus the flips' ~35, on a
-    # stream with nothing to run beside them and a host that needs ~15 us per launch (profiles/r06_step_start_ab.txt).  A form
-    # that was asked for in an earlier forward is a job of ops.SpPackSet: all jobs are packed by ONE launch at the start of each
-    # forward (dn_spconv_pack_weights_multi: the same bytes), and _conv / _dgrad pick the images up.  A form not in the set
-    # (yet), a tap-merged layer, a temporary weight, DN_TRAIN_PACK_MULTI=0: the single launches, as before.
-    def _pack_multi_on(self):
-        return os.environ.get("DN_TRAIN_PACK_MULTI", "1") != "0"
-
-    def _pack_multi(self):
-        """at the start of a forward (after `generation` moved): pack every known form from the parameters as they are now --
-        one launch per conv engine"""
-        if not self._pack_multi_on():
-            return
-        for engine, ps in self.__dict__.get("_packset", {}).items():
-            if ps["pending"]:
-                jobs = dict(ps["jobs"])
-                jobs.update(ps["pending"])
-                # forms nobody asked for in the last 8 forwards leave the set (a change of dgrad_math, of the batch shape)
-                jobs = {k: j for k, j in jobs.items() if self.generation - ps["used"].get(k, self.generation) <= 8}
-                ps["pending"] = {}
-                ps["jobs"] = jobs
-                keys = list(jobs)
-                ps["set"] = ops.PackSet([jobs[k][:6] for k in keys], self.flat_p.device, engine) if keys else None
-                ps["image"] = {k: b for k, b in zip(keys, ps["set"].buffers)} if keys else {}
-                ps["lifts"] = [jobs[k][6] for k in keys]
-            if ps["set"] is not None:
-                ps["set"].run([self._wmul_of(w) if w is not None else 1.0 for w in ps["lifts"]])
-                ps["generation"] = self.generation
-
     def _packed_form(self, w, mode, dd, ci_first, n_in, single, engine="sp", lift=None):
-        """the packed image, for the conv `dd` on `engine`, of Parameter `w`'s weight form (mode, ci_first, n_in: ops.PackSet;
-        lift: the Parameter whose power-of-two lift is multiplied in, None = 1): this forward's one-launch image when the form is
-        in the set, else `single()` (the per-layer launches) -- and a place in the next set"""
+        """_PackedForms.get for `w`: a Parameter, or a labelled view of the flat buffer (`_dn_flat_off`); any other weight: single()"""
         ent = self.grad_of.get(id(w))
-        off = ent[0] if ent is not None else getattr(w, "_dn_flat_off", None)      # a Parameter, or a labelled view of the flat buffer
-        if off is None or not self._pack_multi_on():
-            return single()
-        ps = self.__dict__.setdefault("_packset", {}).setdefault(
-            engine, {"jobs": {}, "pending": {}, "used": {}, "image": {}, "single": set(), "set": None, "generation": -1})
-        key = (off, mode, ci_first, n_in, lift is not None) + _desc_key(dd)
-        ps["used"][key] = self.generation
-        if ps["generation"] == self.generation:
-            img = ps["image"].get(key)
-            if img is not None:
-                return img
-        if key not in ps["jobs"] and key not in ps["pending"] and key not in ps["single"]:
-            w3 = w.detach().reshape(w.shape[0], w.shape[1], -1)
-            if ops.PackSet.supported(dd, engine) and w3.is_contiguous() and w3.dtype == torch.float32:
-                ps["pending"][key] = (_desc_copy(dd), w3, mode, w3.shape[1], ci_first, n_in, lift)
-            else:
-                ps["single"].add(key)       # a tap-merged layer: its own pack kernel
-        return single()
+        off = ent[0] if ent is not None else getattr(w, "_dn_flat_off", None)
+        return self._forms.get(off, w, mode, dd, ci_first, n_in, lift, engine, single)
 
     # ------------------------------------------------------------------
     # forward (training mode)
@@ -700,7 +773,7 @@ class TrainEngine:
     def forward(self, bevs, trans_matrices, num_agent_tensor, batch_size):
         self.check_aliasing()
         self.generation += 1
-        self._pack_multi()
+        self._forms.begin_forward(self.generation, self._wmul_of)
         m, L = self.model, self.L
         A, B = m.agent_num, batch_size
         if m.layer != 3 and m.u_encoder.compress_level > 0:
@@ -779,15 +852,8 @@ class TrainEngine:
         # heads: both first convs as one 64-channel layer (their parameters are adjacent in the
         # flat buffer), then the two 1x1 prediction convs on the halves
         cls, reg = m.classification, m.regression.box_prediction
-        po, _, _ = self.grad_of[id(cls.conv1.weight)]
-        w1 = self.flat_p[po:po + 2 * cls.conv1.weight.numel()].view(64, 32, 3, 3)
-        w1._dn_flat_off = po                              # (its place in the flat buffer: the key of its packed forms)
-        bo, _, _ = self.grad_of[id(cls.conv1.bias)]
-        b1 = self.flat_p[bo:bo + 64]
-        go, _, _ = self.grad_of[id(cls.bn1.weight)]
-        gamma = self.flat_p[go:go + 64]
-        beo, _, _ = self.grad_of[id(cls.bn1.bias)]
-        beta = self.flat_p[beo:beo + 64]
+        w1, b1, gamma, beta = self._heads_merged(self.flat_p)
+        w1._dn_flat_off = self.grad_of[id(cls.conv1.weight)][0]      # (its place in the flat buffer: the key of its packed forms)
         self.head1 = _Layer("heads1", w1, b1, None, 3)
         h1 = self._layer_fwd(self.head1, x8, w=w1, b=b1, gamma=gamma, beta=beta, want_sp=False)
         cls_out, dc = self._conv(cls.conv2.weight, cls.conv2.bias, h1[..., :32], ksize=1)
@@ -842,7 +908,7 @@ class TrainEngine:
         G = self._pass_with_folds(*args, **kw)
         flags = self._range_flags()
         if flags & 1:
-            self._dz_lift.clear()
+            self._lifts.drop_dz()
             self.f32_fallback_steps += 1
             self.last_fallback_step = self.step_count
             G = self._pass_with_folds(*args, **kw)
@@ -858,18 +924,15 @@ class TrainEngine:
     def _pass_with_folds(self, *args, **kw):
         """one reverse pass; the folds of its bias gradients (sums over dz per channel: leaves, read by the optimizer only) are
         collected and launched together behind it (train_ops.DeferredFolds; DN_TRAIN_DEFER_FOLDS=0: each behind its sum)"""
-        if os.environ.get("DN_TRAIN_DEFER_FOLDS", "1") == "0":
+        if self._folds is None:
             return self._backward_pass(*args, **kw)
-        folds = self.__dict__.get("_folds")
-        if folds is None or len(folds._ws) > 256:      # (workspaces are kept per output tensor: a caller that hands in a new
-            folds = self._folds = T.DeferredFolds()    #  gradient buffer every pass must not grow them without bound)
-        self._folds_active = folds
+        self._folds_active = self._folds
         try:
             G = self._backward_pass(*args, **kw)
-            folds.run()
+            self._folds.run()
         finally:
+            self._folds.clear()
             self._folds_active = None
-            folds._jobs, folds._keep = [], []
         return G
 
     def _backward_pass(self, dcls, dloc, G=None, dkd=None):
@@ -895,13 +958,8 @@ class TrainEngine:
                        self.g(cls.conv2.bias, G), dx_out=dh1[..., :32])
         self._conv_bwd(hc["dr"], reg[3].weight, h1[..., 32:], None, dloc, self.g(reg[3].weight, G),
                        self.g(reg[3].bias, G), dx_out=dh1[..., 32:])
-
-        def merged(p, count):
-            off, _, _ = self.grad_of[id(p)]
-            return G[off:off + count]
-        dx8 = self._layer_bwd(self.head1, dh1, G, gw=merged(cls.conv1.weight, 64 * 32 * 9).view(64, 32, 3, 3),
-                              gb=merged(cls.conv1.bias, 64), ggamma=merged(cls.bn1.weight, 64),
-                              gbeta=merged(cls.bn1.bias, 64))
+        gw, gb, ggamma, gbeta = self._heads_merged(G)
+        dx8 = self._layer_bwd(self.head1, dh1, G, gw=gw, gb=gb, ggamma=ggamma, gbeta=gbeta)
 
         d = self._layer_bwd(L["conv8_2"], dx8, G)
         dcat8 = self._layer_bwd(L["conv8_1"], d, G)                     # [.., 64 (up x7) | 32 (x0)]
@@ -964,10 +1022,9 @@ class TrainEngine:
             return 0
         # stream-ordered collect into a word this engine keeps + one host read: the blocking dn_sp_range_flags synchronises the
         # whole device and allocates / frees its scratch word per call (measured ~2 ms per step inside a large process)
-        word = self.__dict__.get("_range_word")
-        if word is None or word.device != self.flat_p.device:
-            word = self._range_word = torch.zeros(1, dtype=torch.int32, device=self.flat_p.device)
-        word = ops.sp_range_flags_into(word, zero_first=True, reset=True)
+        if self._range_word is None:
+            self._range_word = torch.zeros(1, dtype=torch.int32, device=self.flat_p.device)
+        word = ops.sp_range_flags_into(self._range_word, zero_first=True, reset=True)
         if self._force_range_flags:                      # tests: pretend the guard tripped (on this rank only)
             word |= int(self._force_range_flags.pop(0))
         if sharded_run:
@@ -991,7 +1048,7 @@ class TrainEngine:
         dh1 = self._layer_bwd(L["mlp2"], dh2, G)
         dz1 = T.bn_backward(dh1, c["h1"], c["z1"], c["mean1"], c["var1"], f.bn1_1.weight, _EPS,
                             self.g(f.bn1_1.weight, G), self.g(f.bn1_1.bias, G), relu=True)
-        T.channel_sum(dz1, self.g(f.conv1_1.bias, G), folds=self.__dict__.get("_folds_active"))
+        T.channel_sum(dz1, self.g(f.conv1_1.bias, G), folds=self._folds_active)
         dE = T.pair_sum_ego(dz1, F["efirst"], F["epairs"], NI)
         gw1 = self.g(f.conv1_1.weight, G).view(128, 2 * C)
         T.conv_wgrad(c["d_e"], maps[:NI], None, dE, gw1[:, :C], dw_cin_total=2 * C)
@@ -1025,7 +1082,7 @@ class TrainEngine:
                 "exp_avg_sq": {names[id(p)]: view(self.flat_v, p).clone() for p in self.params}}
 
     def load_state_dict(self, sd):
-        self.__dict__.pop("_wmul_cache", None)      # weight lifts belong to the weights that were just replaced
+        self._lifts.drop_weights()      # weight lifts belong to the weights that were just replaced
         self.step_count, self.lr = int(sd["step"]), float(sd["lr"])
         self.betas, self.eps, self.weight_decay = tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
         for n, p in self.model.named_parameters():

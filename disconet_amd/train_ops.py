@@ -264,10 +264,18 @@ class DeferredFolds:
     """The channel-sum folds of one backward pass, launched together (dn_channel_sum_fold_multi).  The sums are leaves of the
     backward (bias gradients): bn_backward(..., dbias=, folds=) and channel_sum(..., folds=) leave their per-workgroup partials
     in a workspace of their own -- kept per output tensor across steps -- and run() folds them all in one launch; the outputs
-    are valid after it."""
+    are valid after it.  Owner of a pass: `folds.run()` behind it, `folds.clear()` in a finally."""
+    _MAX_WORKSPACES = 256      # kept per output tensor: a caller that hands in a new gradient buffer every pass must not grow them without bound
 
     def __init__(self):
         self._ws, self._jobs, self._keep = {}, [], []
+
+    def clear(self):
+        """drop the queued folds and what they keep alive (the end of a pass, run or not); a workspace table past its bound starts
+        over, so that the next pass begins with an empty one"""
+        self._jobs, self._keep = [], []
+        if len(self._ws) > self._MAX_WORKSPACES:
+            self._ws = {}
 
     def workspace(self, out, nbytes):
         key = (out.data_ptr(), out.numel(), sum(1 for _, o in self._keep if o.data_ptr() == out.data_ptr()))   # (a second sum into one tensor: its own partials)
@@ -287,7 +295,7 @@ class DeferredFolds:
         for q, (part, sums, out, nb, c, acc) in zip(jobs, self._jobs):
             q.partials, q.sums, q.out, q.n_blocks, q.c, q.accumulate = part, sums, out, nb, c, acc
         check(_lib.load().dn_channel_sum_fold_multi(jobs, len(self._jobs), _stream()), "dn_channel_sum_fold_multi")
-        self._jobs, self._keep = [], []
+        self.clear()
 
 
 def channel_sum(x, out, accumulate=False, folds=None):

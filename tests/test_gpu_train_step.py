@@ -607,7 +607,7 @@ def test_kd_train_step_at_baseline_size_properties():
 
 @pytest.mark.parametrize("case", ["cfg1", "ragged_a4"])
 def test_steps_on_the_one_launch_weight_packs_are_the_per_layer_packs_steps_bit_for_bit(case, monkeypatch):
-    """TrainEngine._pack_multi (default: every known weight form packed by one launch at the start of the forward) against the
+    """The training engine's _PackedForms (default: every known weight form packed by one launch at the start of the forward) against the
     per-layer launches (DN_TRAIN_PACK_MULTI=0): seven steps from one state -- every parameter the same bits at the end, the losses
     equal (their last bits are the reduction's, not repeatable run to run); an in-place torch update the engine is not told about
     is picked up, update = False steps and a forced fallback pass read the same images."""
@@ -630,8 +630,7 @@ def test_steps_on_the_one_launch_weight_packs_are_the_per_layer_packs_steps_bit_
         losses.append(mod.step(data, c["batch"])["loss"])
         assert mod.engine.f32_fallback_steps == 1
         losses.append(mod.step(data, c["batch"])["loss"])
-        sets = mod.engine.__dict__.get("_packset", {})
-        return losses, mod.engine.flat_p.clone(), {e: ps["set"].n for e, ps in sets.items() if ps["set"] is not None}
+        return losses, mod.engine.flat_p.clone(), mod.engine._forms.sizes()
 
 
     l0, p0, n0 = run("0")
@@ -662,7 +661,7 @@ def test_bias_gradient_folds_launched_together_give_the_same_gradients_bit_for_b
                 mod.engine._force_range_flags = [1]
             mod.step(data, c["batch"])
             grads.append(mod.engine.flat_g.clone())
-        return grads, mod.engine.__dict__.get("_folds")
+        return grads, mod.engine._folds
 
     g0, f0 = run("0")
     g1, f1 = run("1")
