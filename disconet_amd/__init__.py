@@ -7,11 +7,11 @@ include/disconet_hip.h).  See DESIGN.md.
 from .config import Config
 from .model import DiscoNet
 from . import holistic, targets
-from .seg import SegDiscoNet, SegModule
+from .seg import HostMeanIoU, MeanIoU, SegDiscoNet, SegModule
 from .holistic import holistic_views
 from .teacher import TeacherNet
 from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
-__all__ = ["Config", "DiscoNet", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "targets",
+__all__ = ["Config", "DiscoNet", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
            "assign_targets", "holistic", "holistic_views"]

@@ -195,6 +195,7 @@ SIGNATURES = {
     "dn_maxpool2_nhwc_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_upsample2_bilinear_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_upsample2_bilinear_nhwc_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dn_seg_confusion": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     # ---- include/disconet_train.h ----
     "dn_conv_wgrad_workspace": (c_size_t, [POINTER(ConvDesc)]),
     "dn_reduce_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),

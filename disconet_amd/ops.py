@@ -763,6 +763,60 @@ def seg_ce_loss(logits_nhwc, labels, want_grad=True, check_labels=True):
     return loss / counts[0].clamp(min=1).to(torch.float64), grad
 
 
+def _rows_ld(t, name):
+    """float32 rows [..., c] with unit channel stride whose pixels are `ld` floats apart: a dense map (ld = c) or a channel
+    slice of a wider dense map (ld > c) -> ld"""
+    c = t.shape[-1]
+    ok = t.dtype == torch.float32 and t.dim() >= 2 and (c == 1 or t.stride(-1) == 1)
+    ld, run = None, 1
+    for d in range(t.dim() - 2, -1, -1):            # every leading dimension dense over rows of ld floats
+        if t.shape[d] != 1:                         # (the stride of a dimension of size 1 says nothing)
+            if ld is None:
+                ld = t.stride(d) // run if t.stride(d) % run == 0 else -1
+            ok = ok and t.stride(d) == ld * run
+        run *= t.shape[d]
+    ld = c if ld is None else ld                    # one pixel in all: any ld will do
+    if not ok or ld < c:
+        raise _lib.DnError("%s must be float32 rows [..., channels] of a dense map or a channel slice of one (got %s, "
+                           "shape %s, strides %s)" % (name, t.dtype, tuple(t.shape), tuple(t.stride())))
+    return ld
+
+
+def seg_confusion(logits_nhwc, labels, state, live=None, want_pred=False):
+    """dn_seg_confusion: float32 logits [n, h, w, classes] (or [n, pixels, classes]; a channel slice of a wider map is fine)
+    vs labels [n, h, w] of any integer dtype; `state` [n, classes^2 + 1] int64 on the device is ACCUMULATED INTO:
+    state[img, y * classes + p] += the live pixels with label y and prediction p, the last word the ignored ones (label
+    outside [0, classes), -100 included, or live[img] == 0).  live: None or [n] bool / uint8.  One launch, no sync.
+    -> the prediction (int32, the shape of `labels`, == logits.argmax(-1), written for every pixel) or None."""
+    _need_gpu(logits_nhwc, labels, state, live)
+    classes = logits_nhwc.shape[-1]
+    ld = _rows_ld(logits_nhwc, "seg_confusion: logits")
+    n = logits_nhwc.shape[0]
+    pixels = logits_nhwc.numel() // classes
+    if state.dtype != torch.int64 or not state.is_contiguous() or tuple(state.shape) != (n, classes * classes + 1):
+        raise _lib.DnError("seg_confusion: state must be contiguous int64 [%d, %d] (got %s %s)"
+                           % (n, classes * classes + 1, state.dtype, tuple(state.shape)))
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise _lib.DnError("seg_confusion: labels must be integers (got %s)" % labels.dtype)
+    # uint8 label maps are legal input (the reference casts with labels.long()): widen BEFORE the ignore index can matter.
+    # A dtype wider than int32 is clamped to [-1, classes] first: a label such as 2^32 + 3 must stay out of range, not wrap
+    lab = labels.to(device=logits_nhwc.device)
+    if lab.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8):
+        lab = lab.to(torch.int64).clamp(-1, classes)
+    lab = lab.to(torch.int32).contiguous()
+    if lab.numel() != pixels:
+        raise _lib.DnError("seg_confusion: %d labels for %d pixels" % (lab.numel(), pixels))
+    mask = None
+    if live is not None:
+        mask = (live.to(device=logits_nhwc.device) != 0).to(torch.uint8).contiguous()
+        if mask.numel() != n:
+            raise _lib.DnError("seg_confusion: live has %d entries for %d images" % (mask.numel(), n))
+    pred = torch.empty(lab.shape, dtype=torch.int32, device=logits_nhwc.device) if want_pred else None
+    check(_lib.load().dn_seg_confusion(_ptr(logits_nhwc), ld, _ptr(lab), _ptr(mask), n, pixels // n, classes, _ptr(state),
+                                       _ptr(pred), _stream()), "dn_seg_confusion")
+    return pred
+
+
 def pack_post1x1_weights(weight):
     """weight [c_out2, c_in2(, 1, 1)] -> packed split-f16 rows for dn_conv2d_post1x1."""
     _need_gpu(weight)

@@ -20,10 +20,12 @@ torch modules that are never called; the eval forward packs them once and runs
     Upsample x2 bilinear      dn_sp_upsample2_bilinear
     fusion at x4              dn_warp_neighbors + attention MLP + dn_disco_fuse_tail (C = 512)
     cross entropy (SegModule) dn_seg_ce_loss: value + d/d(logits)
+    mean IoU (MeanIoU)        dn_seg_confusion: arg-max + per-image confusion counts, on the device behind the forward
 
 There is no torch / CPU fallback.  Training: SegModule.step (seg_train.py: the detector's training engine + the
 UNet's max-pool / bilinear-upsample backward kernels).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -161,10 +163,15 @@ class SegModule:
         """upstream SegModule.step: one training step (train-mode forward with batch statistics, cross entropy,
         explicit HIP reverse pass, Adam) -> {"loss": float}.  The training engine is built on first use (its flat
         parameter buffer re-points the module's Parameters: build after the model is on the GPU)."""
+        return self.build_engine()._trainer.step(data, batch_size)
+
+    def build_engine(self):
+        """build the training engine now (step() does it on first use): a tool that resumes needs `engine` before the first
+        step, to load the optimizer state into it.  -> self"""
         if self._trainer is None:
             from .seg_train import SegTrainStep
             self._trainer = SegTrainStep(self.model, self._optimizer, self._lr)
-        return self._trainer.step(data, batch_size)
+        return self
 
     def loss(self, logits, labels, want_grad=True):
         """logits [N, classes, H, W] (the model's NCHW-shaped, channels-last view), labels [N, H, W]
@@ -175,9 +182,168 @@ class SegModule:
         loss, grad = ops.seg_ce_loss(z, labels, want_grad)
         return float(loss), (grad.permute(0, 3, 1, 2) if grad is not None else None)
 
-    def evaluate(self, data, batch_size):
+    def evaluate(self, data, batch_size, metric=None):
+        """the eval forward + the cross entropy -> {"loss": float, "pred": [A*B, H, W] int64}.  metric: a MeanIoU -- it is
+        updated on the device (one dn_seg_confusion launch, no sync) and `pred` comes from that launch; the images whose
+        BEV is empty (the padded agent slots: SegTrainStep.step's rule, sum <= 1e-4) are ignored by the metric whatever
+        their labels are.  metric=None: exactly the forward, the loss and logits.argmax(1)."""
         with torch.no_grad():
             out = self.model(data["bev_seq"], data["trans_matrices"], data["num_agent"], batch_size)
         logits = out[0] if isinstance(out, tuple) else out
         loss, _ = self.loss(logits, data["labels"], want_grad=False)
-        return {"loss": loss, "pred": logits.argmax(1)}
+        if metric is None:
+            return {"loss": loss, "pred": logits.argmax(1)}
+        bev = data["bev_seq"]
+        bev = bev.nhwc() if isinstance(bev, ops.SpTensor) else bev
+        live = bev.reshape(bev.shape[0], -1).sum(1) > 1e-4               # on the device, no sync
+        pred = metric.update(logits, data["labels"], live=live, want_pred=True)
+        return {"loss": loss, "pred": pred.long()}
+
+
+# ---------------------------------------------------------------------------
+# mean IoU: the seg variant's figure of merit
+# ---------------------------------------------------------------------------
+# Upstream's tools/seg/test_seg.py keeps this bookkeeping on the host; its source is not available to this project, so what
+# it computes is RECALLED, NOT PINNED: the contract is this project's own -- include/disconet_seg.h (dn_seg_confusion) for the
+# counts, miou_figures for the arithmetic, HostMeanIoU the numpy statement that the device equals bit for bit.
+def host_argmax(rows):
+    """the prediction rule of dn_seg_confusion on float32 rows [P, classes] (numpy): the index of the first NaN if the row
+    has one, else the index of the first maximum (-0.0 == +0.0; all -inf -> 0) -> [P] int32.  (== torch.argmax / numpy.argmax)"""
+    z = np.asarray(rows, dtype=np.float32)
+    nan = np.isnan(z)
+    top = np.where(nan, -np.inf, z).max(1)
+    first_max = (z == top[:, None]).argmax(1)               # argmax of booleans: the first True
+    return np.where(nan.any(1), nan.argmax(1), first_max).astype(np.int32)
+
+
+def miou_figures(confusion, ignored, ignore_classes=()):
+    """One confusion matrix [classes, classes] int64 (rows = label, columns = prediction) -> {"confusion", "iou" [classes]
+    float64 = TP / (TP + FP + FN), NaN for a class absent from both labels and predictions, "mIoU" = the mean over the
+    non-NaN classes not in ignore_classes (NaN if there is none), "accuracy" = trace / total over ALL classes (NaN without a
+    live pixel), "ignored": int}.  The sums are integers; every figure is one float64 division, the mean adds in class order."""
+    conf = np.asarray(confusion, dtype=np.int64)
+    classes = conf.shape[0]
+    tp = np.diagonal(conf)
+    union = conf.sum(1) + conf.sum(0) - tp                  # TP + FN  +  TP + FP  -  TP
+    iou = np.full(classes, np.nan, dtype=np.float64)
+    total, count = 0.0, 0
+    for c in range(classes):
+        if union[c] > 0:
+            iou[c] = float(tp[c]) / float(union[c])
+            if c not in ignore_classes:
+                total += iou[c]
+                count += 1
+    pixels = int(conf.sum())
+    return {"confusion": conf, "iou": iou, "mIoU": total / count if count else float("nan"),
+            "accuracy": float(int(tp.sum())) / float(pixels) if pixels else float("nan"), "ignored": int(ignored)}
+
+
+def miou_line(name, figures):
+    """the tools' line: `<name>: mIoU 0.1234  acc 0.5678  IoU 0.9 0.1 nan ...  ignored N`"""
+    return "%s: mIoU %.4f  acc %.4f  IoU %s  ignored %d" % (
+        name, figures["mIoU"], figures["accuracy"], " ".join("%.4f" % v for v in figures["iou"]), figures["ignored"])
+
+
+class _MeanIoUBase:
+    """what MeanIoU and HostMeanIoU share: the state's shape and compute()'s arithmetic on its host copy"""
+
+    def __init__(self, n_images, classes=8):
+        if not (2 <= int(classes) <= 32) or int(n_images) < 1:
+            raise ValueError("MeanIoU: %d images x %d classes (at least 1 image, 2 .. 32 classes)" % (n_images, classes))
+        self.n_images, self.classes = int(n_images), int(classes)
+
+    def _rows(self, logits):
+        """the model's NCHW-shaped channels-last view [n, classes, H, W] or NHWC [n, H, W, classes] -> NHWC.  A 4-d shape
+        with classes in both places is ambiguous and refused unless it is a channels-last view (unit stride at dimension 1
+        and not at the last one): hand NHWC rows as [n, pixels, classes] then."""
+        c = self.classes
+        if logits.ndim < 2 or logits.shape[0] != self.n_images or (logits.shape[-1] != c and (logits.ndim != 4 or logits.shape[1] != c)):
+            raise ValueError("MeanIoU: logits %s for %d images x %d classes" % (tuple(logits.shape), self.n_images, c))
+        nchw = logits.ndim == 4 and logits.shape[1] == c
+        if nchw and logits.shape[-1] == c:
+            nchw = self._channel_stride(logits, 1) == 1 and self._channel_stride(logits, 3) != 1
+            if not nchw:
+                raise ValueError("MeanIoU: logits %s could be NCHW or NHWC at %d classes; pass the model's channels-last "
+                                 "view or NHWC rows as [n, pixels, classes]" % (tuple(logits.shape), c))
+        if nchw:
+            return logits.transpose(0, 2, 3, 1) if isinstance(logits, np.ndarray) else logits.permute(0, 2, 3, 1)
+        return logits
+
+    @staticmethod
+    def _channel_stride(t, d):
+        return t.strides[d] // t.itemsize if isinstance(t, np.ndarray) else t.stride(d)
+
+    def state_host(self):
+        raise NotImplementedError
+
+    def compute(self, agents=None, ignore_classes=()):
+        """-> {"per_image": [figures] * n_images, "per_agent": [figures] * agents ([] without `agents`; image = agent * B + b),
+        "overall": figures}, figures as miou_figures.  Per agent and overall the confusion matrices are summed (integers)
+        before the one division: the mIoU of all pixels, not a mean of per-image mIoUs."""
+        state = self.state_host()
+        c = self.classes
+        conf, ignored = state[:, :c * c].reshape(self.n_images, c, c), state[:, c * c]
+        ignore_classes = tuple(int(k) for k in ignore_classes)
+        out = {"per_image": [miou_figures(conf[i], ignored[i], ignore_classes) for i in range(self.n_images)], "per_agent": []}
+        if agents is not None:
+            if agents < 1 or self.n_images % agents:
+                raise ValueError("MeanIoU.compute: %d images do not split over %d agents" % (self.n_images, agents))
+            b = self.n_images // agents
+            out["per_agent"] = [miou_figures(conf[a * b:(a + 1) * b].sum(0), ignored[a * b:(a + 1) * b].sum(), ignore_classes)
+                                for a in range(agents)]
+        out["overall"] = miou_figures(conf.sum(0), ignored.sum(), ignore_classes)
+        return out
+
+
+class MeanIoU(_MeanIoUBase):
+    """mean IoU on the GPU: the state [n_images, classes^2 + 1] int64 stays on the device, update() is one dn_seg_confusion
+    launch without a sync (capturable behind the forward), compute() copies the state once."""
+
+    def __init__(self, n_images, classes=8, device="cuda"):
+        super().__init__(n_images, classes)
+        self.state = torch.zeros((self.n_images, self.classes * self.classes + 1), dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.state.zero_()
+
+    def update(self, logits, labels, live=None, want_pred=False):
+        z = self._rows(logits)
+        if z.dtype != torch.float32 or z.stride(-1) != 1:
+            z = z.float().contiguous()
+        return ops.seg_confusion(z, labels, self.state, live, want_pred)
+
+    def state_host(self):
+        return self.state.cpu().numpy()
+
+
+class HostMeanIoU(_MeanIoUBase):
+    """The numpy statement of dn_seg_confusion + MeanIoU with the same interface (numpy arrays or CPU tensors in): the
+    reference of the bit-for-bit tests.  Written for its bits, not for speed."""
+
+    def __init__(self, n_images, classes=8, device=None):
+        super().__init__(n_images, classes)
+        self.state = np.zeros((self.n_images, self.classes * self.classes + 1), dtype=np.int64)
+
+    def reset(self):
+        self.state[:] = 0
+
+    def update(self, logits, labels, live=None, want_pred=False):
+        host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        c, n = self.classes, self.n_images
+        z = self._rows(host(logits))
+        y = host(labels)
+        if y.dtype.kind not in "iu":
+            raise ValueError("HostMeanIoU: labels must be integers (got %s)" % y.dtype)
+        y = y.astype(np.int64).reshape(n, -1)
+        pred = host_argmax(z.reshape(-1, c)).reshape(n, -1)
+        if y.shape != pred.shape:
+            raise ValueError("HostMeanIoU: %d labels for %d pixels" % (y.size, pred.size))
+        alive = np.ones(n, dtype=bool) if live is None else host(live).reshape(n) != 0
+        for img in range(n):
+            counted = (y[img] >= 0) & (y[img] < c) if alive[img] else np.zeros(y.shape[1], dtype=bool)
+            np.add.at(self.state[img], y[img][counted] * c + pred[img][counted], 1)
+            self.state[img, c * c] += int((~counted).sum())
+        return pred.reshape(host(labels).shape) if want_pred else None
+
+    def state_host(self):
+        return self.state.copy()

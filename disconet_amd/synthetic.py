@@ -292,6 +292,104 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
 
 
 # ---------------------------------------------------------------------------
+# labelled scenes for the seg variant: the world boxes above as per-pixel classes
+# ---------------------------------------------------------------------------
+SEG_CLASS_CAR, SEG_CLASS_LONG = 1, 2      # everything else is class 0; SegDiscoNet's other five classes never occur
+SEG_IGNORE = -100                         # nn.CrossEntropyLoss's ignore_index
+
+
+def seg_pixel_centres(cfg):
+    """(xs [H], ys [W]) float64: the centre of every BEV pixel under the voxeliser's index convention -- index
+    i = floor(x / voxel) - floor(extent_lo / voxel), so pixel i spans [(i + lo) voxel, (i + lo + 1) voxel) and its centre
+    is (i + lo + 0.5) * voxel with lo = floor(extent_lo / voxel).  H is the x index, W the y index (bev_seq's layout)."""
+    out = []
+    for d in range(2):
+        vs = float(cfg.voxel_size[d])
+        lo = math.floor(float(cfg.area_extents[d][0]) / vs)
+        out.append((np.arange(int(cfg.map_dims[d]), dtype=np.float64) + lo + 0.5) * vs)
+    return out[0], out[1]
+
+
+def make_seg_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_per_scene=24, clutter=200, device=None,
+                         ignore_border=0):
+    """Seeded scenes whose per-pixel labels and occupancy describe the same boxes (make_box_scene_batch's scenes with a
+    second population and label maps).  Per scene up to `boxes_per_scene` world boxes (x, y, w, h, sin, cos) sit on the
+    grid of pitch 8 m over agent 0's extents, centres jittered by at most 1 m, any yaw.  Box k with k % 3 == 1 is a long
+    vehicle (w ~ U(2.6, 3.2), h ~ U(10, 13): about 3 m x 12 m), class 2; every other box is car-sized (w ~ U(1.6, 2.4),
+    h ~ U(3.5, 5.5)), class 1; everything else is class 0.  Long vehicles may reach into a neighbour's cell: the rule
+    below says who wins.  Agent i sits at agent_pose(i); its cloud is the points on the boxes' sides and roofs
+    (_box_points) plus `clutter` seeded points, in its frame, put through the voxeliser, whose strict extent filter
+    keeps what the agent sees (ops.voxelize_occupy on `device`; device = None: host_occupancy, tensors stay on the host).
+
+    Labels, per image (image = agent * B + b), in float64: pixel (i, j) has the centre (xs[i], ys[j]) of
+    seg_pixel_centres.  With the world boxes carried into the agent's frame by boxes_in_agent_frame, dx = xs[i] - x,
+    dy = ys[j] - y, u = dx * cos + dy * sin, v = dy * cos - dx * sin, box k CONTAINS the centre iff |u| <= w / 2 and
+    |v| <= h / 2 -- the edges belong to the box.  The pixel takes the class of the LOWEST-index box that contains its
+    centre, else 0.  ignore_border = k > 0 then writes -100 into the k outermost rows and columns on every side.
+
+    Returns {"bev_seq" [A*B, Z, H, W] float32 (the NCHW-shaped view of the voxeliser's [H, W, Z] maps that
+    SegModule.step / evaluate read), "trans_matrices", "num_agent" (as make_scene_batch), "labels" [A*B, H, W] int64,
+    "world_boxes": per scene [K, 6] float64, "world_classes": per scene [K] int64, "points": per image [P, 4] float32}."""
+    from .config import Config
+    cfg = Config(map_hw=map_hw)
+    ext, vs, dims = cfg.area_extents, cfg.voxel_size, cfg.map_dims
+    half = float(ext[0][1])
+    cells = max(1, int(round(2 * half / BOX_SCENE_PITCH)))
+    n_img = num_agent * batch_size
+    xs, ys = seg_pixel_centres(cfg)
+    labels = np.zeros((n_img, dims[0], dims[1]), dtype=np.int64)
+    points, world, world_cls = [None] * n_img, [], []
+    for b in range(batch_size):
+        rng = np.random.RandomState((int(seed) * 9973 + b) % (2 ** 31))
+        k = min(int(boxes_per_scene), cells * cells)
+        cell = rng.permutation(cells * cells)[:k]
+        long_one = np.arange(k) % 3 == 1
+        wb = np.zeros((k, 6), dtype=np.float64)
+        wb[:, 0] = -half + (cell // cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+        wb[:, 1] = -half + (cell % cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+        wb[:, 2] = np.where(long_one, rng.uniform(2.6, 3.2, k), rng.uniform(1.6, 2.4, k))
+        wb[:, 3] = np.where(long_one, rng.uniform(10.0, 13.0, k), rng.uniform(3.5, 5.5, k))
+        yaw = rng.uniform(-math.pi, math.pi, k)
+        wb[:, 4], wb[:, 5] = np.sin(yaw), np.cos(yaw)
+        cls = np.where(long_one, SEG_CLASS_LONG, SEG_CLASS_CAR).astype(np.int64)
+        world.append(wb)
+        world_cls.append(cls)
+        cloud = np.concatenate([_box_points(row) for row in wb], 0) if k else np.zeros((0, 3))
+        for a in range(num_agent):
+            img = a * batch_size + b
+            mine = boxes_in_agent_frame(wb, a)
+            for j in range(k - 1, -1, -1):                  # highest index first: the lowest index is written last and wins
+                x, y, w, h, s, c = mine[j]
+                dx, dy = (xs - x)[:, None], (ys - y)[None, :]
+                u, v = dx * c + dy * s, dy * c - dx * s
+                labels[img][(np.abs(u) <= w / 2.0) & (np.abs(v) <= h / 2.0)] = cls[j]
+            T = np.linalg.inv(agent_pose(a))
+            pts = cloud.copy()
+            pts[:, 0] = T[0, 0] * cloud[:, 0] + T[0, 1] * cloud[:, 1] + T[0, 3]
+            pts[:, 1] = T[1, 0] * cloud[:, 0] + T[1, 1] * cloud[:, 1] + T[1, 3]
+            noise = rng.uniform([-half, -half, ext[2][0]], [half, half, ext[2][1]], size=(int(clutter), 3))
+            pts = np.concatenate([pts, noise], 0)
+            points[img] = np.concatenate([pts, rng.uniform(0, 1, (len(pts), 1))], 1).astype(np.float32)
+    kb = int(ignore_border)
+    if kb > 0:
+        frame = np.ones(labels.shape[1:], dtype=bool)
+        frame[kb:labels.shape[1] - kb, kb:labels.shape[2] - kb] = False
+        labels[:, frame] = SEG_IGNORE
+    if device is None:
+        bevs = torch.from_numpy(np.stack([host_occupancy(p, vs, ext, dims) for p in points], 0))
+    else:
+        from . import ops
+        bevs = torch.stack([ops.voxelize_occupy(torch.from_numpy(p).to(device), vs, ext, dims) for p in points], 0)
+    trans = make_trans_matrices(batch_size, num_agent)
+    na = torch.tensor([[num_agent] * num_agent for _ in range(batch_size)], dtype=torch.int64)
+    out = {"bev_seq": bevs.permute(0, 3, 1, 2), "trans_matrices": trans, "num_agent": na, "labels": torch.from_numpy(labels)}
+    if device is not None:
+        out = {key: value.to(device) for key, value in out.items()}
+    out["world_boxes"], out["world_classes"], out["points"] = world, world_cls, points
+    return out
+
+
+# ---------------------------------------------------------------------------
 # detection sequences for the tracker (tracking.Sort / HostSort)
 # ---------------------------------------------------------------------------
 def make_track_sequence(frames, n_images, seed=0, objects=6, width=None, noise=0.05, p_miss=0.1, false_positives=1,

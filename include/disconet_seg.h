@@ -52,6 +52,31 @@ int dn_seg_label_count(const int32_t* labels, long pixels, int classes, int32_t*
 int dn_seg_ce_loss(const float* logits, const int32_t* labels, long pixels, int classes, int ld,
                    float grad_scale, const int32_t* counts, double* loss_sum, float* dlogits, void* stream);
 
+/* Evaluation of the seg variant: the per-pixel prediction and each image's confusion matrix, from which the variant's
+ * figure of merit, mean IoU, follows (disconet_amd/seg.py :: MeanIoU.compute).  Upstream's tools/seg/test_seg.py keeps
+ * this bookkeeping on the host; its source is not available to this project, so what it computes is RECALLED, NOT PINNED:
+ * the contract below is this project's own, stated here and in numpy by seg.HostMeanIoU, which the device equals bit
+ * for bit.
+ *   logits  [n_images * pixels_per_image][ld] float32, the first `classes` columns are read (dn_seg_ce_loss's layout);
+ *           2 <= classes <= 32, ld >= classes.
+ *   prediction, per pixel: the index of the first NaN if the row has one, else the index of the first maximum; -0.0 and
+ *           +0.0 compare equal; a row of all -inf gives 0.  This is torch.argmax / numpy.argmax (checked on the CPU for
+ *           ties, NaN, +-inf and signed zeros): pred == logits.argmax(-1) exactly.
+ *   labels  [n_images * pixels_per_image] int32; a label outside [0, classes), the ignore index -100 included, makes
+ *           the pixel ignored (as in dn_seg_ce_loss).
+ *   live    may be NULL; one byte per image, 0 = every pixel of that image is ignored (upstream drops the empty BEVs of
+ *           padded agent slots before the criterion; SegTrainStep.step follows the same rule).
+ *   state   [n_images][classes * classes + 1] int64, 8-byte aligned, ACCUMULATED INTO and never zeroed by the call:
+ *           state[img][y * classes + p] += #{live pixels of img with label y and prediction p}; the last word counts the
+ *           image's ignored pixels.  Integer counts: the order of the atomics does not matter, the result is
+ *           deterministic.  It stays on the device for the whole evaluation.
+ *   pred    may be NULL; [n_images * pixels_per_image] int32, written for EVERY pixel, ignored ones included.
+ * One launch, no host sync, no allocation: it can be captured in a graph behind the forward.  classes == 8 && ld == 8
+ * on a 16-byte aligned map reads a row as two 16-byte loads; everything else (ld != classes: rows unaligned) takes the
+ * general path with scalar loads.  n_images <= 65535, pixels_per_image <= 2^40. */
+int dn_seg_confusion(const float* logits, int ld, const int32_t* labels, const uint8_t* live, int n_images,
+                     long pixels_per_image, int classes, int64_t* state, int32_t* pred, void* stream);
+
 /* ---- training forms on float32 NHWC maps (SegModule.step: the UNet's reverse pass; conventions of
  * disconet_train.h -- a gradient argument may be a channel slice of a wider map: pointer at its first
  * channel + the pixel stride ld in floats).  c % 4 == 0, 16-byte aligned buffers. ---- */
