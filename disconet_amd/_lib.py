@@ -170,6 +170,8 @@ SIGNATURES = {
                                   c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_neighbors_fm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dn_fuse_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_void_p, c_void_p]),
     "dn_disco_fuse_tail": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    POINTER(MlpTailParams), c_int, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -237,6 +239,9 @@ SIGNATURES = {
     "dn_fuse_combine_backward": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int,
                                                                              c_void_p, c_void_p,
                                                                              c_void_p]),
+    "dn_fuse_reduce_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dn_fuse_reduce_lists_backward": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p,
+                                                                                  c_void_p]),
     "dn_warp_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
     "dn_warp_list": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,

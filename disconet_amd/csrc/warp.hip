@@ -102,24 +102,8 @@ warp_neighbors_kernel(const float* __restrict__ feat, const float* __restrict__ 
   }
 }
 
-// ---- training form: an explicit list of warps, and the backward scatter ------------------
-struct PoseTerms {
-  float r00, r01, r10, r11, x_trans, y_trans;
-};
-__device__ inline PoseTerms pose_terms(const float* m) {
-  return PoseTerms{m[0], m[1], m[4], m[5], (4.f * m[3]) / 128.f, -(4.f * m[7]) / 128.f};
-}
-__device__ inline Bilinear pass2_taps(const PoseTerms& t, int px, int py, int w, int h) {
-  const float bx = (2.f * px + 1.f) / w - 1.f;
-  const float by = (2.f * py + 1.f) / h - 1.f;
-  return bilinear_taps(bx + t.x_trans, by + t.y_trans, w, h);
-}
-__device__ inline Bilinear pass1_taps(const PoseTerms& t, int qx, int qy, int w, int h) {
-  const float qbx = (2.f * qx + 1.f) / w - 1.f;
-  const float qby = (2.f * qy + 1.f) / h - 1.f;
-  return bilinear_taps(t.r00 * qbx + t.r01 * qby, t.r10 * qbx + t.r11 * qby, w, h);
-}
-
+// ---- training form: an explicit list of warps, and the backward scatter (pose_terms, pass1_taps and pass2_taps:
+// warp_device.h) ------------------
 __global__ void __launch_bounds__(256)
 warp_list_kernel(const float* __restrict__ src_maps, const float* __restrict__ poses,
                  const int32_t* __restrict__ src_image, int h, int w, int c,

@@ -70,4 +70,24 @@ __device__ inline f32x4 sample_src(const SrcImage& src, const Bilinear& b, int w
   return acc;
 }
 
+// The pose of one warp (4x4 row-major, neighbour -> ego) as the terms of the two passes, and their tap sets: pass 1 rotates
+// (rotated pixel q reads the source map), pass 2 translates (output pixel p reads the rotated map).  Shared by warp.hip's
+// list / backward kernels and fuse_reduce.hip.
+struct PoseTerms {
+  float r00, r01, r10, r11, x_trans, y_trans;
+};
+__device__ inline PoseTerms pose_terms(const float* m) {
+  return PoseTerms{m[0], m[1], m[4], m[5], (4.f * m[3]) / 128.f, -(4.f * m[7]) / 128.f};
+}
+__device__ inline Bilinear pass2_taps(const PoseTerms& t, int px, int py, int w, int h) {
+  const float bx = (2.f * px + 1.f) / w - 1.f;
+  const float by = (2.f * py + 1.f) / h - 1.f;
+  return bilinear_taps(bx + t.x_trans, by + t.y_trans, w, h);
+}
+__device__ inline Bilinear pass1_taps(const PoseTerms& t, int qx, int qy, int w, int h) {
+  const float qbx = (2.f * qx + 1.f) / w - 1.f;
+  const float qby = (2.f * qy + 1.f) / h - 1.f;
+  return bilinear_taps(t.r00 * qbx + t.r01 * qby, t.r10 * qbx + t.r11 * qby, w, h);
+}
+
 }  // namespace

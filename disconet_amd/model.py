@@ -534,7 +534,7 @@ class DiscoNet(_BackboneNet):
         self.decoder = _DecoderParams()
         self.classification = _ClsHeadParams(config)
         self.regression = _RegHeadParams(config, self.out_seq_len)
-        self.pixel_weighted_fusion = _FusionParams(LAYER_CHANNEL[layer])
+        self._create_fusion_params()
 
         # conv arithmetic: "f16x3" (default) = split-f16: every fp32 operand as hi + lo halves,
         # three f16 MFMAs per product, fp32 accumulate -- max abs deviation from the fp32 oracle
@@ -633,8 +633,21 @@ class DiscoNet(_BackboneNet):
             P["conv1_2_3d"] = _ConvPostLayer(
                 "conv1_2+3d", enc.conv1_2.weight.detach(), P["conv1_2"].affine[0], P["conv1_2"].affine[1],
                 c3.conv3d.weight.detach().reshape(64, 64), s3, t3, 64, True, math=math)
-        P.update(attention_mlp_plan(self.pixel_weighted_fusion, LAYER_CHANNEL[self.layer], math, self.fuse_mlp))
+        P.update(self._fusion_plan(math))
         return P
+
+    # the two places that name the collaboration strategy's own parameters: DiscoGraph's attention MLP here, nothing in the
+    # parameter-free baselines (fusion_modes.py), which override both and fuse()
+    def _create_fusion_params(self):
+        self.pixel_weighted_fusion = _FusionParams(LAYER_CHANNEL[self.layer])
+
+    def _fusion_plan(self, math):
+        return attention_mlp_plan(self.pixel_weighted_fusion, LAYER_CHANNEL[self.layer], math, self.fuse_mlp)
+
+    def _train_engine_class(self):
+        """the training engine of this model (train.train_forward, train.CoDetModule)"""
+        from .train import TrainEngine
+        return TrainEngine
 
     # ------------------------------------------------------------------
     # forward

@@ -870,6 +870,29 @@ def warp_neighbors(feat, trans, num_agent, batch, agents, only_v2i=False, ego_fi
     return warped
 
 
+FUSE_MODES = {"sum": 0, "mean": 1, "max": 2}      # DN_FUSE_SUM / DN_FUSE_MEAN / DN_FUSE_MAX
+
+
+def fuse_reduce(feat, trans, num_agent, batch, agents, mode, only_v2i=False, ego_first=0, ego_count=None, out=None):
+    """The parameter-free fusions `sum` / `mean` / `max` (include/disconet_hip.h :: dn_fuse_reduce): pose warp of every
+    listed neighbour and the reduction over the ego's list in one launch.  feat [A*B, h, w, C] agent-major NHWC (all
+    agents) -> fused [ego_count*B, h, w, C] float32 NHWC, image (i - ego_first) * B + b."""
+    _need_gpu(feat, trans, num_agent)
+    _f32c(feat, "feat")
+    _f32c(trans, "trans_matrices")
+    if mode not in FUSE_MODES:
+        raise ValueError("fuse_reduce mode must be one of %s (got %r)" % (sorted(FUSE_MODES), mode))
+    ego_count = agents if ego_count is None else ego_count
+    n, h, w, c = feat.shape
+    if n != agents * batch:
+        raise ValueError("feat has %d images, expected agents * batch = %d" % (n, agents * batch))
+    fused = out if out is not None else torch.empty((max(ego_count, 0) * batch, h, w, c), dtype=torch.float32,
+                                                     device=feat.device)
+    check(_lib.load().dn_fuse_reduce(_ptr(feat), _ptr(trans), _ptr(num_agent), batch, agents, h, w, c, int(only_v2i),
+                                     ego_first, ego_count, FUSE_MODES[mode], _ptr(fused), _stream()), "dn_fuse_reduce")
+    return fused
+
+
 def disco_fuse_tail(feat, warped, g, fw, num_agent, tail_params, batch, agents, only_v2i=False,
                     want_weights=False, ego_first=0, ego_count=None, out=None):
     """feat: maps of ALL agents; g / warped / fw and the result: the served egos only."""

@@ -446,7 +446,16 @@ class TrainEngine:
         # (a conv without BatchNorm -- the UNet's outc -- is no layer of the graph: it runs through _conv)
         self.L = {r.name: _Layer(r.name, r.weight, r.bias, r.bn, r.ksize, r.stride) for r in self._layers()
                   if r.bn is not None}
-        self.L.update(_fusion_mlp_layers(self.model.pixel_weighted_fusion))
+        self.L.update(self._fusion_layers())
+
+    def _fusion_layers(self):      # the fusion block's own conv + BatchNorm layers (none in the parameter-free baselines)
+        return _fusion_mlp_layers(self.model.pixel_weighted_fusion)
+
+    def _fusion_per_call_stats(self):
+        """(BatchNorm, mean, var) of the fusion block's BatchNorms that are updated once per CALL of the attention MLP"""
+        f, fc = self.model.pixel_weighted_fusion, self.fctx
+        return [(f.bn1_1, fc["mean1"], fc["var1"])] + [(lay.bn, lay.ctx["mean"], lay.ctx["var"]) for lay in self.L.values()
+                                                        if lay.per_call]
 
     # ------------------------------------------------------------------
     # one conv + BN(train) + ReLU
@@ -580,9 +589,7 @@ class TrainEngine:
             # (an agent shard: the statistics span every rank's images -- the unbiased variance's n / (n - 1) is the global batch's)
             T.bn_update_running(mean, var, z.numel() // z.shape[-1] * world, bn.running_mean, bn.running_var, _MOMENTUM)
         # the attention MLP's BatchNorms: the reference updates them once per CALL, in its loop order (scene, then ego)
-        f = m.pixel_weighted_fusion
-        per_call = [(f.bn1_1, fc["mean1"], fc["var1"])] + [(lay.bn, lay.ctx["mean"], lay.ctx["var"]) for lay in self.L.values()
-                                                            if lay.per_call]
+        per_call = self._fusion_per_call_stats()
         n_calls, order, rows = F["n_calls"], F["order"], lambda t: t
         if world > 1:
             # every rank owns some egos' calls: the per-call statistics travel (all-gather) and every rank replays all of them
@@ -591,7 +598,7 @@ class TrainEngine:
             local = F["order"].long()
             n_calls, order = calls["total"], calls["index"]
             rows = lambda t: self.shard.gather_padded(t[local], calls["max_per_rank"]).reshape(-1, t.shape[1])
-        if n_calls:
+        if n_calls and per_call:
             order, hw = order.to(fc["z1"].device), fc["z1"].shape[1] * fc["z1"].shape[2]
             for bn, mean, var in per_call:
                 T.bn_update_running(rows(mean), rows(var), hw, bn.running_mean, bn.running_var, _MOMENTUM, order)
@@ -1141,7 +1148,7 @@ def train_forward(model, bevs, trans_matrices, num_agent_tensor, batch_size):
     """DiscoNet.forward in train() mode"""
     eng = model.__dict__.get("_train_engine")
     if eng is None:
-        eng = TrainEngine(model)
+        eng = model._train_engine_class()(model)
         model.__dict__["_train_engine"] = eng
     if torch.is_grad_enabled():
         cls, loc, x8, x7, x6, x5, fused = _TrainFn.apply(eng, bevs, trans_matrices, num_agent_tensor,
@@ -1183,7 +1190,11 @@ class CoDetModule:
             lr = grp["lr"]
             kw = {"betas": tuple(grp.get("betas", (0.9, 0.999))), "eps": grp.get("eps", 1e-8),
                   "weight_decay": grp.get("weight_decay", 0.0)}
-        self.engine = TrainEngine(model, lr=lr, shard=shard, dgrad_math=dgrad_math, wgrad_math=wgrad_math, **kw)
+        engine_class = model._train_engine_class()
+        if kd_flag and not getattr(engine_class, "_KD_OK", True):
+            raise ValueError("kd_flag = 1: the distillation is DiscoGraph's (--com disco); %s has no teacher"
+                             % type(model).__name__)
+        self.engine = engine_class(model, lr=lr, shard=shard, dgrad_math=dgrad_math, wgrad_math=wgrad_math, **kw)
         model.__dict__["_train_engine"] = self.engine
         self.alpha, self.gamma, self.sigma = alpha, gamma, sigma
 

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .ops import _need_gpu, _ptr, _stream, _stream_handle, conv_desc
+from .ops import FUSE_MODES, _need_gpu, _ptr, _stream, _stream_handle, conv_desc
 
 
 def _ws(device, nbytes, cache={}):
@@ -412,6 +412,25 @@ def fuse_combine_backward(dfused, z4, weights, maps, first, pair_index, map_imag
         _ptr(map_image), _ptr(ego_out), ego_out.numel(), hw, c, _ptr(dmaps), _ptr(dz4), _stream()),
         "dn_fuse_combine_backward")
     return dz4
+
+
+def fuse_reduce_lists(maps, first, map_image, ego_out, mode, fused):
+    """maps [M, h, w, c]; per ego e the entries first[e] .. first[e+1) of map_image, its own map first; writes
+    fused[ego_out[e]] = sum / mean / max (ops.FUSE_MODES) over the list, in list order"""
+    _need_gpu(maps, fused)
+    hw, c = maps.shape[1] * maps.shape[2], maps.shape[3]
+    check(_lib.load().dn_fuse_reduce_lists(_ptr(maps), _ptr(first), _ptr(map_image), _ptr(ego_out), ego_out.numel(), hw, c,
+                                           FUSE_MODES[mode], _ptr(fused), _stream()), "dn_fuse_reduce_lists")
+    return fused
+
+
+def fuse_reduce_lists_backward(dfused, maps, fused, first, map_image, ego_out, mode, dmaps):
+    """writes one row of dmaps per listed map: dfused (sum), dfused / len (mean), dfused on the winner (max)"""
+    hw, c = maps.shape[1] * maps.shape[2], maps.shape[3]
+    check(_lib.load().dn_fuse_reduce_lists_backward(
+        _ptr(dfused), _ld(dfused), _ptr(maps), _ptr(fused), _ptr(first), _ptr(map_image), _ptr(ego_out), ego_out.numel(),
+        hw, c, FUSE_MODES[mode], _ptr(dmaps), _stream()), "dn_fuse_reduce_lists_backward")
+    return dmaps
 
 
 def warp_list(src, poses, src_image, out=None):

@@ -436,6 +436,36 @@ int dn_warp_neighbors(const float* feat, const float* trans, const int32_t* num_
                       int ego_first, int ego_count, float* warped, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The parameter-free collaboration baselines `--com sum | mean | max` (upstream SumFusion, MeanFusion, MaxFusion over
+ * FusionBase.forward; recalled from upstream, not pinned against its source): the pose warp of
+ * every listed neighbour and the reduction over the list in ONE launch -- no warped buffer, no workspace, no atomics, no
+ * host synchronisation; graph-capturable and bit-identical from run to run.
+ *   feat, trans, num_agent, only_v2i, ego_first, ego_count: as dn_warp_neighbors
+ *   mode   DN_FUSE_SUM, DN_FUSE_MEAN or DN_FUSE_MAX
+ *   fused  [ego_count*B][H][W][C] float32 NHWC, image (i - ego_first) * B + b
+ * The list.  For scene b with n = clamp(num_agent[b], 0, A) live agents and ego i < n: the ego's own map first, then
+ * for j = 0 .. n-1, j != i, ascending, the two-pass warp of agent j's map under trans[b][i][j]; only_v2i drops the
+ * pairs with i != 0 and j != 0.  (The order of oracle/disconet_ref.py :: DiscoNetRef.forward and train.fusion_lists.)
+ * The reductions, per element:
+ *   sum   fp32 adds, one after the other in list order (= torch.stack(list).sum(0) on the CPU, bit for bit, for 2..8
+ *         maps of a feature map's size)
+ *   mean  that sum divided by (float)len(list), an IEEE division (= .mean(0))
+ *   max   the first NaN of the list, else its first maximum (= torch.max(dim=0): the first index among ties)
+ * A padded ego (i >= n) passes through: fused = its own map, the same bits.  A dead neighbour's map is never read.
+ * agents == 1 copies the egos' maps.
+ * The warp is dn_warp_neighbors' arithmetic (csrc/warp_device.h: bilinear_taps, sample_src in the order nw, ne, sw, se,
+ * the pass-2 blend in tap order); a different kernel gives those values up to the compiler's per-kernel contraction (a
+ * few ulp), so nothing promises bit equality with dn_warp_neighbors followed by a reduction.
+ * DN_ERR_ARG: c % 4 != 0, a bad ego range, a null pointer, an unknown mode.  c % 64 == 0 (every model): one 8 x 8 tile
+ * x 64 channels of one ego image per workgroup, the neighbour loop inside it; other c: one pixel per wave.
+ * ------------------------------------------------------------------------ */
+#define DN_FUSE_SUM 0
+#define DN_FUSE_MEAN 1
+#define DN_FUSE_MAX 2
+int dn_fuse_reduce(const float* feat, const float* trans, const int32_t* num_agent, int batch, int agents, int h, int w,
+                   int c, int only_v2i, int ego_first, int ego_count, int mode, float* fused, void* stream);
+
+/* ------------------------------------------------------------------------
  * K5 tail + K6 -- per-pixel attention MLP tail, softmax over agents, weighted
  * sum.  Replaces PixelWeightedFusionSoftmax.forward layers 2-4 and the fusion
  * loop body of upstream:coperception/models/det/DiscoNet.py :: DiscoNet.forward

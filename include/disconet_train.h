@@ -259,6 +259,21 @@ int dn_fuse_combine_backward(const float* dfused, int ld_df, const float* z4, co
                              const int* map_image, const int* ego_out, int n_egos, int hw, int c,
                              float* dmaps, float* dz4, void* stream);
 
+/* The reductions of dn_fuse_reduce (disconet_hip.h: DN_FUSE_SUM / MEAN / MAX, the same rules and the same order) over
+ * explicit lists of maps the training forward keeps (dn_warp_list wrote the warps): for ego e in [0, n_egos) the entries
+ * first[e] .. first[e+1) of map_image, the ego's own map first; fused[ego_out[e]] is written.  A padded ego is a list
+ * of one: its map passes through, the same bits. */
+int dn_fuse_reduce_lists(const float* maps, const int32_t* first, const int32_t* map_image, const int32_t* ego_out,
+                         int n_egos, int hw, int c, int mode, float* fused, void* stream);
+/* backward: one row of dmaps per listed map (assignment: every map is in one list) --
+ *   sum: dfused;  mean: dfused / (float)len;  max: dfused on the winner of the element under the forward's rule (the
+ *   first NaN, else the first maximum; re-derived from `maps`) and 0 elsewhere;  a padded ego's row: dfused.
+ * ld: row stride of dfused in floats (a channel slice of a wider map), a multiple of 4.  fused: the forward's result,
+ * may be NULL (not read). */
+int dn_fuse_reduce_lists_backward(const float* dfused, int ld, const float* maps, const float* fused,
+                                  const int32_t* first, const int32_t* map_image, const int32_t* ego_out, int n_egos,
+                                  int hw, int c, int mode, float* dmaps, void* stream);
+
 /* Backward of dn_warp_neighbors for a list of warps: the gradient of warp w (source image
  * src_image[w] in [0, n_src_images), 4x4 pose at poses + 16 * w, row-major, neighbour -> ego) goes
  * back through both bilinear passes and is ADDED to d_src[src_image[w]].  scratch: n_warps maps.

@@ -3,7 +3,7 @@
 forward the detection tail on the GPU (postprocess.detect: top-k by score, rotated greedy NMS, one batched call).
 Prints per frame the forward time, the per-image detection counts and the tail's device time (events).
 
-    python tools/det/detect_codet.py --com disco [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+    python tools/det/detect_codet.py --com disco|sum|mean|max [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T]
 """
 import os
@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import Config, DiscoNet, postprocess  # noqa: E402
+from disconet_amd import COM_MODES, Config, build_model, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -29,13 +29,13 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the detection counts")
-    if args.com != "disco":
-        raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     config = Config("test", binary=True, only_det=True)
-    model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                     compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
+    model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
+                        compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
     if args.resume:
         checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(checkpoint["model_state_dict"])

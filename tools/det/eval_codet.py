@@ -3,7 +3,7 @@
 detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothing read back -- and after the last frame
 mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
 
-    python tools/det/eval_codet.py --com disco [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
+    python tools/det/eval_codet.py --com disco|sum|mean|max [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
@@ -24,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import Config, DiscoNet, postprocess  # noqa: E402
+from disconet_amd import COM_MODES, Config, build_model, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -44,14 +44,14 @@ def main(argv=None):
     args = build_eval_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
-    if args.com != "disco":
-        raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     config = Config("test", binary=True, only_det=True)
     torch.manual_seed(0)              # without --resume the weights are random: seeded, so that a run can be reproduced
-    model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                     compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
+    model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
+                        compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
     if args.resume:
         checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(checkpoint["model_state_dict"])

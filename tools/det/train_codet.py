@@ -7,7 +7,7 @@ resumes from `--resume` / `--resume_teacher` if given, and runs CoDetModule.step
 scenes and targets (there is no V2X-Sim data in this environment) through the MI355X path,
 writing `epoch_N.pth` with the reference's checkpoint keys.
 
-    python tools/det/train_codet.py --com disco [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
+    python tools/det/train_codet.py --com disco|sum|mean|max [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
         [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
         [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4]
@@ -37,7 +37,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
-from disconet_amd import CoDetModule, Config, DiscoNet, TeacherNet  # noqa: E402
+from disconet_amd import COM_MODES, CoDetModule, Config, TeacherNet, build_model  # noqa: E402
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
 
 
@@ -138,8 +138,8 @@ def main(argv=None):
         found = newest_checkpoint(args.auto_resume_path)
         if found:
             args.resume = found
-    if args.com != "disco":
-        raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -152,8 +152,8 @@ def main(argv=None):
     config = Config("train", binary=True, only_det=True)
     hw = config.map_dims[0]
     torch.manual_seed(0)
-    model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                     compress_level=args.compress_level, only_v2i=bool(args.only_v2i)).cuda()
+    model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
+                        compress_level=args.compress_level, only_v2i=bool(args.only_v2i)).cuda()
     teacher = None
     if args.kd_flag:
         teacher = TeacherNet(config).cuda()
