@@ -6,7 +6,8 @@ include/disconet_hip.h).  See DESIGN.md.
 """
 from .config import Config
 from .model import DiscoNet
-from .fusion_modes import COM_MODES, MaxFusion, MeanFusion, SumFusion, build_model
+from .fusion_modes import COM_MODES, DET_COM_MODES, MaxFusion, MeanFusion, NoFusion, SumFusion, build_model
+from .postprocess import late_fuse
 from . import holistic, targets
 from .seg import HostMeanIoU, MeanIoU, SegDiscoNet, SegModule
 from .holistic import holistic_views
@@ -14,5 +15,5 @@ from .teacher import TeacherNet
 from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
-__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "COM_MODES", "build_model", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
+__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "COM_MODES", "DET_COM_MODES", "build_model", "late_fuse", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
            "assign_targets", "holistic", "holistic_views"]

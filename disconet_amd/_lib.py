@@ -138,6 +138,10 @@ SIGNATURES = {
     "dn_detect_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "dn_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_double, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dn_late_fuse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dn_late_fuse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_double, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
     "dn_ap_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dn_ap_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int,

@@ -17,6 +17,12 @@
 //                      the kept rows, then zero / -1 padding up to top_k
 // Keys are 30-bit (a score is in [0, 1] or NaN), so three 10-bit digits find T.  Only integer atomics are used and
 // every ordering is decided by (key, index): the outputs are the same bits on every run.
+//
+// Late fusion (dn_late_fuse, `--com late`) sits behind dn_detect and ends in the same two kernels: per served ego image
+//   late_gather_sort   one workgroup: the rows of the ego's list (own rows, then every listed neighbour's carried into the
+//                      ego's frame in fp64), 64-bit sort words (score key | inverted list slot) sorted in LDS, the first
+//                      top_k rows written where detect_sort writes its own
+//   detect_iou_mask, detect_reduce   as above, on those rows; `index` is then the row's source, agent * k_in + row
 #include <cmath>
 
 #include "dn_internal.h"
@@ -393,6 +399,162 @@ __global__ void __launch_bounds__(kThreads) detect_reduce_kernel(const float* __
   if (threadIdx.x == 0) count[img] = n;
 }
 
+// detect_reduce's dynamic LDS (the mask rows of one image, up to 128 KB) is reserved once per device, by whichever entry
+// point runs first
+int reserve_reduce_lds(const char* who) {
+  const size_t reduce_lds = sizeof(unsigned long long) * (size_t)kMaxK * ((kMaxK + 63) / 64);
+  static dn::PerDeviceFlag lds_flag;
+  bool& lds_ready = lds_flag.here();
+  if (!lds_ready) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_reduce_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds);
+    if (e != hipSuccess)
+      return dn::fail(DN_ERR_LAUNCH, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, reduce_lds, hipGetErrorString(e));
+    lds_ready = true;
+  }
+  return DN_OK;
+}
+
+// ---- late fusion ----------------------------------------------------------------------------------------------------
+constexpr int kLateMaxAgents = 16;
+constexpr int kLateMaxSlots = 8192;      // agents * k_in: 64 KB of sort words in LDS
+constexpr int kLateThreads = 512;
+
+struct LateLayout {
+  size_t sbox, sscore, sidx, nvalid, mask, total;
+};
+
+LateLayout late_layout(int n, int top_k) {
+  const long nb = (top_k + 63) / 64;
+  LateLayout L;
+  size_t o = 0;
+  L.sbox = o;   o = align256(o + sizeof(float) * 6 * (size_t)n * top_k);
+  L.sscore = o; o = align256(o + sizeof(float) * (size_t)n * top_k);
+  L.sidx = o;   o = align256(o + sizeof(int) * (size_t)n * top_k);
+  L.nvalid = o; o = align256(o + sizeof(int) * (size_t)n);
+  L.mask = o;   o = align256(o + sizeof(unsigned long long) * (size_t)n * top_k * nb);
+  L.total = o;
+  return L;
+}
+
+bool late_shape_ok(int batch, int agents, int k_in, int top_k, int ego_first, int ego_count) {
+  return batch > 0 && agents > 0 && agents <= kLateMaxAgents && k_in >= 1 && k_in <= kMaxK &&
+         agents * k_in <= kLateMaxSlots && top_k >= 1 && top_k <= kMaxK && ego_first >= 0 && ego_count > 0 &&
+         ego_first + ego_count <= agents && (long)batch * ego_count <= 65535;
+}
+
+struct LateExtents {
+  double xlo, xhi, ylo, yhi;
+  int use;
+};
+
+// A neighbour's row (x, y, w, h, sin, cos) under M = trans[b][i][j] (row-major 4 x 4, fp32), in fp64: every product and
+// every sum rounded on its own, each result rounded once to fp32 (dn_voxelize_views' discipline; a product of two fp32
+// values is exact in fp64, so only the order of the additions counts).  w and h are copied, the heading is not renormalised.
+__device__ inline void carry_row(const float* __restrict__ row, const float* __restrict__ M, float* out) {
+#pragma clang fp contract(off)
+  const double m00 = M[0], m01 = M[1], m03 = M[3], m10 = M[4], m11 = M[5], m13 = M[7];
+  const double x = row[0], y = row[1], sn = row[4], cs = row[5];
+  out[0] = (float)((m00 * x + m01 * y) + m03);
+  out[1] = (float)((m10 * x + m11 * y) + m13);
+  out[2] = row[2];
+  out[3] = row[3];
+  out[4] = (float)(m10 * cs + m11 * sn);
+  out[5] = (float)(m00 * cs + m01 * sn);
+}
+
+// One workgroup per served ego image (i, b).  list[0] = i, then the listed neighbours ascending; slot = position * k_in +
+// row.  A slot is a candidate when its row is below its agent's clamped count, its score is finite and >= 0 (-0 counts,
+// and its key is +0's) and, for a neighbour's row under use_extents, the carried centre is strictly inside the extents.
+__global__ void __launch_bounds__(kLateThreads) late_gather_sort_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ count,
+    const float* __restrict__ trans, const int* __restrict__ num_agent, int batch, int agents, int k_in, int only_v2i,
+    int ego_first, int top_k, LateExtents ext, float* __restrict__ sbox, float* __restrict__ sscore,
+    int* __restrict__ sidx, int* __restrict__ nvalid) {
+  extern __shared__ unsigned long long sw[];   // [p]: p = the power of two that holds the list's slots
+  __shared__ int list[kLateMaxAgents], cnt[kLateMaxAgents];
+  __shared__ int len_s, nv;
+  const int img = blockIdx.x;                  // (i - ego_first) * batch + b
+  const int b = img % batch, i = ego_first + img / batch;
+  if (threadIdx.x == 0) {
+    int n = num_agent[b];
+    n = n < 0 ? 0 : (n > agents ? agents : n);
+    int len = 0;
+    list[len++] = i;
+    if (i < n)
+      for (int j = 0; j < n; ++j)
+        if (j != i && !(only_v2i && i != 0 && j != 0)) list[len++] = j;
+    for (int p = 0; p < len; ++p) {
+      const int c = count[list[p] * batch + b];
+      cnt[p] = c < 0 ? 0 : (c > k_in ? k_in : c);
+    }
+    len_s = len;
+    nv = 0;
+  }
+  __syncthreads();
+  const int len = len_s;
+  const int slots = len * k_in;
+  int p = 1;
+  while (p < slots) p <<= 1;
+  for (int e = threadIdx.x; e < p; e += kLateThreads) {
+    unsigned long long word = 0ull;
+    if (e < slots) {
+      const int pos = e / k_in, r = e - pos * k_in;
+      if (r < cnt[pos]) {
+        const int j = list[pos];
+        const size_t row = ((size_t)j * batch + b) * k_in + r;
+        const float s = scores[row];
+        bool cand = s >= 0.f && s < INFINITY;            // a NaN fails both
+        if (cand && pos > 0 && ext.use) {
+          float t[6];
+          carry_row(boxes + 6 * row, trans + (((size_t)b * agents + i) * agents + j) * 16, t);
+          const double x = (double)t[0], y = (double)t[1];
+          cand = ext.xlo < x && x < ext.xhi && ext.ylo < y && y < ext.yhi;
+        }
+        if (cand) word = sort_word((__float_as_uint(s) & 0x7fffffffu) + 1u, (unsigned)e);
+      }
+    }
+    sw[e] = word;
+  }
+  __syncthreads();
+  for (int size = 2; size <= p; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < p / 2; t += kLateThreads) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long x = sw[lo], y = sw[hi];
+        if ((x < y) == desc) {
+          sw[lo] = y;
+          sw[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int lim = top_k < p ? top_k : p;
+  for (int q = threadIdx.x; q < lim; q += kLateThreads) {
+    const unsigned long long word = sw[q];
+    if (word == 0ull) continue;
+    if (q + 1 == lim || sw[q + 1] == 0ull) nv = q + 1;
+    const int e = (int)(0xffffffffu - (unsigned)word);
+    const int pos = e / k_in, r = e - pos * k_in;
+    const int j = list[pos];
+    const size_t row = ((size_t)j * batch + b) * k_in + r;
+    const size_t o = (size_t)img * top_k + q;
+    float t[6];
+    if (pos == 0) {
+      for (int c = 0; c < 6; ++c) t[c] = boxes[6 * row + c];
+    } else {
+      carry_row(boxes + 6 * row, trans + (((size_t)b * agents + i) * agents + j) * 16, t);
+    }
+    for (int c = 0; c < 6; ++c) sbox[6 * o + c] = t[c];
+    sscore[o] = scores[row];
+    sidx[o] = j * k_in + r;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) nvalid[img] = nv;
+}
+
 }  // namespace
 
 extern "C" size_t dn_detect_workspace_bytes(int n_images, long anchors_per_image, int top_k) {
@@ -414,16 +576,7 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
              workspace_bytes, L.total);
   const long apl = anchors_per_image;
   const int nb = (top_k + 63) / 64;
-  const size_t reduce_lds = sizeof(unsigned long long) * (size_t)kMaxK * ((kMaxK + 63) / 64);
-  static dn::PerDeviceFlag lds_flag;
-  bool& lds_ready = lds_flag.here();
-  if (!lds_ready) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_reduce_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds);
-    if (e != hipSuccess)
-      return dn::fail(DN_ERR_LAUNCH, "detect: hipFuncSetAttribute(%zu B LDS): %s", reduce_lds, hipGetErrorString(e));
-    lds_ready = true;
-  }
+  if (const int rc = reserve_reduce_lds("detect")) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   unsigned* keys = reinterpret_cast<unsigned*>(ws + L.keys);
@@ -453,4 +606,71 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
                      sizeof(unsigned long long) * (size_t)top_k * nb, s, sbox, sscore, sidx, nvalid, mask, top_k, nb,
                      boxes, scores, index, count);
   return dn::check_launch("detect");
+}
+
+extern "C" size_t dn_late_fuse_workspace_bytes(int batch, int agents, int k_in, int top_k, int ego_first, int ego_count) {
+  if (!late_shape_ok(batch, agents, k_in, top_k, ego_first, ego_count)) return 0;
+  return late_layout(batch * ego_count, top_k).total;
+}
+
+extern "C" int dn_late_fuse(const float* boxes, const float* scores, const int32_t* count, const float* trans,
+                            const int32_t* num_agent, int batch, int agents, int k_in, int only_v2i, int ego_first,
+                            int ego_count, int top_k, double iou_thr, int use_extents, const double* xy_extents_host,
+                            float* out_boxes, float* out_scores, int32_t* out_source, int32_t* out_count,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  DN_REQUIRE(batch > 0 && agents > 0 && agents <= kLateMaxAgents, "late fuse: batch = %d, agents = %d, must be >= 1 and at most %d agents",
+             batch, agents, kLateMaxAgents);
+  DN_REQUIRE(k_in >= 1 && k_in <= kMaxK, "late fuse: k_in = %d, must be in [1, %d]", k_in, kMaxK);
+  DN_REQUIRE(agents * k_in <= kLateMaxSlots, "late fuse: agents * k_in = %d rows in one list, at most %d", agents * k_in,
+             kLateMaxSlots);
+  DN_REQUIRE(top_k >= 1 && top_k <= kMaxK, "late fuse: top_k = %d, must be in [1, %d]", top_k, kMaxK);
+  DN_REQUIRE(std::isfinite(iou_thr) && iou_thr >= 0, "late fuse: iou_thr = %g, must be finite and >= 0", iou_thr);
+  DN_REQUIRE(ego_first >= 0 && ego_count > 0 && ego_first + ego_count <= agents,
+             "late fuse: ego range [%d, %d) outside 0..%d", ego_first, ego_first + ego_count, agents);
+  DN_REQUIRE((long)batch * ego_count <= 65535, "late fuse: %ld output images, at most 65535", (long)batch * ego_count);
+  // (the shapes first: a refused shape may come with empty, null outputs)
+  DN_REQUIRE(boxes && scores && count && trans && num_agent && out_boxes && out_scores && out_source && out_count &&
+                 workspace, "late fuse: null pointer");
+  LateExtents ext = {0.0, 0.0, 0.0, 0.0, use_extents ? 1 : 0};
+  if (use_extents) {
+    DN_REQUIRE(xy_extents_host, "late fuse: use_extents without xy_extents");
+    ext.xlo = xy_extents_host[0];
+    ext.xhi = xy_extents_host[1];
+    ext.ylo = xy_extents_host[2];
+    ext.yhi = xy_extents_host[3];
+    DN_REQUIRE(ext.xlo < ext.xhi && ext.ylo < ext.yhi, "late fuse: extents (%g, %g) x (%g, %g) are empty or not numbers",
+               ext.xlo, ext.xhi, ext.ylo, ext.yhi);
+  }
+  const int n = batch * ego_count;
+  const LateLayout L = late_layout(n, top_k);
+  DN_REQUIRE(workspace_bytes >= L.total, "late fuse: workspace of %zu bytes, %zu needed (dn_late_fuse_workspace_bytes)",
+             workspace_bytes, L.total);
+  if (const int rc = reserve_reduce_lds("late fuse")) return rc;
+  const size_t sort_lds = sizeof(unsigned long long) * (size_t)kLateMaxSlots;
+  static dn::PerDeviceFlag sort_flag;
+  bool& sort_ready = sort_flag.here();
+  if (!sort_ready) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(late_gather_sort_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
+    if (e != hipSuccess)
+      return dn::fail(DN_ERR_LAUNCH, "late fuse: hipFuncSetAttribute(%zu B LDS): %s", sort_lds, hipGetErrorString(e));
+    sort_ready = true;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  float* sbox = reinterpret_cast<float*>(ws + L.sbox);
+  float* sscore = reinterpret_cast<float*>(ws + L.sscore);
+  int* sidx = reinterpret_cast<int*>(ws + L.sidx);
+  int* nvalid = reinterpret_cast<int*>(ws + L.nvalid);
+  unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + L.mask);
+  const int nb = (top_k + 63) / 64;
+  int p = 1;                                   // the launch depends on the shapes only: LDS for the longest possible list
+  while (p < agents * k_in) p <<= 1;
+  hipLaunchKernelGGL(late_gather_sort_kernel, dim3(n), dim3(kLateThreads), sizeof(unsigned long long) * (size_t)p, s,
+                     boxes, scores, count, trans, num_agent, batch, agents, k_in, only_v2i, ego_first, top_k, ext, sbox,
+                     sscore, sidx, nvalid);
+  hipLaunchKernelGGL(detect_iou_mask_kernel, dim3(4 * nb, nb, n), dim3(64), 0, s, sbox, nvalid, top_k, nb, iou_thr, mask);
+  hipLaunchKernelGGL(detect_reduce_kernel, dim3(n), dim3(kThreads), sizeof(unsigned long long) * (size_t)top_k * nb, s,
+                     sbox, sscore, sidx, nvalid, mask, top_k, nb, out_boxes, out_scores, out_source, out_count);
+  return dn::check_launch("late fuse");
 }

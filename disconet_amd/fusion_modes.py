@@ -10,6 +10,10 @@ Inference: one launch, `ops.fuse_reduce` (csrc/fuse_reduce.hip) -- the warped ma
 engine keeps its shape (the warps are materialised; `max` needs them in its backward) with dn_fuse_reduce_lists /
 _backward in the place of the attention MLP and the softmax combine.  The contract is include/disconet_hip.h ::
 dn_fuse_reduce; `host_fuse_reduce` states it in plain torch on the CPU.
+
+The two floors of the comparison live here too: `--com lowerbound` (NoFusion: the identity in place of the reduction, every
+agent detects from its own view) and `--com late`, the same detector with postprocess.late_fuse behind its detection tail
+(collaboration at the box level, dn_late_fuse).  COM_MODES keeps the four feature-level modes; DET_COM_MODES adds the two.
 """
 import torch
 import torch.nn.functional as F
@@ -21,6 +25,9 @@ from .profiling import region
 from .train import TrainEngine
 
 COM_MODES = ("disco", "sum", "mean", "max")
+# the modes of the det / track tools: `lowerbound` is the detector without collaboration, `late` that detector with
+# postprocess.late_fuse behind its detection tail (collaboration at the box level; trained as `lowerbound`)
+DET_COM_MODES = COM_MODES + ("lowerbound", "late")
 
 
 # ---------------------------------------------------------------------------
@@ -128,13 +135,36 @@ class MaxFusion(_ReduceFusionNet):
     com = "max"
 
 
-_CLASSES = {"disco": DiscoNet, "sum": SumFusion, "mean": MeanFusion, "max": MaxFusion}
+class NoFusion(_ReduceFusionNet):
+    """`--com lowerbound`: no collaboration -- the reduction is the identity, every agent detects from its own view.  Also
+    the detector of `--com late`, whose collaboration happens behind the detection tail (postprocess.late_fuse)."""
+    com = "lowerbound"
+
+    def _train_engine_class(self):
+        return NoFusionTrainEngine
+
+    def fuse(self, feat, trans_matrices, num_agent, batch_size, P, want_weights=False, ego_first=0, ego_count=None,
+             sp_out=False):
+        """the served egos' own layer-`layer` maps: no launch, and trans_matrices / num_agent are never read"""
+        if want_weights:
+            raise ValueError("%s has no agent weights" % type(self).__name__)
+        E = self.agent_num if ego_count is None else ego_count
+        if not (0 <= ego_first and E > 0 and ego_first + E <= self.agent_num):
+            raise ValueError("ego range [%d, %d) outside 0..%d" % (ego_first, ego_first + E, self.agent_num))
+        if ego_first == 0 and E == self.agent_num:
+            return feat                 # (NHWC or SP, as the encoder left it: the decoder takes either)
+        return ops.as_nhwc(feat)[ego_first * batch_size:(ego_first + E) * batch_size]
+
+
+_CLASSES = {"disco": DiscoNet, "sum": SumFusion, "mean": MeanFusion, "max": MaxFusion, "lowerbound": NoFusion,
+            "late": NoFusion}
 
 
 def build_model(com, config, **kw):
-    """the detector of `--com com`: DiscoNet for "disco", else the baseline's class; same constructor arguments"""
+    """the detector of `--com com`: DiscoNet for "disco", the baseline's class for sum / mean / max, NoFusion for
+    lowerbound and late; same constructor arguments"""
     if com not in _CLASSES:
-        raise ValueError("--com must be one of %s (got %r)" % (", ".join(COM_MODES), com))
+        raise ValueError("--com must be one of %s (got %r)" % (", ".join(DET_COM_MODES), com))
     return _CLASSES[com](config, **kw)
 
 
@@ -175,3 +205,18 @@ class ReduceTrainEngine(TrainEngine):
         if NW:
             T.warp_backward(dmaps[NI:], F["poses"], F["src_image"], dmaps[:NI], rigid=F["rigid"])
         return dmaps[:NI]
+
+
+class NoFusionTrainEngine(ReduceTrainEngine):
+    """`--com lowerbound`: the fused maps are the egos' own rows of the pair buffer and their gradient passes through.  The
+    lists are those of a batch without live agents (every ego alone in its list: no warps, no poses gathered)."""
+
+    def _fusion_lists(self, trans, num_agent_cpu, B, dev, poses=True):
+        return super()._fusion_lists(trans, torch.zeros_like(num_agent_cpu), B, dev, poses=poses)
+
+    def _fusion_fwd(self, maps, NI, NW, F):
+        self.fctx = dict(maps=maps, NI=NI, NW=NW)
+        return maps[:NI]
+
+    def _fusion_bwd(self, dfused, G):
+        return dfused

@@ -5,6 +5,8 @@ selection, then rotated NMS on the host -- the reference runs NMS on the CPU too
 so this is its placement, not a fallback (predict_all / host_detections).
 detect() runs the same tail on the GPU (dn_detect: top-k, rotated NMS, padded rows)
 for graph-captured inference; host_detections is the reference it is tested against.
+late_fuse() (dn_late_fuse) merges every agent's detections in each ego's frame behind detect() (`--com late`);
+host_late_fuse is its contract in numpy.
 """
 import ctypes
 import math
@@ -189,6 +191,151 @@ def detections_to_host(det):
     counts = packed[:, 7 * k].view(np.int32)
     return [(packed[i, :6 * k].reshape(k, 6)[:counts[i]].copy(), packed[i, 6 * k:7 * k][:counts[i]].copy())
             for i in range(n)]
+
+
+# ---------------------------------------------------------------------------
+# late fusion (`--com late`): every agent's detections merged in each ego's frame, duplicates suppressed (dn_late_fuse)
+# ---------------------------------------------------------------------------
+MAX_LATE_AGENTS = 16
+MAX_LATE_ROWS = 8192         # agents * K: the rows one ego's list can hold
+
+
+def _flat_extents(extents):
+    """((x_lo, x_hi), (y_lo, y_hi)) or a flat (x_lo, x_hi, y_lo, y_hi) -> four floats; None stays None"""
+    if extents is None:
+        return None
+    flat = [float(v) for v in np.asarray(extents, dtype=np.float64).reshape(-1)]
+    if len(flat) != 4:
+        raise ValueError("extents must be ((x_lo, x_hi), (y_lo, y_hi)), got %r" % (extents,))
+    return flat
+
+
+def _ego_range(agents, ego_first, ego_count):
+    E = agents if ego_count is None else int(ego_count)
+    if not (0 <= ego_first and E > 0 and ego_first + E <= agents):
+        raise ValueError("ego range [%d, %d) outside 0..%d" % (ego_first, ego_first + E, agents))
+    return E
+
+
+def late_fuse(det, trans_matrices, num_agent, batch_size, agents, top_k=None, iou_thr=0.01, only_v2i=False, extents=None,
+              ego_first=0, ego_count=None):
+    """Late fusion on the GPU (include/disconet_hip.h :: dn_late_fuse; host_late_fuse is its reference).  `det` is
+    detect()'s dict of every agent's own detections (`--com lowerbound`), or any dict of device tensors "boxes"
+    [A*B, K, 6], "scores" [A*B, K], "count" [A*B] (agent-major images, the rows need not be sorted); trans_matrices
+    [B, A, A, 4, 4]; num_agent the live counts ([B], or the reference's [B, A] tensor).  Each served ego takes its own
+    rows and every listed neighbour's rows carried into its frame -- with `extents` = ((x_lo, x_hi), (y_lo, y_hi)), pass
+    config.area_extents[:2], only those whose centre lands strictly inside -- orders them by score and runs detect()'s
+    greedy rotated NMS.  Returns device tensors {"boxes" [E*B, top_k, 6], "scores" [E*B, top_k], "source" [E*B, top_k]
+    int32 (agent * K + row of the input; -1 past count), "count" [E*B]}, image (i - ego_first) * B + b, rows >= count zero:
+    the form MeanAP, Sort, ClearMot, Identity and Hota take.  top_k defaults to K.  Runs on torch's current stream,
+    allocates through torch's caching allocator and never waits for the device (graph.GraphedStep)."""
+    boxes, scores, count = det["boxes"], det["scores"], det["count"]
+    for t in (boxes, scores, count, trans_matrices):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.DnError("late_fuse needs device tensors (got %s); host_late_fuse is the numpy reference"
+                               % type(t).__name__)
+    _need_gpu(boxes, scores, count, trans_matrices)
+    A, B = int(agents), int(batch_size)
+    n, k = scores.shape
+    top_k = k if top_k is None else int(top_k)
+    if n != A * B or tuple(boxes.shape) != (n, k, 6) or count.numel() != n:
+        raise ValueError("late_fuse: boxes %s scores %s count %s for agents * batch = %d images" % (
+            tuple(boxes.shape), tuple(scores.shape), tuple(count.shape), A * B))
+    if tuple(trans_matrices.shape) != (B, A, A, 4, 4):
+        raise ValueError("late_fuse: trans_matrices %s, expected %s" % (tuple(trans_matrices.shape), (B, A, A, 4, 4)))
+    ext = _flat_extents(extents)
+    E = agents if ego_count is None else int(ego_count)
+    dev = scores.device
+    boxes = boxes.to(torch.float32).contiguous()
+    scores = scores.to(torch.float32).contiguous()
+    count = count.to(torch.int32).contiguous()
+    trans = trans_matrices.to(torch.float32).contiguous()
+    live = _live_counts(num_agent, dev)
+    lib = _lib.load()
+    nbytes = int(lib.dn_late_fuse_workspace_bytes(B, A, k, top_k, ego_first, E))
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    rows, kk = max(E, 0) * B, max(top_k, 1)
+    out = {"boxes": torch.empty((rows, kk, 6), dtype=torch.float32, device=dev),
+           "scores": torch.empty((rows, kk), dtype=torch.float32, device=dev),
+           "source": torch.empty((rows, kk), dtype=torch.int32, device=dev),
+           "count": torch.empty((rows,), dtype=torch.int32, device=dev)}
+    _lib.check(lib.dn_late_fuse(_ptr(boxes), _ptr(scores), _ptr(count), _ptr(trans), _ptr(live), B, A, k, int(bool(only_v2i)),
+                                int(ego_first), E, top_k, float(iou_thr), int(ext is not None),
+                                (ctypes.c_double * 4)(*(ext or [0.0] * 4)), _ptr(out["boxes"]), _ptr(out["scores"]),
+                                _ptr(out["source"]), _ptr(out["count"]), _ptr(ws), nbytes, _stream()), "dn_late_fuse")
+    return out
+
+
+def _live_counts(num_agent, device):
+    from .ops import live_agent_counts
+    if not isinstance(num_agent, torch.Tensor):
+        num_agent = torch.as_tensor(np.asarray(num_agent))
+    return live_agent_counts(num_agent, device)
+
+
+def host_late_fuse(det, trans_matrices, num_agent, batch_size, agents, top_k=None, iou_thr=0.01, only_v2i=False,
+                   extents=None, ego_first=0, ego_count=None):
+    """dn_late_fuse's contract in numpy, float64, on nms_rotated: the reference late_fuse() must equal bit for bit.  `det`
+    is detect()'s dict or pad_detections' (tensors or numpy); num_agent [B] (or [B, A], column 0).  Returns numpy arrays
+    {"boxes" [E*B, top_k, 6] float32, "scores" [E*B, top_k] float32, "source" [E*B, top_k] int32, "count" [E*B] int32}."""
+    boxes = np.asarray(_host(det["boxes"]), dtype=np.float32)
+    scores = np.asarray(_host(det["scores"]), dtype=np.float32)
+    count = np.asarray(_host(det["count"])).reshape(-1)
+    trans = np.asarray(_host(trans_matrices), dtype=np.float32)
+    live = np.asarray(_host(num_agent))
+    live = live[:, 0] if live.ndim == 2 else live.reshape(-1)
+    A, B = int(agents), int(batch_size)
+    n, k = scores.shape
+    top_k = k if top_k is None else int(top_k)
+    if n != A * B or boxes.shape != (n, k, 6) or count.shape[0] != n:
+        raise ValueError("host_late_fuse: boxes %s scores %s count %s for agents * batch = %d images" % (
+            boxes.shape, scores.shape, count.shape, A * B))
+    if not 1 <= top_k <= MAX_TOP_K or not 1 <= k <= MAX_TOP_K or A > MAX_LATE_AGENTS or A * k > MAX_LATE_ROWS:
+        raise ValueError("host_late_fuse: top_k = %d, K = %d, agents = %d: 1..%d rows, at most %d agents and %d rows in a list"
+                         % (top_k, k, A, MAX_TOP_K, MAX_LATE_AGENTS, MAX_LATE_ROWS))
+    if not (math.isfinite(iou_thr) and iou_thr >= 0):
+        raise ValueError("host_late_fuse: iou_thr = %r, must be finite and >= 0" % (iou_thr,))
+    E = _ego_range(A, ego_first, ego_count)
+    ext = _flat_extents(extents)
+    out = {"boxes": np.zeros((E * B, top_k, 6), dtype=np.float32), "scores": np.zeros((E * B, top_k), dtype=np.float32),
+           "source": np.full((E * B, top_k), -1, dtype=np.int32), "count": np.zeros(E * B, dtype=np.int32)}
+    for b in range(B):
+        nl = max(0, min(int(live[b]), A))
+        for i in range(ego_first, ego_first + E):
+            lst = [i] + ([j for j in range(nl) if j != i and not (only_v2i and i != 0 and j != 0)] if i < nl else [])
+            cb, cs, src = [], [], []
+            for pos, j in enumerate(lst):
+                img = j * B + b
+                c = max(0, min(int(count[img]), k))
+                rows = boxes[img, :c]
+                if pos:                                  # a neighbour's rows, carried into the ego's frame
+                    M = trans[b, i, j].astype(np.float64)
+                    r64 = rows.astype(np.float64)
+                    x, y, sn, cn = r64[:, 0], r64[:, 1], r64[:, 4], r64[:, 5]
+                    rows = rows.copy()
+                    rows[:, 0] = ((M[0, 0] * x + M[0, 1] * y) + M[0, 3]).astype(np.float32)
+                    rows[:, 1] = ((M[1, 0] * x + M[1, 1] * y) + M[1, 3]).astype(np.float32)
+                    rows[:, 4] = (M[1, 0] * cn + M[1, 1] * sn).astype(np.float32)
+                    rows[:, 5] = (M[0, 0] * cn + M[0, 1] * sn).astype(np.float32)
+                s = scores[img, :c]
+                with np.errstate(invalid="ignore"):
+                    ok = np.isfinite(s) & (s >= 0)
+                if pos and ext is not None:
+                    x32, y32 = rows[:, 0].astype(np.float64), rows[:, 1].astype(np.float64)
+                    ok &= (ext[0] < x32) & (x32 < ext[1]) & (ext[2] < y32) & (y32 < ext[3])
+                cb.append(rows[ok])
+                cs.append(s[ok])
+                src.append((j * k + np.nonzero(ok)[0]).astype(np.int32))
+            cb, cs, src = np.concatenate(cb), np.concatenate(cs), np.concatenate(src)
+            order = np.argsort(-cs.astype(np.float64), kind="stable")[:top_k]      # (list position, row) among equals
+            cb, cs, src = cb[order], cs[order], src[order]
+            keep = nms_rotated(cb, cs.astype(np.float64), iou_thr) if len(cs) else np.zeros(0, dtype=np.int64)
+            o = (i - ego_first) * B + b
+            out["boxes"][o, :len(keep)] = cb[keep]
+            out["scores"][o, :len(keep)] = cs[keep]
+            out["source"][o, :len(keep)] = src[keep]
+            out["count"][o] = len(keep)
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -586,6 +586,42 @@ int dn_detect(const float* cls, const float* loc, const float* anchors, int n_im
               int32_t* index, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Late fusion, `--com late` (disconet_amd/csrc/detect.hip): collaboration at the box level.  Every agent detects from
+ * its own view (`--com lowerbound`), sends its detections, and each ego merges them in its own frame and suppresses
+ * duplicates.  (What upstream's detection_util :: late_fusion does is recalled, not pinned against its source; the
+ * contract below is this library's own, and postprocess.host_late_fuse states it in numpy.)  Graph-capturable behind
+ * dn_detect: three kernel launches, no host synchronisation, no allocation, integer arithmetic decides every order; the
+ * launch sequence depends on the shapes only and the results are the same bits on every run.
+ *   boxes [A*B][k_in][6], scores [A*B][k_in], count [A*B]: dn_detect's outputs or any rows (they need not be sorted),
+ *   images agent-major; trans [B][A][A][4][4]: trans[b][i][j] carries agent j's frame into agent i's; num_agent [B]
+ *   (clamped to 0..A); only_v2i, ego_first, ego_count as dn_fuse_reduce.
+ * Per served ego (i, b), output image (i - ego_first) * B + b:
+ *   - the list: [i], then the live j != i ascending (only_v2i drops j != 0 for i != 0); a padded ego (i >= n) has the
+ *     list [i] alone; a dead neighbour is never read;
+ *   - candidates: the rows r < clamp(count[j*B+b], 0, k_in) of every listed agent whose score is finite and >= 0 (-0
+ *     counts and compares equal to +0).  An own row is taken bit for bit.  A neighbour's row is carried with
+ *     M = trans[b][i][j], all in fp64 from the fp32 values, every product and every sum rounded on its own:
+ *       x' = (M00 x + M01 y) + M03    y' = (M10 x + M11 y) + M13    sin' = M10 cos + M11 sin    cos' = M00 cos + M01 sin
+ *     each rounded once to fp32; w, h and the score are copied; the heading is not renormalised (the NMS does that).
+ *     With use_extents a neighbour's row is a candidate only when x_lo < x' < x_hi and y_lo < y' < y_hi for the fp32
+ *     x', y' (xy_extents_host = {x_lo, x_hi, y_lo, y_hi}, a HOST array read before the launch); own rows are never
+ *     filtered;
+ *   - order: score descending, then list position ascending, then row ascending; the first min(top_k, #candidates);
+ *   - greedy NMS in that order, exactly dn_detect's (inter / union > iou_thr, union > 0, fp64 geometry);
+ *   - out: count[n]; rows < count of boxes [E*B][top_k][6], scores [E*B][top_k], source [E*B][top_k] in keep order,
+ *     source = j * k_in + r with the agent's own index j; rows >= count are 0 with source -1, on every call.
+ *   1 <= top_k <= 1024, 1 <= k_in <= 1024, agents <= 16, agents * k_in <= 8192, iou_thr finite and >= 0, the ego range
+ *   inside 0..A, non-empty extents; everything else is DN_ERR_ARG with a message.  workspace:
+ *   dn_late_fuse_workspace_bytes(...) bytes (0 for arguments dn_late_fuse refuses).
+ * ------------------------------------------------------------------------ */
+size_t dn_late_fuse_workspace_bytes(int batch, int agents, int k_in, int top_k, int ego_first, int ego_count);
+int dn_late_fuse(const float* boxes, const float* scores, const int32_t* count, const float* trans,
+                 const int32_t* num_agent, int batch, int agents, int k_in, int only_v2i, int ego_first, int ego_count,
+                 int top_k, double iou_thr, int use_extents, const double* xy_extents_host, float* out_boxes,
+                 float* out_scores, int32_t* out_source, int32_t* out_count, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
+/* ------------------------------------------------------------------------
  * Detection mAP, per-frame part (disconet_amd/csrc/ap_match.hip): ground-truth matching and true / false positives
  * at up to 8 IoU thresholds for every image of a call, and the append of one record per detection to caller-owned
  * arrays.  Graph-capturable behind dn_detect: kernel launches only, no host synchronisation, no allocation; the launch

@@ -3,8 +3,11 @@
 forward the detection tail on the GPU (postprocess.detect: top-k by score, rotated greedy NMS, one batched call).
 Prints per frame the forward time, the per-image detection counts and the tail's device time (events).
 
-    python tools/det/detect_codet.py --com disco|sum|mean|max [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+    python tools/det/detect_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T]
+
+--com lowerbound: no collaboration, every agent detects from its own view.  --com late: that detector (pass a lowerbound
+checkpoint), then postprocess.late_fuse merges the agents' boxes in each ego's frame.
 """
 import os
 import sys
@@ -16,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import COM_MODES, Config, build_model, postprocess  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, build_model, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -29,8 +32,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the detection counts")
-    if args.com not in COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in DET_COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     config = Config("test", binary=True, only_det=True)
@@ -59,10 +62,13 @@ def main(argv=None):
         start.record()
         det = postprocess.detect(result, anchors, pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr,
                                  score_thr=args.score_thr)
+        if args.com == "late":            # every agent's boxes merged in each ego's frame, duplicates suppressed
+            det = postprocess.late_fuse(det, trans.cuda(), na.cuda(), args.batch, num_agent, iou_thr=args.iou_thr,
+                                        only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
         end.record()
         end.synchronize()
-        print("frame %d: forward %.2f ms  detections per image %s  (top-k + rotated NMS on the GPU: %.3f ms)" % (
-            frame, forward_ms, det["count"].tolist(), start.elapsed_time(end)))
+        print("frame %d: forward %.2f ms  detections per image %s  (top-k + rotated NMS%s on the GPU: %.3f ms)" % (
+            frame, forward_ms, det["count"].tolist(), " + late fusion" if args.com == "late" else "", start.elapsed_time(end)))
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothing read back -- and after the last frame
 mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
 
-    python tools/det/eval_codet.py --com disco|sum|mean|max [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
+    python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
@@ -14,6 +14,9 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 --gt scene: frame f is synthetic.make_box_scene_batch(seed=f) -- occupancy that shows the scene's own boxes -- scored
     against those boxes: after `train_codet.py --targets boxes --logpath L`, `--gt scene --resume L/epoch_N.pth` prints an
     mAP that belongs to the detector.
+
+--com lowerbound: no collaboration.  --com late: the lowerbound detector (train `--com lowerbound`, pass its checkpoint)
+    with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame.
 """
 import os
 import sys
@@ -24,7 +27,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import COM_MODES, Config, build_model, postprocess  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, build_model, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -44,8 +47,8 @@ def main(argv=None):
     args = build_eval_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
-    if args.com not in COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in DET_COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     config = Config("test", binary=True, only_det=True)
@@ -74,6 +77,9 @@ def main(argv=None):
             out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
         det = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors, pre_nms_top_k=args.pre_nms_top_k,
                                  iou_thr=args.iou_thr, score_thr=args.score_thr)
+        if args.com == "late":            # every agent's boxes merged in each ego's frame, duplicates suppressed
+            det = postprocess.late_fuse(det, trans.cuda(), na.cuda(), args.batch, num_agent, iou_thr=args.iou_thr,
+                                        only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
         if args.gt == "self":
             gt_boxes, gt_count = det["boxes"], det["count"]
         elif args.gt == "scene":

@@ -7,7 +7,7 @@ resumes from `--resume` / `--resume_teacher` if given, and runs CoDetModule.step
 scenes and targets (there is no V2X-Sim data in this environment) through the MI355X path,
 writing `epoch_N.pth` with the reference's checkpoint keys.
 
-    python tools/det/train_codet.py --com disco|sum|mean|max [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
+    python tools/det/train_codet.py --com disco|sum|mean|max|lowerbound [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
         [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
         [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4]
@@ -41,6 +41,7 @@ from disconet_amd import COM_MODES, CoDetModule, Config, TeacherNet, build_model
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
 
 
+TRAIN_COM_MODES = COM_MODES + ("lowerbound",)
 SCENE_BOXES = 64      # --targets boxes: boxes per scene (eval_codet.py --gt scene builds the same scenes)
 
 
@@ -138,8 +139,11 @@ def main(argv=None):
         found = newest_checkpoint(args.auto_resume_path)
         if found:
             args.resume = found
-    if args.com not in COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com == "late":
+        raise SystemExit("--com late has nothing of its own to train: train --com lowerbound and pass its checkpoint to the "
+                         "det / track tools with --com late")
+    if args.com not in TRAIN_COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max | lowerbound are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -10,7 +10,7 @@ per image.  Behind those, HOTA with its detection, association and localisation 
 AssRe, AssPr, LocA, HOTA(0), LocA(0), HOTALocA(0)): tracking.Hota.update() runs in the same captured step and logs every
 frame on the device (--max_frames slots), and Hota.compute() matches all logged frames of all images at once there.
 
-    python tools/track/eval_sort.py --com disco|sum|mean|max [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+    python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
         [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES]
 
@@ -31,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 
-from disconet_amd import COM_MODES, Config, build_model, graph, postprocess, tracking  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, build_model, graph, postprocess, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_track_sequence, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -56,8 +56,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.max_frames is None:
         args.max_frames = max(args.frames, 1)
-    if args.com not in COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in DET_COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
@@ -112,6 +112,9 @@ def main(argv=None):
                 out = model(bevs, trans, na, args.batch)
             found = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors,
                                        pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr, score_thr=args.score_thr)
+            if args.com == "late":        # inside the captured step: every agent's boxes merged in each ego's frame
+                found = postprocess.late_fuse(found, trans, na, args.batch, num_agent, iou_thr=args.iou_thr,
+                                              only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
             return evaluate(sort.update(found))
 
         step = graph.GraphedStep(forward_detect_track_evaluate)

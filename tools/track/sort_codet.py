@@ -5,7 +5,7 @@ nothing is copied to the host but the reported tracks that are written out), and
 (`frame,id,x1,y1,w,h,score,-1,-1,-1`, rectangles in BEV pixels: scale = 1 / voxel_size[0]) lands under --logpath:
 tracks_agent<a>.txt, or tracks_agent<a>_scene<b>.txt for --batch > 1 (every image is its own sequence).
 
-    python tools/track/sort_codet.py --com disco|sum|mean|max [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 8] \
+    python tools/track/sort_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 8] \
         [--logpath logs/track] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--source net|boxes]
 
 --source net (default): test_codet.py's model and synthetic scenes.  With random weights the detections of two frames
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 
-from disconet_amd import COM_MODES, Config, build_model, graph, postprocess, tracking  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, build_model, graph, postprocess, tracking  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch, make_track_sequence, randomize_bn_stats  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
@@ -42,8 +42,8 @@ def main(argv=None):
     ap.add_argument("--max_tracks", type=int, default=128)
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
-    if args.com not in COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max are built on the MI355X path (SURVEY.md §2.1 #8)")
+    if args.com not in DET_COM_MODES:
+        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
     num_agent = args.num_agent + (1 if args.rsu else 0)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
@@ -83,6 +83,9 @@ def main(argv=None):
                 out = model(bevs, trans, na, args.batch)
             det = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors,
                                      pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr, score_thr=args.score_thr)
+            if args.com == "late":        # inside the captured step: every agent's boxes merged in each ego's frame
+                det = postprocess.late_fuse(det, trans, na, args.batch, num_agent, iou_thr=args.iou_thr,
+                                            only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
             return sort.update(det)
 
         step = graph.GraphedStep(forward_detect_track)
