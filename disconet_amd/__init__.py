@@ -8,6 +8,7 @@ from .config import Config
 from .model import DiscoNet
 from .fusion_modes import COM_MODES, DET_COM_MODES, MaxFusion, MeanFusion, NoFusion, SumFusion, build_model
 from .postprocess import late_fuse
+from .detector import Detector, load_checkpoint
 from . import holistic, targets
 from .seg import HostMeanIoU, MeanIoU, SegDiscoNet, SegModule
 from .holistic import holistic_views
@@ -15,5 +16,5 @@ from .teacher import TeacherNet
 from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
-__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "COM_MODES", "DET_COM_MODES", "build_model", "late_fuse", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
+__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "COM_MODES", "DET_COM_MODES", "build_model", "late_fuse", "Detector", "load_checkpoint", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
            "assign_targets", "holistic", "holistic_views"]

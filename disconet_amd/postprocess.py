@@ -138,10 +138,10 @@ def predict_all(model, anchors, bevs, trans_matrices, num_agent_tensor, batch_si
                 pre_nms_top_k=300, iou_thr=0.01, score_thr=None):
     """Per-image detections [(boxes [K, 6], scores [K])] for the agent-major batch: forward
     (HIP), decode (HIP), top-k by score (torch on the GPU), rotated NMS (host)."""
+    from .detector import heads         # (detector imports this module)
     with torch.no_grad():
         out = model(bevs, trans_matrices, num_agent_tensor, batch_size)
-    result = out[0] if isinstance(out, tuple) else out
-    return host_detections(result, anchors, pre_nms_top_k, iou_thr, score_thr)
+    return host_detections(heads(out), anchors, pre_nms_top_k, iou_thr, score_thr)
 
 
 # ---------------------------------------------------------------------------

@@ -39,6 +39,17 @@ class KernelTimer:
         return out
 
 
+def events_ms(fn, iters):
+    """mean device time of one fn() over `iters` back-to-back calls: one event pair around the loop (the probes' timer)"""
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
 @contextlib.contextmanager
 def timing(timer):
     global _active

@@ -154,7 +154,12 @@ def test_det_and_track_tools_take_the_four_modes(rel, monkeypatch):
         asked.append((com, kw["num_agent"]))
         raise _Reached()
     monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **kw: None)
-    monkeypatch.setattr(mod, "build_model", build_model)
+    if rel == "det/train_codet.py":                      # the training tool builds the model itself, ...
+        monkeypatch.setattr(mod, "build_model", build_model)
+    else:                                                # ... the others through Detector, the one construction site
+        from disconet_amd import detector
+        assert not hasattr(mod, "build_model")
+        monkeypatch.setattr(detector, "build_model", build_model)
     extra = []
     if rel.startswith("track/"):                         # (the tracker and the metrics are built first, on the GPU: stand-ins)
         monkeypatch.setattr(mod, "tracking", mock.MagicMock())

@@ -339,8 +339,9 @@ def test_det_and_track_tools_take_lowerbound_and_late(rel, monkeypatch):
     def build_model(com, config, **kw):                  # what the tool builds its detector with: the mode must arrive here
         asked.append((com, kw["num_agent"]))
         raise _Reached()
+    from disconet_amd import detector
     monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **kw: None)
-    monkeypatch.setattr(mod, "build_model", build_model)
+    monkeypatch.setattr(detector, "build_model", build_model)      # Detector's: the tools' one construction site
     extra = []
     if rel.startswith("track/"):                         # (the tracker and the metrics are built first, on the GPU: stand-ins)
         monkeypatch.setattr(mod, "tracking", mock.MagicMock())
@@ -349,7 +350,19 @@ def test_det_and_track_tools_take_lowerbound_and_late(rel, monkeypatch):
         with pytest.raises(_Reached):
             mod.main(["--com", com, "--num_agent", "3"] + extra)
     assert asked == [("lowerbound", 3), ("late", 3)]
-    assert "late_fuse(" in open(os.path.join(ROOT, "tools", rel)).read()
+    # the tool constructs its Detector with com == "late": Detector.tail then runs late_fuse behind detect(), which
+    # tests/test_detector_cpu.py :: test_tail_reaches_late_fuse_for_late_only asserts on the call path itself
+    made = []
+
+    class _Detector:
+        def __init__(self, com, config, num_agent, batch_size, **kw):
+            made.append((com, num_agent, batch_size, kw["only_v2i"], kw["iou_thr"]))
+            raise _Reached()
+    import codet_common                                  # (tools/det: the tool put it on the path)
+    monkeypatch.setattr(codet_common, "Detector", _Detector)
+    with pytest.raises(_Reached):
+        mod.main(["--com", "late", "--num_agent", "3", "--batch", "2", "--only_v2i", "1", "--iou_thr", "0.05"] + extra)
+    assert made == [("late", 3, 2, True, 0.05)]
 
 
 def test_train_tool_takes_lowerbound_and_refuses_late(monkeypatch):

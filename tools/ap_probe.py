@@ -15,18 +15,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from disconet_amd import Config, DiscoNet, graph, postprocess  # noqa: E402
-from disconet_amd.synthetic import make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+from disconet_amd import Config, Detector, graph, postprocess  # noqa: E402
+from disconet_amd.synthetic import make_gt_boxes, make_scene_batch  # noqa: E402
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 
 def main(argv=None):
@@ -40,21 +31,11 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--host_reps", type=int, default=1)
     args = ap.parse_args(argv)
-    torch.manual_seed(0)
-    cfg = Config(map_hw=args.map_hw)
-    model = DiscoNet(cfg, kd_flag=0, num_agent=args.agents)
-    randomize_bn_stats(model)
-    model.eval().cuda()
-    anchors = postprocess.make_anchors(cfg)
+    detector = Detector("disco", Config(map_hw=args.map_hw), args.agents, args.batch, pre_nms_top_k=args.top_k,
+                        iou_thr=args.nms_iou)
     bevs, trans, na = (t.cuda() for t in make_scene_batch(args.batch, args.agents, args.map_hw))
     n = args.agents * args.batch
-
-    def forward_detect():
-        with torch.no_grad():
-            out = model(bevs, trans, na, args.batch)
-        return postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors, pre_nms_top_k=args.top_k,
-                                  iou_thr=args.nms_iou)
-
+    forward_detect = lambda: detector(bevs, trans, na)                               # noqa: E731
     det = forward_detect()
     counts = det["count"].cpu().tolist()
     out = {"images": n, "top_k": args.top_k, "nms_iou": args.nms_iou, "counts": counts, "iters": args.iters,
@@ -68,16 +49,16 @@ def main(argv=None):
             update()
         metric.reset()
         torch.cuda.synchronize()
-        eager_ms = _events_ms(update, args.iters)
+        eager_ms = events_ms(update, args.iters)
         up_graph = graph.GraphedStep(update, range_guard=False)
         full = graph.GraphedStep(lambda: metric.update(forward_detect(), gt_boxes, gt_count), range_guard=False)
         up_ms, both_ms, full_ms = [], [], []
         for _ in range(3):                  # alternate the graphs: the host shares its GPU with other work
             metric.reset()
-            up_ms.append(_events_ms(up_graph, args.iters))
-            both_ms.append(_events_ms(both, args.iters))
+            up_ms.append(events_ms(up_graph, args.iters))
+            both_ms.append(events_ms(both, args.iters))
             metric.reset()
-            full_ms.append(_events_ms(full, args.iters))
+            full_ms.append(events_ms(full, args.iters))
         metric.reset()
         match = update()
         res = metric.compute()

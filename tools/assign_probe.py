@@ -17,16 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from disconet_amd import CoDetModule, Config, DiscoNet, postprocess, targets  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 
 def main(argv=None):
@@ -55,8 +46,8 @@ def main(argv=None):
     out = {"images": n, "anchors_per_image": int(anchors.numel() // 6), "gt_rows": args.gt_rows,
            "gt_boxes": int(gt_count.sum()), "positives": int(t["reg_loss_mask"].sum()),
            "dont_care": int((t["labels"].sum(-1) == 0).sum()), "iters": args.iters,
-           "assign_eager_ms": round(_events_ms(run, args.iters), 4),
-           "assign_no_force_eager_ms": round(_events_ms(lambda: run(False), args.iters), 4)}
+           "assign_eager_ms": round(events_ms(run, args.iters), 4),
+           "assign_no_force_eager_ms": round(events_ms(lambda: run(False), args.iters), 4)}
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -67,7 +58,7 @@ def main(argv=None):
         run()
     g.replay()
     torch.cuda.synchronize()
-    out["assign_graph_ms"] = round(min(_events_ms(g.replay, args.iters) for _ in range(3)), 4)
+    out["assign_graph_ms"] = round(min(events_ms(g.replay, args.iters) for _ in range(3)), 4)
     if not args.no_step:
         torch.manual_seed(0)
         model = DiscoNet(cfg, kd_flag=0, num_agent=args.agents).cuda()
@@ -77,7 +68,7 @@ def main(argv=None):
         for _ in range(5):
             module.step(data, args.batch)
         torch.cuda.synchronize()
-        out["train_step_ms"] = round(min(_events_ms(lambda: module.step(data, args.batch), args.step_iters) for _ in range(3)), 4)
+        out["train_step_ms"] = round(min(events_ms(lambda: module.step(data, args.batch), args.step_iters) for _ in range(3)), 4)
         out["assign_over_step"] = round(out["assign_graph_ms"] / out["train_step_ms"], 4)
     if args.host_images > 0:
         k = min(args.host_images, n)

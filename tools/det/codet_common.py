@@ -1,0 +1,36 @@
+"""What the det, track and seg command lines share: the tail's and SORT's flags, the --com refusal, the --rsu rule and
+the Detector of the parsed flags (the reference's flag names; test_codet.build_parser declares them)."""
+from disconet_amd import Detector
+
+
+def add_tail_flags(ap, pre_nms_top_k):
+    ap.add_argument("--pre_nms_top_k", type=int, default=pre_nms_top_k)
+    ap.add_argument("--iou_thr", type=float, default=0.01, help="the NMS threshold of detect()")
+    ap.add_argument("--score_thr", type=float, default=None)
+
+
+def add_sort_flags(ap):
+    ap.add_argument("--max_age", type=int, default=1)
+    ap.add_argument("--min_hits", type=int, default=3)
+    ap.add_argument("--iou_threshold", type=float, default=0.3, help="SORT's association threshold")
+    ap.add_argument("--max_tracks", type=int, default=128)
+
+
+def require_com(args, modes):
+    if args.com not in modes:
+        raise SystemExit("only --com %s are built on the MI355X path (SURVEY.md §2.1 #8)" % " | ".join(modes))
+
+
+def agents_of(args):
+    """--rsu 1: the road-side unit is one more agent"""
+    return args.num_agent + (1 if args.rsu else 0)
+
+
+def detector_from_args(args, config):
+    """the Detector of the command line (the tail's flags where the tool declares them), and the `loaded` line"""
+    tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr") if hasattr(args, k)}
+    det = Detector(args.com, config, agents_of(args), args.batch, layer=args.layer, kd_flag=args.kd_flag,
+                   compress_level=args.compress_level, only_v2i=bool(args.only_v2i), resume=args.resume, **tail)
+    if args.resume:
+        print("loaded", args.resume, "epoch", det.epoch)
+    return det

@@ -7,7 +7,8 @@ Prints per frame the forward time, the per-image detection counts and the tail's
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T]
 
 --com lowerbound: no collaboration, every agent detects from its own view.  --com late: that detector (pass a lowerbound
-checkpoint), then postprocess.late_fuse merges the agents' boxes in each ego's frame.
+checkpoint), then postprocess.late_fuse merges the agents' boxes in each ego's frame (disconet_amd.Detector owns both).
+Without --resume the weights are random: seeded before the model is built, so that a run can be reproduced.
 """
 import os
 import sys
@@ -19,52 +20,35 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, build_model, postprocess  # noqa: E402
-from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config  # noqa: E402
+from disconet_amd.synthetic import make_scene_batch  # noqa: E402
+from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 
 def main(argv=None):
     ap = build_parser()
-    ap.add_argument("--pre_nms_top_k", type=int, default=300)
-    ap.add_argument("--iou_thr", type=float, default=0.01)
-    ap.add_argument("--score_thr", type=float, default=None)
+    add_tail_flags(ap, 300)
     args = ap.parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the detection counts")
-    if args.com not in DET_COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    require_com(args, DET_COM_MODES)
+    num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)
-    model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                        compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
-    if args.resume:
-        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(checkpoint["model_state_dict"])
-        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
-    else:
-        torch.manual_seed(0)
-        randomize_bn_stats(model)
-    model.eval().cuda()
-    anchors = postprocess.make_anchors(config)
+    detector = detector_from_args(args, config)
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     for frame in range(args.frames):
-        bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
+        scene = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        with torch.no_grad():
-            out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
+        bevs, trans, na = (t.cuda() for t in scene)
+        result = detector.forward(bevs, trans, na)
         torch.cuda.synchronize()
         forward_ms = 1e3 * (time.perf_counter() - t0)
-        result = out[0] if isinstance(out, tuple) else out
         start.record()
-        det = postprocess.detect(result, anchors, pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr,
-                                 score_thr=args.score_thr)
-        if args.com == "late":            # every agent's boxes merged in each ego's frame, duplicates suppressed
-            det = postprocess.late_fuse(det, trans.cuda(), na.cuda(), args.batch, num_agent, iou_thr=args.iou_thr,
-                                        only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
+        det = detector.tail(result, trans, na)
         end.record()
         end.synchronize()
         print("frame %d: forward %.2f ms  detections per image %s  (top-k + rotated NMS%s on the GPU: %.3f ms)" % (

@@ -16,19 +16,19 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
     mAP that belongs to the detector.
 
 --com lowerbound: no collaboration.  --com late: the lowerbound detector (train `--com lowerbound`, pass its checkpoint)
-    with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame.
+    with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame
+    (disconet_amd.Detector owns the model, the checkpoint and that tail).
 """
 import os
 import sys
-
-import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, build_model, postprocess  # noqa: E402
-from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch, randomize_bn_stats  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, postprocess  # noqa: E402
+from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch  # noqa: E402
+from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -36,9 +36,7 @@ GT_MAX_BOXES = 64
 
 def build_eval_parser():
     ap = build_parser()
-    ap.add_argument("--pre_nms_top_k", type=int, default=300)
-    ap.add_argument("--iou_thr", type=float, default=0.01)
-    ap.add_argument("--score_thr", type=float, default=None)
+    add_tail_flags(ap, 300)
     ap.add_argument("--gt", choices=("synthetic", "self", "scene"), default="synthetic")
     return ap
 
@@ -47,22 +45,11 @@ def main(argv=None):
     args = build_eval_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
-    if args.com not in DET_COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    require_com(args, DET_COM_MODES)
+    num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)
-    torch.manual_seed(0)              # without --resume the weights are random: seeded, so that a run can be reproduced
-    model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                        compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
-    if args.resume:
-        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(checkpoint["model_state_dict"])
-        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
-    else:
-        randomize_bn_stats(model)
-    model.eval().cuda()
-    anchors = postprocess.make_anchors(config)
+    detector = detector_from_args(args, config)      # without --resume the weights are random: seeded, so that a run can be reproduced
     n_images = num_agent * args.batch
     metric = postprocess.MeanAP(args.batch, capacity=max(1, args.frames * n_images * args.pre_nms_top_k))
 
@@ -73,13 +60,7 @@ def main(argv=None):
             bevs, trans, na = scene["bev_seq"], scene["trans_matrices"], scene["num_agent"]
         else:
             bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
-        with torch.no_grad():
-            out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
-        det = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors, pre_nms_top_k=args.pre_nms_top_k,
-                                 iou_thr=args.iou_thr, score_thr=args.score_thr)
-        if args.com == "late":            # every agent's boxes merged in each ego's frame, duplicates suppressed
-            det = postprocess.late_fuse(det, trans.cuda(), na.cuda(), args.batch, num_agent, iou_thr=args.iou_thr,
-                                        only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
+        det = detector(bevs.cuda(), trans.cuda(), na.cuda())
         if args.gt == "self":
             gt_boxes, gt_count = det["boxes"], det["count"]
         elif args.gt == "scene":

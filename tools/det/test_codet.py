@@ -4,7 +4,8 @@
 V2X-Sim loading, box decode, NMS, mAP, tracking dumps -- is out of scope
 (SURVEY.md §8(f)); this shim builds the model the way the reference's tool does,
 loads `--resume` if given, and runs the eval-mode forward on synthetic scenes
-(there is no V2X-Sim data in this environment) through the MI355X path.
+(there is no V2X-Sim data in this environment) through the MI355X path.  Without --resume the weights are random:
+seeded before the model is built (disconet_amd.Detector), so that a run can be reproduced.
 
     python tools/det/test_codet.py --com disco [--resume ckpt.pth] [--nworker 0] \
         [--num_agent 5] [--batch 1] [--kd_flag 0] [--rsu 0]
@@ -16,10 +17,13 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, HERE)
 
-from disconet_amd import Config, DiscoNet  # noqa: E402
-from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
+from disconet_amd import Config  # noqa: E402
+from disconet_amd.synthetic import make_scene_batch  # noqa: E402
+from codet_common import agents_of, detector_from_args  # noqa: E402
 
 
 def build_parser():
@@ -52,28 +56,17 @@ def main(argv=None):
               "the detector")
     if args.com != "disco":
         raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)
-    model = DiscoNet(config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                     compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
-    if args.resume:
-        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(checkpoint["model_state_dict"])
-        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
-    else:
-        torch.manual_seed(0)
-        randomize_bn_stats(model)
-    model.eval().cuda()
+    det = detector_from_args(args, config)
 
     for frame in range(args.frames):
         bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        with torch.no_grad():
-            out = model(bevs.cuda(), trans.cuda(), na.cuda(), args.batch)
+        result = det.forward(bevs.cuda(), trans.cuda(), na.cuda())
         torch.cuda.synchronize()
-        result = out[0] if isinstance(out, tuple) else out
         cls = torch.softmax(result["cls"], dim=-1)
         print("frame %d: %.2f ms  cls %s loc %s  max fg score %.4f" % (
             frame, 1e3 * (time.perf_counter() - t0), tuple(result["cls"].shape),

@@ -35,10 +35,13 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, HERE)
 
-from disconet_amd import COM_MODES, CoDetModule, Config, TeacherNet, build_model  # noqa: E402
+from disconet_amd import COM_MODES, CoDetModule, Config, TeacherNet, build_model, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
+from codet_common import agents_of, require_com  # noqa: E402
 
 
 TRAIN_COM_MODES = COM_MODES + ("lowerbound",)
@@ -142,9 +145,8 @@ def main(argv=None):
     if args.com == "late":
         raise SystemExit("--com late has nothing of its own to train: train --com lowerbound and pass its checkpoint to the "
                          "det / track tools with --com late")
-    if args.com not in TRAIN_COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max | lowerbound are built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    require_com(args, TRAIN_COM_MODES)
+    num_agent = agents_of(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -172,8 +174,7 @@ def main(argv=None):
     start_epoch = 1
     optimizer_state = None
     if args.resume:
-        ck = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(ck["model_state_dict"])
+        ck = load_checkpoint(model, args.resume)
         optimizer_state = ck.get("optimizer_state_dict")
         start_epoch = int(ck.get("epoch", 0)) + 1
         print("resumed", args.resume, "-> epoch", start_epoch)

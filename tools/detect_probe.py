@@ -13,18 +13,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from disconet_amd import Config, DiscoNet, graph, postprocess  # noqa: E402
-from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+from disconet_amd import Config, Detector, graph, postprocess  # noqa: E402
+from disconet_amd.synthetic import make_scene_batch  # noqa: E402
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 
 def main(argv=None):
@@ -36,40 +27,29 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--host_reps", type=int, default=1)
     args = ap.parse_args(argv)
-    torch.manual_seed(0)
-    cfg = Config(map_hw=args.map_hw)
-    model = DiscoNet(cfg, kd_flag=0, num_agent=args.agents)
-    randomize_bn_stats(model)
-    model.eval().cuda()
-    anchors = postprocess.make_anchors(cfg)
+    det = Detector("disco", Config(map_hw=args.map_hw), args.agents, args.batch, pre_nms_top_k=args.top_k)
     bevs, trans, na = (t.cuda() for t in make_scene_batch(args.batch, args.agents, args.map_hw))
-
-    def forward():
-        with torch.no_grad():
-            out = model(bevs, trans, na, args.batch)
-        return out[0] if isinstance(out, tuple) else out
-
+    forward = lambda: det.forward(bevs, trans, na)                                  # noqa: E731
     result = forward()
-    tail = lambda: postprocess.detect(result, anchors, pre_nms_top_k=args.top_k)    # noqa: E731
+    tail = lambda: det.tail(result, trans, na)                                      # noqa: E731
     for _ in range(5):
         tail()
     torch.cuda.synchronize()
-    eager_ms = _events_ms(tail, args.iters)
+    eager_ms = events_ms(tail, args.iters)
     fwd = graph.GraphedStep(forward, range_guard=False)
-    both = graph.GraphedStep(lambda: postprocess.detect(forward(), anchors, pre_nms_top_k=args.top_k),
-                             range_guard=False)
+    both = graph.GraphedStep(lambda: det(bevs, trans, na), range_guard=False)
     det_graph = graph.GraphedStep(tail, range_guard=False)
     fwd_ms, both_ms, det_graph_ms = [], [], []
     for _ in range(3):                  # alternate the three graphs: the host shares its GPU with other work
-        fwd_ms.append(_events_ms(fwd, args.iters))
-        both_ms.append(_events_ms(both, args.iters))
-        det_graph_ms.append(_events_ms(det_graph, args.iters))
+        fwd_ms.append(events_ms(fwd, args.iters))
+        both_ms.append(events_ms(both, args.iters))
+        det_graph_ms.append(events_ms(det_graph, args.iters))
     counts = tail()["count"].cpu().tolist()
     host_s = []
     for _ in range(args.host_reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        postprocess.host_detections(result, anchors, pre_nms_top_k=args.top_k)
+        postprocess.host_detections(result, det.anchors, pre_nms_top_k=args.top_k)
         host_s.append(time.perf_counter() - t0)
     out = {
         "images": args.agents * args.batch, "top_k": args.top_k, "counts": counts,

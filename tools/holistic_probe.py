@@ -18,16 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from disconet_amd import Config, holistic, ops  # noqa: E402
 from disconet_amd.synthetic import make_point_cloud, make_trans_matrices  # noqa: E402
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 
 def main(argv=None):
@@ -76,8 +67,8 @@ def main(argv=None):
     same = bool(torch.equal(out["dense"], ref)) and bool(torch.equal(out["bits"].nhwc(), out["dense"][:, 0]))
     res = {"views": src["n_views"], "sources": len(src["src_image"]), "points": int(offsets[-1]), "map_hw": args.map_hw,
            "occupied_cells": int(out["dense"].sum()), "loop_writes_the_same_bytes": same, "iters": args.iters,
-           "one_launch_eager_ms": round(min(_events_ms(run, args.iters) for _ in range(3)), 4),
-           "one_launch_dense_only_eager_ms": round(min(_events_ms(lambda: run(("dense",)), args.iters) for _ in range(3)), 4)}
+           "one_launch_eager_ms": round(min(events_ms(run, args.iters) for _ in range(3)), 4),
+           "one_launch_dense_only_eager_ms": round(min(events_ms(lambda: run(("dense",)), args.iters) for _ in range(3)), 4)}
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -88,8 +79,8 @@ def main(argv=None):
         run()
     g.replay()
     torch.cuda.synchronize()
-    res["one_launch_graph_ms"] = round(min(_events_ms(g.replay, args.iters) for _ in range(3)), 4)
-    res["torch_loop_ms"] = round(min(_events_ms(loop, args.loop_iters) for _ in range(3)), 4)
+    res["one_launch_graph_ms"] = round(min(events_ms(g.replay, args.iters) for _ in range(3)), 4)
+    res["torch_loop_ms"] = round(min(events_ms(loop, args.loop_iters) for _ in range(3)), 4)
     res["loop_over_one_launch"] = round(res["torch_loop_ms"] / res["one_launch_graph_ms"], 2)
     res["loop_over_one_launch_eager"] = round(res["torch_loop_ms"] / res["one_launch_eager_ms"], 2)
     print(json.dumps(res), flush=True)

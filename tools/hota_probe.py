@@ -22,19 +22,10 @@ sys.path.insert(0, ROOT)
 
 from disconet_amd import _lib, graph, tracking  # noqa: E402
 from disconet_amd.synthetic import make_track_sequence  # noqa: E402
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 TRACK_KEYS = ("rect", "id", "count")
 FIN_KEYS = ("counts", "alpha_counts", "alpha_sums", "match")
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
 
 
 def main(argv=None):
@@ -85,9 +76,9 @@ def main(argv=None):
         same = same and np.array_equal(fin[key].cpu().numpy().view(np.uint8), want[key].view(np.uint8))
     figures = hota.compute()["overall"]
     status = hota.status_words().tolist()
-    finish_eager_ms = min(_events_ms(hota.finish, args.finish_iters) for _ in range(3))
+    finish_eager_ms = min(events_ms(hota.finish, args.finish_iters) for _ in range(3))
     finish_step = graph.GraphedStep(hota.finish, range_guard=False)
-    finish_graph_ms = min(_events_ms(finish_step, args.finish_iters) for _ in range(3))
+    finish_graph_ms = min(events_ms(finish_step, args.finish_iters) for _ in range(3))
 
     # the step, on an evaluation of its own whose log is emptied before every round (a full log would time the early return)
     timed = tracking.Hota(4, **dict(sizes, max_frames=args.iters + 8))
@@ -101,7 +92,7 @@ def main(argv=None):
     rounds = []
     for _ in range(3):
         timed.reset()
-        rounds.append(_events_ms(eager, args.iters))
+        rounds.append(events_ms(eager, args.iters))
     eager_ms = min(rounds)
     static_t = {key: tracks_dev[-1][key].clone() for key in TRACK_KEYS}
     static_g = {key: gt_dev[-1][key].clone() for key in gt_dev[-1]}
@@ -109,7 +100,7 @@ def main(argv=None):
     rounds = []
     for _ in range(3):
         timed.reset()
-        rounds.append(_events_ms(step, args.iters))
+        rounds.append(events_ms(step, args.iters))
     graph_ms = min(rounds)
     torch.cuda.synchronize()
     logged_all = bool((timed.finish()["counts"][:, 1] == args.iters).all().item())       # no timed call met a full log

@@ -22,18 +22,9 @@ sys.path.insert(0, ROOT)
 
 from disconet_amd import _lib, graph, tracking  # noqa: E402
 from disconet_amd.synthetic import make_track_sequence  # noqa: E402
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 TRACK_KEYS = ("rect", "id", "count")
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
 
 
 def main(argv=None):
@@ -83,9 +74,9 @@ def main(argv=None):
         same = same and np.array_equal(fin[key].cpu().numpy().view(np.uint8), want[key].view(np.uint8))
     figures = idf.compute()["overall"]
     status = idf.status_words().tolist()
-    finish_eager_ms = min(_events_ms(idf.finish, args.iters) for _ in range(3))
+    finish_eager_ms = min(events_ms(idf.finish, args.iters) for _ in range(3))
     finish_step = graph.GraphedStep(idf.finish, range_guard=False)
-    finish_graph_ms = min(_events_ms(finish_step, args.iters) for _ in range(3))
+    finish_graph_ms = min(events_ms(finish_step, args.iters) for _ in range(3))
 
     # the step; the counts keep growing, which the step's work does not depend on
     frame = [0]
@@ -94,11 +85,11 @@ def main(argv=None):
         frame[0] = (frame[0] + 1) % args.frames
         return idf.update(tracks_dev[frame[0]], gt_dev[frame[0]])
 
-    eager_ms = min(_events_ms(eager, args.iters) for _ in range(3))
+    eager_ms = min(events_ms(eager, args.iters) for _ in range(3))
     static_t = {key: tracks_dev[-1][key].clone() for key in TRACK_KEYS}
     static_g = {key: gt_dev[-1][key].clone() for key in gt_dev[-1]}
     step = graph.GraphedStep(lambda: idf.update(static_t, static_g), range_guard=False)
-    graph_ms = min(_events_ms(step, args.iters) for _ in range(3))
+    graph_ms = min(events_ms(step, args.iters) for _ in range(3))
     out = {"images": args.images, "frames": args.frames, "iters": args.iters, "max_gt_ids": args.max_gt_ids,
            "max_track_ids": args.max_track_ids, "state_mb": round(state_host.numel() / 1e6, 2),
            "tracks_per_image": round(float(np.mean([t["count"].float().mean().item() for t in tracks_dev])), 1),

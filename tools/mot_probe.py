@@ -19,18 +19,9 @@ sys.path.insert(0, ROOT)
 
 from disconet_amd import _lib, graph, tracking  # noqa: E402
 from disconet_amd.synthetic import make_track_sequence  # noqa: E402
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 TRACK_KEYS = ("rect", "id", "count")
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
 
 
 def main(argv=None):
@@ -71,11 +62,11 @@ def main(argv=None):
         frame[0] = (frame[0] + 1) % args.frames
         return mot.update(tracks_dev[frame[0]], gt_dev[frame[0]])
 
-    eager_ms = min(_events_ms(eager, args.iters) for _ in range(3))
+    eager_ms = min(events_ms(eager, args.iters) for _ in range(3))
     static_t = {key: tracks_dev[-1][key].clone() for key in TRACK_KEYS}
     static_g = {key: gt_dev[-1][key].clone() for key in gt_dev[-1]}
     step = graph.GraphedStep(lambda: mot.update(static_t, static_g), range_guard=False)
-    graph_ms = min(_events_ms(step, args.iters) for _ in range(3))
+    graph_ms = min(events_ms(step, args.iters) for _ in range(3))
     out = {"images": args.images, "frames": args.frames, "iters": args.iters,
            "tracks_per_image": round(float(np.mean([t["count"].float().mean().item() for t in tracks_dev])), 1),
            "gt_per_image": round(float(np.mean([gt["count"].mean() for _, _, gt in seq])), 1),

@@ -20,10 +20,13 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 
 import test_seg  # noqa: E402  (tools/seg/test_seg.py: the flags)
-from disconet_amd import MeanIoU, SegDiscoNet, SegModule  # noqa: E402
+from codet_common import agents_of  # noqa: E402
+from disconet_amd import MeanIoU, SegDiscoNet, SegModule, load_checkpoint  # noqa: E402
 from disconet_amd.seg import miou_line  # noqa: E402
 from disconet_amd.synthetic import make_seg_scene_batch, randomize_bn_stats  # noqa: E402
 
@@ -45,13 +48,11 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.com != "disco":
         raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    num_agent = agents_of(args)
     torch.manual_seed(0)
     model = SegDiscoNet(num_agent=num_agent, kd_flag=bool(args.kd_flag), only_v2i=bool(args.only_v2i))
     if args.resume:
-        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(checkpoint["model_state_dict"])
-        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
+        print("loaded", args.resume, "epoch", load_checkpoint(model, args.resume).get("epoch"))
     else:
         randomize_bn_stats(model)
     model.eval().cuda()

@@ -4,7 +4,8 @@
 flag spelling follows the det tools at README.md:68-75).  The reference's tool body -- V2X-Sim
 loading, mIoU bookkeeping, visualisation -- is out of scope; this shim builds
 the model the way the tool does, loads `--resume` if given, and runs the eval forward + the
-per-pixel cross entropy on synthetic scenes through the MI355X path.
+per-pixel cross entropy on synthetic scenes through the MI355X path.  Without --resume the weights are random:
+seeded before the model is built, so that a run can be reproduced.
 
     python tools/seg/test_seg.py --com disco [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--rsu 0]
 """
@@ -15,10 +16,13 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 
-from disconet_amd import SegDiscoNet, SegModule  # noqa: E402
+from disconet_amd import SegDiscoNet, SegModule, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch, randomize_bn_stats  # noqa: E402
+from codet_common import agents_of  # noqa: E402
 
 
 def build_parser():
@@ -44,14 +48,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.com != "disco":
         raise SystemExit("only --com disco is built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    num_agent = agents_of(args)
+    torch.manual_seed(0)
     model = SegDiscoNet(num_agent=num_agent, kd_flag=bool(args.kd_flag), only_v2i=bool(args.only_v2i))
     if args.resume:
-        checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(checkpoint["model_state_dict"])
-        print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
+        print("loaded", args.resume, "epoch", load_checkpoint(model, args.resume).get("epoch"))
     else:
-        torch.manual_seed(0)
         randomize_bn_stats(model)
     model.eval().cuda()
     mod = SegModule(model)

@@ -20,10 +20,13 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 
-from disconet_amd import SegDiscoNet, SegModule  # noqa: E402
+from disconet_amd import SegDiscoNet, SegModule, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch, make_seg_scene_batch  # noqa: E402
+from codet_common import agents_of  # noqa: E402
 
 
 def build_parser():
@@ -70,13 +73,12 @@ def main(argv=None):
         raise SystemExit("the seg KD teacher is not built: --kd_flag 0 only")
     if args.steps_per_epoch < 1:
         raise SystemExit("--steps_per_epoch must be at least 1")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    num_agent = agents_of(args)
     torch.manual_seed(0)
     model = SegDiscoNet(num_agent=num_agent, only_v2i=bool(args.only_v2i))
     start_epoch, optimizer_state = 1, None
     if args.resume:
-        ck = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.load_state_dict(ck["model_state_dict"])
+        ck = load_checkpoint(model, args.resume)
         optimizer_state = ck.get("optimizer_state_dict")
         start_epoch = int(ck.get("epoch", 0)) + 1
         print("resumed", args.resume, "-> epoch", start_epoch)

@@ -17,9 +17,11 @@ frame on the device (--max_frames slots), and Hota.compute() matches all logged 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
 noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
 --source net runs test_codet.py's model on synthetic.make_box_scene_batch(seed = --seed), the same standing scene every
-frame, with the scene's boxes as ground truth and their rows as identities.  With untrained weights the detections have
-little to do with the boxes: the run shows the plumbing only; after `train_codet.py --targets boxes --logpath L`,
-`--resume L/epoch_N.pth` gives figures that belong to the detector.
+frame, with the scene's boxes as ground truth and their rows as identities (disconet_amd.Detector: the model, the
+checkpoint and the tail of the --com mode).  Without --resume the weights are random -- seeded before the model is built,
+so that a run can be reproduced -- and the detections have little to do with the boxes: the run shows the plumbing
+only; after `train_codet.py --targets boxes --logpath L`, `--resume L/epoch_N.pth` gives figures that belong to the
+detector.
 """
 import os
 import sys
@@ -30,10 +32,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
+sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, build_model, graph, postprocess, tracking  # noqa: E402
-from disconet_amd.synthetic import make_box_scene_batch, make_track_sequence, randomize_bn_stats  # noqa: E402
+from disconet_amd import DET_COM_MODES, Config, tracking  # noqa: E402
+from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
+from codet_common import add_sort_flags, add_tail_flags, agents_of, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
+from track_step import build_step  # noqa: E402
 
 
 def main(argv=None):
@@ -41,13 +46,8 @@ def main(argv=None):
     ap.add_argument("--source", choices=("net", "boxes"), default="boxes",
                     help="net: the model on a standing box scene (with untrained weights it shows the plumbing only)")
     ap.add_argument("--seed", type=int, default=0, help="make_track_sequence's / make_box_scene_batch's seed")
-    ap.add_argument("--pre_nms_top_k", type=int, default=128)
-    ap.add_argument("--iou_thr", type=float, default=0.01, help="the NMS threshold of detect()")
-    ap.add_argument("--score_thr", type=float, default=None)
-    ap.add_argument("--max_age", type=int, default=1)
-    ap.add_argument("--min_hits", type=int, default=3)
-    ap.add_argument("--iou_threshold", type=float, default=0.3, help="SORT's association threshold")
-    ap.add_argument("--max_tracks", type=int, default=128)
+    add_tail_flags(ap, 128)
+    add_sort_flags(ap)
     ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
     ap.add_argument("--max_gt_ids", type=int, default=256)
     ap.add_argument("--max_track_ids", type=int, default=1024, help="the identity figures count track ids 1 .. this")
@@ -56,9 +56,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.max_frames is None:
         args.max_frames = max(args.frames, 1)
-    if args.com not in DET_COM_MODES:
-        raise SystemExit("only --com disco | sum | mean | max | lowerbound | late are built on the MI355X path (SURVEY.md §2.1 #8)")
-    num_agent = args.num_agent + (1 if args.rsu else 0)
+    require_com(args, DET_COM_MODES)
+    num_agent = agents_of(args)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
     scale = 1.0 / config.voxel_size[0]
@@ -70,56 +69,20 @@ def main(argv=None):
     hota = tracking.Hota(args.batch, scale=scale, max_gt_ids=args.max_gt_ids, max_track_ids=args.max_track_ids,
                          max_frames=args.max_frames)
 
-    def evaluate(tracks):
+    def evaluate(tracks, gt):
         return mot.update(tracks, gt), idf.update(tracks, gt), hota.update(tracks, gt)
 
-    if args.source == "boxes":
-        seq = make_track_sequence(args.frames, n, seed=args.seed, truth=True)
-        det = {key: torch.from_numpy(seq[0][0][key]).cuda() for key in ("boxes", "scores", "count")}
-        gt = {key: torch.from_numpy(seq[0][2][key]).cuda() for key in ("boxes", "ids", "count")}
-
-        def load(frame):
-            for key in det:
-                det[key].copy_(torch.from_numpy(seq[frame][0][key]))
-            for key in gt:
-                gt[key].copy_(torch.from_numpy(seq[frame][2][key]))
-
-        step = graph.GraphedStep(lambda: evaluate(sort.update(det)))
-    else:
-        model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
-                            compress_level=args.compress_level, only_v2i=bool(args.only_v2i))
-        if args.resume:
-            checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
-            model.load_state_dict(checkpoint["model_state_dict"])
-            print("loaded", args.resume, "epoch", checkpoint.get("epoch"))
-        else:
-            torch.manual_seed(0)
-            randomize_bn_stats(model)
-            print("note: untrained weights -- the figures below show the plumbing, not a detector")
-        model.eval().cuda()
-        anchors = postprocess.make_anchors(config)
+    def net_scene():                   # a standing scene: every frame sees the same boxes, their rows are the identities
         scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=args.seed, device="cuda")
-        bevs, trans, na = (scene[key].cuda() for key in ("bev_seq", "trans_matrices", "num_agent"))
         rows = scene["gt_boxes"].shape[1]
         gt = {"boxes": torch.as_tensor(scene["gt_boxes"]).cuda(), "count": torch.as_tensor(scene["gt_count"]).cuda(),
               "ids": torch.arange(rows, dtype=torch.int32).repeat(n, 1).cuda()}
+        return tuple(scene[key].cuda() for key in ("bev_seq", "trans_matrices", "num_agent")), None, gt
 
-        def load(frame):
-            pass                       # a standing scene: every frame sees the same boxes
-
-        def forward_detect_track_evaluate():
-            with torch.no_grad():
-                out = model(bevs, trans, na, args.batch)
-            found = postprocess.detect(out[0] if isinstance(out, tuple) else out, anchors,
-                                       pre_nms_top_k=args.pre_nms_top_k, iou_thr=args.iou_thr, score_thr=args.score_thr)
-            if args.com == "late":        # inside the captured step: every agent's boxes merged in each ego's frame
-                found = postprocess.late_fuse(found, trans, na, args.batch, num_agent, iou_thr=args.iou_thr,
-                                              only_v2i=bool(args.only_v2i), extents=config.area_extents[:2])
-            return evaluate(sort.update(found))
-
-        step = graph.GraphedStep(forward_detect_track_evaluate)
-    sort.reset()                       # the warm-up runs of the capture advanced the tracker ...
-    mot.reset()                        # ... and were counted
+    if args.source == "net" and not args.resume:
+        print("note: untrained weights -- the figures below show the plumbing, not a detector")
+    step, load, _ = build_step(args, config, sort, net_scene, behind=evaluate, truth=True)
+    mot.reset()                        # the warm-up runs of the capture advanced the tracker (build_step resets it) and were counted
     idf.reset()
     hota.reset()                       # ... and logged
 

@@ -18,16 +18,7 @@ sys.path.insert(0, ROOT)
 
 from disconet_amd import _lib, graph, postprocess, tracking  # noqa: E402
 from disconet_amd.synthetic import make_track_sequence  # noqa: E402
-
-
-def _events_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+from disconet_amd.profiling import events_ms  # noqa: E402
 
 
 def main(argv=None):
@@ -67,9 +58,9 @@ def main(argv=None):
         frame[0] = (frame[0] + 1) % args.frames
         return sort.update(dev[frame[0]])
 
-    eager_ms = min(_events_ms(eager, args.iters) for _ in range(3))
+    eager_ms = min(events_ms(eager, args.iters) for _ in range(3))
     step = graph.GraphedStep(lambda: sort.update(static), range_guard=False)
-    graph_ms = min(_events_ms(step, args.iters) for _ in range(3))
+    graph_ms = min(events_ms(step, args.iters) for _ in range(3))
     out = {"images": args.images, "rows": args.rows, "frames": args.frames, "iters": args.iters,
            "detections_per_image": round(float(np.mean([det["count"].mean() for det in seq])), 1),
            "tracks_per_image_after_sequence": round(float(np.mean(tracks)), 1), "association_paths_last_frame": paths,
