@@ -6,7 +6,8 @@ include/disconet_hip.h).  See DESIGN.md.
 """
 from .config import Config
 from .model import DiscoNet
-from .fusion_modes import COM_MODES, DET_COM_MODES, MaxFusion, MeanFusion, NoFusion, SumFusion, build_model
+from .fusion_modes import (ALL_DET_COM_MODES, COM_MODES, DET_COM_MODES, PARAM_COM_MODES, AgentTrainEngine, AgentWeightedFusion,
+                           MaxFusion, MeanFusion, NoFusion, SumFusion, build_model)
 from .postprocess import late_fuse
 from .detector import Detector, load_checkpoint
 from . import holistic, targets
@@ -16,5 +17,5 @@ from .teacher import TeacherNet
 from .targets import assign_targets
 from .train import CoDetModule, TrainEngine
 
-__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "COM_MODES", "DET_COM_MODES", "build_model", "late_fuse", "Detector", "load_checkpoint", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
+__all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "AgentWeightedFusion", "AgentTrainEngine", "COM_MODES", "DET_COM_MODES", "PARAM_COM_MODES", "ALL_DET_COM_MODES", "build_model", "late_fuse", "Detector", "load_checkpoint", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
            "assign_targets", "holistic", "holistic_views"]

@@ -191,6 +191,9 @@ SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
     "dn_warp_fm_supported": (c_int, [c_int, c_int, c_int]),
+    "dn_agent_fuse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_agent_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(FuseMlpParams), c_void_p, c_void_p, c_int, c_int,
+                              c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -246,6 +249,8 @@ SIGNATURES = {
     "dn_fuse_reduce_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_fuse_reduce_lists_backward": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p,
                                                                                   c_void_p]),
+    "dn_agent_combine_lists": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dn_agent_combine_lists_backward": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_warp_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
     "dn_warp_list": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,

@@ -68,6 +68,11 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
              int kslices = 1, float* workspace = nullptr, size_t workspace_bytes = 0, float* out_nhwc = nullptr,
              int ld_nhwc = 0);
 
+// the score launch of dn_agent_fuse (agent_fuse.hip), an epilogue of the attention MLP's kernel (fuse_mlp.hip)
+int fuse_mlp_agent_scores(const float* feat, const float* warped, int warped_fm, const int32_t* num_agent,
+                          const dn_fuse_mlp_params* p, const float* w5, int batch, int agents, int hw, int c, int only_v2i,
+                          int ego_first, int ego_count, float* partials, hipStream_t stream);
+
 // per-translation-unit words of the split-f16 range flags (sp_device.h); dn_sp_range_flags() ORs them
 void range_collect_conv_sp(unsigned* dst, bool reset, hipStream_t stream);
 void range_collect_conv_spq(unsigned* dst, bool reset, hipStream_t stream);

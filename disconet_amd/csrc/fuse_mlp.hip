@@ -23,6 +23,7 @@
 //
 // Replaces PixelWeightedFusionSoftmax.forward and the fusion loop body of
 // upstream:coperception/models/det/DiscoNet.py :: DiscoNet.forward (Appx A.5).
+#include "agent_device.h"
 #include "dn_internal.h"
 #include "sp_device.h"
 #include <type_traits>
@@ -66,6 +67,9 @@ struct FuseMlpArgs {
   int batch, agents, hw, only_v2i, ego_first, ego_count, tiles;
   int total_tiles;   // batch * ego_count * tiles (the weight-in-LDS form has workgroups of several tiles)
   int warped_fm;   // `warped` is fragment-major (dn_warp_neighbors_fm): a k-step of a tile is two contiguous 1 KB runs
+  // the score epilogue (AG, `--com agent`): conv1_5.weight [hw] and the per-tile partial sums [batch][ego_count][agents][tiles]
+  const float* w5;
+  float* partials;
 };
 // layer-1 weight fragments (L2): requested one k-step ahead of their MFMAs, two register sets.  Two and three steps ahead
 // (ring of four sets, no spills, counted vmcnt waits in the ISA) measured 83.7 us against 84.5 in the same lease: the launch is not
@@ -93,7 +97,12 @@ __device__ inline half8 frag_of(const unsigned char* base, int idx) {
 // fragments come at LDS latency.  In the one-wave form every wave streamed those fragments from L2 for itself (128 KB per layer-1
 // pass, 245 MB per step) with nothing to switch to while a load was in flight: two thirds of the launch was that loop at 30 % MFMA
 // utilisation.  The ego term stays in registers (no e_s), so the static LDS beside the 128 KB is 28 KB.
-template <int C, int G, int NW, int WL = 0>
+//
+// AG (dn_agent_fuse, `--com agent`): the SCORE epilogue.  Layers 1-4 as above, instruction for instruction; instead of exp, the
+// agent sum and the weighted sum, every wave multiplies the s_k of its 32 pixels by conv1_5's weights and writes one partial
+// sum per (ego, list slot, tile) -- agentw::tile_sum32, the fixed order of include/disconet_hip.h :: dn_agent_fuse.  Nothing else
+// is stored: padded egos, the fused map and the range flags belong to the combine launch (agent_fuse.hip).
+template <int C, int G, int NW, int WL = 0, bool AG = false>
 __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ? 1 : 2) disco_fuse_mlp_kernel(const FuseMlpArgs a) {
   constexpr bool kWL = WL > 0;
   constexpr int TWV = kWL ? WL : 1;        // waves of the workgroup that own a tile each
@@ -203,15 +212,17 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
               *t3l = aff_s + 328, *w4l = aff_s + 336;
 
   const bool active = have && i < live;      // kWL: a wave without a live ego still meets the workgroup's barriers
-  if (i >= live) {   // padded agent: its map passes through un-fused
+  if (i >= live) {   // padded agent: its map passes through un-fused (AG: by the combine launch)
+    if constexpr (!AG) {
 #pragma unroll
-    for (int u = 0; u < KSW; ++u) {
-      const int ks = ks_first + u;
-      store_piece(ks, *reinterpret_cast<const f32x4*>(xrow + 16 * ks),
-                  *reinterpret_cast<const f32x4*>(xrow + 16 * ks + 4));
+      for (int u = 0; u < KSW; ++u) {
+        const int ks = ks_first + u;
+        store_piece(ks, *reinterpret_cast<const f32x4*>(xrow + 16 * ks),
+                    *reinterpret_cast<const f32x4*>(xrow + 16 * ks + 4));
+      }
     }
     if constexpr (!kWL) {
-      note_range(amax, nan_seen);
+      if constexpr (!AG) note_range(amax, nan_seen);
       return;
     }
   }
@@ -354,7 +365,15 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
     // the other four units sit in lane (j, 1 - h); the sum is taken in unit order 0..7 on both lanes
     const float other = __shfl_xor(part, 32, 64);
     const float s = fmaxf((lh ? other + part : part + other) + b4v, 0.f);
-    return expf(s);
+    if constexpr (AG) return s;
+    else return expf(s);
+  };
+  // AG: the tile's share of a_k = sum_p w5[p] s_k[p] for list slot k (both lane halves hold the same s: lane 0 writes)
+  float w5v = 0.f;
+  if constexpr (AG) w5v = pvalid ? a.w5[pc] : 0.f;
+  auto emit_partial = [&](int k, float s) {
+    const float v = agentw::tile_sum32(agentw::score_term(s, w5v, pvalid));
+    if (lane == 0) a.partials[(((size_t)b * a.ego_count + il) * a.agents + k) * a.tiles + tile] = v;
   };
 
   // ---- pass 1a: E = W1_ego . x_ego, parked in LDS between the groups ([reg][lane]); kWL: kept in registers
@@ -438,7 +457,7 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
   // ---- pass 1b: scores of the list.  NW = 1: G slots at a time; NW = 4: this wave's slots wave, wave + 4, ...
   if constexpr (kWL) {
     if (!active) {      // nothing left for this wave (no tile, or a padded agent already passed through); no barrier follows
-      note_range(amax, nan_seen);
+      if constexpr (!AG) note_range(amax, nan_seen);
       return;
     }
   }
@@ -468,7 +487,10 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
       mark(2);
 #pragma unroll
       for (int g = 0; g < G; ++g)
-        if (g < cnt) ek_s[tw][g0 + g][lane] = tail(acc[g]);
+        if (g < cnt) {
+          if constexpr (AG) emit_partial(g0 + g, tail(acc[g]));
+          else ek_s[tw][g0 + g][lane] = tail(acc[g]);
+        }
       mark(3);
     }
   } else {
@@ -482,10 +504,12 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[0][nt][r] = e_s[nt * 16 + r][lane];
       layer1(std::integral_constant<int, 1>{}, rows, 1, 1, acc);
-      ek_s[0][k][lane] = tail(acc[0]);
+      if constexpr (AG) emit_partial(k, tail(acc[0]));
+      else ek_s[0][k][lane] = tail(acc[0]);
     }
-    __syncthreads();
+    if constexpr (!AG) __syncthreads();
   }
+  if constexpr (AG) return;
   float den = 0.f;
   for (int k = 0; k < n; ++k) den += ek_s[tw][k][lane];
 
@@ -594,9 +618,9 @@ namespace {
 // the weight-in-LDS form of <C, WL tiles per workgroup>: a FUNCTION template, so that every instantiation has its own
 // per-device "attribute set" flag (a generic lambda taking the kernel pointer instantiates ONCE for all nine kernels -- they
 // share the type void (*)(FuseMlpArgs) -- and raised the dynamic-LDS limit of the first variant launched only)
-template <int CC, int WL>
+template <int CC, int WL, bool AG>
 int launch_wl(const FuseMlpArgs& a, dim3 grid, int lds, hipStream_t s) {
-  auto kern = disco_fuse_mlp_kernel<CC, FUSE_GL, 1, WL>;
+  auto kern = disco_fuse_mlp_kernel<CC, FUSE_GL, 1, WL, AG>;
   static dn::PerDeviceFlag flag;
   bool& done = flag.here();
   if (!done) {
@@ -610,7 +634,7 @@ int launch_wl(const FuseMlpArgs& a, dim3 grid, int lds, hipStream_t s) {
 
 int fuse_mlp_impl(const float* feat, const float* warped, int warped_fm, const int32_t* num_agent, const dn_fuse_mlp_params* p,
                   int batch, int agents, int hw, int c, int only_v2i, int ego_first, int ego_count, void* fused_sp,
-                  float* fused_nhwc, float* weights_out, void* stream);
+                  float* fused_nhwc, float* weights_out, void* stream, const float* w5 = nullptr, float* partials = nullptr);
 }
 
 extern "C" int dn_disco_fuse_mlp(const float* feat, const float* warped, const int32_t* num_agent,
@@ -633,10 +657,15 @@ extern "C" int dn_disco_fuse_mlp_fm(const float* feat, const float* warped_fm, c
 }
 
 namespace {
+template <bool AG>
+int launch_forms(const FuseMlpArgs& a, int c, hipStream_t s);
+
 int fuse_mlp_impl(const float* feat, const float* warped, int warped_fm, const int32_t* num_agent, const dn_fuse_mlp_params* p,
                   int batch, int agents, int hw, int c, int only_v2i, int ego_first, int ego_count, void* fused_sp,
-                  float* fused_nhwc, float* weights_out, void* stream) {
-  DN_REQUIRE(feat && num_agent && p && (fused_sp || fused_nhwc), "fuse_mlp: null pointer");
+                  float* fused_nhwc, float* weights_out, void* stream, const float* w5, float* partials) {
+  const bool agent = partials != nullptr;      // the score epilogue (dn::fuse_mlp_agent_scores): no fused map of its own
+  DN_REQUIRE(feat && num_agent && p && (fused_sp || fused_nhwc || agent), "fuse_mlp: null pointer");
+  DN_REQUIRE(!agent || w5, "fuse_mlp (scores): null conv1_5 weight");
   DN_REQUIRE(agents < 2 || warped, "fuse_mlp: neighbours present but warped is null");
   DN_REQUIRE(batch > 0 && agents > 0 && hw > 0, "fuse_mlp: empty problem");
   DN_REQUIRE(dn_fuse_mlp_supported(c), "fuse_mlp: %d channels unsupported (64, 128 or 256)", c);
@@ -662,8 +691,14 @@ int fuse_mlp_impl(const float* feat, const float* warped, int warped_fm, const i
   a.tiles = (hw + 31) / 32;
   a.total_tiles = batch * ego_count * a.tiles;
   a.warped_fm = warped_fm;
-  dim3 grid(a.total_tiles);   // one workgroup per 32 pixels of one (sample, ego)
+  a.w5 = w5; a.partials = partials;
   hipStream_t s = (hipStream_t)stream;
+  return agent ? launch_forms<true>(a, c, s) : launch_forms<false>(a, c, s);
+}
+
+template <bool AG>
+int launch_forms(const FuseMlpArgs& a, int c, hipStream_t s) {
+  dim3 grid(a.total_tiles);   // one workgroup per 32 pixels of one (sample, ego)
   // Three forms, bit-identical results (tests/test_gpu_fusion.py):
   //   4 -- four waves per tile, when the launch leaves SIMDs idle (fewer tiles than 2 per CU: 128 tiles for one rank's
   //        share of the agent-sharded step, 87 -> 45 us);
@@ -679,21 +714,32 @@ int fuse_mlp_impl(const float* feat, const float* warped, int warped_fm, const i
     const int lds = 4 * (c / 16) * 2 * 2 * 32 * 16;
     int rc = DN_OK;
 #define DN_FUSE_WL(CC)                                                                        \
-    rc = wl == 2 ? launch_wl<CC, 2>(a, g2, lds, s) : wl == 3 ? launch_wl<CC, 3>(a, g2, lds, s) : launch_wl<CC, 4>(a, g2, lds, s)
+    rc = wl == 2 ? launch_wl<CC, 2, AG>(a, g2, lds, s) : wl == 3 ? launch_wl<CC, 3, AG>(a, g2, lds, s) : launch_wl<CC, 4, AG>(a, g2, lds, s)
     if (c == 256) DN_FUSE_WL(256);
     else if (c == 128) DN_FUSE_WL(128);
     else DN_FUSE_WL(64);
 #undef DN_FUSE_WL
     if (rc) return rc;
   } else if (waves == 1) {
-    if (c == 256) hipLaunchKernelGGL((disco_fuse_mlp_kernel<256, FUSE_G, 1>), grid, dim3(64), 0, s, a);
-    else if (c == 128) hipLaunchKernelGGL((disco_fuse_mlp_kernel<128, FUSE_G, 1>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((disco_fuse_mlp_kernel<64, FUSE_G, 1>), grid, dim3(64), 0, s, a);
+    if (c == 256) hipLaunchKernelGGL((disco_fuse_mlp_kernel<256, FUSE_G, 1, 0, AG>), grid, dim3(64), 0, s, a);
+    else if (c == 128) hipLaunchKernelGGL((disco_fuse_mlp_kernel<128, FUSE_G, 1, 0, AG>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((disco_fuse_mlp_kernel<64, FUSE_G, 1, 0, AG>), grid, dim3(64), 0, s, a);
   } else {
-    if (c == 256) hipLaunchKernelGGL((disco_fuse_mlp_kernel<256, 1, 4>), grid, dim3(256), 0, s, a);
-    else if (c == 128) hipLaunchKernelGGL((disco_fuse_mlp_kernel<128, 1, 4>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((disco_fuse_mlp_kernel<64, 1, 4>), grid, dim3(256), 0, s, a);
+    if (c == 256) hipLaunchKernelGGL((disco_fuse_mlp_kernel<256, 1, 4, 0, AG>), grid, dim3(256), 0, s, a);
+    else if (c == 128) hipLaunchKernelGGL((disco_fuse_mlp_kernel<128, 1, 4, 0, AG>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((disco_fuse_mlp_kernel<64, 1, 4, 0, AG>), grid, dim3(256), 0, s, a);
   }
   return dn::check_launch("disco_fuse_mlp_kernel");
 }
 }  // namespace
+
+// the score launch of dn_agent_fuse (agent_fuse.hip): layers 1-4 of the same MLP on the same operands, in the launch form
+// dn_fuse_mlp_set_waves / the tile count selects; partials [batch][ego_count][agents][ceil(hw / 32)]
+int dn::fuse_mlp_agent_scores(const float* feat, const float* warped, int warped_fm, const int32_t* num_agent,
+                              const dn_fuse_mlp_params* p, const float* w5, int batch, int agents, int hw, int c, int only_v2i,
+                              int ego_first, int ego_count, float* partials, hipStream_t stream) {
+  DN_REQUIRE(partials, "agent fuse: null workspace");
+  DN_REQUIRE(!warped_fm || hw % 32 == 0, "agent fuse (fragment-major): hw %d must be a multiple of 32", hw);
+  return fuse_mlp_impl(feat, warped, warped_fm, num_agent, p, batch, agents, hw, c, only_v2i, ego_first, ego_count, nullptr,
+                       nullptr, nullptr, (void*)stream, w5, partials);
+}

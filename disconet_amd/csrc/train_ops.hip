@@ -18,6 +18,7 @@
 #include <initializer_list>
 #include <type_traits>
 
+#include "agent_device.h"
 #include "disconet_train.h"
 #include "dn_internal.h"
 
@@ -913,6 +914,76 @@ fuse_combine_bwd_kernel(const float* __restrict__ dfused, int ld_df, const float
     }
 }
 
+// ---- `--com agent` (include/disconet_train.h :: dn_agent_combine_lists): one scalar weight per list entry, in the order of
+// agent_device.h -- the inference path's (agent_fuse.hip), so the same scores give the same bits
+// one workgroup per ego; wave v takes the list entries v, v + 4, ...; lane l and lane l + 32 carry pixel l of a tile
+__global__ void __launch_bounds__(256)
+agent_list_weights_kernel(const float* __restrict__ z4, const float* __restrict__ w5, const float* __restrict__ b5,
+                          const int* __restrict__ first, const int* __restrict__ pair_index, int hw,
+                          float* __restrict__ weights) {
+  __shared__ float a_s[agentw::kMaxList];
+  const int e = blockIdx.x;
+  const int k0 = first[e];
+  int kn = first[e + 1] - k0;
+  kn = kn < 0 ? 0 : (kn > agentw::kMaxList ? agentw::kMaxList : kn);   // (host side: train.py refuses longer lists)
+  if (kn == 0) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31;
+  const int tiles = (hw + 31) / 32;
+  for (int k = wave; k < kn; k += 4) {
+    const int p = pair_index[k0 + k];
+    float folded = 0.f;
+    if (p >= 0) {
+      const float* z = z4 + (size_t)p * hw;
+      for (int t = 0; t < tiles; ++t) {
+        const int px = t * 32 + li;
+        const bool valid = px < hw;
+        const float s = valid ? fmaxf(z[px], 0.f) : 0.f;
+        const float ts = agentw::tile_sum32(agentw::score_term(s, valid ? w5[px] : 0.f, valid));
+        folded = agentw::fold_tile(folded, ts, t == 0);
+      }
+    }
+    if (lane == 0) a_s[k] = p >= 0 ? agentw::agent_scalar(folded, b5[0]) : 0.f;   // (an ego that is not live: alone in its list)
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float w[agentw::kMaxList];
+    agentw::list_softmax(a_s, kn, w);
+    for (int k = 0; k < kn; ++k) weights[k0 + k] = w[k];
+  }
+}
+
+__global__ void __launch_bounds__(256)
+agent_combine_lists_kernel(const float* __restrict__ maps, const float* __restrict__ weights, const int* __restrict__ first,
+                           const int* __restrict__ map_image, const int* __restrict__ ego_out, long quads,
+                           float* __restrict__ fused) {
+  const int e = blockIdx.y;
+  const int s = first[e], t = first[e + 1];
+  if (t <= s) return;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
+    f32x4 acc = agentw::weigh(*reinterpret_cast<const f32x4*>(maps + ((size_t)map_image[s] * quads + q) * 4), weights[s]);
+    for (int k = s + 1; k < t; ++k)
+      acc = agentw::weigh_add(acc, *reinterpret_cast<const f32x4*>(maps + ((size_t)map_image[k] * quads + q) * 4), weights[k]);
+    *reinterpret_cast<f32x4*>(fused + ((size_t)ego_out[e] * quads + q) * 4) = acc;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+agent_combine_lists_bwd_kernel(const float* __restrict__ dfused, int ld, const float* __restrict__ weights,
+                               const int* __restrict__ first, const int* __restrict__ map_image,
+                               const int* __restrict__ ego_out, int hw, int c4n, float* __restrict__ dmaps) {
+  const int e = blockIdx.y;
+  const int s = first[e], t = first[e + 1];
+  if (t <= s) return;
+  const long quads = (long)hw * c4n;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
+    const long p = q / c4n;
+    const int c4 = (int)(q - p * c4n);
+    const f32x4 g = *reinterpret_cast<const f32x4*>(dfused + ((size_t)ego_out[e] * hw + p) * ld + 4 * c4);
+    for (int k = s; k < t; ++k)
+      *reinterpret_cast<f32x4*>(dmaps + ((size_t)map_image[k] * quads + q) * 4) = agentw::weigh(g, weights[k]);
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // loss and optimiser
 // ---------------------------------------------------------------------------------
@@ -1493,6 +1564,33 @@ extern "C" int dn_fuse_combine_backward(const float* dfused, int ld_df, const fl
                      (hipStream_t)stream, dfused, ld_df, z4, weights, maps, first, pair_index, map_image,
                      ego_out, n_egos, hw, c, dmaps, dz4);
   return dn::check_launch("fuse_combine_bwd_kernel");
+}
+
+extern "C" int dn_agent_combine_lists(const float* z4, const float* w5, const float* b5, const float* maps,
+                                      const int32_t* first, const int32_t* pair_index, const int32_t* map_image,
+                                      const int32_t* ego_out, int n_egos, int hw, int c, float* weights, float* fused,
+                                      void* stream) {
+  DN_REQUIRE(z4 && w5 && b5 && maps && first && pair_index && map_image && ego_out && weights && fused,
+             "agent combine lists: null pointer");
+  DN_REQUIRE(n_egos > 0 && n_egos <= 65535 && hw > 0 && c > 0 && c % 4 == 0, "agent combine lists: bad shape");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(agent_list_weights_kernel, dim3(n_egos), dim3(256), 0, s, z4, w5, b5, first, pair_index, hw, weights);
+  const long quads = (long)hw * (c >> 2);
+  hipLaunchKernelGGL(agent_combine_lists_kernel, dim3(grid_for(quads), n_egos), dim3(256), 0, s, maps, weights, first,
+                     map_image, ego_out, quads, fused);
+  return dn::check_launch("agent_combine_lists_kernel");
+}
+
+extern "C" int dn_agent_combine_lists_backward(const float* dfused, int ld, const float* weights, const int32_t* first,
+                                               const int32_t* map_image, const int32_t* ego_out, int n_egos, int hw, int c,
+                                               float* dmaps, void* stream) {
+  DN_REQUIRE(dfused && weights && first && map_image && ego_out && dmaps, "agent combine lists backward: null pointer");
+  DN_REQUIRE(n_egos > 0 && n_egos <= 65535 && hw > 0 && c > 0 && c % 4 == 0, "agent combine lists backward: bad shape");
+  DN_REQUIRE(ld >= c && ld % 4 == 0 && ((size_t)dfused & 15) == 0,
+             "agent combine lists backward: dfused rows must be 16-byte aligned (ld = %d, c = %d)", ld, c);
+  hipLaunchKernelGGL(agent_combine_lists_bwd_kernel, dim3(grid_for((long)hw * (c >> 2)), n_egos), dim3(256), 0,
+                     (hipStream_t)stream, dfused, ld, weights, first, map_image, ego_out, hw, c >> 2, dmaps);
+  return dn::check_launch("agent_combine_lists_bwd_kernel");
 }
 
 extern "C" int dn_det_loss(const float* cls, const float* labels, const float* loc,

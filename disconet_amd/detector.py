@@ -28,7 +28,7 @@ def load_checkpoint(model, path):
 class Detector:
     def __init__(self, com, config, num_agent, batch_size, *, layer=3, kd_flag=0, compress_level=0, only_v2i=False,
                  pre_nms_top_k=300, iou_thr=0.01, score_thr=None, resume="", seed=0, device="cuda"):
-        """com: one of DET_COM_MODES (build_model raises ValueError otherwise).  Without `resume` the weights are random:
+        """com: one of ALL_DET_COM_MODES (build_model raises ValueError otherwise).  Without `resume` the weights are random:
         seeded before construction, so that a run can be reproduced, and the BatchNorm statistics are randomised
         (synthetic.randomize_bn_stats).  `epoch` is the loaded checkpoint's epoch, or None."""
         self.com, self.config, self.num_agent, self.batch_size = com, config, num_agent, batch_size

@@ -14,13 +14,23 @@ dn_fuse_reduce; `host_fuse_reduce` states it in plain torch on the CPU.
 The two floors of the comparison live here too: `--com lowerbound` (NoFusion: the identity in place of the reduction, every
 agent detects from its own view) and `--com late`, the same detector with postprocess.late_fuse behind its detection tail
 (collaboration at the box level, dn_late_fuse).  COM_MODES keeps the four feature-level modes; DET_COM_MODES adds the two.
+
+`--com agent` (upstream AgentWiseWeightedFusion) is the first baseline with parameters of its own: a weight net with the four
+1x1 layers of DiscoGraph's attention MLP plus conv1_5 = Conv2d(1, 1, (h, w)) gives ONE scalar per entry of the ego's list,
+softmax over the list, weighted sum.  Upstream wraps the scalars in torch.tensor(...), which detaches them: the weight net is
+never trained (no gradient reaches it, Adam skips it), only its BatchNorm running statistics move.  That is kept here.
+Inference: ops.agent_fuse (warp, scores as an epilogue of fuse_mlp.hip's kernel, combine: csrc/agent_fuse.hip); training:
+the base engine's MLP forward up to its last logits, then dn_agent_combine_lists / _backward.  The contract is
+include/disconet_hip.h :: dn_agent_fuse; `host_agent_fuse` states it in plain torch on the CPU.  PARAM_COM_MODES names the
+modes with parameters, ALL_DET_COM_MODES every mode of the det / track tools.
 """
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
 from . import train_ops as T
-from .model import DiscoNet
+from .model import LAYER_CHANNEL, DiscoNet, _FusionParams, fuse_mlp_params_of
 from .profiling import region
 from .train import TrainEngine
 
@@ -28,6 +38,9 @@ COM_MODES = ("disco", "sum", "mean", "max")
 # the modes of the det / track tools: `lowerbound` is the detector without collaboration, `late` that detector with
 # postprocess.late_fuse behind its detection tail (collaboration at the box level; trained as `lowerbound`)
 DET_COM_MODES = COM_MODES + ("lowerbound", "late")
+# the collaboration strategies with parameters of their own, and every mode the det / track tools take
+PARAM_COM_MODES = ("agent",)
+ALL_DET_COM_MODES = DET_COM_MODES + PARAM_COM_MODES
 
 
 # ---------------------------------------------------------------------------
@@ -87,6 +100,84 @@ def host_fuse_reduce(feat, trans, num_agent, batch, agents, mode, only_v2i=False
                             if j != i and not (only_v2i and i != 0 and j != 0)]
             out[(i - ego_first) * B + b] = reduce_list(maps, mode)
     return out.permute(0, 2, 3, 1).contiguous()
+
+
+def _host_scores(net, ego, nb):
+    """s [h, w]: the weight net's layers 1-4 on cat[ego, nb] ([C, h, w] each), eval-mode BatchNorm, fp32"""
+    x = torch.cat([ego, nb], 0).unsqueeze(0)
+    for i in (1, 2, 3):
+        conv, bn = getattr(net, "conv1_%d" % i), getattr(net, "bn1_%d" % i)
+        x = F.relu(F.batch_norm(F.conv2d(x, conv.weight, conv.bias), bn.running_mean, bn.running_var, bn.weight, bn.bias,
+                                False, 0.0, bn.eps))
+    return F.relu(F.conv2d(x, net.conv1_4.weight, net.conv1_4.bias))[0, 0]
+
+
+def agent_scalar(s, w5, b5):
+    """a = relu(b5 + sum_p w5[p] s[p]) in the contract's order (include/disconet_hip.h :: dn_agent_fuse), fp32 on the CPU: the
+    products rounded, tiles of 32 consecutive pixels (zeros past the end), within a tile the tree l with l + 16, + 8, + 4,
+    + 2, + 1, the tiles' sums added one after the other ascending, then + b5 and the ReLU"""
+    prod = s.reshape(-1).float() * w5.reshape(-1).float()
+    tiles = (prod.numel() + 31) // 32
+    v = torch.zeros(tiles * 32, dtype=torch.float32)
+    v[:prod.numel()] = prod
+    v = v.view(tiles, 32)
+    for d in (16, 8, 4, 2, 1):
+        v = v[:, :d] + v[:, d:2 * d]
+    acc = v[0, 0]
+    for t in range(1, tiles):
+        acc = acc + v[t, 0]
+    return torch.clamp(acc + b5.reshape(()).float(), min=0.0)
+
+
+def agent_softmax(a):
+    """w_k = exp(a_k - max a) / sum exp, the sum taken in list order, fp32; a [L]"""
+    e = torch.exp(a - a.max())
+    total = e[0]
+    for k in range(1, e.numel()):
+        total = total + e[k]
+    return e / total
+
+
+def weighted_sum(maps, w):
+    """sum_k w_k map_k: the first product, then product by product in list order (each product rounded before its add)"""
+    acc = w[0] * maps[0]
+    for k in range(1, len(maps)):
+        acc = acc + w[k] * maps[k]
+    return acc
+
+
+def host_agent_fuse(feat, trans, num_agent, batch, agents, net, only_v2i=False, ego_first=0, ego_count=None,
+                    want_weights=False):
+    """ops.agent_fuse's contract in plain torch on the CPU, fp32: feat [A*B, h, w, C] agent-major NHWC, trans
+    [B, A, A, 4, 4], num_agent [B] live counts (clamped to 0..A), net: the weight net (agent_weighted_fusion's names, its
+    BatchNorms in eval mode) -> fused [ego_count*B, h, w, C] (+ weights [B, ego_count, A] in list order).  A padded ego
+    passes through; a dead neighbour is never read."""
+    A, B = agents, batch
+    E = A if ego_count is None else ego_count
+    x = feat.detach().to(device="cpu", dtype=torch.float32).permute(0, 3, 1, 2)      # [A*B, C, h, w]
+    trans = trans.detach().to(device="cpu", dtype=torch.float32)
+    if x.shape[0] != A * B:
+        raise ValueError("feat has %d images, expected agents * batch = %d" % (x.shape[0], A * B))
+    if not (0 <= ego_first and E > 0 and ego_first + E <= A):
+        raise ValueError("ego range [%d, %d) outside 0..%d" % (ego_first, ego_first + E, A))
+    out = torch.empty((E * B,) + tuple(x.shape[1:]), dtype=torch.float32)
+    weights = torch.zeros(B, E, A, dtype=torch.float32)
+    with torch.no_grad():
+        for b in range(B):
+            n = max(0, min(int(num_agent[b]), A))
+            for i in range(ego_first, ego_first + E):
+                ego = x[i * B + b]
+                if i >= n:
+                    out[(i - ego_first) * B + b] = ego
+                    continue
+                maps = [ego] + [_host_warp(x[j * B + b], trans[b, i, j]) for j in range(n)
+                                if j != i and not (only_v2i and i != 0 and j != 0)]
+                a = torch.stack([agent_scalar(_host_scores(net, ego, m), net.conv1_5.weight, net.conv1_5.bias) for m in maps])
+                w = agent_softmax(a)
+                weights[b, i - ego_first, :len(maps)] = w
+                out[(i - ego_first) * B + b] = weighted_sum(maps, w)
+    fused = out.permute(0, 2, 3, 1).contiguous()
+    return (fused, weights) if want_weights else fused
 
 
 # ---------------------------------------------------------------------------
@@ -156,21 +247,81 @@ class NoFusion(_ReduceFusionNet):
         return ops.as_nhwc(feat)[ego_first * batch_size:(ego_first + E) * batch_size]
 
 
+class _AgentNetParams(_FusionParams):
+    """upstream AgentWeightedFusion's parameter names: PixelWeightedFusionSoftmax's four 1x1 layers and conv1_5, whose kernel
+    is the exchanged map's own (h, w) -- 32 x 32 at the reference's 256 x 256 input, upstream's state-dict shape"""
+
+    def __init__(self, channel, h, w):
+        super().__init__(channel)
+        self.conv1_5 = nn.Conv2d(1, 1, kernel_size=(h, w))
+
+
+class AgentWeightedFusion(DiscoNet):
+    """`--com agent`: DiscoNet's walk with one scalar weight per agent of the ego's list (module docstring).  Its parameters
+    are `agent_weighted_fusion.*`; it has no pixel_weighted_fusion, so a DiscoNet checkpoint fails torch's strict check."""
+
+    com = "agent"
+
+    def __init__(self, config, layer=3, *args, **kw):
+        # (the weight net's last kernel spans the exchanged map: its size is needed before DiscoNet creates the parameters)
+        self.__dict__["_fused_hw"] = (int(config.map_dims[0]) >> layer, int(config.map_dims[1]) >> layer)
+        super().__init__(config, layer, *args, **kw)
+
+    def _create_fusion_params(self):
+        self.agent_weighted_fusion = _AgentNetParams(LAYER_CHANNEL[self.layer], *self._fused_hw)
+
+    def _fusion_plan(self, math):
+        """the weight net packed as DiscoNet's one-launch attention (whatever the conv engine's math: the scores are
+        dn_disco_fuse_mlp's layers 1-4) and conv1_5 as it is"""
+        f, C = self.agent_weighted_fusion, LAYER_CHANNEL[self.layer]
+        if not ops.fuse_mlp_supported(C):
+            raise ops._lib.DnError("--com agent: the weight net runs on %d-channel maps only where dn_fuse_mlp_supported "
+                                   "(64, 128 or 256 channels: layer 1, 2 or 3)" % C)
+        P = {}
+        P["_fuse_mlp"], P["_fuse_mlp_tensors"] = fuse_mlp_params_of(f, C)
+        P["_w5"] = f.conv1_5.weight.detach().float().contiguous()
+        P["_b5"] = f.conv1_5.bias.detach().float().contiguous()
+        return P
+
+    def _train_engine_class(self):
+        return AgentTrainEngine
+
+    def fuse(self, feat, trans_matrices, num_agent, batch_size, P, want_weights=False, ego_first=0, ego_count=None,
+             sp_out=False):
+        """ops.agent_fuse over the layer-`layer` maps -> fp32 NHWC (+ the scalar weights [B, E, A] in list order with
+        want_weights; sp_out is ignored: the decoder's first conv splits an NHWC input itself, _ConvLayer.run)"""
+        feat = ops.as_nhwc(feat)
+        n, h, w, c = feat.shape
+        A, B = self.agent_num, batch_size
+        E = A if ego_count is None else ego_count
+        map_bytes, pairs = 4.0 * h * w * c, B * E * (A - 1)
+        flops = 2.0 * B * E * h * w * (128.0 * c * (2 + (A - 1)) + A * (128 * 32 + 32 * 8 + 8))
+        with region("agent_fuse", "agent_combine_kernel", flops, map_bytes * (n + 3 * pairs + 3 * E * B)):
+            return ops.agent_fuse(feat, trans_matrices, num_agent, P["_fuse_mlp"], P["_w5"], P["_b5"], B, A, self.only_v2i,
+                                  want_weights, ego_first, E)
+
+
 _CLASSES = {"disco": DiscoNet, "sum": SumFusion, "mean": MeanFusion, "max": MaxFusion, "lowerbound": NoFusion,
-            "late": NoFusion}
+            "late": NoFusion, "agent": AgentWeightedFusion}
 
 
 def build_model(com, config, **kw):
     """the detector of `--com com`: DiscoNet for "disco", the baseline's class for sum / mean / max, NoFusion for
-    lowerbound and late; same constructor arguments"""
+    lowerbound and late, AgentWeightedFusion for agent; same constructor arguments"""
     if com not in _CLASSES:
-        raise ValueError("--com must be one of %s (got %r)" % (", ".join(DET_COM_MODES), com))
+        raise ValueError("--com must be one of %s, %s (got %r)" % (", ".join(DET_COM_MODES), ", ".join(PARAM_COM_MODES), com))
     return _CLASSES[com](config, **kw)
 
 
 # ---------------------------------------------------------------------------
 # training
 # ---------------------------------------------------------------------------
+def _refuse_shard(model, shard):
+    if shard is not None:
+        raise NotImplementedError("agent-parallel training of --com %s is not built (the sharded step is --com disco's)"
+                                  % model.com)
+
+
 class ReduceTrainEngine(TrainEngine):
     """TrainEngine with the reduction in the place of the attention block: no fusion layers, no per-call BatchNorms;
     everything else (the lifts, the range guard, the fp32 fallback, the checkpoint keys) is the base engine's."""
@@ -178,9 +329,7 @@ class ReduceTrainEngine(TrainEngine):
     _KD_OK = False      # the distillation is DiscoGraph's (CoDetModule refuses kd_flag = 1)
 
     def __init__(self, model, *args, shard=None, **kw):
-        if shard is not None:
-            raise NotImplementedError("agent-parallel training of --com %s is not built (the sharded step is --com disco's)"
-                                      % model.com)
+        _refuse_shard(model, shard)
         super().__init__(model, *args, shard=None, **kw)
 
     def _fusion_layers(self):
@@ -220,3 +369,52 @@ class NoFusionTrainEngine(ReduceTrainEngine):
 
     def _fusion_bwd(self, dfused, G):
         return dfused
+
+
+class AgentTrainEngine(TrainEngine):
+    """`--com agent`: the base engine's MLP forward on the weight net up to its last logits (the warps, the column-cut layer
+    1, per-call BatchNorm statistics, mlp2, mlp3, conv1_4), then dn_agent_combine_lists.  As upstream, whose weights are
+    torch.tensor(list of scalars), the weight net is never trained: no gradient enters it and its parameters are not stepped
+    at all (they lie behind the trained ones in the flat buffer, and Adam -- weight decay included -- runs over the trained
+    prefix).  Its three BatchNorms still move their running statistics once per call of the net."""
+
+    _KD_OK = False      # the distillation is DiscoGraph's (CoDetModule refuses kd_flag = 1)
+
+    def __init__(self, model, *args, shard=None, **kw):
+        _refuse_shard(model, shard)
+        super().__init__(model, *args, shard=None, **kw)
+
+    def _param_order(self, model):
+        frozen = {id(p) for p in model.agent_weighted_fusion.parameters()}
+        order = super()._param_order(model)
+        trained = [p for p in order if id(p) not in frozen]
+        self._n_trained = sum((p.numel() + 3) // 4 * 4 for p in trained)      # (the flat buffer's 16-byte aligned views)
+        return trained + [p for p in order if id(p) in frozen]
+
+    def _fusion_net(self):
+        return self.model.agent_weighted_fusion
+
+    def _fusion_fwd(self, maps, NI, NW, F):
+        c = self._fusion_mlp_fwd(maps, NI, NW, F)
+        f = self._fusion_net()
+        fused = torch.empty((F["ego_out"].numel(),) + tuple(maps.shape[1:]), dtype=torch.float32, device=maps.device)
+        c["weights"] = T.agent_combine_lists(c["z4"], f.conv1_5.weight, f.conv1_5.bias, maps, F["first"], F["pair_index"],
+                                             F["map_image"], F["ego_out"], fused)
+        self.fctx = c
+        return fused
+
+    def _fusion_bwd(self, dfused, G):
+        F, c = self.F, self.fctx
+        maps, NI, NW = c["maps"], c["NI"], c["NW"]
+        dmaps = torch.empty_like(maps)      # every map is in exactly one list: every row is written
+        T.agent_combine_lists_backward(dfused, c["weights"], maps, F["first"], F["map_image"], F["ego_out"], dmaps)
+        if NW:
+            T.warp_backward(dmaps[NI:], F["poses"], F["src_image"], dmaps[:NI], rigid=F["rigid"])
+        return dmaps[:NI]
+
+    def optimizer_step(self):
+        self.step_count += 1
+        n = self._n_trained
+        T.adam_step(self.flat_p[:n], self.flat_g[:n], self.flat_m[:n], self.flat_v[:n], self.step_count, self.lr, self.betas,
+                    self.eps, self.weight_decay)
+        self.model._plan = None          # eval-mode packed weights are stale now

@@ -306,6 +306,16 @@ class _ConvPostLayer:
         return out_a, out_b
 
 
+def fuse_mlp_params_of(f, C):
+    """ops.make_fuse_mlp_params of the four 1x1 layers of `f` (_FusionParams names) over C-channel maps, the eval-mode
+    BatchNorms folded: the packed form dn_disco_fuse_mlp and dn_agent_fuse read.  -> (FuseMlpParams, tensors to keep alive)"""
+    return ops.make_fuse_mlp_params(
+        f.conv1_1.weight.detach().reshape(128, 2 * C), f.conv1_1.bias, ops.fold_bn(None, f.bn1_1, 128),
+        f.conv1_2.weight.reshape(32, 128), f.conv1_2.bias, ops.fold_bn(None, f.bn1_2, 32),
+        f.conv1_3.weight.reshape(8, 32), f.conv1_3.bias, ops.fold_bn(None, f.bn1_3, 8),
+        f.conv1_4.weight, f.conv1_4.bias, C)
+
+
 def attention_mlp_plan(f, C, math, fuse_mlp):
     """the plan entries of the attention MLP (_FusionParams `f` over C-channel maps) for the model's math mode: its two
     1x1 launches on the NHWC engine (layer 1 split W1 = [W1_ego | W1_nbr], see fuse_tail.hip) + the tail kernel's
@@ -335,11 +345,7 @@ def attention_mlp_plan(f, C, math, fuse_mlp):
     P["_tail"] = ops.make_tail_params(tail)
     if math != 0 and fuse_mlp and ops.fuse_mlp_supported(C):
         # split-f16 engines: the whole attention MLP + agent softmax + weighted sum in one launch
-        P["_fuse_mlp"], P["_fuse_mlp_tensors"] = ops.make_fuse_mlp_params(
-            w1, f.conv1_1.bias, (bn1_scale, bn1_shift),
-            f.conv1_2.weight.reshape(32, 128), f.conv1_2.bias, ops.fold_bn(None, f.bn1_2, 32),
-            f.conv1_3.weight.reshape(8, 32), f.conv1_3.bias, ops.fold_bn(None, f.bn1_3, 8),
-            f.conv1_4.weight, f.conv1_4.bias, C)
+        P["_fuse_mlp"], P["_fuse_mlp_tensors"] = fuse_mlp_params_of(f, C)
     return P
 
 

@@ -966,6 +966,43 @@ def disco_fuse_mlp(feat, warped, num_agent, params, batch, agents, only_v2i=Fals
     return (res, weights) if want_weights else res
 
 
+def agent_fuse(feat, trans, num_agent, params, w5, b5, batch, agents, only_v2i=False, want_weights=False, ego_first=0,
+               ego_count=None, fm=None, warped=None):
+    """`--com agent` (include/disconet_hip.h :: dn_agent_fuse): one scalar weight per agent of the ego's list from the weight
+    net (params: make_fuse_mlp_params of its four 1x1 layers; w5 [1, 1, h, w] / b5 [1]: conv1_5), softmax over the list,
+    weighted sum.  Three launches: the pose warp, the scores, the combine.  feat [A*B, h, w, C] agent-major NHWC (all
+    agents) -> fused [ego_count*B, h, w, C] float32 NHWC (+ weights [B, ego_count, A] in list order when want_weights).
+    fm: the warped maps in the fragment-major form (None: where the shape allows); warped: maps that warp_neighbors(fm=fm)
+    already wrote for these egos (tools)."""
+    _need_gpu(feat, trans, num_agent, w5, b5)
+    _f32c(feat, "feat")
+    _f32c(trans, "trans_matrices")
+    _f32c(w5, "conv1_5.weight")
+    _f32c(b5, "conv1_5.bias")
+    ego_count = agents if ego_count is None else ego_count
+    n, h, w, c = feat.shape
+    if n != agents * batch:
+        raise ValueError("feat has %d images, expected agents * batch = %d" % (n, agents * batch))
+    if w5.numel() != h * w or b5.numel() != 1:
+        raise ValueError("conv1_5 is Conv2d(1, 1, (%d, %d)) over this map: weight of %d values (got %d), one bias (got %d)"
+                         % (h, w, h * w, w5.numel(), b5.numel()))
+    if not fuse_mlp_supported(c):
+        raise _lib.DnError("agent_fuse: %d channels unsupported (64, 128 or 256)" % c)
+    lib = _lib.load()
+    if fm is None:
+        fm = agents > 1 and warp_fm_supported(h, w, c)
+    if warped is None and agents > 1 and 0 <= ego_first and 0 < ego_count <= agents - ego_first:
+        warped = warp_neighbors(feat, trans, num_agent, batch, agents, only_v2i, ego_first, ego_count, fm=fm)
+    work = torch.empty(max(lib.dn_agent_fuse_workspace_bytes(batch, agents, max(ego_count, 0), h * w), 16), dtype=torch.uint8,
+                       device=feat.device)
+    fused = torch.empty((max(ego_count, 0) * batch, h, w, c), dtype=torch.float32, device=feat.device)
+    weights = torch.zeros((batch, max(ego_count, 0), agents), dtype=torch.float32, device=feat.device) if want_weights else None
+    check(lib.dn_agent_fuse(_ptr(feat), _ptr(warped), int(bool(fm)), _ptr(num_agent), ctypes.byref(params), _ptr(w5), _ptr(b5),
+                            batch, agents, h * w, c, int(only_v2i), ego_first, ego_count, _ptr(work), work.numel(), _ptr(fused),
+                            _ptr(weights), _stream()), "dn_agent_fuse")
+    return (fused, weights) if want_weights else fused
+
+
 def live_agent_counts(num_agent_tensor, device):
     """The kernels' [B] int32 live-agent counts from the reference's num_agent_tensor [B, A] (column 0 is the
     count).  A 1-D int32 tensor already on the device is taken as is -- no cast / gather kernel inside the step

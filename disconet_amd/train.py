@@ -448,12 +448,15 @@ class TrainEngine:
                   if r.bn is not None}
         self.L.update(self._fusion_layers())
 
+    def _fusion_net(self):         # the module that owns the fusion block's 1x1 layers (`--com agent`: its weight net)
+        return self.model.pixel_weighted_fusion
+
     def _fusion_layers(self):      # the fusion block's own conv + BatchNorm layers (none in the parameter-free baselines)
-        return _fusion_mlp_layers(self.model.pixel_weighted_fusion)
+        return _fusion_mlp_layers(self._fusion_net())
 
     def _fusion_per_call_stats(self):
         """(BatchNorm, mean, var) of the fusion block's BatchNorms that are updated once per CALL of the attention MLP"""
-        f, fc = self.model.pixel_weighted_fusion, self.fctx
+        f, fc = self._fusion_net(), self.fctx
         return [(f.bn1_1, fc["mean1"], fc["var1"])] + [(lay.bn, lay.ctx["mean"], lay.ctx["var"]) for lay in self.L.values()
                                                         if lay.per_call]
 
@@ -877,9 +880,11 @@ class TrainEngine:
                             "cls": cls_out.view(nI, -1, m.category_num)}
         return self.last_result
 
-    def _fusion_fwd(self, maps, NI, NW, F):
-        m, L = self.model, self.L
-        f = m.pixel_weighted_fusion
+    def _fusion_mlp_fwd(self, maps, NI, NW, F):
+        """the warps into maps[NI:] and the attention MLP up to its last logits z4 [P, h, w, 1], one call per map of the pair
+        buffer with per-call BatchNorm statistics -> what the combine and the backward need"""
+        L = self.L
+        f = self._fusion_net()
         C = maps.shape[-1]
         P = NI + NW
         if NW:
@@ -893,11 +898,14 @@ class TrainEngine:
         h2 = self._layer_fwd(L["mlp2"], h1, groups=P)
         h3 = self._layer_fwd(L["mlp3"], h2, groups=P)
         z4, d4 = self._conv(f.conv1_4.weight, f.conv1_4.bias, h3, ksize=1)
+        return dict(maps=maps, NI=NI, NW=NW, z1=z1, mean1=mean1, var1=var1, h1=h1, d_e=d_e, d_f=d_f, h3=h3, z4=z4, d4=d4)
+
+    def _fusion_fwd(self, maps, NI, NW, F):
+        c = self._fusion_mlp_fwd(maps, NI, NW, F)
         n_ego = F["ego_out"].numel()                          # fused maps of this rank's egos (all of them without a shard)
         fused = torch.empty((n_ego,) + tuple(maps.shape[1:]), dtype=torch.float32, device=maps.device)
-        weights = T.fuse_combine(z4, maps, F["first"], F["pair_index"], F["map_image"], F["ego_out"], fused)
-        self.fctx = dict(maps=maps, NI=NI, NW=NW, z1=z1, mean1=mean1, var1=var1, h1=h1, d_e=d_e, d_f=d_f,
-                         h3=h3, z4=z4, d4=d4, weights=weights)
+        c["weights"] = T.fuse_combine(c["z4"], maps, F["first"], F["pair_index"], F["map_image"], F["ego_out"], fused)
+        self.fctx = c
         return fused
 
     # ------------------------------------------------------------------

@@ -433,6 +433,31 @@ def fuse_reduce_lists_backward(dfused, maps, fused, first, map_image, ego_out, m
     return dmaps
 
 
+def agent_combine_lists(z4, w5, b5, maps, first, pair_index, map_image, ego_out, fused):
+    """`--com agent` over the training lists (include/disconet_train.h :: dn_agent_combine_lists): z4 [P, h, w, 1] the weight
+    net's last logits, w5 [1, 1, h, w] / b5 [1] its conv1_5; writes fused[ego_out[e]] = sum_k w_k maps[map_image_k] and
+    returns the scalar weights, one per list entry (at the entry's place in pair_index / map_image)"""
+    _need_gpu(z4, w5, b5, maps, fused)
+    hw, c = maps.shape[1] * maps.shape[2], maps.shape[3]
+    if w5.numel() != hw or b5.numel() != 1:
+        raise ValueError("conv1_5 is Conv2d(1, 1, (%d, %d)) over these maps (weight of %d values, bias of %d)"
+                         % (maps.shape[1], maps.shape[2], w5.numel(), b5.numel()))
+    weights = torch.empty(map_image.numel(), dtype=torch.float32, device=maps.device)
+    check(_lib.load().dn_agent_combine_lists(_ptr(z4), _ptr(w5), _ptr(b5), _ptr(maps), _ptr(first), _ptr(pair_index),
+                                             _ptr(map_image), _ptr(ego_out), ego_out.numel(), hw, c, _ptr(weights),
+                                             _ptr(fused), _stream()), "dn_agent_combine_lists")
+    return weights
+
+
+def agent_combine_lists_backward(dfused, weights, maps, first, map_image, ego_out, dmaps):
+    """writes one row of dmaps per listed map: w_k * dfused of its ego (the weights are constants, as upstream's)"""
+    hw, c = maps.shape[1] * maps.shape[2], maps.shape[3]
+    check(_lib.load().dn_agent_combine_lists_backward(
+        _ptr(dfused), _ld(dfused), _ptr(weights), _ptr(first), _ptr(map_image), _ptr(ego_out), ego_out.numel(), hw, c,
+        _ptr(dmaps), _stream()), "dn_agent_combine_lists_backward")
+    return dmaps
+
+
 def warp_list(src, poses, src_image, out=None):
     """src [M, h, w, c]; poses [n, 4, 4]; src_image [n] int32 -> warped [n, h, w, c]"""
     _need_gpu(src, poses, src_image)

@@ -551,6 +551,43 @@ int dn_disco_fuse_mlp_fm(const float* feat, const float* warped_fm, const int32_
                          int only_v2i, int ego_first, int ego_count, void* fused_sp,
                          float* fused_nhwc, float* weights_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * `--com agent` (dn_version 149) -- upstream AgentWiseWeightedFusion over FusionBase.forward (recalled
+ * from upstream, not pinned against its source): ONE scalar weight per agent of the ego's list, softmax over the list,
+ * weighted sum.  The weight net is PixelWeightedFusionSoftmax's four 1x1 layers plus conv1_5 = Conv2d(1, 1, (h, w)), which
+ * turns the score map into one scalar.  Upstream builds torch.tensor(list of scalars): the weights are detached, so the net
+ * is never trained; this library keeps that (include/disconet_train.h :: dn_agent_combine_lists).
+ * Two launches behind dn_warp_neighbors / dn_warp_neighbors_fm (disconet_amd/csrc/agent_fuse.hip): no atomics, no host
+ * synchronisation, graph-capturable; the same bits from run to run and in every launch form of dn_fuse_mlp_set_waves.
+ *   feat, warped, num_agent, p, batch, agents, hw, c, only_v2i, ego_first, ego_count: as dn_disco_fuse_mlp;
+ *   warped_fm != 0: `warped` is dn_warp_neighbors_fm's form (hw % 32 == 0)
+ *   w5 [hw] = conv1_5.weight [1][1][h][w] (its kernel is the exchanged map's own size: pixel p = y * w + x), b5 [1]
+ *   workspace: dn_agent_fuse_workspace_bytes(batch, agents, ego_count, hw) bytes, 16-byte aligned, owned by the caller;
+ *              written and read inside the call, nothing is kept in it
+ *   fused [ego_count*B][hw][c] float32 NHWC, image (i - ego_first) * B + b
+ *   agent_weights (may be NULL) [B][ego_count][A]: w_k in list order, 0 in unused slots and for a padded ego
+ * For scene b with n = clamp(num_agent[b], 0, A) and ego i < n the list is dn_fuse_reduce's: entry 0 the ego's own map,
+ * then warp(j -> i) for the live j != i ascending (only_v2i drops the pairs with i != 0 and j != 0); L entries.
+ *   scores   s_k[p] = relu(W4 . h3 + b4): exactly dn_disco_fuse_mlp's layers 1-4 on (ego, map_k) -- the same packed weights,
+ *            the same folded eval-mode BatchNorm, the self pair (ego, ego) as entry 0
+ *   scalar   a_k = relu(b5 + sum_p w5[p] * s_k[p]) in fp32, every product rounded before it is added, in this order: the
+ *            pixels in tiles of 32 consecutive p (a pixel past hw contributes +0); within a tile a binary tree over the
+ *            pixel's index l in the tile -- l with l + 16, then with l + 8, + 4, + 2, + 1; the tiles' sums one after the
+ *            other, ascending, starting from tile 0's sum; then + b5, then the ReLU
+ *   softmax  m = max_k a_k;  e_k = expf(a_k - m);  w_k = e_k / sum e, the sum in list order, fp32, IEEE division
+ *   fused    sum_k w_k * map_k: each product rounded to fp32 (no fused multiply-add) and added in list order, starting
+ *            from the first product.  A list of one entry has w_0 = 1: the ego's own bits.
+ * A padded ego (i >= n) passes through, the same bits; a dead neighbour's map is never read; agents == 1 copies (no score
+ * launch).  DN_ERR_ARG, before any launch: a null pointer, a bad ego range, a c that dn_fuse_mlp_supported refuses, more
+ * than 8 agents, a workspace that is too small, unaligned buffers.
+ * fusion_modes.host_agent_fuse states this in plain torch on the CPU.
+ * ------------------------------------------------------------------------ */
+size_t dn_agent_fuse_workspace_bytes(int batch, int agents, int ego_count, int hw);
+int dn_agent_fuse(const float* feat, const float* warped, int warped_fm, const int32_t* num_agent,
+                  const dn_fuse_mlp_params* p, const float* w5, const float* b5, int batch, int agents, int hw, int c,
+                  int only_v2i, int ego_first, int ego_count, void* workspace, size_t workspace_bytes, float* fused,
+                  float* agent_weights, void* stream);
+
 
 /* ------------------------------------------------------------------------
  * Detection decode (first step after the hot path).

@@ -274,6 +274,22 @@ int dn_fuse_reduce_lists_backward(const float* dfused, int ld, const float* maps
                                   const int32_t* first, const int32_t* map_image, const int32_t* ego_out, int n_egos,
                                   int hw, int c, int mode, float* dmaps, void* stream);
 
+/* `--com agent` over the training lists (disconet_hip.h :: dn_agent_fuse: the same scalars, the same order of every sum):
+ * for ego e in [0, n_egos) the entries first[e] .. first[e+1) of (pair_index, map_image), the ego's own map first;
+ *   s_k = relu(z4[pair_k]) [hw];  a_k = relu(b5 + sum_p w5[p] s_k[p]);  w_k = softmax over the list;
+ *   fused[ego_out[e]] = sum_k w_k * maps[map_image_k], product by product in list order (no fused multiply-add)
+ * weights: one float per list entry, at the entry's place in the lists (first[n_egos] floats).  pair_index < 0: an ego
+ * that is not live, alone in its list: weight 1, its map passes through.  Two launches; lists of at most 16 entries. */
+int dn_agent_combine_lists(const float* z4, const float* w5, const float* b5, const float* maps, const int32_t* first,
+                           const int32_t* pair_index, const int32_t* map_image, const int32_t* ego_out, int n_egos, int hw,
+                           int c, float* weights, float* fused, void* stream);
+/* backward: dmaps[map_image_k] = w_k * dfused[ego_out[e]] (assignment: every map is in one list, every row is written
+ * exactly once).  The weights are constants, as upstream's torch.tensor(list of scalars) makes them: nothing flows into
+ * z4, w5 or b5.  ld: row stride of dfused in floats, a multiple of 4. */
+int dn_agent_combine_lists_backward(const float* dfused, int ld, const float* weights, const int32_t* first,
+                                    const int32_t* map_image, const int32_t* ego_out, int n_egos, int hw, int c,
+                                    float* dmaps, void* stream);
+
 /* Backward of dn_warp_neighbors for a list of warps: the gradient of warp w (source image
  * src_image[w] in [0, n_src_images), 4x4 pose at poses + 16 * w, row-major, neighbour -> ego) goes
  * back through both bilinear passes and is ADDED to d_src[src_image[w]].  scratch: n_warps maps.

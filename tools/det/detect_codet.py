@@ -3,7 +3,7 @@
 forward the detection tail on the GPU (postprocess.detect: top-k by score, rotated greedy NMS, one batched call).
 Prints per frame the forward time, the per-image detection counts and the tail's device time (events).
 
-    python tools/det/detect_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+    python tools/det/detect_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T]
 
 --com lowerbound: no collaboration, every agent detects from its own view.  --com late: that detector (pass a lowerbound
@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config  # noqa: E402
+from disconet_amd import ALL_DET_COM_MODES, Config  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
 from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
@@ -32,7 +32,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the detection counts")
-    require_com(args, DET_COM_MODES)
+    require_com(args, ALL_DET_COM_MODES)
     num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)

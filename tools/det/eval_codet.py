@@ -3,7 +3,7 @@
 detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothing read back -- and after the last frame
 mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
 
-    python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
+    python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, postprocess  # noqa: E402
+from disconet_amd import ALL_DET_COM_MODES, Config, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch  # noqa: E402
 from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
@@ -45,7 +45,7 @@ def main(argv=None):
     args = build_eval_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
-    require_com(args, DET_COM_MODES)
+    require_com(args, ALL_DET_COM_MODES)
     num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)

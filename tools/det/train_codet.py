@@ -7,7 +7,7 @@ resumes from `--resume` / `--resume_teacher` if given, and runs CoDetModule.step
 scenes and targets (there is no V2X-Sim data in this environment) through the MI355X path,
 writing `epoch_N.pth` with the reference's checkpoint keys.
 
-    python tools/det/train_codet.py --com disco|sum|mean|max|lowerbound [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
+    python tools/det/train_codet.py --com disco|sum|mean|max|lowerbound|agent [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
         [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
         [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4]
@@ -39,12 +39,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
-from disconet_amd import COM_MODES, CoDetModule, Config, TeacherNet, build_model, load_checkpoint  # noqa: E402
+from disconet_amd import COM_MODES, PARAM_COM_MODES, CoDetModule, Config, TeacherNet, build_model, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
 from codet_common import agents_of, require_com  # noqa: E402
 
 
-TRAIN_COM_MODES = COM_MODES + ("lowerbound",)
+TRAIN_COM_MODES = COM_MODES + ("lowerbound",) + PARAM_COM_MODES
 SCENE_BOXES = 64      # --targets boxes: boxes per scene (eval_codet.py --gt scene builds the same scenes)
 
 

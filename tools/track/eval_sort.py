@@ -10,7 +10,7 @@ per image.  Behind those, HOTA with its detection, association and localisation 
 AssRe, AssPr, LocA, HOTA(0), LocA(0), HOTALocA(0)): tracking.Hota.update() runs in the same captured step and logs every
 frame on the device (--max_frames slots), and Hota.compute() matches all logged frames of all images at once there.
 
-    python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+    python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late|agent [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
         [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES]
 
@@ -34,7 +34,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, tracking  # noqa: E402
+from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
 from codet_common import add_sort_flags, add_tail_flags, agents_of, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
@@ -56,7 +56,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.max_frames is None:
         args.max_frames = max(args.frames, 1)
-    require_com(args, DET_COM_MODES)
+    require_com(args, ALL_DET_COM_MODES)
     num_agent = agents_of(args)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)

@@ -5,7 +5,7 @@ nothing is copied to the host but the reported tracks that are written out), and
 (`frame,id,x1,y1,w,h,score,-1,-1,-1`, rectangles in BEV pixels: scale = 1 / voxel_size[0]) lands under --logpath:
 tracks_agent<a>.txt, or tracks_agent<a>_scene<b>.txt for --batch > 1 (every image is its own sequence).
 
-    python tools/track/sort_codet.py --com disco|sum|mean|max|lowerbound|late [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 8] \
+    python tools/track/sort_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 8] \
         [--logpath logs/track] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--source net|boxes]
 
 --source net (default): test_codet.py's model and synthetic scenes (disconet_amd.Detector: the model, the checkpoint and
@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools", "det"))
 sys.path.insert(0, HERE)
 
-from disconet_amd import DET_COM_MODES, Config, tracking  # noqa: E402
+from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
 from codet_common import add_sort_flags, add_tail_flags, agents_of, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
@@ -40,7 +40,7 @@ def main(argv=None):
     add_sort_flags(ap)
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
-    require_com(args, DET_COM_MODES)
+    require_com(args, ALL_DET_COM_MODES)
     num_agent = agents_of(args)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
