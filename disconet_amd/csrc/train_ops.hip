@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "agent_device.h"
+#include "decode_device.h"
 #include "disconet_train.h"
 #include "dn_internal.h"
 
@@ -1123,6 +1124,151 @@ det_loss_v4_kernel(const float* __restrict__ cls, const float* __restrict__ labe
   }
 }
 
+// ---- corner localisation loss (include/disconet_train.h :: dn_det_loss_corner) ----
+// One assigned anchor: the predicted codes p and the target codes t are decoded against the anchor row a (dn::decode_box,
+// the library's one decode expression), each box gives its four corners in postprocess._corners' order with the RAW
+// (sin, cos) pair, and the value is the sum of the four corner distances.  g[0..5] = scale * d(value)/d(p) by the chain rule
+// through the corners (d/d centre, d/d size, d/d pair) and the decode.  A distance of exactly 0 contributes no gradient
+// (torch's sub-gradient of norm); nothing is clamped, a NaN or inf goes through.  The one formula of both kernels below: their
+// dloc agree bit for bit.
+__device__ __forceinline__ float corner_one(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ t,
+                                            float scale, float* __restrict__ g) {
+  // no fused multiply-adds in THIS body (decode_box keeps its own): with loc == targets bitwise the two boxes' corner
+  // expressions must round alike so that their difference is exactly 0, and both kernels must see the same roundings
+#pragma clang fp contract(off)
+  float bp[6], bt[6];
+  dn::decode_box(a, p, bp);
+  dn::decode_box(a, t, bt);
+  const float hw = 0.5f * bp[2], hh = 0.5f * bp[3], s = bp[4], c = bp[5];
+  const float tw = 0.5f * bt[2], th = 0.5f * bt[3], ts = bt[4], tc = bt[5];
+  float sum = 0.f, gx = 0.f, gy = 0.f, gw = 0.f, gh = 0.f, gs = 0.f, gc = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {      // (-,-), (+,-), (+,+), (-,+)
+    const float sx = (k == 1 || k == 2) ? 1.f : -1.f, sy = k >= 2 ? 1.f : -1.f;
+    const float dx = sx * hw, dy = sy * hh, tdx = sx * tw, tdy = sy * th;
+    // corner - corner with the two centres (up to 32 m, half an ulp = 1.9e-6) subtracted from each other first and the rotated
+    // offsets (a few metres) apart from them: the sum the contract states, without a second rounding at the centres' magnitude
+    // -- d / |d| below loses accuracy like 1 / |d|
+    const float ex = (bp[0] - bt[0]) + ((dx * c - dy * s) - (tdx * tc - tdy * ts));
+    const float ey = (bp[1] - bt[1]) + ((dx * s + dy * c) - (tdx * ts + tdy * tc));
+    const float d = sqrtf(ex * ex + ey * ey);
+    sum += d;
+    const float ux = d == 0.f ? 0.f : ex / d, uy = d == 0.f ? 0.f : ey / d;
+    gx += ux;
+    gy += uy;
+    gw += sx * (c * ux + s * uy);      // d corner / d w = (sx / 2) (cos, sin)
+    gh += sy * (c * uy - s * ux);      // d corner / d h = (sy / 2) (-sin, cos)
+    gc += dx * ux + dy * uy;           // d corner / d cos = (dx, dy)
+    gs += dx * uy - dy * ux;           // d corner / d sin = (-dy, dx)
+  }
+  g[0] = scale * (a[2] * gx);
+  g[1] = scale * (a[3] * gy);
+  g[2] = scale * (hw * gw);            // d w / d p2 = w
+  g[3] = scale * (hh * gh);
+  g[4] = scale * (a[5] * gs - a[4] * gc);
+  g[5] = scale * (a[4] * gs + a[5] * gc);
+  return sum;
+}
+
+// workgroup reduction of the two loss sums, one atomic per workgroup and loss (det_loss_kernel's)
+__device__ inline void corner_loss_sums(double l_cls, double l_loc, float inv_norm, double* __restrict__ losses) {
+  __shared__ double red[2][256];
+  red[0][threadIdx.x] = l_cls;
+  red[1][threadIdx.x] = l_loc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + s];
+      red[1][threadIdx.x] += red[1][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    atomic_add_f64(&losses[0], red[0][0] * inv_norm);
+    atomic_add_f64(&losses[1], red[1][0] * inv_norm);
+  }
+}
+
+// Per-anchor form (odd n or unaligned tensors): a lane per anchor.  loc / targets / anchors are read only under mask != 0 --
+// positives are well under 1 % of the anchors, so the wave runs corner_one for the few lanes that have one (a lane-level
+// branch: the other lanes idle for ~150 instructions in the waves that hold a positive) and the kernel streams cls, labels,
+// mask in and dcls, dloc out.  An unmasked dloc row is written as zeros here: no memset in front.
+__global__ void __launch_bounds__(256)
+det_loss_corner_kernel(const float* __restrict__ cls, const float* __restrict__ labels, const float* __restrict__ loc,
+                       const float* __restrict__ targets, const float* __restrict__ mask, const float* __restrict__ anchors,
+                       long per_image, long n, float alpha, float gamma, float inv_norm, double* __restrict__ losses,
+                       float* __restrict__ dcls, float* __restrict__ dloc) {
+  double l_cls = 0.0, l_loc = 0.0;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float d0, d1;
+    focal_one(cls[2 * i], cls[2 * i + 1], labels[2 * i], labels[2 * i + 1], alpha, gamma, inv_norm, d0, d1, l_cls);
+    dcls[2 * i] = d0;
+    dcls[2 * i + 1] = d1;
+    const float mk = mask[i];
+    float g[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (mk != 0.f)
+      l_loc += (double)(mk * corner_one(anchors + 6 * (i % per_image), loc + 6 * i, targets + 6 * i, mk * inv_norm, g));
+#pragma unroll
+    for (int k = 0; k < 6; ++k) dloc[6 * i + k] = g[k];
+  }
+  corner_loss_sums(l_cls, l_loc, inv_norm, losses);
+}
+
+// The same on FLAT float4 streams, det_loss_v4_kernel's discipline (n even, 16-byte aligned cls / labels / dcls / dloc).
+// Loop A is det_loss_v4_kernel's: two anchors' logits / labels per float4.  Loop B writes dloc four consecutive elements
+// per lane: element 4 i is code r = 4 i % 6 in {0, 2, 4} of anchor a0 = 4 i / 6, so the float4 holds codes r .. of a0 and,
+// for r = 4 only, codes 0, 1 of a0 + 1.  A lane whose anchors are unmasked stores zeros; one that meets a masked anchor
+// runs corner_one for it and keeps its own codes (an anchor's six codes lie in two float4s: two lanes compute it, the one
+// that holds code 0 adds the value).
+__global__ void __launch_bounds__(256)
+det_loss_corner_v4_kernel(const float* __restrict__ cls, const float* __restrict__ labels, const float* __restrict__ loc,
+                          const float* __restrict__ targets, const float* __restrict__ mask,
+                          const float* __restrict__ anchors, long per_image, long n, float alpha, float gamma, float inv_norm,
+                          double* __restrict__ losses, float* __restrict__ dcls, float* __restrict__ dloc) {
+  double l_cls = 0.0, l_loc = 0.0;
+  const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  for (long i = t0; i < n / 2; i += stride) {
+    const f32x4 z = ldv4(cls + 4 * i), lb = ldv4(labels + 4 * i);
+    float d0, d1, d2, d3;
+    focal_one(z[0], z[1], lb[0], lb[1], alpha, gamma, inv_norm, d0, d1, l_cls);
+    focal_one(z[2], z[3], lb[2], lb[3], alpha, gamma, inv_norm, d2, d3, l_cls);
+    *reinterpret_cast<f32x4*>(dcls + 4 * i) = f32x4{d0, d1, d2, d3};
+  }
+  const long m4 = n * 6 / 4;
+  for (long i = t0; i < m4; i += stride) {
+    const long a0 = (4 * i) / 6;
+    const int r = (int)(4 * i - 6 * a0);
+    f32x4 out = {0.f, 0.f, 0.f, 0.f};
+    const float mk0 = mask[a0];
+    if (mk0 != 0.f) {
+      float g[6];
+      const float v = corner_one(anchors + 6 * (a0 % per_image), loc + 6 * a0, targets + 6 * a0, mk0 * inv_norm, g);
+      if (r == 0) {
+        out = f32x4{g[0], g[1], g[2], g[3]};
+        l_loc += (double)(mk0 * v);
+      } else if (r == 2) {
+        out = f32x4{g[2], g[3], g[4], g[5]};
+      } else {
+        out[0] = g[4];
+        out[1] = g[5];
+      }
+    }
+    if (r == 4) {      // (4 i + 3 < 6 n: anchor a0 + 1 exists)
+      const float mk1 = mask[a0 + 1];
+      if (mk1 != 0.f) {
+        float g[6];
+        const float v = corner_one(anchors + 6 * ((a0 + 1) % per_image), loc + 6 * (a0 + 1), targets + 6 * (a0 + 1),
+                                   mk1 * inv_norm, g);
+        out[2] = g[0];
+        out[3] = g[1];
+        l_loc += (double)(mk1 * v);
+      }
+    }
+    *reinterpret_cast<f32x4*>(dloc + 4 * i) = out;
+  }
+  corner_loss_sums(l_cls, l_loc, inv_norm, losses);
+}
+
 // b1 / b2 and their complements c1 = 1 - b1, c2 = 1 - b2 arrive rounded from double each on its own (dn_adam_step): 1.f - b2 of a
 // float-rounded 0.999 is off by 1.3e-5 of itself, which reached the update at ~3e-6 of its size.
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -1610,6 +1756,26 @@ extern "C" int dn_det_loss(const float* cls, const float* labels, const float* l
     hipLaunchKernelGGL(det_loss_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, s, cls, labels, loc, targets,
                        mask, n, code, alpha, gamma, sigma, 1.f / norm, losses, dcls, dloc);
   return dn::check_launch("det_loss_kernel");
+}
+
+extern "C" int dn_det_loss_corner(const float* cls, const float* labels, const float* loc, const float* targets,
+                                  const float* mask, const float* anchors, long per_image, long n, float alpha, float gamma,
+                                  float norm, double* losses, float* dcls, float* dloc, void* stream) {
+  DN_REQUIRE(cls && labels && loc && targets && mask && anchors && losses && dcls && dloc, "corner loss: null pointer");
+  DN_REQUIRE(n > 0 && per_image > 0 && n % per_image == 0 && norm > 0.f,
+             "corner loss: bad arguments (n = %ld anchors, %ld per image)", n, per_image);
+  hipStream_t s = (hipStream_t)stream;
+  if (dn::zero_fill(losses, 2 * sizeof(double), s) != hipSuccess)
+    return dn::fail(DN_ERR_LAUNCH, "corner loss: memset failed");
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  // dn_det_loss' rule (code = 6: n even makes 6 n a multiple of 4)
+  if (n % 2 == 0 && al16(cls) && al16(labels) && al16(loc) && al16(targets) && al16(dcls) && al16(dloc))
+    hipLaunchKernelGGL(det_loss_corner_v4_kernel, dim3(grid_for(n * 6 / 4, 4096)), dim3(256), 0, s, cls, labels, loc, targets,
+                       mask, anchors, per_image, n, alpha, gamma, 1.f / norm, losses, dcls, dloc);
+  else
+    hipLaunchKernelGGL(det_loss_corner_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, s, cls, labels, loc, targets, mask,
+                       anchors, per_image, n, alpha, gamma, 1.f / norm, losses, dcls, dloc);
+  return dn::check_launch("det_loss_corner_kernel");
 }
 
 extern "C" int dn_adam_step(float* p, const float* g, float* m, float* v, long n, double lr,

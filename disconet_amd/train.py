@@ -36,6 +36,7 @@ _WGRAD_MATH_DEFAULT = "sp"        # the weight gradients of the layers dn_conv_w
 _WGRAD_X_LIFT = 16.0              # power-of-two lift of the activations in that kernel (post-BatchNorm maps: |x| << 4094)
 _FWD_MATH_DEFAULT = "sp"          # round 6: the training forward's 3x3 / 1x1 convs on the inference engine's split-f16 LDS-DMA kernels
 _MOMENTUM = 0.1
+LOSS_TYPES = ("faf_loss", "corner_loss")      # Config.loss_type values CoDetModule trains with (upstream's two branches for code_type "faf")
 _LIFT_REFRESH_STEPS = 64          # a measured power-of-two lift (of a weight, of a layer's dz) is good for this many steps either way
 _LIFT_TEMPORARIES_MAX = 256       # entries of the weight-lift table beyond which a parentless temporary starts it over
 _PACK_KEEP_FORWARDS = 8           # a packed weight form nobody asked for in this many forwards leaves the one-launch set
@@ -1176,7 +1177,9 @@ class CoDetModule:
     step(data, batch_size) -> loss values, with the losses, the backward and Adam on the HIP path.
     kd_flag = 1: `teacher` (disconet_amd.TeacherNet, frozen, eval) sees data["bev_seq_teacher"] and
     kd_weight * sum of KLDiv(log_softmax(student), softmax(teacher)) over x5, x6, x7 and the fused
-    layer-3 map (vs the teacher's x3) joins the loss."""
+    layer-3 map (vs the teacher's x3) joins the loss.
+    config.loss_type (LOSS_TYPES): "faf_loss" -- focal + smooth-L1 on the box codes, also without a config; "corner_loss" --
+    focal + the corner distances of the decoded boxes (train_ops.det_loss_corner), step() then reads data["anchors"]."""
 
     def __init__(self, model, teacher=None, config=None, optimizer=None, kd_flag=0, lr=1e-3,
                  alpha=0.25, gamma=2.0, sigma=3.0, shard=None, dgrad_math=None, wgrad_math=None):
@@ -1189,6 +1192,14 @@ class CoDetModule:
         flat gradient) add up to the un-sharded step's."""
         if kd_flag and teacher is None:
             raise ValueError("kd_flag = 1 needs the teacher network")
+        # upstream's loss_calculator has two branches for code_type "faf": "faf_loss" (focal + smooth-L1 on the codes, det_loss)
+        # and "corner_loss" (focal + the corner distances of the decoded boxes, det_loss_corner; step needs data["anchors"])
+        self.loss_type = getattr(config, "loss_type", "faf_loss") if config is not None else "faf_loss"
+        if self.loss_type not in LOSS_TYPES:
+            raise ValueError("config.loss_type must be one of %s (got %r)" % (" / ".join(repr(t) for t in LOSS_TYPES), self.loss_type))
+        if self.loss_type == "corner_loss" and getattr(config, "code_type", "faf") != "faf":
+            raise NotImplementedError("loss_type 'corner_loss' is built for code_type 'faf' only (got %r): upstream's corner_1 .. "
+                                      "corner_3 box codes are not" % config.code_type)
         self.model, self.teacher, self.kd_flag = model, teacher, int(bool(kd_flag))
         if self.kd_flag:
             teacher.eval()
@@ -1213,6 +1224,20 @@ class CoDetModule:
             self.engine.lr *= gamma
         return self.engine.lr
 
+    @staticmethod
+    def _corner_anchors(data, loc):
+        """data["anchors"] as the [per_image, 6] float32 rows the corner loss reads: postprocess.make_anchors' [H, W, A, 6], or
+        that with a leading image dimension of identical copies (upstream's loader stacks one per sample): the first image's"""
+        if "anchors" not in data:
+            raise KeyError("loss_type 'corner_loss' decodes every assigned anchor: step() needs data['anchors'] "
+                           "(postprocess.make_anchors(config), [H, W, A, 6])")
+        anchors = data["anchors"]
+        per_image = loc.numel() // 6 // loc.shape[0]
+        if anchors.shape[-1] != 6 or anchors.numel() % (6 * per_image):
+            raise ValueError("data['anchors'] %s does not hold the %d anchor rows of 6 of one image" % (tuple(anchors.shape), per_image))
+        rows = anchors.reshape(-1, per_image, 6)[0]
+        return rows.to(device=loc.device, dtype=torch.float32).contiguous()
+
     def step(self, data, batch_size, update=True):
         """update = False: forward, losses and every gradient (engine.flat_g), but no gradient exchange and no Adam step --
         tests, and the calibration pass of dgrad_math = "sp" (the first backward measures the gradient maps' lifts)"""
@@ -1225,11 +1250,17 @@ class CoDetModule:
             code = res["loc"].shape[-1]
             dev = bev_seq.device
             f32 = lambda t, shape: t.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
-            losses, dcls, dloc = T.det_loss(
-                res["cls"].reshape(-1, 2), f32(data["labels"], (-1, 2)), res["loc"].reshape(-1, code),
-                f32(data["reg_targets"], (-1, code)), f32(data["reg_loss_mask"], (-1,)),
-                norm=bev_seq.shape[0] * (eng.shard.world if eng.shard is not None else 1),      # the reference's N: all A * B images
-                alpha=self.alpha, gamma=self.gamma, sigma=self.sigma)
+            norm = bev_seq.shape[0] * (eng.shard.world if eng.shard is not None else 1)      # the reference's N: all A * B images
+            if self.loss_type == "corner_loss":
+                losses, dcls, dloc = T.det_loss_corner(
+                    res["cls"].reshape(-1, 2), f32(data["labels"], (-1, 2)), res["loc"].reshape(-1, code),
+                    f32(data["reg_targets"], (-1, code)), f32(data["reg_loss_mask"], (-1,)),
+                    self._corner_anchors(data, res["loc"]), norm=norm, alpha=self.alpha, gamma=self.gamma)
+            else:
+                losses, dcls, dloc = T.det_loss(
+                    res["cls"].reshape(-1, 2), f32(data["labels"], (-1, 2)), res["loc"].reshape(-1, code),
+                    f32(data["reg_targets"], (-1, code)), f32(data["reg_loss_mask"], (-1,)),
+                    norm=norm, alpha=self.alpha, gamma=self.gamma, sigma=self.sigma)
             dkd, kd = None, None
             if self.kd_flag:
                 kd_weight = float(data["kd_weight"]) if "kd_weight" in data else 1e5

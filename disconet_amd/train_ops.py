@@ -494,6 +494,64 @@ def det_loss(cls, labels, loc, targets, mask, norm, alpha=0.25, gamma=2.0, sigma
     return losses, dcls, dloc
 
 
+def _anchor_rows(anchors, n):
+    """anchors [per_image, 6] or [H, W, A, 6] -> ([per_image, 6], per_image); ValueError unless n is a whole number of images"""
+    if anchors.dim() < 2 or anchors.shape[-1] != 6:
+        raise ValueError("anchors must be [per_image, 6] or [H, W, A, 6] rows (x, y, w, h, sin, cos), got %s" % (tuple(anchors.shape),))
+    rows = anchors.reshape(-1, 6)
+    per_image = rows.shape[0]
+    if per_image == 0 or n % per_image:
+        raise ValueError("%d anchors are not a whole number of images of %d anchors" % (n, per_image))
+    return rows, per_image
+
+
+def det_loss_corner(cls, labels, loc, targets, mask, anchors, norm, alpha=0.25, gamma=2.0):
+    """det_loss with the corner localisation loss (Config.loss_type = "corner_loss"; include/disconet_train.h ::
+    dn_det_loss_corner; host_corner_loss below states the localisation half) -> (losses [2] float64 = (cls, loc), dcls, dloc).
+    loc, targets [n, 6]; anchors [per_image, 6] or [H, W, A, 6] (postprocess.make_anchors): anchor i uses row i % per_image."""
+    if not all(t.is_cuda for t in (cls, labels, loc, targets, mask, anchors)):
+        raise ValueError("det_loss_corner: every tensor must be on the GPU (there is no CPU path; host_corner_loss is the reference)")
+    if loc.shape[-1] != 6:
+        raise ValueError("det_loss_corner: the corner loss is defined on the 6 box codes of code_type 'faf', got %d" % loc.shape[-1])
+    n = loc.numel() // 6
+    assert cls.numel() == 2 * n and labels.numel() == 2 * n and mask.numel() == n and targets.numel() == 6 * n
+    rows, per_image = _anchor_rows(anchors, n)
+    rows = rows.contiguous()
+    losses = torch.empty(2, dtype=torch.float64, device=cls.device)
+    dcls, dloc = torch.empty_like(cls), torch.empty_like(loc)
+    check(_lib.load().dn_det_loss_corner(_ptr(cls), _ptr(labels), _ptr(loc), _ptr(targets), _ptr(mask), _ptr(rows), per_image, n,
+                                         float(alpha), float(gamma), float(norm), _ptr(losses), _ptr(dcls), _ptr(dloc), _stream()),
+          "dn_det_loss_corner")
+    return losses, dcls, dloc
+
+
+def host_corner_loss(loc, targets, mask, anchors, norm):
+    """The corner localisation loss in plain torch, any float dtype, differentiable -- the contract of dn_det_loss_corner's
+    loc half and the reference of its tests (upstream CoDetModule.corner_loss for code_type "faf", recalled, not pinned):
+    the MASKED anchors' predicted and target codes are decoded against their anchor row (postprocess.decode's expression),
+    each box gives four corners in postprocess._corners' order and rotation with the raw (sin, cos) pair, and
+        loss = sum_i mask[i] * sum_k |pc[i, k] - tc[i, k]|_2 / norm.
+    Unmasked rows are never touched (boolean indexing, as upstream).  A zero distance has gradient 0 (torch's norm)."""
+    loc, targets = loc.reshape(-1, 6), targets.reshape(-1, 6)
+    mask = mask.reshape(-1)
+    rows, per_image = _anchor_rows(anchors, loc.shape[0])
+    idx = (mask != 0).nonzero().flatten()
+    a = rows.to(loc.dtype)[idx % per_image]
+
+    def corners(t):
+        cx, cy = a[:, 0] + t[:, 0] * a[:, 2], a[:, 1] + t[:, 1] * a[:, 3]
+        w, h = a[:, 2] * torch.exp(t[:, 2]), a[:, 3] * torch.exp(t[:, 3])
+        s, c = a[:, 4] * t[:, 5] + a[:, 5] * t[:, 4], a[:, 5] * t[:, 5] - a[:, 4] * t[:, 4]
+        dx = torch.stack([-w, w, w, -w], 1) / 2
+        dy = torch.stack([-h, -h, h, h], 1) / 2
+        x = dx * c[:, None] - dy * s[:, None] + cx[:, None]
+        y = dx * s[:, None] + dy * c[:, None] + cy[:, None]
+        return torch.stack([x, y], -1)                       # [m, 4, 2]
+
+    dist = torch.linalg.vector_norm(corners(loc[idx]) - corners(targets[idx].to(loc.dtype)), dim=-1)
+    return (mask[idx].to(loc.dtype) * dist.sum(-1)).sum() / norm
+
+
 def kd_kl_loss(student, teacher, kd_weight, loss, zero=False, norm_rows=None):
     """student, teacher [..., c] dense NHWC maps of equal shape; adds kd_weight * KLDiv (mean over
     all elements) to loss[0] (float64, zeroed first if zero) and returns d(term)/d(student).

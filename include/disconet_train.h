@@ -314,6 +314,30 @@ int dn_det_loss(const float* cls, const float* labels, const float* loc, const f
                 const float* mask, long n, int code, float alpha, float gamma, float sigma,
                 float norm, double* losses, float* dcls, float* dloc, void* stream);
 
+/* The same call with the CORNER localisation loss (Config.loss_type = "corner_loss"; dn_version 150) in place of the
+ * smooth-L1: upstream coperception/utils/CoDetModule.py :: corner_loss over bev_box_decode_torch and
+ * center_to_corner_box2d_torch for code_type "faf" -- RECALLED, NOT PINNED: upstream's source was not at hand, the contract
+ * below is this library's (disconet_amd.train_ops.host_corner_loss states it in torch).
+ *   cls, labels [n, 2], mask [n] as above;  loc, targets [n, 6] box codes;  anchors [per_image, 6] rows (x, y, w, h, sin, cos)
+ *   as postprocess.make_anchors makes them; anchor i uses the row i % per_image (n % per_image == 0).
+ *   1. decode: loc[i] and targets[i] are both decoded against the anchor row a with dn_decode_boxes' expression:
+ *      centre (a0 + t0 a2, a1 + t1 a3), size (a2 exp t2, a3 exp t3), pair sin = a4 t5 + a5 t4, cos = a5 t5 - a4 t4.
+ *   2. corners: local offsets (+-w/2, +-h/2) in the order (-,-) (+,-) (+,+) (-,+), x = dx cos - dy sin + cx,
+ *      y = dx sin + dy cos + cy with the RAW pair (no normalisation: the loss also pulls the pair's length to 1).
+ *   3. loss_loc = sum_i mask[i] * sum_{k<4} |pc[i,k] - tc[i,k]|_2 / norm;  dloc = d loss_loc / d loc through 2. and 1.
+ *      A corner at distance exactly 0 contributes gradient 0 (never 0/0).  An anchor with mask[i] == 0 contributes nothing,
+ *      its dloc row is written as zeros (all rows are written: no memset is needed in front) and its loc / targets / anchor
+ *      row are NOT READ: a NaN there does not reach any output.  Nothing is clamped: a non-finite value under mask != 0 gives
+ *      a non-finite result.
+ *   4. loss_cls and dcls are dn_det_loss's, bit for bit, for the same cls / labels / alpha / gamma / norm.
+ * losses: 2 doubles (cls, loc), zeroed by the call, one f64 atomic per workgroup and loss: the reported scalars may differ in
+ * their last bits from run to run; dcls and dloc involve no atomics and are the same bits every run, and the same bits from
+ * both kernel forms (flat float4 streams for even n and 16-byte aligned cls / labels / loc / targets / dcls / dloc -- dn_det_loss'
+ * rule -- else a lane per anchor). */
+int dn_det_loss_corner(const float* cls, const float* labels, const float* loc, const float* targets,
+                       const float* mask, const float* anchors, long per_image, long n, float alpha,
+                       float gamma, float norm, double* losses, float* dcls, float* dloc, void* stream);
+
 /* Knowledge distillation term of CoDetModule.step (kd_flag = 1): for NHWC maps viewed as
  * [rows, c], nn.KLDivLoss(size_average=True)(log_softmax(student, 1), softmax(teacher, 1)) -- the
  * mean over ALL rows * c elements -- times kd_weight: pass scale = kd_weight / (rows * c).

@@ -10,7 +10,7 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
     python tools/det/train_codet.py --com disco|sum|mean|max|lowerbound|agent [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
         [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
-        [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4]
+        [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4] [--loss_type faf_loss|corner_loss]
 
 --targets synthetic (default): random occupancy and synthetic.make_train_targets (Bernoulli noise per anchor).
 --targets boxes: synthetic.make_box_scene_batch -- scenes whose occupancy shows their ground-truth boxes -- with
@@ -24,6 +24,9 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
 
     Without --resume_teacher the teacher keeps its initial weights: the distillation target is then meaningless and only
     the plumbing is exercised (the tool says so).  Training the teacher itself is not built yet (TeacherNet is eval() only).
+
+--loss_type faf_loss (default): focal + smooth-L1 on the box codes.  corner_loss: focal + the corner distances of the decoded
+    boxes (Config.loss_type, train_ops.det_loss_corner); the anchors it decodes against ride in data["anchors"].
 
 Data-parallel: one process per GPU under torch.distributed.run; every rank trains its own
 scenes and the flat gradient buffer is averaged by one RCCL all-reduce per step.
@@ -104,6 +107,8 @@ def build_parser():
     ap.add_argument("--pos_thr", type=float, default=0.6, help="--targets boxes: an anchor is positive from this IoU")
     ap.add_argument("--neg_thr", type=float, default=0.45, help="--targets boxes: an anchor is negative below this IoU")
     ap.add_argument("--scenes", type=int, default=4, help="--targets boxes: the steps cycle through this many scene seeds")
+    ap.add_argument("--loss_type", choices=("faf_loss", "corner_loss"), default="faf_loss",
+                    help="localisation loss: smooth-L1 on the box codes, or the corner distances of the decoded boxes")
     return ap
 
 
@@ -121,6 +126,7 @@ def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, dev
                                      boxes_per_scene=SCENE_BOXES, device=device, teacher=bool(args.kd_flag))
         data = {k: scene[k] for k in ("bev_seq", "trans_matrices", "num_agent")}
         data.update(targets.assign_targets(anchors, scene["gt_boxes"], scene["gt_count"], args.pos_thr, args.neg_thr))
+        data["anchors"] = anchors
         if args.kd_flag:
             data["bev_seq_teacher"] = scene["bev_seq_teacher"]
             data["kd_weight"] = args.kd_weight
@@ -130,6 +136,8 @@ def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, dev
     labels, targets, mask = make_train_targets(n_img, hw, seed=seed)
     data = {"bev_seq": bevs.to(device), "trans_matrices": trans.to(device), "num_agent": na.to(device),
             "labels": labels.to(device), "reg_targets": targets.to(device), "reg_loss_mask": mask.to(device)}
+    if anchors is not None:      # (read by --loss_type corner_loss only)
+        data["anchors"] = anchors
     if args.kd_flag:
         data["bev_seq_teacher"] = make_bevs(args.batch, num_agent, hw, p=0.05).to(device)
         data["kd_weight"] = args.kd_weight
@@ -155,7 +163,7 @@ def main(argv=None):
         import torch.distributed as dist
         dist.init_process_group("nccl")
 
-    config = Config("train", binary=True, only_det=True)
+    config = Config("train", binary=True, only_det=True, loss_type=args.loss_type)
     hw = config.map_dims[0]
     torch.manual_seed(0)
     model = build_model(args.com, config, layer=args.layer, kd_flag=args.kd_flag, num_agent=num_agent,
@@ -182,10 +190,8 @@ def main(argv=None):
     if optimizer_state is not None:
         fafmodule.engine.load_state_dict(optimizer_state)
 
-    anchors = None
-    if args.targets == "boxes":
-        from disconet_amd import postprocess
-        anchors = postprocess.make_anchors(config)
+    from disconet_amd import postprocess
+    anchors = postprocess.make_anchors(config)      # once: the target assignment (--targets boxes) and the corner loss read them
     for epoch in range(start_epoch, start_epoch + args.nepoch):
         t0, running = time.perf_counter(), 0.0
         for it in range(args.steps_per_epoch):
