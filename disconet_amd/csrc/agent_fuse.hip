@@ -10,6 +10,7 @@
 // dn_agent_fuse; the order of every sum is agent_device.h's.
 #include "agent_device.h"
 #include "dn_internal.h"
+#include "ego_list.h"
 
 namespace {
 
@@ -35,8 +36,7 @@ agent_combine_kernel(const float* __restrict__ feat, const float* __restrict__ w
   __shared__ int jl_s[MAX_AGENTS];
   const int out_image = blockIdx.y;                       // (i - ego_first) * batch + b
   const int b = out_image % batch, il = out_image / batch, i = ego_first + il;
-  int live = num_agent[b];
-  live = live < 0 ? 0 : (live < agents ? live : agents);  // a bad count never indexes past the agents
+  const int live = live_count(num_agent, b, agents);
   const int tid = threadIdx.x;
   const size_t quads = (size_t)hw * (c >> 2);
   const float* ego = feat + ((size_t)i * batch + b) * hw * c;
@@ -57,7 +57,7 @@ agent_combine_kernel(const float* __restrict__ feat, const float* __restrict__ w
   // the list, in the reference's order: the ego, then j ascending (workgroup-uniform)
   int n = 1;
   for (int j = 0; j < live; ++j)
-    if (j != i && (!only_v2i || i == 0 || j == 0)) {
+    if (DN_LISTED_LIVE(i, j, only_v2i)) {
       if (tid == 0) jl_s[n] = j;
       ++n;
     }

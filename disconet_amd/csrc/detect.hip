@@ -27,6 +27,7 @@
 
 #include "dn_internal.h"
 #include "decode_device.h"
+#include "ego_list.h"
 #include "rot_iou_device.h"   // Box64, box64, intersection_area: rotated IoU in fp64 (shared with ap_match.hip)
 
 namespace {
@@ -477,13 +478,12 @@ __global__ void __launch_bounds__(kLateThreads) late_gather_sort_kernel(
   const int img = blockIdx.x;                  // (i - ego_first) * batch + b
   const int b = img % batch, i = ego_first + img / batch;
   if (threadIdx.x == 0) {
-    int n = num_agent[b];
-    n = n < 0 ? 0 : (n > agents ? agents : n);
+    const int n = live_count(num_agent, b, agents);
     int len = 0;
     list[len++] = i;
     if (i < n)
       for (int j = 0; j < n; ++j)
-        if (j != i && !(only_v2i && i != 0 && j != 0)) list[len++] = j;
+        if (DN_LISTED_LIVE(i, j, only_v2i)) list[len++] = j;
     for (int p = 0; p < len; ++p) {
       const int c = count[list[p] * batch + b];
       cnt[p] = c < 0 ? 0 : (c > k_in ? k_in : c);

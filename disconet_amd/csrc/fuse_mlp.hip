@@ -25,6 +25,7 @@
 // upstream:coperception/models/det/DiscoNet.py :: DiscoNet.forward (Appx A.5).
 #include "agent_device.h"
 #include "dn_internal.h"
+#include "ego_list.h"
 #include "sp_device.h"
 #include <type_traits>
 
@@ -132,8 +133,7 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
   const int p = tile * 32 + li;
   const bool pvalid = p < a.hw && have;
   const int pc = p < a.hw ? p : a.hw - 1;
-  int live = a.num_agent[b];
-  live = live < 0 ? 0 : (live < a.agents ? live : a.agents);   // never index past the agents that exist
+  const int live = live_count(a.num_agent, b, a.agents);
   const size_t oimg = (size_t)il * a.batch + b;
 
   // A row = this lane's view of one map: piece (ks, r) = 4 floats at p + ks * kss + r * r1.  NHWC rows (the ego map,
@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
   int n = 1;
   jl_s[tw][0] = i;   // NW > 1: every wave writes the same values
   for (int j = 0; j < live; ++j)
-    if (j != i && (!a.only_v2i || i == 0 || j == 0)) jl_s[tw][n++] = j;
+    if (DN_LISTED_LIVE(i, j, a.only_v2i)) jl_s[tw][n++] = j;
   if constexpr (NW > 1 || kWL) __syncthreads();   // list, layer 2-4 weights and affines (kWL: and W1_ego) visible to every wave
   auto row_of = [&](int k) { return k == 0 ? xrow_r : yrow_of(jl_s[tw][k]); };
 

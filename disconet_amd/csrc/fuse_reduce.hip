@@ -16,6 +16,7 @@
 #include "disconet_train.h"
 #include "dn_internal.h"
 
+#include "ego_list.h"
 #include "warp_device.h"
 
 namespace {
@@ -42,46 +43,37 @@ __device__ inline f32x4 finish(const f32x4& acc, int len) {
   return f32x4{acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n};      // IEEE division (x / 1 = x: a list of one)
 }
 
-__device__ inline int live_count(const int32_t* num_agent, int b, int agents) {
-  const int n = num_agent[b];
-  return n < 0 ? 0 : (n > agents ? agents : n);      // a bad count never indexes past the agents
-}
-__device__ inline bool listed(int i, int j, int n_live, int only_v2i) {
-  return j != i && i < n_live && j < n_live && !(only_v2i && i != 0 && j != 0);
-}
-
-// ---- c % 64 == 0: a workgroup owns one 8 x 8 tile x one 64-channel slice of one ego image ------------------------
-constexpr int RT = 8, RQ = RT + 2, RCS = 64;
-typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
-typedef int i32x4r __attribute__((ext_vector_type(4)));
-
+// ---- c % 64 == 0: a workgroup owns one 8 x 8 tile x one 64-channel slice of one ego image.  The tile body is written out
+// here, the steps of warp_device.h :: WarpTile in their order: called through them, this kernel's tap arithmetic is
+// contracted differently (which product of a sum is fused, where 0.5 * x folds into a difference) and its output moves in
+// the last bits against what it has always computed.  A change to WarpTile's steps is made here too.
 template <int MODE>
 __global__ void __launch_bounds__(256)
 fuse_reduce_tiled_kernel(const float* __restrict__ feat, const float* __restrict__ trans,
                          const int32_t* __restrict__ num_agent, int batch, int agents, int h, int w, int c,
                          int only_v2i, int ego_first, int tiles_x, float* __restrict__ fused) {
-  __shared__ f32x4 rot[RQ * RQ][RCS / 4];
-  __shared__ __attribute__((aligned(16))) unsigned tap1_off[RQ * RQ][4];
-  __shared__ __attribute__((aligned(16))) float tap1_w[RQ * RQ][4];
-  __shared__ __attribute__((aligned(16))) int tap2_row[RT * RT][4];
-  __shared__ __attribute__((aligned(16))) float tap2_w[RT * RT][4];
-  const int n_slices = c / RCS;
+  __shared__ f32x4 rot[WARP_Q * WARP_Q][WARP_CS / 4];
+  __shared__ __attribute__((aligned(16))) unsigned tap1_off[WARP_Q * WARP_Q][4];
+  __shared__ __attribute__((aligned(16))) float tap1_w[WARP_Q * WARP_Q][4];
+  __shared__ __attribute__((aligned(16))) int tap2_row[WARP_T * WARP_T][4];
+  __shared__ __attribute__((aligned(16))) float tap2_w[WARP_T * WARP_T][4];
+  const int n_slices = c / WARP_CS;
   const int slice = blockIdx.x % n_slices, tile = blockIdx.x / n_slices;
-  const int tile_x0 = (tile % tiles_x) * RT, tile_y0 = (tile / tiles_x) * RT;
+  const int tile_x0 = (tile % tiles_x) * WARP_T, tile_y0 = (tile / tiles_x) * WARP_T;
   const int out_image = blockIdx.y;                       // (i - ego_first) * batch + b
   const int b = out_image % batch, i = ego_first + out_image / batch;
   const int n_live = live_count(num_agent, b, agents);
   const int tid = threadIdx.x, l = tid & 15;
   const int hw = h * w;
-  const unsigned lane_off = 16u * (slice * (RCS / 4) + l);
+  const unsigned lane_off = 16u * (slice * (WARP_CS / 4) + l);
 
   // the ego's own values: the accumulator (pixels pl = tid / 16 + 16 k of the tile, four channels each)
-  const float* ego = feat + ((size_t)i * batch + b) * hw * c + slice * RCS + 4 * l;
+  const float* ego = feat + ((size_t)i * batch + b) * hw * c + slice * WARP_CS + 4 * l;
   f32x4 acc[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int pl = (tid >> 4) + 16 * k;
-    const int px = tile_x0 + pl % RT, py = tile_y0 + pl / RT;
+    const int px = tile_x0 + pl % WARP_T, py = tile_y0 + pl / WARP_T;
     acc[k] = (px < w && py < h) ? ld4(ego + (size_t)(py * w + px) * c) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int len = 1;
@@ -104,20 +96,20 @@ fuse_reduce_tiled_kernel(const float* __restrict__ feat, const float* __restrict
       }
     }
     __syncthreads();                                      // the previous neighbour's blend has read rot and the tables
-    if (tid < RQ * RQ) {              // pass-1 tap set of rotated pixel q = tid: sample_src's clamped offsets and masked weights
+    if (tid < WARP_Q * WARP_Q) {              // pass-1 tap set of rotated pixel q = tid: sample_src's clamped offsets and masked weights
       const int q = tid;
-      const Bilinear t1 = pass1_taps(t, qx_base + q % RQ, qy_base + q / RQ, w, h);
+      const Bilinear t1 = pass1_taps(t, qx_base + q % WARP_Q, qy_base + q / WARP_Q, w, h);
       const bool x0ok = t1.x0 >= 0 && t1.x0 < w, x1ok = t1.x0 + 1 >= 0 && t1.x0 + 1 < w;
       const bool y0ok = t1.y0 >= 0 && t1.y0 < h, y1ok = t1.y0 + 1 >= 0 && t1.y0 + 1 < h;
       const int x0 = min(max(t1.x0, 0), w - 1), x1 = min(max(t1.x0 + 1, 0), w - 1);
       const int y0 = min(max(t1.y0, 0), h - 1), y1 = min(max(t1.y0 + 1, 0), h - 1);
-      *reinterpret_cast<u32x4r*>(tap1_off[q]) = u32x4r{(unsigned)((y0 * w + x0) * c) * 4u, (unsigned)((y0 * w + x1) * c) * 4u,
+      *reinterpret_cast<u32x4w*>(tap1_off[q]) = u32x4w{(unsigned)((y0 * w + x0) * c) * 4u, (unsigned)((y0 * w + x1) * c) * 4u,
                                                         (unsigned)((y1 * w + x0) * c) * 4u, (unsigned)((y1 * w + x1) * c) * 4u};
       *reinterpret_cast<f32x4*>(tap1_w[q]) = f32x4{(y0ok && x0ok) ? t1.w_nw : 0.f, (y0ok && x1ok) ? t1.w_ne : 0.f,
                                                    (y1ok && x0ok) ? t1.w_sw : 0.f, (y1ok && x1ok) ? t1.w_se : 0.f};
-    } else if (tid >= 128 && tid < 128 + RT * RT) {       // pass-2 tap set of output pixel pl (a wave of its own)
+    } else if (tid >= 128 && tid < 128 + WARP_T * WARP_T) {       // pass-2 tap set of output pixel pl (a wave of its own)
       const int pl = tid - 128;
-      const Bilinear t2 = pass2_taps(t, tile_x0 + pl % RT, tile_y0 + pl / RT, w, h);
+      const Bilinear t2 = pass2_taps(t, tile_x0 + pl % WARP_T, tile_y0 + pl / WARP_T, w, h);
       const float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
       int row[4];
       float wk[4];
@@ -125,18 +117,18 @@ fuse_reduce_tiled_kernel(const float* __restrict__ feat, const float* __restrict
       for (int k = 0; k < 4; ++k) {
         const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
         const bool qok = qx >= 0 && qx < w && qy >= 0 && qy < h;
-        const int lx = min(max(qx - qx_base, 0), RQ - 1), ly = min(max(qy - qy_base, 0), RQ - 1);
-        row[k] = ly * RQ + lx;
+        const int lx = min(max(qx - qx_base, 0), WARP_Q - 1), ly = min(max(qy - qy_base, 0), WARP_Q - 1);
+        row[k] = ly * WARP_Q + lx;
         wk[k] = qok ? qw[k] : 0.f;
       }
-      *reinterpret_cast<i32x4r*>(tap2_row[pl]) = i32x4r{row[0], row[1], row[2], row[3]};
+      *reinterpret_cast<i32x4w*>(tap2_row[pl]) = i32x4w{row[0], row[1], row[2], row[3]};
       *reinterpret_cast<f32x4*>(tap2_w[pl]) = f32x4{wk[0], wk[1], wk[2], wk[3]};
     }
     __syncthreads();
     // pass 1 (rotation) of the tile's q block: nw, ne, sw, se
-    for (int idx = tid; idx < RQ * RQ * 16; idx += 256) {
+    for (int idx = tid; idx < WARP_Q * WARP_Q * 16; idx += 256) {
       const int q = idx >> 4;
-      const u32x4r off = *reinterpret_cast<const u32x4r*>(tap1_off[q]);
+      const u32x4w off = *reinterpret_cast<const u32x4w*>(tap1_off[q]);
       const f32x4 wt = *reinterpret_cast<const f32x4*>(tap1_w[q]);
       const f32x4 v_nw = ldb4(src, off[0] + lane_off), v_ne = ldb4(src, off[1] + lane_off);
       const f32x4 v_sw = ldb4(src, off[2] + lane_off), v_se = ldb4(src, off[3] + lane_off);
@@ -151,7 +143,7 @@ fuse_reduce_tiled_kernel(const float* __restrict__ feat, const float* __restrict
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int pl = (tid >> 4) + 16 * k;
-      const i32x4r row = *reinterpret_cast<const i32x4r*>(tap2_row[pl]);
+      const i32x4w row = *reinterpret_cast<const i32x4w*>(tap2_row[pl]);
       const f32x4 wt = *reinterpret_cast<const f32x4*>(tap2_w[pl]);
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -159,11 +151,11 @@ fuse_reduce_tiled_kernel(const float* __restrict__ feat, const float* __restrict
       fold<MODE>(acc[k], v);
     }
   }
-  float* out = fused + (size_t)out_image * hw * c + slice * RCS + 4 * l;
+  float* out = fused + (size_t)out_image * hw * c + slice * WARP_CS + 4 * l;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int pl = (tid >> 4) + 16 * k;
-    const int px = tile_x0 + pl % RT, py = tile_y0 + pl / RT;
+    const int px = tile_x0 + pl % WARP_T, py = tile_y0 + pl / WARP_T;
     if (px < w && py < h) *reinterpret_cast<f32x4*>(out + (size_t)(py * w + px) * c) = finish<MODE>(acc[k], len);
   }
 }
@@ -200,16 +192,7 @@ fuse_reduce_pixel_kernel(const float* __restrict__ feat, const float* __restrict
         ++len;
         const SrcImage src = make_src_image(feat + ((size_t)j * batch + b) * hw * c, (size_t)hw * c * 4);
         const PoseTerms t = pose_terms(trans + (((size_t)b * agents + i) * agents + j) * 16);
-        const Bilinear t2 = pass2_taps(t, px, py, w, h);
-        const float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
-          const bool qok = qx >= 0 && qx < w && qy >= 0 && qy < h;
-          v += sample_src(src, pass1_taps(t, qx, qy, w, h), w, h, c, c4s) * (qok ? qw[k] : 0.f);
-        }
-        fold<MODE>(acc, v);
+        fold<MODE>(acc, warp_pixel(src, t, px, py, w, h, c, c4s));
       }
       if (on) *reinterpret_cast<f32x4*>(out + (size_t)p * c + 4 * c4) = finish<MODE>(acc, len);
     }
@@ -248,7 +231,7 @@ fuse_reduce_lists_backward_kernel(const float* __restrict__ dfused, int ld, cons
     if (MODE == DN_FUSE_MAX) {
       // the winner of every element, re-derived from the maps under the forward's rule
       f32x4 acc = ld4(maps + ((size_t)map_image[s] * quads + q) * 4);
-      i32x4r win = {s, s, s, s};
+      i32x4w win = {s, s, s, s};
       for (int k = s + 1; k < t; ++k) {
         const f32x4 v = ld4(maps + ((size_t)map_image[k] * quads + q) * 4);
 #pragma unroll
@@ -296,9 +279,9 @@ extern "C" int dn_fuse_reduce(const float* feat, const float* trans, const int32
   DN_REQUIRE((size_t)h * w * c * 4 < ((size_t)1 << 31), "fuse reduce: a %d x %d x %d map is past 2 GiB", h, w, c);
   DN_REQUIRE((long)batch * ego_count <= 65535, "fuse reduce: %ld output images, at most 65535", (long)batch * ego_count);
   hipStream_t s = (hipStream_t)stream;
-  if (c % RCS == 0) {
-    const int tiles_x = (w + RT - 1) / RT, tiles_y = (h + RT - 1) / RT;
-    dim3 grid(tiles_x * tiles_y * (c / RCS), batch * ego_count);
+  if (c % WARP_CS == 0) {
+    const int tiles_x = (w + WARP_T - 1) / WARP_T, tiles_y = (h + WARP_T - 1) / WARP_T;
+    dim3 grid(tiles_x * tiles_y * (c / WARP_CS), batch * ego_count);
 #define DN_LAUNCH(M)                                                                                             \
     hipLaunchKernelGGL(fuse_reduce_tiled_kernel<M>, grid, dim3(256), 0, s, feat, trans, num_agent, batch, agents, \
                        h, w, c, only_v2i, ego_first, tiles_x, fused)

@@ -19,6 +19,7 @@
 // body of upstream:coperception/models/det/DiscoNet.py :: DiscoNet.forward
 // (Appx A.5).
 #include "dn_internal.h"
+#include "ego_list.h"
 
 namespace {
 
@@ -48,8 +49,7 @@ disco_fuse_tail_kernel(const TailArgs a) {
   const int bi = blockIdx.y;                             // b * ego_count + (i - ego_first)
   const int b = bi / a.ego_count, il = bi % a.ego_count, i = a.ego_first + il;
   const int p0 = blockIdx.x * PIX;
-  int n_live = a.num_agent[b];
-  n_live = n_live < 0 ? 0 : (n_live > a.agents ? a.agents : n_live);   // a bad count never indexes past the agents
+  const int n_live = live_count(a.num_agent, b, a.agents);
   const int img = il * a.batch + b;                      // agent-major index among LOCAL egos
   const float* ego = a.feat + ((size_t)i * a.batch + b) * a.hw * a.c;   // feat holds all agents
   float* out = a.fused + (size_t)img * a.hw * a.c;
@@ -67,16 +67,13 @@ disco_fuse_tail_kernel(const TailArgs a) {
     return;
   }
 
-  // neighbour list: ego first, then j ascending (j != i), honouring only_v2i
+  // neighbour list: ego first, then the listed j ascending
   int nk = 0;
   if (tid == 0) {
     nbr_of[0] = i;
     int k = 1;
-    for (int j = 0; j < n_live && k < MAX_NBR; ++j) {
-      if (j == i) continue;
-      if (a.only_v2i && i != 0 && j != 0) continue;
-      nbr_of[k++] = j;
-    }
+    for (int j = 0; j < n_live && k < MAX_NBR; ++j)
+      if (DN_LISTED_LIVE(i, j, a.only_v2i)) nbr_of[k++] = j;
     for (int r = k; r < MAX_NBR; ++r) nbr_of[r] = -1;
   }
   for (int idx = tid; idx < H2 * H1; idx += 256) w2s[idx / H1][idx % H1] = a.p.w2[idx];

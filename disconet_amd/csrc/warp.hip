@@ -7,12 +7,10 @@
 // coordinates of a pixel are wave-uniform, so the bounds tests are scalar
 // branches, not divergent lanes.
 //
-// The two resampling passes cannot be merged algebraically (the rotated map is
-// zero-padded before it is translated; SURVEY.md Appx A.4), but they can be
-// fused in one launch: out2(p) reads <= 4 integer pixels q of the rotated map,
-// and each in-frame out1(q) is re-derived from <= 4 source taps with exactly
-// the per-element arithmetic of the two-pass form (the intermediate map is
-// never written to HBM; the 4x re-derivation is L2-resident work).
+// The two resampling passes are fused in one launch: the intermediate (rotated)
+// map is never written to HBM.  The arithmetic of both forms -- per pixel
+// (warp_pixel: the 4x re-derivation is L2-resident work) and per 8x8 tile
+// (WarpTile) -- is warp_device.h's; who is warped for whom is ego_list.h's.
 //
 // Replaces upstream:coperception/models/det/base/* :: feature_transformation
 // (SURVEY.md §8 a5).
@@ -22,6 +20,7 @@
 #include "disconet_train.h"
 #include "dn_internal.h"
 
+#include "ego_list.h"
 #include "warp_device.h"
 
 namespace {
@@ -37,20 +36,14 @@ warp_neighbors_kernel(const float* __restrict__ feat, const float* __restrict__ 
   const int bi = blockIdx.z;              // b * ego_count + (i - ego_first)
   const int b = bi / ego_count, i = ego_first + bi % ego_count;
   const int j = jj + (jj >= i ? 1 : 0);
-  int n_live = num_agent[b];
-  n_live = n_live < 0 ? 0 : (n_live > agents ? agents : n_live);     // a bad count never indexes past the agents
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c4n = c >> 2;
   const int hw = h * w;
   float* dst = warped + ((size_t)bi * (agents - 1) + jj) * hw * c;
 
-  const bool live = i < n_live && j < n_live && !(only_v2i && i != 0 && j != 0);
+  const bool live = listed(i, j, live_count(num_agent, b, agents), only_v2i);
   const SrcImage src = make_src_image(feat + ((size_t)j * batch + b) * hw * c, (size_t)hw * c * 4);   // image j*B+b
-
-  const float* m = trans + (((size_t)b * agents + i) * agents + j) * 16;
-  const float r00 = m[0], r01 = m[1], r10 = m[4], r11 = m[5];
-  const float x_trans = (4.f * m[3]) / 128.f;
-  const float y_trans = -(4.f * m[7]) / 128.f;
+  const PoseTerms t = pose_terms(trans + (((size_t)b * agents + i) * agents + j) * 16);
 
   // Channel loop with a wave-uniform trip count; whole rows of 64 lanes (c % 256 == 0) carry no per-lane
   // condition.  (Round 1 believed a lane-dependent exit here was behind the corruption seen beside the conv
@@ -71,11 +64,9 @@ warp_neighbors_kernel(const float* __restrict__ feat, const float* __restrict__ 
       }
       continue;
     }
-    // pass 2 (translation): normalised base coords of pixel centres
-    const float bx = (2.f * px + 1.f) / w - 1.f;
-    const float by = (2.f * py + 1.f) / h - 1.f;
-    const Bilinear t2 = bilinear_taps(bx + x_trans, by + y_trans, w, h);
-    // the four rotated-map pixels q this output reads, and their source taps
+    // (the body of warp_pixel with the tap sets of the pixel kept for both loop forms below: through warp_pixel itself this
+    // kernel's tap arithmetic was contracted differently and its output bits moved)
+    const Bilinear t2 = pass2_taps(t, px, py, w, h);
     Bilinear t1[4];
     bool qok[4];
     float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
@@ -83,9 +74,7 @@ warp_neighbors_kernel(const float* __restrict__ feat, const float* __restrict__ 
     for (int k = 0; k < 4; ++k) {
       const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
       qok[k] = qx >= 0 && qx < w && qy >= 0 && qy < h;
-      const float qbx = (2.f * qx + 1.f) / w - 1.f;
-      const float qby = (2.f * qy + 1.f) / h - 1.f;
-      t1[k] = bilinear_taps(r00 * qbx + r01 * qby, r10 * qbx + r11 * qby, w, h);
+      t1[k] = pass1_taps(t, qx, qy, w, h);
     }
     auto channels = [&](int c4) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -102,8 +91,7 @@ warp_neighbors_kernel(const float* __restrict__ feat, const float* __restrict__ 
   }
 }
 
-// ---- training form: an explicit list of warps, and the backward scatter (pose_terms, pass1_taps and pass2_taps:
-// warp_device.h) ------------------
+// ---- training form: an explicit list of warps, and the backward scatter ------------------
 __global__ void __launch_bounds__(256)
 warp_list_kernel(const float* __restrict__ src_maps, const float* __restrict__ poses,
                  const int32_t* __restrict__ src_image, int h, int w, int c,
@@ -116,23 +104,9 @@ warp_list_kernel(const float* __restrict__ src_maps, const float* __restrict__ p
   for (int pp = wave; pp < PIX_PER_BLOCK; pp += 4) {
     const int p = blockIdx.x * PIX_PER_BLOCK + pp;
     if (p >= hw) break;
-    const Bilinear t2 = pass2_taps(t, p % w, p / w, w, h);
-    Bilinear t1[4];
-    bool qok[4];
-    float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
-      qok[k] = qx >= 0 && qx < w && qy >= 0 && qy < h;
-      t1[k] = pass1_taps(t, qx, qy, w, h);
-    }
     float* out = warped + ((size_t)wi * hw + p) * c;
-    for (int c4 = lane; c4 < c4n; c4 += 64) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc += sample_src(src, t1[k], w, h, c, c4) * (qok[k] ? qw[k] : 0.f);
-      *reinterpret_cast<f32x4*>(out + 4 * c4) = acc;
-    }
+    for (int c4 = lane; c4 < c4n; c4 += 64)
+      *reinterpret_cast<f32x4*>(out + 4 * c4) = warp_pixel(src, t, p % w, p / w, w, h, c, c4);
   }
 }
 
@@ -393,35 +367,23 @@ warp_gather1_lanes_kernel(const float* __restrict__ d_out1, const float* __restr
   }
 }
 
-// ---- tile-shared form of the same two passes.  Every output pixel p of an 8x8 tile reads the four
-// rotated-map pixels q = (x0(p) + {0,1}, y0(p) + {0,1}); the translation is one offset per (ego, neighbour)
-// pair, so the tile's q pixels form a (T+1)^2 block (T+2 allowed for a rounding split of floor()).  The
-// rotated map R(q) of that block is computed ONCE per workgroup into LDS (4 taps of the source map each,
-// with sample_src's arithmetic) and the tile's 64 outputs are blended from LDS with the per-pixel weights
-// of the one-pixel-per-wave kernel -- the same values in the same order, with ~3x fewer L2 tap reads
-// (the one-pixel kernel re-derives every R(q) four times and is bound by L2 -> L1 bandwidth, ~1.3 GB per
-// step).  A workgroup covers one 64-channel slice of the tile: 100 x 256 B = 25.6 KB of LDS.
-constexpr int WT = 8, WQ = WT + 2, WCS = 64;
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-typedef int i32x4w __attribute__((ext_vector_type(4)));
-
+// ---- tile-shared form of the same two passes (warp_device.h :: WarpTile): one workgroup = one 8 x 8 tile x one
+// 64-channel slice of one (ego, neighbour) pair ------------------
 __global__ void __launch_bounds__(256)
 warp_neighbors_tiled_kernel(const float* __restrict__ feat, const float* __restrict__ trans,
                             const int32_t* __restrict__ num_agent, int batch, int agents, int h, int w,
                             int c, int only_v2i, int ego_first, int ego_count, int tiles_x, int fm,
                             float* __restrict__ warped) {
-  __shared__ f32x4 rot[WQ * WQ][WCS / 4];
-  const int n_slices = c / WCS;
+  __shared__ WarpTile tile_s;
+  const int n_slices = c / WARP_CS;
   const int slice = blockIdx.x % n_slices, tile = blockIdx.x / n_slices;
-  const int tile_x0 = (tile % tiles_x) * WT, tile_y0 = (tile / tiles_x) * WT;
+  const int tile_x0 = (tile % tiles_x) * WARP_T, tile_y0 = (tile / tiles_x) * WARP_T;
   const int jj = blockIdx.y, bi = blockIdx.z;
   const int b = bi / ego_count, i = ego_first + bi % ego_count;
   const int j = jj + (jj >= i ? 1 : 0);
-  int n_live = num_agent[b];
-  n_live = n_live < 0 ? 0 : (n_live > agents ? agents : n_live);
   const int tid = threadIdx.x, l = tid & 15;
   const int hw = h * w;
-  float* dst = warped + ((size_t)bi * (agents - 1) + jj) * hw * c + (fm ? 0 : slice * WCS + 4 * l);
+  float* dst = warped + ((size_t)bi * (agents - 1) + jj) * hw * c + (fm ? 0 : slice * WARP_CS + 4 * l);
   // fm: FRAGMENT-MAJOR pair block (include/disconet_hip.h :: dn_warp_neighbors_fm) -- the order in which the attention
   // launch reads it: [tile of 32 pixels][k-step of 16 channels][half r][lane = 32 h + j] x 4 floats, channel
   // 16 ks + 8 h + 4 r + e of pixel 32 t + j.  This thread's four channels 64 slice + 4 l .. + 3 are one such piece.
@@ -430,102 +392,23 @@ warp_neighbors_tiled_kernel(const float* __restrict__ feat, const float* __restr
     return fm ? dst + (((((size_t)(p >> 5) * fm_kss + fm_ks) * 2 + fm_r) * 64) + fm_h * 32 + (p & 31)) * 4
               : dst + (size_t)p * c;
   };
-  const bool live = i < n_live && j < n_live && !(only_v2i && i != 0 && j != 0);
+  const bool live = listed(i, j, live_count(num_agent, b, agents), only_v2i);
   if (!live) {
-    for (int pl = tid >> 4; pl < WT * WT; pl += 16) {
-      const int px = tile_x0 + pl % WT, py = tile_y0 + pl / WT;
+    for (int pl = tid >> 4; pl < WARP_T * WARP_T; pl += 16) {
+      const int px = tile_x0 + pl % WARP_T, py = tile_y0 + pl / WARP_T;
       if (px < w && py < h) *reinterpret_cast<f32x4*>(out_of(py * w + px)) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     return;
   }
   const SrcImage src = make_src_image(feat + ((size_t)j * batch + b) * hw * c, (size_t)hw * c * 4);
-  const float* m = trans + (((size_t)b * agents + i) * agents + j) * 16;
-  const float r00 = m[0], r01 = m[1], r10 = m[4], r11 = m[5];
-  const float x_trans = (4.f * m[3]) / 128.f;
-  const float y_trans = -(4.f * m[7]) / 128.f;
-  // The tap sets depend on the pixel only, and sixteen lanes share a pixel: computed ONCE per pixel into LDS (clamped byte
-  // offsets / LDS rows and validity-masked weights, the expressions of sample_src and of the blend below), then every lane
-  // does loads and FMAs only.  Round 3's form re-derived them in every lane: 1290 VALU instructions per wave, half of the
-  // launch's wave cycles stalled on VALU issue (profiles/r04_fuse_pmc.txt).  Same values, same order of operations.
-  __shared__ __attribute__((aligned(16))) unsigned tap1_off[WQ * WQ][4];
-  __shared__ __attribute__((aligned(16))) float tap1_w[WQ * WQ][4];
-  __shared__ __attribute__((aligned(16))) int tap2_row[WT * WT][4];
-  __shared__ __attribute__((aligned(16))) float tap2_w[WT * WT][4];
-  // north-west q of the tile: the smallest x0(p) - (p - tile origin) over the tile's columns / rows; column / row k on lane
-  // k mod 8, minimum over each group of eight lanes (every group holds all eight)
-  int qx_base, qy_base;
-  {
-    const int k = tid & 7;
-    const Bilinear t = bilinear_taps((2.f * (tile_x0 + k) + 1.f) / w - 1.f + x_trans,
-                                     (2.f * (tile_y0 + k) + 1.f) / h - 1.f + y_trans, w, h);
-    qx_base = t.x0 - k;
-    qy_base = t.y0 - k;
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-      qx_base = min(qx_base, __shfl_xor(qx_base, d, 64));
-      qy_base = min(qy_base, __shfl_xor(qy_base, d, 64));
-    }
-  }
-  if (tid < WQ * WQ) {              // pass-1 tap set of rotated pixel q = tid
-    const int q = tid;
-    const int qx = qx_base + q % WQ, qy = qy_base + q / WQ;
-    const float qbx = (2.f * qx + 1.f) / w - 1.f;
-    const float qby = (2.f * qy + 1.f) / h - 1.f;
-    const Bilinear t1 = bilinear_taps(r00 * qbx + r01 * qby, r10 * qbx + r11 * qby, w, h);
-    const bool x0ok = t1.x0 >= 0 && t1.x0 < w, x1ok = t1.x0 + 1 >= 0 && t1.x0 + 1 < w;
-    const bool y0ok = t1.y0 >= 0 && t1.y0 < h, y1ok = t1.y0 + 1 >= 0 && t1.y0 + 1 < h;
-    const int x0 = min(max(t1.x0, 0), w - 1), x1 = min(max(t1.x0 + 1, 0), w - 1);
-    const int y0 = min(max(t1.y0, 0), h - 1), y1 = min(max(t1.y0 + 1, 0), h - 1);
-    *reinterpret_cast<u32x4w*>(tap1_off[q]) = u32x4w{(unsigned)((y0 * w + x0) * c) * 4u, (unsigned)((y0 * w + x1) * c) * 4u,
-                                                      (unsigned)((y1 * w + x0) * c) * 4u, (unsigned)((y1 * w + x1) * c) * 4u};
-    *reinterpret_cast<f32x4*>(tap1_w[q]) = f32x4{(y0ok && x0ok) ? t1.w_nw : 0.f, (y0ok && x1ok) ? t1.w_ne : 0.f,
-                                                 (y1ok && x0ok) ? t1.w_sw : 0.f, (y1ok && x1ok) ? t1.w_se : 0.f};
-  } else if (tid >= 128 && tid < 128 + WT * WT) {     // pass-2 tap set of output pixel pl (a wave of its own)
-    const int pl = tid - 128;
-    const int px = tile_x0 + pl % WT, py = tile_y0 + pl / WT;
-    const float bx = (2.f * px + 1.f) / w - 1.f;
-    const float by = (2.f * py + 1.f) / h - 1.f;
-    const Bilinear t2 = bilinear_taps(bx + x_trans, by + y_trans, w, h);
-    const float qw[4] = {t2.w_nw, t2.w_ne, t2.w_sw, t2.w_se};
-    int row[4];
-    float wk[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int qx = t2.x0 + (k & 1), qy = t2.y0 + (k >> 1);
-      const bool qok = qx >= 0 && qx < w && qy >= 0 && qy < h;
-      const int lx = min(max(qx - qx_base, 0), WQ - 1), ly = min(max(qy - qy_base, 0), WQ - 1);
-      row[k] = ly * WQ + lx;
-      wk[k] = qok ? qw[k] : 0.f;
-    }
-    *reinterpret_cast<i32x4w*>(tap2_row[pl]) = i32x4w{row[0], row[1], row[2], row[3]};
-    *reinterpret_cast<f32x4*>(tap2_w[pl]) = f32x4{wk[0], wk[1], wk[2], wk[3]};
-  }
+  const PoseTerms t = pose_terms(trans + (((size_t)b * agents + i) * agents + j) * 16);
+  warp_tile_fill_taps(tile_s, t, tile_x0, tile_y0, w, h, c, tid);
   __syncthreads();
-  // pass 1 (rotation) of the tile's q block: nw, ne, sw, se as torch's CPU kernel (sample_src)
-  const unsigned lane_off = 16u * (slice * (WCS / 4) + l);
-  for (int idx = tid; idx < WQ * WQ * 16; idx += 256) {
-    const int q = idx >> 4;
-    const u32x4w off = *reinterpret_cast<const u32x4w*>(tap1_off[q]);
-    const f32x4 wt = *reinterpret_cast<const f32x4*>(tap1_w[q]);
-    const f32x4 v_nw = ldb4(src, off[0] + lane_off), v_ne = ldb4(src, off[1] + lane_off);
-    const f32x4 v_sw = ldb4(src, off[2] + lane_off), v_se = ldb4(src, off[3] + lane_off);
-    f32x4 acc = v_nw * wt[0];
-    acc += v_ne * wt[1];
-    acc += v_sw * wt[2];
-    acc += v_se * wt[3];
-    rot[q][l] = acc;
-  }
+  warp_tile_rotate(tile_s, src, slice, tid);
   __syncthreads();
-  // pass 2 (translation): blend the four q of every output pixel
-  for (int pl = tid >> 4; pl < WT * WT; pl += 16) {
-    const int px = tile_x0 + pl % WT, py = tile_y0 + pl / WT;
-    if (px >= w || py >= h) continue;
-    const i32x4w row = *reinterpret_cast<const i32x4w*>(tap2_row[pl]);
-    const f32x4 wt = *reinterpret_cast<const f32x4*>(tap2_w[pl]);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc += rot[row[k]][l] * wt[k];
-    *reinterpret_cast<f32x4*>(out_of(py * w + px)) = acc;
+  for (int pl = tid >> 4; pl < WARP_T * WARP_T; pl += 16) {
+    const int px = tile_x0 + pl % WARP_T, py = tile_y0 + pl / WARP_T;
+    if (px < w && py < h) *reinterpret_cast<f32x4*>(out_of(py * w + px)) = warp_tile_blend(tile_s, pl, l);
   }
 }
 
@@ -585,7 +468,7 @@ extern "C" int dn_warp_neighbors(const float* feat, const float* trans, const in
   return warp_neighbors_impl(feat, trans, num_agent, batch, agents, h, w, c, only_v2i, ego_first, ego_count, warped, 0, stream);
 }
 
-extern "C" int dn_warp_fm_supported(int h, int w, int c) { return c % WCS == 0 && (h * w) % 32 == 0; }
+extern "C" int dn_warp_fm_supported(int h, int w, int c) { return c % WARP_CS == 0 && (h * w) % 32 == 0; }
 
 extern "C" int dn_warp_neighbors_fm(const float* feat, const float* trans, const int32_t* num_agent,
                                     int batch, int agents, int h, int w, int c, int only_v2i,
@@ -604,9 +487,9 @@ int warp_neighbors_impl(const float* feat, const float* trans, const int32_t* nu
              "warp: ego range [%d, %d) outside 0..%d", ego_first, ego_first + ego_count, agents);
   if (agents < 2) return DN_OK;   // no neighbours to warp
   const int hw = h * w;
-  if (c % WCS == 0) {
-    const int tiles_x = (w + WT - 1) / WT, tiles_y = (h + WT - 1) / WT;
-    dim3 tgrid(tiles_x * tiles_y * (c / WCS), agents - 1, batch * ego_count);
+  if (c % WARP_CS == 0) {
+    const int tiles_x = (w + WARP_T - 1) / WARP_T, tiles_y = (h + WARP_T - 1) / WARP_T;
+    dim3 tgrid(tiles_x * tiles_y * (c / WARP_CS), agents - 1, batch * ego_count);
     hipLaunchKernelGGL(warp_neighbors_tiled_kernel, tgrid, dim3(256), 0, (hipStream_t)stream, feat, trans,
                        num_agent, batch, agents, h, w, c, only_v2i, ego_first, ego_count, tiles_x, fm, warped);
     return dn::check_launch("warp_neighbors_tiled_kernel");

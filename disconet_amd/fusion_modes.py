@@ -76,10 +76,11 @@ def reduce_list(maps, mode):
     raise ValueError("mode must be one of %s (got %r)" % (sorted(ops.FUSE_MODES), mode))
 
 
-def host_fuse_reduce(feat, trans, num_agent, batch, agents, mode, only_v2i=False, ego_first=0, ego_count=None):
-    """ops.fuse_reduce's contract in plain torch on the CPU, fp32: feat [A*B, h, w, C] agent-major NHWC, trans
-    [B, A, A, 4, 4], num_agent [B] live counts (clamped to 0..A) -> fused [ego_count*B, h, w, C], image
-    (i - ego_first) * B + b.  A padded ego passes through; a dead neighbour is never read."""
+def _host_fuse_walk(feat, trans, num_agent, batch, agents, only_v2i, ego_first, ego_count, fuse_list):
+    """The walk the host contracts share: feat [A*B, h, w, C] agent-major NHWC, trans [B, A, A, 4, 4], num_agent [B] live
+    counts (clamped to 0..A) -> fused [ego_count*B, h, w, C], image (i - ego_first) * B + b, fp32 on the CPU.  A padded ego
+    passes through; a dead neighbour is never read; a live ego's image is fuse_list(b, i - ego_first, maps), maps = its own
+    [C, h, w] map, then warp(j -> i) of the listed j (ops.ego_list)."""
     A, B = agents, batch
     E = A if ego_count is None else ego_count
     x = feat.detach().to(device="cpu", dtype=torch.float32).permute(0, 3, 1, 2)      # [A*B, C, h, w]
@@ -89,17 +90,24 @@ def host_fuse_reduce(feat, trans, num_agent, batch, agents, mode, only_v2i=False
     if not (0 <= ego_first and E > 0 and ego_first + E <= A):
         raise ValueError("ego range [%d, %d) outside 0..%d" % (ego_first, ego_first + E, A))
     out = torch.empty((E * B,) + tuple(x.shape[1:]), dtype=torch.float32)
-    for b in range(B):
-        n = max(0, min(int(num_agent[b]), A))
-        for i in range(ego_first, ego_first + E):
-            ego = x[i * B + b]
-            if i >= n:
-                out[(i - ego_first) * B + b] = ego
-                continue
-            maps = [ego] + [_host_warp(x[j * B + b], trans[b, i, j]) for j in range(n)
-                            if j != i and not (only_v2i and i != 0 and j != 0)]
-            out[(i - ego_first) * B + b] = reduce_list(maps, mode)
+    with torch.no_grad():
+        for b in range(B):
+            n = max(0, min(int(num_agent[b]), A))
+            for i in range(ego_first, ego_first + E):
+                ego = x[i * B + b]
+                if i >= n:
+                    out[(i - ego_first) * B + b] = ego
+                    continue
+                maps = [ego] + [_host_warp(x[j * B + b], trans[b, i, j]) for j in ops.ego_list(i, n, only_v2i)[1:]]
+                out[(i - ego_first) * B + b] = fuse_list(b, i - ego_first, maps)
     return out.permute(0, 2, 3, 1).contiguous()
+
+
+def host_fuse_reduce(feat, trans, num_agent, batch, agents, mode, only_v2i=False, ego_first=0, ego_count=None):
+    """ops.fuse_reduce's contract in plain torch on the CPU, fp32 (_host_fuse_walk's shapes): every live ego's list reduced
+    by reduce_list."""
+    return _host_fuse_walk(feat, trans, num_agent, batch, agents, only_v2i, ego_first, ego_count,
+                           lambda b, il, maps: reduce_list(maps, mode))
 
 
 def _host_scores(net, ego, nb):
@@ -148,35 +156,17 @@ def weighted_sum(maps, w):
 
 def host_agent_fuse(feat, trans, num_agent, batch, agents, net, only_v2i=False, ego_first=0, ego_count=None,
                     want_weights=False):
-    """ops.agent_fuse's contract in plain torch on the CPU, fp32: feat [A*B, h, w, C] agent-major NHWC, trans
-    [B, A, A, 4, 4], num_agent [B] live counts (clamped to 0..A), net: the weight net (agent_weighted_fusion's names, its
-    BatchNorms in eval mode) -> fused [ego_count*B, h, w, C] (+ weights [B, ego_count, A] in list order).  A padded ego
-    passes through; a dead neighbour is never read."""
-    A, B = agents, batch
-    E = A if ego_count is None else ego_count
-    x = feat.detach().to(device="cpu", dtype=torch.float32).permute(0, 3, 1, 2)      # [A*B, C, h, w]
-    trans = trans.detach().to(device="cpu", dtype=torch.float32)
-    if x.shape[0] != A * B:
-        raise ValueError("feat has %d images, expected agents * batch = %d" % (x.shape[0], A * B))
-    if not (0 <= ego_first and E > 0 and ego_first + E <= A):
-        raise ValueError("ego range [%d, %d) outside 0..%d" % (ego_first, ego_first + E, A))
-    out = torch.empty((E * B,) + tuple(x.shape[1:]), dtype=torch.float32)
-    weights = torch.zeros(B, E, A, dtype=torch.float32)
-    with torch.no_grad():
-        for b in range(B):
-            n = max(0, min(int(num_agent[b]), A))
-            for i in range(ego_first, ego_first + E):
-                ego = x[i * B + b]
-                if i >= n:
-                    out[(i - ego_first) * B + b] = ego
-                    continue
-                maps = [ego] + [_host_warp(x[j * B + b], trans[b, i, j]) for j in range(n)
-                                if j != i and not (only_v2i and i != 0 and j != 0)]
-                a = torch.stack([agent_scalar(_host_scores(net, ego, m), net.conv1_5.weight, net.conv1_5.bias) for m in maps])
-                w = agent_softmax(a)
-                weights[b, i - ego_first, :len(maps)] = w
-                out[(i - ego_first) * B + b] = weighted_sum(maps, w)
-    fused = out.permute(0, 2, 3, 1).contiguous()
+    """ops.agent_fuse's contract in plain torch on the CPU, fp32 (_host_fuse_walk's shapes); net: the weight net
+    (agent_weighted_fusion's names, its BatchNorms in eval mode) -> fused (+ weights [B, ego_count, A] in list order)."""
+    weights = torch.zeros(batch, agents if ego_count is None else max(ego_count, 0), agents, dtype=torch.float32)
+
+    def fuse_list(b, il, maps):
+        a = torch.stack([agent_scalar(_host_scores(net, maps[0], m), net.conv1_5.weight, net.conv1_5.bias) for m in maps])
+        w = agent_softmax(a)
+        weights[b, il, :len(maps)] = w
+        return weighted_sum(maps, w)
+
+    fused = _host_fuse_walk(feat, trans, num_agent, batch, agents, only_v2i, ego_first, ego_count, fuse_list)
     return (fused, weights) if want_weights else fused
 
 

@@ -1015,6 +1015,15 @@ def live_agent_counts(num_agent_tensor, device):
     return t[:, 0].to(device=device, dtype=torch.int32).contiguous()
 
 
+def ego_list(i, n_live, only_v2i):
+    """The agents of ego i's list in a scene of n_live live agents (a count the caller has brought into range its own way),
+    in list order: the ego, then the live j != i ascending -- under only_v2i a vehicle (i != 0) lists the infrastructure,
+    agent 0, only.  A padded ego (i >= n_live) has a list of one.  The host statement of csrc/ego_list.h."""
+    if i >= n_live:
+        return [i]
+    return [i] + [j for j in range(n_live) if j != i and not (only_v2i and i != 0 and j != 0)]
+
+
 def make_tail_params(tensors):
     """tensors: dict name -> float32 device tensor for every dn_mlp_tail_params field."""
     p = MlpTailParams()

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _need_gpu, _ptr, _stream
+from .ops import _need_gpu, _ptr, _stream, ego_list
 
 
 def make_anchors(config, map_hw=None, device="cuda"):
@@ -302,7 +302,7 @@ def host_late_fuse(det, trans_matrices, num_agent, batch_size, agents, top_k=Non
     for b in range(B):
         nl = max(0, min(int(live[b]), A))
         for i in range(ego_first, ego_first + E):
-            lst = [i] + ([j for j in range(nl) if j != i and not (only_v2i and i != 0 and j != 0)] if i < nl else [])
+            lst = ego_list(i, nl, only_v2i)
             cb, cs, src = [], [], []
             for pos, j in enumerate(lst):
                 img = j * B + b

@@ -87,13 +87,7 @@ def fusion_call_counts(agents, only_v2i, num_agent_cpu, B):
     out = []
     for b in range(B):
         n = int(num_agent_cpu[b])
-        row = []
-        for i in range(agents):
-            if i >= n:
-                row.append(0)
-            else:
-                row.append(1 + sum(1 for j in range(n) if j != i and not (only_v2i and i != 0 and j != 0)))
-        out.append(row)
+        out.append([len(ops.ego_list(i, n, only_v2i)) if i < n else 0 for i in range(agents)])
     return out
 
 
@@ -184,9 +178,7 @@ def _fusion_index_lists(agents, only_v2i, num_agent_cpu, B, dev, ego_first=0, eg
             pair_index.append(img(i, b))
             map_image.append(img(i, b))
             order.append(img(i, b))
-            for j in range(n):
-                if j == i or (only_v2i and i != 0 and j != 0):
-                    continue
+            for j in ops.ego_list(i, n, only_v2i)[1:]:
                 wi = len(src_image)
                 src_image.append(img(j, b))
                 poses_idx.append((b, i, j))
