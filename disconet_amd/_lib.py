@@ -194,6 +194,7 @@ SIGNATURES = {
     "dn_agent_fuse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dn_agent_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(FuseMlpParams), c_void_p, c_void_p, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "dn_render_bev": (c_int, [c_void_p, c_void_p, c_void_p]),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -968,6 +968,82 @@ int dn_hota_finish(const void* state, int n_images, int max_gt_ids, int max_trac
                    int64_t* out_counts, int64_t* out_alpha_counts, double* out_alpha_sums, int32_t* out_match,
                    void* stream);
 
+/* ------------------------------------------------------------------------
+ * BEV rendering (disconet_amd/csrc/render.hip, dn_version 151): every image of a batch rasterised into an RGB canvas on
+ * the device -- the scene's occupancy or class map, an optional heat overlay (the DiscoGraph weights), up to 4 sets of
+ * rotated boxes.  The result is integer pixels; render.host_render_bev (numpy, float64 and integers) is the normative
+ * statement, which the kernel equals in every byte.  Graph-capturable behind dn_detect / dn_track_step: one kernel
+ * launch, no atomics, no workspace, no host synchronisation; two runs write the same bytes.
+ *   Canvas.  out [n][S h][S w][3] uint8, S = scale in {1, 2, 4}.  Canvas row r belongs to BEV x index r / S, column q to
+ *   y index q / S (the layout of bev_seq, no flip); a pixel's centre in canvas units is (r + 0.5, q + 0.5).
+ *   DN_ERR_ARG: voxel[0] != voxel[1], voxel not finite and > 0, w % 4 != 0, S outside {1, 2, 4}, n outside 1..65535,
+ *   a canvas of 2^31 bytes or more per image, `out` not 4-byte aligned, a null pointer where one is needed, more than 4
+ *   sets, a set with k < 1, thickness < 1 or fill_alpha outside 0..255, heat_alpha outside 0..255, heat_hi not > heat_lo
+ *   (both finite), h % heat_h != 0 or w % heat_w != 0, an unknown background kind or colour mode.
+ *   Background (bg_kind).  DN_RENDER_BG_NONE: every pixel is `ground`.  DN_RENDER_BG_OCCUPANCY: background is
+ *   [n][h][w] uint32, the words dn_scatter_dense_bits writes; m = min(popcount(word), 8) and each channel is
+ *   (ground (8 - m) + point m + 4) / 8 in integers.  DN_RENDER_BG_CLASSES: background is [n][h][w] int32 labels, palette
+ *   [n_classes][3] uint8; a label outside [0, n_classes) gives `ground`.
+ *   Heat overlay (heat may be null).  heat [n][heat_h][heat_w] fp32, upsampled nearest: pixel (r, q) reads
+ *   heat[(r / S) / (h / heat_h)][(q / S) / (w / heat_w)] = v.  t = ((double)v - heat_lo) / (heat_hi - heat_lo); a NaN
+ *   leaves the pixel alone, otherwise t is clamped to [0, 1], l = floor(t 255), a = (heat_alpha l + 127) / 255 and each
+ *   channel becomes (below (255 - a) + heat_colour a + 127) / 255 (BLEND, in integers).
+ *   Box sets, painted in set order and within a set in ascending row order.  boxes [n][k][6] fp32 = (x, y, w, h, sin,
+ *   cos) in metres, the frame and convention of postprocess._corners (local +x is the heading); count [n] (null: k rows;
+ *   clamped to [0, k]), scores [n][k], ids [n][k] as the colour mode needs them.
+ *   Per row, fp64 from the fp32 members, every product, sum, quotient and root rounded on its own (no contraction):
+ *   nrm = sqrt(s s + c c); the row is skipped when a member is not finite, nrm is not > 0, w or h is not > 0;
+ *   c' = c / nrm, s' = s / nrm; X = ((x - x_lo) / voxel) S, Y = ((y - y_lo) / voxel) S; A = ((w / 2) / voxel) S,
+ *   B = ((h / 2) / voxel) S.  x_lo, y_lo are the lower edges of the extents (make_anchors' origin).
+ *   Per pixel, fp64, the same rule: dx = (r + 0.5) - X, dy = (q + 0.5) - Y; u = dx c' + dy s', v = dy c' - dx s';
+ *   e = max(|u| - A, |v| - B).  Outline when -thickness < e <= 0: the pixel takes the row's colour.  Heading tick (when
+ *   the set has one) when 0 <= u <= A and |v| <= thickness / 2: the same.  Otherwise, when e <= 0 and fill_alpha > 0,
+ *   the pixel is BLENDed with the row's colour at a = fill_alpha.
+ *   Colour.  DN_RENDER_COLOUR_FIXED: `colour`.  DN_RENDER_COLOUR_SCORE: z = (double)score clamped to [0, 1], a NaN
+ *   giving 0; l = floor(z 255); each channel (colour (255 - l) + colour_hi l + 127) / 255.  DN_RENDER_COLOUR_ID: entry
+ *   id mod 32 of DN_RENDER_ID_PALETTE; a row with a negative id (Sort's padding) is skipped.
+ *   The kernel bins the rows per 32 x 32 tile by a conservative circle test first; the contract is the per-pixel rule
+ *   alone.
+ * ------------------------------------------------------------------------ */
+#define DN_RENDER_MAX_SETS 4
+#define DN_RENDER_BG_NONE 0
+#define DN_RENDER_BG_OCCUPANCY 1
+#define DN_RENDER_BG_CLASSES 2
+#define DN_RENDER_COLOUR_FIXED 0
+#define DN_RENDER_COLOUR_SCORE 1
+#define DN_RENDER_COLOUR_ID 2
+/* 32 x (r, g, b) */
+#define DN_RENDER_ID_PALETTE { \
+  229,34,34, 91,229,131, 107,24,165, 165,153,66, 34,196,229, 229,91,166, 59,165,24, 70,66,165, \
+  229,99,34, 91,229,178, 154,24,165, 144,165,66, 34,131,229, 229,91,120, 24,165,36, 103,66,165, \
+  229,164,34, 91,229,224, 165,24,130, 111,165,66, 34,66,229, 229,109,91, 24,165,83, 137,66,165, \
+  228,229,34, 91,188,229, 165,24,83, 78,165,66, 67,34,229, 229,155,91, 24,165,131, 165,66,161 }
+
+typedef struct dn_render_set {
+  const float* boxes;
+  const int32_t* count;
+  const float* scores;
+  const int32_t* ids;
+  int32_t k, thickness, fill_alpha, heading, colour_by;
+  uint8_t colour[4], colour_hi[4];   /* r, g, b, 0 */
+  int32_t reserved;
+} dn_render_set;
+
+typedef struct dn_render_desc {
+  int32_t n, h, w, scale;
+  double x_lo, y_lo, voxel[2];
+  const void* background;
+  const uint8_t* palette;
+  const float* heat;
+  int32_t bg_kind, n_classes, heat_h, heat_w, heat_alpha, n_sets;
+  double heat_lo, heat_hi;
+  uint8_t ground[4], point[4], heat_colour[4];   /* r, g, b, 0 */
+  int32_t reserved;
+  dn_render_set sets[DN_RENDER_MAX_SETS];
+} dn_render_desc;
+
+int dn_render_bev(const dn_render_desc* desc, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
