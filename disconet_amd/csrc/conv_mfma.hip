@@ -54,6 +54,7 @@
 // Replaces the conv2d/conv3d(1x1x1)+batch_norm+relu(+interpolate+cat) chains of
 // upstream:coperception/models/det/backbone/Backbone.py.
 #include "dn_internal.h"
+#include "sp_split.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -369,9 +370,10 @@ conv_mfma_kernel(const ConvArgs a) {
         half4 hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float x = fminf(fmaxf(ra[it][e], -65504.f), 65504.f);
-          hi[e] = (_Float16)x;
-          lo[e] = (_Float16)(x - (float)hi[e]);
+          _Float16 h, l;
+          sp::split(ra[it][e], h, l);
+          hi[e] = h;
+          lo[e] = l;
         }
         if (idx < T::A_VEC) {
           float* rowp = &As[(idx / KV) * PS];
@@ -496,7 +498,7 @@ conv_mfma_kernel(const ConvArgs a) {
           for (int e = 0; e < 4; ++e) {
             float v = acc[wm][0][4 * g + e] * sc[e] + sh[e];
             if (a.relu) v = fmaxf(v, 0.f);
-            v = fminf(fmaxf(v, -65504.f), 65504.f);
+            v = fminf(fmaxf(v, -65504.f), 65504.f);      // sp_split.h :: split, written out: called, this kernel's ISA moves
             hi[e] = (_Float16)v;
             lo[e] = (_Float16)(v - (float)hi[e]);
           }
@@ -765,49 +767,11 @@ inline int nchunks_packed(const dn_conv_desc& d) {
   return (d.c0 + d.c1 + kcp_of(d.ksize) - 1) / kcp_of(d.ksize);
 }
 
-__global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wpk,
-                                    int c_out, int c_in, int taps, int cout_pad, int kcp,
-                                    long total) {
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    long r = idx;
-    const int k = r % kcp; r /= kcp;
-    const int co = r % cout_pad; r /= cout_pad;
-    const int tap = r % taps;
-    const int chp = r / taps;
-    const int ci = chp * kcp + k;
-    float v = 0.f;
-    if (co < c_out && ci < c_in) v = w[((size_t)co * c_in + ci) * taps + tap];
-    wpk[idx] = v;
-  }
-}
-
-// split-f16 rows: [kcp hi halves | kcp lo halves] in the bytes of kcp floats
-__global__ void pack_weights_split_kernel(const float* __restrict__ w, _Float16* __restrict__ wpk,
-                                          int c_out, int c_in, int taps, int cout_pad, int kcp,
-                                          long total) {
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    long r = idx;
-    const int k = r % kcp; r /= kcp;
-    const int co = r % cout_pad; r /= cout_pad;
-    const int tap = r % taps;
-    const int chp = r / taps;
-    const int ci = chp * kcp + k;
-    float v = 0.f;
-    if (co < c_out && ci < c_in) v = w[((size_t)co * c_in + ci) * taps + tap];
-    v = fminf(fmaxf(v, -65504.f), 65504.f);
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    const long row = idx / kcp;
-    wpk[row * 2 * kcp + k] = hi;
-    wpk[row * 2 * kcp + kcp + k] = lo;
-  }
-}
-
-// ---- many packs of this engine in ONE launch (dn_conv_pack_weights_multi; the split-planar engine's twin is in conv_sp.hip).
-// A job = one call of pack_weights_kernel (split = 0) or pack_weights_split_kernel (split = 1) on the weight tensor a VIEW of
-// `w` defines, times the power of two wmul (what the training engine multiplied in with a torch op before it packed):
+// ---- the packed weight image of this engine: ONE body, a job.  dn_conv_pack_weights launches one job by value;
+// dn_conv_pack_weights_multi many packs in one launch from a table (the split-planar engine's twin is in conv_sp.hip).
+// fp32 rows (split = 0): [chunk][tap][cout_pad][kcp] floats; split-f16 rows (split = 1): [kcp hi halves | kcp lo halves] in
+// the bytes of kcp floats.  The weight tensor is a VIEW of `w`, times the power of two wmul (what the training engine
+// multiplied in with a torch op before it packed):
 //   mode 0: W[n][ci][t] = w[n][ci_first + ci][t]                   (the tensor itself, or a column cut of it)
 //   mode 1: W[n][ci][t] = w[ci][ci_first + n][taps - 1 - t]        (dn_conv_dgrad_weights: the data gradient's conv)
 struct NhwcPackJob {
@@ -819,19 +783,8 @@ struct NhwcPackJob {
 };
 static_assert(sizeof(NhwcPackJob) == 80, "dn_conv_pack_multi_table_bytes");
 
-__global__ void __launch_bounds__(256) pack_weights_multi_kernel(const NhwcPackJob* __restrict__ jobs, int n_jobs) {
-  __shared__ NhwcPackJob job;
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = n_jobs - 1;                 // the last job whose first block is <= blockIdx.x
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].block_first <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    job = jobs[lo];
-  }
-  __syncthreads();
-  const NhwcPackJob& j = job;
-  const int vb = blockIdx.x - j.block_first;
+// block `vb` of the job's n_blocks walks the job's elements (chunk, tap, co, k) with a grid-stride loop
+__device__ inline void pack_job_elems(const NhwcPackJob& j, int vb) {
   for (long idx = vb * (long)blockDim.x + threadIdx.x; idx < j.total; idx += (long)j.n_blocks * blockDim.x) {
     long r = idx;
     const int k = r % j.kcp; r /= j.kcp;
@@ -846,9 +799,8 @@ __global__ void __launch_bounds__(256) pack_weights_multi_kernel(const NhwcPackJ
       v *= j.wmul;
     }
     if (j.split) {
-      v = fminf(fmaxf(v, -65504.f), 65504.f);
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
+      _Float16 hi, lo;
+      sp::split(v, hi, lo);
       const long row = idx / j.kcp;
       _Float16* o = static_cast<_Float16*>(j.out);
       o[row * 2 * j.kcp + k] = hi;
@@ -857,6 +809,23 @@ __global__ void __launch_bounds__(256) pack_weights_multi_kernel(const NhwcPackJ
       static_cast<float*>(j.out)[idx] = v;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) pack_weights_job_kernel(const NhwcPackJob j) { pack_job_elems(j, blockIdx.x); }
+
+// A workgroup finds its job from the table's first-block column and walks it as the single launch does.
+__global__ void __launch_bounds__(256) pack_weights_multi_kernel(const NhwcPackJob* __restrict__ jobs, int n_jobs) {
+  __shared__ NhwcPackJob job;
+  if (threadIdx.x == 0) {
+    int lo = 0, hi = n_jobs - 1;                 // the last job whose first block is <= blockIdx.x
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (jobs[mid].block_first <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    job = jobs[lo];
+  }
+  __syncthreads();
+  pack_job_elems(job, blockIdx.x - job.block_first);
 }
 
 __global__ void fold_bn_kernel(const float* bias, const float* gamma, const float* beta,
@@ -930,21 +899,29 @@ extern "C" size_t dn_conv_packed_weight_floats(const dn_conv_desc* d) {
   return (size_t)nchunks_packed(*d) * d->ksize * d->ksize * cout_pad_of(*d) * kcp_of(d->ksize);
 }
 
+namespace {
+// one job of layer `d` (no checks: the callers', block_first: the table's)
+void fill_pack_job(NhwcPackJob& j, const dn_conv_desc* d, const float* w, void* packed, int mode, int cin_total, int ci_first,
+                   float wmul) {
+  j.w = w;
+  j.out = packed;
+  j.c_out = d->c_out; j.c_in = d->c0 + d->c1; j.taps = d->ksize * d->ksize; j.cout_pad = cout_pad_of(*d); j.kcp = kcp_of(d->ksize);
+  j.mode = mode; j.cin_total = cin_total; j.ci_first = ci_first; j.split = d->math == 1;
+  j.wmul = wmul; j.pad_ = 0; j.padf_ = 0.f;
+  j.total = (long)dn_conv_packed_weight_floats(d);
+  j.n_blocks = (int)((j.total + 255) / 256 < 4096 ? (j.total + 255) / 256 : 4096);
+  j.block_first = 0;
+}
+}  // namespace
+
 extern "C" int dn_conv_pack_weights(const dn_conv_desc* d, const float* weight_oihw,
                                     float* packed, void* stream) {
   if (int rc = validate(d)) return rc;
   DN_REQUIRE(weight_oihw && packed, "conv pack: null pointer");
-  const long total = (long)dn_conv_packed_weight_floats(d);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (d->math == 1)
-    hipLaunchKernelGGL(pack_weights_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       weight_oihw, reinterpret_cast<_Float16*>(packed), d->c_out, d->c0 + d->c1,
-                       d->ksize * d->ksize, cout_pad_of(*d), kcp_of(d->ksize), total);
-  else
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       weight_oihw, packed, d->c_out, d->c0 + d->c1, d->ksize * d->ksize,
-                       cout_pad_of(*d), kcp_of(d->ksize), total);
-  return dn::check_launch("pack_weights_kernel");
+  NhwcPackJob j;      // the layer's own weight tensor: mode 0, all its columns, wmul 1 (x * 1 = x: the same bits)
+  fill_pack_job(j, d, weight_oihw, packed, 0, d->c0 + d->c1, 0, 1.f);
+  hipLaunchKernelGGL(pack_weights_job_kernel, dim3(j.n_blocks), dim3(256), 0, (hipStream_t)stream, j);
+  return dn::check_launch("pack_weights_job_kernel");
 }
 
 extern "C" size_t dn_conv_pack_multi_table_bytes(int n_jobs) { return n_jobs > 0 ? sizeof(NhwcPackJob) * (size_t)n_jobs : 0; }
@@ -962,16 +939,9 @@ extern "C" int dn_conv_pack_multi_prepare(const dn_pack_job* jobs, int n_jobs, v
     const int c_in = d->c0 + d->c1;
     DN_REQUIRE(q.ci_first >= 0 && q.ci_first + (q.mode == 0 ? c_in : d->c_out) <= q.cin_total,
                "conv pack multi: job %d: columns %d + %d of %d", i, q.ci_first, q.mode == 0 ? c_in : d->c_out, q.cin_total);
-    NhwcPackJob& j = t[i];
-    j.w = q.weight;
-    j.out = q.packed;
-    j.c_out = d->c_out; j.c_in = c_in; j.taps = d->ksize * d->ksize; j.cout_pad = cout_pad_of(*d); j.kcp = kcp_of(d->ksize);
-    j.mode = q.mode; j.cin_total = q.cin_total; j.ci_first = q.ci_first; j.split = d->math == 1;
-    j.wmul = q.wmul; j.pad_ = 0; j.padf_ = 0.f;
-    j.total = (long)dn_conv_packed_weight_floats(d);
-    j.n_blocks = (int)((j.total + 255) / 256 < 4096 ? (j.total + 255) / 256 : 4096);      // the single launch's grid
-    j.block_first = first;
-    first += j.n_blocks;
+    fill_pack_job(t[i], d, q.weight, q.packed, q.mode, q.cin_total, q.ci_first, q.wmul);
+    t[i].block_first = first;
+    first += t[i].n_blocks;      // the single launch's grid
   }
   *total_blocks = first;
   return DN_OK;
@@ -1003,11 +973,10 @@ __global__ void pack_post1x1_kernel(const float* __restrict__ w2, _Float16* __re
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= 64 * 64) return;
   const int n = idx / 64, k = idx % 64;
-  float v = (n < c_out2 && k < c_in2) ? w2[(size_t)n * c_in2 + k] : 0.f;
-  v = fminf(fmaxf(v, -65504.f), 65504.f);
-  const _Float16 hi = (_Float16)v;
+  _Float16 hi, lo;
+  sp::split((n < c_out2 && k < c_in2) ? w2[(size_t)n * c_in2 + k] : 0.f, hi, lo);
   out[n * 128 + k] = hi;
-  out[n * 128 + 64 + k] = (_Float16)(v - (float)hi);
+  out[n * 128 + 64 + k] = lo;
 }
 
 int fill_args(const dn_conv_desc* d, const float* src0, const float* src1, const float* packed,

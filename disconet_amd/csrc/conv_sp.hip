@@ -36,6 +36,7 @@
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
+#include "sp_split.h"
 #include <array>
 #include <cstdlib>
 #include <type_traits>
@@ -1176,19 +1177,14 @@ __global__ void sp_from_nhwc_kernel(const float* __restrict__ src, unsigned char
     const int cg = r % cg_total;
     const long img = r / cg_total;
     const float* s = src + (img * hw + px) * ld + cg * 16 + oct * 8;
-    half8 hi, lo;
+    float x[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float x = (cg * 16 + oct * 8 + e < c) ? s[e] : 0.f;
-      amax = fmaxf(amax, fabsf(x));
-      nan_in |= x != x;
-      x = fminf(fmaxf(x, -65504.f), 65504.f);
-      hi[e] = (_Float16)x;
-      lo[e] = (_Float16)(x - (float)hi[e]);
+      x[e] = (cg * 16 + oct * 8 + e < c) ? s[e] : 0.f;
+      amax = fmaxf(amax, fabsf(x[e]));
+      nan_in |= x[e] != x[e];
     }
-    unsigned char* d = dst + (((img * cg_total + cg) * 4 + oct) * hw + px) * 16;
-    *reinterpret_cast<half8*>(d) = hi;
-    *reinterpret_cast<half8*>(d + 2 * hw * 16) = lo;
+    sp::split_store(dst, sp::act_piece(img, cg_total, cg, sp::quarter_of(0, oct), hw, px), 2 * hw, x);
   }
   note_range(amax, nan_in);
 }
@@ -1203,13 +1199,12 @@ __global__ void sp_to_nhwc_kernel(const unsigned char* __restrict__ src, float* 
     const long r = idx / noct;
     const long px = r % hw, img = r / hw;
     const int cg = o / 2, oct = o % 2;
-    const unsigned char* s = src + (((img * cg_total + cg) * 4 + oct) * hw + px) * 16;
-    const half8 hi = *reinterpret_cast<const half8*>(s);
-    const half8 lo = *reinterpret_cast<const half8*>(s + 2 * hw * 16);
+    half8 hi, lo;
+    sp::load_pair(src, sp::act_piece(img, cg_total, cg, sp::quarter_of(0, oct), hw, px), 2 * hw, hi, lo);
     float* d = dst + (img * hw + px) * ld + o * 8;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      if (o * 8 + e < c) d[e] = (float)hi[e] + (float)lo[e];
+      if (o * 8 + e < c) d[e] = sp::value(hi[e], lo[e]);
   }
 }
 
@@ -1236,59 +1231,29 @@ __global__ void sp_pack_weights_up_kernel(const float* __restrict__ w, unsigned 
       cg = c0g + (int)(q / 9);
       ty0 = (int)(q % 9) / 3; ty1 = -1; tx = (int)(q % 3);
     }
-    half8 hi, lo;
+    float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int ci = cg * 16 + oct * 8 + e;
-      float v = 0.f;
+      v[e] = 0.f;
       if (n < c_out && ci < c_in) {
         const float* wp = w + ((size_t)n * c_in + ci) * 9;
-        v = wp[ty0 * 3 + tx];
-        if (ty1 >= 0) v += wp[ty1 * 3 + tx];
-        v *= wmul;
+        v[e] = wp[ty0 * 3 + tx];
+        if (ty1 >= 0) v[e] += wp[ty1 * 3 + tx];
+        v[e] *= wmul;
       }
-      v = fminf(fmaxf(v, -65504.f), 65504.f);
-      hi[e] = (_Float16)v;
-      lo[e] = (_Float16)(v - (float)hi[e]);
     }
-    unsigned char* d = wpk + (((size_t)r * 4 + oct) * cout_pad + n) * 16;
-    *reinterpret_cast<half8*>(d) = hi;
-    *reinterpret_cast<half8*>(d + (size_t)2 * cout_pad * 16) = lo;
+    sp::split_store(wpk, sp::weight_piece(r, sp::quarter_of(0, oct), cout_pad, n), (size_t)2 * cout_pad, v);
   }
 }
 
-__global__ void sp_pack_weights_kernel(const float* __restrict__ w, unsigned char* __restrict__ wpk,
-                                       int c_out, int c_in, int taps, int cout_pad, int nchunks,
-                                       float wmul, long total) {
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    long r = idx;
-    const int n = r % cout_pad; r /= cout_pad;
-    const int oct = r % 2; r /= 2;
-    const int tap = r % taps;
-    const int cg = r / taps;
-    half8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int ci = cg * 16 + oct * 8 + e;
-      float v = (n < c_out && ci < c_in) ? w[((size_t)n * c_in + ci) * taps + tap] * wmul : 0.f;
-      v = fminf(fmaxf(v, -65504.f), 65504.f);
-      hi[e] = (_Float16)v;
-      lo[e] = (_Float16)(v - (float)hi[e]);
-    }
-    unsigned char* d = wpk + ((((size_t)cg * taps + tap) * 4 + oct) * cout_pad + n) * 16;
-    *reinterpret_cast<half8*>(d) = hi;
-    *reinterpret_cast<half8*>(d + (size_t)2 * cout_pad * 16) = lo;
-  }
-}
-
-// ---- every plain-layout pack of a training step in ONE launch (dn_spconv_pack_weights_multi).  A job = one call of
-// sp_pack_weights_kernel whose weight tensor W[n][ci][tap] is given by a SOURCE VIEW of a forward weight tensor `w`:
+// ---- the plain image [chunk][tap][4 quarter][cout_pad]: ONE body, a job.  dn_spconv_pack_weights launches one job by
+// value; dn_spconv_pack_weights_multi every plain-layout pack of a training step in one launch from a table.  A job's
+// weight tensor W[n][ci][tap] is given by a SOURCE VIEW of a forward weight tensor `w`:
 //   mode 0: W[n][ci][t] = w[n][ci_first + ci][t]                              (the layer's own forward; a column cut)
 //   mode 1: W[n][ci][t] = w[ci][ci_first + n][taps - 1 - t]                    (dn_conv_dgrad_weights: flipped, transposed cut)
 //   mode 2: W[k n_in + j][ci][v] = class (py, px) = (k / 2, k % 2) of dn_conv_dgrad_class_weights over columns ci_first + j
-// -- the values the two-launch forms write through a temporary, so the packed images are the same bytes.  A workgroup finds its
-// job from the table's first-block column and walks that job's pieces with the single launch's grid-stride loop.
+// -- the values the two-launch forms write through a temporary, so the packed images are the same bytes.
 struct PackJob {
   const float* w;
   unsigned char* out;
@@ -1307,6 +1272,28 @@ __device__ inline float pack_job_elem(const PackJob& j, int n, int ci, int tap) 
   return (ty < 0 || tx < 0) ? 0.f : j.w[((size_t)ci * j.cin_total + j.ci_first + jj) * 9 + ty * 3 + tx];
 }
 
+// block `vb` of the job's n_blocks walks the job's piece pairs (chunk, tap, oct, n) with a grid-stride loop
+__device__ inline void pack_job_pieces(const PackJob& j, int vb) {
+  for (long idx = vb * (long)blockDim.x + threadIdx.x; idx < j.total; idx += (long)j.n_blocks * blockDim.x) {
+    long r = idx;
+    const int n = r % j.cout_pad; r /= j.cout_pad;
+    const int oct = r % 2; r /= 2;
+    const int tap = r % j.taps;
+    const int cg = r / j.taps;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ci = cg * 16 + oct * 8 + e;
+      v[e] = (n < j.c_out && ci < j.c_in) ? pack_job_elem(j, n, ci, tap) * j.wmul : 0.f;
+    }
+    sp::split_store(j.out, sp::weight_piece(sp::plain_block(cg, j.taps, tap), sp::quarter_of(0, oct), j.cout_pad, n),
+                    (size_t)2 * j.cout_pad, v);
+  }
+}
+
+__global__ void __launch_bounds__(256) sp_pack_weights_job_kernel(const PackJob j) { pack_job_pieces(j, blockIdx.x); }
+
+// A workgroup finds its job from the table's first-block column and walks it as the single launch does.
 __global__ void __launch_bounds__(256) sp_pack_weights_multi_kernel(const PackJob* __restrict__ jobs, int n_jobs) {
   __shared__ PackJob job;
   if (threadIdx.x == 0) {
@@ -1318,46 +1305,13 @@ __global__ void __launch_bounds__(256) sp_pack_weights_multi_kernel(const PackJo
     job = jobs[lo];
   }
   __syncthreads();
-  const PackJob& j = job;
-  const int vb = blockIdx.x - j.block_first;
-  for (long idx = vb * (long)blockDim.x + threadIdx.x; idx < j.total; idx += (long)j.n_blocks * blockDim.x) {
-    long r = idx;
-    const int n = r % j.cout_pad; r /= j.cout_pad;
-    const int oct = r % 2; r /= 2;
-    const int tap = r % j.taps;
-    const int cg = r / j.taps;
-    half8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int ci = cg * 16 + oct * 8 + e;
-      float v = (n < j.c_out && ci < j.c_in) ? pack_job_elem(j, n, ci, tap) * j.wmul : 0.f;
-      v = fminf(fmaxf(v, -65504.f), 65504.f);
-      hi[e] = (_Float16)v;
-      lo[e] = (_Float16)(v - (float)hi[e]);
-    }
-    unsigned char* d = j.out + ((((size_t)cg * j.taps + tap) * 4 + oct) * j.cout_pad + n) * 16;
-    *reinterpret_cast<half8*>(d) = hi;
-    *reinterpret_cast<half8*>(d + (size_t)2 * j.cout_pad * 16) = lo;
-  }
+  pack_job_pieces(job, blockIdx.x - job.block_first);
 }
 
 // w2 [c_out2][c_in2] * wmul -> [nt 2][ks 4][part 2][h 2][n 32] pieces (A-operand fragments)
 __global__ void sp_pack_post_kernel(const float* __restrict__ w2, unsigned char* __restrict__ out,
                                     int c_out2, int c_in2, float wmul) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (nt, ks, h, n)
-  if (idx >= 2 * 4 * 2 * 32) return;
-  const int n = idx % 32, h = (idx / 32) % 2, ks = (idx / 64) % 4, nt = idx / 256;
-  half8 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int row = nt * 32 + n, k = ks * 16 + h * 8 + e;
-    float v = (row < c_out2 && k < c_in2) ? w2[(size_t)row * c_in2 + k] * wmul : 0.f;
-    v = fminf(fmaxf(v, -65504.f), 65504.f);
-    hi[e] = (_Float16)v;
-    lo[e] = (_Float16)(v - (float)hi[e]);
-  }
-  *reinterpret_cast<half8*>(out + ((((nt * 4 + ks) * 2 + 0) * 2 + h) * 32 + n) * 16) = hi;
-  *reinterpret_cast<half8*>(out + ((((nt * 4 + ks) * 2 + 1) * 2 + h) * 32 + n) * 16) = lo;
+  sp::pack_frags(w2, c_in2, 0, c_out2, c_in2, 2, 4, wmul, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1368,7 +1322,7 @@ inline int out_dim(int in, int ksize, int stride) {
   return (in + 2 * pad - ksize) / stride + 1;
 }
 inline int cout_pad_of(int c_out) { return (c_out + 63) / 64 * 64; }
-inline int chunks_of(int c) { return (c + 15) / 16; }
+using sp::chunks_of;
 // weights are padded to whole groups of 4 chunks so that a 1x1 A group never runs past them
 // Row-merged form of a 3x3 conv whose first source is nearest-upsampled (SpTile UPM): decided by the layer
 // alone, so that pack time and run time agree.
@@ -1703,7 +1657,7 @@ unsigned* sp_range_word() {
 }
 
 extern "C" size_t dn_sp_tensor_bytes(int n_images, int h, int w, int channels) {
-  return (size_t)n_images * chunks_of(channels) * 4 * h * w * 16;
+  return sp::act_bytes(n_images, channels, (size_t)h * w);
 }
 
 extern "C" int dn_sp_from_nhwc(const float* src, int n_images, int h, int w, int channels, int ld,
@@ -1732,15 +1686,31 @@ extern "C" int dn_sp_to_nhwc(const void* src, int n_images, int h, int w, int ch
 
 extern "C" size_t dn_spconv_packed_weight_bytes(const dn_conv_desc* d) {
   if (validate(d) != DN_OK) return 0;
-  return packed_blocks(*d) * 4 * cout_pad_of(d->c_out) * 16;
+  return sp::weight_bytes(packed_blocks(*d), cout_pad_of(d->c_out));
 }
+
+namespace {
+// one plain-image job of layer `d` (no checks: the callers', block_first: the table's)
+void fill_pack_job(PackJob& j, const dn_conv_desc& d, const float* w, void* packed, int mode, int cin_total, int ci_first,
+                   int n_in, float wmul) {
+  j.w = w;
+  j.out = static_cast<unsigned char*>(packed);
+  j.c_out = d.c_out; j.c_in = d.c0 + d.c1; j.taps = d.ksize * d.ksize; j.cout_pad = cout_pad_of(d.c_out);
+  j.nchunks = packed_chunks(d);
+  j.mode = mode; j.cin_total = cin_total; j.ci_first = ci_first; j.n_in = n_in;
+  j.wmul = wmul; j.pad_ = 0; j.padf_ = 0.f;
+  j.total = (long)j.nchunks * j.taps * 2 * j.cout_pad;
+  j.n_blocks = (int)((j.total + 255) / 256 < 4096 ? (j.total + 255) / 256 : 4096);
+  j.block_first = 0;
+}
+}  // namespace
 
 extern "C" int dn_spconv_pack_weights(const dn_conv_desc* d, const float* weight_oihw, float wmul,
                                       void* packed, void* stream) {
   if (int rc = validate(d)) return rc;
   DN_REQUIRE(weight_oihw && packed, "spconv pack: null pointer");
   DN_REQUIRE(d->c1 == 0 || d->c0 % 16 == 0, "spconv pack: concat needs c0 %% 16 == 0");
-  const int taps = d->ksize * d->ksize, cp = cout_pad_of(d->c_out), nch = packed_chunks(*d);
+  const int cp = cout_pad_of(d->c_out), nch = packed_chunks(*d);
   if (up_mode(*d) == 2)
     return dn::spq_pack_weights(weight_oihw, packed, d->c_out, d->c0 + d->c1, chunks_of(d->c0), cp, nch, wmul,
                                 (hipStream_t)stream);
@@ -1749,12 +1719,10 @@ extern "C" int dn_spconv_pack_weights(const dn_conv_desc* d, const float* weight
                        (unsigned char*)packed, d->c_out, d->c0 + d->c1, chunks_of(d->c0), cp, nch, wmul);
     return dn::check_launch("sp_pack_weights_up_kernel");
   }
-  const long total = (long)nch * taps * 2 * cp;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(sp_pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                     weight_oihw, (unsigned char*)packed, d->c_out, d->c0 + d->c1, taps, cp, nch, wmul,
-                     total);
-  return dn::check_launch("sp_pack_weights_kernel");
+  PackJob j;      // the layer's own weight tensor: mode 0, all its columns
+  fill_pack_job(j, *d, weight_oihw, packed, 0, d->c0 + d->c1, 0, 0, wmul);
+  hipLaunchKernelGGL(sp_pack_weights_job_kernel, dim3(j.n_blocks), dim3(256), 0, (hipStream_t)stream, j);
+  return dn::check_launch("sp_pack_weights_job_kernel");
 }
 
 extern "C" size_t dn_spconv_pack_multi_table_bytes(int n_jobs) { return n_jobs > 0 ? sizeof(PackJob) * (size_t)n_jobs : 0; }
@@ -1782,16 +1750,9 @@ extern "C" int dn_spconv_pack_multi_prepare(const dn_pack_job* jobs, int n_jobs,
     if (q.mode == 2)
       DN_REQUIRE(taps == 9 && q.n_in > 0 && d->c_out == 4 * q.n_in && q.ci_first >= 0 && q.ci_first + q.n_in <= q.cin_total,
                  "spconv pack multi: job %d: class form needs a 3x3 layer of 4 * n_in outputs", i);
-    PackJob& j = t[i];
-    j.w = q.weight;
-    j.out = static_cast<unsigned char*>(q.packed);
-    j.c_out = d->c_out; j.c_in = c_in; j.taps = taps; j.cout_pad = cout_pad_of(d->c_out); j.nchunks = packed_chunks(*d);
-    j.mode = q.mode; j.cin_total = q.cin_total; j.ci_first = q.ci_first; j.n_in = q.n_in;
-    j.wmul = q.wmul; j.pad_ = 0; j.padf_ = 0.f;
-    j.total = (long)j.nchunks * taps * 2 * j.cout_pad;
-    j.n_blocks = (int)((j.total + 255) / 256 < 4096 ? (j.total + 255) / 256 : 4096);      // the single launch's grid
-    j.block_first = first;
-    first += j.n_blocks;
+    fill_pack_job(t[i], *d, q.weight, q.packed, q.mode, q.cin_total, q.ci_first, q.n_in, q.wmul);
+    t[i].block_first = first;
+    first += t[i].n_blocks;      // the single launch's grid
   }
   *total_blocks = first;
   return DN_OK;
@@ -1804,7 +1765,7 @@ extern "C" int dn_spconv_pack_weights_multi(const void* table_device, int n_jobs
   return dn::check_launch("sp_pack_weights_multi_kernel");
 }
 
-extern "C" size_t dn_sp_post1x1_packed_bytes(void) { return 2 * 4 * 2 * 2 * 32 * 16; }
+extern "C" size_t dn_sp_post1x1_packed_bytes(void) { return sp::frag_bytes(2, 4); }
 
 extern "C" int dn_sp_post1x1_pack_weights(const float* w2, int c_out2, int c_in2, float wmul,
                                           void* packed, void* stream) {
@@ -1825,18 +1786,14 @@ __global__ void sp_pack_heads_kernel(const float* __restrict__ w2, unsigned char
   if (idx >= 2 * 2 * 2 * 2 * 32) return;
   const int n = idx % 32, h = (idx / 32) % 2, ks = (idx / 64) % 2, nt = (idx / 128) % 2, cb = idx / 256;
   const int rows = cb ? c_out2 - split : split, row0 = cb ? split : 0;
-  half8 hi, lo;
+  float v[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int r = nt * 32 + n, k = ks * 16 + h * 8 + e;
-    float v = r < rows ? w2[(size_t)(row0 + r) * 64 + cb * 32 + k] * wmul : 0.f;
-    v = fminf(fmaxf(v, -65504.f), 65504.f);
-    hi[e] = (_Float16)v;
-    lo[e] = (_Float16)(v - (float)hi[e]);
+    v[e] = r < rows ? w2[(size_t)(row0 + r) * 64 + cb * 32 + k] * wmul : 0.f;
   }
-  unsigned char* o = out + (size_t)((((((cb * 2 + nt) * 2 + ks) * 2 + 0) * 2 + h) * 32 + n)) * 16;
-  *reinterpret_cast<half8*>(o) = hi;
-  *reinterpret_cast<half8*>(o + 2 * 32 * 16) = lo;
+  // two fragment images of 2 tiles x 2 k-steps, one per column block
+  sp::split_store(out, sp::frag_piece(cb * 2 + nt, ks, 2, 0, h, n), sp::frag_piece(0, 0, 2, 1, 0, 0), v);
 }
 }  // namespace
 

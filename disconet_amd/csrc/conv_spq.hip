@@ -30,6 +30,7 @@
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
+#include "sp_split.h"
 #include <type_traits>
 
 namespace {
@@ -666,24 +667,19 @@ __global__ void spq_pack_weights_kernel(const float* __restrict__ w, unsigned ch
       dy0 = dy1 = (int)(q % 9) / 3;
       dx0 = dx1 = (int)(q % 3);
     }
-    half8 hi, lo;
+    float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int ci = cg * 16 + oct * 8 + e;
-      float v = 0.f;
+      v[e] = 0.f;
       if (n < c_out && ci < c_in) {
         const float* wp = w + ((size_t)n * c_in + ci) * 9;
         for (int dy = dy0; dy <= dy1; ++dy)
-          for (int dx = dx0; dx <= dx1; ++dx) v += wp[dy * 3 + dx];
-        v *= wmul;
+          for (int dx = dx0; dx <= dx1; ++dx) v[e] += wp[dy * 3 + dx];
+        v[e] *= wmul;
       }
-      v = fminf(fmaxf(v, -65504.f), 65504.f);
-      hi[e] = (_Float16)v;
-      lo[e] = (_Float16)(v - (float)hi[e]);
     }
-    unsigned char* d = wpk + (((size_t)r * 4 + oct) * cout_pad + n) * 16;
-    *reinterpret_cast<half8*>(d) = hi;
-    *reinterpret_cast<half8*>(d + (size_t)2 * cout_pad * 16) = lo;
+    sp::split_store(wpk, sp::weight_piece(r, sp::quarter_of(0, oct), cout_pad, n), (size_t)2 * cout_pad, v);
   }
 }
 

@@ -27,6 +27,7 @@
 #include "dn_internal.h"
 #include "ego_list.h"
 #include "sp_device.h"
+#include "sp_split.h"
 #include <type_traits>
 
 // tools/ab (DN_FUSE_PHASES 1): every active wave of the weight-in-LDS form adds its cycles per phase into g_fuse_phase --
@@ -48,7 +49,7 @@ extern "C" int dn_fuse_phase_cycles(unsigned long long* host8, int reset) {
 namespace {
 
 constexpr int MAX_AGENTS = 8;
-constexpr size_t kW2Bytes = 8 * 2 * 2 * 32 * 16, kW3Bytes = 2 * 2 * 2 * 32 * 16;
+constexpr size_t kW2Bytes = sp::frag_bytes(1, 8), kW3Bytes = sp::frag_bytes(1, 2);
 constexpr int FUSE_G = 3;   // list slots per layer-1 pass: 3 accumulator sets (192 AGPRs) is what hipcc allocates without spilling
 // the same for the weight-in-LDS form, whose ego term holds 64 more registers: 3 spills 16 of them (tools/kernel_resources.py
 // fuse_mlp); the grouping does not change a bit of any slot's chain
@@ -560,23 +561,10 @@ __global__ void __launch_bounds__(64 * (WL > 0 ? WL : NW), (NW == 1 || WL > 0) ?
 // past the matrix are zero); `col0` = first column of the source matrix (row stride ld)
 __global__ void pack_frags_kernel(const float* __restrict__ w, int ld, int col0, int rows, int cols,
                                   int n_tiles, int ksteps, float wmul, unsigned char* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (nt, ks, h, row)
-  if (idx >= n_tiles * ksteps * 2 * 32) return;
-  const int row = idx % 32, h = (idx / 32) % 2, ks = (idx / 64) % ksteps, nt = idx / (64 * ksteps);
-  half8 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int r = nt * 32 + row, c = ks * 16 + h * 8 + e;
-    float v = (r < rows && c < cols) ? w[(size_t)r * ld + col0 + c] * wmul : 0.f;
-    v = fminf(fmaxf(v, -65504.f), 65504.f);
-    hi[e] = (_Float16)v;
-    lo[e] = (_Float16)(v - (float)hi[e]);
-  }
-  *reinterpret_cast<half8*>(out + (size_t)((((nt * ksteps + ks) * 2 + 0) * 2 + h) * 32 + row) * 16) = hi;
-  *reinterpret_cast<half8*>(out + (size_t)((((nt * ksteps + ks) * 2 + 1) * 2 + h) * 32 + row) * 16) = lo;
+  sp::pack_frags(w, ld, col0, rows, cols, n_tiles, ksteps, wmul, out);
 }
 
-inline size_t w1_bytes(int c) { return (size_t)2 * 4 * (c / 16) * 2 * 2 * 32 * 16; }
+inline size_t w1_bytes(int c) { return 2 * sp::frag_bytes(4, c / 16); }      // [W_ego | W_nbr]: 4 tiles x c / 16 k-steps each
 
 }  // namespace
 

@@ -12,46 +12,34 @@
 // (source not mounted: /root/reference/coperception is an empty submodule directory; the only
 // mounted mention of the task is /root/reference/README.md:15).
 #include "dn_internal.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+#include "sp_split.h"
 
 namespace {
-
-__device__ inline float sp_value(const half8 hi, const half8 lo, int e) { return (float)hi[e] + (float)lo[e]; }
-
-__device__ inline void sp_split(float x, _Float16& hi, _Float16& lo) {
-  x = fminf(fmaxf(x, -65504.f), 65504.f);
-  hi = (_Float16)x;
-  lo = (_Float16)(x - (float)hi);
-}
 
 // idx over (img, chunk, oct, oy, ox) of the OUTPUT, ox fastest
 __global__ void sp_maxpool2_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
                                    int cg_total, int h, int w, long total) {
   const int ho = h >> 1, wo = w >> 1;
-  const size_t ip = (size_t)h * w * 16, op = (size_t)ho * wo * 16;
+  const size_t ihw = (size_t)h * w, ohw = (size_t)ho * wo;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int ox = idx % wo;
     long r = idx / wo;
     const int oy = r % ho; r /= ho;
-    const int oct = r % 2; r /= 2;          // r = img * cg_total + cg
-    const unsigned char* s = src + ((size_t)r * 4 + oct) * ip;
+    const int oct = r % 2; r /= 2;          // r = img * cg_total + cg: chunk r of the whole tensor (of image 0)
     half8 bh, bl;
     float best[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const size_t px = ((size_t)(2 * oy + (k >> 1)) * w + 2 * ox + (k & 1)) * 16;
-      const half8 hi = *reinterpret_cast<const half8*>(s + px);
-      const half8 lo = *reinterpret_cast<const half8*>(s + 2 * ip + px);
+      half8 hi, lo;
+      sp::load_pair(src, sp::act_piece(0, cg_total, r, sp::quarter_of(0, oct), ihw, (size_t)(2 * oy + (k >> 1)) * w + 2 * ox + (k & 1)),
+                    2 * ihw, hi, lo);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float v = sp_value(hi, lo, e);
+        const float v = sp::value(hi[e], lo[e]);
         if (k == 0 || v > best[e]) { best[e] = v; bh[e] = hi[e]; bl[e] = lo[e]; }   // the pair is copied: exact
       }
     }
-    unsigned char* d = dst + ((size_t)r * 4 + oct) * op + ((size_t)oy * wo + ox) * 16;
-    *reinterpret_cast<half8*>(d) = bh;
-    *reinterpret_cast<half8*>(d + 2 * op) = bl;
+    sp::store_pair(dst, sp::act_piece(0, cg_total, r, sp::quarter_of(0, oct), ohw, (size_t)oy * wo + ox), 2 * ohw, bh, bl);
   }
 }
 
@@ -73,38 +61,29 @@ __device__ inline Lerp lerp_of(int o, int in, int out) {
 __global__ void sp_upsample2_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
                                     int cg_total, int h, int w, long total) {
   const int ho = 2 * h, wo = 2 * w;
-  const size_t ip = (size_t)h * w * 16, op = (size_t)ho * wo * 16;
+  const size_t ihw = (size_t)h * w, ohw = (size_t)ho * wo;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int ox = idx % wo;
     long r = idx / wo;
     const int oy = r % ho; r /= ho;
-    const int oct = r % 2; r /= 2;
+    const int oct = r % 2; r /= 2;          // r = img * cg_total + cg, as in sp_maxpool2_kernel
     const Lerp ty = lerp_of(oy, h, ho), tx = lerp_of(ox, w, wo);
     const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
     const float ly0 = ty.l0, ly1 = ty.l1, lx0 = tx.l0, lx1 = tx.l1;
-    const unsigned char* s = src + ((size_t)r * 4 + oct) * ip;
     auto piece = [&](int y, int x, half8& hi, half8& lo) {
-      const size_t px = ((size_t)y * w + x) * 16;
-      hi = *reinterpret_cast<const half8*>(s + px);
-      lo = *reinterpret_cast<const half8*>(s + 2 * ip + px);
+      sp::load_pair(src, sp::act_piece(0, cg_total, r, sp::quarter_of(0, oct), ihw, (size_t)y * w + x), 2 * ihw, hi, lo);
     };
-    half8 ah, al, bh, bl, ch, cl, dh, dl, oh, ol;
+    half8 ah, al, bh, bl, ch, cl, dh, dl;
     piece(y0, x0, ah, al);
     piece(y0, x1, bh, bl);
     piece(y1, x0, ch, cl);
     piece(y1, x1, dh, dl);
+    float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = ly0 * (lx0 * sp_value(ah, al, e) + lx1 * sp_value(bh, bl, e)) +
-                      ly1 * (lx0 * sp_value(ch, cl, e) + lx1 * sp_value(dh, dl, e));
-      _Float16 hi, lo;
-      sp_split(v, hi, lo);
-      oh[e] = hi;
-      ol[e] = lo;
-    }
-    unsigned char* d = dst + ((size_t)r * 4 + oct) * op + ((size_t)oy * wo + ox) * 16;
-    *reinterpret_cast<half8*>(d) = oh;
-    *reinterpret_cast<half8*>(d + 2 * op) = ol;
+    for (int e = 0; e < 8; ++e)
+      v[e] = ly0 * (lx0 * sp::value(ah[e], al[e]) + lx1 * sp::value(bh[e], bl[e])) +
+             ly1 * (lx0 * sp::value(ch[e], cl[e]) + lx1 * sp::value(dh[e], dl[e]));
+    sp::split_store(dst, sp::act_piece(0, cg_total, r, sp::quarter_of(0, oct), ohw, (size_t)oy * wo + ox), 2 * ohw, v);
   }
 }
 
@@ -309,7 +288,7 @@ extern "C" int dn_sp_maxpool2(const void* src_sp, int n_images, int h, int w, in
                               void* stream) {
   DN_REQUIRE(src_sp && dst_sp && n_images > 0 && channels > 0, "sp_maxpool2: bad arguments");
   DN_REQUIRE(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "sp_maxpool2: %d x %d is not even", h, w);
-  const int cg = (channels + 15) / 16;
+  const int cg = sp::chunks_of(channels);
   const long total = (long)n_images * cg * 2 * (h / 2) * (w / 2);
   hipLaunchKernelGGL(sp_maxpool2_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned char*)src_sp, (unsigned char*)dst_sp, cg, h, w, total);
@@ -320,7 +299,7 @@ extern "C" int dn_sp_upsample2_bilinear(const void* src_sp, int n_images, int h,
                                         void* dst_sp, void* stream) {
   DN_REQUIRE(src_sp && dst_sp && n_images > 0 && channels > 0 && h > 0 && w > 0,
              "sp_upsample2_bilinear: bad arguments");
-  const int cg = (channels + 15) / 16;
+  const int cg = sp::chunks_of(channels);
   const long total = (long)n_images * cg * 2 * (2 * h) * (2 * w);
   hipLaunchKernelGGL(sp_upsample2_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned char*)src_sp, (unsigned char*)dst_sp, cg, h, w, total);

@@ -90,8 +90,9 @@ __device__ __attribute__((always_inline)) inline f32x4 lds_table4(const f32x4* _
   return *p;
 }
 
-// x -> (hi, lo) halves, 4 values -> two dword pairs.  amax: running max |x| of what this lane has split
-// (note_range() reports it once per epilogue).
+// x -> (hi, lo) halves, 4 values -> two dword pairs: sp_split.h :: split, which states the format's values, on every
+// finite x -- another instruction sequence, chosen for the epilogues; a NaN goes through med3 here and does not become
+// -65504 as there.  amax: running max |x| of what this lane has split (note_range() reports it once per epilogue).
 // Vector form on purpose: gfx950 has v_cvt_pk_f16_f32 (two fp32 -> packed halves, round to nearest even, the scalar
 // conversion's result) and v_med3_f32 / v_max3_f32 -- 18 VALU instructions per 4 values against ~30 for the
 // element-wise form; every epilogue of the short-K layers runs this for each of its outputs.

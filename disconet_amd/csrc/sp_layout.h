@@ -1,19 +1,12 @@
-// Index maps of the split-planar ("SP") activation format and of the LDS images
-// the SP conv engine (conv_sp.hip) stages with LDS-DMA.  Pure integer functions,
-// usable from host code (tests/c_abi/check_sp_layout.cpp checks bijection and
-// ds_read_b128 bank-conflict freedom on the CPU) and from the kernels.
-//
-// SP activation tensor:  [image][C/16 chunk][4 quarter][H][W] x 16 bytes
-//   one 16-byte piece = 8 halves = channels 16*chunk + 8*oct + 0..7 of one pixel,
-//   quarter q = 2*part + oct, part 0 = hi = half(x), part 1 = lo = half(x - hi).
-//   A value is x ~= hi + lo (22-bit significand); bytes per element = 4, as fp32.
-//   This is the B-operand fragment order of v_mfma_f32_32x32x16_f16 (lane (j, h)
-//   holds k = 8h..8h+7), so a plane row is at once an HBM burst, an LDS-DMA burst
-//   and a conflict-free ds_read_b128 source.
-//
-// SP packed weights:     [chunk][tap][4 quarter][cout_pad] x 16 bytes
-//   piece = 8 halves = input channels 16*chunk + 8*oct + 0..7 of output channel n.
+// Index maps of the split-planar ("SP") f16 format: where a 16-byte piece of an activation tensor, of a
+// packed weight image and of an A-operand fragment image lies, and the LDS images the SP conv engine
+// (conv_sp.hip) stages with LDS-DMA.  Pure integer functions, usable from host code
+// (tests/c_abi/check_sp_layout.cpp checks bijection, quarter order and ds_read_b128 bank-conflict freedom on
+// the CPU) and from the kernels.  The values inside a piece -- hi = half(x), lo = half(x - hi) -- are
+// sp_split.h's.  Every unit that reads or writes the format goes through these functions; a hot kernel that
+// keeps an index written out (its ISA would change) names the function it restates.
 #pragma once
+#include <stddef.h>
 
 #if defined(__HIPCC__)
 #define SP_HD __host__ __device__ inline
@@ -22,6 +15,41 @@
 #endif
 
 namespace sp {
+
+// A piece is 16 bytes = 8 halves = 8 consecutive channels: channels 16 * chunk + 8 * oct + 0..7.
+SP_HD constexpr int chunks_of(int c) { return (c + 15) / 16; }
+// The four pieces of a chunk: part 0 = hi, part 1 = lo, each for octet 0 and 1 -> hi-oct0, hi-oct1, lo-oct0, lo-oct1.
+SP_HD constexpr int quarter_of(int part, int oct) { return 2 * part + oct; }
+
+// SP activation tensor [image][C/16 chunk][4 quarter][H][W] x 16 bytes: piece of pixel px (of hw) of one image.
+// A value is x ~= hi + lo (22-bit significand); bytes per element = 4, as fp32.  The piece is the B-operand
+// fragment order of v_mfma_f32_32x32x16_f16 (lane (j, h) holds k = 8h..8h+7), so a plane row is at once an HBM
+// burst, an LDS-DMA burst and a conflict-free ds_read_b128 source.  `quarters` = 2: the hi-only tensor
+// (dn_scatter_dense_sp_hi), whose chunks hold the two hi pieces alone.
+SP_HD constexpr size_t act_piece(size_t img, int chunks, size_t chunk, int quarter, size_t hw, size_t px, int quarters = 4) {
+  return ((img * chunks + chunk) * quarters + quarter) * hw + px;
+}
+SP_HD constexpr size_t act_bytes(size_t n_images, int channels, size_t hw, int quarters = 4) {
+  return act_piece(n_images, chunks_of(channels), 0, 0, hw, 0, quarters) * 16;
+}
+
+// SP packed weights [block][4 quarter][cout_pad] x 16 bytes: piece = input channels 16 * chunk + 8 * oct + 0..7 of
+// output channel n.  A plain image has one block per (chunk, tap); the tap-merged images (conv_sp.hip row-merged,
+// conv_spq.hip quad-merged) count their own blocks per chunk.
+SP_HD constexpr size_t weight_piece(size_t block, int quarter, int cout_pad, int n) {
+  return (block * 4 + quarter) * cout_pad + n;
+}
+SP_HD constexpr size_t weight_bytes(size_t blocks, int cout_pad) { return weight_piece(blocks, 0, cout_pad, 0) * 16; }
+SP_HD constexpr int plain_block(int chunk, int taps, int tap) { return chunk * taps + tap; }
+
+// A-operand fragment image [nt][ks][part][h][32 rows] x 16 bytes of a matrix W[rows][cols]: piece = columns
+// 16 * ks + 8 * h + 0..7 of row 32 * nt + row (fuse_mlp.hip's MLP weights, conv_sp.hip's post-1x1 weights).
+SP_HD constexpr int frag_piece(int nt, int ks, int ksteps, int part, int h, int row) {
+  return (((nt * ksteps + ks) * 2 + part) * 2 + h) * 32 + row;
+}
+SP_HD constexpr size_t frag_bytes(int n_tiles, int ksteps) { return (size_t)frag_piece(n_tiles, 0, ksteps, 0, 0, 0) * 16; }
+
+// ---- LDS images of the SP conv engine ----
 
 // ds_read_b128 is serviced in four 16-lane groups; within the low 32 lanes they are
 // g1 = {0-3, 12-15, 20-27} and g2 = {4-11, 16-19, 28-31} (MI355X_MICROARCH.md, LDS).

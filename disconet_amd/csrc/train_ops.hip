@@ -22,6 +22,7 @@
 #include "decode_device.h"
 #include "disconet_train.h"
 #include "dn_internal.h"
+#include "sp_layout.h"
 
 namespace {
 
@@ -191,6 +192,38 @@ bn_apply_v4_kernel(const float* __restrict__ z, const float* __restrict__ mean,
   }
 }
 
+// The SP copy of a BatchNorm output (sp_layout.h: [image][c / 16][4 quarters][hw] x 16 bytes), vector form of sp_split.h ::
+// split over the four channels 4 c4 .. 4 c4 + 3 of pixel `row` a thread holds.  A piece is 8 channels of one pixel = the values
+// of TWO adjacent threads (c % 16 == 0: an even / odd pair never straddles a wavefront or the end of the loop, and there is no
+// padded octet to zero): they swap halves, the even thread writes the hi piece, the odd one the lo piece.  amax: running max of
+// the clamped magnitudes, for sp_note_range.  Called by every thread of the pair (the swap is a cross-lane read).
+__device__ inline void sp_store_quad(const f32x4 v, float& amax, unsigned char* __restrict__ out, unsigned row, unsigned hw,
+                                     int c4, int c) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  typedef unsigned u2 __attribute__((ext_vector_type(2)));
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  f32x4 x;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    x[e] = fminf(fmaxf(v[e], -65504.f), 65504.f);
+    amax = fmaxf(amax, fabsf(x[e]));
+  }
+  const h4 hi = __builtin_convertvector(x, h4);
+  const h4 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), h4);
+  const u2 hu = __builtin_bit_cast(u2, hi), lu = __builtin_bit_cast(u2, lo);
+  const bool odd = c4 & 1;
+  // the even thread needs its partner's hi halves, the odd one its partner's lo halves
+  const unsigned t0 = __shfl_xor(odd ? hu[0] : lu[0], 1), t1 = __shfl_xor(odd ? hu[1] : lu[1], 1);
+  const u4 piece = odd ? u4{t0, t1, lu[0], lu[1]} : u4{hu[0], hu[1], t0, t1};
+  const unsigned img = row / hw, px = row - img * hw;
+  const int oct8 = c4 >> 1;
+  *reinterpret_cast<u4*>(out + sp::act_piece(img, c >> 4, oct8 >> 1, sp::quarter_of(odd, oct8 & 1), hw, px) * 16) = piece;
+}
+// magnitudes of split values, into the conv engine's sticky range word (sp_device.h :: note_range's rule)
+__device__ inline void sp_note_range(float amax, unsigned* __restrict__ flags) {
+  if (amax > 16384.f && flags) atomicOr(flags, amax >= 65504.f ? 3u : 2u);
+}
+
 // One group, c / 4 a power of two, fewer than 2^31 float4s (every BatchNorm of the conv stack): the general kernel above spends
 // ~300 VALU instructions per float4 on two 64-bit divisions and four 1 / sqrtf -- it is instruction-bound at ~4.8 TB/s, not
 // HBM-bound (round 5: rocprofv3 counters, profiles/r05_train_pmc.txt).  Here 1 / sqrtf(var + eps) is computed once per workgroup
@@ -216,33 +249,10 @@ bn_apply_v4_fast_kernel(const float* __restrict__ z, const float* __restrict__ m
     if (relu_mask) relu_mask[idx] = (unsigned char)((v[0] > 0.f) | ((v[1] > 0.f) << 1) | ((v[2] > 0.f) << 2) | ((v[3] > 0.f) << 3));
     if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
     *reinterpret_cast<f32x4*>(y + (size_t)row * c + 4 * c4) = v;
-    if constexpr (SP) {
-      // the SP copy of y (the next layer's forward operand on the split-f16 engine): the piece assembly of
-      // bn_bwd_apply_v4_kernel<true> -- two adjacent threads hold the 8 channels of a piece and swap halves
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      typedef unsigned u2 __attribute__((ext_vector_type(2)));
-      f32x4 x;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        x[e] = fminf(fmaxf(v[e], -65504.f), 65504.f);
-        amax = fmaxf(amax, fabsf(x[e]));
-      }
-      const h4 hi = __builtin_convertvector(x, h4);
-      const h4 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), h4);
-      const u2 hu = __builtin_bit_cast(u2, hi), lu = __builtin_bit_cast(u2, lo);
-      const bool odd = c4 & 1;
-      const unsigned t0 = __shfl_xor(odd ? hu[0] : lu[0], 1), t1 = __shfl_xor(odd ? hu[1] : lu[1], 1);
-      typedef unsigned u4 __attribute__((ext_vector_type(4)));
-      const u4 piece = odd ? u4{t0, t1, lu[0], lu[1]} : u4{hu[0], hu[1], t0, t1};
-      const unsigned img = row / hw, px = row - img * hw;
-      const int oct8 = c4 >> 1, cg = oct8 >> 1, oct = oct8 & 1, cg_total = c >> 4;
-      const size_t q = ((size_t)img * cg_total + cg) * 4 + (odd ? 2 : 0) + oct;
-      *reinterpret_cast<u4*>(y_sp + (q * hw + px) * 16) = piece;
-    }
+    // the SP copy of y: the next layer's forward operand on the split-f16 engine
+    if constexpr (SP) sp_store_quad(v, amax, y_sp, row, hw, c4, c);
   }
-  if constexpr (SP) {
-    if (amax > 16384.f && flags) atomicOr(flags, amax >= 65504.f ? 3u : 2u);
-  }
+  if constexpr (SP) sp_note_range(amax, flags);
 }
 
 __global__ void __launch_bounds__(256)
@@ -560,11 +570,8 @@ bn_bwd_reduce_v4_kernel(GradSrc src, const float* __restrict__ z, const float* _
 }
 
 // SP: a second copy of dz, multiplied by the power of two `sp_lift`, as the split-planar f16 hi / lo tensor of the inference conv
-// engine (include/disconet_hip.h "SP tensor": [image][c / 16][4 quarters][h][w] x 16 bytes, quarter = 2 * part + octet) -- the
-// operand of the split-f16 data gradient (dn_spconv2d_nhwc).  A piece is 8 channels of one pixel = the values of TWO adjacent
-// threads (c % 16 == 0: an even / odd pair never straddles a wavefront or the end of the loop): they swap halves, the even thread
-// writes the hi piece, the odd one the lo piece.  The split is dn_sp_from_nhwc's (clamp to +-65504, hi = half(x), lo = half(x - hi)),
-// magnitudes reported into the conv engine's sticky range word (`flags`).
+// engine -- the operand of the split-f16 data gradient (dn_spconv2d_nhwc) -- written by sp_store_quad, magnitudes reported into
+// the conv engine's sticky range word (`flags`).
 template <bool SP>
 __global__ void __launch_bounds__(256)
 bn_bwd_apply_v4_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
@@ -590,32 +597,9 @@ bn_bwd_apply_v4_kernel(GradSrc src, const float* __restrict__ z, const float* __
     }
     const f32x4 v = ldv4(gamma + 4 * c4) * rs * (src.v4(row, c4) - m1 - zh * m2);
     *reinterpret_cast<f32x4*>(dz + row * c + 4 * c4) = v;
-    if constexpr (SP) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      typedef unsigned u2 __attribute__((ext_vector_type(2)));
-      f32x4 x;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        x[e] = fminf(fmaxf(v[e] * sp_lift, -65504.f), 65504.f);
-        amax = fmaxf(amax, fabsf(x[e]));
-      }
-      const h4 hi = __builtin_convertvector(x, h4);
-      const h4 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), h4);
-      const u2 hu = __builtin_bit_cast(u2, hi), lu = __builtin_bit_cast(u2, lo);
-      const bool odd = c4 & 1;
-      // the even thread needs its partner's hi halves, the odd one its partner's lo halves
-      const unsigned t0 = __shfl_xor(odd ? hu[0] : lu[0], 1), t1 = __shfl_xor(odd ? hu[1] : lu[1], 1);
-      typedef unsigned u4 __attribute__((ext_vector_type(4)));
-      const u4 piece = odd ? u4{t0, t1, lu[0], lu[1]} : u4{hu[0], hu[1], t0, t1};
-      const unsigned urow = (unsigned)row, img = urow / hw, px = urow - img * hw;
-      const int oct8 = c4 >> 1, cg = oct8 >> 1, oct = oct8 & 1, cg_total = c >> 4;      // (c % 16 == 0: no padded octet to zero)
-      const size_t q = ((size_t)img * cg_total + cg) * 4 + (odd ? 2 : 0) + oct;
-      *reinterpret_cast<u4*>(dz_sp + (q * hw + px) * 16) = piece;
-    }
+    if constexpr (SP) sp_store_quad(v * sp_lift, amax, dz_sp, (unsigned)row, hw, c4, c);
   }
-  if constexpr (SP) {
-    if (amax > 16384.f && flags) atomicOr(flags, amax >= 65504.f ? 3u : 2u);
-  }
+  if constexpr (SP) sp_note_range(amax, flags);
 }
 
 // The one-group fast form of bn_bwd_apply_v4_kernel (see bn_apply_v4_fast_kernel): per channel 1 / sqrtf(var + eps) and the two
@@ -653,31 +637,9 @@ bn_bwd_apply_v4_fast_kernel(GradSrc src, const float* __restrict__ z, const floa
     const f32x4 v = ldv4(gamma + 4 * c4) * rs * (src.v4u(row, c4) - m1 - zh * m2);
     if (!SP || dz) *reinterpret_cast<f32x4*>(dz + (size_t)row * c + 4 * c4) = v;      // (dz NULL: the SP copy is the only consumer's)
     if constexpr (BIAS) bsum += v;
-    if constexpr (SP) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      typedef unsigned u2 __attribute__((ext_vector_type(2)));
-      f32x4 x;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        x[e] = fminf(fmaxf(v[e] * sp_lift, -65504.f), 65504.f);
-        amax = fmaxf(amax, fabsf(x[e]));
-      }
-      const h4 hi = __builtin_convertvector(x, h4);
-      const h4 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), h4);
-      const u2 hu = __builtin_bit_cast(u2, hi), lu = __builtin_bit_cast(u2, lo);
-      const bool odd = c4 & 1;
-      const unsigned t0 = __shfl_xor(odd ? hu[0] : lu[0], 1), t1 = __shfl_xor(odd ? hu[1] : lu[1], 1);
-      typedef unsigned u4 __attribute__((ext_vector_type(4)));
-      const u4 piece = odd ? u4{t0, t1, lu[0], lu[1]} : u4{hu[0], hu[1], t0, t1};
-      const unsigned img = row / hw, px = row - img * hw;
-      const int oct8 = c4 >> 1, cg = oct8 >> 1, oct = oct8 & 1, cg_total = c >> 4;
-      const size_t q = ((size_t)img * cg_total + cg) * 4 + (odd ? 2 : 0) + oct;
-      *reinterpret_cast<u4*>(dz_sp + (q * hw + px) * 16) = piece;
-    }
+    if constexpr (SP) sp_store_quad(v * sp_lift, amax, dz_sp, row, hw, c4, c);
   }
-  if constexpr (SP) {
-    if (amax > 16384.f && flags) atomicOr(flags, amax >= 65504.f ? 3u : 2u);
-  }
+  if constexpr (SP) sp_note_range(amax, flags);
   if constexpr (BIAS) {
     __shared__ __attribute__((aligned(16))) float bred[256][4];
     *reinterpret_cast<f32x4*>(bred[threadIdx.x]) = bsum;

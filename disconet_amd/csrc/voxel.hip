@@ -8,6 +8,7 @@
 // dense rebuild of upstream:coperception/datasets/V2XSimDet.py :: __getitem__
 // (SURVEY.md §8 a1, a2).
 #include "dn_internal.h"
+#include "sp_layout.h"
 
 namespace {
 
@@ -189,7 +190,7 @@ __global__ void scatter_dense_sp_kernel(const int32_t* __restrict__ indices,
                                         const int32_t* __restrict__ offsets, int n_images, int total,
                                         int dx, int dy, int dz, int quarters, unsigned short* __restrict__ sp) {
   const size_t hw = (size_t)dx * dy;
-  const int chunks = (dz + 15) / 16;
+  const int chunks = sp::chunks_of(dz);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     int lo = 0, hi = n_images;
     while (hi - lo > 1) {
@@ -199,8 +200,8 @@ __global__ void scatter_dense_sp_kernel(const int32_t* __restrict__ indices,
     const int ix = indices[3 * (size_t)i], iy = indices[3 * (size_t)i + 1],
               iz = indices[3 * (size_t)i + 2];
     if ((unsigned)ix < (unsigned)dx && (unsigned)iy < (unsigned)dy && (unsigned)iz < (unsigned)dz) {
-      const int cg = iz >> 4, oct = (iz >> 3) & 1, e = iz & 7;
-      sp[((((size_t)lo * chunks + cg) * quarters + oct) * hw + (size_t)ix * dy + iy) * 8 + e] = 0x3C00;
+      const int cg = iz >> 4, oct = (iz >> 3) & 1, e = iz & 7;      // half e of the hi piece of octet oct
+      sp[sp::act_piece(lo, chunks, cg, sp::quarter_of(0, oct), hw, (size_t)ix * dy + iy, quarters) * 8 + e] = 0x3C00;
     }
   }
 }
@@ -347,7 +348,7 @@ int scatter_dense_sp_impl(const int32_t* indices, const int32_t* offsets, int n_
                           void* dense_sp, int quarters, hipStream_t s) {
   DN_REQUIRE(dims && dense_sp && offsets, "scatter_dense_sp: null pointer");
   DN_REQUIRE(n_images > 0 && total >= 0 && (total == 0 || indices), "scatter_dense_sp: bad sizes");
-  const size_t bytes = (size_t)n_images * ((dims[2] + 15) / 16) * quarters * dims[0] * dims[1] * 16;
+  const size_t bytes = sp::act_bytes(n_images, dims[2], (size_t)dims[0] * dims[1], quarters);
   hipError_t e = dn::zero_fill(dense_sp, bytes, s);
   if (e != hipSuccess) return dn::fail(DN_ERR_LAUNCH, "scatter_dense_sp: memset: %s", hipGetErrorString(e));
   if (total == 0) return DN_OK;

@@ -7,7 +7,7 @@ every mutant fails it; tests/test_gpu_nhwc_conv_fp64.py holds every tile form of
 
 Operands as stored.  math 0 (exact fp32): x and w are the fp32 values themselves.  math 1 (split-f16): x is clamped to
 +-65504 and split hi = half(x), lo = half(x - hi) while it is staged (store_chunk); w is clamped and split at pack time
-WITH NO LIFT (pack_weights_split_kernel takes w as given), so for Kaiming-sized weights the lo half is an f16 subnormal
+WITH NO LIFT (dn_conv_pack_weights takes w as given), so for Kaiming-sized weights the lo half is an f16 subnormal
 and carries fewer bits -- torch's .half() rounds the same way, and the reference is computed on hi + lo of both.
 
 The layer.  y = float64 conv on those operands, * scale + shift, ReLU.  up0 = 1: source 0 nearest-upsampled x2;
