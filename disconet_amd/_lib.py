@@ -195,6 +195,8 @@ SIGNATURES = {
     "dn_agent_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(FuseMlpParams), c_void_p, c_void_p, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "dn_render_bev": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "dn_lidar_scan": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_double, c_int] +
+                      [c_void_p] * 7),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -78,6 +78,37 @@ def _device_sources(counts, agents, batch, ego_first, ego_count, own, device):
     return hit
 
 
+def _ranges_of(src, offsets, dev):
+    off = torch.from_numpy(offsets.astype(np.int32)).to(dev)
+    begin = off[src["d_image"]].contiguous()
+    sizes = np.diff(offsets)
+    return {"src": src, "begin": begin, "count": (off[src["d_next"]] - begin).contiguous(),
+            "max_count": int(sizes[src["src_image"]].max()) if len(src["src_image"]) else 0}
+
+
+def source_ranges(offsets, num_agent, agents, batch_size, ego_first=0, ego_count=None, own=False, device="cuda"):
+    """The device index tensors that holistic_views derives from the clouds' sizes and the live counts, made once and OWNED
+    BY THE CALLER: offsets [A*B + 1] (pack_clouds' / lidar.scan's host offsets), num_agent as holistic_views takes it.
+    Pass the result as holistic_views(..., ranges=...) with the same offsets, counts, egos and `own`: that call uploads
+    nothing and holds no tensor that a module cache could drop, so it can be captured into a graph.  Keep the result alive
+    as long as the graph: the graph reads these tensors at every replay."""
+    A, B = int(agents), int(batch_size)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    if len(offsets) != A * B + 1:
+        raise ValueError("%d clouds for %d agents x %d scenes" % (len(offsets) - 1, A, B))
+    counts = _live_counts(num_agent, B)
+    E = A - ego_first if ego_count is None else int(ego_count)
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    src = view_sources(counts, A, B, int(ego_first), E, own)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)      # noqa: E731
+    src = dict(src, d_view=i32(src["src_view"]), d_pose=i32(src["src_pose"]),
+               d_image=torch.tensor(src["src_image"], dtype=torch.long, device=dev),
+               d_next=torch.tensor([k + 1 for k in src["src_image"]], dtype=torch.long, device=dev))
+    return dict(_ranges_of(src, offsets, dev), key=(counts, A, B, int(ego_first), E, bool(own), offsets.tobytes()))
+
+
 def pack_clouds(points, device):
     """points: the per-image list of clouds [P_k, >= 3] (numpy arrays or tensors, agent-major: image = agent * B + b), all
     with the same number of columns -> (the concatenated float32 device tensor [P_total, columns], the host offsets
@@ -100,13 +131,15 @@ def pack_clouds(points, device):
 
 
 def holistic_views(points, trans_matrices, num_agent, batch_size, config, ego_first=0, ego_count=None, want=("dense",),
-                   own=False, device="cuda"):
+                   own=False, device="cuda", ranges=None):
     """points: per image [P_k, >= 3] (pack_clouds' input), or pack_clouds' result (pts, offsets) for a caller that keeps
     its clouds on the device; trans_matrices [B, A, A, 4, 4]; num_agent: the live counts [B] (host ints: nothing waits for
     the device) or the reference's [B, A] tensor; config: voxel_size / area_extents / map_dims (disconet_amd.Config).
     -> {"dense": [E*B, 1, X, Y, Z] float32 -- data["bev_seq_teacher"] of CoDetModule.step for the egos [ego_first,
     ego_first + ego_count), agent-major --, "bits": the same as an ops.SpTensor(bits=True)}, the keys of `want`; with own
-    also "own_dense" / "own_bits", the egos' own views (data["bev_seq"]), written by the same launch."""
+    also "own_dense" / "own_bits", the egos' own views (data["bev_seq"]), written by the same launch.
+    ranges: source_ranges' result for these offsets, counts and egos -- the call then uploads nothing and reads no module
+    cache, which is what a caller that captures it into a graph needs (and it must keep `ranges` as long as the graph)."""
     B = int(batch_size)
     A = int(trans_matrices.shape[1])
     if trans_matrices.dim() != 5 or tuple(trans_matrices.shape[2:]) != (A, 4, 4) or trans_matrices.shape[0] < B:
@@ -121,12 +154,13 @@ def holistic_views(points, trans_matrices, num_agent, batch_size, config, ego_fi
     dev = pts.device
     counts = _live_counts(num_agent, B)
     E = A - ego_first if ego_count is None else int(ego_count)
-    src = _device_sources(counts, A, B, int(ego_first), E, own, dev)
-    off = torch.from_numpy(offsets.astype(np.int32)).to(dev)
-    begin = off[src["d_image"]].contiguous()
-    count = (off[src["d_next"]] - begin).contiguous()
-    sizes = np.diff(offsets)
-    max_count = int(sizes[src["src_image"]].max()) if len(src["src_image"]) else 0
+    key = (counts, A, B, int(ego_first), E, bool(own), offsets.tobytes())
+    if ranges is not None and (ranges["key"] != key or ranges["begin"].device != dev):
+        raise ValueError("holistic_views: `ranges` was made for other clouds, live counts, egos or another device")
+    src = ranges["src"] if ranges is not None else _device_sources(counts, A, B, int(ego_first), E, own, dev)
+    if ranges is None:
+        ranges = _ranges_of(src, offsets, dev)
+    begin, count, max_count = ranges["begin"], ranges["count"], ranges["max_count"]
     poses = trans_matrices.to(device=dev, dtype=torch.float32).contiguous()
     res = ops.voxelize_views(pts, begin, count, src["d_view"], src["d_pose"], poses, src["n_views"], max_count,
                              config.voxel_size, config.area_extents, config.map_dims, want=want)

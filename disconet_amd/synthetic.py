@@ -292,6 +292,117 @@ def make_box_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_pe
 
 
 # ---------------------------------------------------------------------------
+# the same cars seen by a sensor model: ray-cast scans, occluders, the ground truth that somebody can see (lidar.py)
+# ---------------------------------------------------------------------------
+LIDAR_KEEP_OUT = 4.0             # a car whose centre is within this of a sensor is dropped (m)
+LIDAR_OCCLUDER = (4.0, 4.0, -2.0, 1.5)      # w, l, z_lo, z_hi of an occluder (m), yaw 0
+LIDAR_OCCLUDER_MARGIN = 1.5      # an occluder's footprint grown by this holds no sensor (m)
+
+
+def lidar_world_solids(num_agent, map_hw, seed, scene, boxes_per_scene, occluders):
+    """The solids of scene `scene` of make_lidar_scene_batch: (rows [n, 8] float64 = (x, y, w, l, sin, cos, z_lo, z_hi), the
+    number of cars among them -- the first rows).  The cars are make_box_scene_batch's world boxes of the same seed (the
+    RNG draws come in the same order) minus those whose centre is within LIDAR_KEEP_OUT of a sensor; up to `occluders`
+    occluders follow on the grid cells the cars did not take, in the permutation's order, skipping a cell whose occluder
+    footprint grown by LIDAR_OCCLUDER_MARGIN holds a sensor."""
+    from .config import Config
+    half = float(Config(map_hw=map_hw).area_extents[0][1])
+    cells = max(1, int(round(2 * half / BOX_SCENE_PITCH)))
+    rng = np.random.RandomState((int(seed) * 9973 + int(scene)) % (2 ** 31))
+    k = min(int(boxes_per_scene), cells * cells)
+    perm = rng.permutation(cells * cells)
+    cell = perm[:k]
+    wb = np.zeros((k, 8), dtype=np.float64)
+    wb[:, 0] = -half + (cell // cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+    wb[:, 1] = -half + (cell % cells + 0.5) * (2 * half / cells) + rng.uniform(-1.0, 1.0, k)
+    wb[:, 2] = rng.uniform(1.6, 2.4, k)
+    wb[:, 3] = rng.uniform(3.5, 5.5, k)
+    yaw = rng.uniform(-math.pi, math.pi, k)
+    wb[:, 4], wb[:, 5] = np.sin(yaw), np.cos(yaw)
+    wb[:, 6], wb[:, 7] = BOX_Z
+    sensors = np.array([agent_pose(a)[:2, 3] for a in range(num_agent)], dtype=np.float64).reshape(-1, 2)
+    far = np.ones(k, dtype=bool)
+    for sx, sy in sensors:
+        far &= np.hypot(wb[:, 0] - sx, wb[:, 1] - sy) > LIDAR_KEEP_OUT
+    cars = wb[far]
+    w, l, z_lo, z_hi = LIDAR_OCCLUDER
+    rows = []
+    for c in perm[k:]:
+        if len(rows) >= int(occluders):
+            break
+        x = -half + (c // cells + 0.5) * (2 * half / cells)
+        y = -half + (c % cells + 0.5) * (2 * half / cells)
+        if any(abs(sx - x) <= w / 2.0 + LIDAR_OCCLUDER_MARGIN and abs(sy - y) <= l / 2.0 + LIDAR_OCCLUDER_MARGIN
+               for sx, sy in sensors):
+            continue
+        rows.append([x, y, w, l, 0.0, 1.0, z_lo, z_hi])
+    return np.concatenate([cars, np.asarray(rows, dtype=np.float64).reshape(-1, 8)], 0), len(cars)
+
+
+def make_lidar_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_per_scene=24, occluders=10, beams=32,
+                           azimuths=1024, min_points=5, keep_ground=False, device=None, teacher=False, gt_rows=None):
+    """make_box_scene_batch's scenes seen through a sensor model (lidar.py; include/disconet_hip.h states the rule): the
+    same world cars (lidar_world_solids) with z from BOX_Z, plus up to `occluders` tall blocks; agent i at agent_pose(i)
+    casts beams x azimuths rays (lidar.beam_table, -30 .. +10 degrees) and keeps each ray's nearest return, so a car
+    behind a block or another car is absent from that agent's cloud, present in a neighbour's and in the teacher's holistic
+    view.  The ground truth of an image is the cars whose centre is strictly inside the extents AND on which the scene's
+    agents together have at least `min_points` returns.  Returns make_box_scene_batch's keys with the same shapes and
+    meaning ("points": per image the scan's [beams * azimuths, 4] rows, a miss a row of NaNs; "world_boxes": per scene the
+    cars [K, 6] float64), plus "gt_own_hits" [A*B, boxes_per_scene] int32 (the image's own returns on each ground-truth
+    row), "solid_hits" [A*B, boxes_per_scene + occluders] int32 and "world_solids": per scene [n, 8] float64.
+    The occluders stand on the grid cells that the cars left free: boxes_per_scene at or above the grid's cell count (64 at
+    map_hw = 256) leaves none.  gt_rows (default boxes_per_scene, and not below it) pads "gt_boxes" and "gt_own_hits" to that
+    many rows for a caller whose metric wants a fixed width, without adding cars.
+    device = None: lidar.host_scan, host_occupancy and holistic.host_holistic_views, tensors stay on the host; else
+    lidar.scan and one holistic.holistic_views(own=True) launch on `device`."""
+    from . import holistic, lidar
+    from .config import Config
+    cfg = Config(map_hw=map_hw)
+    ext, vs, dims = cfg.area_extents, cfg.voxel_size, cfg.map_dims
+    g = int(boxes_per_scene)
+    rows_out = g if gt_rows is None else int(gt_rows)
+    if rows_out < g:
+        raise ValueError("gt_rows = %d is below boxes_per_scene = %d" % (rows_out, g))
+    K = g + int(occluders)
+    solids = np.zeros((batch_size, K, 8), dtype=np.float64)
+    solid_count = np.zeros(batch_size, dtype=np.int32)
+    object_count = np.zeros(batch_size, dtype=np.int32)
+    world, world_solids = [], []
+    for b in range(batch_size):
+        rows, cars = lidar_world_solids(num_agent, map_hw, seed, b, g, occluders)
+        solids[b, :len(rows)] = rows
+        solid_count[b], object_count[b] = len(rows), cars
+        world.append(rows[:cars, :6].copy())
+        world_solids.append(rows)
+    args = (solids, solid_count, object_count, lidar.sensor_from_world(batch_size, num_agent),
+            np.full(batch_size, num_agent, dtype=np.int32), lidar.beam_table(beams, azimuths))
+    kw = dict(keep_ground=keep_ground, min_points=min_points, half_extent=float(ext[0][1]), gt_rows=rows_out)
+    trans = make_trans_matrices(batch_size, num_agent)
+    na = torch.tensor([[num_agent] * num_agent for _ in range(batch_size)], dtype=torch.int64)
+    live = [num_agent] * batch_size
+    keys = ("gt_boxes", "gt_count", "gt_own_hits", "solid_hits")
+    if device is None:
+        res = lidar.host_scan(*args, **kw)
+        points = [res["points"][i] for i in range(num_agent * batch_size)]
+        out = {"bev_seq": torch.from_numpy(np.stack([host_occupancy(p, vs, ext, dims) for p in points], 0))[:, None],
+               "trans_matrices": trans, "num_agent": na}
+        out.update({k: torch.from_numpy(res[k]) for k in keys})
+        if teacher:
+            out["bev_seq_teacher"] = torch.from_numpy(holistic.host_holistic_views(points, trans, live, batch_size, cfg)["dense"])
+    else:
+        res = lidar.scan(*args, device=device, **kw)
+        points = list(res["points"].unbind(0))
+        out = {"trans_matrices": trans.to(device), "num_agent": na.to(device)}
+        views = holistic.holistic_views(res["cloud"], out["trans_matrices"], live, batch_size, cfg, own=True, device=device)
+        out["bev_seq"] = views["own_dense"]
+        out.update({k: res[k] for k in keys})
+        if teacher:
+            out["bev_seq_teacher"] = views["dense"]
+    out["points"], out["world_boxes"], out["world_solids"] = points, world, world_solids
+    return out
+
+
+# ---------------------------------------------------------------------------
 # labelled scenes for the seg variant: the world boxes above as per-pixel classes
 # ---------------------------------------------------------------------------
 SEG_CLASS_CAR, SEG_CLASS_LONG = 1, 2      # everything else is class 0; SegDiscoNet's other five classes never occur

@@ -1044,6 +1044,59 @@ typedef struct dn_render_desc {
 
 int dn_render_bev(const dn_render_desc* desc, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Occlusion-aware lidar scenes (disconet_amd/csrc/lidar.hip, dn_version 152): a spinning lidar's rays cast from every
+ * agent's pose against the scene's solids, the nearest hit kept, and the ground truth that somebody in the scene can see.
+ * THIS IS THE PROJECT'S OWN SENSOR MODEL, not recalled from upstream: the reference ships CARLA recordings, not a
+ * simulator.  lidar.host_scan (numpy, float64) is the normative statement, which the kernels equal in every byte.
+ * Graph-capturable: one stream, no host read, nothing allocated; the library's zero-fill launch (solid_hits) and two
+ * kernels of its own.  Images are agent-major: image a * S + s is agent a of scene s.
+ *   solids            [S][K][8] float64, world frame: x, y, w, l, sin, cos, z_lo, z_hi; the footprint as in gt_boxes (w
+ *                     along the heading).  Rows at or beyond solid_count are never read: a NaN there reaches nothing.
+ *   solid_count       [S] int32, clamped to [0, K].
+ *   object_count      [S] int32, clamped to [0, solid_count]: the first object_count solids are ground-truth candidates,
+ *                     the rest are occluders.
+ *   sensor_from_world [S][A][4][4] float64 row-major = inverse(agent pose), computed by the host.  The poses are planar
+ *                     (synthetic.agent_pose): only T00, T01, T03, T10, T11, T13 are read and the sensor sits at z = 0.
+ *   num_agent         [S] int32, the live agents.  A padded agent's image (a >= num_agent[s]) is all misses with zero
+ *                     counts and no ground truth.
+ *   dirs              [R][3] float64, unit ray directions in the sensor frame (lidar.beam_table): the device evaluates no
+ *                     sin or cos.
+ *   range_jitter      nullable: [A*S][R] float32 (finite), added to the hit distance.
+ * All geometry is fp64, + - * / and comparisons only, every operation rounded on its own (no contraction).
+ * THE SCAN, one ray d = (dx, dy, dz) of image (a, s), T = sensor_from_world[s][a].  A solid (x, y, w, l, sn, cs, z_lo,
+ * z_hi) is carried into the agent's frame with synthetic.boxes_in_agent_frame's expressions:
+ *     cx = (T00 x + T01 y) + T03,  cy = (T10 x + T11 y) + T13,  s = T10 cs + T11 sn,  c = T00 cs + T01 sn.
+ * For each solid k ascending the ray (origin 0) is taken into the solid's frame and put through the slab test:
+ *     ox = (-cx) c + (-cy) s,  oy = (-cy) c - (-cx) s,  oz = 0;   ex = dx c + dy s,  ey = dy c - dx s,  ez = dz;
+ *     slabs [-(w/2), w/2] on x', [-(l/2), l/2] on y', [z_lo, z_hi] on z; per axis t0 = (lo - o) / e, t1 = (hi - o) / e,
+ *     tmin = max over axes of min(t0, t1), tmax = min over axes of max(t0, t1) (from -inf / +inf); an axis whose e is
+ *     exactly 0 makes no division: it requires lo <= o <= hi instead, else the solid is missed.
+ * The solid is hit iff 0 < tmin <= tmax and tmin <= max_range (a sensor inside a solid gets no return from it).  The
+ * nearest tmin wins, on a tie the lowest k.  The ground competes as a solid of index -1 that loses ties: for dz < 0,
+ * t = ground_z / dz, a candidate iff 0 < t <= max_range.  It competes whatever keep_ground says; with keep_ground = 0 a ray
+ * whose nearest return is the ground is reported as a miss.
+ *   points     [A*S][R][4] float32 out: float32((t + (double)jitter) d_i) per component (the sensor-frame d), column 3 =
+ *              1.0 for a solid and 0.0 for the ground; a miss is four quiet NaNs (0x7fc00000), which
+ *              dn_voxelize_occupy and dn_voxelize_views drop by their strict extent test.
+ *   hit        [A*S][R] int32 out: k, -1 for the ground, -2 for a miss.
+ *   solid_hits [A*S][K] int32 out: the rays of the image whose hit is k (integer atomics: no order dependence).
+ * THE VISIBLE GROUND TRUTH, per image, objects k < object_count ascending: the box (cx, cy, w, l, s, c) in the agent's
+ * frame by the expressions above is kept iff |cx| < half_extent and |cy| < half_extent (strict, on the fp64 values) and
+ * the sum over the scene's LIVE agents of solid_hits[.][k] is >= min_points -- somebody sees it.
+ *   gt_boxes    [A*S][G][6] float32 out, compacted in k order, rows at or beyond the count zero; boxes beyond G dropped
+ *   gt_count    [A*S] int32 out
+ *   gt_own_hits [A*S][G] int32 out: this agent's own returns on each kept box (rows beyond the count zero)
+ * DN_ERR_ARG: K outside [0, DN_LIDAR_MAX_SOLIDS] (the LDS table: 256 solids x 64 B), R, S, A or G < 1, A*S > 65535, a null
+ * required pointer (solids may be null when K == 0), max_range or half_extent not finite and > 0, ground_z not finite.
+ * ------------------------------------------------------------------------ */
+#define DN_LIDAR_MAX_SOLIDS 256
+int dn_lidar_scan(const double* solids, const int32_t* solid_count, const int32_t* object_count,
+                  const double* sensor_from_world, const int32_t* num_agent, const double* dirs, const float* range_jitter,
+                  int n_scenes, int n_agents, int k, int n_rays, double max_range, double ground_z, int keep_ground,
+                  int min_points, double half_extent, int gt_rows, float* points, int32_t* hit, int32_t* solid_hits,
+                  float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

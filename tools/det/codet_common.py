@@ -26,6 +26,18 @@ def agents_of(args):
     return args.num_agent + (1 if args.rsu else 0)
 
 
+LIDAR_SCENE_CARS = 24      # cars of a --scene lidar scene: 24 of the grid's 64 cells at map_hw = 256, so the occluders find free cells
+
+
+def lidar_scene(batch, num_agent, map_hw, seed, gt_rows, device="cuda", teacher=False):
+    """The scene of `--scene lidar` in every det tool: synthetic.make_lidar_scene_batch with LIDAR_SCENE_CARS cars and its
+    default ten occluders, the ground truth padded to the tool's `gt_rows` rows.  (The tools' box scenes ask for gt_rows
+    cars; that many would take every grid cell and leave no room for an occluder.)"""
+    from disconet_amd.synthetic import make_lidar_scene_batch
+    return make_lidar_scene_batch(batch, num_agent, map_hw, seed=seed, boxes_per_scene=min(LIDAR_SCENE_CARS, int(gt_rows)),
+                                  gt_rows=gt_rows, device=device, teacher=teacher)
+
+
 def detector_from_args(args, config):
     """the Detector of the command line (the tail's flags where the tool declares them), and the `loaded` line"""
     tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr") if hasattr(args, k)}

@@ -22,14 +22,21 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
-from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
+from codet_common import add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 
-def main(argv=None):
+def build_detect_parser():
     ap = build_parser()
     add_tail_flags(ap, 300)
-    args = ap.parse_args(argv)
+    ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
+                    help="boxes: the tool's seeded occupancy, as ever; lidar: synthetic.make_lidar_scene_batch(seed = frame), "
+                         "ray-cast scans with occluders")
+    return ap
+
+
+def main(argv=None):
+    args = build_detect_parser().parse_args(argv)
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the detection counts")
     require_com(args, ALL_DET_COM_MODES)
@@ -40,7 +47,11 @@ def main(argv=None):
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     for frame in range(args.frames):
-        scene = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
+        if args.scene == "lidar":
+            seen = lidar_scene(args.batch, num_agent, config.map_dims[0], frame, 64)
+            scene = tuple(seen[k] for k in ("bev_seq", "trans_matrices", "num_agent"))
+        else:
+            scene = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         bevs, trans, na = (t.cuda() for t in scene)

@@ -28,7 +28,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch  # noqa: E402
-from codet_common import add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
+from codet_common import add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -38,6 +38,9 @@ def build_eval_parser():
     ap = build_parser()
     add_tail_flags(ap, 300)
     ap.add_argument("--gt", choices=("synthetic", "self", "scene"), default="synthetic")
+    ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
+                    help="--gt scene: lidar = synthetic.make_lidar_scene_batch, ray-cast scans with occluders, scored against "
+                         "the boxes that somebody in the scene sees")
     return ap
 
 
@@ -46,6 +49,8 @@ def main(argv=None):
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
     require_com(args, ALL_DET_COM_MODES)
+    if args.scene == "lidar" and args.gt != "scene":
+        raise SystemExit("--scene lidar needs --gt scene: the lidar scenes are scored against their own visible boxes")
     num_agent = agents_of(args)
 
     config = Config("test", binary=True, only_det=True)
@@ -55,8 +60,11 @@ def main(argv=None):
 
     for frame in range(args.frames):
         if args.gt == "scene":
-            scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=frame, boxes_per_scene=GT_MAX_BOXES,
-                                         device="cuda")
+            if args.scene == "lidar":
+                scene = lidar_scene(args.batch, num_agent, config.map_dims[0], frame, GT_MAX_BOXES)
+            else:
+                scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=frame, boxes_per_scene=GT_MAX_BOXES,
+                                             device="cuda")
             bevs, trans, na = scene["bev_seq"], scene["trans_matrices"], scene["num_agent"]
         else:
             bevs, trans, na = make_scene_batch(args.batch, num_agent, config.map_dims[0], jitter_seed=frame)

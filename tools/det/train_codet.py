@@ -44,7 +44,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import COM_MODES, PARAM_COM_MODES, CoDetModule, Config, TeacherNet, build_model, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
-from codet_common import agents_of, require_com  # noqa: E402
+from codet_common import agents_of, lidar_scene, require_com  # noqa: E402
 
 
 TRAIN_COM_MODES = COM_MODES + ("lowerbound",) + PARAM_COM_MODES
@@ -109,6 +109,9 @@ def build_parser():
     ap.add_argument("--scenes", type=int, default=4, help="--targets boxes: the steps cycle through this many scene seeds")
     ap.add_argument("--loss_type", choices=("faf_loss", "corner_loss"), default="faf_loss",
                     help="localisation loss: smooth-L1 on the box codes, or the corner distances of the decoded boxes")
+    ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
+                    help="--targets boxes: lidar = the same cars seen by ray-cast scans with occluders "
+                         "(synthetic.make_lidar_scene_batch), the ground truth what somebody in the scene sees")
     return ap
 
 
@@ -122,8 +125,12 @@ def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, dev
     n_img = num_agent * args.batch
     if args.targets == "boxes":
         from disconet_amd import targets
-        scene = make_box_scene_batch(args.batch, num_agent, hw, seed=((epoch * 1000 + it) * world + rank) % max(1, args.scenes),
-                                     boxes_per_scene=SCENE_BOXES, device=device, teacher=bool(args.kd_flag))
+        seed = ((epoch * 1000 + it) * world + rank) % max(1, args.scenes)
+        if args.scene == "lidar":
+            scene = lidar_scene(args.batch, num_agent, hw, seed, SCENE_BOXES, device=device, teacher=bool(args.kd_flag))
+        else:
+            scene = make_box_scene_batch(args.batch, num_agent, hw, seed=seed, boxes_per_scene=SCENE_BOXES, device=device,
+                                         teacher=bool(args.kd_flag))
         data = {k: scene[k] for k in ("bev_seq", "trans_matrices", "num_agent")}
         data.update(targets.assign_targets(anchors, scene["gt_boxes"], scene["gt_count"], args.pos_thr, args.neg_thr))
         data["anchors"] = anchors
@@ -154,6 +161,8 @@ def main(argv=None):
         raise SystemExit("--com late has nothing of its own to train: train --com lowerbound and pass its checkpoint to the "
                          "det / track tools with --com late")
     require_com(args, TRAIN_COM_MODES)
+    if args.scene == "lidar" and args.targets != "boxes":
+        raise SystemExit("--scene lidar needs --targets boxes: the lidar scenes come with ground-truth boxes, not with targets")
     num_agent = agents_of(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -22,7 +22,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, BoxLayer, Config, render, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_tail_flags, agents_of, detector_from_args, require_com  # noqa: E402
+from codet_common import add_sort_flags, add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -37,6 +37,8 @@ def build_vis_parser():
     ap.add_argument("--tracks", type=int, default=0, help="1: boxes from SORT, coloured by id")
     ap.add_argument("--attention", type=int, default=0, help="1: the DiscoGraph weight sheet of every ego (--com disco)")
     ap.add_argument("--map_hw", type=int, default=256)
+    ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
+                    help="lidar: synthetic.make_lidar_scene_batch, ray-cast scans with occluders and the visible ground truth")
     return ap
 
 
@@ -59,8 +61,11 @@ def main(argv=None):
     os.makedirs(logpath, exist_ok=True)
     written = 0
     for frame in range(args.frames):
-        scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=frame, boxes_per_scene=GT_MAX_BOXES,
-                                     device="cuda")
+        if args.scene == "lidar":
+            scene = lidar_scene(args.batch, num_agent, config.map_dims[0], frame, GT_MAX_BOXES)
+        else:
+            scene = make_box_scene_batch(args.batch, num_agent, config.map_dims[0], seed=frame, boxes_per_scene=GT_MAX_BOXES,
+                                         device="cuda")
         bevs, trans, na = scene["bev_seq"].cuda(), scene["trans_matrices"].cuda(), scene["num_agent"].cuda()
         det = detector(bevs, trans, na)
         layers = []
