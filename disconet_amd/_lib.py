@@ -147,6 +147,12 @@ SIGNATURES = {
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int,
                             c_int, c_void_p]),
     "dn_ap_reset": (c_int, [c_void_p, c_int, c_void_p]),
+    "dn_gt_strata": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
+    "dn_ap_match_strata_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dn_ap_match_strata": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   POINTER(c_double), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p]),
+    "dn_ap_strata_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "dn_assign_targets_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "dn_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_double, c_double, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

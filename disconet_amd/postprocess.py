@@ -590,3 +590,314 @@ class MeanAP:
             out["per_agent"].append(row)
         out.update(n_det=int(len(scores)), n_gt=int(gt.sum()), n_tp=[int(tp[t].sum()) for t in range(len(names))])
         return out
+
+
+# ---------------------------------------------------------------------------
+# Stratified AP: every ground-truth box carries a stratum (own visibility or range from the ego, gt_strata), matching,
+# records and counters per stratum on the GPU (dn_ap_match_strata), the figures on the host from the integer records.
+#
+# The metric, for a threshold t and a stratum s: a record is LEFT OUT when its reach bit t is set (best_gt >= 0 and
+# best_iou >= t, claim won or not) and its stratum -- that of its best_gt -- is not s: it found a real box of another
+# stratum or a don't-care box (stratum -1).  Every other record stays: a true positive when its tp bit t is set (its
+# stratum is then s), a false positive otherwise (duplicates on a box of s, detections that reach nothing).  n_gt is the
+# stratum's counter; recall = TP / n_gt, NaN when n_gt == 0 (AP is then 0.0).  The row "all" leaves out only the records
+# that reach a don't-care box; its n_gt is the sum over the strata.
+# ---------------------------------------------------------------------------
+MAX_STRATA = 8           # (stratum + 1) shares a record word with the reach byte
+STRATA_MODES = {"range": 0, "visibility": 1}
+
+
+def _check_edges(mode, edges):
+    if mode not in STRATA_MODES:
+        raise ValueError("strata mode %r: one of %s" % (mode, " | ".join(STRATA_MODES)))
+    e = [float(v) for v in np.asarray(edges, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(e) <= MAX_STRATA - 1:
+        raise ValueError("%d strata edges: 1..%d are supported" % (len(e), MAX_STRATA - 1))
+    if not all(np.isfinite(v) and v > 0 for v in e) or any(b <= a for a, b in zip(e, e[1:])):
+        raise ValueError("strata edges %s: finite, positive and strictly ascending" % (e,))
+    if mode == "visibility" and not all(v >= 1 and v == int(v) and v < 2 ** 31 for v in e):
+        raise ValueError("strata edges %s: the edges of own visibility are integers >= 1 (returns)" % (e,))
+    return STRATA_MODES[mode], e
+
+
+def strata_names(mode, edges):
+    """The names of the len(edges) + 1 strata of gt_strata(mode, edges), lowest first."""
+    _, e = _check_edges(mode, edges)
+    if mode == "visibility":
+        e = [int(v) for v in e]
+        if len(e) == 1:
+            return ["hidden from the ego (< %d own returns)" % e[0], "seen by the ego (>= %d own returns)" % e[0]]
+        return ["< %d own returns" % e[0]] + ["%d..%d own returns" % (a, b - 1) for a, b in zip(e, e[1:])] + [
+            ">= %d own returns" % e[-1]]
+    return ["< %g m" % e[0]] + ["%g..%g m" % (a, b) for a, b in zip(e, e[1:])] + [">= %g m" % e[-1]]
+
+
+def host_gt_strata(gt_boxes, gt_count, mode, edges, own_hits=None):
+    """numpy statement of gt_strata (dn_gt_strata), equal to it in every word: stratum [N, G] int32 of gt_boxes [N, G, 6],
+    gt_count [N]; rows at or beyond the (clamped) count get -1.  The stratum of a row is the number of `edges` it has
+    reached.  mode "range": d2 = x * x + y * y in float64 from the float32 centre, each operation rounded on its own,
+    against the edges squared in float64 (no square root); a non-finite x or y gives -1.  mode "visibility":
+    own_hits [N, G] (a lidar scene's "gt_own_hits") against integer edges; with the single edge 5 stratum 0 is "hidden
+    from the ego", stratum 1 "seen by the ego itself"."""
+    m, e = _check_edges(mode, edges)
+    gt_boxes, gt_count = np.asarray(_host(gt_boxes), dtype=np.float32), _host(gt_count)
+    n, g = gt_boxes.shape[:2]
+    if m == 0:
+        x, y = gt_boxes[..., 0].astype(np.float64), gt_boxes[..., 1].astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = x * x + y * y
+        ok = np.isfinite(gt_boxes[..., 0]) & np.isfinite(gt_boxes[..., 1])
+        e = [q * q for q in e]
+    else:
+        if own_hits is None:
+            raise ValueError("strata by own visibility need own_hits (a lidar scene's gt_own_hits)")
+        v = np.asarray(_host(own_hits)).reshape(n, g).astype(np.float64)
+        ok = np.ones((n, g), dtype=bool)
+    st = np.zeros((n, g), dtype=np.int32)
+    for q in e:
+        with np.errstate(invalid="ignore"):
+            st += (v >= q).astype(np.int32)
+    gc = np.clip(gt_count.astype(np.int64), 0, g)
+    st[~ok | (np.arange(g)[None, :] >= gc[:, None])] = -1
+    return st
+
+
+def gt_strata(gt_boxes, gt_count, mode, edges, own_hits=None):
+    """The stratum of every ground-truth box on the GPU (dn_gt_strata; host_gt_strata is its statement and its docstring
+    the rule): device tensors gt_boxes [N, G, 6], gt_count [N], own_hits [N, G] int32 for mode "visibility" -> [N, G]
+    int32 on the device, len(edges) + 1 strata.  One launch on torch's current stream; never waits for the device."""
+    m, e = _check_edges(mode, edges)
+    for t in (gt_boxes, gt_count) + ((own_hits,) if m == 1 else ()):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.DnError("gt_strata needs device tensors (got %s); host_gt_strata is the numpy form" % type(t).__name__)
+    _need_gpu(gt_boxes, gt_count)
+    n, g = gt_boxes.shape[:2]
+    if tuple(gt_boxes.shape) != (n, g, 6) or gt_count.numel() != n or (m == 1 and tuple(own_hits.shape) != (n, g)):
+        raise ValueError("shapes: gt_boxes %s gt_count %s own_hits %s" % (
+            tuple(gt_boxes.shape), tuple(gt_count.shape), None if own_hits is None else tuple(own_hits.shape)))
+    gt_boxes, gt_count = gt_boxes.to(torch.float32).contiguous(), gt_count.to(torch.int32).contiguous()
+    own = own_hits.to(torch.int32).contiguous() if m == 1 else None
+    out = torch.empty((n, g), dtype=torch.int32, device=gt_boxes.device)
+    _lib.check(_lib.load().dn_gt_strata(_ptr(gt_boxes), _ptr(gt_count), _ptr(own), n, g, m, (ctypes.c_double * len(e))(*e),
+                                        len(e), _ptr(out), _stream()), "dn_gt_strata")
+    return out
+
+
+def _check_strata(n_strata):
+    n_strata = int(n_strata)
+    if not 1 <= n_strata <= MAX_STRATA:
+        raise ValueError("%d strata: 1..%d are supported" % (n_strata, MAX_STRATA))
+    return n_strata
+
+
+def host_match_strata(det, gt_boxes, gt_count, gt_stratum, n_strata, iou_thrs=(0.5, 0.7)):
+    """numpy reference of match_ground_truth_strata: host_match_ground_truth's dict (unchanged) plus
+    "gt_claim" [T, N, G] int32 (the rank of the detection that claimed the box at that threshold, -1 when none did and
+    beyond gt_count), "stratum" [N, K] int32 (that of the row's best_gt; -1 when it has none), "reach" [N, K] uint8 (bit t:
+    best_gt >= 0 and best_iou >= t, claim won or not), "counts" [N, S + 1] int64 (the image's boxes per stratum, the
+    don't-care boxes last) and "status" (the bits one update leaves in the accumulator's status word when every record
+    fits: 2 = a row below count had a non-finite score, 4 = a row below gt_count carried a stratum outside [-1, S), which
+    counts as -1)."""
+    thrs, s_n = _check_thrs(iou_thrs), _check_strata(n_strata)
+    out = host_match_ground_truth(det, gt_boxes, gt_count, thrs)
+    gt_count, words = _host(gt_count), np.asarray(_host(gt_stratum)).astype(np.int64)
+    n, k = out["rank"].shape
+    g = words.shape[1]
+    gc = np.clip(gt_count.astype(np.int64), 0, g)
+    below = np.arange(g)[None, :] < gc[:, None]
+    bad = (words < -1) | (words >= s_n)
+    st = np.where(bad, -1, words)
+    scores, count = _host(det["scores"]), _host(det["count"])
+    rows_below = np.arange(k)[None, :] < np.clip(count.astype(np.int64), 0, k)[:, None]
+    out["status"] = (4 if (bad & below).any() else 0) | (2 if (~np.isfinite(scores) & rows_below).any() else 0)
+    out["counts"] = np.stack([np.bincount(np.where(st[i, :gc[i]] < 0, s_n, st[i, :gc[i]]), minlength=s_n + 1)
+                              for i in range(n)]).astype(np.int64)
+    has = out["best_gt"] >= 0
+    col = np.where(has, out["best_gt"], 0)
+    out["stratum"] = np.where(has, np.take_along_axis(st, col.astype(np.int64), axis=1), -1).astype(np.int32)
+    reach = np.zeros((n, k), dtype=np.uint8)
+    claim = np.full((len(thrs), n, g), -1, dtype=np.int32)
+    for t, thr in enumerate(thrs):
+        reach |= ((has & (out["best_iou"] >= thr)).astype(np.uint8) << t).astype(np.uint8)
+        img, row = np.nonzero(out["tp"][t])
+        claim[t, img, out["best_gt"][img, row]] = out["rank"][img, row]
+    out["reach"], out["gt_claim"] = reach, claim
+    return out
+
+
+def strata_records_from_match(det, match, batch_size=1):
+    """The records one call contributes, in accumulation order (image, then rank), as dn_ap_match_strata writes them:
+    [R, 4] uint32 {score bits, agent << 8 | tp bits, (stratum + 1) << 8 | reach bits, best_gt}; `match` is
+    host_match_strata's dict."""
+    scores, rank, tp = np.asarray(_host(det["scores"]), dtype=np.float32), _host(match["rank"]), _host(match["tp"])
+    out = []
+    for img in range(scores.shape[0]):
+        rows = np.nonzero(rank[img] >= 0)[0]
+        rows = rows[np.argsort(rank[img, rows], kind="stable")]
+        bits = np.zeros(len(rows), dtype=np.uint32)
+        for t in range(tp.shape[0]):
+            bits |= tp[t, img, rows].astype(np.uint32) << np.uint32(t)
+        rec = np.empty((len(rows), 4), dtype=np.uint32)
+        rec[:, 0] = scores[img, rows].view(np.uint32)
+        rec[:, 1] = np.uint32((img // int(batch_size)) << 8) | bits
+        rec[:, 2] = ((match["stratum"][img, rows].astype(np.int64) + 1) << 8).astype(np.uint32) | match["reach"][img, rows]
+        rec[:, 3] = match["best_gt"][img, rows].astype(np.int32).view(np.uint32)
+        out.append(rec)
+    return np.concatenate(out) if out else np.zeros((0, 4), dtype=np.uint32)
+
+
+def _strata_row(scores, tp_word, st_word, thrs, stratum, n_gt):
+    """one row of the table: stratum = None is "all" """
+    st = (st_word >> 8).astype(np.int64) - 1
+    row = {"n_gt": int(n_gt), "n_counted": [], "n_left_out": [], "n_tp": []}
+    for t, thr in enumerate(thrs):
+        reach = ((st_word >> t) & 1).astype(bool)
+        left = reach & ((st == -1) if stratum is None else (st != stratum))
+        keep = ~left
+        hit = ((tp_word >> t) & 1).astype(np.uint8)[keep]
+        row["AP@%g" % thr] = average_precision_from_records(scores[keep], hit, n_gt)
+        row["recall@%g" % thr] = float(hit.sum()) / int(n_gt) if int(n_gt) else float("nan")
+        row["n_counted"].append(int(keep.sum()))
+        row["n_left_out"].append(int(left.sum()))
+        row["n_tp"].append(int(hit.sum()))
+    row["n_det"] = int(len(scores))
+    return row
+
+
+def stratified_ap_from_records(records, counts, n_strata, iou_thrs=(0.5, 0.7), names=None):
+    """The stratified figures in float64 from the integer records (the rule: the comment above host_gt_strata's section).
+    records [R, 4] 32-bit words in accumulation order (strata_records_from_match / StratifiedAP.host_records), counts
+    [n_agents, S + 1] ground-truth boxes per agent and stratum (don't-care last).  Returns {"all": row, "strata": [row +
+    "name", ...], "per_agent": [the "all" row of each agent's records, ...]}; a row is {"AP@<t>", "recall@<t>" (NaN when
+    n_gt == 0), "n_gt", "n_det" (records looked at), and per threshold "n_counted", "n_left_out", "n_tp"}."""
+    thrs, s_n = _check_thrs(iou_thrs), _check_strata(n_strata)
+    names = ["stratum %d" % s for s in range(s_n)] if names is None else [str(v) for v in names]
+    if len(names) != s_n:
+        raise ValueError("%d names for %d strata" % (len(names), s_n))
+    rec = np.ascontiguousarray(np.asarray(records)).view(np.uint32).reshape(-1, 4)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, s_n + 1)
+    scores, tp_word, st_word = rec[:, 0].copy().view(np.float32), rec[:, 1] & np.uint32(0xff), rec[:, 2]
+    agent = (rec[:, 1] >> 8).astype(np.int64)
+    per_stratum = counts[:, :s_n].sum(axis=0) if len(counts) else np.zeros(s_n, np.int64)
+    out = {"all": _strata_row(scores, tp_word, st_word, thrs, None, per_stratum.sum()), "strata": [], "per_agent": []}
+    for s in range(s_n):
+        row = {"name": names[s]}
+        row.update(_strata_row(scores, tp_word, st_word, thrs, s, per_stratum[s]))
+        out["strata"].append(row)
+    for a in range(len(counts)):
+        m = agent == a
+        out["per_agent"].append(_strata_row(scores[m], tp_word[m], st_word[m], thrs, None, counts[a, :s_n].sum()))
+    return out
+
+
+def _ap_match_strata(det, gt_boxes, gt_count, gt_stratum, n_strata, thrs, accum=None):
+    boxes, scores, count, gt_boxes, gt_count, n, k, g = _ap_inputs(det, gt_boxes, gt_count)
+    if not isinstance(gt_stratum, torch.Tensor) or tuple(gt_stratum.shape) != (n, g):
+        raise ValueError("gt_stratum: a device tensor [%d, %d] is needed (gt_strata makes one)" % (n, g))
+    _need_gpu(gt_stratum)
+    gt_stratum = gt_stratum.to(torch.int32).contiguous()
+    lib = _lib.load()
+    dev = scores.device
+    nt = len(thrs)
+    nbytes = int(lib.dn_ap_match_strata_workspace_bytes(n, k, g, nt, n_strata))
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    out = {"best_iou": torch.empty((n, k), dtype=torch.float64, device=dev),
+           "best_gt": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "rank": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "tp": torch.empty((nt, n, k), dtype=torch.uint8, device=dev),
+           "gt_claim": torch.empty((nt, n, g), dtype=torch.int32, device=dev)}
+    records, capacity, state, n_agents, batch = accum if accum is not None else (None, 0, None, 0, 1)
+    _lib.check(lib.dn_ap_match_strata(_ptr(boxes), _ptr(scores), _ptr(count), _ptr(gt_boxes), _ptr(gt_count),
+                                      _ptr(gt_stratum), n, k, g, (ctypes.c_double * nt)(*thrs), nt, n_strata,
+                                      _ptr(out["best_iou"]), _ptr(out["best_gt"]), _ptr(out["rank"]), _ptr(out["tp"]),
+                                      _ptr(out["gt_claim"]), _ptr(ws), nbytes, _ptr(records), capacity, _ptr(state),
+                                      n_agents, batch, _stream()), "dn_ap_match_strata")
+    return out
+
+
+def match_ground_truth_strata(det, gt_boxes, gt_count, gt_stratum, n_strata, iou_thrs=(0.5, 0.7)):
+    """match_ground_truth through dn_ap_match_strata: the same four tensors, bit for bit, and "gt_claim" [T, N, G] int32 --
+    the rank of the detection that claimed each ground-truth box at each threshold, -1 when none did.  gt_stratum [N, G]
+    int32 on the device (gt_strata), n_strata <= 8.  host_match_strata is the reference."""
+    return _ap_match_strata(det, gt_boxes, gt_count, gt_stratum, _check_strata(n_strata), _check_thrs(iou_thrs))
+
+
+class StratifiedAP:
+    """AP and recall per stratum of the ground truth over an evaluation run: update() after every frame's detect() with
+    the frame's gt_strata() (enqueues dn_ap_match_strata on the current stream: matching, 16-byte records and per-stratum
+    counters on the GPU, no host synchronisation), compute() once at the end (one copy of the state words and one of the
+    filled records, then stratified_ap_from_records on the host in float64).  A box with stratum -1 is a don't-care box:
+    it is counted apart and the detections that reach it are left out of every row.
+
+    Images are agent-major, `batch_size` per agent (up to 64 agents); `names` label the strata in compute()'s rows.
+    compute() raises DnError when more records arrived than `capacity`, when a row below its count carried a non-finite
+    score, or when a ground-truth row carried a stratum outside [-1, n_strata) -- never a silently wrong metric.
+
+    update() is usable inside graph.GraphedStep (forward + detect() + gt_strata() + update() in one captured graph; every
+    replay appends that frame's records).  GraphedStep runs its step three times to warm up before it captures and those
+    runs append records too: call reset() after constructing the GraphedStep, before the first replay that counts."""
+
+    def __init__(self, batch_size, n_strata, names=None, iou_thrs=(0.5, 0.7), capacity=1 << 20):
+        self.batch_size = int(batch_size)
+        self.n_strata = _check_strata(n_strata)
+        self.names = ["stratum %d" % s for s in range(self.n_strata)] if names is None else [str(v) for v in names]
+        self.iou_thrs = _check_thrs(iou_thrs)
+        self.capacity = int(capacity)
+        if self.batch_size < 1 or self.capacity < 1:
+            raise ValueError("StratifiedAP: batch_size = %d, capacity = %d, both must be positive" % (
+                self.batch_size, self.capacity))
+        if len(self.names) != self.n_strata:
+            raise ValueError("StratifiedAP: %d names for %d strata" % (len(self.names), self.n_strata))
+        self.n_agents = 0            # agents seen by update() (host-side: from the shapes only)
+        self.records = None          # [capacity, 4] int32 on the device
+        self.state = None            # [2 + MAX_AGENTS * (n_strata + 1)] int64 on the device
+
+    def _allocate(self, device):
+        self.records = torch.empty((self.capacity, 4), dtype=torch.int32, device=device)
+        self.state = torch.empty((2 + MAX_AGENTS * (self.n_strata + 1),), dtype=torch.int64, device=device)
+        self.reset()
+
+    def reset(self):
+        """Forget every record and counter (one zero-fill launch on the current stream)."""
+        if self.state is not None:
+            _lib.check(_lib.load().dn_ap_strata_reset(_ptr(self.state), MAX_AGENTS, self.n_strata, _stream()),
+                       "dn_ap_strata_reset")
+
+    def update(self, det, gt_boxes, gt_count, gt_stratum):
+        """Match one call's detections (detect()'s dict) against its ground truth and append the records.  Enqueues only.
+        Returns match_ground_truth_strata's tensors for that call."""
+        _ap_inputs(det, gt_boxes, gt_count)
+        n = det["scores"].shape[0]
+        agents = -(-n // self.batch_size)
+        if agents > MAX_AGENTS:
+            raise ValueError("StratifiedAP: %d images at batch %d are %d agents, at most %d" % (
+                n, self.batch_size, agents, MAX_AGENTS))
+        if self.state is None:
+            self._allocate(det["scores"].device)
+        self.n_agents = max(self.n_agents, agents)
+        return _ap_match_strata(det, gt_boxes, gt_count, gt_stratum, self.n_strata, self.iou_thrs,
+                                (self.records, self.capacity, self.state, MAX_AGENTS, self.batch_size))
+
+    def host_records(self):
+        """(records [R, 4] uint32, counts [n_agents, S + 1] int64, status) -- waits for the device; R = records kept (at
+        most capacity)."""
+        if self.state is None:
+            return np.zeros((0, 4), np.uint32), np.zeros((0, self.n_strata + 1), np.int64), 0
+        state = self.state.cpu().numpy()
+        filled = int(min(state[0], self.capacity))
+        rec = self.records[:filled].cpu().numpy().view(np.uint32)
+        counts = state[2:].reshape(MAX_AGENTS, self.n_strata + 1)[:self.n_agents].copy()
+        return rec, counts, int(state[1])
+
+    def compute(self):
+        """stratified_ap_from_records of everything accumulated: {"all": row, "strata": [row with "name", ...],
+        "per_agent": [row, ...]}."""
+        rec, counts, status = self.host_records()
+        if status & 1:
+            raise _lib.DnError("StratifiedAP: more detections arrived than the capacity of %d records; the metric would be "
+                               "truncated (raise `capacity`)" % self.capacity)
+        if status & 2:
+            raise _lib.DnError("StratifiedAP: a detection with a non-finite score was passed to update()")
+        if status & 4:
+            raise _lib.DnError("StratifiedAP: a ground-truth row carried a stratum outside [-1, %d)" % self.n_strata)
+        return stratified_ap_from_records(rec, counts, self.n_strata, self.iou_thrs, self.names)

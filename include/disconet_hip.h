@@ -694,6 +694,58 @@ int dn_ap_match(const float* boxes, const float* scores, const int32_t* count, c
 int dn_ap_reset(long long* state, int n_agents, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Stratified detection AP (disconet_amd/csrc/ap_match.hip, dn_version 153): every ground-truth box carries a stratum and
+ * the matching, the records and the counters are kept per stratum.  All three entries are graph-capturable: kernel
+ * launches only, no host synchronisation, no allocation; the launch sequence depends on the shapes only.  Host
+ * references: postprocess.host_gt_strata, host_match_strata, stratified_ap_from_records.
+ *
+ * dn_gt_strata: stratum [n][g] int32 of gt_boxes [n][g][6], gt_count [n] (clamped to [0, g]); rows at or beyond the
+ *   count get -1.  edges: a HOST array of n_edges doubles (read before the launch), 1 <= n_edges <= 7, finite, positive,
+ *   strictly ascending; the stratum of a row is the number of edges it has reached, 0 .. n_edges.
+ *   - mode 0, range from the ego: d2 = (double)x * (double)x + (double)y * (double)y, both products and the sum each
+ *     rounded on their own; stratum = #{e : d2 >= e2[e]} with e2[e] = edges[e] * edges[e] squared on the host in fp64 and
+ *     passed by value (no square root, no division: numpy states the same words).  A row whose x or y is not finite
+ *     gets -1.  gt_own_hits may be NULL.
+ *   - mode 1, own visibility: gt_own_hits [n][g] int32 (dn_lidar_scan's) is needed, the edges are integers >= 1;
+ *     stratum = #{e : own_hits >= edges[e]}.  With the single edge 5 (the lidar scenes' min_points) stratum 0 is
+ *     "hidden from the ego" and stratum 1 "seen by the ego itself".
+ *
+ * dn_ap_match_strata: dn_ap_match's arguments and gt_stratum [n][g] int32, n_strata S in [1, 8] and the optional output
+ *   gt_claim [n_thr][n][g] int32 (NULL skips it): the rank of the detection that claimed the box at that threshold, -1
+ *   when none did and for rows at or beyond gt_count.  rank, best_iou, best_gt and tp are dn_ap_match's, bit for bit (the
+ *   same ap_rank / ap_iou / ap_claim launches; the tp bits come from one device function).  A stratum word of a row
+ *   below gt_count outside [-1, S) counts as -1 everywhere.  -1 is a don't-care box: it can be matched and claimed, it is
+ *   counted apart, and the metric leaves out the detections that reach it.
+ *   workspace: dn_ap_match_strata_workspace_bytes(n, k, g, n_thr, S) bytes (0 for arguments the call refuses).
+ *   Accumulation (records != NULL, 16-byte aligned):
+ *   - records [capacity][4] 32-bit words, one 16-byte store each, at dn_ap_match's position (cursor + valid rows of
+ *     the images before + rank): {score bits, agent << 8 | tp bits, (stratum + 1) << 8 | reach bits, best_gt};
+ *     stratum is that of the row's best_gt, -1 when it has none; reach bit t is set when best_gt >= 0 and
+ *     best_iou >= iou_thrs[t], whether the row won the claim or is a duplicate;
+ *   - state: 2 + n_agents * (S + 1) 64-bit integers -- [0] the cursor, [1] the status: bits 0 and 1 as in dn_ap_match,
+ *     bit 2 (sticky) = a row below gt_count carried a stratum outside [-1, S); [2 + a * (S + 1) + s] the ground-truth
+ *     boxes of agent a in stratum s, s == S the don't-care boxes.  Counted per image in a workgroup with LDS integer
+ *     counters, folded in image order by the advance launch.  dn_ap_strata_reset zeroes all of it.
+ *   Only integer atomics: two runs write the same bytes.
+ *
+ * The metric (evaluated on the host in fp64 from the records, postprocess.stratified_ap_from_records), for a threshold t
+ * and a stratum s: a record is LEFT OUT when its reach bit t is set and its stratum is not s (it found a real box of
+ * another stratum, or a don't-care box); every other record stays, a true positive when its tp bit t is set (its
+ * stratum is then s), a false positive otherwise (duplicates on a box of s, detections that reach nothing).  n_gt is the
+ * stratum's counter, recall = TP / n_gt (NaN when n_gt == 0; AP is then 0).  The row "all" leaves out only the records
+ * that reach a don't-care box and has the sum of the strata's counters as n_gt.
+ * ------------------------------------------------------------------------ */
+int dn_gt_strata(const float* gt_boxes, const int32_t* gt_count, const int32_t* gt_own_hits, int n_images, int g, int mode,
+                 const double* edges, int n_edges, int32_t* stratum, void* stream);
+size_t dn_ap_match_strata_workspace_bytes(int n_images, int k, int g, int n_thr, int n_strata);
+int dn_ap_match_strata(const float* boxes, const float* scores, const int32_t* count, const float* gt_boxes,
+                       const int32_t* gt_count, const int32_t* gt_stratum, int n_images, int k, int g,
+                       const double* iou_thrs, int n_thr, int n_strata, double* best_iou, int32_t* best_gt, int32_t* rank,
+                       uint8_t* tp, int32_t* gt_claim, void* workspace, size_t workspace_bytes, void* records,
+                       long long capacity, long long* state, int n_agents, int batch, void* stream);
+int dn_ap_strata_reset(long long* state, int n_agents, int n_strata, void* stream);
+
+/* ------------------------------------------------------------------------
  * Training targets from ground-truth boxes (disconet_amd/csrc/assign.hip): the anchor assignment that the reference runs
  * on the CPU when it creates the dataset (upstream:tools/det/create_data_det.py; the SECOND / FaF rule, thresholds as
  * parameters), here per training step on the GPU.  Graph-capturable beside the training step: kernel launches only, no

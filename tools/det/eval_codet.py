@@ -4,7 +4,8 @@ detection tail (postprocess.detect) and MeanAP.update() -- all on the GPU, nothi
 mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prints them.
 
     python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
-        [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene]
+        [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene] \
+        [--strata none|range|visibility] [--strata_edges 10,20]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
     have nothing to do with the synthetic occupancy (there is no V2X-Sim data here): the figure checks the plumbing, not
@@ -18,6 +19,13 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 --com lowerbound: no collaboration.  --com late: the lowerbound detector (train `--com lowerbound`, pass its checkpoint)
     with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame
     (disconet_amd.Detector owns the model, the checkpoint and that tail).
+
+--strata range|visibility: the metric per stratum of the ground truth (postprocess.StratifiedAP in MeanAP's place, still
+    nothing read back per frame).  range: the box centre's distance from the ego, edges in metres (default 10,20: three
+    strata).  visibility: the image's own returns on the box (--scene lidar --gt scene only), default edge 5 = the
+    scenes' min_points: stratum 0 holds the boxes an ego can only learn of through collaboration.  The per-agent and
+    overall lines come from the "all" row; one line per stratum follows.  A detection that reaches a box of another
+    stratum is left out of a stratum's row, not counted as a false positive (postprocess.stratified_ap_from_records).
 """
 import os
 import sys
@@ -41,11 +49,34 @@ def build_eval_parser():
     ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
                     help="--gt scene: lidar = synthetic.make_lidar_scene_batch, ray-cast scans with occluders, scored against "
                          "the boxes that somebody in the scene sees")
+    ap.add_argument("--strata", choices=("none", "range", "visibility"), default="none",
+                    help="also print AP and recall per stratum of the ground truth: range from the ego, or the ego's own "
+                         "returns on the box (visibility: --scene lidar --gt scene only)")
+    ap.add_argument("--strata_edges", default=None,
+                    help="comma-separated ascending edges: metres for range (default 10,20), returns for visibility (default 5)")
     return ap
+
+
+STRATA_DEFAULT_EDGES = {"range": (10.0, 20.0), "visibility": (5.0,)}
+
+
+def strata_edges_of(args):
+    """the edges of --strata / --strata_edges, checked before anything is built"""
+    if args.strata_edges is None:
+        return list(STRATA_DEFAULT_EDGES[args.strata])
+    try:
+        edges = [float(v) for v in args.strata_edges.split(",")]
+        postprocess.strata_names(args.strata, edges)
+    except ValueError as e:
+        raise SystemExit("--strata_edges %s: %s" % (args.strata_edges, e))
+    return edges
 
 
 def main(argv=None):
     args = build_eval_parser().parse_args(argv)
+    if args.strata == "visibility" and not (args.scene == "lidar" and args.gt == "scene"):
+        raise SystemExit("--strata visibility needs --scene lidar --gt scene: only the lidar scenes know how many returns "
+                         "an ego's own scan put on a box")
     if args.tracking or args.visualization:
         print("note: --tracking / --visualization are accepted for compatibility; this tool prints the metric")
     require_com(args, ALL_DET_COM_MODES)
@@ -56,7 +87,13 @@ def main(argv=None):
     config = Config("test", binary=True, only_det=True)
     detector = detector_from_args(args, config)      # without --resume the weights are random: seeded, so that a run can be reproduced
     n_images = num_agent * args.batch
-    metric = postprocess.MeanAP(args.batch, capacity=max(1, args.frames * n_images * args.pre_nms_top_k))
+    capacity = max(1, args.frames * n_images * args.pre_nms_top_k)
+    if args.strata == "none":
+        metric = postprocess.MeanAP(args.batch, capacity=capacity)
+    else:
+        edges = strata_edges_of(args)
+        names = postprocess.strata_names(args.strata, edges)
+        metric = postprocess.StratifiedAP(args.batch, len(names), names=names, capacity=capacity)
 
     for frame in range(args.frames):
         if args.gt == "scene":
@@ -75,9 +112,18 @@ def main(argv=None):
             gt_boxes, gt_count = scene["gt_boxes"], scene["gt_count"]
         else:
             gt_boxes, gt_count = (t.cuda() for t in make_gt_boxes(n_images, seed=frame, max_boxes=GT_MAX_BOXES))
-        metric.update(det, gt_boxes, gt_count)
+        if args.strata == "none":
+            metric.update(det, gt_boxes, gt_count)
+        else:
+            own = scene["gt_own_hits"] if args.strata == "visibility" else None
+            metric.update(det, gt_boxes, gt_count, postprocess.gt_strata(gt_boxes, gt_count, args.strata, edges, own))
 
     res = metric.compute()
+    strata = []
+    if args.strata != "none":       # the lines below from the "all" row, under MeanAP's names
+        strata = res["strata"]
+        rows = [dict(row, **{"mAP@0.5": row["AP@0.5"], "mAP@0.7": row["AP@0.7"]}) for row in [res["all"]] + res["per_agent"]]
+        res = dict(rows[0], per_agent=rows[1:])
     what = ("ground truth = the detections themselves" if args.gt == "self" else
             "ground truth = the boxes of the scenes%s" % ("" if args.resume else ", random weights") if args.gt == "scene" else
             "synthetic ground truth%s: plumbing, not accuracy" % ("" if args.resume else " and random weights"))
@@ -87,6 +133,11 @@ def main(argv=None):
             a, row["mAP@0.5"], row["mAP@0.7"], row["n_det"], row["n_gt"], row["n_tp"][0], row["n_tp"][1]))
     print("overall: mAP@0.5 %.4f  mAP@0.7 %.4f  (%d detections, %d ground-truth boxes, true positives %d / %d)" % (
         res["mAP@0.5"], res["mAP@0.7"], res["n_det"], res["n_gt"], res["n_tp"][0], res["n_tp"][1]))
+    for s, row in enumerate(strata):
+        print("stratum %d, %s: AP@0.5 %.4f  AP@0.7 %.4f  recall %.4f / %.4f  (%d ground-truth boxes, detections counted "
+              "%d / %d, left out %d / %d)" % (
+                  s, row["name"], row["AP@0.5"], row["AP@0.7"], row["recall@0.5"], row["recall@0.7"], row["n_gt"],
+                  row["n_counted"][0], row["n_counted"][1], row["n_left_out"][0], row["n_left_out"][1]))
 
 
 if __name__ == "__main__":
