@@ -203,6 +203,9 @@ SIGNATURES = {
     "dn_render_bev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "dn_lidar_scan": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_double, c_int] +
                       [c_void_p] * 7),
+    "dn_lidar_scan_ids": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_double,
+                                                   c_int] + [c_void_p] * 8),
+    "dn_lidar_world_step": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int] + [c_void_p] * 4),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -12,7 +12,8 @@
 //                      atomics), then one global atomic per solid the workgroup hit.
 // lidar_visible_kernel grid A*S, one object per lane: the box in the agent's frame, the strict extents test, the hits
 //                      summed over the scene's live agents; the kept rows are compacted in k order (64-bit ballot,
-//                      popcount prefix per wave, wave counts through LDS, as render.hip bins its rows).
+//                      popcount prefix per wave, wave counts through LDS, as render.hip bins its rows).  With gt_ids
+//                      (dn_lidar_scan_ids) each kept row's k is written beside it, -1 beyond the count.
 #include <cmath>
 
 #include "dn_internal.h"
@@ -135,7 +136,7 @@ lidar_visible_kernel(const double* __restrict__ solids, const int32_t* __restric
                      const int32_t* __restrict__ object_count, const double* __restrict__ sensor_from_world,
                      const int32_t* __restrict__ num_agent, const int32_t* __restrict__ solid_hits, int S, int A, int K,
                      int min_points, double half_extent, int G, float* __restrict__ gt_boxes, int32_t* __restrict__ gt_count,
-                     int32_t* __restrict__ gt_own_hits) {
+                     int32_t* __restrict__ gt_own_hits, int32_t* __restrict__ gt_ids) {
 #pragma clang fp contract(off)
   __shared__ int wave_count[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -176,24 +177,24 @@ lidar_visible_kernel(const double* __restrict__ solids, const int32_t* __restric
     float* o = gt_boxes + 6 * e;
     o[0] = (float)f.cx; o[1] = (float)f.cy; o[2] = (float)row[2]; o[3] = (float)row[3]; o[4] = (float)f.s; o[5] = (float)f.c;
     gt_own_hits[e] = solid_hits[(size_t)img * K + tid];
+    if (gt_ids) gt_ids[e] = tid;
   }
   for (int g = kept + tid; g < G; g += kThreads) {
     const size_t e = (size_t)img * G + g;
 #pragma unroll
     for (int j = 0; j < 6; ++j) gt_boxes[6 * e + j] = 0.0f;
     gt_own_hits[e] = 0;
+    if (gt_ids) gt_ids[e] = -1;
   }
   if (tid == 0) gt_count[img] = kept;
 }
 
-}  // namespace
-
-extern "C" int dn_lidar_scan(const double* solids, const int32_t* solid_count, const int32_t* object_count,
-                             const double* sensor_from_world, const int32_t* num_agent, const double* dirs,
-                             const float* range_jitter, int n_scenes, int n_agents, int k, int n_rays, double max_range,
-                             double ground_z, int keep_ground, int min_points, double half_extent, int gt_rows, float* points,
-                             int32_t* hit, int32_t* solid_hits, float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits,
-                             void* stream) {
+// both entry points: gt_ids is null for dn_lidar_scan
+int lidar_scan(const double* solids, const int32_t* solid_count, const int32_t* object_count,
+               const double* sensor_from_world, const int32_t* num_agent, const double* dirs, const float* range_jitter,
+               int n_scenes, int n_agents, int k, int n_rays, double max_range, double ground_z, int keep_ground,
+               int min_points, double half_extent, int gt_rows, float* points, int32_t* hit, int32_t* solid_hits,
+               float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits, int32_t* gt_ids, void* stream) {
   DN_REQUIRE(k >= 0 && k <= DN_LIDAR_MAX_SOLIDS, "lidar_scan: K = %d solids, must be in [0, %d]", k, DN_LIDAR_MAX_SOLIDS);
   DN_REQUIRE(n_rays >= 1 && n_scenes >= 1 && n_agents >= 1 && gt_rows >= 1,
              "lidar_scan: R = %d, S = %d, A = %d, G = %d, every one must be >= 1", n_rays, n_scenes, n_agents, gt_rows);
@@ -219,6 +220,31 @@ extern "C" int dn_lidar_scan(const double* solids, const int32_t* solid_count, c
   if (int rc = dn::check_launch("lidar_scan_kernel")) return rc;
   hipLaunchKernelGGL(lidar_visible_kernel, dim3(images), dim3(kThreads), 0, s, solids, solid_count, object_count,
                      sensor_from_world, num_agent, solid_hits, n_scenes, n_agents, k, min_points, half_extent, gt_rows,
-                     gt_boxes, gt_count, gt_own_hits);
+                     gt_boxes, gt_count, gt_own_hits, gt_ids);
   return dn::check_launch("lidar_visible_kernel");
+}
+
+}  // namespace
+
+extern "C" int dn_lidar_scan(const double* solids, const int32_t* solid_count, const int32_t* object_count,
+                             const double* sensor_from_world, const int32_t* num_agent, const double* dirs,
+                             const float* range_jitter, int n_scenes, int n_agents, int k, int n_rays, double max_range,
+                             double ground_z, int keep_ground, int min_points, double half_extent, int gt_rows, float* points,
+                             int32_t* hit, int32_t* solid_hits, float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits,
+                             void* stream) {
+  return lidar_scan(solids, solid_count, object_count, sensor_from_world, num_agent, dirs, range_jitter, n_scenes, n_agents,
+                    k, n_rays, max_range, ground_z, keep_ground, min_points, half_extent, gt_rows, points, hit, solid_hits,
+                    gt_boxes, gt_count, gt_own_hits, nullptr, stream);
+}
+
+extern "C" int dn_lidar_scan_ids(const double* solids, const int32_t* solid_count, const int32_t* object_count,
+                                 const double* sensor_from_world, const int32_t* num_agent, const double* dirs,
+                                 const float* range_jitter, int n_scenes, int n_agents, int k, int n_rays, double max_range,
+                                 double ground_z, int keep_ground, int min_points, double half_extent, int gt_rows,
+                                 float* points, int32_t* hit, int32_t* solid_hits, float* gt_boxes, int32_t* gt_count,
+                                 int32_t* gt_own_hits, int32_t* gt_ids, void* stream) {
+  DN_REQUIRE(gt_ids, "lidar_scan_ids: null gt_ids");
+  return lidar_scan(solids, solid_count, object_count, sensor_from_world, num_agent, dirs, range_jitter, n_scenes, n_agents,
+                    k, n_rays, max_range, ground_z, keep_ground, min_points, half_extent, gt_rows, points, hit, solid_hits,
+                    gt_boxes, gt_count, gt_own_hits, gt_ids, stream);
 }

@@ -403,6 +403,120 @@ def make_lidar_scene_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, boxes_
 
 
 # ---------------------------------------------------------------------------
+# a world that moves: the frame-0 description of a lidar sequence (lidar.world_step / lidar.Sequence)
+# ---------------------------------------------------------------------------
+LIDAR_LANES = ((-2.5, 1.0), (2.5, -1.0), (-7.5, 1.0), (7.5, -1.0))   # (y, direction along x)
+LIDAR_LANE_PITCH = 10.0          # slots along a lane (m), jittered by at most +-1.5 m
+LIDAR_LANE_SPEED = (0.3, 0.8)    # a lane's speed is uniform in this range (m per frame)
+LIDAR_LANE_REACH = 60.0          # slots cover x in [-60, 60]
+LIDAR_PARK_Y = 13.5              # the two bands of parked cars and occluders, y = +-13.5
+LIDAR_PARK_PITCH = 9.0           # slots along a band (m), jittered by at most +-1 m: two 5.5 m cars at any yaw (circumscribed
+                                 # radius < 3.01 m) then keep 7 - 6.02 > 0.5 m between their footprints
+LIDAR_CLEARANCE = 0.5            # no two footprints come closer than this in any frame (m)
+
+
+def make_lidar_world(num_agent=2, map_hw=256, seed=0, scene=0, frames=40, fill=0.8, park_fill=0.8, occluder_share=0.4,
+                     van_share=0.2, rows=None):
+    """The seeded description of one moving world, scene `scene` of sequence seed `seed`: lidar.host_world_step's arrays with
+    S = 1 -- "solids0" [1, K, 8] float64 (dn_lidar_scan's rows at frame 0), "solid_vel" [1, K, 2], "solid_count" [1],
+    "agent0" [1, A, 4] (x, y, sin, cos), "agent_vel" [1, A, 2] (metres per frame) -- plus "object_count" [1] (the cars: the
+    first rows, the occluders follow), "num_agent" [1] and "world": {"frames", "lanes": per lane (y, direction, speed),
+    "agent_lane", "half_extent"}.  rows: K, the solids padded with zero rows beyond the count (default: the count), so that
+    worlds of several seeds share one shape.
+
+    Four lanes run parallel to x (LIDAR_LANES: y = +-2.5 and +-7.5, traffic on the right), each with one speed ~
+    U(LIDAR_LANE_SPEED) m per frame; slots every LIDAR_LANE_PITCH over +-LIDAR_LANE_REACH, jittered by +-1.5 m, are filled
+    with probability `fill`: a share `van_share` of them with a moving LIDAR_OCCLUDER block (a van: it hides the lanes and
+    the band behind it from one side of the road while an agent on the other side still sees them), the rest with a car,
+    its long side (l) along x: the heading (cos, sin) = (0, direction), as w lies along the heading.  Agent a rides in
+    lane a % 4 in a slot of its own (a sensor, not a solid), heading along its travel, in the free slot that brings it
+    nearest x = 0 at the middle frame; the first two ride in the two central lanes.  Parked cars at any yaw and standing
+    LIDAR_OCCLUDER blocks (a share `occluder_share` of the `park_fill` filled slots) stand in the two bands y =
+    +-LIDAR_PARK_Y; nothing moves behind a band, where every agent's view would be shadowed at once and a car would come
+    and go from the ground truth.  For every frame (nothing depends on f: a lane shares one velocity) footprints keep
+    LIDAR_CLEARANCE: along a lane 10 - 3 - 5.5 m, across lanes 5 - 4 m (two vans), lane to band 6 - 2 - 3.01 m, along a
+    band 9 - 2 - 6.02 m; a sensor is 7 m or more from a car centre in its lane and 5 m from one in another (LIDAR_KEEP_OUT
+    is 4), and 5 - 2 m or more from an occluder's footprint (LIDAR_OCCLUDER_MARGIN is 1.5).  The occluders' rows carry a
+    velocity too: a van's is its lane's."""
+    from .config import Config
+    A, frames = int(num_agent), int(frames)
+    if A < 1 or frames < 1:
+        raise ValueError("num_agent = %d, frames = %d: both must be >= 1" % (A, frames))
+    rng = np.random.RandomState((int(seed) * 9973 + int(scene) * 131 + 7) % (2 ** 31))
+    slots = np.arange(-LIDAR_LANE_REACH, LIDAR_LANE_REACH + 1e-9, LIDAR_LANE_PITCH)
+    lanes, cars, vel, blocks, block_vel = [], [], [], [], []
+    ow, ol, oz_lo, oz_hi = LIDAR_OCCLUDER
+    agent0 = np.zeros((A, 4), dtype=np.float64)
+    agent_vel = np.zeros((A, 2), dtype=np.float64)
+    riders = {}
+    for a in range(A):
+        riders.setdefault(a % len(LIDAR_LANES), []).append(a)
+    for lane, (y, direction) in enumerate(LIDAR_LANES):
+        speed = float(rng.uniform(*LIDAR_LANE_SPEED))
+        x = slots + rng.uniform(-1.5, 1.5, len(slots))
+        filled = rng.uniform(0.0, 1.0, len(slots)) < fill
+        w = rng.uniform(1.6, 2.4, len(slots))
+        l = rng.uniform(3.5, 5.5, len(slots))
+        van = rng.uniform(0.0, 1.0, len(slots)) < van_share
+        lanes.append((y, direction, speed))
+        taken = set()
+        for a in riders.get(lane, ()):                         # the free slot nearest to where the middle frame is at x = 0
+            want = -direction * speed * (frames - 1) / 2.0
+            order = [int(i) for i in np.argsort(np.abs(slots - want), kind="stable") if int(i) not in taken]
+            taken.add(order[0])
+            agent0[a] = (x[order[0]], y, 0.0, direction)       # yaw 0 or pi: sin exactly 0
+            agent_vel[a] = (direction * speed, 0.0)
+        for i in range(len(slots)):
+            if filled[i] and i not in taken and van[i]:
+                blocks.append([x[i], y, ow, ol, 0.0, 1.0, oz_lo, oz_hi])
+                block_vel.append([direction * speed, 0.0])
+            elif filled[i] and i not in taken:
+                cars.append([x[i], y, w[i], l[i], direction, 0.0, BOX_Z[0], BOX_Z[1]])
+                vel.append([direction * speed, 0.0])
+    park = np.arange(-LIDAR_LANE_REACH, LIDAR_LANE_REACH + 1e-9, LIDAR_PARK_PITCH)
+    for y in (-LIDAR_PARK_Y, LIDAR_PARK_Y):
+        x = park + rng.uniform(-1.0, 1.0, len(park))
+        filled = rng.uniform(0.0, 1.0, len(park)) < park_fill
+        block = rng.uniform(0.0, 1.0, len(park)) < occluder_share
+        w = rng.uniform(1.6, 2.4, len(park))
+        l = rng.uniform(3.5, 5.5, len(park))
+        yaw = rng.uniform(-math.pi, math.pi, len(park))
+        for i in range(len(park)):
+            if not filled[i]:
+                continue
+            if block[i]:
+                blocks.append([x[i], y, ow, ol, 0.0, 1.0, oz_lo, oz_hi])
+                block_vel.append([0.0, 0.0])
+            else:
+                cars.append([x[i], y, w[i], l[i], math.sin(yaw[i]), math.cos(yaw[i]), BOX_Z[0], BOX_Z[1]])
+                vel.append([0.0, 0.0])
+    n = len(cars) + len(blocks)
+    K = n if rows is None else int(rows)
+    if K < n:
+        raise ValueError("rows = %d is below the world's %d solids" % (K, n))
+    solids0 = np.zeros((1, K, 8), dtype=np.float64)
+    solid_vel = np.zeros((1, K, 2), dtype=np.float64)
+    solids0[0, :n] = np.asarray(cars + blocks, dtype=np.float64).reshape(-1, 8)
+    solid_vel[0, :n] = np.asarray(vel + block_vel, dtype=np.float64).reshape(-1, 2)
+    return {"solids0": solids0, "solid_vel": solid_vel, "solid_count": np.array([n], dtype=np.int32),
+            "object_count": np.array([len(cars)], dtype=np.int32), "agent0": agent0[None], "agent_vel": agent_vel[None],
+            "num_agent": np.array([A], dtype=np.int32),
+            "world": {"frames": frames, "lanes": lanes, "agent_lane": [a % len(LIDAR_LANES) for a in range(A)],
+                      "half_extent": float(Config(map_hw=map_hw).area_extents[0][1])}}
+
+
+def make_lidar_world_batch(batch_size=1, num_agent=2, map_hw=256, seed=0, frames=40, rows=None, **kw):
+    """make_lidar_world's scenes 0 .. batch_size - 1 of one seed as one description with S = batch_size, the solids padded
+    to a common K (`rows`, default the largest count); "world" is the list of the scenes' metadata."""
+    worlds = [make_lidar_world(num_agent, map_hw, seed, b, frames, **kw) for b in range(int(batch_size))]
+    K = max(int(w["solid_count"][0]) for w in worlds) if rows is None else int(rows)
+    worlds = [make_lidar_world(num_agent, map_hw, seed, b, frames, rows=K, **kw) for b in range(int(batch_size))]
+    out = {k: np.concatenate([w[k] for w in worlds], 0) for k in worlds[0] if k != "world"}
+    out["world"] = [w["world"] for w in worlds]
+    return out
+
+
+# ---------------------------------------------------------------------------
 # labelled scenes for the seg variant: the world boxes above as per-pixel classes
 # ---------------------------------------------------------------------------
 SEG_CLASS_CAR, SEG_CLASS_LONG = 1, 2      # everything else is class 0; SegDiscoNet's other five classes never occur

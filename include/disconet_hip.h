@@ -1149,6 +1149,56 @@ int dn_lidar_scan(const double* solids, const int32_t* solid_count, const int32_
                   int min_points, double half_extent, int gt_rows, float* points, int32_t* hit, int32_t* solid_hits,
                   float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Lidar sequences (disconet_amd/csrc/lidar_seq.hip and lidar.hip, dn_version 154): the scan's world at frame f, and the
+ * identities of the scan's ground truth.
+ *
+ * dn_lidar_scan_ids is dn_lidar_scan with one more output through the same two kernels (dn_lidar_scan passes null):
+ *   gt_ids [A*S][G] int32 out: the solid index k of each kept row of gt_boxes; rows at or beyond gt_count are -1.
+ * Every other output has dn_lidar_scan's bytes.  DN_ERR_ARG: dn_lidar_scan's cases, and a null gt_ids.
+ *
+ * dn_lidar_world_step moves the world: one launch, grid S (one workgroup per scene), graph-capturable, no host read,
+ * nothing allocated.  Motion is closed-form, not integrated: the state at frame f depends on f only, so the world is
+ * random-access and lidar.host_world_step (numpy, float64) states it exactly -- the kernel equals it in every byte.
+ *   solids0     [S][K][8] float64, the frame-0 rows in dn_lidar_scan's layout
+ *   solid_vel   [S][K][2] float64, metres per frame
+ *   solid_count [S] int32, clamped to [0, K] as the scan does
+ *   agent0      [S][A][4] float64: x, y, sin, cos of each sensor's pose at frame 0
+ *   agent_vel   [S][A][2] float64, metres per frame
+ *   frame       [S] int32, the cursor, in and out
+ * Everything is fp64, + - * only, every operation rounded on its own (no contraction).  t = (double)frame[s].
+ * SOLIDS.  Row k < solid_count[s]: x = x0 + t * vx, y = y0 + t * vy (one product and one sum each); columns 2 to 7 are
+ * copied as bytes.  A row at or beyond solid_count is the frame-0 row's bytes, all 8 columns, with no arithmetic: a NaN
+ * there keeps its payload.
+ * SENSORS.  Agent a: x, y as for a solid, (sn, cs) as given; T = sensor_from_world[s][a] = inverse of the planar pose:
+ *     T00 = cs,   T01 = sn,  T03 = -((cs * x) + (sn * y)),
+ *     T10 = -sn,  T11 = cs,  T13 = (sn * x) - (cs * y),
+ *     T22 = T33 = 1, every other entry +0.0.
+ * TRANS.  trans[s][i][j] = T_i^-1 T_j in synthetic.make_trans_matrices' layout and meaning.  For i != j, with Ti =
+ * sensor_from_world[s][i] and (xj, yj, sj, cj) agent j's pose at the frame:
+ *     r00 = Ti00 cj + Ti01 sj,  r01 = Ti01 cj - Ti00 sj,  r03 = (Ti00 xj + Ti01 yj) + Ti03,
+ *     r10 = Ti10 cj + Ti11 sj,  r11 = Ti11 cj - Ti10 sj,  r13 = (Ti10 xj + Ti11 yj) + Ti13,
+ *     r22 = r33 = 1, the rest 0; each result is rounded once to float32.  i == j is the exact identity.
+ * All A agents are computed: the call takes no num_agent (the scan ignores padded agents).
+ *   solids            [S][K][8] float64 out
+ *   sensor_from_world [S][A][4][4] float64 out
+ *   trans             [S][A][A][4][4] float32 out
+ * THE CURSOR.  Every lane of workgroup s reads frame[s] before a barrier and lane 0 writes frame[s] + 1 after it; a
+ * workgroup touches no other scene's cursor.  A replay of the captured step therefore advances the world with nothing
+ * uploaded.  The caller may write the cursor to seek; negative frames are legal and exact.
+ * DN_ERR_ARG: K outside [0, DN_LIDAR_MAX_SOLIDS], S or A < 1, a null required pointer (solids0, solid_vel and solids may
+ * be null when K == 0).
+ * ------------------------------------------------------------------------ */
+int dn_lidar_scan_ids(const double* solids, const int32_t* solid_count, const int32_t* object_count,
+                      const double* sensor_from_world, const int32_t* num_agent, const double* dirs,
+                      const float* range_jitter, int n_scenes, int n_agents, int k, int n_rays, double max_range,
+                      double ground_z, int keep_ground, int min_points, double half_extent, int gt_rows, float* points,
+                      int32_t* hit, int32_t* solid_hits, float* gt_boxes, int32_t* gt_count, int32_t* gt_own_hits,
+                      int32_t* gt_ids, void* stream);
+int dn_lidar_world_step(const double* solids0, const double* solid_vel, const int32_t* solid_count, const double* agent0,
+                        const double* agent_vel, int32_t* frame, int n_scenes, int n_agents, int k, double* solids,
+                        double* sensor_from_world, float* trans, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

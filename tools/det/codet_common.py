@@ -38,6 +38,35 @@ def lidar_scene(batch, num_agent, map_hw, seed, gt_rows, device="cuda", teacher=
                                   gt_rows=gt_rows, device=device, teacher=teacher)
 
 
+LIDAR_SEQUENCE_ROWS = 128    # solids (K) and ground-truth rows (G) of a --source lidar / --sequence_frames world: every slot of
+                             # synthetic.make_lidar_world filled is 80 solids, so worlds of every seed share these shapes
+
+
+def lidar_sequence(batch, num_agent, config, seed, frames, device="cuda"):
+    """The moving world of `--source lidar` (track tools) and `--scene lidar --sequence_frames N` (train_codet.py): the
+    lidar.Sequence of synthetic.make_lidar_world_batch(seed = the sequence seed), solids and ground truth padded to
+    LIDAR_SEQUENCE_ROWS rows, so that every seed's ground truth has one width."""
+    from disconet_amd import lidar
+    from disconet_amd.synthetic import make_lidar_world_batch
+    world = make_lidar_world_batch(batch, num_agent, config.map_dims[0], seed=seed, frames=max(1, int(frames)),
+                                   rows=LIDAR_SEQUENCE_ROWS)
+    return lidar.Sequence(world, config, gt_rows=LIDAR_SEQUENCE_ROWS, device=device)
+
+
+def add_source_flags(ap, default):
+    """--source / --detections of the track tools"""
+    ap.add_argument("--source", choices=("net", "boxes", "lidar"), default=default,
+                    help="lidar: a moving world scanned frame after frame inside the captured step (lidar.Sequence), "
+                         "--seed picks the sequence")
+    ap.add_argument("--detections", choices=("net", "truth"), default="net",
+                    help="--source lidar: truth feeds the frame's ground-truth boxes to SORT in place of the network")
+
+
+def check_source_flags(args):
+    if args.detections == "truth" and args.source != "lidar":
+        raise SystemExit("--detections truth needs --source lidar: the other sources have no per-frame ground truth to feed")
+
+
 def detector_from_args(args, config):
     """the Detector of the command line (the tail's flags where the tool declares them), and the `loaded` line"""
     tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr") if hasattr(args, k)}

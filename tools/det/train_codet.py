@@ -10,7 +10,8 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
     python tools/det/train_codet.py --com disco|sum|mean|max|lowerbound|agent [--batch 4] [--nepoch 2] [--steps_per_epoch 8] \
         [--kd_flag 1 --resume_teacher teacher.pth --kd_weight 100000] [--resume epoch_1.pth] \
         [--logpath logs/] [--num_agent 5] [--layer 3] [--compress_level 0] [--only_v2i 0] \
-        [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4] [--loss_type faf_loss|corner_loss]
+        [--targets synthetic|boxes] [--pos_thr 0.6] [--neg_thr 0.45] [--scenes 4] [--loss_type faf_loss|corner_loss] \
+        [--scene boxes|lidar] [--sequence_frames 0]
 
 --targets synthetic (default): random occupancy and synthetic.make_train_targets (Bernoulli noise per anchor).
 --targets boxes: synthetic.make_box_scene_batch -- scenes whose occupancy shows their ground-truth boxes -- with
@@ -24,6 +25,11 @@ writing `epoch_N.pth` with the reference's checkpoint keys.
 
     Without --resume_teacher the teacher keeps its initial weights: the distillation target is then meaningless and only
     the plumbing is exercised (the tool says so).  Training the teacher itself is not built yet (TeacherNet is eval() only).
+
+--scene lidar --sequence_frames N (N > 0, with --targets boxes): moving worlds instead of standing scenes -- a step's scene
+    is sequence seed it % --scenes ((it * world + rank) % --scenes with several ranks; synthetic.make_lidar_world through
+    lidar.Sequence) sought to frame (steps so far // --scenes) % N, the targets assigned from that frame's ground truth.  `eval_sort.py --source lidar --resume <logpath>/epoch_N.pth` then
+    tracks with a detector that has seen moving worlds; --seed at or above --scenes picks a world it was not trained on.
 
 --loss_type faf_loss (default): focal + smooth-L1 on the box codes.  corner_loss: focal + the corner distances of the decoded
     boxes (Config.loss_type, train_ops.det_loss_corner); the anchors it decodes against ride in data["anchors"].
@@ -44,7 +50,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import COM_MODES, PARAM_COM_MODES, CoDetModule, Config, TeacherNet, build_model, load_checkpoint  # noqa: E402
 from disconet_amd.synthetic import make_bevs, make_box_scene_batch, make_scene_batch, make_train_targets  # noqa: E402
-from codet_common import agents_of, lidar_scene, require_com  # noqa: E402
+from codet_common import agents_of, lidar_scene, lidar_sequence, require_com  # noqa: E402
 
 
 TRAIN_COM_MODES = COM_MODES + ("lowerbound",) + PARAM_COM_MODES
@@ -112,6 +118,10 @@ def build_parser():
     ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
                     help="--targets boxes: lidar = the same cars seen by ray-cast scans with occluders "
                          "(synthetic.make_lidar_scene_batch), the ground truth what somebody in the scene sees")
+    ap.add_argument("--sequence_frames", type=int, default=0,
+                    help="--scene lidar: N > 0 trains on moving worlds (lidar.Sequence): a step's scene is sequence seed "
+                         "it %% --scenes (with several ranks (it * world + rank) %% --scenes) sought to frame "
+                         "(steps so far // --scenes) %% N; 0: the static lidar scenes")
     return ap
 
 
@@ -120,13 +130,35 @@ def parse_args(argv=None):
     return _rsu_from_leftovers(args, rest)
 
 
-def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, device="cuda"):
+_SEQUENCES = {}      # --sequence_frames: sequence seed -> its lidar.Sequence (a few small device tensors each)
+
+
+def sequence_frame(args, num_agent, config, epoch, it, world=1, rank=0, device="cuda"):
+    """--scene lidar --sequence_frames N: the scene of step `it` -- sequence seed (it * world + rank) % --scenes: it % --scenes
+    on one GPU, as the static scenes cycle --, sought to frame (steps so far // --scenes) % N, the steps so far counted over
+    all epochs and ranks, so that every seed walks through its N frames as the epochs go by -- in make_lidar_scene_batch's
+    keys (the ground truth of that frame, what somebody in the scene sees)."""
+    step = ((epoch - 1) * args.steps_per_epoch + it) * world + rank
+    scenes = max(1, args.scenes)
+    seed, frame = (it * world + rank) % scenes, (step // scenes) % args.sequence_frames
+    seq = _SEQUENCES.get(seed)
+    if seq is None:
+        seq = _SEQUENCES[seed] = lidar_sequence(args.batch, num_agent, config, seed, args.sequence_frames, device=device)
+    seq.seek(frame)
+    out = seq.step(teacher=bool(args.kd_flag))
+    out["gt_boxes"], out["gt_count"] = out["gt"]["boxes"], out["gt"]["count"]
+    return out
+
+
+def step_data(args, num_agent, hw, epoch, it, world=1, rank=0, anchors=None, device="cuda", config=None):
     """The `data` dict of one CoDetModule.step."""
     n_img = num_agent * args.batch
     if args.targets == "boxes":
         from disconet_amd import targets
         seed = ((epoch * 1000 + it) * world + rank) % max(1, args.scenes)
-        if args.scene == "lidar":
+        if args.scene == "lidar" and args.sequence_frames > 0:
+            scene = sequence_frame(args, num_agent, config, epoch, it, world, rank, device)
+        elif args.scene == "lidar":
             scene = lidar_scene(args.batch, num_agent, hw, seed, SCENE_BOXES, device=device, teacher=bool(args.kd_flag))
         else:
             scene = make_box_scene_batch(args.batch, num_agent, hw, seed=seed, boxes_per_scene=SCENE_BOXES, device=device,
@@ -163,6 +195,9 @@ def main(argv=None):
     require_com(args, TRAIN_COM_MODES)
     if args.scene == "lidar" and args.targets != "boxes":
         raise SystemExit("--scene lidar needs --targets boxes: the lidar scenes come with ground-truth boxes, not with targets")
+    if args.sequence_frames < 0 or (args.sequence_frames and (args.scene != "lidar" or args.targets != "boxes")):
+        raise SystemExit("--sequence_frames N >= 0, and N > 0 needs --scene lidar --targets boxes: the moving worlds are lidar "
+                         "scenes, and they come with ground-truth boxes, not with targets")
     num_agent = agents_of(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -204,7 +239,7 @@ def main(argv=None):
     for epoch in range(start_epoch, start_epoch + args.nepoch):
         t0, running = time.perf_counter(), 0.0
         for it in range(args.steps_per_epoch):
-            data = step_data(args, num_agent, hw, epoch, it, world, rank, anchors)
+            data = step_data(args, num_agent, hw, epoch, it, world, rank, anchors, config=config)
             out = fafmodule.step(data, args.batch)
             running += out["loss"]
         torch.cuda.synchronize()

@@ -10,8 +10,8 @@ per image.  Behind those, HOTA with its detection, association and localisation 
 AssRe, AssPr, LocA, HOTA(0), LocA(0), HOTALocA(0)): tracking.Hota.update() runs in the same captured step and logs every
 frame on the device (--max_frames slots), and Hota.compute() matches all logged frames of all images at once there.
 
-    python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late|agent [--source boxes|net] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
-        [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
+    python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late|agent [--source boxes|net|lidar] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
+        [--seed 0] [--detections net|truth] [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
         [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES]
 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
@@ -22,6 +22,14 @@ checkpoint and the tail of the --com mode).  Without --resume the weights are ra
 so that a run can be reproduced -- and the detections have little to do with the boxes: the run shows the plumbing
 only; after `train_codet.py --targets boxes --logpath L`, `--resume L/epoch_N.pth` gives figures that belong to the
 detector.
+--source lidar runs it on a world that moves: the lidar.Sequence of sequence seed --seed (synthetic.make_lidar_world: cars
+and vans in four lanes, parked cars and occluders beside them, every agent a sensor riding in a lane) is stepped, scanned
+and voxelised INSIDE the captured step, in front of the detector, and its ground truth -- the cars somebody sees, one id
+per car across frames -- goes to the three metrics; a sequence is --frames replays with nothing uploaded between them.
+After `train_codet.py --scene lidar --sequence_frames N --targets boxes --logpath L`, `--resume L/epoch_N.pth` gives the
+tracking figures of that detector; other seeds are worlds it was not trained on.  --detections truth feeds the frame's
+ground-truth boxes to SORT in place of the network: this world's counterpart of --source boxes, meaningful with no
+checkpoint (what SORT loses on perfect detections: births, and cars that come back from behind something).
 """
 import os
 import sys
@@ -36,16 +44,16 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_tail_flags, agents_of, require_com  # noqa: E402
+from codet_common import add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
-from track_step import build_step  # noqa: E402
+from track_step import build_step, lidar_net_scene  # noqa: E402
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = build_parser()
-    ap.add_argument("--source", choices=("net", "boxes"), default="boxes",
-                    help="net: the model on a standing box scene (with untrained weights it shows the plumbing only)")
-    ap.add_argument("--seed", type=int, default=0, help="make_track_sequence's / make_box_scene_batch's seed")
+    add_source_flags(ap, "boxes")     # net: the model on a standing box scene (with untrained weights it shows the plumbing only)
+    ap.add_argument("--seed", type=int, default=0,
+                    help="make_track_sequence's / make_box_scene_batch's seed; --source lidar: the sequence seed")
     add_tail_flags(ap, 128)
     add_sort_flags(ap)
     ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
@@ -57,6 +65,12 @@ def main(argv=None):
     if args.max_frames is None:
         args.max_frames = max(args.frames, 1)
     require_com(args, ALL_DET_COM_MODES)
+    check_source_flags(args)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     num_agent = agents_of(args)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
@@ -79,9 +93,10 @@ def main(argv=None):
               "ids": torch.arange(rows, dtype=torch.int32).repeat(n, 1).cuda()}
         return tuple(scene[key].cuda() for key in ("bev_seq", "trans_matrices", "num_agent")), None, gt
 
-    if args.source == "net" and not args.resume:
+    if args.source != "boxes" and args.detections == "net" and not args.resume:
         print("note: untrained weights -- the figures below show the plumbing, not a detector")
-    step, load, _ = build_step(args, config, sort, net_scene, behind=evaluate, truth=True)
+    scene = (lambda: lidar_net_scene(args, config)) if args.source == "lidar" else net_scene
+    step, load, _ = build_step(args, config, sort, scene, behind=evaluate, truth=True)
     mot.reset()                        # the warm-up runs of the capture advanced the tracker (build_step resets it) and were counted
     idf.reset()
     hota.reset()                       # ... and logged

@@ -6,13 +6,16 @@ nothing is copied to the host but the reported tracks that are written out), and
 tracks_agent<a>.txt, or tracks_agent<a>_scene<b>.txt for --batch > 1 (every image is its own sequence).
 
     python tools/track/sort_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 8] \
-        [--logpath logs/track] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--source net|boxes]
+        [--logpath logs/track] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--source net|boxes|lidar] [--seed 0] [--detections net|truth]
 
 --source net (default): test_codet.py's model and synthetic scenes (disconet_amd.Detector: the model, the checkpoint and
 the tail of the --com mode).  Without --resume the weights are random -- seeded before the model is built, so that a run
 can be reproduced -- and the detections of two frames have little to do with each other; the run shows the plumbing.
 --source boxes skips the network and feeds synthetic.make_track_sequence (moving boxes with detection noise, misses and
 false positives): the mode that shows meaningful tracks, and it prints how many true identities kept a single track id.
+--source lidar: the model on a world that moves -- the lidar.Sequence of sequence seed --seed, stepped, scanned and
+voxelised inside the captured step (eval_sort.py's docstring says more); --detections truth feeds the frame's ground-truth
+boxes to SORT in place of the network.
 """
 import os
 import sys
@@ -27,20 +30,26 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_tail_flags, agents_of, require_com  # noqa: E402
+from codet_common import add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
-from track_step import build_step  # noqa: E402
+from track_step import build_step, lidar_net_scene  # noqa: E402
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = build_parser()
-    ap.add_argument("--source", choices=("net", "boxes"), default="net")
-    ap.add_argument("--seed", type=int, default=0, help="--source boxes: make_track_sequence's seed")
+    add_source_flags(ap, "net")
+    ap.add_argument("--seed", type=int, default=0, help="--source boxes: make_track_sequence's seed; --source lidar: the sequence seed")
     add_tail_flags(ap, 128)
     add_sort_flags(ap)
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
     require_com(args, ALL_DET_COM_MODES)
+    check_source_flags(args)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     num_agent = agents_of(args)
     n = num_agent * args.batch
     config = Config("test", binary=True, only_det=True)
@@ -53,7 +62,9 @@ def main(argv=None):
     def net_scene():                   # a fresh scene every frame, no ground truth
         return tuple(t.cuda() for t in scene(0)), scene, None
 
-    step, load, seq = build_step(args, config, sort, net_scene)
+    if args.source == "lidar" and args.detections == "net" and not args.resume:
+        print("note: untrained weights -- the tracks below show the plumbing, not a detector")
+    step, load, seq = build_step(args, config, sort, (lambda: lidar_net_scene(args, config)) if args.source == "lidar" else net_scene)
 
     logpath = args.logpath or os.path.join("logs", "track")
     os.makedirs(logpath, exist_ok=True)
