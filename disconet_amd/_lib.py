@@ -131,6 +131,7 @@ SIGNATURES = {
     "dn_spconv_force_config": (c_int, [c_int]),
     "dn_spconv_set_upmode": (c_int, [c_int]),
     "dn_spconv_last_form": (c_int, [POINTER(c_int), c_int]),
+    "dn_spconv_last_resident": (c_int, []),
     "dn_conv_force_config": (c_int, [c_int]),
     "dn_conv_last_form": (c_int, [POINTER(c_int), c_int]),
     "dn_decode_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p,

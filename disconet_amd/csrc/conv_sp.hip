@@ -1375,6 +1375,7 @@ enum SpCfgId { S3_256x64, S3_256x32, S3_128x64, S3_64x64, S3S2_128x64, S3S2_64x6
 enum SpForceId {
   FORCE_SPQ_BN32 = 20, FORCE_SPQ_BN64 = 21, FORCE_SPQ_DEEP = 22,   // conv_spq.hip: BN 32 / 64 / the one-step-per-chunk form
   FORCE_SPQ_ABL = 22,                                // 23..25: ablations 1..3 of its BN = 32 form (DN_SP_ABL)
+  FORCE_SPQ_RES = 26,                                // conv_spq.hip: BN 32 with resident weights (20 stays the streaming form)
   FORCE_TOOLS = 100,
   FORCE_ABL_256x64 = 100, FORCE_ABL_256x32 = 200,    // 101..105, 201..207 (DN_SP_ABL)
   FORCE_ABL_64x64_T9 = 300,                          // 301..305, in every build
@@ -1828,6 +1829,10 @@ extern "C" int dn_spconv_last_form(int* out, int n) {
   return kInts;
 }
 
+extern "C" int dn_spconv_last_resident(void) {
+  return dn::g_sp_last_form.family == 1 && dn::g_spq_last_resident ? 1 : 0;
+}
+
 namespace {
 int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, const void* packed, const float* scale,
                   const float* shift, void* out, float* out_nhwc, int ld_nhwc, void* stream, int kslices = 1,
@@ -1908,7 +1913,7 @@ int spconv2d_impl(const dn_conv_desc* d, const void* src0, const void* src1, con
   if (up_mode(*d) == 2) {   // the packed image is the quad-merged one: conv_spq.hip, which takes its own codes for a forced form
     DN_REQUIRE(a.c1g == 0 || d->c0 % 16 == 0, "spconv: concat needs c0 %% 16 == 0");
     const int f = g_sp_force;
-    const int bn = f == FORCE_SPQ_BN32 ? 32 : f == FORCE_SPQ_BN64 ? 64 : f == FORCE_SPQ_DEEP ? 33 :
+    const int bn = f == FORCE_SPQ_BN32 ? 32 : f == FORCE_SPQ_BN64 ? 64 : f == FORCE_SPQ_DEEP ? 33 : f == FORCE_SPQ_RES ? 34 :
                    (f > FORCE_SPQ_ABL && f <= FORCE_SPQ_ABL + 3) ? 100 + (f - FORCE_SPQ_ABL) : 0;
     return dn::spq_conv(d, src0, src1, packed, (size_t)a.wpk_bytes, scale, shift, out, a.cout_pad, bn, s, kslices,
                         (float*)workspace, workspace_bytes, out_nhwc, ld_nhwc);

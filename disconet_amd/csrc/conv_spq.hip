@@ -24,8 +24,18 @@
 // Pipeline (double-buffered patch per chunk, double-buffered weights per step, raw s_barrier + counted
 // vmcnt waits, next tile's first operands under the current tile's last step), persistent workgroups, XCD-aware
 // item order and the register epilogue are those of conv_sp_kernel.
+//
+// Resident weights (RES, struct SpqRes below).  A layer of <= 4 + 2 chunks with one channel block (conv8_1: 96 -> 32) reads
+// the same 164 KB of weights for every one of its 5120 tiles; the streaming form moves them L2 -> LDS again per tile, in 14
+// barrier-separated steps of 12-18 MFMAs per wave.  The RES form fetches them once per workgroup -- a wave's class blocks of
+// the upsampled source into 128 registers, the second source's 9-tap blocks into LDS -- and a tile is then 6 patch hand-overs:
+// per chunk one barrier, the next patch's DMA, all 4 merged (or 9 plain) taps.  Every accumulator receives the streaming
+// form's products in the streaming form's order: the two forms agree bit for bit (tests/test_gpu_conv_spq_resident.py).
 #ifndef DN_SP_ABL
 #define DN_SP_ABL 0      // 1 = the timing-only ablations of the BN = 32 form (bn 101..103; see conv_sp.hip)
+#endif
+#ifndef DN_SPQ_RES
+#define DN_SPQ_RES 1     // 0 = the dispatch never chooses the resident-weights form (A/B builds; a forced launch still reaches it)
 #endif
 #include "dn_internal.h"
 #include "sp_layout.h"
@@ -92,12 +102,34 @@ struct SpqTile {
   static_assert((DEEP ? 1 : 2) * LDS_BYTES <= 160 * 1024, "two workgroups per CU (DEEP: one)");
 };
 
+// RES: the resident-weights form of the BN = 32 tile, for a layer of <= 4 + 2 chunks and ONE channel block (conv8_1: 96 -> 32).
+// Nothing a tile needs besides its patch changes from tile to tile there, so the weights are fetched once per workgroup:
+//   * a wave is one parity class and reads only its class's blocks of the upsampled source: 4 chunks x 4 merged taps x (hi, lo)
+//     fragments = 128 registers per lane, loaded before the first tile;
+//   * the 9-tap blocks of the second source (<= 2 chunks x 9 x 2 KB), shared by the four waves, sit in LDS beside the two
+//     patch stages.
+// Two workgroups per CU still fit: a patch stage holds its 1360 pieces and no padding (the ragged 22nd DMA instruction moves
+// 16 lanes), the epilogue affine is one 32-channel block for the workgroup.
+struct SpqRes {
+  static constexpr int C0G = 4, C1G = 2;
+  static constexpr int A_STAGE = QA_PIECES * 16;          // 21760 B
+  static constexpr int BLK = 4 * 32 * 16;                 // one weight block [4 quarters][32]
+  static constexpr int W1_INSTR = C1G * 9 * BLK / 1024;   // DMA instructions that stage the second source's blocks
+  static constexpr int OFF_W1 = 2 * A_STAGE;
+  static constexpr int OFF_AFF = OFF_W1 + C1G * 9 * BLK;
+  static constexpr int LDS_BYTES = OFF_AFF + 2 * 32 * 4;  // 80640 B
+  static_assert(W1_INSTR % QNW == 0, "the second source's blocks: whole rounds of DMA instructions");
+  static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
+};
+
 // ABL (tools/sp_conv_check only, results are garbage): 1 = no weight DMA, 2 = no patch DMA, 3 = neither
 // KSL: K-sliced launch (sp_device.h :: KSlices): whole tiles fold their slices in a second accumulator set, split
 // tiles hand theirs through `ks.partial` to the fix-up pass.  BN = 32 only (at BN = 64 the second set does not fit).
-template <int BN, int DEEP, int ABL = 0, int KSL = 0>
+template <int BN, int DEEP, int ABL = 0, int KSL = 0, int RES = 0>
 __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   static_assert(!KSL || BN == 32, "K slices: the 32-channel tile");
+  static_assert(!RES || (BN == 32 && !DEEP && !KSL && !ABL), "resident weights: the plain 32-channel tile");
+  constexpr int A_STRIDE = RES ? SpqRes::A_STAGE : QA_STAGE;   // bytes between the two patch stages
   using T = SpqTile<BN, DEEP>;
   constexpr int WTN = T::WTN, TGQ = T::TGQ, NS0 = T::NS0, NS1 = T::NS1, BLK = T::BLK, QB_STAGE = T::QB_STAGE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -253,10 +285,13 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
     if constexpr ((ABL & 2) != 0) return;
     const bool from1 = g >= a.c0g;
     const int soff = from1 ? (g - a.c0g) * 4 * (int)plane1 : g * 4 * (int)plane0;
-    unsigned char* base = smem + sa * QA_STAGE + wave * 1024;
+    unsigned char* base = smem + sa * A_STRIDE + wave * 1024;
 #pragma unroll
     for (int it = 0; it < QA_IT; ++it) {
       if (it == QA_IT - 1 && wave >= QA_INSTR - (QA_IT - 1) * QNW) break;   // ragged last round
+      if constexpr (RES != 0) {   // an unpadded stage: the lanes past the last piece move nothing
+        if (it == QA_IT - 1 && (it * QNW + wave) * 64 + lane >= QA_PIECES) break;
+      }
       if (from1)
         dma16(rsrc1, base + it * QNW * 1024, voff_a[it], soff);
       else
@@ -386,7 +421,10 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   // The affine of the current channel block lives in a WAVE-PRIVATE 512-byte LDS block (64 registers at BN = 64
   // would spill): written when the workgroup moves to another block, read by the same wave's epilogue -- in-order
   // LDS operations of one wave, no barrier.  Channels past c_out get scale = shift = 0.
-  float* aff_s = reinterpret_cast<float*>(smem + 2 * QA_STAGE + 2 * QB_STAGE) + wave * 128;
+  // (RES: ONE block of 32 channels for the workgroup -- every wave writes the same values and reads them after its own write)
+  constexpr int AFF_SH = RES ? 32 : 64;      // floats from a channel's scale to its shift
+  float* aff_s = RES ? reinterpret_cast<float*>(smem + SpqRes::OFF_AFF)
+                     : reinterpret_cast<float*>(smem + 2 * QA_STAGE + 2 * QB_STAGE) + wave * 128;
   int aff_n0 = -1;
   auto load_affine = [&](int n0) {
     if (n0 == aff_n0) return;
@@ -394,12 +432,19 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
     if (lane < BN) {
       const int co = n0 + lane, ci = min(co, a.c_out - 1);
       aff_s[lane] = co < a.c_out ? a.scale[ci] : 0.f;
-      aff_s[64 + lane] = co < a.c_out ? a.shift[ci] : 0.f;
+      aff_s[AFF_SH + lane] = co < a.c_out ? a.shift[ci] : 0.f;
     }
   };
   // Stores: buffer stores against a descriptor of the output image (32-bit lane offset + quarter-plane offset in the
   // vector operand, out-of-map lanes dropped by the bounds check), ReLU as a max against a uniform floor -- as in
   // conv_sp_kernel's store_sp_tile (which also says why the plane offset is not in the scalar operand).
+  // (RES: the affine is re-read for every accumulator tile through an offset the compiler cannot see through -- kept across
+  // the tiles and the two output blocks it is 32 registers beside the 128 of the resident weights: scratch)
+  auto aff_of_tile = [&]() {
+    int ao = 0;
+    if constexpr (RES != 0) asm volatile("" : "+v"(ao));
+    return aff_s + ao;
+  };
   auto epilogue = [&](const QTile& tc) {
     const int plane = a.h * a.w * 16;
     const int img_bytes = a.cog * 4 * plane;
@@ -412,13 +457,14 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
         const int oy = tc.oy0 + prow[wm], ox = tc.ox0 + pcol;
         const bool inside = oy < a.h && ox < a.w;
         float* orow = a.out_f32 + (((size_t)tc.img * a.h + oy) * a.w + ox) * a.ldo_f32;
+        const float* aff = aff_of_tile();
 #pragma unroll
         for (int wn = 0; wn < WTN; ++wn)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int co = tc.n0 + 32 * wn + 8 * g + 4 * lh;
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(aff_s + wn * 32 + 8 * g + 4 * lh);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(aff_s + 64 + wn * 32 + 8 * g + 4 * lh);
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + wn * 32 + 8 * g + 4 * lh);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + AFF_SH + wn * 32 + 8 * g + 4 * lh);
             f32x4 v = affine4(quad_of(acc[wm][wn], g), sc, sh);
             nan_seen |= !(fabsf(v[0]) <= 3.4028235e38f) | !(fabsf(v[1]) <= 3.4028235e38f) | !(fabsf(v[2]) <= 3.4028235e38f) |
                         !(fabsf(v[3]) <= 3.4028235e38f);
@@ -434,13 +480,14 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       const int oy = tc.oy0 + prow[wm], ox = tc.ox0 + pcol;
       const bool inside = oy < a.h && ox < a.w;
       const int voff = inside ? (oy * a.w + ox) * 16 + lh * plane : (int)0x80000000;
+      const float* aff = aff_of_tile();
 #pragma unroll
       for (int wn = 0; wn < WTN; ++wn) {
         u32x2 hi[4], lo[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const f32x4 sc = *reinterpret_cast<const f32x4*>(aff_s + wn * 32 + 8 * g + 4 * lh);
-          const f32x4 sh = *reinterpret_cast<const f32x4*>(aff_s + 64 + wn * 32 + 8 * g + 4 * lh);
+          const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + wn * 32 + 8 * g + 4 * lh);
+          const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + AFF_SH + wn * 32 + 8 * g + 4 * lh);
           const f32x4 v = affine4(quad_of(acc[wm][wn], g), sc, sh);
           split4(v, hi[g], lo[g], amax, lo_clamp);      // the ReLU rides in the split's clamp (sp_device.h)
         }
@@ -522,6 +569,154 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       }
       return;
     }
+  }
+  if constexpr (RES != 0) {
+    using R = SpqRes;
+    // ---- once per workgroup: the second source's blocks -> LDS (piece = (block, quarter, channel), as setup_voff_b's map) ...
+    const int w1_instr = a.c1g * (9 * R::BLK / 1024);
+#pragma unroll
+    for (int it = 0; it < R::W1_INSTR / QNW; ++it) {
+      const int ins = it * QNW + wave;
+      const int piece = ins * 64 + lane;
+      const unsigned vo = (unsigned)((((piece >> 7) * 4 + ((piece >> 5) & 3)) * a.cout_pad + (piece & 31)) * 16);
+      if (ins < w1_instr) dma16(rsrcw, smem + R::OFF_W1 + ins * 1024, vo, a.c0g * 16 * 4 * a.cout_pad * 16);
+    }
+    // ... and this wave's class blocks of the upsampled source -> registers: the bytes the streaming form's wave reads from
+    // its weight stage at b_offq (block g * 16 + 4 t + class, quarters lh and lh + 2, channel li)
+    half8 wh[R::C0G][4], wl[R::C0G][4];
+#pragma unroll
+    for (int g = 0; g < R::C0G; ++g)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        // The whole byte offset rides in the VECTOR operand: that is the offset the descriptor's range check tests (a scalar
+        // offset is added behind it), so no load can leave the packed image.  A chunk the layer does not have (g >= c0g,
+        // uniform) takes the out-of-range offset -- zeros, nothing read, as the patch DMA's padding -- and is never multiplied.
+        const unsigned vo = (unsigned)((((g * 16 + t * 4 + wave) * 4 + lh) * a.cout_pad + li) * 16);
+        const unsigned vh = g < a.c0g ? vo : OOB, vl = g < a.c0g ? vo + (unsigned)(2 * a.cout_pad * 16) : OOB;
+        wh[g][t] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrcw, vh, 0, 0));
+        wl[g][t] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrcw, vl, 0, 0));
+      }
+    load_affine(0);
+    // (waited for HERE, with the builtin the compiler's wait-count pass understands: left to the pass, the fragments' first
+    // use inside the persistent loop gets a vmcnt(0) that in steady state waits for the next patch -- conv_sp.hip :: load_affine)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    QTile cur = decode(item);
+    setup_rsrc(cur);
+    setup_voff_a(cur, false);
+    issue_a(0, 0);
+    int sa = 0;
+    // all four merged taps of a chunk of the upsampled source, weights from registers: the streaming form's tap order
+    auto compute0r = [&](const unsigned char* As, const half8 (&bh)[4], const half8 (&bl)[4]) {
+      Frags f[2];
+      auto load = [&](auto t_c) {
+        constexpr int t = decltype(t_c)::value, am = t >> 1, b = t & 1;
+        Frags& d = f[t & 1];
+#pragma unroll
+        for (int wm = 0; wm < 2; ++wm) {
+          d.ah[wm] = *reinterpret_cast<const half8*>(As + a_b0[wm][b][am]);
+          d.al[wm] = *reinterpret_cast<const half8*>(As + a_b0[wm][b][am] + 2 * QNPIX * 16);
+        }
+        d.bh[0] = bh[t];
+        d.bl[0] = bl[t];
+      };
+      load(std::integral_constant<int, 0>{});
+      load(std::integral_constant<int, 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+      mma(f[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      load(std::integral_constant<int, 2>{});
+      __builtin_amdgcn_sched_barrier(0);
+      mma(f[1]);
+      __builtin_amdgcn_sched_barrier(0);
+      load(std::integral_constant<int, 3>{});
+      __builtin_amdgcn_sched_barrier(0);
+      mma(f[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(f[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // all nine taps of a chunk of the second source, in the streaming form's order (dy, then dx).  The patch fragments run
+    // one tap ahead; the weight fragments are ONE set, re-read behind the tap's MFMAs (a second set would not fit beside the
+    // 128 resident registers)
+    auto compute1r = [&](const unsigned char* As, const unsigned char* Bs) {
+      Frags f[2];
+      auto load_a = [&](int u) {
+        Frags& d = f[u & 1];
+#pragma unroll
+        for (int wm = 0; wm < 2; ++wm) {
+          d.ah[wm] = *reinterpret_cast<const half8*>(As + a_b1[wm][u % 3] + (u / 3) * QPITCH * 16);
+          d.al[wm] = *reinterpret_cast<const half8*>(As + a_b1[wm][u % 3] + (u / 3) * QPITCH * 16 + 2 * QNPIX * 16);
+        }
+      };
+      half8 bh, bl;
+      auto load_b = [&](int u) {
+        bh = *reinterpret_cast<const half8*>(Bs + b_off[0] + u * BLK);
+        bl = *reinterpret_cast<const half8*>(Bs + b_off[0] + u * BLK + 2 * BN * 16);
+      };
+      load_a(0);
+      load_b(0);
+#pragma unroll
+      for (int u = 0; u < 9; ++u) {
+        if (u + 1 < 9) load_a(u + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        f[u & 1].bh[0] = bh;
+        f[u & 1].bl[0] = bl;
+        mma(f[u & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (u + 1 < 9) load_b(u + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    while (true) {
+#pragma unroll
+      for (int wm = 0; wm < 2; ++wm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[wm][0][r] = 0.f;
+      const bool has_next = item + G < a.total_items;
+      QTile nxt = cur;
+      if (has_next) nxt = decode(item + G);
+      // one hand-over per chunk: its patch has landed (every wave waited for its own DMAs), the other stage is free again;
+      // the next patch -- the next chunk's, or the next tile's first -- goes out under this chunk's MFMAs
+      auto hand_over = [&](int g) {
+        // vmcnt(0) on purpose, not a counted wait: the only loads in flight are this chunk's patch.  At a tile's first
+        // chunk that also waits for the previous tile's epilogue stores (the streaming form's first step does the same);
+        // the patch they share the counter with was issued before them, so a count could not let them pass anyway.
+        wait_vm0();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (g + 1 < nchunks) {
+          if (g + 1 == a.c0g) setup_voff_a(cur, true);   // concat: switch to source 1
+          issue_a(g + 1, sa ^ 1);
+        } else if (has_next) {
+          setup_rsrc(nxt);
+          setup_voff_a(nxt, false);
+          issue_a(0, sa ^ 1);
+        }
+      };
+#pragma unroll
+      for (int g = 0; g < R::C0G; ++g)
+        if (g < a.c0g) {
+          hand_over(g);
+          compute0r(smem + sa * A_STRIDE, wh[g], wl[g]);
+          sa ^= 1;
+        }
+      for (int g1 = 0; g1 < a.c1g; ++g1) {
+        hand_over(a.c0g + g1);
+        const unsigned char* As = smem + sa * A_STRIDE;
+        const unsigned char* Bs = smem + R::OFF_W1 + g1 * 9 * R::BLK;
+        compute1r(As, Bs);
+        sa ^= 1;
+      }
+      epilogue(cur);
+      note_range(amax, nan_seen);
+      if (!has_next) break;
+      item += G;
+      cur = nxt;
+    }
+    return;
   }
   Work cw = decode_work(item);
   QTile cur = cw.tc;
@@ -683,17 +878,18 @@ __global__ void spq_pack_weights_kernel(const float* __restrict__ w, unsigned ch
   }
 }
 
-template <int BN, int DEEP = 0, int ABL = 0, int KSL = 0>
+template <int BN, int DEEP = 0, int ABL = 0, int KSL = 0, int RES = 0>
 int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
   using T = SpqTile<BN, DEEP>;
-  auto kern = conv_spq_kernel<BN, DEEP, ABL, KSL>;
+  auto kern = conv_spq_kernel<BN, DEEP, ABL, KSL, RES>;
+  constexpr int LDS_BYTES = RES ? (int)SpqRes::LDS_BYTES : (int)T::LDS_BYTES;
   static dn::PerDeviceFlag attr_flag;
   bool& attr_set = attr_flag.here();
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)T::LDS_BYTES);
+                                       LDS_BYTES);
     if (e != hipSuccess)
-      return dn::fail(DN_ERR_LAUNCH, "spconv (quad-merged): hipFuncSetAttribute(%d B LDS): %s", (int)T::LDS_BYTES,
+      return dn::fail(DN_ERR_LAUNCH, "spconv (quad-merged): hipFuncSetAttribute(%d B LDS): %s", LDS_BYTES,
                       hipGetErrorString(e));
     attr_set = true;
   }
@@ -707,7 +903,9 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
   a.rcp_ncb = 1.0f / (float)a.n_cb; a.rcp_tx = 1.0f / (float)a.tiles_x; a.rcp_ty = 1.0f / (float)a.tiles_y;
   const long resident = (DEEP ? 1L : 2L) * kCUs;
   // what dn_spconv_last_form reports (family 1): the pixel tile, BN, DEEP and KSL of this instantiation
+  // (the record is what it was before the resident form existed; dn_spconv_last_resident tells the two BN = 32 forms apart)
   dn::SpLastForm form = {1, 3, 1, QTH, QTW, BN, 0, 1, 0, 0, 2, 0, KSL, 0, DEEP, 0, 0, 0, 0, 0};
+  dn::g_spq_last_resident = RES;
   if constexpr (KSL != 0) {
     KSlices& k = a.ks;
     const int S = k.count, ng = a.c0g + a.c1g;
@@ -746,7 +944,7 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
   dim3 grid((unsigned)(total > resident ? resident : total));
   form.grid = (int)grid.x; form.total_items = (int)total; form.n_whole = (int)total;
   dn::g_sp_last_form = form;
-  hipLaunchKernelGGL(kern, grid, dim3(QNT), T::LDS_BYTES, stream, a);
+  hipLaunchKernelGGL(kern, grid, dim3(QNT), LDS_BYTES, stream, a);
   return dn::check_launch("conv_spq_kernel");
 }
 
@@ -765,7 +963,10 @@ int spq_pack_weights(const float* weight_oihw, void* packed, int c_out, int c_in
   return check_launch("spq_pack_weights_kernel");
 }
 
-// bn: 32 or 64 output channels per workgroup; 33 = 32 in the one-step-per-chunk (DEEP) form; 0 = choose
+int g_spq_last_resident = 0;
+
+// bn: 32 or 64 output channels per workgroup; 33 = 32 in the one-step-per-chunk (DEEP) form; 34 = 32 in the resident-weights
+// form (SpqRes); 0 = choose
 int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const void* packed, size_t packed_bytes,
              const float* scale, const float* shift, void* out, int cout_pad, int bn, hipStream_t stream,
              int kslices, float* workspace, size_t workspace_bytes, float* out_nhwc, int ld_nhwc) {
@@ -779,6 +980,7 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
   a.cout_pad = cout_pad; a.wpk_bytes = (int)packed_bytes;
   a.tiles_x = a.tiles_y = a.total_items = 0;
   a.ks = KSlices{workspace, kslices, 0, 0, 0, 0, 0, 0, 0, 0};
+  const bool resident_ok = a.c0g <= SpqRes::C0G && a.c1g <= SpqRes::C1G && d->c_out <= 32 && kslices <= 1;
   if (kslices > 1) {
     // K-sliced layer: the 32-channel tile whatever the launch size (the result must not depend on it); the
     // one-step-per-chunk form when even the slices leave CUs without a workgroup
@@ -794,6 +996,13 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
     bn = (d->c_out > 32 && tiles * ((d->c_out + 63) / 64) >= 4L * kCUs) ? 64 : 32;
     // fewer items than CUs: latency regime (SpqTile DEEP)
     if (bn == 32 && tiles * ((d->c_out + 31) / 32) <= (long)kCUs) bn = 33;
+    // more items than that, and every weight the launch reads fits on chip: fetched once per workgroup, not once per tile
+    if (DN_SPQ_RES && bn == 32 && resident_ok) bn = 34;
+  }
+  if (bn == 34) {
+    DN_REQUIRE(resident_ok, "spconv (quad-merged): the resident-weights form takes <= %d + %d chunks, c_out <= 32, no K slices",
+               SpqRes::C0G, SpqRes::C1G);
+    return launch_spq<32, 0, 0, 0, 1>(a, stream);
   }
   if (bn == 64) return launch_spq<64>(a, stream);
   if (bn == 33) return launch_spq<32, 1>(a, stream);

@@ -91,6 +91,7 @@ struct SpLastForm {
   int fixup_grid;                 // workgroups of the K-sliced fix-up launch (0: none)
 };
 extern SpLastForm g_sp_last_form;
+extern int g_spq_last_resident;   // family 1 only: the launch ran conv_spq.hip's resident-weights form (dn_spconv_last_resident)
 
 }  // namespace dn
 

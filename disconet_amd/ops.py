@@ -629,6 +629,11 @@ def sp_last_form():
     return dict(zip(SP_FORM_FIELDS, (int(v) for v in buf)))
 
 
+def sp_last_resident():
+    """-> bool: the launch sp_last_form() describes ran conv_spq_kernel's resident-weights form (dn_spconv_last_resident)"""
+    return bool(_lib.load().dn_spconv_last_resident())
+
+
 def sp_conv2d_pre_pair_supported(d1, d2):
     return bool(_lib.load().dn_spconv2d_pre_pair_supported(ctypes.byref(d1), ctypes.byref(d2)))
 

@@ -29,7 +29,7 @@
  *     thread-local message for the last failing call on this thread;
  *   - re-entrant.  Process-wide state is limited to launch-time caches filled on first use
  *     (kernel attributes / occupancy per instantiation), the tools-only hooks dn_spconv_force_config(),
- *     dn_spconv_set_upmode(), dn_spconv_last_form(), dn_conv_force_config(), dn_conv_last_form() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
+ *     dn_spconv_set_upmode(), dn_spconv_last_form(), dn_spconv_last_resident(), dn_conv_force_config(), dn_conv_last_form() and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
  *     DN_WARP_GATHER_LEGACY (environment, read once: the other side of a bitwise / agreement test).
  */
 #ifndef DISCONET_HIP_H
@@ -397,6 +397,12 @@ int dn_spconv_set_upmode(int mode);
  * and returns 20.  A call that fails its argument checks before the launch leaves the record as it was.
  * Process-wide, not thread-safe (like dn_spconv_force_config). */
 int dn_spconv_last_form(int* out, int n);
+
+/* tools and tests only: 1 when the launch that dn_spconv_last_form() describes ran conv_spq_kernel's resident-weights form
+ * (BN = 32; the weights of a layer of <= 4 + 2 chunks and c_out <= 32 stay in registers / LDS for the whole launch:
+ * dn_spconv_force_config(26), or the dispatch's own choice when such a layer has more work items than CUs), else 0.  The
+ * record of dn_spconv_last_form() is the same for both BN = 32 forms. */
+int dn_spconv_last_resident(void);
 
 /* tools and tests only, the fp32-NHWC engine (dn_conv2d, dn_conv2d_taps): run tile configuration `cfg` -- a CfgId of
  * conv_mfma.hip: 0 T3_256x32, 1 T3_256x64, 2 T3_128x64, 3 T3_64x64, 4 T3S2_64x64, 5 T1_256x32, 6 T1_256x64,

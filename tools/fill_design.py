@@ -30,7 +30,7 @@ LAYERS = [
     ("conv6_2", "conv6_2", "128→128 @64²", 3.0),
     ("conv7_1 (up+cat)", "conv7_1", "192→64 @128², tap-merged", 3.0 * 17 / 27),
     ("conv7_2", "conv7_2", "64→64 @128²", 3.0),
-    ("conv8_1 (up+cat)", "conv8_1", "96→32 @256², tap-merged", 3.0 * 17 / 27),
+    ("conv8_1 (up+cat)", "conv8_1", "96→32 @256², tap-merged (streaming form; now resident weights, below)", 3.0 * 17 / 27),
     ("conv8_2", "conv8_2", "32→32 @256²", 3.0),
     ("heads (3x3 + block-diag 1x1)", "heads", "32→64→(12, 36) @256², fp32 out", 3.0),
 ]

@@ -210,7 +210,7 @@ static void run_layer(const char* name, int n, int h, int w, int c0, int c1, int
   const bool abl = g_mode == 2 && getenv("SPCHECK_ABL") && atoi(getenv("SPCHECK_ABL"));
   if (up0 && upmode == 2) {
     printf(" [quad]");
-    cfgs.insert(cfgs.end(), {20, 21, 22});
+    cfgs.insert(cfgs.end(), {20, 21, 22, 26});           // 26: BN = 32 with resident weights ("n/a" where they do not fit)
     if (abl) cfgs.insert(cfgs.end(), {23, 24, 25});   // timing only: no weight DMA / no patch DMA / neither
   } else if (!quick) {
     if (ks == 1) cfgs.insert(cfgs.end(), {6, 7});
@@ -245,7 +245,7 @@ static void run_layer(const char* name, int n, int h, int w, int c0, int c1, int
     const float t = tm.us([&] { dn_spconv2d(&d, sp0, sp1, pk, sc2, sh, spo, 0); });
     const bool ok = err < 2e-5;
     if (!ok) ++g_fail;
-    printf(" %s %6.1f us %6.1f TF err %.1e%s |", cfg < 0 ? "auto" : cfg == 20 ? "q32" : cfg == 21 ? "q64" : cfg == 22 ? "q32/deep" : kCfgName[cfg], t,
+    printf(" %s %6.1f us %6.1f TF err %.1e%s |", cfg < 0 ? "auto" : cfg == 20 ? "q32" : cfg == 21 ? "q64" : cfg == 22 ? "q32/deep" : cfg == 26 ? "q32/res" : kCfgName[cfg], t,
            gf / t * 1e3, err, ok ? "" : " FAIL");
     if (!ok) dump_mismatch(out_new, out_ref, n, ho, wo, cout);
   }
