@@ -10,7 +10,7 @@ from .fusion_modes import (ALL_DET_COM_MODES, COM_MODES, DET_COM_MODES, PARAM_CO
                            MaxFusion, MeanFusion, NoFusion, SumFusion, build_model)
 from .postprocess import StratifiedAP, gt_strata, late_fuse
 from .detector import Detector, load_checkpoint
-from . import holistic, lidar, render, targets
+from . import exchange, holistic, lidar, render, targets
 from .render import BoxLayer, attention_sheet, host_render_bev, read_png, render_bev, write_png
 from .seg import HostMeanIoU, MeanIoU, SegDiscoNet, SegModule
 from .holistic import holistic_views
@@ -20,4 +20,4 @@ from .train import CoDetModule, TrainEngine
 
 __all__ = ["Config", "DiscoNet", "SumFusion", "MeanFusion", "MaxFusion", "NoFusion", "AgentWeightedFusion", "AgentTrainEngine", "COM_MODES", "DET_COM_MODES", "PARAM_COM_MODES", "ALL_DET_COM_MODES", "build_model", "late_fuse", "Detector", "load_checkpoint", "TeacherNet", "CoDetModule", "TrainEngine", "SegDiscoNet", "SegModule", "MeanIoU", "HostMeanIoU", "targets",
            "assign_targets", "holistic", "holistic_views", "lidar", "render", "BoxLayer", "render_bev", "host_render_bev", "attention_sheet", "write_png",
-           "read_png", "StratifiedAP", "gt_strata"]
+           "read_png", "StratifiedAP", "gt_strata", "exchange"]

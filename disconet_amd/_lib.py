@@ -207,6 +207,9 @@ SIGNATURES = {
     "dn_lidar_scan_ids": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_double,
                                                    c_int] + [c_void_p] * 8),
     "dn_lidar_world_step": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int] + [c_void_p] * 4),
+    "dn_exchange_message_bytes": (c_long, [c_int, c_int, c_int, c_int]),
+    "dn_exchange_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dn_exchange_decode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

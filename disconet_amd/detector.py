@@ -8,6 +8,7 @@ late_fuse() allocate themselves, so a call can be captured by graph.GraphedStep.
 """
 import torch
 
+from . import exchange as exchange_format
 from . import postprocess
 from .fusion_modes import build_model
 from .synthetic import randomize_bn_stats
@@ -27,10 +28,16 @@ def load_checkpoint(model, path):
 
 class Detector:
     def __init__(self, com, config, num_agent, batch_size, *, layer=3, kd_flag=0, compress_level=0, only_v2i=False,
-                 pre_nms_top_k=300, iou_thr=0.01, score_thr=None, resume="", seed=0, device="cuda"):
+                 pre_nms_top_k=300, iou_thr=0.01, score_thr=None, resume="", seed=0, device="cuda", exchange="f32"):
         """com: one of ALL_DET_COM_MODES (build_model raises ValueError otherwise).  Without `resume` the weights are random:
         seeded before construction, so that a run can be reproduced, and the BatchNorm statistics are randomised
-        (synthetic.randomize_bn_stats).  `epoch` is the loaded checkpoint's epoch, or None."""
+        (synthetic.randomize_bn_stats).  `epoch` is the loaded checkpoint's epoch, or None.
+        exchange: the wire format of the exchanged map (exchange.FORMATS, model.exchange); anything but "f32" needs
+        com = "disco" -- the baselines' one-launch kernels read own and neighbour maps from one tensor, lowerbound and
+        late exchange no features."""
+        if exchange_format.check_format(exchange) != "f32" and com != "disco":
+            raise ValueError("exchange = %r needs --com disco (got --com %s): only the DiscoGraph fusion reads the "
+                             "neighbours' maps through a tensor of their own" % (exchange, com))
         self.com, self.config, self.num_agent, self.batch_size = com, config, num_agent, batch_size
         self.only_v2i = bool(only_v2i)
         self.pre_nms_top_k, self.iou_thr, self.score_thr = pre_nms_top_k, iou_thr, score_thr
@@ -42,6 +49,7 @@ class Detector:
             self.epoch = load_checkpoint(self.model, resume).get("epoch")
         else:
             randomize_bn_stats(self.model)
+        self.model.exchange = exchange
         self.model.eval().to(device)
         self.anchors = postprocess.make_anchors(config, device=device)
 

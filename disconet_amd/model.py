@@ -27,7 +27,7 @@ import re
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import exchange, ops
 from .profiling import region
 
 LAYER_CHANNEL = {4: 512, 3: 256, 2: 128, 1: 64, 0: 32}
@@ -350,14 +350,18 @@ def attention_mlp_plan(f, C, math, fuse_mlp):
 
 
 def disco_fuse(feat, trans_matrices, num_agent, batch_size, P, agents, only_v2i, want_weights=False,
-               ego_first=0, ego_count=None, sp_out=False):
+               ego_first=0, ego_count=None, sp_out=False, received=None):
     """DiscoGraph fusion of one pyramid level.  `feat` holds the maps of ALL agents (agent-major NHWC); the result
     covers the egos [ego_first, ego_first + ego_count) -- every agent on one GPU, this rank's agents when a scene is
-    sharded one agent per GPU (sharded.py)."""
+    sharded one agent per GPU (sharded.py).  `received` (feat's shape): what the agents SENT each other, where that is
+    not what they computed (exchange.roundtrip) -- the pose warp reads the neighbours from it, the attention keeps
+    reading each ego's own map, which is never transmitted, from `feat`."""
     A = agents
     E = A if ego_count is None else ego_count
     feat = ops.as_nhwc(feat)
     n, h, w, c = feat.shape
+    if received is not None and tuple(received.shape) != (n, h, w, c):
+        raise ValueError("received is %s, the maps are %s" % (tuple(received.shape), (n, h, w, c)))
     B = batch_size
     map_bytes = 4.0 * h * w * c
     pairs = B * E * (A - 1)
@@ -366,7 +370,8 @@ def disco_fuse(feat, trans_matrices, num_agent, batch_size, P, agents, only_v2i,
     # allows: an opaque intermediate between the two launches (include/disconet_hip.h :: dn_warp_neighbors_fm)
     fm = ("_fuse_mlp" in P and A > 1 and ops.warp_fm_supported(h, w, c))
     with region("warp", "warp_neighbors_kernel", 0.0, map_bytes * (n + pairs)):
-        ops.warp_neighbors(feat, trans_matrices, num_agent, B, A, only_v2i, ego_first, E, out=warped, fm=fm)
+        ops.warp_neighbors(feat if received is None else received, trans_matrices, num_agent, B, A, only_v2i, ego_first, E,
+                           out=warped, fm=fm)
     if "_fuse_mlp" in P:
         flops = 2.0 * B * E * h * w * (128.0 * c * (2 + (A - 1)) + A * (128 * 32 + 32 * 8 + 8))
         with region("fuse_mlp", "disco_fuse_mlp_kernel", flops, map_bytes * (3 * E * B + 2 * pairs)):
@@ -564,6 +569,10 @@ class DiscoNet(_BackboneNet):
         self._overlap_streams = False
         self.overlap_streams = os.environ.get("DISCONET_OVERLAP", "0") == "1"
         self._side = {}
+        # the wire format of the exchanged map in the eval forward (exchange.FORMATS): "f32" sends it as it is, today's
+        # path with nothing new called; "f16" | "mxfp8" | "mxfp4" put what the neighbours receive through
+        # exchange.roundtrip (csrc/exchange.hip).  --com disco only; training refuses it (no quantisation-aware training).
+        self.exchange = "f32"
 
     @property
     def overlap_streams(self):
@@ -659,10 +668,29 @@ class DiscoNet(_BackboneNet):
     # forward
     # ------------------------------------------------------------------
     def fuse(self, feat, trans_matrices, num_agent, batch_size, P, want_weights=False,
-             ego_first=0, ego_count=None, sp_out=False):
+             ego_first=0, ego_count=None, sp_out=False, received=None):
         """DiscoGraph fusion of the layer-`layer` maps (disco_fuse)"""
         return disco_fuse(feat, trans_matrices, num_agent, batch_size, P, self.agent_num, self.only_v2i,
-                          want_weights, ego_first, ego_count, sp_out)
+                          want_weights, ego_first, ego_count, sp_out, received)
+
+    def _fuse_exchanged(self, feat, trans, num_agent, batch_size, P):
+        """the eval forward's fusion: with a wire format, the neighbours' maps as the receivers decode them"""
+        sp_out = self.conv_math == "sp"
+        if self.exchange == "f32":
+            return self.fuse(feat, trans, num_agent, batch_size, P, sp_out=sp_out)
+        feat = ops.as_nhwc(feat)
+        return self.fuse(feat, trans, num_agent, batch_size, P, sp_out=sp_out,
+                         received=exchange.roundtrip(feat, self.exchange))
+
+    def _check_exchange(self):
+        if exchange.check_format(self.exchange) == "f32":
+            return
+        if type(self).fuse is not DiscoNet.fuse:
+            raise ValueError("%s.exchange = %r: only the DiscoGraph fusion (--com disco) takes a wire format; this "
+                             "mode's kernels read own and neighbour maps from one tensor" % (type(self).__name__, self.exchange))
+        if self.training:
+            raise NotImplementedError("DiscoNet.exchange = %r in train() mode: quantisation-aware training is not built; "
+                                      "train with \"f32\" and set the format for evaluation" % self.exchange)
 
     def heads(self, x8, P):
         if "heads_fused" in P:                          # conv1 of both heads + both conv2, one launch
@@ -676,6 +704,7 @@ class DiscoNet(_BackboneNet):
         return {"loc": loc_preds, "cls": cls_preds}
 
     def forward(self, bevs, trans_matrices, num_agent_tensor, batch_size=1):
+        self._check_exchange()
         if not bevs.is_cuda:
             raise ops._lib.DnError("DiscoNet.forward needs GPU tensors; there is no CPU path")
         if self.training:
@@ -716,14 +745,14 @@ class DiscoNet(_BackboneNet):
                     enc[3] = P["decompress"].run(P["compress"].run(enc[3]))
             elif "compress" in P:
                 feat = P["decompress"].run(P["compress"].run(feat))
-            fused = self.fuse(feat, trans, num_agent, batch_size, P, sp_out=self.conv_math == "sp")
+            fused = self._fuse_exchanged(feat, trans, num_agent, batch_size, P)
             main.wait_stream(side)
             for t in enc[self.layer + 1:]:
                 t.record_stream(main)
             enc[self.layer] = fused
         else:
             enc = self.encode(bevs, P)
-            fused = self.fuse(enc[self.layer], trans, num_agent, batch_size, P, sp_out=self.conv_math == "sp")
+            fused = self._fuse_exchanged(enc[self.layer], trans, num_agent, batch_size, P)
             enc[self.layer] = fused
         x8, x7, x6, x5 = self.decode(enc, P)
 

@@ -1008,6 +1008,62 @@ def agent_fuse(feat, trans, num_agent, params, w5, b5, batch, agents, only_v2i=F
     return (fused, weights) if want_weights else fused
 
 
+# ---------------------------------------------------------------------------
+# feature exchange wire format (include/disconet_hip.h; the numpy statement is exchange.py)
+# ---------------------------------------------------------------------------
+EXCHANGE_FORMATS = {"f32": 0, "f16": 1, "mxfp8": 2, "mxfp4": 3}      # DN_EXCHANGE_*
+
+
+def _exchange_format(fmt):
+    """the DN_EXCHANGE_* value of a format's name (a value passes through: the library judges it)"""
+    if isinstance(fmt, str):
+        if fmt not in EXCHANGE_FORMATS:
+            raise _lib.DnError("exchange format must be one of %s (got %r)" % (" | ".join(EXCHANGE_FORMATS), fmt))
+        return EXCHANGE_FORMATS[fmt]
+    return int(fmt)
+
+
+def exchange_message_bytes(fmt, h, w, c):
+    """bytes of one [h, w, c] image's message in format `fmt` (dn_exchange_message_bytes); c % 32 == 0"""
+    lib = _lib.load()
+    nbytes = lib.dn_exchange_message_bytes(_exchange_format(fmt), h, w, c)
+    check(0 if nbytes >= 0 else int(nbytes), "dn_exchange_message_bytes")
+    return int(nbytes)
+
+
+def exchange_encode(feat, fmt, out=None):
+    """feat [n, h, w, c] float32 NHWC -> wire [n, message_bytes] uint8: every image's message (payload, scale bytes, zero
+    padding), one launch.  fmt: "f16" | "mxfp8" | "mxfp4" ("f32" is the identity and has no launch: refused)."""
+    _need_gpu(feat, out)
+    _f32c(feat, "feat")
+    n, h, w, c = feat.shape
+    f = _exchange_format(fmt)
+    nbytes = exchange_message_bytes(f, h, w, c)
+    wire = out if out is not None else torch.empty((n, nbytes), dtype=torch.uint8, device=feat.device)
+    if wire.dtype != torch.uint8 or not wire.is_contiguous() or wire.numel() < n * nbytes:
+        raise _lib.DnError("exchange_encode: out must be contiguous uint8 with at least %d x %d bytes (got %s, %d elements)"
+                           % (n, nbytes, wire.dtype, wire.numel()))
+    check(_lib.load().dn_exchange_encode(_ptr(feat), n, h, w, c, f, _ptr(wire), _stream()), "dn_exchange_encode")
+    return wire
+
+
+def exchange_decode(wire, fmt, h, w, c, out=None):
+    """wire [n, message_bytes] uint8 -> feat [n, h, w, c] float32 NHWC, one launch"""
+    _need_gpu(wire, out)
+    f = _exchange_format(fmt)
+    nbytes = exchange_message_bytes(f, h, w, c)
+    if wire.dtype != torch.uint8 or not wire.is_contiguous() or wire.dim() != 2 or wire.shape[1] != nbytes:
+        raise _lib.DnError("exchange_decode: wire must be contiguous uint8 [n, %d] for a %d x %d x %d map (got %s %s)"
+                           % (nbytes, h, w, c, wire.dtype, tuple(wire.shape)))
+    n = wire.shape[0]
+    feat = out if out is not None else torch.empty((n, h, w, c), dtype=torch.float32, device=wire.device)
+    _f32c(feat, "out")
+    if feat.numel() != n * h * w * c:
+        raise _lib.DnError("exchange_decode: out holds %d values, the wire %d" % (feat.numel(), n * h * w * c))
+    check(_lib.load().dn_exchange_decode(_ptr(wire), n, h, w, c, f, _ptr(feat), _stream()), "dn_exchange_decode")
+    return feat
+
+
 def live_agent_counts(num_agent_tensor, device):
     """The kernels' [B] int32 live-agent counts from the reference's num_agent_tensor [B, A] (column 0 is the
     count).  A 1-D int32 tensor already on the device is taken as is -- no cast / gather kernel inside the step

@@ -1205,6 +1205,61 @@ int dn_lidar_world_step(const double* solids0, const double* solid_vel, const in
                         const double* agent_vel, int32_t* frame, int n_scenes, int n_agents, int k, double* solids,
                         double* sensor_from_world, float* trans, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Feature exchange wire format (disconet_amd/csrc/exchange.hip, dn_version 155): what one agent sends the others -- its
+ * map of the exchanged pyramid level -- as f16, MXFP8 or MXFP4 instead of fp32.  disconet_amd/exchange.py states the same
+ * contract in numpy (host_encode / host_decode); the kernels equal it in every byte.
+ *
+ * FORMATS.  DN_EXCHANGE_F32 is the identity: no bytes change and there is nothing to launch (dn_exchange_encode /
+ * _decode refuse it); it has a message size so that the formats can be compared.
+ *
+ * MESSAGE of one image [h][w][c] fp32 NHWC, c % 32 == 0: one contiguous range of dn_exchange_message_bytes() bytes, the
+ * payload first, then the scale bytes, then zero bytes up to a multiple of 16 (the zeros are part of the contract: the
+ * encode launch writes them).  Payload in pixel-major, channel order:
+ *   f16    2 bytes per value, little endian; no scales.
+ *   mxfp8  1 byte per value.
+ *   mxfp4  two values per byte, the lower channel index in the low nibble.
+ * Scales: one byte per BLOCK = 32 consecutive channels of one pixel, in [pixel][block] order.  At 32 x 32 x 256 a message
+ * is 1 048 576 (f32), 524 288 (f16), 270 336 (mxfp8), 139 264 (mxfp4) bytes.
+ *
+ * f16: IEEE binary16, round to nearest even, plain conversion (numpy.astype(float16)): overflow gives +-Inf, a NaN stays
+ * a NaN.  Decode is the exact widening.
+ *
+ * mxfp8 / mxfp4: OCP Microscaling v1.0.  Element format E4M3 (e4m3fn: bias 7, largest magnitude 448 = code 0x7E,
+ * subnormals mant * 2^-9; emax = 8) or E2M1 (magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6; emax = 2); the block's shared scale is
+ * E8M0.  For a block v_0 .. v_31:
+ *   - any v_i a NaN or +-Inf: scale byte 0xFF, every element code 0; every value of the block decodes to a NaN;
+ *   - else m = max |v_i|, E = floor(log2 m) read from m's fp32 bits (a subnormal m: the position of its leading mantissa
+ *     bit), e = max(E - emax, -127), and e = -127 for m == 0.  The scale byte is e + 127;
+ *   - element i is v_i * 2^-e, computed exactly, rounded to nearest even as if the element format had no upper exponent
+ *     limit, the magnitude then clamped to the format's largest (448 or 6).  The sign bit of v_i is always kept: also
+ *     when the magnitude rounds to zero, and for -0.
+ * Decode is value(code) * 2^e, and that product is exact in fp32: value(code) is an integer below 16 (below 4) times a
+ * power of two, so the product has at most 4 significant bits, and its exponent lies inside fp32's -- the smallest
+ * non-zero product is 2^-9 * 2^-127 = 2^-136 >= 2^-149, the largest are 448 * 2^119 < 2^128 and 6 * 2^125 < 2^128 (e <=
+ * 127 - emax).  The E4M3 NaN codes 0x7F / 0xFF, which encode never writes, decode to a NaN.
+ * Consequences: decode(encode(.)) is idempotent in every bit (a decoded block's maximum keeps E unless it was rounded up
+ * to the clamp, and every decoded value is representable under the new scale); per block |x - x'| <= m / 8 for mxfp8 (the
+ * worst case is the clamp from 512 to 448 scaled; rounding alone gives m / 16) and <= m / 4 for mxfp4.  The two bounds
+ * need a scale above its floor: for m < 2^(emax - 127) -- fp32's own subnormals and the binades just above them, which
+ * E8M0 cannot follow -- e stays -127 and the error is at most half the smallest quantum left, 2^-137 (mxfp8) or 2^-129
+ * (mxfp4): such a block decodes to zeros with the signs kept.
+ *
+ *   feat  [n_images][h][w][c] float32 NHWC
+ *   wire  [n_images][dn_exchange_message_bytes(format, h, w, c)] bytes: the messages back to back
+ * One launch each, graph-capturable, no atomics, no workspace, no host read; every byte of `wire` (of `feat`) is
+ * written.  dn_exchange_message_bytes returns DN_ERR_ARG, and the two calls return it before anything is launched, for:
+ * c not a positive multiple of 32, a map of 2^31 values or more, an unknown format; the two calls also for
+ * DN_EXCHANGE_F32, a null pointer, n_images < 1, and a feat or wire that is not 16-byte aligned.
+ * ------------------------------------------------------------------------ */
+#define DN_EXCHANGE_F32 0
+#define DN_EXCHANGE_F16 1
+#define DN_EXCHANGE_MXFP8 2
+#define DN_EXCHANGE_MXFP4 3
+long dn_exchange_message_bytes(int format, int h, int w, int c);
+int dn_exchange_encode(const float* feat, int n_images, int h, int w, int c, int format, uint8_t* wire, void* stream);
+int dn_exchange_decode(const uint8_t* wire, int n_images, int h, int w, int c, int format, float* feat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

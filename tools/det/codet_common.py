@@ -1,6 +1,6 @@
 """What the det, track and seg command lines share: the tail's and SORT's flags, the --com refusal, the --rsu rule and
 the Detector of the parsed flags (the reference's flag names; test_codet.build_parser declares them)."""
-from disconet_amd import Detector
+from disconet_amd import Detector, exchange
 
 
 def add_tail_flags(ap, pre_nms_top_k):
@@ -14,6 +14,22 @@ def add_sort_flags(ap):
     ap.add_argument("--min_hits", type=int, default=3)
     ap.add_argument("--iou_threshold", type=float, default=0.3, help="SORT's association threshold")
     ap.add_argument("--max_tracks", type=int, default=128)
+
+
+def add_exchange_flag(ap):
+    ap.add_argument("--exchange", choices=tuple(exchange.FORMATS), default="f32",
+                    help="the wire format of the exchanged feature map (--com disco): f16, mxfp8 or mxfp4 put what the "
+                         "neighbours receive through exchange.roundtrip; f32 sends it as it is")
+
+
+def exchange_line(args, config):
+    """--exchange other than f32: the line eval_codet.py and eval_sort.py print, the message bytes per agent per frame"""
+    from disconet_amd.model import LAYER_CHANNEL
+    side = config.map_dims[0] >> args.layer              # the exchanged level's side: level k is the map halved k times
+    c = LAYER_CHANNEL[args.layer]
+    return "exchange %s: %d bytes per agent per frame (a %d x %d x %d map; f32 %d)" % (
+        args.exchange, exchange.message_bytes(args.exchange, side, side, c), side, side, c,
+        exchange.message_bytes("f32", side, side, c))
 
 
 def require_com(args, modes):
@@ -65,11 +81,15 @@ def add_source_flags(ap, default):
 def check_source_flags(args):
     if args.detections == "truth" and args.source != "lidar":
         raise SystemExit("--detections truth needs --source lidar: the other sources have no per-frame ground truth to feed")
+    if getattr(args, "exchange", "f32") != "f32" and (args.source == "boxes" or args.detections == "truth"):
+        raise SystemExit("--exchange %s needs the network's detections (--source net | lidar, --detections net): nothing "
+                         "is exchanged otherwise" % args.exchange)
 
 
 def detector_from_args(args, config):
-    """the Detector of the command line (the tail's flags where the tool declares them), and the `loaded` line"""
-    tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr") if hasattr(args, k)}
+    """the Detector of the command line (the tail's flags and --exchange where the tool declares them), and the `loaded`
+    line"""
+    tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr", "exchange") if hasattr(args, k)}
     det = Detector(args.com, config, agents_of(args), args.batch, layer=args.layer, kd_flag=args.kd_flag,
                    compress_level=args.compress_level, only_v2i=bool(args.only_v2i), resume=args.resume, **tail)
     if args.resume:

@@ -22,13 +22,14 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
-from codet_common import add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 
 def build_detect_parser():
     ap = build_parser()
     add_tail_flags(ap, 300)
+    add_exchange_flag(ap)
     ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
                     help="boxes: the tool's seeded occupancy, as ever; lidar: synthetic.make_lidar_scene_batch(seed = frame), "
                          "ray-cast scans with occluders")

@@ -5,7 +5,7 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 
     python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene] \
-        [--strata none|range|visibility] [--strata_edges 10,20]
+        [--strata none|range|visibility] [--strata_edges 10,20] [--exchange f32|f16|mxfp8|mxfp4]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
     have nothing to do with the synthetic occupancy (there is no V2X-Sim data here): the figure checks the plumbing, not
@@ -15,6 +15,9 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 --gt scene: frame f is synthetic.make_box_scene_batch(seed=f) -- occupancy that shows the scene's own boxes -- scored
     against those boxes: after `train_codet.py --targets boxes --logpath L`, `--gt scene --resume L/epoch_N.pth` prints an
     mAP that belongs to the detector.
+
+--exchange f16|mxfp8|mxfp4 (--com disco): the neighbours' feature maps go through the wire format (disconet_amd.exchange:
+    encoded and decoded on the GPU inside the forward); one more line gives the message bytes per agent per frame.
 
 --com lowerbound: no collaboration.  --com late: the lowerbound detector (train `--com lowerbound`, pass its checkpoint)
     with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame
@@ -36,7 +39,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch  # noqa: E402
-from codet_common import add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_tail_flags, agents_of, exchange_line, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -45,6 +48,7 @@ GT_MAX_BOXES = 64
 def build_eval_parser():
     ap = build_parser()
     add_tail_flags(ap, 300)
+    add_exchange_flag(ap)
     ap.add_argument("--gt", choices=("synthetic", "self", "scene"), default="synthetic")
     ap.add_argument("--scene", choices=("boxes", "lidar"), default="boxes",
                     help="--gt scene: lidar = synthetic.make_lidar_scene_batch, ray-cast scans with occluders, scored against "
@@ -128,6 +132,8 @@ def main(argv=None):
             "ground truth = the boxes of the scenes%s" % ("" if args.resume else ", random weights") if args.gt == "scene" else
             "synthetic ground truth%s: plumbing, not accuracy" % ("" if args.resume else " and random weights"))
     print("%d frames x %d images (%s)" % (args.frames, n_images, what))
+    if args.exchange != "f32":
+        print(exchange_line(args, config))
     for a, row in enumerate(res["per_agent"]):
         print("agent %d: mAP@0.5 %.4f  mAP@0.7 %.4f  (%d detections, %d ground-truth boxes, true positives %d / %d)" % (
             a, row["mAP@0.5"], row["mAP@0.7"], row["n_det"], row["n_gt"], row["n_tp"][0], row["n_tp"][1]))

@@ -22,7 +22,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, BoxLayer, Config, render, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_sort_flags, add_tail_flags, agents_of, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -31,6 +31,7 @@ GT_MAX_BOXES = 64
 def build_vis_parser():
     ap = build_parser()
     add_tail_flags(ap, 300)
+    add_exchange_flag(ap)
     add_sort_flags(ap)
     ap.add_argument("--gt", choices=("scene", "none"), default="scene")
     ap.add_argument("--scale", type=int, default=2, choices=render.SCALES, help="canvas pixels per BEV cell")

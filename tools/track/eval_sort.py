@@ -12,7 +12,7 @@ frame on the device (--max_frames slots), and Hota.compute() matches all logged 
 
     python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late|agent [--source boxes|net|lidar] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--seed 0] [--detections net|truth] [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
-        [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES]
+        [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES] [--exchange f32|f16|mxfp8|mxfp4]
 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
 noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
@@ -44,7 +44,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, exchange_line, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 from track_step import build_step, lidar_net_scene  # noqa: E402
 
@@ -55,6 +55,7 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0,
                     help="make_track_sequence's / make_box_scene_batch's seed; --source lidar: the sequence seed")
     add_tail_flags(ap, 128)
+    add_exchange_flag(ap)
     add_sort_flags(ap)
     ap.add_argument("--eval_iou", type=float, default=0.5, help="the IoU a track needs to count for a ground truth")
     ap.add_argument("--max_gt_ids", type=int, default=256)
@@ -109,6 +110,8 @@ def main(argv=None):
     figures = mot.compute()            # the one copy; raises on a sticky status bit of the evaluation
     print("%d frames, %d images (%d agents x batch %d), tracks need IoU >= %g" % (args.frames, n, num_agent, args.batch,
                                                                                   args.eval_iou))
+    if args.exchange != "f32":
+        print(exchange_line(args, config))
     for a, row in enumerate(figures["per_agent"]):
         print(tracking.mot_line("agent %d" % a, row))
     print(tracking.mot_line("overall", figures["overall"]))

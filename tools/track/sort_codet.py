@@ -30,7 +30,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_scene_batch  # noqa: E402
-from codet_common import add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 from track_step import build_step, lidar_net_scene  # noqa: E402
 
@@ -40,6 +40,7 @@ def parse_args(argv=None):
     add_source_flags(ap, "net")
     ap.add_argument("--seed", type=int, default=0, help="--source boxes: make_track_sequence's seed; --source lidar: the sequence seed")
     add_tail_flags(ap, 128)
+    add_exchange_flag(ap)
     add_sort_flags(ap)
     ap.set_defaults(frames=8)
     args = ap.parse_args(argv)
