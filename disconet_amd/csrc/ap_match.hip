@@ -6,8 +6,9 @@
 // Launch sequence (fixed: it depends on the shapes only, never on the data; nothing is read back, nothing is allocated):
 //   ap_rank      one workgroup per image: rank of every row in the stable descending score order, the number of valid
 //                rows (row < count and a finite score), the non-finite status bit, the claim words set to INT_MAX
-//   ap_iou       tile (64 rows, 16-column ground-truth piece) per wave: circumscribed-circle test, then the fp64 polygon
-//                clip per lane; the piece's best (IoU, lowest column) per row
+//   ap_iou       tile (64 rows, 16-column ground-truth piece) per wave: rot_iou_device.h's columns, circle test and IoU
+//                (stage_columns, circles_meet, pair_iou: the pair body of the NMS and of the anchor assignment); the
+//                piece's best (IoU, lowest column) per row
 //   ap_claim     per row: the pieces folded in column order (strict >, so the lowest column that attains the maximum wins);
 //                per threshold an integer atomicMin of the row's rank into the claim word of its ground-truth box
 //   ap_tp        per row and threshold: true positive when the row's rank is the claim word; the record at
@@ -32,11 +33,12 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxK = 1024;    // detection rows per image (dn_detect's limit for top_k)
-constexpr int kMaxG = 1024;    // ground-truth rows per image
+constexpr int kMaxK = dn::kMaxBoxRows;
+constexpr int kMaxG = dn::kMaxGtRows;
 constexpr int kMaxT = 8;       // thresholds: one bit each in a record's flag byte
 constexpr int kCols = 16;      // ground-truth columns per tile
 constexpr int kMaxAgents = 65536;
+using dn::clampi;
 
 struct Thresholds {
   double t[kMaxT];
@@ -46,21 +48,17 @@ struct Layout {
   size_t nvalid, claim, piou, pgt, total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 Layout layout(int n, int k, int g, int nt) {
   const size_t pieces = (size_t)(g + kCols - 1) / kCols;
+  dn::Carver c;
   Layout L;
-  size_t o = 0;
-  L.nvalid = o; o = align256(o + sizeof(int) * (size_t)n);
-  L.claim = o;  o = align256(o + sizeof(int) * (size_t)nt * n * g);
-  L.piou = o;   o = align256(o + sizeof(double) * (size_t)n * k * pieces);
-  L.pgt = o;    o = align256(o + sizeof(int) * (size_t)n * k * pieces);
-  L.total = o;
+  L.nvalid = c.take(sizeof(int) * (size_t)n);
+  L.claim = c.take(sizeof(int) * (size_t)nt * n * g);
+  L.piou = c.take(sizeof(double) * (size_t)n * k * pieces);
+  L.pgt = c.take(sizeof(int) * (size_t)n * k * pieces);
+  L.total = c.at;
   return L;
 }
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __global__ void __launch_bounds__(kThreads) ap_rank_kernel(const float* __restrict__ scores,
                                                            const int* __restrict__ count, int k, int g, int nt,
@@ -106,24 +104,14 @@ __global__ void __launch_bounds__(64) ap_iou_kernel(const float* __restrict__ bo
                                                     const int* __restrict__ gt_count, int k, int g, int pieces,
                                                     double* __restrict__ piou, int* __restrict__ pgt) {
 #pragma clang fp contract(off)
-  __shared__ double cxs[4][kCols], cys[4][kCols], ccx[kCols], ccy[kCols], crad[kCols], carea[kCols];
-  __shared__ double bufx[2][dn::kClipCap][64], bufy[2][dn::kClipCap][64];
+  __shared__ dn::BoxColumns<kCols> cols;
+  __shared__ dn::ClipScratch scratch;
   const int piece = blockIdx.x, rb = blockIdx.y, img = blockIdx.z, t = threadIdx.x;
   const int c = clampi(count[img], k), gc = clampi(gt_count[img], g);
   const int j0 = piece * kCols;
   if (j0 >= gc || rb * 64 >= c) return;
-  if (t < kCols && j0 + t < gc) {
-    dn::Box64 b;
-    dn::box64(gt + 6 * ((size_t)img * g + j0 + t), b);
-    for (int q = 0; q < 4; ++q) {
-      cxs[q][t] = b.x[q];
-      cys[q][t] = b.y[q];
-    }
-    ccx[t] = b.cx;
-    ccy[t] = b.cy;
-    crad[t] = b.radius;
-    carea[t] = b.area;
-  }
+  const int jend = gc - j0 < kCols ? gc - j0 : kCols;
+  dn::stage_columns(cols, gt + 6 * ((size_t)img * g + j0), jend, t);
   __syncthreads();
   const int i = rb * 64 + t;
   if (i >= c || rank[(size_t)img * k + i] < 0) return;
@@ -131,19 +119,9 @@ __global__ void __launch_bounds__(64) ap_iou_kernel(const float* __restrict__ bo
   dn::box64(boxes + 6 * ((size_t)img * k + i), a);
   double best = 0.0;
   int best_j = -1;
-  const int jend = gc - j0 < kCols ? gc - j0 : kCols;
   for (int jj = 0; jj < jend; ++jj) {
-    const double dist = hypot(ccx[jj] - a.cx, ccy[jj] - a.cy);
-    if (!(dist < crad[jj] + a.radius)) continue;   // circumscribed circles apart: IoU 0
-    double bx[4], by[4];
-    for (int q = 0; q < 4; ++q) {
-      bx[q] = cxs[q][jj];
-      by[q] = cys[q][jj];
-    }
-    const double inter = dn::intersection_area(a.x, a.y, bx, by, &bufx[0][0][t], &bufy[0][0][t], &bufx[1][0][t],
-                                               &bufy[1][0][t]);
-    const double uni = a.area + carea[jj] - inter;
-    const double iou = uni > 0 ? inter / uni : 0.0;
+    if (!dn::circles_meet(cols, jj, a)) continue;   // circumscribed circles apart: IoU 0
+    const double iou = dn::pair_iou(cols, jj, a, scratch, t);
     if (iou > best) {
       best = iou;
       best_j = j0 + jj;
@@ -359,7 +337,7 @@ __global__ void ap_strata_advance_kernel(const int* __restrict__ nvalid, const i
 }
 
 bool shapes_ok(int n, int k, int g, int nt) {
-  return n > 0 && n <= 65535 && k >= 1 && k <= kMaxK && g >= 1 && g <= kMaxG && nt >= 1 && nt <= kMaxT;
+  return n > 0 && n <= dn::kMaxImages && k >= 1 && k <= kMaxK && g >= 1 && g <= kMaxG && nt >= 1 && nt <= kMaxT;
 }
 
 // What dn_ap_match and dn_ap_match_strata check alike, under the caller's name; fills `thr`.
@@ -367,7 +345,7 @@ int check_match(const char* who, bool pointers, int n_images, int k, int g, cons
                 size_t workspace_bytes, size_t need, const void* records, long long capacity, const long long* state,
                 int n_agents, int batch, Thresholds& thr) {
   DN_REQUIRE(pointers, "%s: null pointer", who);
-  DN_REQUIRE(n_images > 0 && n_images <= 65535, "%s: %d images is out of range [1, 65535]", who, n_images);
+  DN_REQUIRE(n_images > 0 && n_images <= dn::kMaxImages, "%s: %d images is out of range [1, 65535]", who, n_images);
   DN_REQUIRE(k >= 1 && k <= kMaxK, "%s: K = %d detection rows, must be in [1, %d]", who, k, kMaxK);
   DN_REQUIRE(g >= 1 && g <= kMaxG, "%s: G = %d ground-truth rows, must be in [1, %d]", who, g, kMaxG);
   DN_REQUIRE(n_thr >= 1 && n_thr <= kMaxT, "%s: T = %d thresholds, must be in [1, %d]", who, n_thr, kMaxT);
@@ -405,7 +383,7 @@ void launch_match(hipStream_t s, const Layout& L, char* ws, const float* boxes, 
                      n_thr, best_iou, best_gt, claim);
 }
 
-size_t strata_counts_bytes(int n, int ns) { return align256(sizeof(int) * (size_t)n * (ns + 1)); }
+size_t strata_counts_bytes(int n, int ns) { return dn::align256(sizeof(int) * (size_t)n * (ns + 1)); }
 
 }  // namespace
 
@@ -453,7 +431,7 @@ extern "C" int dn_ap_reset(long long* state, int n_agents, void* stream) {
 extern "C" int dn_gt_strata(const float* gt_boxes, const int32_t* gt_count, const int32_t* gt_own_hits, int n_images,
                             int g, int mode, const double* edges, int n_edges, int32_t* stratum, void* stream) {
   DN_REQUIRE(gt_boxes && gt_count && edges && stratum, "gt_strata: null pointer");
-  DN_REQUIRE(n_images > 0 && n_images <= 65535, "gt_strata: %d images is out of range [1, 65535]", n_images);
+  DN_REQUIRE(n_images > 0 && n_images <= dn::kMaxImages, "gt_strata: %d images is out of range [1, 65535]", n_images);
   DN_REQUIRE(g >= 1 && g <= kMaxG, "gt_strata: G = %d ground-truth rows, must be in [1, %d]", g, kMaxG);
   DN_REQUIRE(mode == 0 || mode == 1, "gt_strata: mode = %d, must be 0 (range) or 1 (own visibility)", mode);
   DN_REQUIRE(mode == 0 || gt_own_hits, "gt_strata: mode 1 (own visibility) needs gt_own_hits");

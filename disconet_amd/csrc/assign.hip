@@ -5,8 +5,9 @@
 //
 // Launch sequence (fixed: it depends on the shapes only, never on the data; nothing is read back, nothing is allocated):
 //   assign_init    per (image, row): the row's maximum IoU word = 0, its anchor word = INT_MAX
-//   assign_iou     one wave per 64 neighbouring anchors, the image's ground truth through LDS 64 rows at a time:
-//                  circumscribed-circle test, then the fp64 polygon clip per lane; the anchor's best (IoU, lowest row);
+//   assign_iou     one wave per 64 neighbouring anchors, the image's ground truth through LDS 64 rows at a time with
+//                  rot_iou_device.h's columns, circle test and IoU (stage_columns, circles_meet, pair_iou: the pair body
+//                  of the NMS and of the mAP matching); the anchor's best (IoU, lowest row);
 //                  per row the wave's maximum by a 64-bit integer max in LDS (positive doubles order as integers), then
 //                  one global atomicMax of it
 //   assign_arg     (force match only) per anchor and row: candidates are the anchors whose own best IoU reaches the row's
@@ -24,24 +25,24 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxG = 1024;    // ground-truth rows per image (dn_ap_match's limit)
+constexpr int kMaxG = dn::kMaxGtRows;
 constexpr int kChunk = 64;     // ground-truth rows held in LDS at a time
-constexpr int kMaxImages = 65535;
+using dn::clampi;
+using dn::kMaxImages;
+using GtChunk = dn::BoxColumns<kChunk>;
 
 struct Layout {
   size_t rowmax, rowarg, biou, bgt, total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 Layout layout(int n, long apl, int g) {
+  dn::Carver c;
   Layout L;
-  size_t o = 0;
-  L.rowmax = o; o = align256(o + sizeof(unsigned long long) * (size_t)n * g);
-  L.rowarg = o; o = align256(o + sizeof(int) * (size_t)n * g);
-  L.biou = o;   o = align256(o + sizeof(double) * (size_t)n * apl);
-  L.bgt = o;    o = align256(o + sizeof(int) * (size_t)n * apl);
-  L.total = o;
+  L.rowmax = c.take(sizeof(unsigned long long) * (size_t)n * g);
+  L.rowarg = c.take(sizeof(int) * (size_t)n * g);
+  L.biou = c.take(sizeof(double) * (size_t)n * apl);
+  L.bgt = c.take(sizeof(int) * (size_t)n * apl);
+  L.total = c.at;
   return L;
 }
 
@@ -49,57 +50,12 @@ bool shapes_ok(int n, long apl, int g) {
   return n >= 1 && n <= kMaxImages && apl >= 1 && apl <= (long)INT_MAX - 64 && g >= 1 && g <= kMaxG;
 }
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 __global__ void __launch_bounds__(kThreads) assign_init_kernel(unsigned long long* __restrict__ rowmax,
                                                                int* __restrict__ rowarg, int rows) {
   const int e = blockIdx.x * kThreads + threadIdx.x;
   if (e >= rows) return;
   rowmax[e] = 0ull;
   rowarg[e] = INT_MAX;
-}
-
-// One 64-row piece of an image's ground truth in LDS.
-struct GtChunk {
-  double x[4][kChunk], y[4][kChunk], cx[kChunk], cy[kChunk], radius[kChunk], area[kChunk];
-};
-
-__device__ __forceinline__ void load_chunk(GtChunk& c, const float* __restrict__ gt, int rows, int t) {
-  if (t < rows) {
-    dn::Box64 b;
-    dn::box64(gt + 6 * (size_t)t, b);
-    for (int q = 0; q < 4; ++q) {
-      c.x[q][t] = b.x[q];
-      c.y[q][t] = b.y[q];
-    }
-    c.cx[t] = b.cx;
-    c.cy[t] = b.cy;
-    c.radius[t] = b.radius;
-    c.area[t] = b.area;
-  }
-}
-
-// The strict circumscribed-circle test of the host reference.  The squared-distance comparison in front of it only
-// spares the hypot of pairs that are far apart: its bound is a hundredth wider than the circles' sum, far beyond any
-// rounding, so it never rejects a pair that the test itself would pass.
-__device__ __forceinline__ bool circles_meet(const GtChunk& c, int jj, const dn::Box64& a) {
-#pragma clang fp contract(off)
-  const double dx = c.cx[jj] - a.cx, dy = c.cy[jj] - a.cy, reach = c.radius[jj] + a.radius;
-  if (dx * dx + dy * dy > 1.01 * reach * reach + 1e-12) return false;
-  return hypot(dx, dy) < reach;
-}
-
-__device__ __forceinline__ double pair_iou(const GtChunk& c, int jj, const dn::Box64& a, double* px, double* py,
-                                           double* qx, double* qy) {
-#pragma clang fp contract(off)
-  double bx[4], by[4];
-  for (int q = 0; q < 4; ++q) {
-    bx[q] = c.x[q][jj];
-    by[q] = c.y[q][jj];
-  }
-  const double inter = dn::intersection_area(a.x, a.y, bx, by, px, py, qx, qy);
-  const double uni = a.area + c.area[jj] - inter;
-  return uni > 0 ? inter / uni : 0.0;
 }
 
 // Lane t is anchor i = 64 * blockIdx.x + t of image blockIdx.y.
@@ -110,7 +66,7 @@ __global__ void __launch_bounds__(64) assign_iou_kernel(const float* __restrict_
 #pragma clang fp contract(off)
   __shared__ GtChunk c;
   __shared__ unsigned long long wmax[kChunk];
-  __shared__ double bufx[2][dn::kClipCap][64], bufy[2][dn::kClipCap][64];
+  __shared__ dn::ClipScratch scratch;
   const int img = blockIdx.y, t = threadIdx.x;
   const long i = (long)blockIdx.x * 64 + t;
   const bool live = i < apl;
@@ -122,13 +78,13 @@ __global__ void __launch_bounds__(64) assign_iou_kernel(const float* __restrict_
   for (int j0 = 0; j0 < gc; j0 += kChunk) {
     const int rows = gc - j0 < kChunk ? gc - j0 : kChunk;
     __syncthreads();
-    load_chunk(c, gt + 6 * ((size_t)img * g + j0), rows, t);
+    dn::stage_columns(c, gt + 6 * ((size_t)img * g + j0), rows, t);
     wmax[t] = 0ull;
     __syncthreads();
     if (live) {
       for (int jj = 0; jj < rows; ++jj) {
-        if (!circles_meet(c, jj, a)) continue;
-        const double iou = pair_iou(c, jj, a, &bufx[0][0][t], &bufy[0][0][t], &bufx[1][0][t], &bufy[1][0][t]);
+        if (!dn::circles_meet(c, jj, a)) continue;
+        const double iou = dn::pair_iou(c, jj, a, scratch, t);
         if (iou > 0) atomicMax(&wmax[jj], (unsigned long long)__double_as_longlong(iou));
         if (iou > best) {
           best = iou;
@@ -152,7 +108,7 @@ __global__ void __launch_bounds__(64) assign_arg_kernel(const float* __restrict_
 #pragma clang fp contract(off)
   __shared__ GtChunk c;
   __shared__ double rmax[kChunk];
-  __shared__ double bufx[2][dn::kClipCap][64], bufy[2][dn::kClipCap][64];
+  __shared__ dn::ClipScratch scratch;
   const int img = blockIdx.y, t = threadIdx.x;
   const long i = (long)blockIdx.x * 64 + t;
   const bool live = i < apl;
@@ -164,15 +120,15 @@ __global__ void __launch_bounds__(64) assign_arg_kernel(const float* __restrict_
   for (int j0 = 0; j0 < gc; j0 += kChunk) {
     const int rows = gc - j0 < kChunk ? gc - j0 : kChunk;
     __syncthreads();
-    load_chunk(c, gt + 6 * ((size_t)img * g + j0), rows, t);
+    dn::stage_columns(c, gt + 6 * ((size_t)img * g + j0), rows, t);
     if (t < rows) rmax[t] = __longlong_as_double((long long)rowmax[(size_t)img * g + j0 + t]);
     __syncthreads();
     if (live && mine > 0) {
       for (int jj = 0; jj < rows; ++jj) {
         const double m = rmax[jj];
         if (!(m > 0) || mine < m) continue;     // an anchor that attains the row's maximum has a best IoU of at least it
-        if (!circles_meet(c, jj, a)) continue;
-        const double iou = pair_iou(c, jj, a, &bufx[0][0][t], &bufy[0][0][t], &bufx[1][0][t], &bufy[1][0][t]);
+        if (!dn::circles_meet(c, jj, a)) continue;
+        const double iou = dn::pair_iou(c, jj, a, scratch, t);
         if (iou == m) atomicMin(&rowarg[(size_t)img * g + j0 + jj], (int)i);
       }
     }

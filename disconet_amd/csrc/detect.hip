@@ -12,7 +12,8 @@
 //                      per-workgroup tie counts are scanned, so the lowest indices win whatever the schedule
 //   detect_sort        the k survivors of one image sorted in LDS by (key desc, index asc), decoded with
 //                      decode_device.h (bit for bit dn_decode_boxes), non-candidates (key 0) dropped from the tail
-//   detect_iou_mask    one bit per pair i < j of an image: IoU(i, j) > iou_thr, 64x16 tiles, fp64 polygon clip per lane
+//   detect_iou_mask    one bit per pair i < j of an image: IoU(i, j) > iou_thr, 64x16 tiles; columns, circle test and
+//                      IoU are rot_iou_device.h's (stage_columns, circles_meet, pair_iou), shared with the matching kernels
 //   detect_reduce      one wave per image walks the rows in order (the "removed" words live in its lanes) and writes
 //                      the kept rows, then zero / -1 padding up to top_k
 // Keys are 30-bit (a score is in [0, 1] or NaN), so three 10-bit digits find T.  Only integer atomics are used and
@@ -23,12 +24,13 @@
 //                      ego's frame in fp64), 64-bit sort words (score key | inverted list slot) sorted in LDS, the first
 //                      top_k rows written where detect_sort writes its own
 //   detect_iou_mask, detect_reduce   as above, on those rows; `index` is then the row's source, agent * k_in + row
+// Both entry points hand the sorted rows to one tail (NmsLayout, launch_nms): the carve, the casts and the two launches.
 #include <cmath>
 
 #include "dn_internal.h"
 #include "decode_device.h"
 #include "ego_list.h"
-#include "rot_iou_device.h"   // Box64, box64, intersection_area: rotated IoU in fp64 (shared with ap_match.hip)
+#include "rot_iou_device.h"
 
 namespace {
 
@@ -36,35 +38,56 @@ constexpr int kThreads = 256;
 constexpr int kItems = 16;
 constexpr long kChunk = (long)kThreads * kItems;   // anchors per workgroup of the select passes
 constexpr int kBins = 1024;                         // 10-bit digits
-constexpr int kMaxK = 1024;
-using dn::Box64;
-using dn::box64;
-using dn::intersection_area;
-using dn::kClipCap;
+constexpr int kMaxK = dn::kMaxBoxRows;
 
-struct Layout {
-  size_t keys, hist, gcount, state, ties, cand, sbox, sscore, sidx, nvalid, mask, total;
+// The NMS tail's part of a workspace: the sorted rows of every image (detect_sort or late_gather_sort writes them),
+// the number of them that are valid, and the pair mask.
+struct NmsLayout {
+  size_t sbox, sscore, sidx, nvalid, mask;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+NmsLayout nms_layout(dn::Carver& c, int n, int top_k) {
+  const size_t rows = (size_t)n * top_k, nb = (top_k + 63) / 64;
+  NmsLayout L;
+  L.sbox = c.take(sizeof(float) * 6 * rows);
+  L.sscore = c.take(sizeof(float) * rows);
+  L.sidx = c.take(sizeof(int) * rows);
+  L.nvalid = c.take(sizeof(int) * (size_t)n);
+  L.mask = c.take(sizeof(unsigned long long) * rows * nb);
+  return L;
+}
+
+struct NmsArrays {
+  float *sbox, *sscore;
+  int *sidx, *nvalid;
+  unsigned long long* mask;
+};
+
+NmsArrays nms_arrays(const NmsLayout& L, char* ws) {
+  return {reinterpret_cast<float*>(ws + L.sbox), reinterpret_cast<float*>(ws + L.sscore),
+          reinterpret_cast<int*>(ws + L.sidx), reinterpret_cast<int*>(ws + L.nvalid),
+          reinterpret_cast<unsigned long long*>(ws + L.mask)};
+}
+
+struct Layout {
+  size_t keys, hist, gcount, state, ties, cand;
+  NmsLayout nms;
+  size_t total;
+};
 
 Layout layout(int n, long apl, int top_k) {
   const long bpi = (apl + kChunk - 1) / kChunk;
-  const long nb = (top_k + 63) / 64;
+  const size_t hist_bytes = sizeof(unsigned) * (size_t)n * 3 * kBins;
+  dn::Carver c;
   Layout L;
-  size_t o = 0;
-  L.keys = o;   o = align256(o + sizeof(unsigned) * (size_t)n * apl);
-  L.hist = o;   o += sizeof(unsigned) * (size_t)n * 3 * kBins;          // hist and gcount: one zero fill
-  L.gcount = o; o = align256(o + sizeof(unsigned) * (size_t)n);
-  L.state = o;  o = align256(o + sizeof(unsigned) * (size_t)n * 8);
-  L.ties = o;   o = align256(o + sizeof(unsigned) * (size_t)n * bpi);
-  L.cand = o;   o = align256(o + sizeof(unsigned long long) * (size_t)n * top_k);
-  L.sbox = o;   o = align256(o + sizeof(float) * 6 * (size_t)n * top_k);
-  L.sscore = o; o = align256(o + sizeof(float) * (size_t)n * top_k);
-  L.sidx = o;   o = align256(o + sizeof(int) * (size_t)n * top_k);
-  L.nvalid = o; o = align256(o + sizeof(int) * (size_t)n);
-  L.mask = o;   o = align256(o + sizeof(unsigned long long) * (size_t)n * top_k * nb);
-  L.total = o;
+  L.keys = c.take(sizeof(unsigned) * (size_t)n * apl);
+  L.hist = c.take(hist_bytes + sizeof(unsigned) * (size_t)n);            // hist and gcount: one region, one zero fill
+  L.gcount = L.hist + hist_bytes;
+  L.state = c.take(sizeof(unsigned) * (size_t)n * 8);
+  L.ties = c.take(sizeof(unsigned) * (size_t)n * bpi);
+  L.cand = c.take(sizeof(unsigned long long) * (size_t)n * top_k);
+  L.nms = nms_layout(c, n, top_k);
+  L.total = c.at;
   return L;
 }
 
@@ -286,45 +309,25 @@ __global__ void __launch_bounds__(64) detect_iou_mask_kernel(const float* __rest
                                                              const int* __restrict__ nvalid, int top_k, int nb,
                                                              double iou_thr,
                                                              unsigned long long* __restrict__ mask) {
-  __shared__ double cxs[4][kMaskCols], cys[4][kMaskCols], ccx[kMaskCols], ccy[kMaskCols], crad[kMaskCols],
-      carea[kMaskCols];
-  __shared__ double bufx[2][kClipCap][64], bufy[2][kClipCap][64];
+#pragma clang fp contract(off)
+  __shared__ dn::BoxColumns<kMaskCols> cols;
+  __shared__ dn::ClipScratch scratch;
   const int cb = blockIdx.x / 4, q = blockIdx.x % 4, rb = blockIdx.y, img = blockIdx.z, t = threadIdx.x;
   const int nv = nvalid[img];
   if (cb < rb || cb * 64 >= nv) return;
   const int j0 = cb * 64 + q * kMaskCols;
-  if (t < kMaskCols && j0 + t < nv) {
-    Box64 b;
-    box64(sbox + 6 * ((size_t)img * top_k + j0 + t), b);
-    for (int k = 0; k < 4; ++k) {
-      cxs[k][t] = b.x[k];
-      cys[k][t] = b.y[k];
-    }
-    ccx[t] = b.cx;
-    ccy[t] = b.cy;
-    crad[t] = b.radius;
-    carea[t] = b.area;
-  }
+  const int jend = nv - j0 < kMaskCols ? nv - j0 : kMaskCols;   // <= 0: the piece lies behind the last valid row
+  dn::stage_columns(cols, sbox + 6 * ((size_t)img * top_k + j0), jend, t);
   __syncthreads();
   const int i = rb * 64 + t;
   if (i >= nv) return;
-  Box64 a;
-  box64(sbox + 6 * ((size_t)img * top_k + i), a);
+  dn::Box64 a;
+  dn::box64(sbox + 6 * ((size_t)img * top_k + i), a);
   unsigned bits = 0;
-  const int jend = nv - j0 < kMaskCols ? nv - j0 : kMaskCols;
   for (int jj = 0; jj < jend; ++jj) {
     if (j0 + jj <= i) continue;
-    const double dist = hypot(ccx[jj] - a.cx, ccy[jj] - a.cy);
-    if (!(dist < crad[jj] + a.radius)) continue;   // circumscribed circles apart: IoU 0
-    double bx[4], by[4];
-    for (int k = 0; k < 4; ++k) {
-      bx[k] = cxs[k][jj];
-      by[k] = cys[k][jj];
-    }
-    const double inter = intersection_area(a.x, a.y, bx, by, &bufx[0][0][t], &bufy[0][0][t], &bufx[1][0][t],
-                                           &bufy[1][0][t]);
-    const double uni = a.area + carea[jj] - inter;
-    if (uni > 0 && inter / uni > iou_thr) bits |= 1u << jj;
+    if (!dn::circles_meet(cols, jj, a)) continue;   // circumscribed circles apart: IoU 0
+    if (dn::pair_iou(cols, jj, a, scratch, t) > iou_thr) bits |= 1u << jj;   // iou_thr >= 0: an IoU of 0 never sets a bit
   }
   reinterpret_cast<unsigned short*>(mask + ((size_t)img * top_k + i) * nb + cb)[q] = (unsigned short)bits;
 }
@@ -400,20 +403,21 @@ __global__ void __launch_bounds__(kThreads) detect_reduce_kernel(const float* __
   if (threadIdx.x == 0) count[img] = n;
 }
 
-// detect_reduce's dynamic LDS (the mask rows of one image, up to 128 KB) is reserved once per device, by whichever entry
-// point runs first
-int reserve_reduce_lds(const char* who) {
-  const size_t reduce_lds = sizeof(unsigned long long) * (size_t)kMaxK * ((kMaxK + 63) / 64);
+// The NMS tail of dn_detect and dn_late_fuse on the sorted rows of n images.  detect_reduce's dynamic LDS (the mask rows
+// of one image, up to 128 KB) is reserved once per device, by whichever entry point runs first.
+int launch_nms(const char* who, const NmsLayout& L, char* ws, int n, int top_k, double iou_thr, float* boxes,
+               float* scores, int* index, int* count, hipStream_t s) {
   static dn::PerDeviceFlag lds_flag;
-  bool& lds_ready = lds_flag.here();
-  if (!lds_ready) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_reduce_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds);
-    if (e != hipSuccess)
-      return dn::fail(DN_ERR_LAUNCH, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, reduce_lds, hipGetErrorString(e));
-    lds_ready = true;
-  }
-  return DN_OK;
+  if (const int rc = dn::reserve_dynamic_lds(reinterpret_cast<const void*>(detect_reduce_kernel), lds_flag,
+                                             sizeof(unsigned long long) * (size_t)kMaxK * ((kMaxK + 63) / 64), who))
+    return rc;
+  const NmsArrays a = nms_arrays(L, ws);
+  const int nb = (top_k + 63) / 64;
+  hipLaunchKernelGGL(detect_iou_mask_kernel, dim3(4 * nb, nb, n), dim3(64), 0, s, a.sbox, a.nvalid, top_k, nb, iou_thr,
+                     a.mask);
+  hipLaunchKernelGGL(detect_reduce_kernel, dim3(n), dim3(kThreads), sizeof(unsigned long long) * (size_t)top_k * nb, s,
+                     a.sbox, a.sscore, a.sidx, a.nvalid, a.mask, top_k, nb, boxes, scores, index, count);
+  return dn::check_launch(who);
 }
 
 // ---- late fusion ----------------------------------------------------------------------------------------------------
@@ -421,27 +425,10 @@ constexpr int kLateMaxAgents = 16;
 constexpr int kLateMaxSlots = 8192;      // agents * k_in: 64 KB of sort words in LDS
 constexpr int kLateThreads = 512;
 
-struct LateLayout {
-  size_t sbox, sscore, sidx, nvalid, mask, total;
-};
-
-LateLayout late_layout(int n, int top_k) {
-  const long nb = (top_k + 63) / 64;
-  LateLayout L;
-  size_t o = 0;
-  L.sbox = o;   o = align256(o + sizeof(float) * 6 * (size_t)n * top_k);
-  L.sscore = o; o = align256(o + sizeof(float) * (size_t)n * top_k);
-  L.sidx = o;   o = align256(o + sizeof(int) * (size_t)n * top_k);
-  L.nvalid = o; o = align256(o + sizeof(int) * (size_t)n);
-  L.mask = o;   o = align256(o + sizeof(unsigned long long) * (size_t)n * top_k * nb);
-  L.total = o;
-  return L;
-}
-
 bool late_shape_ok(int batch, int agents, int k_in, int top_k, int ego_first, int ego_count) {
   return batch > 0 && agents > 0 && agents <= kLateMaxAgents && k_in >= 1 && k_in <= kMaxK &&
          agents * k_in <= kLateMaxSlots && top_k >= 1 && top_k <= kMaxK && ego_first >= 0 && ego_count > 0 &&
-         ego_first + ego_count <= agents && (long)batch * ego_count <= 65535;
+         ego_first + ego_count <= agents && (long)batch * ego_count <= dn::kMaxImages;
 }
 
 struct LateExtents {
@@ -567,7 +554,7 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
                          float* boxes, float* scores, int* index, int* count, void* workspace,
                          size_t workspace_bytes, void* stream) {
   DN_REQUIRE(cls && loc && anchors && boxes && scores && index && count && workspace, "detect: null pointer");
-  DN_REQUIRE(n_images > 0 && n_images <= 65535 && anchors_per_image > 0 && anchors_per_image < (1L << 31),
+  DN_REQUIRE(n_images > 0 && n_images <= dn::kMaxImages && anchors_per_image > 0 && anchors_per_image < (1L << 31),
              "detect: %d images of %ld anchors is out of range", n_images, anchors_per_image);
   DN_REQUIRE(top_k >= 1 && top_k <= kMaxK, "detect: top_k = %d, must be in [1, %d]", top_k, kMaxK);
   DN_REQUIRE(std::isfinite(iou_thr) && iou_thr >= 0, "detect: iou_thr = %g, must be finite and >= 0", iou_thr);
@@ -575,8 +562,6 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
   DN_REQUIRE(workspace_bytes >= L.total, "detect: workspace of %zu bytes, %zu needed (dn_detect_workspace_bytes)",
              workspace_bytes, L.total);
   const long apl = anchors_per_image;
-  const int nb = (top_k + 63) / 64;
-  if (const int rc = reserve_reduce_lds("detect")) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   unsigned* keys = reinterpret_cast<unsigned*>(ws + L.keys);
@@ -585,11 +570,7 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
   unsigned* state = reinterpret_cast<unsigned*>(ws + L.state);
   unsigned* ties = reinterpret_cast<unsigned*>(ws + L.ties);
   unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + L.cand);
-  float* sbox = reinterpret_cast<float*>(ws + L.sbox);
-  float* sscore = reinterpret_cast<float*>(ws + L.sscore);
-  int* sidx = reinterpret_cast<int*>(ws + L.sidx);
-  int* nvalid = reinterpret_cast<int*>(ws + L.nvalid);
-  unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + L.mask);
+  const NmsArrays a = nms_arrays(L.nms, ws);
 
   if (dn::zero_fill(hist, L.gcount + sizeof(unsigned) * n_images - L.hist, s) != hipSuccess)
     return dn::fail(DN_ERR_LAUNCH, "detect: zero fill of the histograms failed");
@@ -599,18 +580,15 @@ extern "C" int dn_detect(const float* cls, const float* loc, const float* anchor
     hipLaunchKernelGGL(detect_radix_kernel, grid, dim3(kThreads), 0, s, keys, apl, top_k, pass, hist, state, ties);
   hipLaunchKernelGGL(detect_gather_kernel, grid, dim3(kThreads), 0, s, keys, apl, top_k, state, ties, gcount, cand);
   hipLaunchKernelGGL(detect_sort_kernel, dim3(n_images), dim3(kSortThreads), 0, s, cls, loc, anchors, apl, top_k, cand,
-                     sbox, sscore, sidx, nvalid);
-  hipLaunchKernelGGL(detect_iou_mask_kernel, dim3(4 * nb, nb, n_images), dim3(64), 0, s, sbox, nvalid, top_k, nb, iou_thr,
-                     mask);
-  hipLaunchKernelGGL(detect_reduce_kernel, dim3(n_images), dim3(kThreads),
-                     sizeof(unsigned long long) * (size_t)top_k * nb, s, sbox, sscore, sidx, nvalid, mask, top_k, nb,
-                     boxes, scores, index, count);
-  return dn::check_launch("detect");
+                     a.sbox, a.sscore, a.sidx, a.nvalid);
+  return launch_nms("detect", L.nms, ws, n_images, top_k, iou_thr, boxes, scores, index, count, s);
 }
 
 extern "C" size_t dn_late_fuse_workspace_bytes(int batch, int agents, int k_in, int top_k, int ego_first, int ego_count) {
   if (!late_shape_ok(batch, agents, k_in, top_k, ego_first, ego_count)) return 0;
-  return late_layout(batch * ego_count, top_k).total;
+  dn::Carver c;
+  (void)nms_layout(c, batch * ego_count, top_k);
+  return c.at;
 }
 
 extern "C" int dn_late_fuse(const float* boxes, const float* scores, const int32_t* count, const float* trans,
@@ -627,7 +605,7 @@ extern "C" int dn_late_fuse(const float* boxes, const float* scores, const int32
   DN_REQUIRE(std::isfinite(iou_thr) && iou_thr >= 0, "late fuse: iou_thr = %g, must be finite and >= 0", iou_thr);
   DN_REQUIRE(ego_first >= 0 && ego_count > 0 && ego_first + ego_count <= agents,
              "late fuse: ego range [%d, %d) outside 0..%d", ego_first, ego_first + ego_count, agents);
-  DN_REQUIRE((long)batch * ego_count <= 65535, "late fuse: %ld output images, at most 65535", (long)batch * ego_count);
+  DN_REQUIRE((long)batch * ego_count <= dn::kMaxImages, "late fuse: %ld output images, at most 65535", (long)batch * ego_count);
   // (the shapes first: a refused shape may come with empty, null outputs)
   DN_REQUIRE(boxes && scores && count && trans && num_agent && out_boxes && out_scores && out_source && out_count &&
                  workspace, "late fuse: null pointer");
@@ -642,35 +620,21 @@ extern "C" int dn_late_fuse(const float* boxes, const float* scores, const int32
                ext.xlo, ext.xhi, ext.ylo, ext.yhi);
   }
   const int n = batch * ego_count;
-  const LateLayout L = late_layout(n, top_k);
-  DN_REQUIRE(workspace_bytes >= L.total, "late fuse: workspace of %zu bytes, %zu needed (dn_late_fuse_workspace_bytes)",
-             workspace_bytes, L.total);
-  if (const int rc = reserve_reduce_lds("late fuse")) return rc;
-  const size_t sort_lds = sizeof(unsigned long long) * (size_t)kLateMaxSlots;
+  dn::Carver carve;
+  const NmsLayout L = nms_layout(carve, n, top_k);
+  DN_REQUIRE(workspace_bytes >= carve.at, "late fuse: workspace of %zu bytes, %zu needed (dn_late_fuse_workspace_bytes)",
+             workspace_bytes, carve.at);
   static dn::PerDeviceFlag sort_flag;
-  bool& sort_ready = sort_flag.here();
-  if (!sort_ready) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(late_gather_sort_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
-    if (e != hipSuccess)
-      return dn::fail(DN_ERR_LAUNCH, "late fuse: hipFuncSetAttribute(%zu B LDS): %s", sort_lds, hipGetErrorString(e));
-    sort_ready = true;
-  }
+  if (const int rc = dn::reserve_dynamic_lds(reinterpret_cast<const void*>(late_gather_sort_kernel), sort_flag,
+                                             sizeof(unsigned long long) * (size_t)kLateMaxSlots, "late fuse"))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
-  float* sbox = reinterpret_cast<float*>(ws + L.sbox);
-  float* sscore = reinterpret_cast<float*>(ws + L.sscore);
-  int* sidx = reinterpret_cast<int*>(ws + L.sidx);
-  int* nvalid = reinterpret_cast<int*>(ws + L.nvalid);
-  unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + L.mask);
-  const int nb = (top_k + 63) / 64;
+  const NmsArrays a = nms_arrays(L, ws);
   int p = 1;                                   // the launch depends on the shapes only: LDS for the longest possible list
   while (p < agents * k_in) p <<= 1;
   hipLaunchKernelGGL(late_gather_sort_kernel, dim3(n), dim3(kLateThreads), sizeof(unsigned long long) * (size_t)p, s,
-                     boxes, scores, count, trans, num_agent, batch, agents, k_in, only_v2i, ego_first, top_k, ext, sbox,
-                     sscore, sidx, nvalid);
-  hipLaunchKernelGGL(detect_iou_mask_kernel, dim3(4 * nb, nb, n), dim3(64), 0, s, sbox, nvalid, top_k, nb, iou_thr, mask);
-  hipLaunchKernelGGL(detect_reduce_kernel, dim3(n), dim3(kThreads), sizeof(unsigned long long) * (size_t)top_k * nb, s,
-                     sbox, sscore, sidx, nvalid, mask, top_k, nb, out_boxes, out_scores, out_source, out_count);
-  return dn::check_launch("late fuse");
+                     boxes, scores, count, trans, num_agent, batch, agents, k_in, only_v2i, ego_first, top_k, ext, a.sbox,
+                     a.sscore, a.sidx, a.nvalid);
+  return launch_nms("late fuse", L, ws, n, top_k, iou_thr, out_boxes, out_scores, out_source, out_count, s);
 }

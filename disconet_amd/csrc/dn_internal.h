@@ -53,6 +53,31 @@ inline int static_lds_of(const void* kernel, PerDeviceFlag& flag, int* cache, in
   return cache[dev & 63];
 }
 
+// Reserve `bytes` of dynamic LDS for `kernel`, once per device.  `flag` is a function-local static of the caller.
+inline int reserve_dynamic_lds(const void* kernel, PerDeviceFlag& flag, size_t bytes, const char* who) {
+  bool& ready = flag.here();
+  if (!ready) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess)
+      return fail(DN_ERR_LAUNCH, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, bytes, hipGetErrorString(e));
+    ready = true;
+  }
+  return DN_OK;
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Carves a caller-owned workspace into arrays: take(bytes) returns the current offset and advances to the next 256-byte
+// boundary; `at` is then the bytes needed so far.
+struct Carver {
+  size_t at = 0;
+  size_t take(size_t bytes) {
+    const size_t o = at;
+    at = align256(at + bytes);
+    return o;
+  }
+};
+
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(DN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));

@@ -1,13 +1,21 @@
-// Rotated-box IoU in fp64, operation for operation postprocess._corners / _intersection_area: the geometry shared by
-// the NMS of detect.hip and the ground-truth matching of ap_match.hip.  Every function carries
-// `#pragma clang fp contract(off)`: the library is built with hipcc's default contraction, and a fused multiply-add
-// here would make the device's decisions differ from the host reference's.
+// Box geometry shared by the kernels that decide from rotated-box IoU in fp64: the NMS of dn_detect and dn_late_fuse
+// (detect.hip), the ground-truth matching of dn_ap_match / dn_ap_match_strata (ap_match.hip) and the anchor assignment
+// of dn_assign_targets (assign.hip).  Corners, the circumscribed-circle test, the polygon clip and the IoU are operation
+// for operation postprocess._corners / _intersection_area / nms_rotated.  All of it is contract code: a detection that is
+// a true positive for dn_ap_match at IoU v is the box dn_detect suppresses at any threshold below v, because both run the
+// pair body below -- so a change to the circle test, a guard or the staging is made HERE, once.  Every function carries `#pragma clang fp contract(off)`: the library is built with hipcc's default contraction, and a
+// fused multiply-add here would make the device's decisions differ from the host reference's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace dn {
 
-constexpr int kClipCap = 12;   // vertices of a clipped polygon kept per lane (a convex quad clipped 4 times has <= 8)
+constexpr int kClipCap = 12;        // vertices of a clipped polygon kept per lane (a convex quad clipped 4 times has <= 8)
+constexpr int kMaxBoxRows = 1024;   // box rows per image: dn_detect's top_k, dn_late_fuse's k_in, dn_ap_match's K
+constexpr int kMaxGtRows = 1024;    // ground-truth rows per image
+constexpr int kMaxImages = 65535;   // images per call (a grid dimension)
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 struct Box64 {
   double x[4], y[4];
@@ -78,6 +86,64 @@ __device__ inline double intersection_area(const double* ax, const double* ay, c
     s2 = s2 + py[64 * k] * px[64 * k1];
   }
   return 0.5 * fabs(s1 - s2);
+}
+
+// N boxes of one image in LDS, the columns a 64-lane wave tests its rows against.
+template <int N>
+struct BoxColumns {
+  double x[4][N], y[4][N], cx[N], cy[N], radius[N], area[N];
+};
+
+// Lane t < rows stages row t of `boxes` (float6 rows) as column t; the caller's barrier follows.
+template <int N>
+__device__ __forceinline__ void stage_columns(BoxColumns<N>& c, const float* __restrict__ boxes, int rows, int t) {
+  if (t < rows) {
+    Box64 b;
+    box64(boxes + 6 * (size_t)t, b);
+    for (int q = 0; q < 4; ++q) {
+      c.x[q][t] = b.x[q];
+      c.y[q][t] = b.y[q];
+    }
+    c.cx[t] = b.cx;
+    c.cy[t] = b.cy;
+    c.radius[t] = b.radius;
+    c.area[t] = b.area;
+  }
+}
+
+// The two ping-pong polygons of intersection_area for each of a wave's 64 lanes.
+struct ClipScratch {
+  double x[2][kClipCap][64], y[2][kClipCap][64];
+  __device__ __forceinline__ double clip(const double* ax, const double* ay, const double* bx, const double* by, int lane) {
+    return intersection_area(ax, ay, bx, by, &x[0][0][lane], &y[0][0][lane], &x[1][0][lane], &y[1][0][lane]);
+  }
+};
+
+// The strict circumscribed-circle test of the host reference.  The squared-distance comparison in front of it only
+// spares the hypot of pairs that are far apart: its bound is a hundredth wider than the circles' sum, far beyond any
+// rounding, so it never rejects a pair that the test itself would pass.  A NaN makes the comparison false and the pair
+// goes on to the strict test; an infinite distance under a finite reach is rejected by both.
+template <int N>
+__device__ __forceinline__ bool circles_meet(const BoxColumns<N>& c, int jj, const Box64& a) {
+#pragma clang fp contract(off)
+  const double dx = c.cx[jj] - a.cx, dy = c.cy[jj] - a.cy, reach = c.radius[jj] + a.radius;
+  if (dx * dx + dy * dy > 1.01 * reach * reach + 1e-12) return false;
+  return hypot(dx, dy) < reach;
+}
+
+// IoU of box a and column jj; 0 when the union is not positive (or not a number).
+template <int N>
+__device__ __forceinline__ double pair_iou(const BoxColumns<N>& c, int jj, const Box64& a, ClipScratch& scratch,
+                                           int lane) {
+#pragma clang fp contract(off)
+  double bx[4], by[4];
+  for (int q = 0; q < 4; ++q) {
+    bx[q] = c.x[q][jj];
+    by[q] = c.y[q][jj];
+  }
+  const double inter = scratch.clip(a.x, a.y, bx, by, lane);
+  const double uni = a.area + c.area[jj] - inter;
+  return uni > 0 ? inter / uni : 0.0;
 }
 
 }  // namespace dn
