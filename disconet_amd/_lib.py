@@ -232,6 +232,8 @@ SIGNATURES = {
                                  c_float, c_void_p]),
     "dn_conv_wgrad_sp_z": (c_int, [POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                  c_float, c_void_p]),
+    "dn_conv_wgrad_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int), c_int]),
+    "dn_conv_wgrad_last_form": (c_int, [POINTER(c_int), c_int]),
     "dn_conv_dgrad_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p]),
     "dn_conv_dgrad_class_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,

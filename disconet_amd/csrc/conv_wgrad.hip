@@ -392,7 +392,17 @@ int validate(const dn_conv_desc* d) {
 
 struct Plan {
   int h_out, w_out, tiles_x, tiles_y, n_tiles, n_cot, n_cit, n_slices, taps, ct;
+  int th, tw;                      // output pixels of one tile
 };
+
+// tools and tests only (dn_conv_wgrad_last_form): the record every entry point writes once nothing can refuse the call any more
+struct WgradLastForm {
+  int entry;                       // 0 dn_conv_wgrad, 1 dn_conv_wgrad_sp, 2 dn_conv_wgrad_sp_z
+  int ks, stride, block, zsp;      // the kernel instantiation
+  int vec0, vec1, vecz;            // 16-byte loads of source 0 / source 1 / dz (split-f16 kernels: vec0 = vec1 = vecx)
+  int grid, n_slices;
+};
+WgradLastForm g_wgrad_last = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 Plan make_plan(const dn_conv_desc& d) {
   Plan p;
@@ -401,6 +411,8 @@ Plan make_plan(const dn_conv_desc& d) {
           d.c1 % 64 == 0 && d.ld0 % 4 == 0 && d.ld1 % 4 == 0 && d.ldo % 4 == 0)
              ? 64 : 32;
   const int th = (d.stride == 1 && p.ct == 32) ? 8 : 4, tw = 16;
+  p.th = th;
+  p.tw = tw;
   p.h_out = out_dim(d.h_in, d.ksize, d.stride);
   p.w_out = out_dim(d.w_in, d.ksize, d.stride);
   p.tiles_x = (p.w_out + tw - 1) / tw;
@@ -469,9 +481,10 @@ extern "C" int dn_conv_wgrad(const dn_conv_desc* d, const float* src0, const flo
   a.vecz = aligned(dz, d->c_out, d->ldo);
   hipStream_t s = (hipStream_t)stream;
   int rc;
+  // the 64-channel blocks' vector path also needs 16-byte aligned bases
+  DN_REQUIRE(p.ct != 64 || (a.vec0 && a.vec1 && a.vecz), "wgrad: 64-channel blocks need 16-byte aligned sources");
+  g_wgrad_last = WgradLastForm{0, d->ksize, d->stride, p.ct, 0, a.vec0, a.vec1, a.vecz, p.n_cot * p.n_cit * p.n_slices, p.n_slices};
   if (p.ct == 64) {
-    // the vector path also needs 16-byte aligned bases
-    DN_REQUIRE(a.vec0 && a.vec1 && a.vecz, "wgrad: 64-channel blocks need 16-byte aligned sources");
     constexpr int lds = (6 * 18 * 64 + 64 * 64) * 4;
     static dn::PerDeviceFlag ready_flag;
     bool& ready = ready_flag.here();
@@ -517,6 +530,8 @@ Plan make_plan_sp(const dn_conv_desc& d, int cb) {
   p.h_out = out_dim(d.h_in, 3, d.stride);
   p.w_out = out_dim(d.w_in, 3, d.stride);
   const int th = d.stride == 2 ? (cb == 64 ? WspShape2<64>::TH : WspShape2<32>::TH) : (cb == 64 ? WspShape<64>::TH : WspShape<32>::TH);
+  p.th = th;
+  p.tw = 16;
   p.tiles_x = (p.w_out + 15) / 16;
   p.tiles_y = (p.h_out + th - 1) / th;
   p.n_tiles = d.n_images * p.tiles_x * p.tiles_y;
@@ -601,6 +616,7 @@ int conv_wgrad_sp_impl(const dn_conv_desc* d, const float* src0, const float* sr
   a.dz_lift = dz_lift; a.x_lift = x_lift; a.vecx = vecx ? 1 : 0;
   a.dz_sp = static_cast<const unsigned char*>(dz_sp);
   hipStream_t s = (hipStream_t)stream;
+  g_wgrad_last = WgradLastForm{dz_sp ? 2 : 1, 3, d->stride, cb, dz_sp ? 1 : 0, a.vecx, a.vecx, 1, p.n_cot * p.n_cit * p.n_slices, p.n_slices};
   if (int rc = dz_sp ? (d->stride == 2 ? (cb == 64 ? launch_sp<64, 2, true>(a, p, s) : launch_sp<32, 2, true>(a, p, s))
                                        : (cb == 64 ? launch_sp<64, 1, true>(a, p, s) : launch_sp<32, 1, true>(a, p, s)))
                      : (d->stride == 2 ? (cb == 64 ? launch_sp<64, 2>(a, p, s) : launch_sp<32, 2>(a, p, s))
@@ -614,6 +630,31 @@ int conv_wgrad_sp_impl(const dn_conv_desc* d, const float* src0, const float* sr
   return dn::check_launch("wgrad_reduce_kernel");
 }
 }  // namespace
+
+extern "C" int dn_conv_wgrad_plan(const dn_conv_desc* d, int sp, int* out, int n) {
+  if (int rc = validate(d)) return rc;
+  DN_REQUIRE(out && n > 0, "wgrad plan: null pointer / no room");
+  Plan p;
+  if (sp) {
+    const int cb = sp_block(*d);
+    DN_REQUIRE(cb != 0, "wgrad plan: the layer has no split-f16 kernel (dn_conv_wgrad_sp_supported)");
+    p = make_plan_sp(*d, cb);
+  } else {
+    p = make_plan(*d);
+  }
+  const int f[12] = {p.ct, p.th, p.tw, p.h_out, p.w_out, p.tiles_x, p.tiles_y, p.n_tiles, p.n_cot, p.n_cit, p.n_slices, p.taps};
+  for (int i = 0; i < n && i < 12; ++i) out[i] = f[i];
+  return 12;
+}
+
+extern "C" int dn_conv_wgrad_last_form(int* out, int n) {
+  constexpr int kInts = (int)(sizeof(WgradLastForm) / sizeof(int));
+  static_assert(sizeof(WgradLastForm) == 10 * sizeof(int), "dn_conv_wgrad_last_form: the record is 10 ints");
+  DN_REQUIRE(out && n > 0, "wgrad last form: null pointer / no room");
+  const int* f = reinterpret_cast<const int*>(&g_wgrad_last);
+  for (int i = 0; i < n && i < kInts; ++i) out[i] = f[i];
+  return kInts;
+}
 
 namespace dn { void range_collect_conv_wgrad(unsigned* dst, bool reset, hipStream_t s) { sp_range_collect_here(dst, reset, s); } }
 

@@ -47,6 +47,20 @@ __device__ inline void zsp_put(unsigned* H, int slot, const u32x4 a, const u32x4
   *reinterpret_cast<u32x4*>(&H[slot + 4]) = hi4;
 }
 
+// Range flags of the staging pass (sp_device.h :: g_sp_range_flags).  The maximum is taken of the lifted values BEFORE the clamp, so
+// "clamped" (bit 0: this step's gradients are invalid) is raised by a value BEYOND +-65504 only, as include/disconet_train.h states: a
+// lifted value of exactly +-65504 is the largest binary16 and is stored as it is.  (note_range() sees clamped values, cannot tell the
+// two apart and reports both.)
+__device__ inline float lifted_max(float amax, const f32x4 a, const f32x4 b) {
+  amax = fmaxf(fmaxf(amax, fabsf(a[0])), fabsf(a[1]));
+  amax = fmaxf(fmaxf(amax, fabsf(a[2])), fabsf(a[3]));
+  amax = fmaxf(fmaxf(amax, fabsf(b[0])), fabsf(b[1]));
+  return fmaxf(fmaxf(amax, fabsf(b[2])), fabsf(b[3]));
+}
+__device__ inline void note_lifted_range(float amax) {
+  if (amax > 16384.f) atomicOr(&g_sp_range_flags, amax > 65504.f ? 3u : 2u);
+}
+
 // CB = channels per side of a workgroup's (co, ci) block.
 //   64: four waves = the four 32 x 32 quadrants, each over all pixels of a 4 x 16 tile (3x3 layers with >= 64 channels both sides).
 //   32: ONE 32 x 32 block; the four waves split the rows of an 8 x 16 tile (two each) and meet in a fixed-order LDS sum at the end
@@ -184,8 +198,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradSpArgs
   // two pixels x four channels -> per channel one dword (pixel 0 in the low half, pixel 1 in the high half), hi and lo parts
   auto put = [&](unsigned* H, unsigned* L, int slot, const f32x4 p0, const f32x4 p1, float lift) {
     u32x2 h01, l01, h23, l23;
-    split4(f32x4{p0[0] * lift, p1[0] * lift, p0[1] * lift, p1[1] * lift}, h01, l01, amax);
-    split4(f32x4{p0[2] * lift, p1[2] * lift, p0[3] * lift, p1[3] * lift}, h23, l23, amax);
+    const f32x4 v01 = {p0[0] * lift, p1[0] * lift, p0[1] * lift, p1[1] * lift}, v23 = {p0[2] * lift, p1[2] * lift, p0[3] * lift, p1[3] * lift};
+    amax = lifted_max(amax, v01, v23);
+    split4(v01, h01, l01);
+    split4(v23, h23, l23);
     *reinterpret_cast<u32x4*>(&H[slot]) = u32x4{h01[0], h01[1], h23[0], h23[1]};
     *reinterpret_cast<u32x4*>(&L[slot]) = u32x4{l01[0], l01[1], l23[0], l23[1]};
   };
@@ -267,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradSpArgs
     if (more) store_tile();
     __syncthreads();
   }
-  note_range(amax);
+  note_lifted_range(amax);
 
   float* out = a.partial + ((size_t)(slice * a.n_cot + cot) * a.n_cit + cit) * (9 * CB * CB);
   if constexpr (CB == 64) {
@@ -424,8 +440,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_s2_kernel(const WgradSpA
   };
   auto put = [&](unsigned* H, unsigned* L, int slot, const f32x4 p0, const f32x4 p1, float lift) {
     u32x2 h01, l01, h23, l23;
-    split4(f32x4{p0[0] * lift, p1[0] * lift, p0[1] * lift, p1[1] * lift}, h01, l01, amax);
-    split4(f32x4{p0[2] * lift, p1[2] * lift, p0[3] * lift, p1[3] * lift}, h23, l23, amax);
+    const f32x4 v01 = {p0[0] * lift, p1[0] * lift, p0[1] * lift, p1[1] * lift}, v23 = {p0[2] * lift, p1[2] * lift, p0[3] * lift, p1[3] * lift};
+    amax = lifted_max(amax, v01, v23);
+    split4(v01, h01, l01);
+    split4(v23, h23, l23);
     *reinterpret_cast<u32x4*>(&H[slot]) = u32x4{h01[0], h01[1], h23[0], h23[1]};
     *reinterpret_cast<u32x4*>(&L[slot]) = u32x4{l01[0], l01[1], l23[0], l23[1]};
   };
@@ -507,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_s2_kernel(const WgradSpA
     if (more) store_tile();
     __syncthreads();
   }
-  note_range(amax);
+  note_lifted_range(amax);
 
   float* out = a.partial + ((size_t)(slice * a.n_cot + cot) * a.n_cit + cit) * (9 * CB * CB);
   if constexpr (CB == 64) {

@@ -68,6 +68,32 @@ def conv_wgrad_sp_supported(desc):
     return bool(_lib.load().dn_conv_wgrad_sp_supported(ctypes.byref(desc)))
 
 
+WGRAD_PLAN_FIELDS = ("ct", "TH", "TW", "h_out", "w_out", "tiles_x", "tiles_y", "n_tiles", "n_cot", "n_cit", "n_slices", "taps")
+WGRAD_FORM_FIELDS = ("entry", "ks", "stride", "block", "zsp", "vec0", "vec1", "vecz", "grid", "n_slices")
+
+
+def _ints(fn, name, fields, *args):
+    buf = (ctypes.c_int * len(fields))()
+    n = fn(*args, buf, len(fields))
+    if n < 0:
+        check(n, name)
+    if n != len(fields):
+        raise _lib.DnError("%s: %d fields, expected %d" % (name, n, len(fields)))
+    return dict(zip(fields, (int(v) for v in buf)))
+
+
+def conv_wgrad_plan(desc, sp=False):
+    """-> dict: the weight gradient's plan for the layer (dn_conv_wgrad_plan; tools and tests): the fp32 kernels' (sp False) or
+    the split-f16 kernels'.  Host only: runs without a GPU."""
+    return _ints(_lib.load().dn_conv_wgrad_plan, "dn_conv_wgrad_plan", WGRAD_PLAN_FIELDS, ctypes.byref(desc), int(bool(sp)))
+
+
+def conv_wgrad_last_form():
+    """-> dict: which kernel the last weight-gradient launch of this process ran (dn_conv_wgrad_last_form; tools and tests).
+    Host-side record, not thread-safe."""
+    return _ints(_lib.load().dn_conv_wgrad_last_form, "dn_conv_wgrad_last_form", WGRAD_FORM_FIELDS)
+
+
 def dgrad_weights(w, ci_first=0, c_in=None):
     """w [c_out, cin_total, k, k] -> wt [c_in, c_out, k, k], taps flipped (weights of the
     data-gradient conv for input columns ci_first .. ci_first + c_in)."""

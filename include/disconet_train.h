@@ -69,6 +69,19 @@ int dn_conv_wgrad_sp(const dn_conv_desc* d, const float* src0, const float* src1
 int dn_conv_wgrad_sp_z(const dn_conv_desc* d, const float* src0, const float* src1, const void* dz_sp, void* workspace, float* dw,
                        int dw_cin_total, int accumulate, float dz_lift, float x_lift, void* stream);
 
+/* tools and tests only: the plan of the weight gradient of layer `d` -- sp = 0: dn_conv_wgrad, sp != 0: dn_conv_wgrad_sp / _sp_z
+ * (DN_ERR_ARG where the layer has no split-f16 kernel) -- from the very functions the launch uses.  Host only: launches nothing,
+ * needs no GPU.  Writes up to n of 12 ints and returns 12:
+ *   [0] ct (channels per side of a workgroup's block, 32 / 64)  [1] TH  [2] TW (output pixels of a tile)  [3] h_out  [4] w_out
+ *   [5] tiles_x  [6] tiles_y  [7] n_tiles (all images)  [8] n_cot  [9] n_cit  [10] n_slices  [11] taps */
+int dn_conv_wgrad_plan(const dn_conv_desc* d, int sp, int* out, int n);
+/* tools and tests only: which kernel did the last weight-gradient launch of this process run?  Written by the entry points once
+ * nothing can refuse the call any more (a refused call leaves the record as it was).  Writes up to n of 10 ints, returns 10:
+ *   [0] entry (0 dn_conv_wgrad, 1 dn_conv_wgrad_sp, 2 dn_conv_wgrad_sp_z; -1: none yet)  [1] ksize  [2] stride
+ *   [3] block (32 / 64)  [4] 1 = the ZSP instantiation  [5] vec0  [6] vec1  [7] vecz: 16-byte loads of source 0 / source 1 / dz
+ *   (split-f16 kernels: vec0 = vec1 = their one vecx flag, vecz = 1)  [8] workgroups of the launch  [9] n_slices */
+int dn_conv_wgrad_last_form(int* out, int n);
+
 /* Weights of the data-gradient conv: wt[ci][co][2-ky][2-kx] = w[co][ci][ky][kx] for the
  * c_in columns starting at `ci_first` of a [c_out][cin_total][k][k] tensor.  dx is then
  * dn_conv2d(dz; pack(wt)) with stride 1 -- for a stride-2 layer with src0 read zero-stuffed

@@ -49,6 +49,16 @@ static int errors_only(void) {
   d.math = 0;
   CHECK(dn_conv_wgrad_workspace(&d) > 0, "wgrad workspace");
   CHECK(dn_conv_wgrad(&d, NULL, NULL, NULL, NULL, NULL, 0, 0, NULL) == DN_ERR_ARG, "wgrad null");
+  /* the weight gradient's tools hooks: a 12-int plan (8 x 8 map, 32 -> 32: one 8 x 16 tile, one slice), a 10-int record */
+  {
+    int plan[12], form[10];
+    CHECK(dn_conv_wgrad_plan(&d, 0, NULL, 12) == DN_ERR_ARG, "wgrad plan: null accepted");
+    CHECK(dn_conv_wgrad_plan(&d, 0, plan, 12) == 12 && plan[0] == 32 && plan[1] == 8 && plan[2] == 16 && plan[7] == 1 &&
+          plan[10] == 1 && plan[11] == 9, "wgrad plan: %d %d %d %d %d %d", plan[0], plan[1], plan[2], plan[7], plan[10], plan[11]);
+    CHECK(dn_conv_wgrad_plan(&d, 1, plan, 12) == 12 && plan[0] == 32 && plan[1] == 8, "wgrad plan, split-f16");
+    CHECK(dn_conv_wgrad_last_form(NULL, 10) == DN_ERR_ARG, "wgrad last form: null accepted");
+    CHECK(dn_conv_wgrad_last_form(form, 10) == 10, "wgrad last form: 10 fields");
+  }
   /* the split-f16 weight gradient: 32 -> 32 channels takes the 32-channel block form; a 13-channel source has none */
   CHECK(dn_conv_wgrad_sp_supported(&d) == 32 && dn_conv_wgrad_sp_workspace(&d) > 0, "wgrad_sp supported");
   CHECK(dn_conv_wgrad_sp(&d, NULL, NULL, NULL, NULL, NULL, 0, 0, 256.f, 16.f, NULL) == DN_ERR_ARG, "wgrad_sp null");
