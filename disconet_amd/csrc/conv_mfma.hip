@@ -85,7 +85,6 @@ struct ConvArgs {
   int wpk_bytes;  // size of the packed weights (buffer bounds)
   int total_items;     // work items = channel blocks x images x tiles
   int vec_out;    // out / scale / shift allow 16-byte accesses
-  int xcd_order;  // work-item order keeps a pixel tile's channel blocks on one XCD
   // fused 1x1 stage (POST kernels only): out2 = act2(h . W2^T * scale2 + shift2)
   const float* w2;      // packed split-f16 rows [64][BN hi halves | BN lo halves]
   const float* scale2;
@@ -100,7 +99,6 @@ struct ConvArgs {
 };
 
 constexpr int kcp_of(int ksize) { return ksize == 3 ? 16 : 32; }
-constexpr int kNumCUs = 256;   // MI355X
 
 template <int KS, int STRIDE, int TH, int TW, int BN, int KC, int WAVES_M, int WAVES_N,
           int WTM, int WTN>
@@ -181,7 +179,7 @@ conv_mfma_kernel(const ConvArgs a) {
   // form spreads those loads under the MFMA stream.
   const int G = gridDim.x;
   const int spatial_items = a.n_images * a.tiles_y * a.tiles_x;
-  // XCD-aware order (a.xcd_order): workgroup b runs on XCD b % 8 (observed, not a
+  // XCD-aware order: workgroup b runs on XCD b % 8 (observed, not a
   // contract -- a wrong guess only costs speed), each XCD has its own L2.  All
   // channel blocks of a pixel tile re-read the same patch, so they take ids
   // b, b + 8, b + 16, ...: same XCD, dispatched back to back, the patch comes out of
@@ -191,15 +189,12 @@ conv_mfma_kernel(const ConvArgs a) {
   auto decode = [&](int item) {
     TileCoord tc;
     int cb, sp;
-    if (!a.xcd_order) {
-      cb = item / spatial_items;
-      sp = item % spatial_items;
-    } else if (item < sp_full * n_cb) {
+    if (item < sp_full * n_cb) {
       const int j = item >> 3;
       cb = j % n_cb;
-      // order 2: each XCD walks its own contiguous run of pixel tiles, so tiles that
+      // each XCD walks its own contiguous run of pixel tiles, so tiles that
       // share halo rows / columns meet in one L2 as well
-      sp = a.xcd_order == 2 ? (item & 7) * (sp_full >> 3) + j / n_cb : (j / n_cb) * 8 + (item & 7);
+      sp = (item & 7) * (sp_full >> 3) + j / n_cb;
     } else {
       const int r = item - sp_full * n_cb, rem = spatial_items - sp_full;
       cb = r / rem;
@@ -879,12 +874,11 @@ int launch(ConvArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   // order 2: each XCD walks its own contiguous run of pixel tiles.  Measured (batch 4): conv FETCH per step
   // 3.54 GB (channel-block-major order, 0) -> 2.79 GB (pixel tiles interleaved over the XCDs, 1) -> 2.49 GB (2);
   // step time within 1 % of each other -- the re-reads came out of the 256 MB MALL.
-  a.xcd_order = 2;
   // persistent grid: as many workgroups as are resident (no inter-workgroup sync
   // depends on the count; an over-estimate only queues the surplus).  History on MI355X, batch 4: with
   // the XCD-aware order, interleaved A/B runs put "always persistent" 1.5-2 % ahead of persisting only the
   // 256-pixel / fused tiles with 2-4 chunks (split-f16) and 3.4 % (exact fp32); "never" lands within 0.5 %.
-  const long resident = (long)occupancy * kNumCUs;
+  const long resident = (long)occupancy * dn::kCUs;
   dim3 grid((unsigned)(total > resident ? resident : total));
   // what dn_conv_last_form reports: the template parameters of this very instantiation
   g_last_form = LastForm{g_entry, KS, STRIDE, TH, TW, BN, KC, MATH, POST, (int)grid.x, a.total_items};

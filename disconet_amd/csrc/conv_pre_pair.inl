@@ -11,7 +11,7 @@
 //            hi/lo split and writes the SP pieces into LDS in the patch layout conv_pre_2's K loop reads -- zero where the
 //            patch pixel lies outside the map (that is conv_pre_2's zero padding, not relu(bias));
 //   stage 2  is conv_pre_2's weight-stationary K loop over that patch (both 16-channel chunks resident: no DMA, no stage
-//            hand-over) and conv_sp_kernel's register epilogue.
+//            hand-over) and the SP engine's register epilogue (sp_tile_device.h :: store_sp_quads).
 // Every accumulation chain has the order of the two-launch path (stage 1: per tap w_lo.x then w_hi.x, taps 0..8; stage 2:
 // per tap w_lo.x_hi, w_hi.x_lo, w_hi.x_hi, chunks 0, 1) and the same affine4 / split4, so the output is bit-identical to
 // dn_spconv2d(math 4) followed by dn_spconv2d; 19.5 % of stage 1 is halo recompute.
@@ -47,11 +47,10 @@ struct PrePairArgs {
   const float *s1, *t1, *s2, *t2;
   unsigned char* out;            // SP tensor [n][cog][4][h][w] x 16 B
   int n, h, w, c_out, cog, relu1, relu2;
-  int tiles_x, tiles_y, items;
-  float rcp_tx, rcp_ty;
+  ItemOrder order;               // the work-item decode, no channel blocks (sp_tile_device.h)
 };
 
-// byte m of an occupancy word -> the 8 halves (0x3C00 where the bit is set) of the hi-only stage: conv_sp_kernel's commit_a
+// byte m of an occupancy word -> the 8 halves (0x3C00 where the bit is set) of the hi-only stage (conv_sp_kernel :: commit_a's expansion)
 __device__ inline half8 expand_octet(unsigned m) {
   u32x4 v;
 #pragma unroll
@@ -68,7 +67,7 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const int G = gridDim.x;
   int item = blockIdx.x;
-  if (item >= a.items) return;
+  if (item >= a.order.items) return;
 
   // ---- once per workgroup: both layers' weights and affines -> LDS
   // (packed images: [chunk][tap][4 quarters][cout_pad] pieces -- the first 32 channels of every quarter row)
@@ -94,18 +93,10 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
 #else
   auto mark = [&](int) {};
 #endif
-  const int sp_full = a.items & ~7;
-  auto decode = [&](int it) {
-    TileCoord tc;
-    int spi = it < sp_full ? (it & 7) * (sp_full >> 3) + (it >> 3) : it;     // XCD-aware order, as conv_sp_kernel
-    int tx, ty;
-    spi = fdivmod(spi, a.tiles_x, a.rcp_tx, tx);
-    tc.img = fdivmod(spi, a.tiles_y, a.rcp_ty, ty);
-    tc.img = __builtin_amdgcn_readfirstlane(tc.img);
-    tc.ox0 = __builtin_amdgcn_readfirstlane(tx * TW);
-    tc.oy0 = __builtin_amdgcn_readfirstlane(ty * TH);
-    tc.n0 = 0;
-    return tc;
+  auto decode = [&](int item) {
+    const Item it = decode_item<false>(a.order, item);
+    return TileCoord{__builtin_amdgcn_readfirstlane(it.img), __builtin_amdgcn_readfirstlane(it.ty * TH),
+                     __builtin_amdgcn_readfirstlane(it.tx * TW), 0};
   };
 
   // ---- occupancy words of a tile: word idx of the 20 x 36 block = tid, tid + 512 (< 720); out of the map: 0
@@ -169,7 +160,6 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
     sh2[g] = *reinterpret_cast<const f32x4*>(aff + 96 + 8 * g + 4 * lh);
   }
   const float lo_clamp1 = a.relu1 ? 0.f : -65504.f, lo_clamp2 = a.relu2 ? 0.f : -65504.f;
-  const int plane = a.h * a.w * 16, img_bytes = a.cog * 4 * plane;
 
   while (true) {
     // ================= stage 1: conv_pre_1 on the halo patch -> LDS =================
@@ -215,20 +205,17 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
     mark(0);
     __syncthreads();                                             // the patch is complete; the occupancy block is free
     mark(1);
-    const bool has_next = item + G < a.items;
+    const bool has_next = item + G < a.order.items;
     TileCoord nxt = cur;
     if (has_next) {
       nxt = decode(item + G);
       load_words(nxt);                                           // lands under stage 2
     }
     // ================= stage 2: conv_pre_2 over the patch =================
-    f32x16 acc2[2];
-#pragma unroll
-    for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[wm][r] = 0.f;
+    f32x16 acc2[2][1];                                           // two pixel tiles x one channel tile per wave
+    acc_zero(acc2);
     {
-      half8 ah[2][2], al[2][2], bh[2], bl[2];
+      half8 ah[2][2], al[2][2], bh[2][1], bl[2][1];
       auto load = [&](int s, int g, int u) {
         const unsigned char* As = smem + g * MID_CHUNK + ((u / 3) * MW + u % 3) * 16;
         const unsigned char* Bs = smem + OFF_W2 + (g * 9 + u) * 2048 + b_off;
@@ -237,17 +224,10 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
           ah[s][wm] = *reinterpret_cast<const half8*>(As + a_off[wm]);
           al[s][wm] = *reinterpret_cast<const half8*>(As + a_off[wm] + 2 * MNPIX * 16);
         }
-        bh[s] = *reinterpret_cast<const half8*>(Bs);
-        bl[s] = *reinterpret_cast<const half8*>(Bs + 1024);
+        bh[s][0] = *reinterpret_cast<const half8*>(Bs);
+        bl[s][0] = *reinterpret_cast<const half8*>(Bs + 1024);
       };
-      auto mma = [&](int s) {
-#pragma unroll
-        for (int wm = 0; wm < 2; ++wm) acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s], ah[s][wm], acc2[wm], 0, 0, 0);
-#pragma unroll
-        for (int wm = 0; wm < 2; ++wm) acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], al[s][wm], acc2[wm], 0, 0, 0);
-#pragma unroll
-        for (int wm = 0; wm < 2; ++wm) acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], ah[s][wm], acc2[wm], 0, 0, 0);
-      };
+      auto mma = [&](int s) { mma_x3(acc2, ah[s], al[s], bh[s], bl[s]); };
       load(0, 0, 0);
 #pragma unroll
       for (int q = 0; q < 18; ++q) {                             // (chunk, tap) = (q / 9, q % 9): reads of q + 1 before the MFMAs of q
@@ -258,29 +238,17 @@ __global__ void __launch_bounds__(pp::NTHR, 1) conv_pre_pair_kernel(const PrePai
       }
     }
 #if DN_PHASE_TIMING
-    { float probe = acc2[1][0]; asm volatile("v_mov_b32 %0, %0" : "+v"(probe)); }
+    { float probe = acc2[1][0][0]; asm volatile("v_mov_b32 %0, %0" : "+v"(probe)); }
 #endif
     mark(2);
-    // ---- epilogue: conv_sp_kernel's store_sp_tile (register affine, buffer stores against the output image)
+    // ---- epilogue: register affines, buffer stores against the output image
     {
-      const auto rsrc_o = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)cur.img * img_bytes, 0, img_bytes, 0x00020000);
+      const SpOut so = sp_out_of(a.out, cur.img, a.cog, a.h, a.w);
 #pragma unroll
       for (int wm = 0; wm < 2; ++wm) {
         const int oy = cur.oy0 + 2 * wave + wm, ox = cur.ox0 + li;
-        const bool inside = oy < a.h && ox < a.w;
-        const int voff = inside ? (oy * a.w + ox) * 16 + lh * plane : (int)0x80000000;
-        u32x2 hi[4], lo[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) split4(affine4(quad_of(acc2[wm], g), sc2[g], sh2[g]), hi[g], lo[g], amax, lo_clamp2);
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const u32x4 ph = gather_octet(hi[2 * m], hi[2 * m + 1]);
-          const u32x4 pl = gather_octet(lo[2 * m], lo[2 * m + 1]);
-          if (m < a.cog) {
-            __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff + m * 4 * plane, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff + (m * 4 + 2) * plane, 0, 0);
-          }
-        }
+        const int voff = sp_out_voff(so, oy < a.h && ox < a.w, oy * a.w + ox, lh);
+        store_sp_quads([&](int g) { return affine4(quad_of(acc2[wm][0], g), sc2[g], sh2[g]); }, so, voff, 0, lo_clamp2, amax);
       }
     }
     mark(3);
@@ -319,10 +287,8 @@ extern "C" int dn_spconv2d_pre_pair(const dn_conv_desc* d1, const dn_conv_desc* 
   a.n = d1->n_images; a.h = d1->h_in; a.w = d1->w_in; a.c_out = d2->c_out; a.cog = (d2->c_out + 15) / 16;
   a.relu1 = d1->relu; a.relu2 = d2->relu;
   a.cout_pad = cout_pad_of(32);      // both layers: c_out <= 32 -> the same padded row (dn_spconv_pack_weights)
-  a.tiles_x = (a.w + pp::TW - 1) / pp::TW; a.tiles_y = (a.h + pp::TH - 1) / pp::TH;
-  a.items = a.n * a.tiles_x * a.tiles_y;
-  a.rcp_tx = 1.f / a.tiles_x; a.rcp_ty = 1.f / a.tiles_y;
-  DN_REQUIRE((size_t)a.cog * 4 * a.h * a.w * 16 < ((size_t)1 << 31) && (size_t)a.h * a.w * 4 < ((size_t)1 << 31) && a.items < (1 << 22),
+  a.order = item_order_of(a.n, (a.h + pp::TH - 1) / pp::TH, (a.w + pp::TW - 1) / pp::TW);
+  DN_REQUIRE((size_t)a.cog * 4 * a.h * a.w * 16 < ((size_t)1 << 31) && (size_t)a.h * a.w * 4 < ((size_t)1 << 31) && a.order.items < (1 << 22),
              "spconv pre pair: map too large");
   static dn::PerDeviceFlag attr_flag;
   bool& attr_set = attr_flag.here();
@@ -332,8 +298,8 @@ extern "C" int dn_spconv2d_pre_pair(const dn_conv_desc* d1, const dn_conv_desc* 
     if (e != hipSuccess) return dn::fail(DN_ERR_LAUNCH, "spconv pre pair: hipFuncSetAttribute: %s", hipGetErrorString(e));
     attr_set = true;
   }
-  const int grid = a.items < kCUs ? a.items : kCUs;
-  dn::g_sp_last_form = dn::SpLastForm{2, 3, 1, pp::TH, pp::TW, 32, 0, 0, 0, 1, 0, 2, 0, 0, 0, grid, a.items, a.items, 0, 0};
+  const int grid = a.order.items < kCUs ? a.order.items : kCUs;
+  dn::g_sp_last_form = dn::SpLastForm{2, 3, 1, pp::TH, pp::TW, 32, 0, 0, 0, 1, 0, 2, 0, 0, 0, grid, a.order.items, a.order.items, 0, 0};
   hipLaunchKernelGGL(conv_pre_pair_kernel, dim3(grid), dim3(pp::NTHR), pp::LDS_BYTES, (hipStream_t)stream, a);
   return dn::check_launch("conv_pre_pair_kernel");
 }

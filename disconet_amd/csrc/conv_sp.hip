@@ -36,6 +36,7 @@
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
+#include "sp_tile_device.h"
 #include "sp_split.h"
 #include <array>
 #include <cstdlib>
@@ -54,7 +55,7 @@ extern "C" int dn_sp_phase_cycles(unsigned long long* host8, int reset) {
 
 namespace {
 
-constexpr int kCUs = 256;
+using dn::kCUs;
 
 struct SpArgs {
   const unsigned char* src0;   // SP tensors
@@ -67,9 +68,7 @@ struct SpArgs {
   int c0g, c1g;                // 16-channel chunks taken from src0 / src1
   int up0, c_out, cog, relu;   // cog = chunks of the output tensor
   int ngroups;                 // A groups (CA chunks each) of the K loop
-  int tiles_x, tiles_y, total_items, xcd_order;
-  int n_cb;                    // channel blocks; reciprocals of the work-item decode's divisors (sp_device.h :: fdivmod)
-  float rcp_ncb, rcp_tx, rcp_ty;
+  ItemOrder order;             // the work-item decode (sp_tile_device.h)
   int cout_pad, wpk_bytes;
   // fused 1x1 stage
   const unsigned char* w2;     // [2 n-tiles][4 k-steps][2 parts][2 h][32 n] x 16 B
@@ -203,32 +202,11 @@ conv_sp_kernel(const SpArgs a) {
   const int li = lane & 31;
   const int lh = lane >> 5;
 
-  // ---- work items (channel block, image, tile_y, tile_x), XCD-aware order as in conv_mfma.hip
+  // ---- work items (channel block, image, tile_y, tile_x) in the XCD-aware order (sp_tile_device.h :: decode_item)
   const int G = gridDim.x;
-  const int spatial_items = a.n_images * a.tiles_y * a.tiles_x;
-  const int n_cb = a.n_cb;
-  const int sp_full = spatial_items & ~7;
   auto decode = [&](int item) {
-    TileCoord tc;
-    int cb, spi;
-    if (!a.xcd_order) {
-      cb = item / spatial_items;
-      spi = item % spatial_items;
-    } else if (item < sp_full * n_cb) {
-      const int j = item >> 3;
-      const int jq = fdivmod(j, n_cb, a.rcp_ncb, cb);
-      spi = (item & 7) * (sp_full >> 3) + jq;
-    } else {
-      const int r = item - sp_full * n_cb, rem = spatial_items - sp_full;   // the last < 8 spatial items: rare
-      cb = r / rem;
-      spi = sp_full + r % rem;
-    }
-    tc.n0 = cb * BN;
-    int tx, ty;
-    spi = fdivmod(spi, a.tiles_x, a.rcp_tx, tx);
-    tc.img = fdivmod(spi, a.tiles_y, a.rcp_ty, ty);
-    tc.ox0 = tx * TW;
-    tc.oy0 = ty * TH;
+    const Item it = decode_item(a.order, item);
+    TileCoord tc{it.img, it.ty * TH, it.tx * TW, it.cb * BN};
     if constexpr (AHI == 2) {   // plain buffer loads in the K loop: without this the compiler treats the tile as divergent
       tc.n0 = __builtin_amdgcn_readfirstlane(tc.n0);      // and wraps every buffer store of the epilogue in a waterfall loop
       tc.img = __builtin_amdgcn_readfirstlane(tc.img);
@@ -238,28 +216,10 @@ conv_sp_kernel(const SpArgs a) {
     return tc;
   };
 
-  // K-sliced launches (KSL): work item v < n_whole is a whole tile (all K slices, folded in registers); the others
-  // are single slices of the tiles behind them, `kslices` consecutive work items per tile (sp_device.h :: KSlices)
-  // sl0 .. sl1: the slices the item computes (all of them: a whole tile, folded in registers; one: a split tile's
-  // slice `sl0`, partial index j = v - n_whole = tile * kslices + slice)
-  struct Work {
-    TileCoord tc;
-    int sl0, sl1, j;
-  };
-  auto decode_work = [&](int v) {
-    Work w;
-    if (KSL == 0 || v < a.ks.n_whole) {
-      w.tc = decode(v);
-      w.sl0 = 0; w.sl1 = KSL ? a.ks.count : 1; w.j = -1;
-    } else {
-      w.j = v - a.ks.n_whole;
-      w.sl0 = w.j & ((1 << a.ks.log2) - 1);
-      w.sl1 = w.sl0 + 1;
-      w.tc = decode(a.ks.n_whole + (w.j >> a.ks.log2));
-    }
-    return w;
-  };
-  auto first_group = [&](const Work& w) { return KSL ? a.ks.bound(w.sl0) : 0; };
+  // K-sliced launches (KSL): whole tiles and single slices of split tiles (sp_tile_device.h :: KWork)
+  using Work = KWork<TileCoord>;
+  auto decode_work = [&](int v) { return ks_decode_work<KSL>(a.ks, v, decode); };
+  auto first_group = [&](const Work& w) { return ks_first_group<KSL>(a.ks, w); };
 
   // ---- LDS read offsets (bytes) of this lane's MFMA fragments
   int a_off[WTM], b_off[WTN], prow[WTM], pcol;
@@ -281,7 +241,6 @@ conv_sp_kernel(const SpArgs a) {
   bool nan_seen = false;   // a NaN reached an epilogue (ReLU / the clamp of the split would hide it)
 
   // ---- DMA state
-  constexpr unsigned OOB = 0xFFFFFFFFu;
   const int hs0 = a.up0 ? (a.h_in >> 1) : a.h_in, ws0 = a.up0 ? (a.w_in >> 1) : a.w_in;
   const unsigned plane0 = (unsigned)(hs0 * ws0) * 16u, plane1 = (unsigned)(a.h_in * a.w_in) * 16u;
   const size_t img0_bytes = AHI == 2 ? (size_t)(hs0 * ws0) * 4 : (size_t)a.c0g * T::AQ * plane0;
@@ -292,10 +251,6 @@ conv_sp_kernel(const SpArgs a) {
                                                         a.wpk_bytes, 0x00020000);
   unsigned voff_a[A_IT], voff_b[B_IT];
 
-  auto opaque = [](int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-  };
   // per-lane source offsets of the A pieces this lane moves: piece (it * NW + wave) * 64 + lane.  Which patch
   // pixel (row r, column cc) and quarter plane cq a piece is does not depend on the tile: decoded ONCE per launch
   // into one packed register per piece (r | cc + 1 << 8 | cq << 16 | valid << 31) -- the two constant divisions and
@@ -448,34 +403,9 @@ conv_sp_kernel(const SpArgs a) {
         }
       }
     };
-    auto mma = [&](auto u_c) {
+    auto mma = [&](auto u_c) {   // the product group of sub-step u (sp_tile_device.h :: mma_x3)
       constexpr int s = decltype(u_c)::value & 1;
-      // D[i = channel][j = pixel]; small terms first; independent accumulators interleaved
-      // The accumulator tiles of a product group are walked in Gray order -- consecutive MFMAs then differ in ONE operand
-      // register set, not two (every accumulator still receives its three products in the same order: same bits)
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int k = 0; k < WTN; ++k) {
-          const int wn = (wm & 1) ? WTN - 1 - k : k;
-          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s][wn], ah[s][wm], acc[wm][wn], 0, 0, 0);
-        }
-      if constexpr (AHI == 0) {
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int k = 0; k < WTN; ++k) {
-          const int wn = (wm & 1) ? WTN - 1 - k : k;
-          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][wn], al[s][wm], acc[wm][wn], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int k = 0; k < WTN; ++k) {
-          const int wn = (wm & 1) ? WTN - 1 - k : k;
-          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][wn], ah[s][wm], acc[wm][wn], 0, 0, 0);
-        }
+      mma_x3<AHI != 0>(acc, ah[s], al[s], bh[s], bl[s]);
     };
     load(std::integral_constant<int, 0>{});
     auto body = [&](auto u_c) {
@@ -532,39 +462,28 @@ conv_sp_kernel(const SpArgs a) {
     // the prefetch it was meant to hide had landed (round 4, phase timing: tools/phase_probe.py).
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
   };
-  // One 32-pixel x 32-channel accumulator tile -> SP pieces.  Stores are buffer stores against a descriptor of the
-  // output IMAGE (32-bit lane offset computed once per tile + the quarter-plane offset; a lane outside the map
-  // carries an out-of-range offset and the bounds check drops its store): no 64-bit address
-  // arithmetic and no exec-mask juggling per store.  ReLU is a max against a uniform floor (0 or -inf).
+  // One 32-pixel x 32-channel accumulator tile: this kernel's three affine sources, then the shared stores
+  // (sp_tile_device.h :: store_f32_quads, store_sp_quads).
   auto store_sp_tile = [&](const f32x16& c, const float* scale, const float* shift, int relu,
                            int ch0, int c_lim, unsigned char* out, int cog, int img, int oy, int ox,
                            int wn_r = -1) {
     const bool inside = oy < a.h_out && ox < a.w_out;
-    const int plane = a.h_out * a.w_out * 16;                       // bytes of one quarter plane (launch checks the image < 2 GiB)
-    const int img_bytes = cog * 4 * plane;
-    const auto rsrc_o = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)img * img_bytes, 0, img_bytes, 0x00020000);
-    const int voff = inside ? (oy * a.w_out + ox) * 16 + lh * plane : (int)0x80000000;
+    const SpOut so = sp_out_of(out, img, cog, a.h_out, a.w_out);
+    const int voff = sp_out_voff(so, inside, oy * a.w_out + ox, lh);
     // ReLU: in the fp32 copy a max against a uniform floor (0 or -inf); in the split it is the lower clamp bound
-    // (sp_device.h :: split4), so the affine for the split applies none (`relu_here` false)
+    // (sp_device.h :: split4): the affine itself applies none
     const float floor_v = relu ? 0.f : -__builtin_inff(), lo_clamp = relu ? 0.f : -65504.f;
-    auto affine = [&](int g, f32x4& v, bool relu_here) {
+    auto affine = [&](int g) {
       const int co = ch0 + 8 * g + 4 * lh;
-      const float fl = relu_here ? floor_v : -__builtin_inff();
+      f32x4 v;
       if (wn_r >= 0) {            // register-resident affine (channels past c_out: scale = shift = 0 -> 0)
         v = affine4(quad_of(c, g), sc_r[kRegAffine ? wn_r : 0][g], sh_r[kRegAffine ? wn_r : 0][g]);
-        if (relu_here) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], fl);
-        }
       } else if (POST == 1 && wn_r == -2) {   // stage-2 affine of the fused 1x1 from LDS (zero past c_out2)
         const f32x4 sc = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[POST == 1 ? 2 : 0][co & 63]), smem);
         const f32x4 sh = lds_table4(reinterpret_cast<const f32x4*>(&aff1_s[POST == 1 ? 3 : 0][co & 63]), smem);
         v = affine4(quad_of(c, g), sc, sh);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (relu_here) v[e] = fmaxf(v[e], fl);
-          v[e] = co + e < c_lim ? v[e] : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) v[e] = co + e < c_lim ? v[e] : 0.f;
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -573,57 +492,22 @@ conv_sp_kernel(const SpArgs a) {
           v[e] = c[4 * g + e] * scale[ci] + shift[ci];
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (relu_here) v[e] = fmaxf(v[e], fl);
-          v[e] = co + e < c_lim ? v[e] : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) v[e] = co + e < c_lim ? v[e] : 0.f;
       }
+      return v;
     };
     if constexpr (POST == 0) {   // optional second output: the same values as fp32 NHWC rows (the exchanged level).
       // A block of its own behind ONE uniform branch: written inside the loop below, every launch without a second
       // output paid a masked-off store sequence per register quad.
       if (a.out_b != nullptr) {
         float* orow = a.out_b + (((size_t)img * a.h_out + oy) * a.w_out + ox) * a.ldo_b;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int co = ch0 + 8 * g + 4 * lh;
-          f32x4 v;
-          affine(g, v, false);
-          // the fp32 copy leaves the engine (fusion kernels, the agent all-gather): the one place where a NaN / Inf test of
-          // the conv stack is free -- one launch per step, behind a uniform branch.  Before the ReLU, which would hide a NaN.
-          nan_seen |= !(fabsf(v[0]) <= 3.4028235e38f) | !(fabsf(v[1]) <= 3.4028235e38f) | !(fabsf(v[2]) <= 3.4028235e38f) |
-                      !(fabsf(v[3]) <= 3.4028235e38f);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], floor_v);
-          if (inside && co < c_lim) *reinterpret_cast<f32x4*>(orow + co) = v;
-        }
+        store_f32_quads(affine, orow, ch0, lh, c_lim, inside, floor_v, nan_seen);
         // dn_spconv2d_nhwc (the training step's split-f16 data gradient): the fp32 rows are the ONLY output -- nothing is
         // split, no magnitude is tracked (a gradient may exceed the f16 range: it never becomes an f16 pair here)
         if (out == nullptr) return;
       }
     }
-    u32x2 hi[4], lo[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 v;
-      affine(g, v, false);
-      split4(v, hi[g], lo[g], amax, lo_clamp);
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      // chunk ch0 / 16 + m: lane half 0 ends up with octet 0, lane half 1 with octet 1
-      const u32x4 ph = gather_octet(hi[2 * m], hi[2 * m + 1]);
-      const u32x4 pl = gather_octet(lo[2 * m], lo[2 * m + 1]);
-      const int cg = ch0 / 16 + m;
-      if (cg < cog && (!kNoStore || ph[0] == 0x12345678u)) {
-        // The plane offset rides in the VECTOR offset, the scalar offset operand stays 0.  With it in the scalar
-        // operand hipcc leaves out the wait states between a dwordx4 store and a VALU write of its data registers
-        // (its hazard recognizer exempts SGPR offsets; gfx950 needs them): the round-3 form wrote ~1e-4 of the lo
-        // pieces wrong, lanes 12-15 / 28-31 of both halves.  DESIGN.md 3.6 (C); tools/soff; tests/test_isa_hazard_cpu.py.
-        __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff + cg * 4 * plane, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff + (cg * 4 + 2) * plane, 0, 0);
-      }
-    }
+    store_sp_quads<kNoStore>(affine, so, voff, ch0 / 16, lo_clamp, amax);
   };
 
   auto epilogue = [&](const TileCoord& tc) {
@@ -818,7 +702,7 @@ conv_sp_kernel(const SpArgs a) {
 
   // ---- main loop
   int item = blockIdx.x;
-  if (item >= a.total_items) return;
+  if (item >= a.order.items) return;
   if constexpr (POST == 2) {   // both stages' affines (64 hidden channels; <= 64 outputs over the two heads)
     if (tid < 64) {
       aff1_s[0][tid] = a.scale[tid];
@@ -843,14 +727,7 @@ conv_sp_kernel(const SpArgs a) {
   }
   TileCoord cur = decode(KSL != 0 ? 0 : item);   // (K-sliced launches decode their first WORK item below)
   setup_rsrc(cur);
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-      for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[wm][wn][r] = 0.f;
-  };
+  auto zero_acc = [&]() { acc_zero(acc); };
   int sa = 0;
 
   if constexpr (BSTAT != 0) {
@@ -883,7 +760,7 @@ conv_sp_kernel(const SpArgs a) {
     while (true) {
       zero_acc();
       load_affine(cur.n0);
-      const bool has_next = item + G < a.total_items;
+      const bool has_next = item + G < a.order.items;
       TileCoord nxt = cur;
       if (has_next) nxt = decode(item + G);
       mark(4);
@@ -940,67 +817,12 @@ conv_sp_kernel(const SpArgs a) {
     return;
   }
 
-  // K slices: partial sums of a split tile <-> global memory, one f32x4 per lane and register quad (1 KB runs)
-  auto partial_of = [&](int j) {     // j = tile * kslices + slice
-    return a.ks.partial + ((size_t)j * NW + wave) * (WTM * WTN * 16 * 64) + lane * 4;
-  };
-  auto fold_acc = [&]() {       // tot += acc (fp32 adds, the order the fix-up pass uses), acc = 0
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            tot[wm][wn][r] += acc[wm][wn][r];
-            acc[wm][wn][r] = 0.f;
-          }
-    }
-  };
-  auto zero_tot = [&]() {
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) tot[wm][wn][r] = 0.f;
-    }
-  };
-  auto tot_to_acc = [&]() {
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn) acc[wm][wn] = tot[wm][wn];
-    }
-  };
   if constexpr (KSL != 0) {
     if (a.ks.fixup) {
-      // ---- fix-up pass: the split tiles' slices, added in slice order from zero -- the arithmetic of fold_acc --
-      // then the ordinary epilogue.  No operand DMA, no LDS.
-      for (int p = blockIdx.x; p < a.ks.n_split; p += G) {
-        const TileCoord tc = decode(a.ks.n_whole + p);
-        load_affine(tc.n0);
-        zero_tot();
-        for (int sl = 0; sl < a.ks.count; ++sl) {
-          const float* pb = partial_of((p << a.ks.log2) + sl);
-#pragma unroll
-          for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-            for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(pb + ((wm * WTN + wn) * 4 + q) * 256);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[wm][wn][4 * q + e] = v[e];
-              }
-          fold_acc();
-        }
-        tot_to_acc();
+      ks_fixup<NW>(a.ks, wave, lane, acc, tot, decode, load_affine, [&](const TileCoord& tc) {
         epilogue(tc);
         note_range(amax, nan_seen);
-      }
+      });
       return;
     }
   }
@@ -1028,7 +850,7 @@ conv_sp_kernel(const SpArgs a) {
   while (true) {
     zero_acc();
     load_affine(cur.n0);
-    const bool has_next = item + G < a.total_items;
+    const bool has_next = item + G < a.order.items;
     TileCoord nxt = cur;
     int ng0 = 0;                            // first K group of the next work item
     if (has_next) {
@@ -1036,7 +858,7 @@ conv_sp_kernel(const SpArgs a) {
       nxt = nw.tc;
       ng0 = first_group(nw);
     }
-    if constexpr (KSL != 0) zero_tot();
+    if constexpr (KSL != 0) acc_zero(tot);
     const int g_end = KSL ? a.ks.bound(cw.sl1) : a.ngroups;      // last group of the item + 1
 
     // K slices: one pass of the group loop per slice (KSL == 0: one pass over all groups), the loop body is the same
@@ -1133,22 +955,14 @@ conv_sp_kernel(const SpArgs a) {
       }
       sa ^= 1;
     }
-    if (KSL != 0 && cw.j < 0) fold_acc();      // a slice of a whole tile is complete: add it, restart the chain from zero
+    if constexpr (KSL != 0) {
+      if (cw.j < 0) ks_fold(tot, acc);         // a slice of a whole tile is complete: add it, restart the chain from zero
     }
-    if (KSL != 0 && cw.j >= 0) {
-      if constexpr (KSL != 0) {                  // one slice of a split tile: raw accumulators to the partial buffer
-        float* pb = partial_of(cw.j);
-#pragma unroll
-        for (int wm = 0; wm < WTM; ++wm)
-#pragma unroll
-          for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              *reinterpret_cast<f32x4*>(pb + ((wm * WTN + wn) * 4 + q) * 256) =
-                  f32x4{acc[wm][wn][4 * q], acc[wm][wn][4 * q + 1], acc[wm][wn][4 * q + 2], acc[wm][wn][4 * q + 3]};
-      }
+    }
+    if (KSL != 0 && cw.j >= 0) {               // one slice of a split tile: raw accumulators to the partial buffer
+      if constexpr (KSL != 0) ks_store_partial(ks_partial_of<NW, WTM * WTN>(a.ks, cw.j, wave, lane), acc);
     } else {
-      tot_to_acc();
+      if constexpr (KSL != 0) acc_move(acc, tot);
       epilogue(cur);
       note_range(amax, nan_seen);
     }
@@ -1543,15 +1357,11 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
   // launch bounds were compiled for
   int occupancy = 160 * 1024 / lds_bytes;
   occupancy = occupancy < 1 ? 1 : (occupancy > T::OCC_W ? T::OCC_W : occupancy);
-  a.tiles_x = (a.w_out + TW - 1) / TW;
-  a.tiles_y = (a.h_out + TH - 1) / TH;
-  const long total = (long)a.n_images * a.tiles_y * a.tiles_x * ((d.c_out + BN - 1) / BN);
+  const int tiles_x = (a.w_out + TW - 1) / TW, tiles_y = (a.h_out + TH - 1) / TH, n_cb = (d.c_out + BN - 1) / BN;
+  const long total = (long)a.n_images * tiles_y * tiles_x * n_cb;
   DN_REQUIRE(total < (1L << 31), "spconv: too many tiles (%ld)", total);
   DN_REQUIRE(total < (1L << 22), "spconv: too many work items for the reciprocal decode (%ld)", total);
-  a.total_items = (int)total;
-  a.xcd_order = 1;
-  a.n_cb = (d.c_out + BN - 1) / BN;
-  a.rcp_ncb = 1.0f / (float)a.n_cb; a.rcp_tx = 1.0f / (float)a.tiles_x; a.rcp_ty = 1.0f / (float)a.tiles_y;
+  a.order = item_order_of(a.n_images, tiles_y, tiles_x, n_cb);
   const long resident = (long)occupancy * kCUs;
   // what dn_spconv_last_form reports: the template parameters of this very instantiation
   dn::SpLastForm form = {0, KS, STRIDE, TH, TW, BN, TG, CA, POST, BSTAT, UPM, AHI, KSL, NB, 0, 0, 0, 0, 0, 0};
@@ -1568,7 +1378,7 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
     k.n_split = (int)(total - k.n_whole);
     k.fixup = 0;
     const long work = k.n_whole + (long)k.n_split * S;
-    a.total_items = (int)work;
+    a.order.items = (int)work;
     form.grid = (int)(work > resident ? resident : work); form.total_items = (int)work;
     form.n_whole = k.n_whole; form.n_split = k.n_split;
     form.fixup_grid = k.n_split ? (int)(k.n_split > 4 * kCUs ? 4 * kCUs : k.n_split) : 0;
@@ -1576,7 +1386,7 @@ int launch(SpArgs& a, const dn_conv_desc& d, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3((unsigned)(work > resident ? resident : work)), dim3(T::NT), lds_bytes, stream, a);
     if (k.n_split) {     // the split tiles' slices added in slice order + their epilogue: same kernel, no operands
       k.fixup = 1;
-      a.total_items = k.n_split;
+      a.order.items = k.n_split;
       hipLaunchKernelGGL(kern, dim3((unsigned)(k.n_split > 4 * kCUs ? 4 * kCUs : k.n_split)), dim3(T::NT), 0, stream, a);
     }
     return dn::check_launch("conv_sp_kernel (K slices)");

@@ -22,8 +22,9 @@
 //     shared by all waves.  The per-lane LDS bases absorb the class (registers, not immediates), the tap
 //     offsets stay compile-time.
 // Pipeline (double-buffered patch per chunk, double-buffered weights per step, raw s_barrier + counted
-// vmcnt waits, next tile's first operands under the current tile's last step), persistent workgroups, XCD-aware
-// item order and the register epilogue are those of conv_sp_kernel.
+// vmcnt waits, next tile's first operands under the current tile's last step) and persistent workgroups follow
+// conv_sp_kernel; the XCD-aware item order, the K-slice bookkeeping, the MFMA product group and the register
+// epilogue's stores are the shared phases of sp_tile_device.h.
 //
 // Resident weights (RES, struct SpqRes below).  A layer of <= 4 + 2 chunks with one channel block (conv8_1: 96 -> 32) reads
 // the same 164 KB of weights for every one of its 5120 tiles; the streaming form moves them L2 -> LDS again per tile, in 14
@@ -40,12 +41,13 @@
 #include "dn_internal.h"
 #include "sp_layout.h"
 #include "sp_device.h"
+#include "sp_tile_device.h"
 #include "sp_split.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int kCUs = 256;
+using dn::kCUs;
 
 // patch geometry: PH x PW pixels, columns de-interleaved (QHALF even columns, then QHALF odd ones)
 constexpr int QTH = 8, QTW = 32, QPH = QTH + 2, QPW = QTW + 2, QHALF = QPW / 2, QPITCH = QPW, QNPIX = QPH * QPITCH;
@@ -68,10 +70,8 @@ struct SpqArgs {
   int n_images, h, w;          // conv input = output size (src0 is stored at h / 2 x w / 2)
   int c0g, c1g;                // 16-channel chunks from src0 / src1
   int c_out, cog, relu;
-  int tiles_x, tiles_y, total_items;
+  ItemOrder order;             // the work-item decode (sp_tile_device.h)
   int cout_pad, wpk_bytes;
-  int n_cb;                    // channel blocks; reciprocals of the work-item decode's divisors (sp_device.h :: fdivmod)
-  float rcp_ncb, rcp_tx, rcp_ty;
   KSlices ks;                  // K slices (KSL kernels; sp_device.h :: KSlices)
 };
 
@@ -141,53 +141,18 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   const int li = lane & 31, lh = lane >> 5;
   const int py = wave & 1, px = wave >> 1;                 // this wave's parity class
 
-  // ---- work items (channel block, image, tile_y, tile_x), XCD-aware order as in conv_sp_kernel
+  // ---- work items (channel block, image, tile_y, tile_x) in the XCD-aware order (sp_tile_device.h :: decode_item)
   const int G = gridDim.x;
-  const int spatial_items = a.n_images * a.tiles_y * a.tiles_x;
-  const int n_cb = a.n_cb;
-  const int sp_full = spatial_items & ~7;
   auto decode = [&](int item) {
-    QTile tc;
-    int cb, spi;
-    if (item < sp_full * n_cb) {
-      const int j = item >> 3;
-      const int jq = fdivmod(j, n_cb, a.rcp_ncb, cb);
-      spi = (item & 7) * (sp_full >> 3) + jq;
-    } else {
-      const int r = item - sp_full * n_cb, rem = spatial_items - sp_full;   // the last < 8 spatial items: rare
-      cb = r / rem;
-      spi = sp_full + r % rem;
-    }
-    tc.n0 = cb * BN;
-    int tx, ty;
-    spi = fdivmod(spi, a.tiles_x, a.rcp_tx, tx);
-    tc.img = fdivmod(spi, a.tiles_y, a.rcp_ty, ty);
-    tc.ox0 = tx * QTW;
-    tc.oy0 = ty * QTH;
-    return tc;
+    const Item it = decode_item(a.order, item);
+    return QTile{it.img, it.ty * QTH, it.tx * QTW, it.cb * BN};
   };
 
-  // sl0 .. sl1: the slices the item computes (all of them: a whole tile, folded in registers; one: a split tile's
-  // slice `sl0`, partial index j = v - n_whole = tile * kslices + slice)
-  struct Work {
-    QTile tc;
-    int sl0, sl1, j;
-  };
+  // K-sliced launches (KSL): whole tiles and single slices of split tiles (sp_tile_device.h :: KWork)
+  using Work = KWork<QTile>;
   const int nchunks = a.c0g + a.c1g;
-  auto decode_work = [&](int v) {
-    Work w;
-    if (KSL == 0 || v < a.ks.n_whole) {
-      w.tc = decode(v);
-      w.sl0 = 0; w.sl1 = KSL ? a.ks.count : 1; w.j = -1;
-    } else {
-      w.j = v - a.ks.n_whole;
-      w.sl0 = w.j & ((1 << a.ks.log2) - 1);
-      w.sl1 = w.sl0 + 1;
-      w.tc = decode(a.ks.n_whole + (w.j >> a.ks.log2));
-    }
-    return w;
-  };
-  auto first_group = [&](const Work& w) { return KSL ? a.ks.bound(w.sl0) : 0; };
+  auto decode_work = [&](int v) { return ks_decode_work<KSL>(a.ks, v, decode); };
+  auto first_group = [&](const Work& w) { return ks_first_group<KSL>(a.ks, w); };
 
   // ---- this lane's pixels and LDS read bases (bytes).  MFMA tile wm of the class: tile rows
   // r = py + 4 wm + 2 rsel, columns c = px + 2 k; one 16-lane ds_read_b128 group = one row, k = 0..15.
@@ -221,7 +186,6 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   bool nan_seen = false;
 
   // ---- DMA state
-  constexpr unsigned OOB = 0xFFFFFFFFu;
   const int hs0 = a.h >> 1, ws0 = a.w >> 1;
   const unsigned plane0 = (unsigned)(hs0 * ws0) * 16u, plane1 = (unsigned)(a.h * a.w) * 16u;
   const size_t img0_bytes = (size_t)a.c0g * 4 * plane0, img1_bytes = (size_t)a.c1g * 4 * plane1;
@@ -230,13 +194,10 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   const auto rsrcw = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.wpk), 0, a.wpk_bytes, 0x00020000);
   unsigned voff_a[QA_IT], voff_b[T::B_IT0];
 
-  auto opaque = [](int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-  };
   // per-lane source offsets of the patch pieces this lane moves: LDS piece (it * NW + wave) * 64 + lane.  The piece's
   // patch pixel (r, cc) and quarter plane are tile-independent: decoded once per launch into one packed register
-  // (r | cc << 8 | cq << 16 | valid << 31), as in conv_sp_kernel; a tile adds its origin and tests the image bounds.
+  // (r | cc << 8 | cq << 16 | valid << 31) -- the two constant divisions and the column map per piece are a large part of a
+  // short-K tile's instruction stream; a tile adds its origin and tests the image bounds.
   unsigned piece_map[QA_IT];
 #pragma unroll
   for (int it = 0; it < QA_IT; ++it) {
@@ -315,31 +276,7 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   struct Frags {
     half8 ah[2], al[2], bh[WTN], bl[WTN];
   };
-  auto mma = [&](const Frags& f) {
-    // (Gray order of the accumulator tiles inside a product group, as conv_sp_kernel's mma: consecutive MFMAs differ in one
-    // operand register set; every accumulator receives its three products in the same order -- same bits)
-#pragma unroll
-    for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-      for (int k = 0; k < WTN; ++k) {
-        const int wn = (wm & 1) ? WTN - 1 - k : k;
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bl[wn], f.ah[wm], acc[wm][wn], 0, 0, 0);
-      }
-#pragma unroll
-    for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-      for (int k = 0; k < WTN; ++k) {
-        const int wn = (wm & 1) ? WTN - 1 - k : k;
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bh[wn], f.al[wm], acc[wm][wn], 0, 0, 0);
-      }
-#pragma unroll
-    for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-      for (int k = 0; k < WTN; ++k) {
-        const int wn = (wm & 1) ? WTN - 1 - k : k;
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bh[wn], f.ah[wm], acc[wm][wn], 0, 0, 0);
-      }
-  };
+  auto mma = [&](const Frags& f) { mma_x3(acc, f.ah, f.al, f.bh, f.bl); };   // sp_tile_device.h
   // step ST of a source-1 chunk: taps (dy = ST, dx = 0..2), weights shared by the four waves
   auto compute1 = [&](auto st_c, const unsigned char* As, const unsigned char* Bs) {
     constexpr int DY = decltype(st_c)::value;
@@ -417,7 +354,7 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // ---- epilogue: affine (+ ReLU) -> split -> permlane gather -> 16-byte SP pieces, as conv_sp_kernel's POST 0.
+  // ---- epilogue: affine (+ ReLU) -> split -> permlane gather -> 16-byte SP pieces, in registers.
   // The affine of the current channel block lives in a WAVE-PRIVATE 512-byte LDS block (64 registers at BN = 64
   // would spill): written when the workgroup moves to another block, read by the same wave's epilogue -- in-order
   // LDS operations of one wave, no barrier.  Channels past c_out get scale = shift = 0.
@@ -435,9 +372,7 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       aff_s[AFF_SH + lane] = co < a.c_out ? a.shift[ci] : 0.f;
     }
   };
-  // Stores: buffer stores against a descriptor of the output image (32-bit lane offset + quarter-plane offset in the
-  // vector operand, out-of-map lanes dropped by the bounds check), ReLU as a max against a uniform floor -- as in
-  // conv_sp_kernel's store_sp_tile (which also says why the plane offset is not in the scalar operand).
+  // The stores are sp_tile_device.h :: store_f32_quads / store_sp_quads; this kernel's part is the affine out of aff_s.
   // (RES: the affine is re-read for every accumulator tile through an offset the compiler cannot see through -- kept across
   // the tiles and the two output blocks it is 32 registers beside the 128 of the resident weights: scratch)
   auto aff_of_tile = [&]() {
@@ -446,11 +381,17 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
     return aff_s + ao;
   };
   auto epilogue = [&](const QTile& tc) {
-    const int plane = a.h * a.w * 16;
-    const int img_bytes = a.cog * 4 * plane;
-    const auto rsrc_o = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)tc.img * img_bytes, 0, img_bytes, 0x00020000);
-    const float lo_clamp = a.relu ? 0.f : -65504.f;
-    if (a.out_f32 != nullptr) {   // fp32 NHWC rows (as conv_sp_kernel's second output): a block of its own behind ONE uniform branch
+    const SpOut so = sp_out_of(a.out, tc.img, a.cog, a.h, a.w);
+    const float lo_clamp = a.relu ? 0.f : -65504.f;      // the ReLU rides in the split's clamp (sp_device.h)
+    // affine'd quad g of accumulator tile (wm, wn), scale / shift read at `aff`
+    auto quads_of = [&](int wm, int wn, const float* aff) {
+      return [&, wm, wn, aff](int g) {
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + wn * 32 + 8 * g + 4 * lh);
+        const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + AFF_SH + wn * 32 + 8 * g + 4 * lh);
+        return affine4(quad_of(acc[wm][wn], g), sc, sh);
+      };
+    };
+    if (a.out_f32 != nullptr) {   // optional fp32 NHWC rows: a block of its own behind ONE uniform branch
       const float floor_v = a.relu ? 0.f : -__builtin_inff();
 #pragma unroll
       for (int wm = 0; wm < 2; ++wm) {
@@ -460,113 +401,30 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
         const float* aff = aff_of_tile();
 #pragma unroll
         for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int co = tc.n0 + 32 * wn + 8 * g + 4 * lh;
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + wn * 32 + 8 * g + 4 * lh);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + AFF_SH + wn * 32 + 8 * g + 4 * lh);
-            f32x4 v = affine4(quad_of(acc[wm][wn], g), sc, sh);
-            nan_seen |= !(fabsf(v[0]) <= 3.4028235e38f) | !(fabsf(v[1]) <= 3.4028235e38f) | !(fabsf(v[2]) <= 3.4028235e38f) |
-                        !(fabsf(v[3]) <= 3.4028235e38f);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], floor_v);
-            if (inside && co < a.c_out) *reinterpret_cast<f32x4*>(orow + co) = v;
-          }
+          store_f32_quads(quads_of(wm, wn, aff), orow, tc.n0 + 32 * wn, lh, a.c_out, inside, floor_v, nan_seen);
       }
       if (a.out == nullptr) return;      // nothing is split: no magnitude to track
     }
 #pragma unroll
     for (int wm = 0; wm < 2; ++wm) {
       const int oy = tc.oy0 + prow[wm], ox = tc.ox0 + pcol;
-      const bool inside = oy < a.h && ox < a.w;
-      const int voff = inside ? (oy * a.w + ox) * 16 + lh * plane : (int)0x80000000;
+      const int voff = sp_out_voff(so, oy < a.h && ox < a.w, oy * a.w + ox, lh);
       const float* aff = aff_of_tile();
 #pragma unroll
-      for (int wn = 0; wn < WTN; ++wn) {
-        u32x2 hi[4], lo[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + wn * 32 + 8 * g + 4 * lh);
-          const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + AFF_SH + wn * 32 + 8 * g + 4 * lh);
-          const f32x4 v = affine4(quad_of(acc[wm][wn], g), sc, sh);
-          split4(v, hi[g], lo[g], amax, lo_clamp);      // the ReLU rides in the split's clamp (sp_device.h)
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          // chunk (n0 + 32 wn) / 16 + m: lane half 0 ends up with octet 0, lane half 1 with octet 1
-          const u32x4 ph = gather_octet(hi[2 * m], hi[2 * m + 1]);
-          const u32x4 pl = gather_octet(lo[2 * m], lo[2 * m + 1]);
-          const int cg = (tc.n0 + 32 * wn) / 16 + m;
-          if (cg < a.cog) {
-            __builtin_amdgcn_raw_buffer_store_b128(ph, rsrc_o, voff + cg * 4 * plane, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(pl, rsrc_o, voff + (cg * 4 + 2) * plane, 0, 0);
-          }
-        }
-      }
+      for (int wn = 0; wn < WTN; ++wn)
+        store_sp_quads(quads_of(wm, wn, aff), so, voff, (tc.n0 + 32 * wn) / 16, lo_clamp, amax);
     }
   };
 
   // ---- main loop
   int item = blockIdx.x;
-  if (item >= a.total_items) return;
-  auto partial_of = [&](int j) {     // j = tile * kslices + slice
-    return a.ks.partial + ((size_t)j * QNW + wave) * (2 * WTN * 16 * 64) + lane * 4;
-  };
-  auto fold_acc = [&]() {       // tot += acc (fp32 adds, the order the fix-up pass uses), acc = 0
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            tot[wm][wn][r] += acc[wm][wn][r];
-            acc[wm][wn][r] = 0.f;
-          }
-    }
-  };
-  auto zero_tot = [&]() {
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) tot[wm][wn][r] = 0.f;
-    }
-  };
-  auto tot_to_acc = [&]() {
-    if constexpr (KSL != 0) {
-#pragma unroll
-      for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-        for (int wn = 0; wn < WTN; ++wn) acc[wm][wn] = tot[wm][wn];
-    }
-  };
+  if (item >= a.order.items) return;
   if constexpr (KSL != 0) {
-    if (a.ks.fixup) {   // fix-up pass: the split tiles' slices added in slice order from zero, then the epilogue
-      for (int p = blockIdx.x; p < a.ks.n_split; p += G) {
-        const QTile tc = decode(a.ks.n_whole + p);
-        load_affine(tc.n0);
-        zero_tot();
-        for (int sl = 0; sl < a.ks.count; ++sl) {
-          const float* pb = partial_of((p << a.ks.log2) + sl);
-#pragma unroll
-          for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-            for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(pb + ((wm * WTN + wn) * 4 + q) * 256);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[wm][wn][4 * q + e] = v[e];
-              }
-          fold_acc();
-        }
-        tot_to_acc();
+    if (a.ks.fixup) {
+      ks_fixup<QNW>(a.ks, wave, lane, acc, tot, decode, load_affine, [&](const QTile& tc) {
         epilogue(tc);
         note_range(amax, nan_seen);
-      }
+      });
       return;
     }
   }
@@ -671,11 +529,8 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     };
     while (true) {
-#pragma unroll
-      for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[wm][0][r] = 0.f;
-      const bool has_next = item + G < a.total_items;
+      acc_zero(acc);
+      const bool has_next = item + G < a.order.items;
       QTile nxt = cur;
       if (has_next) nxt = decode(item + G);
       // one hand-over per chunk: its patch has landed (every wave waited for its own DMAs), the other stage is free again;
@@ -729,14 +584,9 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
   bool a_pending = true;   // patch DMAs issued AFTER the weight DMAs the next step waits for
 
   while (true) {
-#pragma unroll
-    for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-      for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[wm][wn][r] = 0.f;
+    acc_zero(acc);
     load_affine(cur.n0);
-    const bool has_next = item + G < a.total_items;
+    const bool has_next = item + G < a.order.items;
     QTile nxt = cur;
     int ng0 = 0;                            // first chunk of the next work item
     if (has_next) {
@@ -744,7 +594,7 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       nxt = nw.tc;
       ng0 = first_group(nw);
     }
-    if constexpr (KSL != 0) zero_tot();
+    if constexpr (KSL != 0) acc_zero(tot);
     const int g_end = KSL ? a.ks.bound(cw.sl1) : nchunks;      // last chunk of the item + 1
 
     // K slices: one pass of the chunk loop per slice (KSL == 0: one pass over all chunks), the loop body is the same
@@ -813,22 +663,14 @@ __global__ void __launch_bounds__(QNT, 2) conv_spq_kernel(const SpqArgs a) {
       }
       sa ^= 1;
     }
-    if (KSL != 0 && cw.j < 0) fold_acc();      // a slice of a whole tile is complete: add it, restart the chain from zero
+    if constexpr (KSL != 0) {
+      if (cw.j < 0) ks_fold(tot, acc);         // a slice of a whole tile is complete: add it, restart the chain from zero
     }
-    if (KSL != 0 && cw.j >= 0) {
-      if constexpr (KSL != 0) {                  // one slice of a split tile: raw accumulators to the partial buffer
-        float* pb = partial_of(cw.j);
-#pragma unroll
-        for (int wm = 0; wm < 2; ++wm)
-#pragma unroll
-          for (int wn = 0; wn < WTN; ++wn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              *reinterpret_cast<f32x4*>(pb + ((wm * WTN + wn) * 4 + q) * 256) =
-                  f32x4{acc[wm][wn][4 * q], acc[wm][wn][4 * q + 1], acc[wm][wn][4 * q + 2], acc[wm][wn][4 * q + 3]};
-      }
+    }
+    if (KSL != 0 && cw.j >= 0) {               // one slice of a split tile: raw accumulators to the partial buffer
+      if constexpr (KSL != 0) ks_store_partial(ks_partial_of<QNW, 2 * WTN>(a.ks, cw.j, wave, lane), acc);
     } else {
-      tot_to_acc();
+      if constexpr (KSL != 0) acc_move(acc, tot);
       epilogue(cur);
       note_range(amax, nan_seen);
     }
@@ -893,14 +735,11 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
                       hipGetErrorString(e));
     attr_set = true;
   }
-  a.tiles_x = (a.w + QTW - 1) / QTW;
-  a.tiles_y = (a.h + QTH - 1) / QTH;
-  const long total = (long)a.n_images * a.tiles_y * a.tiles_x * ((a.c_out + BN - 1) / BN);
+  const int tiles_x = (a.w + QTW - 1) / QTW, tiles_y = (a.h + QTH - 1) / QTH, n_cb = (a.c_out + BN - 1) / BN;
+  const long total = (long)a.n_images * tiles_y * tiles_x * n_cb;
   DN_REQUIRE(total < (1L << 22), "spconv (quad-merged): too many tiles (%ld)", total);
   DN_REQUIRE((long)a.h * a.w * 16 * 4 * a.cog < (1L << 31), "spconv (quad-merged): one output image exceeds 2 GiB");
-  a.total_items = (int)total;
-  a.n_cb = (a.c_out + BN - 1) / BN;
-  a.rcp_ncb = 1.0f / (float)a.n_cb; a.rcp_tx = 1.0f / (float)a.tiles_x; a.rcp_ty = 1.0f / (float)a.tiles_y;
+  a.order = item_order_of(a.n_images, tiles_y, tiles_x, n_cb);
   const long resident = (DEEP ? 1L : 2L) * kCUs;
   // what dn_spconv_last_form reports (family 1): the pixel tile, BN, DEEP and KSL of this instantiation
   // (the record is what it was before the resident form existed; dn_spconv_last_resident tells the two BN = 32 forms apart)
@@ -927,7 +766,7 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
     k.n_split = (int)(total - k.n_whole);
     k.fixup = 0;
     const long work = k.n_whole + (long)k.n_split * S;
-    a.total_items = (int)work;
+    a.order.items = (int)work;
     form.grid = (int)(work > resident ? resident : work); form.total_items = (int)work;
     form.n_whole = k.n_whole; form.n_split = k.n_split;
     form.fixup_grid = k.n_split ? (int)(k.n_split > 2 * kCUs ? 2 * kCUs : k.n_split) : 0;
@@ -935,7 +774,7 @@ int launch_spq(SpqArgs& a, hipStream_t stream, size_t ws_bytes = 0) {
     hipLaunchKernelGGL(kern, dim3((unsigned)(work > resident ? resident : work)), dim3(QNT), T::LDS_BYTES, stream, a);
     if (k.n_split) {
       k.fixup = 1;
-      a.total_items = k.n_split;
+      a.order.items = k.n_split;
       // the fix-up pass reads the epilogue affine through the wave-private LDS block: same dynamic LDS
       hipLaunchKernelGGL(kern, dim3((unsigned)(k.n_split > 2 * kCUs ? 2 * kCUs : k.n_split)), dim3(QNT), T::LDS_BYTES, stream, a);
     }
@@ -978,7 +817,7 @@ int spq_conv(const dn_conv_desc* d, const void* src0, const void* src1, const vo
   a.c0g = (d->c0 + 15) / 16; a.c1g = (d->c1 + 15) / 16;
   a.c_out = d->c_out; a.cog = (d->c_out + 15) / 16; a.relu = d->relu;
   a.cout_pad = cout_pad; a.wpk_bytes = (int)packed_bytes;
-  a.tiles_x = a.tiles_y = a.total_items = 0;
+  a.order = ItemOrder{};
   a.ks = KSlices{workspace, kslices, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool resident_ok = a.c0g <= SpqRes::C0G && a.c1g <= SpqRes::C1G && d->c_out <= 32 && kslices <= 1;
   if (kslices > 1) {

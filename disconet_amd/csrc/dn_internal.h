@@ -10,6 +10,8 @@ namespace dn {
 
 char* err_buf();   // thread-local, 512 bytes
 
+constexpr int kCUs = 256;   // MI355X: what the conv launchers size their persistent grids by
+
 inline int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

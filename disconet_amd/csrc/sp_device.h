@@ -1,6 +1,7 @@
 // Device helpers shared by the split-planar conv kernels (conv_sp.hip, conv_spq.hip): vector types, counted
 // vmcnt waits, the LDS-DMA instruction, the f16 hi/lo split and the permlane gather that turns MFMA
-// accumulator quads into 16-byte SP pieces.  gfx950 only.
+// accumulator quads into 16-byte SP pieces.  The phases built from them that the conv kernels share (item order,
+// K slices, MFMA product group, tile stores) are in sp_tile_device.h.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,15 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+// A buffer offset past every descriptor's range: the load returns zeros (the LDS-DMA writes them), nothing is read.
+constexpr unsigned OOB = 0xFFFFFFFFu;
+// A copy of v the compiler cannot see through: per-lane values derived from it are recomputed where they are used
+// instead of being hoisted out of the tile loop and held live across it.
+__device__ inline int opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 
 __device__ inline void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 template <int N>
