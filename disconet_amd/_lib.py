@@ -210,6 +210,11 @@ SIGNATURES = {
     "dn_exchange_message_bytes": (c_long, [c_int, c_int, c_int, c_int]),
     "dn_exchange_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_exchange_decode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dn_exchange_cells_message_bytes": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    "dn_exchange_cells_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "dn_exchange_encode_cells": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                         c_void_p, c_void_p]),
+    "dn_exchange_decode_cells": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     # ---- include/disconet_seg.h ----
     "dn_sp_maxpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dn_sp_upsample2_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -25,7 +25,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["common.hip", "conv_mfma.hip", "conv_sp.hip", "conv_spq.hip", "voxel.hip", "warp.hip", "fuse_reduce.hip", "fuse_tail.hip", "fuse_mlp.hip", "agent_fuse.hip", "decode.hip", "detect.hip", "ap_match.hip", "assign.hip", "track.hip", "mot_eval.hip", "idf_eval.hip", "hota_eval.hip",
-           "conv_wgrad.hip", "train_ops.hip", "seg_ops.hip", "seg_eval.hip", "render.hip", "lidar.hip", "lidar_seq.hip", "exchange.hip"]
+           "conv_wgrad.hip", "train_ops.hip", "seg_ops.hip", "seg_eval.hip", "render.hip", "lidar.hip", "lidar_seq.hip", "exchange.hip",
+           "exchange_cells.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]
 LIB_PATH = os.path.join(os.path.dirname(HERE), "libdisconet_hip.so")
 

@@ -28,16 +28,22 @@ def load_checkpoint(model, path):
 
 class Detector:
     def __init__(self, com, config, num_agent, batch_size, *, layer=3, kd_flag=0, compress_level=0, only_v2i=False,
-                 pre_nms_top_k=300, iou_thr=0.01, score_thr=None, resume="", seed=0, device="cuda", exchange="f32"):
+                 pre_nms_top_k=300, iou_thr=0.01, score_thr=None, resume="", seed=0, device="cuda", exchange="f32",
+                 exchange_cells=0):
         """com: one of ALL_DET_COM_MODES (build_model raises ValueError otherwise).  Without `resume` the weights are random:
         seeded before construction, so that a run can be reproduced, and the BatchNorm statistics are randomised
         (synthetic.randomize_bn_stats).  `epoch` is the loaded checkpoint's epoch, or None.
         exchange: the wire format of the exchanged map (exchange.FORMATS, model.exchange); anything but "f32" needs
         com = "disco" -- the baselines' one-launch kernels read own and neighbour maps from one tensor, lowerbound and
-        late exchange no features."""
+        late exchange no features.
+        exchange_cells: how many cells of the exchanged map an agent sends (model.exchange_cells; 0: every cell), with any
+        format; the same rule: anything but 0 needs com = "disco"."""
         if exchange_format.check_format(exchange) != "f32" and com != "disco":
             raise ValueError("exchange = %r needs --com disco (got --com %s): only the DiscoGraph fusion reads the "
                              "neighbours' maps through a tensor of their own" % (exchange, com))
+        if exchange_cells and com != "disco":
+            raise ValueError("exchange_cells = %r needs --com disco (got --com %s): only the DiscoGraph fusion reads the "
+                             "neighbours' maps through a tensor of their own" % (exchange_cells, com))
         self.com, self.config, self.num_agent, self.batch_size = com, config, num_agent, batch_size
         self.only_v2i = bool(only_v2i)
         self.pre_nms_top_k, self.iou_thr, self.score_thr = pre_nms_top_k, iou_thr, score_thr
@@ -50,7 +56,9 @@ class Detector:
         else:
             randomize_bn_stats(self.model)
         self.model.exchange = exchange
+        self.model.exchange_cells = exchange_cells
         self.model.eval().to(device)
+        self.model._check_exchange()                # a budget outside [0, P] is refused here, not at the first frame
         self.anchors = postprocess.make_anchors(config, device=device)
 
     def forward(self, bevs, trans, num_agent_tensor):

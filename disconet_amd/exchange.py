@@ -8,6 +8,14 @@ numpy -- integer operations on the fp32 bit patterns, no float8 type anywhere --
     f16    2 bytes per value (numpy.astype(float16)), no scales
     mxfp8  1 byte per value (E4M3), one E8M0 scale byte per 32 channels of a pixel
     mxfp4  two values per byte (E2M1, the lower channel in the low nibble), the same scales
+
+Selective exchange (the header's "Selective exchange", csrc/exchange_cells.hip): an agent sends the K strongest cells of
+its map, in any of the four formats.  host_select / host_encode_cells / host_decode_cells state it in numpy.
+
+    score of a cell = max over its channels of (bits & 0x7fffffff); the selected cells are the first min(K, non-zero cells)
+    by (score descending, index ascending), listed in ascending index
+    message of one image = uint32 count + 12 zero bytes | K uint16 indices (0xFFFF beyond count), zeros up to a multiple
+    of 16 | the dense message of the gathered [1, K, c] image (rows beyond count are +0.0)
 """
 import numpy as np
 
@@ -133,10 +141,106 @@ def host_decode(wire, fmt, h, w, c):
     return v.astype(np.float32).reshape(n, h, w, c)
 
 
-def roundtrip(feat, fmt):
-    """what a receiver decodes of `feat` [n, h, w, c] fp32 NHWC on the GPU: ops.exchange_encode + ops.exchange_decode, two
-    launches.  "f32" sends the map as it is: `feat` itself comes back and nothing is launched."""
-    if check_format(fmt) == "f32":
+CELLS_MAX = 16384                                           # DN_EXCHANGE_CELLS_MAX: one image's scores fit in 64 KiB of LDS
+_BITS = {"f32": 32, "f16": 16, "mxfp8": 8, "mxfp4": 4}
+
+
+def _check_cells(h, w, cells):
+    P = h * w
+    if min(h, w) <= 0 or P > CELLS_MAX:
+        raise ValueError("exchange: a %d x %d map has %d cells, the selective exchange takes 1 .. %d" % (h, w, P, CELLS_MAX))
+    if not 1 <= cells <= P:
+        raise ValueError("exchange: cells = %d must be in [1, %d], the cells of a %d x %d map" % (cells, P, h, w))
+    return P
+
+
+def cells_message_bytes(fmt, h, w, c, cells):
+    """bytes one agent sends per frame with capacity `cells` (dn_exchange_cells_message_bytes): the fixed-capacity message"""
+    _check_cells(h, w, cells)
+    return 16 + (2 * cells + 15) // 16 * 16 + _layout(fmt, 1, cells, c)[2]
+
+
+def sent_bytes(fmt, c, count):
+    """what a variable-length link would carry for `count` cells (a number, a mean included): the header, two bytes of
+    index and the element bytes per cell, and for the MX formats one scale byte per 32 channels"""
+    check_format(fmt)
+    per_cell = 2 + c * _BITS[fmt] // 8 + (c // BLOCK if fmt in _ELEM else 0)
+    return 16 + count * per_cell
+
+
+def host_scores(feat):
+    """feat [n, h, w, c] float32 -> score [n, h * w] uint32: the largest magnitude of a cell as its bit pattern"""
+    feat = np.ascontiguousarray(np.asarray(feat), dtype=np.float32)
+    n, h, w, c = feat.shape
+    return (feat.reshape(n, h * w, c).view(np.uint32) & np.uint32(0x7fffffff)).max(axis=2)
+
+
+def host_select(feat, cells):
+    """feat [n, h, w, c] float32 -> (index [n, cells] uint16, count [n] int32): per image the first min(cells, non-zero
+    cells) cells by (score descending, index ascending), listed in ascending index; 0xFFFF beyond count"""
+    score = host_scores(feat).astype(np.int64)
+    n, P = score.shape
+    _check_cells(feat.shape[1], feat.shape[2], cells)
+    index = np.full((n, cells), 0xFFFF, np.uint16)
+    count = np.zeros(n, np.int32)
+    for i in range(n):
+        order = np.lexsort((np.arange(P), -score[i]))      # the last key is the primary one
+        count[i] = min(cells, int((score[i] > 0).sum()))
+        index[i, :count[i]] = np.sort(order[:count[i]])
+    return index, count
+
+
+def host_encode_cells(feat, fmt, cells):
+    """feat [n, h, w, c] float32 -> wire [n, cells_message_bytes] uint8"""
+    feat = np.ascontiguousarray(np.asarray(feat), dtype=np.float32)
+    n, h, w, c = feat.shape
+    total = cells_message_bytes(fmt, h, w, c, cells)
+    index, count = host_select(feat, cells)
+    body_at = 16 + (2 * cells + 15) // 16 * 16
+    wire = np.zeros((n, total), np.uint8)
+    wire[:, :4] = count.astype("<u4").view(np.uint8).reshape(n, 4)
+    wire[:, 16:16 + 2 * cells] = index.astype("<u2").view(np.uint8).reshape(n, 2 * cells)
+    rows = np.zeros((n, 1, cells, c), np.float32)
+    cell = feat.reshape(n, h * w, c)
+    for i in range(n):
+        rows[i, 0, :count[i]] = cell[i, index[i, :count[i]]]
+    wire[:, body_at:] = host_encode(rows, fmt)
+    return wire
+
+
+def host_decode_cells(wire, fmt, h, w, c, cells):
+    """wire [n, cells_message_bytes] uint8 -> feat [n, h, w, c] float32: cell index[r] gets the dense decode of row r for
+    r < min(count, cells), an index >= h * w is skipped, every other cell is +0.0"""
+    wire = np.ascontiguousarray(np.asarray(wire), dtype=np.uint8)
+    total = cells_message_bytes(fmt, h, w, c, cells)
+    if wire.ndim != 2 or wire.shape[1] != total:
+        raise ValueError("exchange: wire must be [n, %d] bytes for %d cells of a %d x %d x %d %s map (got %s)"
+                         % (total, cells, h, w, c, fmt, tuple(wire.shape)))
+    n, P = wire.shape[0], h * w
+    body_at = 16 + (2 * cells + 15) // 16 * 16
+    count = np.minimum(wire[:, :4].copy().view("<u4").reshape(n).astype(np.int64), cells)
+    index = wire[:, 16:16 + 2 * cells].copy().view("<u2").reshape(n, cells).astype(np.int64)
+    rows = host_decode(wire[:, body_at:], fmt, 1, cells, c).reshape(n, cells, c)
+    feat = np.zeros((n, P, c), np.float32)
+    for i in range(n):
+        r = np.arange(count[i])
+        r = r[index[i, :count[i]] < P]
+        feat[i, index[i, r]] = rows[i, r]
+    return feat.reshape(n, h, w, c)
+
+
+def roundtrip(feat, fmt, cells=0, sent=None):
+    """what a receiver decodes of `feat` [n, h, w, c] fp32 NHWC on the GPU.
+    cells = 0: the whole map -- ops.exchange_encode + ops.exchange_decode, two launches; "f32" sends the map as it is:
+    `feat` itself comes back and nothing is launched.
+    cells = K > 0: the K strongest cells of every image, in any of the four formats -- ops.exchange_encode_cells +
+    ops.exchange_decode_cells, four launches; `sent` (int64 [>= n] on the device, or None) takes each image's count."""
+    check_format(fmt)
+    if cells:
+        n, h, w, c = feat.shape
+        wire = ops.exchange_encode_cells(feat, fmt, cells, sent=sent)
+        return ops.exchange_decode_cells(wire, fmt, h, w, c, cells)
+    if fmt == "f32":
         return feat
     n, h, w, c = feat.shape
     return ops.exchange_decode(ops.exchange_encode(feat, fmt), fmt, h, w, c)

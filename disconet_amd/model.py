@@ -573,6 +573,15 @@ class DiscoNet(_BackboneNet):
         # path with nothing new called; "f16" | "mxfp8" | "mxfp4" put what the neighbours receive through
         # exchange.roundtrip (csrc/exchange.hip).  --com disco only; training refuses it (no quantisation-aware training).
         self.exchange = "f32"
+        # how many cells of the exchanged map an agent sends (exchange.host_select: the strongest by max |v|, the rest arrive
+        # as zeros -- what the pose warp's zero padding already gives a cell outside a neighbour's view).  0 sends every
+        # cell: today's path.  K > 0 puts what the neighbours receive through exchange.roundtrip(cells=K), with any wire
+        # format, "f32" included (csrc/exchange_cells.hip).  The same rules as a format: --com disco, eval() only.
+        self.exchange_cells = 0
+        # with exchange_cells > 0, created by the first forward: int64 [images + 1] on the device -- the cells every image has
+        # sent so far, then the forwards counted (one device-side add each: a captured step counts its replays)
+        self.exchange_sent = None
+        self._exchanged_hw = (int(config.map_dims[0]) >> layer, int(config.map_dims[1]) >> layer)
 
     @property
     def overlap_streams(self):
@@ -674,15 +683,48 @@ class DiscoNet(_BackboneNet):
                           want_weights, ego_first, ego_count, sp_out, received)
 
     def _fuse_exchanged(self, feat, trans, num_agent, batch_size, P):
-        """the eval forward's fusion: with a wire format, the neighbours' maps as the receivers decode them"""
+        """the eval forward's fusion: with a wire format or a cell budget, the neighbours' maps as the receivers decode them"""
         sp_out = self.conv_math == "sp"
-        if self.exchange == "f32":
+        if self.exchange == "f32" and not self.exchange_cells:
             return self.fuse(feat, trans, num_agent, batch_size, P, sp_out=sp_out)
         feat = ops.as_nhwc(feat)
-        return self.fuse(feat, trans, num_agent, batch_size, P, sp_out=sp_out,
-                         received=exchange.roundtrip(feat, self.exchange))
+        if not self.exchange_cells:
+            received = exchange.roundtrip(feat, self.exchange)
+        else:
+            n, h, w, _ = feat.shape
+            if self.exchange_cells > h * w:
+                raise ValueError("%s.exchange_cells = %d: the exchanged %d x %d map has P = %d cells, the value must be in "
+                                 "[0, %d]" % (type(self).__name__, self.exchange_cells, h, w, h * w, h * w))
+            sent = self.exchange_sent
+            if sent is None or sent.numel() != n + 1 or sent.device != feat.device:
+                sent = self.exchange_sent = torch.zeros(n + 1, dtype=torch.int64, device=feat.device)
+            received = exchange.roundtrip(feat, self.exchange, cells=self.exchange_cells, sent=sent)
+            sent[n:] += 1
+        return self.fuse(feat, trans, num_agent, batch_size, P, sp_out=sp_out, received=received)
+
+    def exchange_sent_summary(self):
+        """one read of exchange_sent -> {"frames", "cells_per_image" (the mean cells an image sent per forward),
+        "mean_cells" (their mean over the images)}, or None before the first forward with exchange_cells > 0"""
+        if self.exchange_sent is None:
+            return None
+        host = self.exchange_sent.cpu().tolist()
+        frames = max(int(host[-1]), 1)
+        per_image = [v / frames for v in host[:-1]]
+        return {"frames": int(host[-1]), "cells_per_image": per_image, "mean_cells": sum(per_image) / len(per_image)}
 
     def _check_exchange(self):
+        cells = self.exchange_cells
+        if cells:
+            h, w = self._exchanged_hw
+            if isinstance(cells, bool) or not isinstance(cells, int) or not 0 <= cells <= h * w:
+                raise ValueError("%s.exchange_cells = %r: the exchanged %d x %d map has P = %d cells, the value must be an "
+                                 "integer in [0, %d] (0 sends every cell)" % (type(self).__name__, cells, h, w, h * w, h * w))
+            if type(self).fuse is not DiscoNet.fuse:
+                raise ValueError("%s.exchange_cells = %d: only the DiscoGraph fusion (--com disco) takes a cell budget; this "
+                                 "mode's kernels read own and neighbour maps from one tensor" % (type(self).__name__, cells))
+            if self.training:
+                raise NotImplementedError("DiscoNet.exchange_cells = %d in train() mode: training with the selection mask is "
+                                          "not built; train with 0 and set the budget for evaluation" % cells)
         if exchange.check_format(self.exchange) == "f32":
             return
         if type(self).fuse is not DiscoNet.fuse:

@@ -1064,6 +1064,60 @@ def exchange_decode(wire, fmt, h, w, c, out=None):
     return feat
 
 
+def exchange_cells_message_bytes(fmt, h, w, c, cells):
+    """bytes of one [h, w, c] image's selective message of capacity `cells` in format `fmt`
+    (dn_exchange_cells_message_bytes): header, index list, the dense message of the [1, cells, c] image"""
+    nbytes = _lib.load().dn_exchange_cells_message_bytes(_exchange_format(fmt), h, w, c, cells)
+    check(0 if nbytes >= 0 else int(nbytes), "dn_exchange_cells_message_bytes")
+    return int(nbytes)
+
+
+def exchange_encode_cells(feat, fmt, cells, out=None, sent=None):
+    """feat [n, h, w, c] float32 NHWC -> wire [n, exchange_cells_message_bytes] uint8: per image the `cells` strongest
+    cells (include/disconet_hip.h, "Selective exchange"), three launches.  fmt: any of EXCHANGE_FORMATS, "f32" included.
+    sent: int64 [>= n] on the device, or None: each image's count is added to its word."""
+    _need_gpu(feat, out, sent)
+    _f32c(feat, "feat")
+    n, h, w, c = feat.shape
+    f = _exchange_format(fmt)
+    cells = int(cells)
+    nbytes = exchange_cells_message_bytes(f, h, w, c, cells)
+    wire = out if out is not None else torch.empty((n, nbytes), dtype=torch.uint8, device=feat.device)
+    if wire.dtype != torch.uint8 or not wire.is_contiguous() or wire.numel() < n * nbytes:
+        raise _lib.DnError("exchange_encode_cells: out must be contiguous uint8 with at least %d x %d bytes (got %s, %d "
+                           "elements)" % (n, nbytes, wire.dtype, wire.numel()))
+    if sent is not None and (sent.dtype != torch.int64 or not sent.is_contiguous() or sent.numel() < n):
+        raise _lib.DnError("exchange_encode_cells: sent must be contiguous int64 with at least %d elements (got %s, %d)"
+                           % (n, sent.dtype, sent.numel()))
+    lib = _lib.load()
+    need = lib.dn_exchange_cells_workspace_bytes(n, h, w)
+    check(0 if need >= 0 else int(need), "dn_exchange_cells_workspace_bytes")
+    work = torch.empty(max(int(need), 16), dtype=torch.uint8, device=feat.device)
+    check(lib.dn_exchange_encode_cells(_ptr(feat), n, h, w, c, f, cells, _ptr(work), work.numel(), _ptr(wire), _ptr(sent),
+                                       _stream()), "dn_exchange_encode_cells")
+    return wire
+
+
+def exchange_decode_cells(wire, fmt, h, w, c, cells, out=None):
+    """wire [n, exchange_cells_message_bytes] uint8 -> feat [n, h, w, c] float32 NHWC, every value written: a sent cell as
+    the dense decode gives it, every other cell +0.0; one launch"""
+    _need_gpu(wire, out)
+    f = _exchange_format(fmt)
+    cells = int(cells)
+    nbytes = exchange_cells_message_bytes(f, h, w, c, cells)
+    if wire.dtype != torch.uint8 or not wire.is_contiguous() or wire.dim() != 2 or wire.shape[1] != nbytes:
+        raise _lib.DnError("exchange_decode_cells: wire must be contiguous uint8 [n, %d] for %d cells of a %d x %d x %d map "
+                           "(got %s %s)" % (nbytes, cells, h, w, c, wire.dtype, tuple(wire.shape)))
+    n = wire.shape[0]
+    feat = out if out is not None else torch.empty((n, h, w, c), dtype=torch.float32, device=wire.device)
+    _f32c(feat, "out")
+    if feat.numel() != n * h * w * c:
+        raise _lib.DnError("exchange_decode_cells: out holds %d values, the wire %d" % (feat.numel(), n * h * w * c))
+    check(_lib.load().dn_exchange_decode_cells(_ptr(wire), n, h, w, c, f, cells, _ptr(feat), _stream()),
+          "dn_exchange_decode_cells")
+    return feat
+
+
 def live_agent_counts(num_agent_tensor, device):
     """The kernels' [B] int32 live-agent counts from the reference's num_agent_tensor [B, A] (column 0 is the
     count).  A 1-D int32 tensor already on the device is taken as is -- no cast / gather kernel inside the step

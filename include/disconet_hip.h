@@ -1260,6 +1260,60 @@ long dn_exchange_message_bytes(int format, int h, int w, int c);
 int dn_exchange_encode(const float* feat, int n_images, int h, int w, int c, int format, uint8_t* wire, void* stream);
 int dn_exchange_decode(const uint8_t* wire, int n_images, int h, int w, int c, int format, float* feat, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Selective exchange (disconet_amd/csrc/exchange_cells.hip, dn_version 156): an agent sends only the K strongest cells
+ * of its map, in any of the four formats above.  disconet_amd/exchange.py states the same contract in numpy (host_select,
+ * host_encode_cells, host_decode_cells); the kernels equal it in every byte, with no tolerance anywhere.
+ *
+ * INPUT.  feat [n_images][h][w][c] fp32 NHWC, c % 32 == 0, P = h * w cells with 1 <= P <= 16384 (one image's scores fit
+ * in 64 KiB of LDS), capacity cells = K with 1 <= K <= P.
+ *
+ * SCORE of cell p: max over its c channels of (bits(v) & 0x7fffffff), as a uint32.  fp32 magnitudes order as their bit
+ * patterns, so no float compare and no summation order is involved; Inf and NaN sort at the top, so a poisoned cell is
+ * always sent.
+ *
+ * SELECTION.  Z = number of cells with score > 0.  Order the cells by score descending, then by cell index ascending: the
+ * selected cells are the first count = min(K, Z) of that order.  A cell whose values are all +-0 is never sent.  The
+ * selected cells are LISTED in ascending cell index: the message is canonical and a receiver can binary-search it.  The
+ * selection is the same for all four formats.
+ *
+ * MESSAGE of one image, one contiguous range of dn_exchange_cells_message_bytes() bytes, every byte written by the
+ * encode call:
+ *   16 bytes            uint32 count, then three zero words
+ *   pad16(2 K) bytes    K uint16 little-endian cell indices p = y * w + x; entries at and beyond count are 0xFFFF; then
+ *                       zero bytes up to a multiple of 16
+ *   body                exactly the dense message of `format` for the image [1][K][c]: row r is cell index[r] for
+ *                       r < count and +0.0 in every channel for r >= count; dn_exchange_message_bytes(format, 1, K, c)
+ *                       bytes.  For DN_EXCHANGE_F32 the body is the raw 4 K c bytes.
+ * At 32 x 32 x 256, K = 128: 131 344 (f32), 65 808 (f16), 34 064 (mxfp8), 17 680 (mxfp4) bytes.  The capacity is fixed
+ * so that the step stays graph-capturable; what a variable-length link would carry for `count` cells is
+ *   sent_bytes = 16 + 2 count + count c bits / 8  (+ count c / 32 scale bytes for the MX formats).
+ *
+ * DECODE.  Every byte of feat is written: cell index[r], for r < min(count, K), gets the dense decode of row r; every
+ * other cell is +0.0 in every channel.  An index >= P is skipped.  A wire the encoder cannot have produced (duplicates,
+ * not ascending) does not fault; which row wins is then unspecified.  MX blocks are 32 channels of one pixel, so a sent
+ * cell decodes to exactly what the dense round trip gives that cell.
+ *
+ * COUNTS.  sent_cells [n_images] int64, nullable: encode adds each image's count to its word -- one lane per image owns
+ * it, a plain read-modify-write: no floating point, no global atomics.
+ *
+ *   workspace  dn_exchange_cells_workspace_bytes(n_images, h, w) bytes, 16-byte aligned: the scores
+ *   wire       [n_images][dn_exchange_cells_message_bytes(format, h, w, c, cells)] bytes, the messages back to back
+ * Encode is three launches (score, select, pack), decode one; both are graph-capturable, read nothing back to the host
+ * and give the same bytes on every run.  dn_exchange_cells_message_bytes returns DN_ERR_ARG, and the two calls return it
+ * before anything is launched, for: c not a positive multiple of 32, P outside [1, 16384], cells outside [1, P], an
+ * unknown format; dn_exchange_cells_workspace_bytes for n_images < 1 or P outside [1, 16384]; the two calls also for a
+ * null feat / wire / workspace, n_images < 1, a workspace that is too small, and a feat, wire or workspace that is not
+ * 16-byte aligned (sent_cells: 8-byte).
+ * ------------------------------------------------------------------------ */
+#define DN_EXCHANGE_CELLS_MAX 16384
+long dn_exchange_cells_message_bytes(int format, int h, int w, int c, int cells);
+long dn_exchange_cells_workspace_bytes(int n_images, int h, int w);
+int dn_exchange_encode_cells(const float* feat, int n_images, int h, int w, int c, int format, int cells, void* workspace,
+                             size_t workspace_bytes, uint8_t* wire, int64_t* sent_cells, void* stream);
+int dn_exchange_decode_cells(const uint8_t* wire, int n_images, int h, int w, int c, int format, int cells, float* feat,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

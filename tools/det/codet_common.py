@@ -20,16 +20,42 @@ def add_exchange_flag(ap):
     ap.add_argument("--exchange", choices=tuple(exchange.FORMATS), default="f32",
                     help="the wire format of the exchanged feature map (--com disco): f16, mxfp8 or mxfp4 put what the "
                          "neighbours receive through exchange.roundtrip; f32 sends it as it is")
+    ap.add_argument("--exchange_cells", type=int, default=0,
+                    help="how many cells of the exchanged feature map an agent sends (--com disco): the N strongest by "
+                         "max |v|, the others arrive as zeros; with any --exchange format; 0 sends every cell")
+
+
+def exchanges(args):
+    """does the command line put the exchanged map through exchange.roundtrip at all (a format or a cell budget)"""
+    return getattr(args, "exchange", "f32") != "f32" or getattr(args, "exchange_cells", 0) != 0
 
 
 def exchange_line(args, config):
-    """--exchange other than f32: the line eval_codet.py and eval_sort.py print, the message bytes per agent per frame"""
+    """--exchange other than f32, or --exchange_cells: the line eval_codet.py and eval_sort.py print, the message bytes per
+    agent per frame (with a cell budget, of the fixed-capacity message)"""
     from disconet_amd.model import LAYER_CHANNEL
     side = config.map_dims[0] >> args.layer              # the exchanged level's side: level k is the map halved k times
     c = LAYER_CHANNEL[args.layer]
+    cells = getattr(args, "exchange_cells", 0)
+    if cells:
+        return "exchange %s, %d cells: capacity %d bytes per agent per frame (%d of the %d cells of a %d x %d x %d map; f32 %d)" % (
+            args.exchange, cells, exchange.cells_message_bytes(args.exchange, side, side, c, cells), cells, side * side,
+            side, side, c, exchange.message_bytes("f32", side, side, c))
     return "exchange %s: %d bytes per agent per frame (a %d x %d x %d map; f32 %d)" % (
         args.exchange, exchange.message_bytes(args.exchange, side, side, c), side, side, c,
         exchange.message_bytes("f32", side, side, c))
+
+
+def exchange_sent_line(args, detector):
+    """--exchange_cells: the line the eval tools print after the run, from one read of the model's exchange_sent -- the
+    mean cells an agent sent per frame and what a variable-length link would have carried for them"""
+    from disconet_amd.model import LAYER_CHANNEL
+    seen = detector.model.exchange_sent_summary()
+    if seen is None:
+        return "exchange sent: nothing (no frame ran)"
+    c = LAYER_CHANNEL[args.layer]
+    return "exchange sent: %.1f cells per agent per frame on average over %d frames (capacity %d), %.0f bytes sent per agent per frame" % (
+        seen["mean_cells"], seen["frames"], args.exchange_cells, exchange.sent_bytes(args.exchange, c, seen["mean_cells"]))
 
 
 def require_com(args, modes):
@@ -84,12 +110,16 @@ def check_source_flags(args):
     if getattr(args, "exchange", "f32") != "f32" and (args.source == "boxes" or args.detections == "truth"):
         raise SystemExit("--exchange %s needs the network's detections (--source net | lidar, --detections net): nothing "
                          "is exchanged otherwise" % args.exchange)
+    if getattr(args, "exchange_cells", 0) and (args.source == "boxes" or args.detections == "truth"):
+        raise SystemExit("--exchange_cells %d needs the network's detections (--source net | lidar, --detections net): nothing "
+                         "is exchanged otherwise" % args.exchange_cells)
 
 
 def detector_from_args(args, config):
-    """the Detector of the command line (the tail's flags and --exchange where the tool declares them), and the `loaded`
+    """the Detector of the command line (the tail's flags and --exchange / --exchange_cells where the tool declares them), and the `loaded`
     line"""
-    tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr", "exchange") if hasattr(args, k)}
+    tail = {k: getattr(args, k) for k in ("pre_nms_top_k", "iou_thr", "score_thr", "exchange", "exchange_cells")
+            if hasattr(args, k)}
     det = Detector(args.com, config, agents_of(args), args.batch, layer=args.layer, kd_flag=args.kd_flag,
                    compress_level=args.compress_level, only_v2i=bool(args.only_v2i), resume=args.resume, **tail)
     if args.resume:

@@ -5,7 +5,7 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 
     python tools/det/eval_codet.py --com disco|sum|mean|max|lowerbound|late|agent [--resume ckpt.pth] [--num_agent 5] [--batch 1] [--frames 4] \
         [--pre_nms_top_k 300] [--iou_thr 0.01] [--score_thr T] [--gt synthetic|self|scene] \
-        [--strata none|range|visibility] [--strata_edges 10,20] [--exchange f32|f16|mxfp8|mxfp4]
+        [--strata none|range|visibility] [--strata_edges 10,20] [--exchange f32|f16|mxfp8|mxfp4] [--exchange_cells N]
 
 --gt synthetic: frame f is scored against synthetic.make_gt_boxes(images, seed=f, max_boxes=64) -- seeded boxes that
     have nothing to do with the synthetic occupancy (there is no V2X-Sim data here): the figure checks the plumbing, not
@@ -18,6 +18,10 @@ mAP@0.5 and mAP@0.7 per agent and overall, as the reference's test_codet.py prin
 
 --exchange f16|mxfp8|mxfp4 (--com disco): the neighbours' feature maps go through the wire format (disconet_amd.exchange:
     encoded and decoded on the GPU inside the forward); one more line gives the message bytes per agent per frame.
+
+--exchange_cells N (--com disco): an agent sends only the N strongest cells of its map, in the --exchange format (f32
+    included); the others arrive as zeros.  Two more lines: the capacity message's bytes, and after the run the mean cells
+    sent and the bytes a variable-length link would have carried, from one read of the model's exchange_sent.
 
 --com lowerbound: no collaboration.  --com late: the lowerbound detector (train `--com lowerbound`, pass its checkpoint)
     with postprocess.late_fuse between detect() and the metric: the agents' boxes merged in each ego's frame
@@ -39,7 +43,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, postprocess  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch, make_gt_boxes, make_scene_batch  # noqa: E402
-from codet_common import add_exchange_flag, add_tail_flags, agents_of, exchange_line, detector_from_args, lidar_scene, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_tail_flags, agents_of, exchange_line, exchange_sent_line, exchanges, detector_from_args, lidar_scene, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 
 GT_MAX_BOXES = 64
@@ -132,8 +136,10 @@ def main(argv=None):
             "ground truth = the boxes of the scenes%s" % ("" if args.resume else ", random weights") if args.gt == "scene" else
             "synthetic ground truth%s: plumbing, not accuracy" % ("" if args.resume else " and random weights"))
     print("%d frames x %d images (%s)" % (args.frames, n_images, what))
-    if args.exchange != "f32":
+    if exchanges(args):
         print(exchange_line(args, config))
+    if args.exchange_cells:
+        print(exchange_sent_line(args, detector))
     for a, row in enumerate(res["per_agent"]):
         print("agent %d: mAP@0.5 %.4f  mAP@0.7 %.4f  (%d detections, %d ground-truth boxes, true positives %d / %d)" % (
             a, row["mAP@0.5"], row["mAP@0.7"], row["n_det"], row["n_gt"], row["n_tp"][0], row["n_tp"][1]))

@@ -12,7 +12,7 @@ frame on the device (--max_frames slots), and Hota.compute() matches all logged 
 
     python tools/track/eval_sort.py --com disco|sum|mean|max|lowerbound|late|agent [--source boxes|net|lidar] [--resume ckpt.pth] [--num_agent 5] [--batch 1] \
         [--seed 0] [--detections net|truth] [--frames 8] [--max_age 1] [--min_hits 3] [--iou_threshold 0.3] [--eval_iou 0.5] \
-        [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES] [--exchange f32|f16|mxfp8|mxfp4]
+        [--max_gt_ids 256] [--max_track_ids 1024] [--max_frames FRAMES] [--exchange f32|f16|mxfp8|mxfp4] [--exchange_cells N]
 
 --source boxes (default) skips the network: synthetic.make_track_sequence(truth=True) -- moving boxes with detection
 noise, misses and false positives, evaluated against their noise-free boxes.  The mode that shows meaningful figures.
@@ -44,7 +44,7 @@ sys.path.insert(0, HERE)
 
 from disconet_amd import ALL_DET_COM_MODES, Config, tracking  # noqa: E402
 from disconet_amd.synthetic import make_box_scene_batch  # noqa: E402
-from codet_common import add_exchange_flag, add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, exchange_line, require_com  # noqa: E402
+from codet_common import add_exchange_flag, add_sort_flags, add_source_flags, add_tail_flags, agents_of, check_source_flags, exchange_line, exchange_sent_line, exchanges, require_com  # noqa: E402
 from test_codet import build_parser  # noqa: E402  (the evaluation tool's command line)
 from track_step import build_step, lidar_net_scene  # noqa: E402
 
@@ -101,6 +101,8 @@ def main(argv=None):
     mot.reset()                        # the warm-up runs of the capture advanced the tracker (build_step resets it) and were counted
     idf.reset()
     hota.reset()                       # ... and logged
+    if step.detector is not None and step.detector.model.exchange_sent is not None:
+        step.detector.model.exchange_sent.zero_()      # ... and sent cells
 
     for frame in range(args.frames):
         load(frame)
@@ -110,8 +112,10 @@ def main(argv=None):
     figures = mot.compute()            # the one copy; raises on a sticky status bit of the evaluation
     print("%d frames, %d images (%d agents x batch %d), tracks need IoU >= %g" % (args.frames, n, num_agent, args.batch,
                                                                                   args.eval_iou))
-    if args.exchange != "f32":
+    if exchanges(args):
         print(exchange_line(args, config))
+    if args.exchange_cells and step.detector is not None:
+        print(exchange_sent_line(args, step.detector))
     for a, row in enumerate(figures["per_agent"]):
         print(tracking.mot_line("agent %d" % a, row))
     print(tracking.mot_line("overall", figures["overall"]))

@@ -39,8 +39,10 @@ def build_step(args, config, sort, net_scene, behind=None, truth=False):
         uploaded), `refresh(frame)` is called for its effect (it seeks the sequence).  --detections truth feeds that gt's
         boxes to the tracker with score 1 and builds no Detector.
     behind(tracks, gt) runs behind sort.update() inside the captured step (None: the step returns the tracks).  The
-    tracker's reset() follows the capture; whatever `behind` counts is the tool's to reset."""
+    tracker's reset() follows the capture; whatever `behind` counts is the tool's to reset.  step.detector is the Detector
+    the step runs, or None."""
     seq = None
+    detector = None
     if args.source == "boxes":
         seq = make_track_sequence(args.frames, agents_of(args) * args.batch, seed=args.seed, truth=truth)
         static = {part: {key: torch.from_numpy(seq[0][part][key]).cuda() for key in PARTS[part]}
@@ -83,5 +85,6 @@ def build_step(args, config, sort, net_scene, behind=None, truth=False):
         return tracks if behind is None else behind(tracks, frame_gt)
 
     step = graph.GraphedStep(run)
+    step.detector = detector           # the step's Detector, or None (--source boxes, --detections truth)
     sort.reset()                       # the warm-up runs of the capture advanced the tracker
     return step, load, seq
