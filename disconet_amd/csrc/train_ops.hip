@@ -39,90 +39,72 @@ __device__ inline int lanes_for(int c) {   // power-of-two channel lanes per row
 // its last bits between runs, no gradient or parameter depends on it
 __device__ inline void atomic_add_f64(double* p, double v) { atomicAdd(p, v); }
 
+// V channels of one pixel, held by one thread: a float (any c, stride, alignment) or a float4 (c % 4 == 0, 16-byte aligned rows)
+template <int V> struct vec_of { typedef float type; };
+template <> struct vec_of<4> { typedef f32x4 type; };
+template <int V> using vec = typename vec_of<V>::type;
+template <int V> __device__ inline vec<V> ldv(const float* p) { return *reinterpret_cast<const vec<V>*>(p); }
+template <int V> __device__ inline void stv(float* p, const vec<V> v) { *reinterpret_cast<vec<V>*>(p) = v; }
+__device__ inline f32x4 ldv4(const float* p) { return ldv<4>(p); }
+__device__ inline float lane(float v, int) { return v; }
+__device__ inline float lane(const f32x4 v, int e) { return v[e]; }
+__device__ inline void set_lane(float& v, int, float x) { v = x; }
+__device__ inline void set_lane(f32x4& v, int e, float x) { v[e] = x; }
+
 // ---------------------------------------------------------------------------------
 // per-(group, channel) sums of up to two quantities over the rows of a group -- DETERMINISTIC: the rows a thread
 // adds, the order in which a workgroup adds its threads' partials (LDS, by row-lane index) and the order in which
-// the workgroups' partials are added (fold_partials_kernel, by block index) are all fixed by the launch shape,
+// the workgroups' partials are added (fold, by block index) are all fixed by the launch shape,
 // so two runs of a training step produce the same bits (round 2 used f64 atomics in LDS and in global memory).
 // ---------------------------------------------------------------------------------
-// F(row_in_group, c, &q0, &q1) yields the two addends; grid = (blocks per group, groups).  The workgroup's partial
-// goes to part_g[blockIdx.x * NQ * c + q * c + channel].
-constexpr int kRedSlots = 2048;     // ty_n * c <= 2048 for every launch shape (c <= kMaxC)
-template <int NQ, class F>
-__device__ inline void group_channel_sums(int c, long rows_per_group, double* part_g, F f) {
-  __shared__ double red[2][kRedSlots];
-  const int tx_n = lanes_for(c), ty_n = blockDim.x / tx_n;
-  const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
-  const long chunk = (rows_per_group + gridDim.x - 1) / gridDim.x;
-  const long r0 = blockIdx.x * chunk;
-  const long r1 = r0 + chunk < rows_per_group ? r0 + chunk : rows_per_group;
-  for (int cc = tx; cc < c; cc += tx_n) {
-    double s0 = 0.0, s1 = 0.0;
-    for (long r = r0 + ty; r < r1; r += ty_n) {
-      float q0 = 0.f, q1 = 0.f;
-      f(r, cc, q0, q1);
-      s0 += q0;
-      if (NQ > 1) s1 += q1;
-    }
-    red[0][ty * c + cc] = s0;
-    if (NQ > 1) red[1][ty * c + cc] = s1;
-  }
-  __syncthreads();
-  double* out = part_g + (size_t)blockIdx.x * NQ * c;
-  for (int i = threadIdx.x; i < NQ * c; i += blockDim.x) {
-    const int q = i / c, cc = i % c;
-    double t = 0.0;
-    for (int y = 0; y < ty_n; ++y) t += red[q][y * c + cc];
-    out[i] = t;
-  }
-}
-
-// float4 form: lanes over groups of 4 channels (c % 4 == 0, 16-byte aligned rows).
+// F(row_in_group, first channel, &q0, &q1) yields the two addends of V channels; grid = (blocks per group, groups).  The
+// workgroup's partial goes to part_g[blockIdx.x * NQ * c + q * c + channel].  Lanes run over groups of V channels.
 // U: rows a thread fetches before it adds them.  The adds stay in row order (the same sums, bit for bit, as U = 1), but U rows'
 // loads are in flight at once: with one row per iteration the kernels moved 3.8-4.5 TB/s, bound by bytes in flight per CU
 // (16 waves x 64 lanes x 2 loads of 16 B against ~2 us of HBM latency), not by the HBM (round 5, profiles/r05_train_pmc.txt).
-template <int NQ, int U = 4, class F>
-__device__ inline void group_channel_sums_v4(int c, long rows_per_group, double* part_g, F f) {
+constexpr int kRedSlots = 2048;     // ty_n * c <= 2048 for every launch shape (c <= kMaxC)
+template <int NQ, int V, int U, class F>
+__device__ inline void group_channel_sums(int c, long rows_per_group, double* part_g, F f) {
   __shared__ double red[2][kRedSlots];
-  const int c4n = c >> 2;
-  const int tx_n = lanes_for(c4n), ty_n = blockDim.x / tx_n;
+  const int cvn = V == 4 ? c >> 2 : c;
+  const int tx_n = lanes_for(cvn), ty_n = blockDim.x / tx_n;
   const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
   const long chunk = (rows_per_group + gridDim.x - 1) / gridDim.x;
   const long r0 = blockIdx.x * chunk;
   const long r1 = r0 + chunk < rows_per_group ? r0 + chunk : rows_per_group;
-  for (int c4 = tx; c4 < c4n; c4 += tx_n) {
-    double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int cv = tx; cv < cvn; cv += tx_n) {
+    double s0[V], s1[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) s0[e] = s1[e] = 0.0;
+    const auto add = [&](const vec<V> q0, const vec<V> q1) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        s0[e] += lane(q0, e);
+        if (NQ > 1) s1[e] += lane(q1, e);
+      }
+    };
     long r = r0 + ty;
     if constexpr (U > 1) {
       for (; r + (long)(U - 1) * ty_n < r1; r += (long)U * ty_n) {
-        f32x4 q0[U], q1[U];
+        vec<V> q0[U], q1[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          q1[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          f(r + (long)u * ty_n, c4, q0[u], q1[u]);
+          q1[u] = vec<V>{};
+          f(r + (long)u * ty_n, V * cv, q0[u], q1[u]);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            s0[e] += q0[u][e];
-            if (NQ > 1) s1[e] += q1[u][e];
-          }
+        for (int u = 0; u < U; ++u) add(q0[u], q1[u]);
       }
     }
     for (; r < r1; r += ty_n) {
-      f32x4 q0, q1 = {0.f, 0.f, 0.f, 0.f};
-      f(r, c4, q0, q1);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        s0[e] += q0[e];
-        if (NQ > 1) s1[e] += q1[e];
-      }
+      vec<V> q0, q1 = vec<V>{};
+      f(r, V * cv, q0, q1);
+      add(q0, q1);
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[0][ty * c + 4 * c4 + e] = s0[e];
-      if (NQ > 1) red[1][ty * c + 4 * c4 + e] = s1[e];
+    for (int e = 0; e < V; ++e) {
+      red[0][ty * c + V * cv + e] = s0[e];
+      if (NQ > 1) red[1][ty * c + V * cv + e] = s1[e];
     }
   }
   __syncthreads();
@@ -135,60 +117,258 @@ __device__ inline void group_channel_sums_v4(int c, long rows_per_group, double*
   }
 }
 
-// sums[g][i] = sum over the group's blocks of part[g][blk][i]   (i < per = NQ * c), in a FIXED order: one wavefront
-// per output; lane l adds blocks l, l + 64, l + 128, ... in that order, then the 64 lane sums go through a xor
-// butterfly (a fixed tree).  (A single thread walking up to 2048 partials was a 1 ms serial chain per reduction.)
+// t[q] = sum over the blocks b of p[b * stride + q * q_stride]   (NQ quantities of one channel: the same blocks), in a FIXED
+// order: one wavefront per output; lane l adds blocks l, l + 64, l + 128, ... in that order, then the 64 lane sums go through a
+// xor butterfly (a fixed tree).  (A single thread walking up to 2048 partials was a 1 ms serial chain per reduction.)
+// FOLD_BATCH: partials a lane fetches before it adds them (in the same order: the same bits), all NQ fetches of a batch in
+// flight together.  With one load per iteration a lane's up to 16 partials were 16 L2 round trips in a row: 7-11 us per launch,
+// 72 launches per step (profiles/r06_fold_batch_ab.txt).
+constexpr int FOLD_BATCH = 8;
+template <int NQ>
+__device__ inline void fold(const double* __restrict__ p, size_t q_stride, int n_blocks, size_t stride, int lane, double (&t)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) t[q] = 0.0;
+  int b = lane;
+  for (; b + 64 * (FOLD_BATCH - 1) < n_blocks; b += 64 * FOLD_BATCH) {
+    double v[FOLD_BATCH][NQ];
+#pragma unroll
+    for (int u = 0; u < FOLD_BATCH; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) v[u][q] = p[(size_t)(b + 64 * u) * stride + q * q_stride];
+#pragma unroll
+    for (int u = 0; u < FOLD_BATCH; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) t[q] += v[u][q];
+  }
+  for (; b < n_blocks; b += 64) {
+    double v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = p[(size_t)b * stride + q * q_stride];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) t[q] += v[q];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) t[q] += __shfl_xor(t[q], o, 64);
+}
+
+// ---- what a fold's sums become: each rule once, called by the standalone kernel (two-phase and multi-group paths) and by the
+// fused fold kernel (one launch instead of a fold and a 3-5 us finish launch behind it)
+// batch statistics of one (group, channel) from its sums of z and z^2 over `rows` rows
+__device__ inline void bn_stats_finish(double s0, double s1, long rows, float& mean, float& var) {
+  const double m = s0 / rows;
+  const double v = __builtin_fma(-m, m, s1 / rows);
+  mean = (float)m;
+  var = (float)(v > 0.0 ? v : 0.0);
+}
+// one group's step of the running statistics.  Every product is rounded (no contraction): which of the two products of a sum
+// hipcc fused differed between the fused kernel (neither) and the first of bn_update_running_kernel's eight unrolled steps.
+__device__ inline float bn_unbias(long rows) { return rows > 1 ? (float)rows / (float)(rows - 1) : 1.f; }
+__device__ inline void bn_running_step(float& rm, float& rv, float mean, float var, float unbias, float momentum) {
+#pragma clang fp contract(off)
+  rm = (1.f - momentum) * rm + momentum * mean;
+  rv = (1.f - momentum) * rv + momentum * (var * unbias);
+}
+// a finished per-channel sum into its fp32 gradient (dgamma, dbeta, bias gradients)
+__device__ inline void store_channel_sum(float* __restrict__ out, int cc, double s, int accumulate) {
+  out[cc] = (accumulate ? out[cc] : 0.f) + (float)s;
+}
+
+// sums[g][i] = sum over the group's blocks of part[g][blk][i]   (i < per = NQ * c)
 __global__ void __launch_bounds__(256) fold_partials_kernel(const double* __restrict__ part, int n_blocks, int per,
                                                             int n_groups, double* __restrict__ sums) {
   const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (idx >= n_groups * per) return;
   const int g = idx / per, i = idx % per;
-  const double* p = part + (size_t)g * n_blocks * per + i;
-  double t = 0.0;
-  for (int b = lane; b < n_blocks; b += 64) t += p[(size_t)b * per];
+  double t[1];
+  fold<1>(part + (size_t)g * n_blocks * per + i, 0, n_blocks, per, lane, t);
+  if (lane == 0) sums[idx] = t[0];
+}
+
+__global__ void bn_stats_finalize_kernel(const double* __restrict__ sums, int n, int c, long rows,
+                                         float* __restrict__ mean, float* __restrict__ var) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (group, channel)
+  if (i >= n) return;
+  const int g = i / c, cc = i % c;
+  bn_stats_finish(sums[(size_t)g * 2 * c + cc], sums[(size_t)g * 2 * c + c + cc], rows, mean[i], var[i]);
+}
+
+__global__ void bn_update_running_kernel(const float* __restrict__ mean, const float* __restrict__ var,
+                                         int n_groups, long rows, int c, const int* __restrict__ order,
+                                         float momentum, float* __restrict__ rmean,
+                                         float* __restrict__ rvar) {
+  const int cc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cc >= c) return;
+  float rm = rmean[cc], rv = rvar[cc];
+  const float unbias = bn_unbias(rows);
+  // the recurrence runs in group order; the groups' statistics are fetched eight at a time (one round trip instead of eight)
+  for (int k0 = 0; k0 < n_groups; k0 += 8) {
+    float m[8], v[8];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  if (lane == 0) sums[idx] = t;
+    for (int u = 0; u < 8; ++u) {
+      const int k = k0 + u < n_groups ? k0 + u : n_groups - 1;
+      const int g = order ? order[k] : k;
+      m[u] = mean[g * c + cc];
+      v[u] = var[g * c + cc];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (k0 + u < n_groups) bn_running_step(rm, rv, m[u], v[u], unbias, momentum);
+  }
+  rmean[cc] = rm;
+  rvar[cc] = rv;
 }
 
-__device__ inline f32x4 ldv4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ inline f32x4 rstd4(const float* var, float eps) {
-  const f32x4 v = ldv4(var);
-  return f32x4{1.f / sqrtf(v[0] + eps), 1.f / sqrtf(v[1] + eps), 1.f / sqrtf(v[2] + eps),
-               1.f / sqrtf(v[3] + eps)};
+__global__ void bn_param_grad_kernel(const double* __restrict__ sums, int n_groups, int c,
+                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                     int accumulate) {
+  const int cc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cc >= c) return;
+  double s1 = 0.0, s2 = 0.0;
+  int g = 0;
+  for (; g + 7 < n_groups; g += 8) {      // group order, eight groups' sums in flight
+    double a[8], b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      a[u] = sums[(size_t)(g + u) * 2 * c + cc];
+      b[u] = sums[(size_t)(g + u) * 2 * c + c + cc];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      s1 += a[u];
+      s2 += b[u];
+    }
+  }
+  for (; g < n_groups; ++g) {
+    s1 += sums[(size_t)g * 2 * c + cc];
+    s2 += sums[(size_t)g * 2 * c + c + cc];
+  }
+  store_channel_sum(dbeta, cc, s1, accumulate);
+  store_channel_sum(dgamma, cc, s2, accumulate);
 }
 
-template <int U>
+// ---- fold + finish in ONE launch (round 6: the step ran ~75 fold_partials launches of 6.7 us each plus as many finish launches
+// behind them).  One wavefront per (group, channel) folds BOTH quantities of its channel, lane 0 finishes them.
 __global__ void __launch_bounds__(256)
-bn_stats_v4_kernel(const float* __restrict__ z, long rows_per_group, int c, int ldz,
-                   double* __restrict__ sums) {
-  const int g = blockIdx.y;
-  const float* zg = z + (size_t)g * rows_per_group * ldz;
-  group_channel_sums_v4<2, U>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
-                           [&](long r, int c4, f32x4& q0, f32x4& q1) {
-                             q0 = ldv4(zg + r * ldz + 4 * c4);
-                             q1 = q0 * q0;
-                           });
+fold_stats_finish_kernel(const double* __restrict__ part, int n_blocks, int c, int n_groups, long norm_rows, double* __restrict__ sums,
+                         float* __restrict__ mean, float* __restrict__ var, float* __restrict__ rmean, float* __restrict__ rvar,
+                         float momentum, long unbias_rows) {
+  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (idx >= n_groups * c) return;
+  const int g = idx / c, cc = idx % c;
+  double t[2];
+  fold<2>(part + (size_t)g * n_blocks * 2 * c + cc, c, n_blocks, 2 * c, lane, t);
+  if (lane == 0) {
+    sums[(size_t)g * 2 * c + cc] = t[0];
+    sums[(size_t)g * 2 * c + c + cc] = t[1];
+    float mf, vf;
+    bn_stats_finish(t[0], t[1], norm_rows, mf, vf);
+    mean[idx] = mf;
+    var[idx] = vf;
+    if (rmean) {      // one group
+      float rm = rmean[cc], rv = rvar[cc];
+      bn_running_step(rm, rv, mf, vf, bn_unbias(unbias_rows), momentum);
+      rmean[cc] = rm;
+      rvar[cc] = rv;
+    }
+  }
+}
+__global__ void __launch_bounds__(256)
+fold_param_grad_kernel(const double* __restrict__ part, int n_blocks, int c, double* __restrict__ sums, float* __restrict__ dgamma,
+                       float* __restrict__ dbeta, int accumulate) {      // one group
+  const int cc = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (cc >= c) return;
+  double t[2];
+  fold<2>(part + cc, c, n_blocks, 2 * c, lane, t);
+  if (lane == 0) {
+    sums[cc] = t[0];
+    sums[c + cc] = t[1];
+    store_channel_sum(dbeta, cc, t[0], accumulate);
+    store_channel_sum(dgamma, cc, t[1], accumulate);
+  }
+}
+__global__ void __launch_bounds__(256)
+fold_channel_sum_kernel(const double* __restrict__ part, int n_blocks, int c, double* __restrict__ sums, float* __restrict__ out,
+                        int accumulate) {
+  const int cc = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (cc >= c) return;
+  double t[1];
+  fold<1>(part + cc, 0, n_blocks, c, lane, t);
+  if (lane == 0) {
+    sums[cc] = t[0];
+    store_channel_sum(out, cc, t[0], accumulate);
+  }
 }
 
-__global__ void __launch_bounds__(256)
-bn_apply_v4_kernel(const float* __restrict__ z, const float* __restrict__ mean,
-                   const float* __restrict__ var, const float* __restrict__ gamma,
-                   const float* __restrict__ beta, float eps, int relu, long rows_per_group, int c,
-                   int ldz, long total4, float* __restrict__ y, unsigned char* __restrict__ relu_mask) {
-  const int c4n = c >> 2;
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total4;
-       idx += (long)gridDim.x * blockDim.x) {
-    const long row = idx / c4n;
-    const int c4 = (int)(idx % c4n);
-    const int g = (int)(row / rows_per_group);
-    const f32x4 rs = rstd4(var + g * c + 4 * c4, eps);
-    f32x4 v = (ldv4(z + row * ldz + 4 * c4) - ldv4(mean + g * c + 4 * c4)) * rs * ldv4(gamma + 4 * c4) +
-              ldv4(beta + 4 * c4);
-    // one byte per four channels: bit e = (y[4 c4 + e] > 0), what the backward's ReLU gate asks of y -- 1/16 of y's bytes
-    if (relu_mask) relu_mask[idx] = (unsigned char)((v[0] > 0.f) | ((v[1] > 0.f) << 1) | ((v[2] > 0.f) << 2) | ((v[3] > 0.f) << 3));
-    if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-    *reinterpret_cast<f32x4*>(y + row * (long)c + 4 * c4) = v;
+// ---- the channel-sum folds of a whole backward pass in ONE launch (dn_channel_sum_fold_multi).  The sums they finish -- bias
+// gradients: leaves of the backward -- are not read before the optimizer step, so the launches that leave the partials
+// (dn_bn_bwd_out.n_blocks, dn_channel_sum_partial) need not be followed by a fold each (26 launches of
+// 5 us per step).  Jobs ride in the kernel arguments; one wavefront per (job, channel).
+constexpr int kFoldJobs = 32;
+struct FoldJobs {
+  const double* part[kFoldJobs];
+  double* sums[kFoldJobs];
+  float* out[kFoldJobs];
+  int n_blocks[kFoldJobs], c[kFoldJobs], accumulate[kFoldJobs];
+  int first[kFoldJobs + 1];      // first wavefront of job j; first[n_jobs] = all wavefronts
+};
+__global__ void __launch_bounds__(256) fold_channel_sum_multi_kernel(const FoldJobs J, int n_jobs) {
+  const int wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wv >= J.first[n_jobs]) return;
+  int j = 0;
+  while (j + 1 < n_jobs && J.first[j + 1] <= wv) ++j;      // wave-uniform
+  const int cc = wv - J.first[j], c = J.c[j];
+  double t[1];
+  fold<1>(J.part[j] + cc, 0, J.n_blocks[j], c, lane, t);
+  if (lane == 0) {
+    J.sums[j][cc] = t[0];
+    store_channel_sum(J.out[j], cc, t[0], J.accumulate[j]);
+  }
+}
+
+// ---- the BatchNorm elements: each expression once, for V = 1 or 4 channels (T: float or f32x4)
+template <int V>
+__device__ inline vec<V> bn_rstd(const float* var, float eps) {
+  const vec<V> v = ldv<V>(var);
+  vec<V> r;
+#pragma unroll
+  for (int e = 0; e < V; ++e) set_lane(r, e, 1.f / sqrtf(lane(v, e) + eps));
+  return r;
+}
+template <class T> __device__ inline T bn_zhat(T z, T mean, T rstd) { return (z - mean) * rstd; }
+// The fused multiply-adds are spelled out.  Left to contraction, hipcc paired zhat * m2 with gamma * rstd into one packed
+// multiply in the scalar backward kernel and the subtraction stayed unfused: other bits than the float4 kernels'.
+template <class T> __device__ inline T bn_fwd_element(T z, T mean, T rstd, T gamma, T beta) {
+  return __builtin_elementwise_fma(bn_zhat(z, mean, rstd), gamma, beta);
+}
+// g: the incoming gradient; m1, m2: the group's means of g and g * zhat
+template <class T> __device__ inline T bn_bwd_element(T z, T mean, T rstd, T gamma, T g, T m1, T m2) {
+  return gamma * rstd * __builtin_elementwise_fma(-bn_zhat(z, mean, rstd), m2, g - m1);
+}
+// a mean of the backward: double sum / norm_rows, rounded to float
+template <int V>
+__device__ inline vec<V> bn_bwd_mean(const double* sums, long norm_rows) {
+  vec<V> m;
+#pragma unroll
+  for (int e = 0; e < V; ++e) set_lane(m, e, (float)(sums[e] / norm_rows));
+  return m;
+}
+
+// The flat index of an apply kernel over [rows][c / V] into (row, first channel, group).  General: two 64-bit divisions.
+// FAST (one group, c / 4 = 1 << sh, fewer than 2^31 float4s -- every BatchNorm of the conv stack): a shift and a mask.
+template <bool FAST> using bn_index = std::conditional_t<FAST, unsigned, long>;
+template <int V, bool FAST>
+__device__ inline void bn_decode(bn_index<FAST> idx, int c, int sh, long rows_per_group, bn_index<FAST>& row, int& cc, int& g) {
+  if constexpr (FAST) {
+    row = idx >> sh;
+    cc = V * (int)(idx & ((1u << sh) - 1u));
+    g = 0;
+  } else {
+    const int cvn = V == 4 ? c >> 2 : c;
+    row = idx / cvn;
+    cc = V * (int)(idx % cvn);
+    g = (int)(row / rows_per_group);
   }
 }
 
@@ -224,59 +404,45 @@ __device__ inline void sp_note_range(float amax, unsigned* __restrict__ flags) {
   if (amax > 16384.f && flags) atomicOr(flags, amax >= 65504.f ? 3u : 2u);
 }
 
-// One group, c / 4 a power of two, fewer than 2^31 float4s (every BatchNorm of the conv stack): the general kernel above spends
-// ~300 VALU instructions per float4 on two 64-bit divisions and four 1 / sqrtf -- it is instruction-bound at ~4.8 TB/s, not
-// HBM-bound (round 5: rocprofv3 counters, profiles/r05_train_pmc.txt).  Here 1 / sqrtf(var + eps) is computed once per workgroup
-// into LDS (the same expression: the same bits) and (row, channel quad) come from a shift and a mask.  DN_BN_LEGACY=1 routes
-// every call to the general kernels (tests: bitwise A/B).
-template <bool SP>
-__global__ void __launch_bounds__(256)
-bn_apply_v4_fast_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ var,
-                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu, int c, int sh,
-                        int ldz, unsigned total4, float* __restrict__ y, unsigned char* __restrict__ relu_mask,
-                        unsigned char* __restrict__ y_sp, unsigned hw, unsigned* __restrict__ flags) {
-  __shared__ __attribute__((aligned(16))) float rstd_s[kMaxC];
-  for (int i = threadIdx.x; i < c; i += 256) rstd_s[i] = 1.f / sqrtf(var[i] + eps);
-  __syncthreads();
-  const unsigned c4m = (1u << sh) - 1u;
+// ---- forward apply: y = (z - mean) * rstd * gamma + beta, optionally the ReLU and its byte mask, optionally (SP) the SP copy
+// of y -- the next layer's forward operand on the split-f16 engine.
+// Where the per-channel constants come from: the general kernels compute them per element from global memory -- ~300 VALU
+// instructions per float4 on two 64-bit divisions and four 1 / sqrtf: instruction-bound at ~4.8 TB/s, not HBM-bound (round 5:
+// rocprofv3 counters, profiles/r05_train_pmc.txt).  FAST computes them once per workgroup into LDS, by the same functions.
+// DN_BN_LEGACY=1 routes every call to the general kernels (tests: bitwise A/B).
+template <int V, bool FAST, bool SP>
+__device__ inline void bn_apply_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ var,
+                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu,
+                                     long rows_per_group, int c, int sh, int ldz, bn_index<FAST> total, float* __restrict__ y,
+                                     unsigned char* __restrict__ relu_mask, unsigned char* __restrict__ y_sp, unsigned hw,
+                                     unsigned* __restrict__ flags) {
+  typedef bn_index<FAST> I;
+  __shared__ __attribute__((aligned(16))) float rstd_s[FAST ? kMaxC : 4];
+  if constexpr (FAST) {
+    for (int i = threadIdx.x; i < c; i += 256) rstd_s[i] = bn_rstd<1>(var + i, eps);
+    __syncthreads();
+  }
   float amax = 0.f;
-  for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < total4; idx += gridDim.x * 256u) {
-    const unsigned row = idx >> sh;
-    const int c4 = (int)(idx & c4m);
-    const f32x4 rs = *reinterpret_cast<const f32x4*>(&rstd_s[4 * c4]);
-    f32x4 v = (ldv4(z + (size_t)row * ldz + 4 * c4) - ldv4(mean + 4 * c4)) * rs * ldv4(gamma + 4 * c4) +
-              ldv4(beta + 4 * c4);
-    if (relu_mask) relu_mask[idx] = (unsigned char)((v[0] > 0.f) | ((v[1] > 0.f) << 1) | ((v[2] > 0.f) << 2) | ((v[3] > 0.f) << 3));
-    if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-    *reinterpret_cast<f32x4*>(y + (size_t)row * c + 4 * c4) = v;
-    // the SP copy of y: the next layer's forward operand on the split-f16 engine
-    if constexpr (SP) sp_store_quad(v, amax, y_sp, row, hw, c4, c);
+  for (I idx = blockIdx.x * (I)256 + threadIdx.x; idx < total; idx += gridDim.x * (I)256) {
+    I row;
+    int cc, g;
+    bn_decode<V, FAST>(idx, c, sh, rows_per_group, row, cc, g);
+    vec<V> rs;
+    if constexpr (FAST) rs = ldv<V>(&rstd_s[cc]);
+    else rs = bn_rstd<V>(var + g * c + cc, eps);
+    vec<V> v = bn_fwd_element(ldv<V>(z + (size_t)row * ldz + cc), ldv<V>(mean + g * c + cc), rs, ldv<V>(gamma + cc), ldv<V>(beta + cc));
+    if constexpr (V == 4) {
+      // one byte per four channels: bit e = (y[cc + e] > 0), what the backward's ReLU gate asks of y -- 1/16 of y's bytes
+      if (relu_mask) relu_mask[idx] = (unsigned char)((v[0] > 0.f) | ((v[1] > 0.f) << 1) | ((v[2] > 0.f) << 2) | ((v[3] > 0.f) << 3));
+    }
+    if (relu) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) set_lane(v, e, fmaxf(lane(v, e), 0.f));
+    }
+    stv<V>(y + (size_t)row * c + cc, v);
+    if constexpr (SP) sp_store_quad(v, amax, y_sp, row, hw, cc >> 2, c);
   }
   if constexpr (SP) sp_note_range(amax, flags);
-}
-
-__global__ void __launch_bounds__(256)
-bn_stats_kernel(const float* __restrict__ z, long rows_per_group, int c, int ldz,
-                double* __restrict__ sums) {
-  const int g = blockIdx.y;
-  const float* zg = z + (size_t)g * rows_per_group * ldz;
-  group_channel_sums<2>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
-                        [&](long r, int cc, float& q0, float& q1) {
-                          const float v = zg[r * ldz + cc];
-                          q0 = v;
-                          q1 = v * v;
-                        });
-}
-
-__global__ void bn_stats_finalize_kernel(const double* __restrict__ sums, int n, int c, long rows,
-                                         float* __restrict__ mean, float* __restrict__ var) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (group, channel)
-  if (i >= n) return;
-  const int g = i / c, cc = i % c;
-  const double m = sums[(size_t)g * 2 * c + cc] / rows;
-  const double v = sums[(size_t)g * 2 * c + c + cc] / rows - m * m;
-  mean[i] = (float)m;
-  var[i] = (float)(v > 0.0 ? v : 0.0);
 }
 
 __global__ void __launch_bounds__(256)
@@ -284,365 +450,181 @@ bn_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean,
                 const float* __restrict__ var, const float* __restrict__ gamma,
                 const float* __restrict__ beta, float eps, int relu, long rows_per_group, int c,
                 int ldz, long total, float* __restrict__ y) {
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    const long row = idx / c;
-    const int cc = (int)(idx % c);
-    const int g = (int)(row / rows_per_group);
-    const float rstd = 1.f / sqrtf(var[g * c + cc] + eps);
-    float v = (z[row * ldz + cc] - mean[g * c + cc]) * rstd * gamma[cc] + beta[cc];
-    if (relu) v = fmaxf(v, 0.f);
-    y[idx] = v;
-  }
-}
-
-__global__ void bn_update_running_kernel(const float* __restrict__ mean, const float* __restrict__ var,
-                                         int n_groups, long rows, int c, const int* __restrict__ order,
-                                         float momentum, float* __restrict__ rmean,
-                                         float* __restrict__ rvar) {
-  const int cc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cc >= c) return;
-  float rm = rmean[cc], rv = rvar[cc];
-  const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
-  // the recurrence runs in group order; the groups' statistics are fetched eight at a time (one round trip instead of eight)
-  for (int k0 = 0; k0 < n_groups; k0 += 8) {
-    float m[8], v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = k0 + u < n_groups ? k0 + u : n_groups - 1;
-      const int g = order ? order[k] : k;
-      m[u] = mean[g * c + cc];
-      v[u] = var[g * c + cc];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (k0 + u < n_groups) {
-        rm = (1.f - momentum) * rm + momentum * m[u];
-        rv = (1.f - momentum) * rv + momentum * (v[u] * unbias);
-      }
-  }
-  rmean[cc] = rm;
-  rvar[cc] = rv;
-}
-
-// ---- fold + finish in ONE launch (round 6: the step ran ~75 fold_partials launches of 6.7 us each plus as many 3-5 us finalize
-// launches behind them).  One wavefront per (group, channel) folds BOTH quantities of its channel in fold_partials_kernel's order
-// (lane l adds blocks l, l + 64, ...; xor butterfly): the same sums bit for bit, then the finish arithmetic of the kernel it
-// replaces -- bn_stats_finalize_kernel (+ optionally bn_update_running_kernel: one group), bn_param_grad_kernel (one group),
-// channel_sum_finalize_kernel.
-// FOLD_BATCH: partials a lane fetches before it adds them (in the same order: the same bits).  With one load per iteration a
-// lane's up to 16 partials were 16 L2 round trips in a row: 7-11 us per launch, 72 launches per step (profiles/r06_fold_batch_ab.txt).
-constexpr int FOLD_BATCH = 8;
-__device__ inline double fold_one(const double* __restrict__ p, int n_blocks, size_t stride, int lane) {
-  double t = 0.0;
-  int b = lane;
-  for (; b + 64 * (FOLD_BATCH - 1) < n_blocks; b += 64 * FOLD_BATCH) {
-    double v[FOLD_BATCH];
-#pragma unroll
-    for (int u = 0; u < FOLD_BATCH; ++u) v[u] = p[(size_t)(b + 64 * u) * stride];
-#pragma unroll
-    for (int u = 0; u < FOLD_BATCH; ++u) t += v[u];
-  }
-  for (; b < n_blocks; b += 64) t += p[(size_t)b * stride];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  return t;
-}
-// two quantities of one channel (p0, p1: the same blocks): both fetches of a batch in flight together, each sum in fold_one's order
-__device__ inline void fold_two(const double* __restrict__ p0, const double* __restrict__ p1, int n_blocks, size_t stride, int lane,
-                                double& t0, double& t1) {
-  double a = 0.0, c = 0.0;
-  int b = lane;
-  for (; b + 64 * (FOLD_BATCH - 1) < n_blocks; b += 64 * FOLD_BATCH) {
-    double v[FOLD_BATCH], w[FOLD_BATCH];
-#pragma unroll
-    for (int u = 0; u < FOLD_BATCH; ++u) {
-      v[u] = p0[(size_t)(b + 64 * u) * stride];
-      w[u] = p1[(size_t)(b + 64 * u) * stride];
-    }
-#pragma unroll
-    for (int u = 0; u < FOLD_BATCH; ++u) {
-      a += v[u];
-      c += w[u];
-    }
-  }
-  for (; b < n_blocks; b += 64) {
-    const double v = p0[(size_t)b * stride], w = p1[(size_t)b * stride];
-    a += v;
-    c += w;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    c += __shfl_xor(c, o, 64);
-  }
-  t0 = a;
-  t1 = c;
+  bn_apply_body<1, false, false>(z, mean, var, gamma, beta, eps, relu, rows_per_group, c, 0, ldz, total, y, nullptr, nullptr, 1u, nullptr);
 }
 __global__ void __launch_bounds__(256)
-fold_stats_finish_kernel(const double* __restrict__ part, int n_blocks, int c, int n_groups, long norm_rows, double* __restrict__ sums,
-                         float* __restrict__ mean, float* __restrict__ var, float* __restrict__ rmean, float* __restrict__ rvar,
-                         float momentum, long unbias_rows) {
-  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (idx >= n_groups * c) return;
-  const int g = idx / c, cc = idx % c;
-  const double* p = part + (size_t)g * n_blocks * 2 * c + cc;
-  double t0, t1;
-  fold_two(p, p + c, n_blocks, 2 * c, lane, t0, t1);
-  if (lane == 0) {
-    sums[(size_t)g * 2 * c + cc] = t0;
-    sums[(size_t)g * 2 * c + c + cc] = t1;
-    const double m = t0 / norm_rows;
-    const double v = t1 / norm_rows - m * m;
-    const float mf = (float)m, vf = (float)(v > 0.0 ? v : 0.0);
-    mean[idx] = mf;
-    var[idx] = vf;
-    if (rmean) {      // (one group) bn_update_running_kernel's arithmetic
-      const float unbias = unbias_rows > 1 ? (float)unbias_rows / (float)(unbias_rows - 1) : 1.f;
-      rmean[cc] = (1.f - momentum) * rmean[cc] + momentum * mf;
-      rvar[cc] = (1.f - momentum) * rvar[cc] + momentum * (vf * unbias);
-    }
-  }
+bn_apply_v4_kernel(const float* __restrict__ z, const float* __restrict__ mean,
+                   const float* __restrict__ var, const float* __restrict__ gamma,
+                   const float* __restrict__ beta, float eps, int relu, long rows_per_group, int c,
+                   int ldz, long total4, float* __restrict__ y, unsigned char* __restrict__ relu_mask) {
+  bn_apply_body<4, false, false>(z, mean, var, gamma, beta, eps, relu, rows_per_group, c, 0, ldz, total4, y, relu_mask, nullptr, 1u, nullptr);
 }
+template <bool SP>
 __global__ void __launch_bounds__(256)
-fold_param_grad_kernel(const double* __restrict__ part, int n_blocks, int c, double* __restrict__ sums, float* __restrict__ dgamma,
-                       float* __restrict__ dbeta, int accumulate) {      // one group
-  const int cc = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (cc >= c) return;
-  double t0, t1;
-  fold_two(part + cc, part + c + cc, n_blocks, 2 * c, lane, t0, t1);
-  if (lane == 0) {
-    sums[cc] = t0;
-    sums[c + cc] = t1;
-    double s1 = 0.0, s2 = 0.0;      // (bn_param_grad_kernel's sum over its one group)
-    s1 += t0;
-    s2 += t1;
-    dbeta[cc] = (accumulate ? dbeta[cc] : 0.f) + (float)s1;
-    dgamma[cc] = (accumulate ? dgamma[cc] : 0.f) + (float)s2;
-  }
-}
-__global__ void __launch_bounds__(256)
-fold_channel_sum_kernel(const double* __restrict__ part, int n_blocks, int c, double* __restrict__ sums, float* __restrict__ out,
-                        int accumulate) {
-  const int cc = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (cc >= c) return;
-  const double t = fold_one(part + cc, n_blocks, c, lane);
-  if (lane == 0) {
-    sums[cc] = t;
-    out[cc] = (accumulate ? out[cc] : 0.f) + (float)t;
-  }
+bn_apply_v4_fast_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ var,
+                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu, int c, int sh,
+                        int ldz, unsigned total4, float* __restrict__ y, unsigned char* __restrict__ relu_mask,
+                        unsigned char* __restrict__ y_sp, unsigned hw, unsigned* __restrict__ flags) {
+  bn_apply_body<4, true, SP>(z, mean, var, gamma, beta, eps, relu, 0L, c, sh, ldz, total4, y, relu_mask, y_sp, hw, flags);
 }
 
-// ---- the channel-sum folds of a whole backward pass in ONE launch (dn_channel_sum_fold_multi).  The sums they finish -- bias
-// gradients: leaves of the backward -- are not read before the optimizer step, so the launches that leave the partials
-// (dn_bn_bwd_out.n_blocks, dn_channel_sum_partial) need not be followed by a fold each (26 launches of
-// 5 us per step).  Jobs ride in the kernel arguments; one wavefront per (job, channel) runs fold_channel_sum_kernel's body.
-constexpr int kFoldJobs = 32;
-struct FoldJobs {
-  const double* part[kFoldJobs];
-  double* sums[kFoldJobs];
-  float* out[kFoldJobs];
-  int n_blocks[kFoldJobs], c[kFoldJobs], accumulate[kFoldJobs];
-  int first[kFoldJobs + 1];      // first wavefront of job j; first[n_jobs] = all wavefronts
-};
-__global__ void __launch_bounds__(256) fold_channel_sum_multi_kernel(const FoldJobs J, int n_jobs) {
-  const int wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (wv >= J.first[n_jobs]) return;
-  int j = 0;
-  while (j + 1 < n_jobs && J.first[j + 1] <= wv) ++j;      // wave-uniform
-  const int cc = wv - J.first[j], c = J.c[j];
-  const double t = fold_one(J.part[j] + cc, J.n_blocks[j], c, lane);
-  if (lane == 0) {
-    J.sums[j][cc] = t;
-    float* out = J.out[j];
-    out[cc] = (J.accumulate[j] ? out[cc] : 0.f) + (float)t;
-  }
-}
-
-// incoming gradient of one element: dy_a (optionally the 2 x 2 block sum of a map at twice
-// the resolution) + dy_b, gated by the ReLU
+// incoming gradient of one element: dy_a (dense, the 2 x 2 block sum of a map at twice the resolution, or the space-to-depth
+// image of the gradient) + dy_b, gated by the ReLU
 struct GradSrc {
   const float* dy_a;
   const float* dy_b;
   const float* y;
   int ld_a, up_a, ld_b, relu, h, w, c;
-  __device__ inline float operator()(long row, int cc) const {
-    float g;
-    if (up_a == 2) {
-      // dy_a is the space-to-depth image of the gradient: [img][h / 2][w / 2][4 c], pixel (y, x) channel cc at
-      // (y / 2, x / 2), channel ((y & 1) * 2 + (x & 1)) * c + cc -- what ONE split-f16 launch over the four parity classes of a
-      // stride-2 layer's data gradient writes (train.py :: _dgrad)
-      const long img = row / ((long)h * w);
-      const int p = (int)(row % ((long)h * w));
-      const int py = p / w, px = p % w;
-      g = dy_a[((img * (h >> 1) + (py >> 1)) * (long)(w >> 1) + (px >> 1)) * ld_a + ((py & 1) * 2 + (px & 1)) * c + cc];
-    } else if (up_a) {
-      const long img = row / ((long)h * w);
-      const int p = (int)(row % ((long)h * w));
-      const int py = p / w, px = p % w;
-      const float* b = dy_a + ((img * 2 * h + 2 * py) * (2L * w) + 2 * px) * ld_a + cc;
-      g = (b[0] + b[ld_a]) + (b[2L * w * ld_a] + b[(2L * w + 1) * ld_a]);
-    } else {
-      g = dy_a[row * ld_a + cc];
-    }
-    if (dy_b) g += dy_b[row * ld_b + cc];
-    if (relu == 2) {          // y is the byte mask of dn_bn_train_apply (c % 4 == 0)
-      if (!((reinterpret_cast<const unsigned char*>(y)[(row * c + cc) >> 2] >> (cc & 3)) & 1)) g = 0.f;
-    } else if (relu && !(y[row * c + cc] > 0.f)) g = 0.f;
-    return g;
-  }
-  // v4 for rows below 2^31 (the one-group fast kernels): the same values, the pixel decode in 32-bit arithmetic
-  __device__ inline f32x4 v4u(unsigned row, int c4) const {
-    f32x4 g;
+  // channels cc .. cc + V - 1 of pixel `row`.  R: long, or unsigned for rows below 2^31 (the one-group fast kernels): the same
+  // values, the pixel decode in 32-bit arithmetic
+  template <int V, class R>
+  __device__ inline vec<V> load(R row, int cc) const {
+    vec<V> g;
     if (up_a) {
-      const unsigned hw = (unsigned)h * (unsigned)w;
-      const unsigned img = row / hw, p = row - img * hw;
-      const unsigned py = p / (unsigned)w, px = p - py * (unsigned)w;
+      const R hw = (R)h * (R)w, img = row / hw;
+      const unsigned p = (unsigned)(row % hw), py = p / (unsigned)w, px = p - py * (unsigned)w;
       if (up_a == 2) {
-        g = ldv4(dy_a + (((size_t)img * (h >> 1) + (py >> 1)) * (size_t)(w >> 1) + (px >> 1)) * ld_a + ((py & 1) * 2 + (px & 1)) * c + 4 * c4);
+        // dy_a is the space-to-depth image of the gradient: [img][h / 2][w / 2][4 c], pixel (y, x) channel cc at
+        // (y / 2, x / 2), channel ((y & 1) * 2 + (x & 1)) * c + cc -- what ONE split-f16 launch over the four parity classes of a
+        // stride-2 layer's data gradient writes (train.py :: _dgrad)
+        g = ldv<V>(dy_a + (((size_t)img * (h >> 1) + (py >> 1)) * (size_t)(w >> 1) + (px >> 1)) * ld_a + ((py & 1) * 2 + (px & 1)) * c + cc);
       } else {
-        const float* b = dy_a + (((size_t)img * 2 * h + 2 * py) * (2L * w) + 2 * px) * ld_a + 4 * c4;
-        g = (ldv4(b) + ldv4(b + ld_a)) + (ldv4(b + 2L * w * ld_a) + ldv4(b + (2L * w + 1) * ld_a));
+        const float* b = dy_a + (((size_t)img * 2 * h + 2 * py) * (2L * w) + 2 * px) * ld_a + cc;
+        g = (ldv<V>(b) + ldv<V>(b + ld_a)) + (ldv<V>(b + 2L * w * ld_a) + ldv<V>(b + (2L * w + 1) * ld_a));
       }
     } else {
-      g = ldv4(dy_a + (size_t)row * ld_a + 4 * c4);
+      g = ldv<V>(dy_a + (size_t)row * ld_a + cc);
     }
-    if (dy_b) g += ldv4(dy_b + (size_t)row * ld_b + 4 * c4);
-    if (relu == 2) {
-      const unsigned m = reinterpret_cast<const unsigned char*>(y)[(size_t)row * (c >> 2) + c4];
+    if (dy_b) g += ldv<V>(dy_b + (size_t)row * ld_b + cc);
+    if (relu == 2) {          // y is the byte mask of dn_bn_train_apply (c % 4 == 0): bit cc & 3 of byte (row * c + cc) / 4
+      const unsigned m = reinterpret_cast<const unsigned char*>(y)[((size_t)row * c + cc) >> 2] >> (cc & 3);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (!((m >> e) & 1)) g[e] = 0.f;
+      for (int e = 0; e < V; ++e)
+        if (!((m >> e) & 1)) set_lane(g, e, 0.f);
     } else if (relu) {
-      const f32x4 yv = ldv4(y + (size_t)row * c + 4 * c4);
+      const vec<V> yv = ldv<V>(y + (size_t)row * c + cc);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (!(yv[e] > 0.f)) g[e] = 0.f;
-    }
-    return g;
-  }
-  __device__ inline f32x4 v4(long row, int c4) const {
-    f32x4 g;
-    if (up_a == 2) {
-      const long img = row / ((long)h * w);
-      const int p = (int)(row % ((long)h * w));
-      const int py = p / w, px = p % w;
-      g = ldv4(dy_a + ((img * (h >> 1) + (py >> 1)) * (long)(w >> 1) + (px >> 1)) * ld_a + ((py & 1) * 2 + (px & 1)) * c + 4 * c4);
-    } else if (up_a) {
-      const long img = row / ((long)h * w);
-      const int p = (int)(row % ((long)h * w));
-      const int py = p / w, px = p % w;
-      const float* b = dy_a + ((img * 2 * h + 2 * py) * (2L * w) + 2 * px) * ld_a + 4 * c4;
-      g = (ldv4(b) + ldv4(b + ld_a)) + (ldv4(b + 2L * w * ld_a) + ldv4(b + (2L * w + 1) * ld_a));
-    } else {
-      g = ldv4(dy_a + row * ld_a + 4 * c4);
-    }
-    if (dy_b) g += ldv4(dy_b + row * ld_b + 4 * c4);
-    if (relu == 2) {
-      const unsigned m = reinterpret_cast<const unsigned char*>(y)[row * (long)(c >> 2) + c4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (!((m >> e) & 1)) g[e] = 0.f;
-    } else if (relu) {
-      const f32x4 yv = ldv4(y + row * (long)c + 4 * c4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (!(yv[e] > 0.f)) g[e] = 0.f;
+      for (int e = 0; e < V; ++e)
+        if (!(lane(yv, e) > 0.f)) set_lane(g, e, 0.f);
     }
     return g;
   }
 };
 
+// ---- the reductions: each quantity's addend once, for V = 1 or 4 channels per lane
+template <int V, int U>
+__device__ inline void bn_stats_body(const float* __restrict__ z, long rows_per_group, int c, int ldz, double* __restrict__ sums) {
+  const int g = blockIdx.y;
+  const float* zg = z + (size_t)g * rows_per_group * ldz;
+  group_channel_sums<2, V, U>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
+                              [&](long r, int cc, vec<V>& q0, vec<V>& q1) {
+                                q0 = ldv<V>(zg + r * ldz + cc);
+                                q1 = q0 * q0;
+                              });
+}
+template <int V, int U>
+__device__ inline void bn_bwd_reduce_body(const GradSrc& src, const float* __restrict__ z, const float* __restrict__ mean,
+                                          const float* __restrict__ var, float eps, long rows_per_group, double* __restrict__ sums) {
+  const int g = blockIdx.y, c = src.c;
+  const long base = (long)g * rows_per_group;
+  group_channel_sums<2, V, U>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
+                              [&](long r, int cc, vec<V>& q0, vec<V>& q1) {
+                                q0 = src.load<V>(base + r, cc);
+                                q1 = q0 * bn_zhat(ldv<V>(z + (base + r) * c + cc), ldv<V>(mean + g * c + cc), bn_rstd<V>(var + g * c + cc, eps));
+                              });
+}
+template <int V, int U>
+__device__ inline void channel_sum_body(const float* __restrict__ x, long rows, int c, int ld, double* __restrict__ sums) {
+  group_channel_sums<1, V, U>(c, rows, sums, [&](long r, int cc, vec<V>& q0, vec<V>& q1) {
+    q0 = ldv<V>(x + r * ld + cc);
+    (void)q1;
+  });
+}
+
+__global__ void __launch_bounds__(256)
+bn_stats_kernel(const float* __restrict__ z, long rows_per_group, int c, int ldz, double* __restrict__ sums) {
+  bn_stats_body<1, 1>(z, rows_per_group, c, ldz, sums);
+}
+template <int U>
+__global__ void __launch_bounds__(256)
+bn_stats_v4_kernel(const float* __restrict__ z, long rows_per_group, int c, int ldz, double* __restrict__ sums) {
+  bn_stats_body<4, U>(z, rows_per_group, c, ldz, sums);
+}
+__global__ void __launch_bounds__(256)
+bn_bwd_reduce_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
+                     const float* __restrict__ var, float eps, long rows_per_group, double* __restrict__ sums) {
+  bn_bwd_reduce_body<1, 1>(src, z, mean, var, eps, rows_per_group, sums);
+}
 template <int U>
 __global__ void __launch_bounds__(256)
 bn_bwd_reduce_v4_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
-                        const float* __restrict__ var, float eps, long rows_per_group,
-                        double* __restrict__ sums) {
-  const int g = blockIdx.y, c = src.c;
-  const long base = (long)g * rows_per_group;
-  group_channel_sums_v4<2, U>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
-                           [&](long r, int c4, f32x4& q0, f32x4& q1) {
-                             q0 = src.v4(base + r, c4);
-                             const f32x4 zh = (ldv4(z + (base + r) * c + 4 * c4) - ldv4(mean + g * c + 4 * c4)) *
-                                              rstd4(var + g * c + 4 * c4, eps);
-                             q1 = q0 * zh;
-                           });
+                        const float* __restrict__ var, float eps, long rows_per_group, double* __restrict__ sums) {
+  bn_bwd_reduce_body<4, U>(src, z, mean, var, eps, rows_per_group, sums);
+}
+__global__ void __launch_bounds__(256)
+channel_sum_kernel(const float* __restrict__ x, long rows, int c, int ld, double* __restrict__ sums) {
+  channel_sum_body<1, 1>(x, rows, c, ld, sums);
+}
+template <int U>
+__global__ void __launch_bounds__(256)
+channel_sum_v4_kernel(const float* __restrict__ x, long rows, int c, int ld, double* __restrict__ sums) {
+  channel_sum_body<4, U>(x, rows, c, ld, sums);
 }
 
+// ---- backward apply: dz = gamma * rstd * (g - m1 - zhat * m2).  The per-channel constants (1 / sqrtf(var + eps) and the two
+// means: eight fp64 divisions per float4 in the general kernels) and the index decode: as in bn_apply_body; FAST also decodes
+// the incoming gradient's pixel in 32 bits.
 // SP: a second copy of dz, multiplied by the power of two `sp_lift`, as the split-planar f16 hi / lo tensor of the inference conv
 // engine -- the operand of the split-f16 data gradient (dn_spconv2d_nhwc) -- written by sp_store_quad, magnitudes reported into
-// the conv engine's sticky range word (`flags`).
-template <bool SP>
-__global__ void __launch_bounds__(256)
-bn_bwd_apply_v4_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
-                       const float* __restrict__ var, const float* __restrict__ gamma, float eps,
-                       long rows_per_group, long norm_rows, const double* __restrict__ sums, long total4,
-                       float* __restrict__ dz, unsigned char* __restrict__ dz_sp, float sp_lift, unsigned hw,
-                       unsigned* __restrict__ flags) {
-  const int c = src.c, c4n = c >> 2;
-  float amax = 0.f;
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total4;
-       idx += (long)gridDim.x * blockDim.x) {
-    const long row = idx / c4n;
-    const int c4 = (int)(idx % c4n);
-    const int g = (int)(row / rows_per_group);
-    const f32x4 rs = rstd4(var + g * c + 4 * c4, eps);
-    const f32x4 zh = (ldv4(z + row * c + 4 * c4) - ldv4(mean + g * c + 4 * c4)) * rs;
-    const double* sg = sums + (size_t)g * 2 * c + 4 * c4;
-    f32x4 m1, m2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      m1[e] = (float)(sg[e] / norm_rows);
-      m2[e] = (float)(sg[c + e] / norm_rows);
-    }
-    const f32x4 v = ldv4(gamma + 4 * c4) * rs * (src.v4(row, c4) - m1 - zh * m2);
-    *reinterpret_cast<f32x4*>(dz + row * c + 4 * c4) = v;
-    if constexpr (SP) sp_store_quad(v * sp_lift, amax, dz_sp, (unsigned)row, hw, c4, c);
-  }
-  if constexpr (SP) sp_note_range(amax, flags);
-}
-
-// The one-group fast form of bn_bwd_apply_v4_kernel (see bn_apply_v4_fast_kernel): per channel 1 / sqrtf(var + eps) and the two
-// means (double sum / norm_rows, rounded to float -- eight fp64 divisions per float4 in the general kernel) once per workgroup
-// into LDS, the same expressions; (row, channel quad) by shift and mask; the pixel decode of the incoming gradient in 32 bits.
-// BIAS: the per-channel sums of dz -- the gradient of the conv bias in front of this BatchNorm -- leave this launch as one
-// double per (workgroup, channel) in `bias_part` (folded by fold_partials_kernel in a fixed order: deterministic), instead of
-// a dn_channel_sum pass that reads dz again (round 6: 0.5 ms of the det step).  A thread's channel quad never changes (the
+// the conv engine's sticky range word (`flags`).  FAST only (round 6): dz may be NULL, the SP copy is then the only consumer's.
+// BIAS (FAST only, round 6): the per-channel sums of dz -- the gradient of the conv bias in front of this BatchNorm -- leave this
+// launch as one double per (workgroup, channel) in `bias_part` (folded in a fixed order: deterministic), instead of
+// a dn_channel_sum pass that reads dz again (0.5 ms of the det step).  A thread's channel quad never changes (the
 // grid stride is a multiple of c / 4): it adds its own dz values in fp32 in loop order, the workgroup adds the threads of a
 // quad in thread order in double.
-template <bool SP, bool BIAS = false>
-__global__ void __launch_bounds__(256)
-bn_bwd_apply_v4_fast_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
-                            const float* __restrict__ var, const float* __restrict__ gamma, float eps, long norm_rows,
-                            const double* __restrict__ sums, int sh, unsigned total4, float* __restrict__ dz,
-                            unsigned char* __restrict__ dz_sp, float sp_lift, unsigned hw, unsigned* __restrict__ flags,
-                            double* __restrict__ bias_part = nullptr) {
-  __shared__ __attribute__((aligned(16))) float rstd_s[kMaxC], m1_s[kMaxC], m2_s[kMaxC];
+template <int V, bool FAST, bool SP, bool BIAS>
+__device__ inline void bn_bwd_apply_body(const GradSrc& src, const float* __restrict__ z, const float* __restrict__ mean,
+                                         const float* __restrict__ var, const float* __restrict__ gamma, float eps,
+                                         long rows_per_group, long norm_rows, const double* __restrict__ sums, int sh,
+                                         bn_index<FAST> total, float* __restrict__ dz, unsigned char* __restrict__ dz_sp,
+                                         float sp_lift, unsigned hw, unsigned* __restrict__ flags, double* __restrict__ bias_part) {
+  static_assert(FAST || !BIAS, "the bias partials are the fast form's");
+  typedef bn_index<FAST> I;
+  __shared__ __attribute__((aligned(16))) float rstd_s[FAST ? kMaxC : 4], m1_s[FAST ? kMaxC : 4], m2_s[FAST ? kMaxC : 4];
   const int c = src.c;
-  for (int i = threadIdx.x; i < c; i += 256) {
-    rstd_s[i] = 1.f / sqrtf(var[i] + eps);
-    m1_s[i] = (float)(sums[i] / norm_rows);
-    m2_s[i] = (float)(sums[c + i] / norm_rows);
+  if constexpr (FAST) {
+    for (int i = threadIdx.x; i < c; i += 256) {
+      rstd_s[i] = bn_rstd<1>(var + i, eps);
+      m1_s[i] = bn_bwd_mean<1>(sums + i, norm_rows);
+      m2_s[i] = bn_bwd_mean<1>(sums + c + i, norm_rows);
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  const unsigned c4m = (1u << sh) - 1u;
   float amax = 0.f;
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-  for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < total4; idx += gridDim.x * 256u) {
-    const unsigned row = idx >> sh;
-    const int c4 = (int)(idx & c4m);
-    const f32x4 rs = *reinterpret_cast<const f32x4*>(&rstd_s[4 * c4]);
-    const f32x4 zh = (ldv4(z + (size_t)row * c + 4 * c4) - ldv4(mean + 4 * c4)) * rs;
-    const f32x4 m1 = *reinterpret_cast<const f32x4*>(&m1_s[4 * c4]), m2 = *reinterpret_cast<const f32x4*>(&m2_s[4 * c4]);
-    const f32x4 v = ldv4(gamma + 4 * c4) * rs * (src.v4u(row, c4) - m1 - zh * m2);
-    if (!SP || dz) *reinterpret_cast<f32x4*>(dz + (size_t)row * c + 4 * c4) = v;      // (dz NULL: the SP copy is the only consumer's)
+  vec<V> bsum = vec<V>{};
+  for (I idx = blockIdx.x * (I)256 + threadIdx.x; idx < total; idx += gridDim.x * (I)256) {
+    I row;
+    int cc, g;
+    bn_decode<V, FAST>(idx, c, sh, rows_per_group, row, cc, g);
+    vec<V> rs, m1, m2;
+    if constexpr (FAST) {
+      rs = ldv<V>(&rstd_s[cc]);
+      m1 = ldv<V>(&m1_s[cc]);
+      m2 = ldv<V>(&m2_s[cc]);
+    } else {
+      rs = bn_rstd<V>(var + g * c + cc, eps);
+      m1 = bn_bwd_mean<V>(sums + (size_t)g * 2 * c + cc, norm_rows);
+      m2 = bn_bwd_mean<V>(sums + (size_t)g * 2 * c + c + cc, norm_rows);
+    }
+    const vec<V> v = bn_bwd_element(ldv<V>(z + (size_t)row * c + cc), ldv<V>(mean + g * c + cc), rs, ldv<V>(gamma + cc), src.load<V>(row, cc), m1, m2);
+    if (!SP || dz) stv<V>(dz + (size_t)row * c + cc, v);
     if constexpr (BIAS) bsum += v;
-    if constexpr (SP) sp_store_quad(v * sp_lift, amax, dz_sp, row, hw, c4, c);
+    if constexpr (SP) sp_store_quad(v * sp_lift, amax, dz_sp, (unsigned)row, hw, cc >> 2, c);
   }
   if constexpr (SP) sp_note_range(amax, flags);
   if constexpr (BIAS) {
     __shared__ __attribute__((aligned(16))) float bred[256][4];
-    *reinterpret_cast<f32x4*>(bred[threadIdx.x]) = bsum;
+    stv<4>(bred[threadIdx.x], bsum);
     __syncthreads();
     const int c4n = 1 << sh;
     for (int cc = threadIdx.x; cc < c; cc += 256) {
@@ -654,88 +636,29 @@ bn_bwd_apply_v4_fast_kernel(GradSrc src, const float* __restrict__ z, const floa
 }
 
 __global__ void __launch_bounds__(256)
-bn_bwd_reduce_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
-                     const float* __restrict__ var, float eps, long rows_per_group,
-                     double* __restrict__ sums) {
-  const int g = blockIdx.y, c = src.c;
-  const long base = (long)g * rows_per_group;
-  group_channel_sums<2>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
-                        [&](long r, int cc, float& q0, float& q1) {
-                          const float gr = src(base + r, cc);
-                          const float rstd = 1.f / sqrtf(var[g * c + cc] + eps);
-                          q0 = gr;
-                          q1 = gr * ((z[(base + r) * c + cc] - mean[g * c + cc]) * rstd);
-                        });
-}
-
-__global__ void __launch_bounds__(256)
 bn_bwd_apply_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
                     const float* __restrict__ var, const float* __restrict__ gamma, float eps,
                     long rows_per_group, long norm_rows, const double* __restrict__ sums, long total,
                     float* __restrict__ dz) {
-  const int c = src.c;
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    const long row = idx / c;
-    const int cc = (int)(idx % c);
-    const int g = (int)(row / rows_per_group);
-    const float rstd = 1.f / sqrtf(var[g * c + cc] + eps);
-    const float zh = (z[idx] - mean[g * c + cc]) * rstd;
-    const float m1 = (float)(sums[(size_t)g * 2 * c + cc] / norm_rows);
-    const float m2 = (float)(sums[(size_t)g * 2 * c + c + cc] / norm_rows);
-    dz[idx] = gamma[cc] * rstd * (src(row, cc) - m1 - zh * m2);
-  }
+  bn_bwd_apply_body<1, false, false, false>(src, z, mean, var, gamma, eps, rows_per_group, norm_rows, sums, 0, total, dz, nullptr, 1.f, 1u, nullptr, nullptr);
 }
-
-__global__ void bn_param_grad_kernel(const double* __restrict__ sums, int n_groups, int c,
-                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                     int accumulate) {
-  const int cc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cc >= c) return;
-  double s1 = 0.0, s2 = 0.0;
-  int g = 0;
-  for (; g + 7 < n_groups; g += 8) {      // group order, eight groups' sums in flight
-    double a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = sums[(size_t)(g + u) * 2 * c + cc];
-      b[u] = sums[(size_t)(g + u) * 2 * c + c + cc];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      s1 += a[u];
-      s2 += b[u];
-    }
-  }
-  for (; g < n_groups; ++g) {
-    s1 += sums[(size_t)g * 2 * c + cc];
-    s2 += sums[(size_t)g * 2 * c + c + cc];
-  }
-  dbeta[cc] = (accumulate ? dbeta[cc] : 0.f) + (float)s1;
-  dgamma[cc] = (accumulate ? dgamma[cc] : 0.f) + (float)s2;
-}
-
+template <bool SP>
 __global__ void __launch_bounds__(256)
-channel_sum_kernel(const float* __restrict__ x, long rows, int c, int ld, double* __restrict__ sums) {
-  group_channel_sums<1>(c, rows, sums, [&](long r, int cc, float& q0, float& q1) {
-    q0 = x[r * ld + cc];
-    (void)q1;
-  });
+bn_bwd_apply_v4_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
+                       const float* __restrict__ var, const float* __restrict__ gamma, float eps,
+                       long rows_per_group, long norm_rows, const double* __restrict__ sums, long total4,
+                       float* __restrict__ dz, unsigned char* __restrict__ dz_sp, float sp_lift, unsigned hw,
+                       unsigned* __restrict__ flags) {
+  bn_bwd_apply_body<4, false, SP, false>(src, z, mean, var, gamma, eps, rows_per_group, norm_rows, sums, 0, total4, dz, dz_sp, sp_lift, hw, flags, nullptr);
 }
-
-template <int U>
+template <bool SP, bool BIAS = false>
 __global__ void __launch_bounds__(256)
-channel_sum_v4_kernel(const float* __restrict__ x, long rows, int c, int ld, double* __restrict__ sums) {
-  group_channel_sums_v4<1, U>(c, rows, sums, [&](long r, int c4, f32x4& q0, f32x4& q1) {
-    q0 = ldv4(x + r * ld + 4 * c4);
-    (void)q1;
-  });
-}
-
-__global__ void channel_sum_finalize_kernel(const double* __restrict__ sums, int c,
-                                            float* __restrict__ out, int accumulate) {
-  const int cc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cc < c) out[cc] = (accumulate ? out[cc] : 0.f) + (float)sums[cc];
+bn_bwd_apply_v4_fast_kernel(GradSrc src, const float* __restrict__ z, const float* __restrict__ mean,
+                            const float* __restrict__ var, const float* __restrict__ gamma, float eps, long norm_rows,
+                            const double* __restrict__ sums, int sh, unsigned total4, float* __restrict__ dz,
+                            unsigned char* __restrict__ dz_sp, float sp_lift, unsigned hw, unsigned* __restrict__ flags,
+                            double* __restrict__ bias_part = nullptr) {
+  bn_bwd_apply_body<4, true, SP, BIAS>(src, z, mean, var, gamma, eps, 0L, norm_rows, sums, sh, total4, dz, dz_sp, sp_lift, hw, flags, bias_part);
 }
 
 __global__ void add_rows_kernel(float* __restrict__ a, int ld_a, const float* __restrict__ b, int ld_b,

@@ -495,6 +495,32 @@ def test_bn_fast_kernels_equal_the_general_kernels_bit_for_bit(tmp_path):
         assert torch.equal(a.view(torch.uint8), b.view(torch.uint8))
 
 
+def test_bn_stats_two_phase_equals_the_one_call_form_bit_for_bit():
+    """dn_bn_train_stats_partial + dn_bn_train_stats_finish (fold_partials_kernel, bn_stats_finalize_kernel) against
+    dn_bn_train_stats (fold_stats_finish_kernel): the same fold and the same finish, so the same bits -- at shapes that put the fold
+    at each of its edges (blocks per group = min(1024 / groups, rows per group / 64)).  One group: the running statistics that
+    leave the fused launch are bn_update_running's."""
+    from disconet_amd import train_ops
+    for shape, groups in (((1, 8, 8, 16), 1),          # 1 block
+                          ((1, 20, 32, 4), 1),         # 10 blocks: most lanes idle
+                          ((1, 192, 192, 8), 1),       # 576 blocks: one full batch of 8 x 64 plus a tail
+                          ((2, 96, 96, 12), 2),        # 144 blocks per group, float4 multi-group
+                          ((2, 16, 16, 5), 2)):        # scalar kernels
+        c = shape[-1]
+        g = torch.Generator().manual_seed(61)
+        z = (torch.randn(shape, generator=g) * 2 + 0.5).to(_dev())
+        mean2, var2 = train_ops.bn_stats(z, groups, sync=lambda t: None)
+        mean1, var1 = train_ops.bn_stats(z, groups)
+        assert torch.equal(mean1, mean2) and torch.equal(var1, var2), shape
+        if groups == 1:
+            rm0, rv0 = torch.randn(c, generator=g).to(_dev()), (torch.rand(c, generator=g) + 0.5).to(_dev())
+            rm, rv = rm0.clone(), rv0.clone()
+            mean3, var3 = train_ops.bn_stats(z, running=(rm, rv, 0.1))
+            assert torch.equal(mean3, mean2) and torch.equal(var3, var2), shape
+            train_ops.bn_update_running(mean2, var2, z.numel() // c, rm0, rv0, 0.1)
+            assert torch.equal(rm, rm0) and torch.equal(rv, rv0), shape
+
+
 def test_bn_backward_sp_copy_flags_a_gradient_that_outgrows_its_lift():
     from disconet_amd import ops, train_ops
     n, h, w, c = 1, 8, 8, 32
