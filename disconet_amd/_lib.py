@@ -253,6 +253,7 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
     "dn_bn_bias_workspace_bytes": (c_size_t, [c_long, c_int]),
     "dn_bn_train_form_supported": (c_int, [c_int, c_int, c_long, c_int]),
+    "dn_bn_train_last_form": (c_int, [c_int, POINTER(c_int), c_int]),
     "dn_bn_train_backward_partial": (c_int, [POINTER(BnBwdDesc), c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
     "dn_bn_train_backward_finish": (c_int, [POINTER(BnBwdDesc), c_void_p, c_long, POINTER(BnBwdOut), c_void_p]),
     "dn_bn_train_backward": (c_int, [POINTER(BnBwdDesc), c_void_p, c_size_t, POINTER(BnBwdOut), c_void_p, c_void_p, c_int,

@@ -62,8 +62,11 @@ __device__ inline void set_lane(f32x4& v, int e, float x) { v[e] = x; }
 // U: rows a thread fetches before it adds them.  The adds stay in row order (the same sums, bit for bit, as U = 1), but U rows'
 // loads are in flight at once: with one row per iteration the kernels moved 3.8-4.5 TB/s, bound by bytes in flight per CU
 // (16 waves x 64 lanes x 2 loads of 16 B against ~2 us of HBM latency), not by the HBM (round 5, profiles/r05_train_pmc.txt).
+// SQ (the batch statistics): the second quantity is q0 * q0 TAKEN IN DOUBLE -- a float x float product is exact there, so the sum
+// of squares carries no fp32 rounding of numbers of size mean^2 (squared in fp32, var = E[z^2] - mean^2 lost 2^-24 mean^2: 2e-3 of
+// a variance of 1 at a mean of 1000); F leaves q1 alone.
 constexpr int kRedSlots = 2048;     // ty_n * c <= 2048 for every launch shape (c <= kMaxC)
-template <int NQ, int V, int U, class F>
+template <int NQ, int V, int U, bool SQ = false, class F>
 __device__ inline void group_channel_sums(int c, long rows_per_group, double* part_g, F f) {
   __shared__ double red[2][kRedSlots];
   const int cvn = V == 4 ? c >> 2 : c;
@@ -80,7 +83,8 @@ __device__ inline void group_channel_sums(int c, long rows_per_group, double* pa
 #pragma unroll
       for (int e = 0; e < V; ++e) {
         s0[e] += lane(q0, e);
-        if (NQ > 1) s1[e] += lane(q1, e);
+        if constexpr (SQ) s1[e] = __builtin_fma((double)lane(q0, e), (double)lane(q0, e), s1[e]);
+        else if (NQ > 1) s1[e] += lane(q1, e);
       }
     };
     long r = r0 + ty;
@@ -516,11 +520,11 @@ template <int V, int U>
 __device__ inline void bn_stats_body(const float* __restrict__ z, long rows_per_group, int c, int ldz, double* __restrict__ sums) {
   const int g = blockIdx.y;
   const float* zg = z + (size_t)g * rows_per_group * ldz;
-  group_channel_sums<2, V, U>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
-                              [&](long r, int cc, vec<V>& q0, vec<V>& q1) {
-                                q0 = ldv<V>(zg + r * ldz + cc);
-                                q1 = q0 * q0;
-                              });
+  group_channel_sums<2, V, U, true>(c, rows_per_group, sums + (size_t)g * gridDim.x * 2 * c,
+                                    [&](long r, int cc, vec<V>& q0, vec<V>& q1) {
+                                      q0 = ldv<V>(zg + r * ldz + cc);
+                                      (void)q1;
+                                    });
 }
 template <int V, int U>
 __device__ inline void bn_bwd_reduce_body(const GradSrc& src, const float* __restrict__ z, const float* __restrict__ mean,
@@ -1205,12 +1209,21 @@ int bn_fast_shift(int n_groups, long rows_per_group, int c, bool honour_legacy =
 
 // The kernels a BatchNorm pass runs: the general ones (any c, stride, alignment), the float4 ones (c % 4 == 0, 16-byte aligned
 // strides and tensors) or, of those, the one-group fast ones (`shift`: bn_fast_shift).  A reduction runs float4 unless general.
-enum class BnKernels { general, vec4, fast };
+enum class BnKernels { general = 0, vec4 = 1, fast = 2 };
 struct BnForm { BnKernels k; int shift; };
 BnForm bn_form(int n_groups, long rows_per_group, int c, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
   if (!vec4_ok(c, lds, ptrs)) return {BnKernels::general, -1};
   const int sh = bn_fast_shift(n_groups, rows_per_group, c);
   return {sh >= 0 ? BnKernels::fast : BnKernels::vec4, sh};
+}
+
+// tools and tests only (dn_bn_train_last_form): the record every BatchNorm entry point writes once nothing can refuse the call
+// any more.  Host side; no kernel knows of it.
+struct BnLastForm { int cls, u, flags, fold, grid, groups, c, rows; };
+BnLastForm g_bn_last[DN_BN_PASSES] = {{-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0},
+                                      {-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}};
+void bn_note(int pass, BnKernels k, int u, int flags, int fold, int grid, int groups, int c, long rows) {
+  g_bn_last[pass] = BnLastForm{(int)k, u, flags, fold, grid, groups, c, (int)(rows > 0x7fffffffL ? 0x7fffffffL : rows)};
 }
 
 // Workgroups of a per-channel reduction over all groups.  1024 since round 5 (2048 before): measured in one lease
@@ -1236,7 +1249,9 @@ int bn_stats_reduce(const float* z, int n_groups, long rows_per_group, int c, in
              dn_reduce_workspace_bytes(n_groups, rows_per_group, c));
   *nblk = blocks_per_group(rows_per_group, n_groups);
   double* part = sums + (size_t)2 * c * n_groups;
-  if (bn_form(n_groups, rows_per_group, c, {ldz}, {z}).k != BnKernels::general)
+  const BnKernels k = bn_form(n_groups, rows_per_group, c, {ldz}, {z}).k;
+  bn_note(DN_BN_PASS_STATS_REDUCE, k, k == BnKernels::general || bn_legacy() ? 1 : 4, 0, DN_BN_FOLD_NONE, *nblk, n_groups, c, rows_per_group);
+  if (k != BnKernels::general)
     hipLaunchKernelGGL(bn_legacy() ? bn_stats_v4_kernel<1> : bn_stats_v4_kernel<4>, dim3(*nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
   else
     hipLaunchKernelGGL(bn_stats_kernel, dim3(*nblk, n_groups), dim3(256), 0, s, z, rows_per_group, c, ldz, part);
@@ -1299,6 +1314,7 @@ extern "C" int dn_bn_train_stats_partial(const float* z, int n_groups, long rows
   hipStream_t s = (hipStream_t)stream;
   int nblk;
   if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
+  bn_note(DN_BN_PASS_STATS_FINISH, BnKernels::general, 1, 0, DN_BN_FOLD_PARTIALS_FINALIZE, (n_groups * 2 * c + 3) / 4, n_groups, c, rows_per_group);
   hipLaunchKernelGGL(fold_partials_kernel, dim3((n_groups * 2 * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups,
                      nblk, 2 * c, n_groups, sums);
   return dn::check_launch("bn_stats_kernel");
@@ -1309,6 +1325,7 @@ extern "C" int dn_bn_train_stats_finish(const double* sums, int n_groups, long n
   DN_REQUIRE(sums && mean && var, "bn stats finish: null pointer");
   DN_REQUIRE(n_groups > 0 && norm_rows > 0 && c > 0 && c <= kMaxC, "bn stats finish: bad shape");
   const int n = n_groups * c;
+  bn_note(DN_BN_PASS_STATS_FINISH, BnKernels::general, 1, 0, DN_BN_FOLD_PARTIALS_FINALIZE, (n + 255) / 256, n_groups, c, norm_rows);
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, n, c,
                      norm_rows, mean, var);
   return dn::check_launch("bn_stats_finalize_kernel");
@@ -1323,6 +1340,8 @@ extern "C" int dn_bn_train_stats(const float* z, int n_groups, long rows_per_gro
   int nblk;
   if (int rc = bn_stats_reduce(z, n_groups, rows_per_group, c, ldz, sums, sums_bytes, &nblk, s)) return rc;
   // fold + finish (+ the running statistics) in one launch: the sums and statistics of the two-launch path, bit for bit
+  bn_note(DN_BN_PASS_STATS_FINISH, BnKernels::general, 1, running_mean ? DN_BN_REC_RUNNING : 0, DN_BN_FOLD_STATS_FINISH, (n_groups * c + 3) / 4,
+          n_groups, c, rows_per_group);
   hipLaunchKernelGGL(fold_stats_finish_kernel, dim3((n_groups * c + 3) / 4), dim3(256), 0, s, sums + (size_t)2 * c * n_groups, nblk, c,
                      n_groups, rows_per_group, sums, mean, var, running_mean, running_var, running_mean ? momentum : 0.f,
                      running_mean ? rows_per_group : 0L);
@@ -1340,6 +1359,8 @@ extern "C" int dn_bn_train_apply(const float* z, const float* mean, const float*
   if (!y_sp) {
     const BnForm f = bn_form(n_groups, rows_per_group, c, {ldz}, {z, y, mean, var, gamma, beta});
     DN_REQUIRE(!relu_mask || f.k != BnKernels::general, "bn apply (mask): needs c %% 4 == 0 and 16-byte aligned tensors");
+    bn_note(DN_BN_PASS_APPLY, f.k, 1, relu_mask ? DN_BN_REC_MASK : 0, DN_BN_FOLD_NONE,
+            grid_for(f.k == BnKernels::general ? total : total / 4, 8192), n_groups, c, rows_per_group);
     if (f.k == BnKernels::fast)
       hipLaunchKernelGGL(bn_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, z, mean, var,
                          gamma, beta, eps, relu, c, f.shift, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)nullptr, 1u,
@@ -1363,6 +1384,7 @@ extern "C" int dn_bn_train_apply(const float* z, const float* mean, const float*
   unsigned* flags = dn::sp_range_word();
   DN_REQUIRE(flags, "bn apply (mask + SP): the range word of the split-f16 engine is not addressable");
   const int fsh = bn_fast_shift(1, rows_per_group, c, false);      // (the SP form has no general-kernel twin for DN_BN_LEGACY to select)
+  bn_note(DN_BN_PASS_APPLY, BnKernels::fast, 1, DN_BN_REC_MASK | DN_BN_REC_SP, DN_BN_FOLD_NONE, grid_for(total / 4, 8192), n_groups, c, rows_per_group);
   hipLaunchKernelGGL(bn_apply_v4_fast_kernel<true>, dim3(grid_for(total / 4, 8192)), dim3(256), 0, s, z, mean, var,
                      gamma, beta, eps, 1, c, fsh, ldz, (unsigned)(total / 4), y, relu_mask, (unsigned char*)y_sp, (unsigned)hw, flags);
   return dn::check_launch("bn_apply_kernel (mask + SP)");
@@ -1373,6 +1395,7 @@ extern "C" int dn_bn_update_running(const float* mean, const float* var, int n_g
                                     float* running_mean, float* running_var, void* stream) {
   DN_REQUIRE(mean && var && running_mean && running_var, "bn running: null pointer");
   DN_REQUIRE(n_groups > 0 && rows_per_group > 0 && c > 0, "bn running: bad shape");
+  bn_note(DN_BN_PASS_RUNNING, BnKernels::general, 8, order ? DN_BN_REC_ORDER : 0, DN_BN_FOLD_NONE, (c + 63) / 64, n_groups, c, rows_per_group);
   hipLaunchKernelGGL(bn_update_running_kernel, dim3((c + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                      mean, var, n_groups, rows_per_group, c, order, momentum, running_mean, running_var);
   return dn::check_launch("bn_update_running_kernel");
@@ -1396,7 +1419,10 @@ extern "C" int dn_bn_train_backward_partial(const dn_bn_bwd_desc* d, double* sum
   const GradSrc src = bn_grad_src(d);
   const int nblk = blocks_per_group(rows_per_group, n_groups);
   double* part = sums + (size_t)2 * c * n_groups;      // workspace layout: see dn_bn_train_stats_partial
-  if (bn_form(n_groups, rows_per_group, c, {d->ld_a, d->dy_b ? d->ld_b : 0}, {d->dy_a, d->dy_b, d->y, d->z, d->mean, d->var}).k != BnKernels::general)
+  const BnKernels rk = bn_form(n_groups, rows_per_group, c, {d->ld_a, d->dy_b ? d->ld_b : 0}, {d->dy_a, d->dy_b, d->y, d->z, d->mean, d->var}).k;
+  bn_note(DN_BN_PASS_BWD_REDUCE, rk, rk == BnKernels::general || bn_legacy() ? 1 : 2, d->relu == 2 ? DN_BN_REC_MASK : 0,
+          n_groups == 1 && !bn_legacy() ? DN_BN_FOLD_PARAM_GRAD : DN_BN_FOLD_PARTIALS_PARAM_GRAD, nblk, n_groups, c, rows_per_group);
+  if (rk != BnKernels::general)
     hipLaunchKernelGGL(bn_legacy() ? bn_bwd_reduce_v4_kernel<1> : bn_bwd_reduce_v4_kernel<2>, dim3(nblk, n_groups), dim3(256), 0, s, src, d->z, d->mean, d->var, d->eps,
                        rows_per_group, part);
   else
@@ -1445,6 +1471,7 @@ extern "C" int dn_bn_train_backward_finish(const dn_bn_bwd_desc* d, const double
   const long total = (long)n_groups * rows_per_group * c;
   unsigned char* sp = (unsigned char*)out->dz_sp;
   const float lift = sp ? out->sp_lift : 1.f;
+  const int rec = (sp ? DN_BN_REC_SP : 0) | (bias ? DN_BN_REC_BIAS : 0) | (d->relu == 2 ? DN_BN_REC_MASK : 0) | (dz ? 0 : DN_BN_REC_DZ_NULL);
   if (bias) {
     // the fused bias gradient (round 6): the apply launch leaves one double per (workgroup, channel), folded in a fixed order
     const int blocks = grid_for(total / 4, kBiasBlocks);
@@ -1452,6 +1479,7 @@ extern "C" int dn_bn_train_backward_finish(const dn_bn_bwd_desc* d, const double
                "bn backward: bias workspace of %zu bytes, dn_bn_bias_workspace_bytes() asks for %zu", (size_t)out->bias_ws_bytes,
                dn_bn_bias_workspace_bytes(rows_per_group, c));
     double* part = out->bias_ws + c;      // [c] folded sums, then [blocks][c] partials
+    bn_note(DN_BN_PASS_BWD_APPLY, f.k, 1, rec, out->n_blocks ? DN_BN_FOLD_DEFERRED : DN_BN_FOLD_CHANNEL_SUM, blocks, n_groups, c, norm_rows);
     hipLaunchKernelGGL((sp ? bn_bwd_apply_v4_fast_kernel<true, true> : bn_bwd_apply_v4_fast_kernel<false, true>), dim3(blocks), dim3(256), 0,
                        s, src, d->z, d->mean, d->var, d->gamma, d->eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, (unsigned)(h * w), flags, part);
     if (out->n_blocks)      // the fold is the caller's (dn_channel_sum_fold_multi): the partials stay in bias_ws
@@ -1461,6 +1489,7 @@ extern "C" int dn_bn_train_backward_finish(const dn_bn_bwd_desc* d, const double
     return dn::check_launch("bn backward apply kernel (+ bias gradient)");
   }
   const unsigned hw = sp ? (unsigned)(h * w) : 1u;
+  bn_note(DN_BN_PASS_BWD_APPLY, f.k, 1, rec, DN_BN_FOLD_NONE, grid_for(f.k == BnKernels::general ? total : total / 4, 8192), n_groups, c, norm_rows);
   if (f.k == BnKernels::fast)
     hipLaunchKernelGGL(sp ? bn_bwd_apply_v4_fast_kernel<true> : bn_bwd_apply_v4_fast_kernel<false>, dim3(grid_for(total / 4, 8192)), dim3(256),
                        0, s, src, d->z, d->mean, d->var, d->gamma, d->eps, norm_rows, sums, f.shift, (unsigned)(total / 4), dz, sp, lift, hw, flags, (double*)nullptr);
@@ -1482,13 +1511,15 @@ extern "C" int dn_bn_train_backward(const dn_bn_bwd_desc* d, double* sums, size_
 
 extern "C" int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, void* stream) {
   DN_REQUIRE(jobs && n_jobs > 0, "channel sum fold multi: no jobs");
+  for (int j = 0; j < n_jobs; ++j)      // every job is looked at before the first launch: a refused call has folded nothing
+    DN_REQUIRE(jobs[j].partials && jobs[j].sums && jobs[j].out && jobs[j].n_blocks > 0 && jobs[j].c > 0 && jobs[j].c <= kMaxC,
+               "channel sum fold multi: job %d", j);
   for (int j0 = 0; j0 < n_jobs; j0 += kFoldJobs) {
     const int n = n_jobs - j0 < kFoldJobs ? n_jobs - j0 : kFoldJobs;
     FoldJobs J;
     int waves = 0;
     for (int j = 0; j < n; ++j) {
       const dn_fold_job& q = jobs[j0 + j];
-      DN_REQUIRE(q.partials && q.sums && q.out && q.n_blocks > 0 && q.c > 0 && q.c <= kMaxC, "channel sum fold multi: job %d", j0 + j);
       J.part[j] = q.partials; J.sums[j] = q.sums; J.out[j] = q.out;
       J.n_blocks[j] = q.n_blocks; J.c[j] = q.c; J.accumulate[j] = q.accumulate;
       J.first[j] = waves;
@@ -1496,6 +1527,7 @@ extern "C" int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, vo
     }
     for (int j = n; j <= kFoldJobs; ++j) J.first[j] = waves;
     for (int j = n; j < kFoldJobs; ++j) { J.part[j] = nullptr; J.sums[j] = nullptr; J.out[j] = nullptr; J.n_blocks[j] = J.c[j] = J.accumulate[j] = 0; }
+    bn_note(DN_BN_PASS_FOLD_MULTI, BnKernels::general, FOLD_BATCH, 0, DN_BN_FOLD_MULTI, n, j0 / kFoldJobs + 1, waves, 0);
     hipLaunchKernelGGL(fold_channel_sum_multi_kernel, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, J, n);
   }
   return dn::check_launch("fold_channel_sum_multi_kernel");
@@ -1511,6 +1543,8 @@ extern "C" int dn_channel_sum_partial(const float* x, long rows, int c, int ld, 
   hipStream_t s = (hipStream_t)stream;
   const int nblk = blocks_per_group(rows, 1);
   double* part = sums + c;                              // [c] folded sums (the fold's), then the workgroups' partials [blocks][c]
+  bn_note(DN_BN_PASS_CHANNEL_SUM, vec4_ok(c, {ld}, {x}) ? BnKernels::vec4 : BnKernels::general, vec4_ok(c, {ld}, {x}) && !bn_legacy() ? 4 : 1, 0,
+          DN_BN_FOLD_DEFERRED, nblk, 1, c, rows);
   if (vec4_ok(c, {ld}, {x}))
     hipLaunchKernelGGL(bn_legacy() ? channel_sum_v4_kernel<1> : channel_sum_v4_kernel<4>, dim3(nblk), dim3(256), 0, s, x, rows, c, ld, part);
   else
@@ -1524,9 +1558,19 @@ extern "C" int dn_channel_sum(const float* x, long rows, int c, int ld, double* 
   DN_REQUIRE(out, "channel sum: null pointer");
   int nblk;
   if (int rc = dn_channel_sum_partial(x, rows, c, ld, sums, sums_bytes, &nblk, stream)) return rc;
+  g_bn_last[DN_BN_PASS_CHANNEL_SUM].fold = DN_BN_FOLD_CHANNEL_SUM;
   hipLaunchKernelGGL(fold_channel_sum_kernel, dim3((c + 3) / 4), dim3(256), 0, (hipStream_t)stream, sums + c, nblk, c, sums, out,
                      accumulate);
   return dn::check_launch("fold_channel_sum_kernel");
+}
+
+extern "C" int dn_bn_train_last_form(int pass, int* out, int n) {
+  constexpr int kInts = (int)(sizeof(BnLastForm) / sizeof(int));
+  static_assert(sizeof(BnLastForm) == 8 * sizeof(int), "dn_bn_train_last_form: the record is 8 ints");
+  DN_REQUIRE(out && n > 0 && pass >= 0 && pass < DN_BN_PASSES, "bn last form: null pointer / no room / unknown pass %d", pass);
+  const int* f = reinterpret_cast<const int*>(&g_bn_last[pass]);
+  for (int i = 0; i < n && i < kInts; ++i) out[i] = f[i];
+  return kInts;
 }
 
 extern "C" int dn_add_rows(float* a, int ld_a, const float* b, int ld_b, long rows, int c,

@@ -169,6 +169,21 @@ def bn_form_supported(form, z, n_groups=1):
     return z.dim() == 4 and bool(_lib.load().dn_bn_train_form_supported(form, n_groups, z.numel() // c // n_groups, c))
 
 
+# dn_bn_train_last_form: the passes, the record's fields and what its words mean (include/disconet_train.h)
+BN_PASSES = ("stats_reduce", "stats_finish", "apply", "bwd_reduce", "bwd_apply", "channel_sum", "running", "fold_multi")
+BN_FORM_FIELDS = ("cls", "u", "flags", "fold", "grid", "groups", "c", "rows")
+BN_CLASSES = ("general", "vec4", "fast")
+BN_REC_SP, BN_REC_BIAS, BN_REC_MASK, BN_REC_DZ_NULL, BN_REC_RUNNING, BN_REC_ORDER = 1, 2, 4, 8, 16, 32
+BN_FOLDS = ("none", "fold_partials+finalize", "fold_stats_finish", "fold_param_grad", "fold_partials+bn_param_grad", "fold_channel_sum",
+            "deferred", "fold_channel_sum_multi")
+
+
+def bn_last_form(which):
+    """-> dict: which kernels the last call of BatchNorm pass `which` (a name of BN_PASSES) ran in this process
+    (dn_bn_train_last_form; tools and tests).  Host-side record, not thread-safe."""
+    return _ints(_lib.load().dn_bn_train_last_form, "dn_bn_train_last_form", BN_FORM_FIELDS, BN_PASSES.index(which))
+
+
 def bn_apply_sp_supported(z, n_groups=1):
     """can bn_apply(..., sp_out=...) also write y as an SP tensor?"""
     return bn_form_supported(BN_FORM_SP_APPLY, z, n_groups)

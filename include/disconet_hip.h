@@ -29,7 +29,7 @@
  *     thread-local message for the last failing call on this thread;
  *   - re-entrant.  Process-wide state is limited to launch-time caches filled on first use
  *     (kernel attributes / occupancy per instantiation), the tools-only hooks dn_spconv_force_config(),
- *     dn_spconv_set_upmode(), dn_spconv_last_form(), dn_spconv_last_resident(), dn_conv_force_config(), dn_conv_last_form(), dn_conv_wgrad_last_form() (disconet_train.h) and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
+ *     dn_spconv_set_upmode(), dn_spconv_last_form(), dn_spconv_last_resident(), dn_conv_force_config(), dn_conv_last_form(), dn_conv_wgrad_last_form(), dn_bn_train_last_form() (disconet_train.h) and dn_fuse_mlp_set_waves(), and the test switches DN_SP_B3, DN_BN_LEGACY and
  *     DN_WARP_GATHER_LEGACY (environment, read once: the other side of a bitwise / agreement test).
  */
 #ifndef DISCONET_HIP_H

@@ -238,6 +238,28 @@ int dn_channel_sum_fold_multi(const dn_fold_job* jobs, int n_jobs, void* stream)
 enum { DN_BN_FORM_SP_APPLY = 0, DN_BN_FORM_BIAS = 1, DN_BN_FORM_DZ_NULL = 2 };
 int dn_bn_train_form_supported(int form, int n_groups, long rows_per_group, int c);
 
+/* tools and tests only: which kernels did the last call of BatchNorm pass `pass` run in this process?  Host side: written by
+ * the entry points once nothing can refuse the call any more (a refused call leaves the record as it was), no kernel knows of it;
+ * not thread-safe.  Writes up to n of 8 ints and returns 8 (DN_ERR_ARG: null pointer, no room, unknown pass):
+ *   [0] kernel class: 0 general (any c, stride, alignment), 1 float4, 2 the one-group fast float4 kernels; -1: no call yet
+ *   [1] U: rows (reductions) a thread fetches before it adds them; the running update: groups per fetch (8); an apply: 1
+ *   [2] flags: DN_BN_REC_SP the SP copy is written | DN_BN_REC_BIAS the fused bias partials | DN_BN_REC_MASK the byte mask is
+ *       written (apply) or read (backward, relu = 2) | DN_BN_REC_DZ_NULL | DN_BN_REC_RUNNING the running update fused into the
+ *       finish | DN_BN_REC_ORDER dn_bn_update_running was given `order`
+ *   [3] what finished the sums: DN_BN_FOLD_* below (0: the pass has no fold)
+ *   [4] workgroups per group of a reduction, the grid of an apply or of a finish
+ *   [5] groups  [6] c  [7] the row count the pass normalised by or reduced over, saturated at INT32_MAX
+ * DN_BN_PASS_STATS_FINISH is written by dn_bn_train_stats_partial (fold_partials, statistics pending), dn_bn_train_stats_finish
+ * and dn_bn_train_stats; DN_BN_PASS_CHANNEL_SUM by dn_channel_sum_partial (deferred) and dn_channel_sum;
+ * dn_channel_sum_fold_multi writes DN_BN_PASS_FOLD_MULTI: [1] partials a lane fetches per batch, [4] jobs of its last launch,
+ * [5] launches, [6] wavefronts of the last launch. */
+enum { DN_BN_PASS_STATS_REDUCE = 0, DN_BN_PASS_STATS_FINISH = 1, DN_BN_PASS_APPLY = 2, DN_BN_PASS_BWD_REDUCE = 3,
+       DN_BN_PASS_BWD_APPLY = 4, DN_BN_PASS_CHANNEL_SUM = 5, DN_BN_PASS_RUNNING = 6, DN_BN_PASS_FOLD_MULTI = 7, DN_BN_PASSES = 8 };
+enum { DN_BN_REC_SP = 1, DN_BN_REC_BIAS = 2, DN_BN_REC_MASK = 4, DN_BN_REC_DZ_NULL = 8, DN_BN_REC_RUNNING = 16, DN_BN_REC_ORDER = 32 };
+enum { DN_BN_FOLD_NONE = 0, DN_BN_FOLD_PARTIALS_FINALIZE = 1, DN_BN_FOLD_STATS_FINISH = 2, DN_BN_FOLD_PARAM_GRAD = 3,
+       DN_BN_FOLD_PARTIALS_PARAM_GRAD = 4, DN_BN_FOLD_CHANNEL_SUM = 5, DN_BN_FOLD_DEFERRED = 6, DN_BN_FOLD_MULTI = 7 };
+int dn_bn_train_last_form(int pass, int* out, int n);
+
 /* Backward of the decoder's nearest x2 upsample as a pass of its own (only needed where no
  * BatchNorm backward follows directly: the fusion on layer 4): out [n, h, w, c] dense = 2 x 2
  * block sums of g [n, 2h, 2w, c'] read with row stride ld. */

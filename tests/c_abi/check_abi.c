@@ -58,6 +58,8 @@ static int errors_only(void) {
     CHECK(dn_conv_wgrad_plan(&d, 1, plan, 12) == 12 && plan[0] == 32 && plan[1] == 8, "wgrad plan, split-f16");
     CHECK(dn_conv_wgrad_last_form(NULL, 10) == DN_ERR_ARG, "wgrad last form: null accepted");
     CHECK(dn_conv_wgrad_last_form(form, 10) == 10, "wgrad last form: 10 fields");
+    CHECK(dn_bn_train_last_form(DN_BN_PASS_APPLY, NULL, 8) == DN_ERR_ARG && dn_bn_train_last_form(DN_BN_PASSES, form, 8) == DN_ERR_ARG, "bn last form: null / unknown pass accepted");
+    CHECK(dn_bn_train_last_form(DN_BN_PASS_APPLY, form, 8) == 8 && form[0] == -1, "bn last form: 8 fields, no call yet");
   }
   /* the split-f16 weight gradient: 32 -> 32 channels takes the 32-channel block form; a 13-channel source has none */
   CHECK(dn_conv_wgrad_sp_supported(&d) == 32 && dn_conv_wgrad_sp_workspace(&d) > 0, "wgrad_sp supported");
