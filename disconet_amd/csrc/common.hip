@@ -30,7 +30,7 @@ hipError_t zero_fill(void* ptr, size_t bytes, hipStream_t stream) {
 }
 }  // namespace dn
 
-extern "C" int dn_version(void) { return 157; }  // 0.1.3: round-5 kernels (profiles carry this number; 131: dn_conv_wgrad_sp; 132: round 6 -- Gray MFMA order, fp32 rows from the tap-merged kernel, fused bias gradients; 133: dn_spconv_pack_weights_multi, lane-parallel warp gathers; 134: dn_conv_wgrad_sp_z, dz = NULL in the BatchNorm backward; 135: dn_detect; 136: dn_ap_match, dn_ap_reset; 137: the BatchNorm training passes take dn_bn_bwd_desc / dn_bn_bwd_out and optional outputs -- 8 entry points for 14; 138: dn_assign_targets; 139: dn_voxelize_views; 140: the focal loss takes log q from the logit difference (log-softmax form) -- loss and class gradient of anchors with a wrong-side logit gap above 69 change; dn_adam_step takes its hyper-parameters as doubles; the x2 bilinear upsample kernels take the source coordinate as an exact rational; 141: dn_spconv_last_form (host side only: every kernel as in 140); 142: dn_conv_force_config, dn_conv_last_form (host side only: every kernel as in 140); 143: dn_mot_state_bytes, dn_mot_reset, dn_mot_step (a new kernel; every other kernel as in 140); 144: dn_idf_state_bytes, dn_idf_reset, dn_idf_step, dn_idf_finish (two new kernels; every other kernel as in 140); 145: dn_hota_state_bytes, dn_hota_work_bytes, dn_hota_reset, dn_hota_step, dn_hota_finish (three new kernels; every other kernel as in 140); 146: dn_seg_confusion (one new kernel; every other kernel as in 140); 147: dn_fuse_reduce, dn_fuse_reduce_lists, dn_fuse_reduce_lists_backward (fuse_reduce.hip: four new kernels; every other kernel as in 140); 148: dn_late_fuse_workspace_bytes, dn_late_fuse (detect.hip: one new kernel in front of dn_detect's pair-mask and wave-walk kernels; every other kernel as in 140); 149: dn_agent_fuse, dn_agent_fuse_workspace_bytes, dn_agent_combine_lists / _backward (agent_fuse.hip, a score epilogue of fuse_mlp.hip's kernel as new instantiations; every shipped instantiation as in 148); 150: dn_det_loss_corner (train_ops.hip: two new kernels; the six decode lines of decode_device.h in a helper that dn_decode_boxes, dn_detect and the new kernels inline; every shipped kernel as in 149); 151: dn_render_bev (render.hip: one new kernel; every other kernel as in 150); 152: dn_lidar_scan (lidar.hip: two new kernels; every other kernel as in 150); 153: dn_gt_strata, dn_ap_match_strata_workspace_bytes, dn_ap_match_strata, dn_ap_strata_reset (ap_match.hip: four new kernels; ap_tp_kernel takes its tp bits and its record offset from two device functions that the stratified kernel shares -- the same words; every other kernel as in 150); 154: dn_lidar_world_step (lidar_seq.hip: one new kernel), dn_lidar_scan_ids (lidar.hip: lidar_visible_kernel takes a nullable gt_ids, null from dn_lidar_scan -- the same bytes; every other kernel as in 153); 155: dn_exchange_message_bytes, dn_exchange_encode, dn_exchange_decode (exchange.hip: two new kernels; every other kernel as in 154); 156: dn_exchange_cells_message_bytes, dn_exchange_cells_workspace_bytes, dn_exchange_encode_cells, dn_exchange_decode_cells (exchange_cells.hip: four new kernels; exchange.hip's two take their octet bodies from exchange_device.h -- the same bytes; every other kernel as in 155); 157: dn_bn_train_last_form (host side only); the batch statistics square z in double (bn_stats_kernel, bn_stats_v4_kernel: var may differ from 156's, mean is the same bits; every other kernel as in 156))
+extern "C" int dn_version(void) { return 158; }  // 0.1.3: round-5 kernels (profiles carry this number; 131: dn_conv_wgrad_sp; 132: round 6 -- Gray MFMA order, fp32 rows from the tap-merged kernel, fused bias gradients; 133: dn_spconv_pack_weights_multi, lane-parallel warp gathers; 134: dn_conv_wgrad_sp_z, dz = NULL in the BatchNorm backward; 135: dn_detect; 136: dn_ap_match, dn_ap_reset; 137: the BatchNorm training passes take dn_bn_bwd_desc / dn_bn_bwd_out and optional outputs -- 8 entry points for 14; 138: dn_assign_targets; 139: dn_voxelize_views; 140: the focal loss takes log q from the logit difference (log-softmax form) -- loss and class gradient of anchors with a wrong-side logit gap above 69 change; dn_adam_step takes its hyper-parameters as doubles; the x2 bilinear upsample kernels take the source coordinate as an exact rational; 141: dn_spconv_last_form (host side only: every kernel as in 140); 142: dn_conv_force_config, dn_conv_last_form (host side only: every kernel as in 140); 143: dn_mot_state_bytes, dn_mot_reset, dn_mot_step (a new kernel; every other kernel as in 140); 144: dn_idf_state_bytes, dn_idf_reset, dn_idf_step, dn_idf_finish (two new kernels; every other kernel as in 140); 145: dn_hota_state_bytes, dn_hota_work_bytes, dn_hota_reset, dn_hota_step, dn_hota_finish (three new kernels; every other kernel as in 140); 146: dn_seg_confusion (one new kernel; every other kernel as in 140); 147: dn_fuse_reduce, dn_fuse_reduce_lists, dn_fuse_reduce_lists_backward (fuse_reduce.hip: four new kernels; every other kernel as in 140); 148: dn_late_fuse_workspace_bytes, dn_late_fuse (detect.hip: one new kernel in front of dn_detect's pair-mask and wave-walk kernels; every other kernel as in 140); 149: dn_agent_fuse, dn_agent_fuse_workspace_bytes, dn_agent_combine_lists / _backward (agent_fuse.hip, a score epilogue of fuse_mlp.hip's kernel as new instantiations; every shipped instantiation as in 148); 150: dn_det_loss_corner (train_ops.hip: two new kernels; the six decode lines of decode_device.h in a helper that dn_decode_boxes, dn_detect and the new kernels inline; every shipped kernel as in 149); 151: dn_render_bev (render.hip: one new kernel; every other kernel as in 150); 152: dn_lidar_scan (lidar.hip: two new kernels; every other kernel as in 150); 153: dn_gt_strata, dn_ap_match_strata_workspace_bytes, dn_ap_match_strata, dn_ap_strata_reset (ap_match.hip: four new kernels; ap_tp_kernel takes its tp bits and its record offset from two device functions that the stratified kernel shares -- the same words; every other kernel as in 150); 154: dn_lidar_world_step (lidar_seq.hip: one new kernel), dn_lidar_scan_ids (lidar.hip: lidar_visible_kernel takes a nullable gt_ids, null from dn_lidar_scan -- the same bytes; every other kernel as in 153); 155: dn_exchange_message_bytes, dn_exchange_encode, dn_exchange_decode (exchange.hip: two new kernels; every other kernel as in 154); 156: dn_exchange_cells_message_bytes, dn_exchange_cells_workspace_bytes, dn_exchange_encode_cells, dn_exchange_decode_cells (exchange_cells.hip: four new kernels; exchange.hip's two take their octet bodies from exchange_device.h -- the same bytes; every other kernel as in 155); 157: dn_bn_train_last_form (host side only); the batch statistics square z in double (bn_stats_kernel, bn_stats_v4_kernel: var may differ from 156's, mean is the same bits; every other kernel as in 156); 158: the four dn_scatter_dense forms skip rows outside [offsets[0], offsets[n_images]) (157 wrote them into the first / the last image; the same bytes for a list that its offsets cover); the voxel entry points name the argument they refuse (every other kernel as in 157))
 
 // The hash of every source / header / flag this library was built from (csrc/build.py :: tree_hash), behind a marker
 // that build.py also finds in the file without loading it.  _lib.load() refuses a library whose id is not the tree's.

@@ -167,16 +167,25 @@ __global__ void compact_write_kernel(const float* __restrict__ dense, long ncell
   }
 }
 
+// The image that owns row i of a batched index list: the g with offsets[g] <= i < offsets[g + 1], found as the last g
+// with offsets[g] <= i (empty images share their offset with the next one and own nothing).  -1: the row lies before
+// offsets[0] or at / past offsets[n_images] and belongs to no image.
+__device__ inline int owner_of_row(const int32_t* __restrict__ offsets, int n_images, int i) {
+  if (i < offsets[0] || i >= offsets[n_images]) return -1;
+  int lo = 0, hi = n_images;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 __global__ void scatter_dense_kernel(const int32_t* __restrict__ indices,
                                      const int32_t* __restrict__ offsets, int n_images, int total,
                                      int dx, int dy, int dz, float* __restrict__ dense) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    // image that owns row i: last g with offsets[g] <= i
-    int lo = 0, hi = n_images;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = owner_of_row(offsets, n_images, i);
+    if (lo < 0) continue;
     const int ix = indices[3 * (size_t)i], iy = indices[3 * (size_t)i + 1],
               iz = indices[3 * (size_t)i + 2];
     if ((unsigned)ix < (unsigned)dx && (unsigned)iy < (unsigned)dy && (unsigned)iz < (unsigned)dz)
@@ -192,11 +201,8 @@ __global__ void scatter_dense_sp_kernel(const int32_t* __restrict__ indices,
   const size_t hw = (size_t)dx * dy;
   const int chunks = sp::chunks_of(dz);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    int lo = 0, hi = n_images;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = owner_of_row(offsets, n_images, i);
+    if (lo < 0) continue;
     const int ix = indices[3 * (size_t)i], iy = indices[3 * (size_t)i + 1],
               iz = indices[3 * (size_t)i + 2];
     if ((unsigned)ix < (unsigned)dx && (unsigned)iy < (unsigned)dy && (unsigned)iz < (unsigned)dz) {
@@ -213,11 +219,8 @@ __global__ void scatter_dense_bits_kernel(const int32_t* __restrict__ indices,
                                           const int32_t* __restrict__ offsets, int n_images, int total,
                                           int dx, int dy, int dz, unsigned* __restrict__ bits) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    int lo = 0, hi = n_images;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = owner_of_row(offsets, n_images, i);
+    if (lo < 0) continue;
     const int ix = indices[3 * (size_t)i], iy = indices[3 * (size_t)i + 1],
               iz = indices[3 * (size_t)i + 2];
     if ((unsigned)ix < (unsigned)dx && (unsigned)iy < (unsigned)dy && (unsigned)iz < (unsigned)dz)
@@ -230,15 +233,13 @@ inline int ntiles_of(const int* dims) {
   return (int)((ncell + COMPACT_TILE - 1) / COMPACT_TILE);
 }
 
-}  // namespace
-
-extern "C" int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
-                                  const double* vs, const double* ext, const int* dims,
-                                  float* dense, void* stream) {
-  DN_REQUIRE(vs && ext && dims && dense, "voxelize: null pointer");
-  DN_REQUIRE(n_pts >= 0 && (n_pts == 0 || pts), "voxelize: bad point buffer");
-  DN_REQUIRE(pt_stride >= 3, "voxelize: points need >= 3 columns (got %d)", pt_stride);
-  DN_REQUIRE(vs[0] > 0 && vs[1] > 0 && vs[2] > 0, "voxelize: voxel size must be positive");
+// The host arguments both voxelizers share, refused by name, and the kernel's geometry from them.
+int voxel_geom(const char* who, int pt_stride, const double* vs, const double* ext, const int* dims, VoxelGeom* out) {
+  DN_REQUIRE(vs, "%s: null voxel_size", who);
+  DN_REQUIRE(ext, "%s: null extents", who);
+  DN_REQUIRE(dims, "%s: null dims", who);
+  DN_REQUIRE(pt_stride >= 3, "%s: pt_stride: points need >= 3 columns (got %d)", who, pt_stride);
+  DN_REQUIRE(vs[0] > 0 && vs[1] > 0 && vs[2] > 0, "%s: voxel_size (%g, %g, %g) must be positive", who, vs[0], vs[1], vs[2]);
   VoxelGeom g;
   g.vx = vs[0]; g.vy = vs[1]; g.vz = vs[2];
   g.xlo = ext[0]; g.xhi = ext[1]; g.ylo = ext[2]; g.yhi = ext[3]; g.zlo = ext[4]; g.zhi = ext[5];
@@ -248,9 +249,35 @@ extern "C" int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
   const int ex = (int)ceil(ext[1] / vs[0]) - g.minx, ey = (int)ceil(ext[3] / vs[1]) - g.miny,
             ez = (int)ceil(ext[5] / vs[2]) - g.minz;
   DN_REQUIRE(dims[0] == ex && dims[1] == ey && dims[2] == ez,
-             "voxelize: dims (%d,%d,%d) do not match extents/voxel_size (%d,%d,%d)", dims[0],
-             dims[1], dims[2], ex, ey, ez);
+             "%s: dims (%d,%d,%d) do not match extents/voxel_size (%d,%d,%d)", who, dims[0], dims[1], dims[2], ex, ey, ez);
+  DN_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "%s: empty grid: dims (%d,%d,%d)", who, dims[0], dims[1], dims[2]);
   g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
+  *out = g;
+  return DN_OK;
+}
+
+// The arguments the four rebuild forms share, refused by name.
+int scatter_args(const char* who, const int32_t* indices, const int32_t* offsets, int n_images, int total, const int* dims,
+                 const void* out) {
+  DN_REQUIRE(dims, "%s: null dims", who);
+  DN_REQUIRE(offsets, "%s: null offsets", who);
+  DN_REQUIRE(out, "%s: null output", who);
+  DN_REQUIRE(n_images > 0, "%s: n_images %d (at least one image is needed)", who, n_images);
+  DN_REQUIRE(total >= 0, "%s: n_indices_total %d", who, total);
+  DN_REQUIRE(total == 0 || indices, "%s: null indices with n_indices_total %d", who, total);
+  DN_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "%s: empty grid: dims (%d,%d,%d)", who, dims[0], dims[1], dims[2]);
+  return DN_OK;
+}
+
+}  // namespace
+
+extern "C" int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
+                                  const double* vs, const double* ext, const int* dims,
+                                  float* dense, void* stream) {
+  DN_REQUIRE(dense, "voxelize: null dense");
+  DN_REQUIRE(n_pts >= 0 && (n_pts == 0 || pts), "voxelize: bad point buffer (pts, n_pts %d)", n_pts);
+  VoxelGeom g;
+  if (const int rc = voxel_geom("voxelize", pt_stride, vs, ext, dims, &g)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t bytes = (size_t)g.dx * g.dy * g.dz * sizeof(float);
   hipError_t e = dn::zero_fill(dense, bytes, s);
@@ -266,7 +293,6 @@ extern "C" int dn_voxelize_views(const float* pts, long n_pts, int pt_stride, co
                                  const float* poses, int n_pose, int n_src, int max_count, int n_views,
                                  const double* vs, const double* ext, const int* dims, float* dense, uint32_t* bits,
                                  void* stream) {
-  DN_REQUIRE(vs && ext && dims, "voxelize_views: null pointer (voxel size, extents or dims)");
   DN_REQUIRE(dense || bits, "voxelize_views: null outputs: one of dense / bits is needed");
   DN_REQUIRE(n_views >= 1, "voxelize_views: %d views (at least one is needed)", n_views);
   DN_REQUIRE(n_src >= 0, "voxelize_views: %d sources", n_src);
@@ -275,21 +301,9 @@ extern "C" int dn_voxelize_views(const float* pts, long n_pts, int pt_stride, co
   DN_REQUIRE(n_pts >= 0 && (n_pts == 0 || pts), "voxelize_views: bad point buffer (%ld rows)", n_pts);
   DN_REQUIRE(n_pose >= 0 && (n_pose == 0 || poses), "voxelize_views: bad pose buffer (%d poses)", n_pose);
   DN_REQUIRE(max_count >= 0, "voxelize_views: max_count %d", max_count);
-  DN_REQUIRE(pt_stride >= 3, "voxelize_views: points need >= 3 columns (got %d)", pt_stride);
-  DN_REQUIRE(vs[0] > 0 && vs[1] > 0 && vs[2] > 0, "voxelize_views: voxel size must be positive");
   VoxelGeom g;
-  g.vx = vs[0]; g.vy = vs[1]; g.vz = vs[2];
-  g.xlo = ext[0]; g.xhi = ext[1]; g.ylo = ext[2]; g.yhi = ext[3]; g.zlo = ext[4]; g.zhi = ext[5];
-  g.minx = (int)floor(ext[0] / vs[0]); g.miny = (int)floor(ext[2] / vs[1]);
-  g.minz = (int)floor(ext[4] / vs[2]);
-  const int ex = (int)ceil(ext[1] / vs[0]) - g.minx, ey = (int)ceil(ext[3] / vs[1]) - g.miny,
-            ez = (int)ceil(ext[5] / vs[2]) - g.minz;
-  DN_REQUIRE(dims[0] == ex && dims[1] == ey && dims[2] == ez,
-             "voxelize_views: dims (%d,%d,%d) do not match extents/voxel_size (%d,%d,%d)", dims[0],
-             dims[1], dims[2], ex, ey, ez);
-  DN_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "voxelize_views: empty grid (%d,%d,%d)", dims[0], dims[1], dims[2]);
-  DN_REQUIRE(!bits || dims[2] <= 32, "voxelize_views: %d height bins do not fit one word per pixel", dims[2]);
-  g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
+  if (const int rc = voxel_geom("voxelize_views", pt_stride, vs, ext, dims, &g)) return rc;
+  DN_REQUIRE(!bits || dims[2] <= 32, "voxelize_views: dims[2] = %d height bins do not fit one word per pixel", dims[2]);
   hipStream_t s = (hipStream_t)stream;
   const size_t pixels = (size_t)n_views * g.dx * g.dy;
   hipError_t e = hipSuccess;
@@ -314,10 +328,12 @@ extern "C" size_t dn_voxel_compact_workspace(const int* dims) {
 
 extern "C" int dn_voxel_compact(const float* dense, const int* dims, int32_t* indices,
                                 int capacity, int32_t* count, void* workspace, void* stream) {
-  DN_REQUIRE(dense && dims && count && workspace, "voxel_compact: null pointer");
-  DN_REQUIRE(capacity >= 0 && (capacity == 0 || indices), "voxel_compact: bad index buffer");
+  DN_REQUIRE(dims, "voxel_compact: null dims");
+  DN_REQUIRE(dense && count && workspace, "voxel_compact: null pointer (dense, count or workspace)");
+  DN_REQUIRE(capacity >= 0, "voxel_compact: capacity %d", capacity);
+  DN_REQUIRE(capacity == 0 || indices, "voxel_compact: null indices with capacity %d", capacity);
+  DN_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "voxel_compact: empty grid: dims (%d,%d,%d)", dims[0], dims[1], dims[2]);
   const long ncell = (long)dims[0] * dims[1] * dims[2];
-  DN_REQUIRE(ncell > 0, "voxel_compact: empty grid");
   const int ntiles = ntiles_of(dims);
   hipStream_t s = (hipStream_t)stream;
   int* tiles = static_cast<int*>(workspace);
@@ -330,8 +346,7 @@ extern "C" int dn_voxel_compact(const float* dense, const int* dims, int32_t* in
 
 extern "C" int dn_scatter_dense(const int32_t* indices, const int32_t* offsets, int n_images,
                                 int total, const int* dims, float* dense, void* stream) {
-  DN_REQUIRE(dims && dense && offsets, "scatter_dense: null pointer");
-  DN_REQUIRE(n_images > 0 && total >= 0 && (total == 0 || indices), "scatter_dense: bad sizes");
+  if (const int rc = scatter_args("scatter_dense", indices, offsets, n_images, total, dims, dense)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t bytes = (size_t)n_images * dims[0] * dims[1] * dims[2] * sizeof(float);
   hipError_t e = dn::zero_fill(dense, bytes, s);
@@ -346,8 +361,7 @@ extern "C" int dn_scatter_dense(const int32_t* indices, const int32_t* offsets, 
 namespace {
 int scatter_dense_sp_impl(const int32_t* indices, const int32_t* offsets, int n_images, int total, const int* dims,
                           void* dense_sp, int quarters, hipStream_t s) {
-  DN_REQUIRE(dims && dense_sp && offsets, "scatter_dense_sp: null pointer");
-  DN_REQUIRE(n_images > 0 && total >= 0 && (total == 0 || indices), "scatter_dense_sp: bad sizes");
+  if (const int rc = scatter_args("scatter_dense_sp", indices, offsets, n_images, total, dims, dense_sp)) return rc;
   const size_t bytes = sp::act_bytes(n_images, dims[2], (size_t)dims[0] * dims[1], quarters);
   hipError_t e = dn::zero_fill(dense_sp, bytes, s);
   if (e != hipSuccess) return dn::fail(DN_ERR_LAUNCH, "scatter_dense_sp: memset: %s", hipGetErrorString(e));
@@ -371,9 +385,8 @@ extern "C" int dn_scatter_dense_sp_hi(const int32_t* indices, const int32_t* off
 
 extern "C" int dn_scatter_dense_bits(const int32_t* indices, const int32_t* offsets, int n_images,
                                      int total, const int* dims, uint32_t* bits, void* stream) {
-  DN_REQUIRE(dims && bits && offsets, "scatter_dense_bits: null pointer");
-  DN_REQUIRE(n_images > 0 && total >= 0 && (total == 0 || indices), "scatter_dense_bits: bad sizes");
-  DN_REQUIRE(dims[2] >= 1 && dims[2] <= 32, "scatter_dense_bits: %d height bins do not fit one word per pixel", dims[2]);
+  if (const int rc = scatter_args("scatter_dense_bits", indices, offsets, n_images, total, dims, bits)) return rc;
+  DN_REQUIRE(dims[2] <= 32, "scatter_dense_bits: dims[2] = %d height bins do not fit one word per pixel", dims[2]);
   hipStream_t s = (hipStream_t)stream;
   const size_t bytes = (size_t)n_images * dims[0] * dims[1] * sizeof(uint32_t);
   hipError_t e = dn::zero_fill(bits, bytes, s);

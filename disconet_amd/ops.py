@@ -149,7 +149,8 @@ def voxel_compact(dense, capacity=None):
 
 def scatter_dense(indices, offsets, n_images, dims):
     """Batched dense rebuild: indices [Mtot, 3] int32, offsets [n_images + 1] int32
-    -> dense [n_images, 1, X, Y, Z] float32 (the bevs layout of the reference)."""
+    -> dense [n_images, 1, X, Y, Z] float32 (the bevs layout of the reference).  Image g owns rows offsets[g] ..
+    offsets[g + 1] - 1; rows outside [offsets[0], offsets[n_images]) belong to no image and write nothing (all forms)."""
     _need_gpu(indices, offsets)
     if indices.dtype != torch.int32 or offsets.dtype != torch.int32:
         raise _lib.DnError("scatter_dense needs int32 indices/offsets")

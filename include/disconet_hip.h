@@ -94,6 +94,8 @@ int dn_sp_range_flags_async(unsigned* dst_device, int reset, void* stream);
  *   voxel_size_host[3], extents_host[6] = {xlo,xhi,ylo,yhi,zlo,zhi}  (host doubles)
  *   dims_host[3]   = grid dims (X, Y, Z); dense is [X][Y][Z] float32, set to
  *                    0/1 by this call (it zero-fills first).
+ * A point with a NaN, infinite or out-of-extent x, y or z fails the strict test and is dropped, as in numpy (the four
+ * quiet NaNs dn_lidar_scan writes for a missed ray among them); columns past 2 are never read.
  * ------------------------------------------------------------------------ */
 int dn_voxelize_occupy(const float* pts, int n_pts, int pt_stride,
                        const double* voxel_size_host, const double* extents_host,
@@ -141,31 +143,43 @@ int dn_voxelize_views(const float* pts, long n_pts, int pt_stride, const int32_t
 
 /* Sorted-unique voxel index list of a dense grid, in the reference's
  * lexsort(x, then y, then z) order (= linear order of the [X][Y][Z] grid).
+ * A cell is OCCUPIED when dense != 0: any non-zero value, negative ones, float32 subnormals and NaN included; 0.0 and
+ * -0.0 are empty (numpy's argwhere(dense != 0)).
  *   indices   [capacity][3] int32 out;  count: int32 out (device)
- *   workspace: dn_voxel_compact_workspace(dims) bytes. */
+ *   workspace: dn_voxel_compact_workspace(dims) bytes.
+ * count is ALWAYS the number of occupied cells of the grid, whatever the capacity.  When capacity < count the first
+ * `capacity` rows of the list are written and nothing from row `capacity` on: the caller compares count with its
+ * capacity to learn that the list was cut.  capacity == 0 (indices may then be null) only counts. */
 size_t dn_voxel_compact_workspace(const int* dims_host);
 int dn_voxel_compact(const float* dense, const int* dims_host, int32_t* indices,
                      int capacity, int32_t* count, void* workspace, void* stream);
 
 /* Replaces upstream:coperception/datasets/V2XSimDet.py :: __getitem__ (dense
  * rebuild) for a whole batch: image g owns rows
- * offsets[g]..offsets[g+1] of indices[.][3]; dense[g][X][Y][Z] = 1 there, else 0. */
+ * offsets[g]..offsets[g+1] of indices[.][3]; dense[g][X][Y][Z] = 1 there, else 0.
+ *   offsets   [n_images + 1] int32 (device), ascending; an image with offsets[g] == offsets[g+1] is all zero
+ * Rows outside [offsets[0], offsets[n_images]) belong to no image and write nothing.  A row whose cell lies outside the
+ * grid (a negative coordinate, ix >= X, iy >= Y or iz >= Z) writes nothing either; duplicated rows and the order of the
+ * rows cannot change a byte.  The call zero-fills its output first; n_indices_total == 0 leaves it zero. */
 int dn_scatter_dense(const int32_t* indices, const int32_t* offsets, int n_images,
                      int n_indices_total, const int* dims_host, float* dense, void* stream);
 /* The same rebuild written in the conv engine's split-planar layout (see "SP tensor" below):
- * dense_sp is the SP tensor [n_images][ceil(Z/16)][4][X][Y] x 16 bytes of the bevs batch. */
+ * dense_sp is the SP tensor [n_images][ceil(Z/16)][4][X][Y] x 16 bytes of the bevs batch.  Rows outside
+ * [offsets[0], offsets[n_images]) belong to no image and write nothing. */
 int dn_scatter_dense_sp(const int32_t* indices, const int32_t* offsets, int n_images,
                         int n_indices_total, const int* dims_host, void* dense_sp, void* stream);
 /* ... and as a HI-ONLY SP tensor [n_images][ceil(Z/16)][2 octets][X][Y] x 16 bytes (half the bytes): an
  * occupancy grid is exact in binary16, its lo planes would be all zero.  dn_spconv2d reads it as
  * source 0 of a 3x3 stride-1 layer when dn_conv_desc.math == 3 (half the operand traffic, two MFMAs per
- * product instead of three; the results are bit-identical to the full form). */
+ * product instead of three; the results are bit-identical to the full form).  The same rows as dn_scatter_dense_sp
+ * (one kernel writes both forms). */
 int dn_scatter_dense_sp_hi(const int32_t* indices, const int32_t* offsets, int n_images,
                            int n_indices_total, const int* dims_host, void* dense_sp_hi, void* stream);
 /* ... and as an occupancy BIT grid bits[n_images][X][Y] (uint32; bit z = height bin z holds a point; Z <= 32):
  * 1/32 of the float32 grid ("520 KB/scene as bits").  dn_spconv2d reads it as source 0 of a 3x3
  * stride-1 layer with c_out <= 32 when dn_conv_desc.math == 4: the words are expanded to the hi-only form's halves on
- * their way into LDS, the arithmetic and every result are those of math == 3 on the expanded grid. */
+ * their way into LDS, the arithmetic and every result are those of math == 3 on the expanded grid.  Rows outside
+ * [offsets[0], offsets[n_images]) belong to no image and write nothing. */
 int dn_scatter_dense_bits(const int32_t* indices, const int32_t* offsets, int n_images,
                           int n_indices_total, const int* dims_host, uint32_t* bits, void* stream);
 
